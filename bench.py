@@ -11,10 +11,13 @@ assembly) followed by the all-gather of the [B,61] parameters over RCCL.  ``--sc
 string describes): the batch is the GLOBAL batch, rank r generates rows shard_range(B, r, R) -- B/R grasps, 2.0 MB per
 rank into the all-gather at B=65536, R=8; ``--scaling weak``: ``--batch`` grasps per rank.  Inputs and weights are
 resident in HBM before the timed region; the noise is generated inside the step, keyed by the global row.
-The headline is timed with the library's per-launch profiling OFF; the kernel breakdown comes from a second, identical
-pass with every launch bracketed by HIP events on the launch stream.
+The headline is timed with the library's per-launch profiling OFF; with ``--full``, the kernel breakdown comes from a second,
+identical pass with every launch bracketed by HIP events on the launch stream.
 
-Extra objects in the JSON line:
+A plain run sets up, warms up, times the steps, writes the outputs if asked (``--dump-outputs DIR``: the last timed step's
+[B, 61] parameters as DIR/params61.npy) and prints the line; everything else it measures runs only with ``--full``.
+
+Extra objects in the JSON line (``--full``):
   roofline            the matrix-core kernel with the largest share of the step (GEMMs AND the PointNet trunk are candidates),
                       algorithmic FLOPs / HIP-event time against the roof of its arithmetic; ``traffic`` from the committed PMC passes
                       next to ``algorithmic_bytes``; the dominant GEMM and the PointNet group beside it
@@ -96,6 +99,12 @@ def parse():
                          "one-GPU box: init, all_gather_into_tensor, barrier, all_reduce)")
     ap.add_argument("--no-latency", action="store_true", help="skip the small-batch latency leg (B = 1, 8, 100)")
     ap.add_argument("--sources-digest", action="store_true", help="print the digest of the kernel sources (what a PMC file must carry to be quoted) and exit")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the per-launch kernel breakdown and roofline (second pass), the VQ argmin microbench, the "
+                         "small-batch latency leg and the CPU baseline with its parity check (each still subject to its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (the gathered [B, 61] MANO parameters, float32) as "
+                         "DIR/params61.npy; above 64 MB a fixed, seeded sample of rows, their indices in DIR/params61_rows.npy")
     return ap.parse_args()
 
 
@@ -208,6 +217,27 @@ def pmc_traffic(kind, batch):
     except Exception:
         pass
     return None, None
+
+
+DUMP_LIMIT_BYTES = 64 * 1024 * 1024
+
+
+def dump_outputs(out_dir, params):
+    """--dump-outputs: the [B, 61] float32 parameters the last timed step gathered, as out_dir/params61.npy.  A batch above 64 MB
+    writes a fixed, seeded sample of rows (sorted) instead, with their row indices (float64) in out_dir/params61_rows.npy."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    params = np.ascontiguousarray(params, dtype=np.float32)
+    rows_path = os.path.join(out_dir, "params61_rows.npy")
+    if os.path.exists(rows_path):
+        os.remove(rows_path)                   # an earlier, sampled dump's
+    if params.nbytes > DUMP_LIMIT_BYTES:
+        n = DUMP_LIMIT_BYTES // (params.shape[1] * 4 + 8)
+        rows = np.sort(np.random.default_rng(0).choice(params.shape[0], size=n, replace=False))
+        params = params[rows]
+        np.save(rows_path, rows.astype(np.float64))
+    np.save(os.path.join(out_dir, "params61.npy"), params)
+    log(f"outputs: {params.shape[0]} x {params.shape[1]} float32 parameters -> {os.path.join(out_dir, 'params61.npy')}")
 
 
 def prof_read(lib, _lib):
@@ -728,10 +758,14 @@ def main():
     assert gathered.shape == (B_global, 61) and bool(torch.isfinite(gathered).all())
     import hashlib
     # the last timed step's gathered parameters: identical for every world size (strong scaling + noise keyed by the global row)
-    gathered_sha = hashlib.sha256(gathered.cpu().numpy().tobytes()).hexdigest()
+    gathered_np = gathered.cpu().numpy()
+    gathered_sha = hashlib.sha256(gathered_np.tobytes()).hexdigest()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, gathered_np)
+    del gathered_np
     # second pass, NOT part of the headline: every launch bracketed by two HIP events on its stream -> kernel breakdown
     kernels, prof_elapsed = {}, None
-    if not args.no_prof and args.prof_steps > 0:
+    if args.full and not args.no_prof and args.prof_steps > 0:
         # The timed steps run the PointNet's exact stage and STN FCs on a second stream beside the next launch's trunk kernel; two
         # kernels sharing the chip each take longer than alone, so a per-launch duration measured that way is not the kernel's own.
         # The breakdown pass therefore runs ONE stream (DVQ_PN_STREAMS=0: same kernels, same launches, same results): its durations
@@ -783,10 +817,11 @@ def main():
                                   "tflops": (v["flops"] / (v["ms"] * 1e-3) / 1e12) if v["ms"] > 0 else 0.0}
                               for k, v in sorted(kernels.items(), key=lambda kv: -kv[1]["ms"])}
 
-        out["roofline_vq_argmin"] = vq_microbench(args, lib, _lib, ops, dev, K)
-        if not args.no_latency and world == 1:
+        if args.full:
+            out["roofline_vq_argmin"] = vq_microbench(args, lib, _lib, ops, dev, K)
+        if args.full and not args.no_latency and world == 1:
             out["latency_ms"] = latency_leg(net, synth, dev, K)
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"], out["parity"] = cpu_baseline(sd, arrays, args.cpu_grasps, N, K, net, dev)
             out["gpu_over_cpu"] = value / out["cpu_baseline"]["value"]
             b1 = out["cpu_baseline"]["reference_faithful_b1_loop"].get(f"N={N}", {}).get("grasps_per_s")

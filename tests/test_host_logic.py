@@ -4,7 +4,6 @@ import json
 import os
 
 import numpy as np
-import pytest
 import torch
 
 from dvqvae_amd import dist, diversity, generate, packing, synth
@@ -100,10 +99,14 @@ def test_synthetic_data_is_deterministic():
     assert float(q.min()) > 0
 
 
-def test_mano_readers_agree():
-    path = "/root/reference/models/mano/MANO_RIGHT.pkl"
-    if not os.path.exists(path):
-        pytest.skip("MANO_RIGHT.pkl only exists in the build container")
+def test_mano_readers_agree(tmp_path):
+    """Both MANO readers on tests/golden/g9_mano_right.pkl.xz: MANO_RIGHT.pkl as shipped (Python-2 pickle of chumpy objects), with
+    posedirs rounded to fp16 values and the unread hands_coeffs zeroed to fit the size limit (tools/make_golden.py mano)."""
+    import lzma
+    path = str(tmp_path / "MANO_RIGHT.pkl")
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "g9_mano_right.pkl.xz"), "rb") as f, \
+            open(path, "wb") as out:
+        out.write(lzma.decompress(f.read()))
     a, b = dmano.read_mano_pkl(path), mano_oracle.load_mano_pkl(path)
     for k in ("v_template", "shapedirs", "posedirs", "J_regressor", "weights", "hands_components", "hands_mean", "parents"):
         assert np.array_equal(np.asarray(a[k]), np.asarray(b[k])), k

@@ -7,7 +7,7 @@ mkdir -p $OUT
 for rep in 1 2; do
   for v in new old; do
     if [ $v = old ]; then export DVQ_DIAG_LIB=1; else unset DVQ_DIAG_LIB; fi
-    timeout 600 python3 bench.py --gpus 1 --steps 6 --warmup 2 --no-cpu-baseline --no-latency > $OUT/$v$rep.json 2> $OUT/$v$rep.err
+    timeout 600 python3 bench.py --gpus 1 --steps 6 --warmup 2 --full --no-cpu-baseline --no-latency > $OUT/$v$rep.json 2> $OUT/$v$rep.err
     python3 - $OUT/$v$rep.json $v$rep <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

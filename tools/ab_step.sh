@@ -7,7 +7,8 @@ mkdir -p $OUT
 for rep in 1 2; do
   for v in new base; do
     if [ $v = base ]; then b=tools/ab/base/bench.py; else b=bench.py; fi
-    timeout 600 python3 $b --gpus 1 --steps 6 --warmup 2 --no-cpu-baseline --no-latency > $OUT/$v$rep.json 2> $OUT/$v$rep.err
+    full=$(grep -q -- '"--full"' $b && echo --full)        # a base tree older than --full prints the kernels without it
+    timeout 600 python3 $b --gpus 1 --steps 6 --warmup 2 $full --no-cpu-baseline --no-latency > $OUT/$v$rep.json 2> $OUT/$v$rep.err
     python3 - $OUT/$v$rep.json $v$rep <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

@@ -4,7 +4,7 @@ set -u
 OUT=gpurun_out/${1:-chunk_sweep}
 mkdir -p $OUT
 for c in 8192 16384 32768 65536; do
-  DVQ_PIXELCNN_CHUNK=$c timeout 600 python3 bench.py --gpus 1 --steps 6 --warmup 2 --no-cpu-baseline --no-latency > $OUT/c$c.json 2> $OUT/c$c.err
+  DVQ_PIXELCNN_CHUNK=$c timeout 600 python3 bench.py --gpus 1 --steps 6 --warmup 2 --full --no-cpu-baseline --no-latency > $OUT/c$c.json 2> $OUT/c$c.err
   python3 - $OUT/c$c.json $c <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

@@ -15,7 +15,11 @@ all:
   (6) ``Tensor.multinomial`` replaced by the exponential race ``argmax(p / q)`` with recorded q;
       the equivalence with the real ``multinomial(1)`` under a replayed generator is asserted first.
 
+The one data file taken over from the reference is its MANO model, for the pickle readers' test (g9_mano_pkl: trimmed to
+fit the size limit of a committed file).
+
 Usage:  python tools/make_golden.py            (writes tests/golden/)
+        python tools/make_golden.py mano       (only tests/golden/g9_mano_right.pkl.xz)
 """
 import os
 import sys
@@ -370,9 +374,37 @@ def g0_state_dict_layout():
     print("g0_state_dict_layout", {k: len(v) for k, v in out.items()})
 
 
+def g9_mano_pkl():
+    """models/mano/MANO_RIGHT.pkl as the MANO readers meet it (Python-2 pickle: chumpy Select/Ch, scipy csc_matrix, numpy arrays),
+    byte for byte, except two payloads that keep it under the size limit: posedirs rounded to fp16 values (still float64; the
+    readers' checks run at zero pose) and hands_coeffs, which neither reader reads, zeroed.  xz-compressed (data, not source)."""
+    import lzma
+    import pickletools
+    raw = bytearray(open(os.path.join(REF, "models", "mano", "MANO_RIGHT.pkl"), "rb").read())
+    key, seen = None, set()
+    for op, arg, pos in pickletools.genops(bytes(raw)):
+        if op.name == "SHORT_BINSTRING" and arg in ("posedirs", "hands_coeffs"):
+            key = arg
+        elif op.name == "BINSTRING" and key is not None and len(arg) > 1000:       # the key's array payload: 'T' + 4-byte length
+            n = int.from_bytes(raw[pos + 1: pos + 5], "little")
+            a = np.frombuffer(bytes(raw[pos + 5: pos + 5 + n]), "<f8")
+            a = a.astype(np.float16).astype("<f8") if key == "posedirs" else np.zeros_like(a)
+            raw[pos + 5: pos + 5 + n] = a.tobytes()
+            seen.add(key)
+            key = None
+    assert seen == {"posedirs", "hands_coeffs"}, seen
+    path = os.path.join(OUT, "g9_mano_right.pkl.xz")
+    with open(path, "wb") as f:
+        f.write(lzma.compress(bytes(raw), preset=9 | lzma.PRESET_EXTREME))
+    print(f"wrote {path}  ({os.path.getsize(path) / 1024:.1f} KiB)")
+
+
 def main():
     if len(sys.argv) > 1 and sys.argv[1] == "layout":
         g0_state_dict_layout()
+        return
+    if len(sys.argv) > 1 and sys.argv[1] == "mano":
+        g9_mano_pkl()
         return
     check_multinomial_equivalence()
     g0_state_dict_layout()
