@@ -8,8 +8,8 @@
 #include <mutex>
 #include "../../include/dvq.h"
 
-// Diagnostics build (make EXTRA=-DDVQ_DIAG): timing-only ablation variants (DVQ_VQ_ABL, DVQ_PN_ABL, DVQ_GEMM_ABL: results
-// INVALID), phase stamps (DVQ_VQ_DBG, DVQ_GEMM_CLK) and the DVQ_GEMM_NODMA switch exist only there.  The shipped library
+// Diagnostics build (make EXTRA=-DDVQ_DIAG): timing-only ablation variants (DVQ_VQ16_ABL, DVQ_PN_ABL, DVQ_GEMM_ABL: results
+// INVALID), phase stamps (DVQ_VQ16_DBG, DVQ_GEMM_CLK) and the DVQ_GEMM_NODMA switch exist only there.  The shipped library
 // never reads those variables: a stray one in the environment cannot change a result.
 #ifdef DVQ_DIAG
 #define DVQ_DIAG_ON 1
@@ -32,13 +32,13 @@ __device__ __forceinline__ void dvq_dma_barrier() {
     __syncthreads();
 }
 // Workgroup barrier with the wave's own LDS operations COMPLETE before it arrives, spelled out.  __syncthreads() is supposed to
-// imply it, and the compiler normally emits "s_waitcnt lgkmcnt(0)" in front of s_barrier -- but not always: in pn_trunk3_kernel
-// (round 5) the barrier at the head of the conv3 loop came out WITHOUT the wait although the back edge carries LDS stores (the next
-// chunk's W3 rows, the ring pairs).  A wave then passes the barrier with its stores still in flight, its neighbours read the old
-// contents -- nothing at one workgroup per CU, where the four waves run in step, a wrong tile record every few thousand tiles as soon
-// as workgroups share a CU.  (This is the shape of the round-3 fault of pn_trunk_filter_kernel, whose barrier has the wait in the
-// current build.)  EVERY workgroup barrier of pointnet.hip and pointnet_filter.hip goes through here (round 6: the exact stage's,
-// the centre kernel's and the unfused trunk's too).
+// imply it, and the compiler normally emits "s_waitcnt lgkmcnt(0)" in front of s_barrier -- but not always: in the three-workgroup
+// trunk kernel (round 5; a diagnostics-only variant, removed since) the barrier at the head of the conv3 loop came out WITHOUT the
+// wait although the back edge carries LDS stores (the next chunk's W3 rows, the ring pairs).  A wave then passes the barrier with
+// its stores still in flight, its neighbours read the old contents -- nothing at one workgroup per CU, where the four waves run in
+// step, a wrong tile record every few thousand tiles as soon as workgroups share a CU.  (This is the shape of the round-3 fault of
+// pn_trunk_filter_kernel, whose barrier has the wait in the current build.)  EVERY workgroup barrier of pointnet.hip and
+// pointnet_filter.hip goes through here (round 6: the exact stage's, the centre kernel's and the unfused trunk's too).
 __device__ __forceinline__ void dvq_lds_barrier() {
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __syncthreads();
@@ -216,8 +216,6 @@ struct DvqKnobs {
     int gemm_wide;        // 0: 128 x 128 kernels only
     int gemm_dephase;
     int gemm_tn;          // 0 (default): the tiled f16x2 kernel picks 128 x 256 or 128 x 128 tiles per launch; 128 / 256 force one (DVQ_GEMM_TN)
-    int vq_kernel;        // 16 (default): vq_stream16.hip; 8: vq_stream.hip's eight-wave kernel; 32: vq_rows.hip (DVQ_VQ_KERNEL)
-    int vq_rows_delay;    // vq_rows.hip: start delay of the second half of the grid, 10 ns ticks (DVQ_VQ_ROWS_DELAY)
     int gemm_skinny_prefetch;   // 0: no helper workgroups (DVQ_GEMM_SKINNY_PREFETCH=0)
     int gemm_skinny;      // 0: tiled kernels also for M <= 256 (DVQ_GEMM_SKINNY=0; the two must agree bitwise)
     int gemm_skinny_cols; // f16x2 skinny kernel: output columns per wave, 16 / 8 / 4 (DVQ_GEMM_SKINNY_COLS; 0 = by the launch's size; same bits)
@@ -226,7 +224,6 @@ struct DvqKnobs {
     int pn_exhaustive;    // 1: exact stage evaluates every point (what the filter must reproduce bit for bit)
     int pn_caps[2];       // candidate-list capacities (tests shrink them to reach the overflow paths); <= 0: default
     long pn_chunk;        // samples per PointNet launch (<= 0: at most 4 096, at least four launches per pass; DVQ_PN_CHUNK)
-    int pn_trunk3;        // diagnostics build only: DVQ_PN_TRUNK3=1: full tiles on pn_trunk3_kernel (three workgroups per CU; measured 4.5 % slower); default 0: pn_trunk_filter_kernel (two)
     int pn_streams;       // 1 (default): the exact stage / STN FCs of a launch on a second stream beside the next launch's trunk kernel (DVQ_PN_STREAMS=0: one stream)
     int pn_slots;         // scratch sets the launches rotate through (<= 0: 2; DVQ_PN_SLOTS)
     int pn_stats;
@@ -234,12 +231,6 @@ struct DvqKnobs {
     int pixelcnn_tables;  // 1 (default): what depends on the class label only is evaluated once per class (DVQ_PIXELCNN_TABLES=0: per row)
 };
 const DvqKnobs& dvq_knobs();
-int dvq_launch_vq_stream16(const float* z, const float* E, const void* packed, long M, int64_t* idx, unsigned long long* slow_rows,
-                           unsigned long long* dbg, hipStream_t st);
-int dvq_launch_vq_pipe(const float* z, const float* E, const void* packed, long M, int64_t* idx, unsigned long long* slow_rows,
-                       unsigned long long* dbg, hipStream_t st);
-int dvq_launch_vq_rows(const float* z, const float* E, const void* packed, long M, int64_t* idx, unsigned long long* slow_rows,
-                       hipStream_t st);
 // simple helpers implemented in misc.hip
 int dvq_launch_gather_rows(const float* table, const int64_t* idx, long idx_stride, long M, int K, int D,
                            float* out, long ldo, int32_t* err_flag, hipStream_t stream);

@@ -26,13 +26,8 @@ DvqKnobs* read_knobs() {
     k->gemm_tn = (int)num("DVQ_GEMM_TN");
     k->gemm_dephase = is("DVQ_GEMM_DEPHASE", '0') ? 0 : (is("DVQ_GEMM_DEPHASE", '1') ? 1 : 2);    // f16x2 tiled kernel: 2 = ping-pong (default)
     k->gemm_skinny = is("DVQ_GEMM_SKINNY", '0') ? 0 : (is("DVQ_GEMM_SKINNY", '2') ? 2 : 1);   // 2: the register-staged variant
-    {
-        const int v = getenv("DVQ_VQ_KERNEL") ? atoi(getenv("DVQ_VQ_KERNEL")) : 0;
-        k->vq_kernel = v == 8 ? 8 : (v == 32 ? 32 : (v == 17 ? 17 : 16));       // default: the sixteen-wave kernel; 8: eight waves (generated tile body); 32: rows resident, codebook streamed
-    }
     k->gemm_skinny_prefetch = !is("DVQ_GEMM_SKINNY_PREFETCH", '0');
     k->gemm_skinny_cols = (int)num("DVQ_GEMM_SKINNY_COLS");
-    k->vq_rows_delay = getenv("DVQ_VQ_ROWS_DELAY") ? (int)num("DVQ_VQ_ROWS_DELAY") : 0;
     k->pn_filter = is("DVQ_PN_FILTER", '0') ? 0 : (is("DVQ_PN_FILTER", '2') ? 2 : 1);
     k->pn_tail = is("DVQ_PN_TAIL", '0') ? 0 : 1;
     k->pn_exhaustive = is("DVQ_PN_EXHAUSTIVE", '1');
@@ -43,11 +38,6 @@ DvqKnobs* read_knobs() {
     }
     k->pn_chunk = num("DVQ_PN_CHUNK");
     k->pn_streams = is("DVQ_PN_STREAMS", '0') ? 0 : 1;
-#ifdef DVQ_DIAG
-    k->pn_trunk3 = is("DVQ_PN_TRUNK3", '1') ? 1 : 0;            // the kernel exists in the diagnostics build only
-#else
-    k->pn_trunk3 = 0;
-#endif
     k->pn_slots = (int)num("DVQ_PN_SLOTS");
     k->pn_stats = getenv("DVQ_PN_STATS") != nullptr;
     k->pixelcnn_chunk = num("DVQ_PIXELCNN_CHUNK");

@@ -1,38 +1,69 @@
-// Fast VQ nearest-codebook-entry for the headline shape (K = 512, D = 256), second structure (DVQ_VQ_KERNEL=16): SIXTEEN waves per
-// workgroup, four per SIMD, each holding 32 codebook entries; plain straight-line code, no generated gap tables.  Same result
-// as vq_stream.hip / vq.hip / oracle/vq_canonical.c, bit for bit.  Reference: VectorQuantizer.forward(z, istrain=False),
-// network/vqvae/quantizer.py:46-49.
+// Fast VQ nearest-codebook-entry for the headline shape (K = 512, D = 256; a codebook of fewer entries runs on a padded image):
+// same indices as the exact kernel (vq.hip / oracle/vq_canonical.c), bit for bit, with z streamed from HBM exactly once UNDER the
+// matrix work.  Reference: VectorQuantizer.forward(z, istrain=False), network/vqvae/quantizer.py:46-49.
 //
-// Why it exists (round 3; every number: MI355X, M = 65 536, six rotating inputs, tools/vq_kernel_ab.py, tools/vq16_phase_stamps.py,
-// tools/vq_pmc.sh).  Three structures were built to get the 36 us of vq_stream.hip (eight waves, two per SIMD) to the 21.3 us the
-// task asks for:
+// Structure (persistent, codebook in registers, z through registers and one fp16 LDS tile): one 1024-thread workgroup per CU walks
+// over up to 8 tiles of 32 rows (tile = blockIdx + j * gridDim); SIXTEEN waves, four per SIMD, each holding 32 codebook entries;
+// plain straight-line code, no generated gap tables.
+//   * wave w keeps entries [32w, 32w+32) -- fp16 of -2 sE e_k, all 256 dims -- as the MFMA A operand in 64 VGPRs (<= 128 VGPRs:
+//     four waves per SIMD); the accumulators START at sE |e_k|^2 (read from the LDS each tile), so they END as the scores
+//     sE (|e_k|^2 - 2 z.e_k);
+//   * per tile: one s_barrier (the fp16 image of tile t and the slots of tile t-1 are complete), 16 fragment reads + 16 MFMAs,
+//     scores -> the wave's slot (min, second) per row; waves 0-7 convert 4 rows of tile t+1 each (16 lanes per row, loaded a
+//     tile earlier) to fp16 ONCE (|h(z)|^2, the measured rounding error |z - h(z)|, eps_row; 528-byte padded LDS rows) and load
+//     tile t+2; waves 8-11 merge 8 rows of tile t-1 each (8 lanes per row, 4 slots per lane); waves 4-11 do that vector work
+//     BEFORE their MFMAs, the others after (the four waves of a SIMD leave the barrier together);
+//   * the merge finds the row minimum over the 32 (wave, lane half) slots of a row and the slots within eps_row of it: decided
+//     rows write their entry; every row leaves a record {threshold, flags}; undecided rows go to the merging wave's own list (no
+//     atomics, no branch in the loop) and are expanded into candidate pairs after the loop (all slots stay in the LDS: 9 x 8.7 KB);
+//   * after the last tile: the canonical fp32 evaluation d_k = (zz + ee_k) - 2 dot_k (k-ordered fmaf chains, eight lanes per
+//     chain) of the listed pairs, a u64 minimum of (ordered distance bits, entry) per row = torch.argmin's order (first minimum,
+//     NaN first).  Rows with NaN/Inf, fp16 overflow or an overflowing list: all K entries canonically.
+//
+// Error bound (filter keeps the exact winner).  No per-row scaling: h(.) = round to nearest fp16, subnormals kept (by the
+// conversion and, measured on gfx950, by the matrix core: tests/test_gpu_parity.py::test_mfma_keeps_f16_subnormals).
+// With dz_j = z_j - h(z_j), de_kj = e_kj - h(-2 sE e_kj)/(-2 sE) (exact in fp32), products h.h exact in the MFMA's fp32,
+// T_k = sE (true_k - |z|^2), gamma_n = n 2^-24 (gamma'_n = n 2^-23 allows a truncating accumulator):
+//   |S_k - T_k|         <= sE [2 (|dz||e_k| + |z||de_k| + |dz||de_k|) + gamma'_259 (|e_k|^2 + 2|z||e_k|)]          (filter)
+//   |d_k - true_k|      <= gamma_260 (|z| + |e_k|)^2                                                            (exact side)
+//   |packed(S_k) - S_k| <= 2^-18 |S_k| <= 2^-18 sE (|z| + |e_k|)^2                                 (5-bit id in the mantissa)
+// so for the canonical winner k* and every k:  packed(S_k*) <= packed(S_k) + sE eps_row,
+//   eps_row = 4 (|dz| Emax + |z| dEmax + |dz| dEmax) + (2 gamma'_259 + 2^-17 + 2 gamma_260 = 9.97e-5) (|z| + Emax)^2,
+// |dz| measured by the kernel's own conversion (-DDVQ_MEASURE_DZ=0: half-ulp bound 2^-11 |h(z)| + 2^-21), |z| <= |h(z)| + |dz|, dEmax measured by
+// dvq_vq_pack, norms rounded up.  A slot whose
+// SECOND score is within eps may hide a third: all 16 entries of that slot are listed, so the list always contains k*.
+// Algorithmic HBM bytes per row: D*4 (z) + 8 (int64 index); the codebook (K*D*4) is read once.
+//
+// Hand-issued LDS reads (inline asm + counted s_waitcnt) carry three rules, each learnt from a wrong result:
+//   (1) the destination of a read is "defined" for the compiler at the asm statement: it must not be copied or reused before
+//       the wait -- so no such read is in flight across a control-flow join, and a read whose value is never used is still
+//       pinned by the wait that completes it;
+//   (2) vector work placed in an MFMA gap is anchored there by an empty asm that uses its result (else the compiler
+//       sinks it to the end of the loop body, behind every MFMA);
+//   (3) __builtin_bit_cast applied directly to a vector-element expression reads element 0: copy the element out first.
+//
+// Why this structure (round 3; every number: MI355X, M = 65 536, six rotating inputs, tools/vq16_phase_stamps.py, tools/vq_pmc.sh).
+// Three structures were built to get the 36 us of the first streaming kernel (eight waves, two per SIMD, 64 entries each) to the
+// 21.3 us the task asks for:
 //   (a) FOUR waves, one per SIMD, the codebook as the MFMA A operand in a[0:255] (inline asm; microbenchmark
 //       tools/microbench/mfma_agpr_operand.hip: 32.1 cycles per dependent MFMA, 4-5 placed vector instructions per gap free),
 //       64-gap generated body: 37-43 us.  A single in-order wave per SIMD pays the dependent-issue latency of every vector
 //       chain (SQ counters: 29 % of the wave cycles issuing vector instructions, 44 % waiting, MFMA busy 23 %); compile-time
 //       ablations were ADDITIVE (no MFMA -8.5 us of 22.3, no scoring -2.4, no merge decisions -3.7, no barrier -1.3, no row
 //       loads 0): nothing overlapped.  Removed from the tree (history: "VQ: four-wave streaming kernel").
-//   (b) THIS kernel: 36.4 us = vq_stream.hip.  Ablations of its loop (21-24 us): no conversion -7.4, no MFMA -9.9, no merge -2.7,
-//       no scoring -2.5, no barrier -2.1, no row loads -2.0: additive again although a matrix-only wave and a vector-only wave on one
-//       SIMD do run concurrently (tools/microbench/mfma_valu_two_waves.hip: 520 vs 512 cycles per 16 MFMAs, vector chain +9 %).
-//       SQ counters: 8.2 M vector instructions per launch at 4.0 cycles of SIMD issue each = 15 us of pure vector issue per SIMD;
-//       dealing the vector work by role (below) took 4 000 -> 2 200 instructions per tile and CU and the loop 24.4 -> 21.3 us.
+//   (b) THIS kernel: 36.4 us = the eight-wave kernel.  Ablations of its loop (21-24 us): no conversion -7.4, no MFMA -9.9, no merge
+//       -2.7, no scoring -2.5, no barrier -2.1, no row loads -2.0: additive again although a matrix-only wave and a vector-only wave
+//       on one SIMD do run concurrently (tools/microbench/mfma_valu_two_waves.hip: 520 vs 512 cycles per 16 MFMAs, vector chain
+//       +9 %).  SQ counters: 8.2 M vector instructions per launch at 4.0 cycles of SIMD issue each = 15 us of pure vector issue per
+//       SIMD; dealing the vector work by role (above) took 4 000 -> 2 200 instructions per tile and CU and the loop 24.4 -> 21.3 us.
 //   (c) 64-row tiles (half the barriers): 24.4 us, 17 spilled registers: not kept.
 // What the three have in common is ~6 000 cycles per 32-row tile and CU against 2 048 of matrix work and ~2 200 of vector issue:
 // the per-tile dependency chain (barrier -> fragment reads -> 16 dependent MFMAs -> 16-step top-2 chain -> slot -> barrier, and
 // beside it load -> convert -> row reduction -> LDS) is executed by too few independent instruction streams to fill either pipe.
-//
-//   * wave w keeps entries [32w, 32w+32) -- fp16 of -2 sE e_k, all 256 dims -- as the MFMA A operand in 64 VGPRs (<= 128 VGPRs:
-//     four waves per SIMD); the accumulator start values sE |e_k|^2 come from the LDS each tile;
-//   * per tile: one s_barrier (the fp16 image of tile t and the slots of tile t-1 are complete), 16 fragment reads + 16 MFMAs,
-//     scores -> the wave's slot (min, second) per row; waves 0-7 convert 4 rows of tile t+1 each (16 lanes per row, loaded a
-//     tile earlier) and load tile t+2; waves 8-11 merge 8 rows of tile t-1 each (8 lanes per row, 4 slots per lane); waves 4-11
-//     do that vector work BEFORE their MFMAs, the others after (the four waves of a SIMD leave the barrier together);
-//   * decided rows write their entry; every row leaves a record {threshold, flags}; undecided rows go to the merging wave's own
-//     list (no atomics, no branch in the loop) and are expanded into candidate pairs after the loop (all slots stay in the LDS:
-//     9 x 8.7 KB), then the canonical fp32 refine of vq_stream.hip (see its header for the error bound), eight lanes per chain.
+// Built, measured and removed since (sources at commit 66a0f2d, measurements in DESIGN.md 3.2 and profiles/): the eight-wave kernel
+// after round 3 (35.6-35.9 us against 34.1-35.0 us for this one in the same microbenchmark), a rows-resident kernel that streams
+// the codebook (42 us) and round 6's generated single-instruction-block kernel (35.2 against 32.1 us in the steady state).
 #include "dvq_internal.h"
-#include "vq_pack.h"
 
 namespace {
 
@@ -40,7 +71,99 @@ typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
-constexpr int K = VQ_K, D = VQ_D;
+constexpr int K = 512, D = 256;
+
+// ------------------------------------------------------------------------------------------------ pack
+// Packed codebook image (dvq_vq_pack): header, canonical |e_k|^2, fp16 image of -2 sE E in MFMA-fragment order.
+constexpr int EXP_LIMIT = 40;                      // |log2(max codebook magnitude)| beyond this -> exact fallback
+struct PackHeader {
+    float emax;        // upper bound of max_k |e_k|_2 (inf if the codebook is not finite)
+    int sexp;          // codebook scale sE = 2^sexp
+    int valid;         // 0: codebook magnitudes outside the filter's range -> every row takes the exact path
+    int K, D;
+    float demax;       // upper bound of max_k |e_k - image_k / (-2 sE)|_2: the image's MEASURED fp16 rounding error
+    int layout;        // 3: image in MFMA-fragment order (below)
+};
+constexpr size_t PK_OFF_EE = 256;                          // [K] f32 canonical |e_k|^2
+constexpr size_t PK_OFF_IMG = PK_OFF_EE + (size_t)K * 4;   // fp16 image, fragment order
+constexpr size_t PK_BYTES = PK_OFF_IMG + (size_t)K * D * 2;
+
+__device__ __forceinline__ float pow2f(int e) { return __int_as_float((e + 127) << 23); }   // e in [-126, 127]
+
+// image position (in fp16 elements) of dim j of entry k: fragment f = ((w*2 + jn)*16 + s), lane = 32 h + r, element e
+//   k = 64 w + 32 jn + r,  j = 16 s + 8 h + e      (wave 2w + jn of the kernel holds fragments 16 (2w + jn) .. +15;
+//   lane l loads 16 B at f*1024 + 16 l: coalesced)
+__host__ __device__ __forceinline__ int img_pos(int k, int j) {
+    const int w = k >> 6, jn = (k >> 5) & 1, r = k & 31, s = j >> 4, h = (j >> 3) & 1, e = j & 7;
+    return ((((w * 2 + jn) * 16 + s) * 64 + (h * 32 + r)) << 3) + e;
+}
+
+// A codebook of Kr < K entries (Kr a multiple of 32; round 6: the model's K = 128 codebooks) is PADDED to the kernel's K = 512: the
+// padding entries have a zero image and 3e38 as |e|^2 (their filter scores are 3e38, never within eps of a real one; the canonical
+// paths stop at Kr); hdr->K = Kr.
+__global__ void vq_pack_norm_kernel(const float* __restrict__ E, int Kr, float* __restrict__ ee, PackHeader* hdr) {
+    __shared__ float red[K];
+    __shared__ float redm[K];
+    const int k = threadIdx.x;                                   // blockDim = K
+    const float* p = E + (k < Kr ? k : 0) * D;
+    float acc = 0.f, mx = 0.f;
+    bool finite = true;
+    for (int j = 0; j < D; ++j) {
+        acc = fmaf(p[j], p[j], acc);                             // canonical chain (same as rownorm_kernel)
+        finite = finite && (fabsf(p[j]) <= 3.0e38f);
+        mx = fmaxf(mx, fabsf(p[j]));
+    }
+    ee[k] = k < Kr ? acc : 3.0e38f;
+    red[k] = k >= Kr ? 0.f : (finite && acc <= 3.0e38f) ? acc : INFINITY;
+    redm[k] = k >= Kr ? 0.f : finite ? mx : INFINITY;
+    __syncthreads();
+    for (int o = K / 2; o > 0; o >>= 1) {
+        if (k < o) {
+            red[k] = fmaxf(red[k], red[k + o]);
+            redm[k] = fmaxf(redm[k], redm[k + o]);
+        }
+        __syncthreads();
+    }
+    if (k == 0) {
+        hdr->emax = sqrtf(red[0]) * 1.00001f;
+        const float m2 = 2.0f * redm[0];                         // the image holds -2 e
+        const int e = (int)((__float_as_uint(m2) >> 23) & 0xff) - 127;
+        const bool ok = redm[0] > 0.f && e >= -EXP_LIMIT && e <= EXP_LIMIT && red[0] <= 3.0e38f;
+        hdr->sexp = ok ? 13 - e : 0;
+        hdr->valid = ok ? 1 : 0;
+        hdr->K = Kr;
+        hdr->D = D;
+        hdr->layout = 3;
+    }
+}
+
+// image: fp16 of -2 sE e in fragment order
+__global__ void vq_pack_img_kernel(const float* __restrict__ E, int Kr, const PackHeader* __restrict__ hdr, _Float16* __restrict__ img) {
+    const int gid = blockIdx.x * blockDim.x + threadIdx.x;
+    if (gid >= K * D) return;
+    img[img_pos(gid / D, gid % D)] = gid < Kr * D ? (_Float16)(-2.0f * pow2f(hdr->sexp) * E[gid]) : (_Float16)0.0f;   // (subnormals kept; the error kernel measures what is stored)
+}
+
+// measured rounding error of the image, per entry, as a 2-norm in codebook units; its maximum goes into the header
+__global__ void vq_pack_err_kernel(const float* __restrict__ E, int Kr, const _Float16* __restrict__ img, PackHeader* hdr) {
+    __shared__ float red[K];
+    const int k = threadIdx.x;                                   // blockDim = K
+    const float m2s = -2.0f * pow2f(hdr->sexp);
+    float acc = 0.f;
+    for (int j = 0; j < D && k < Kr; ++j) {
+        const float sv = m2s * E[k * D + j];                     // exact (power-of-two scale, range checked by `valid`)
+        const float d = sv - (float)img[img_pos(k, j)];          // exact: fp32 values at most 11 significant bits apart (or sv itself)
+        acc = fmaf(d, d, acc);
+    }
+    red[k] = acc;
+    __syncthreads();
+    for (int o = K / 2; o > 0; o >>= 1) {
+        if (k < o) red[k] = fmaxf(red[k], red[k + o]);
+        __syncthreads();
+    }
+    if (k == 0) hdr->demax = hdr->valid ? sqrtf(red[0]) / fabsf(m2s) * 1.0001f : INFINITY;
+}
+
 constexpr int NWV = 16;                            // waves per workgroup = 32-entry slices of the codebook, four per SIMD
 constexpr int NT = 64 * NWV;                       // 1024 threads, one workgroup per CU
 constexpr int TILE = 32;
@@ -121,7 +244,7 @@ __device__ __forceinline__ unsigned long long order_key(float d, int k) {
     return ((unsigned long long)u << 32) | (unsigned)k;
 }
 
-// ------------------------------------------------------------------------------------------------ refine chains (as vq_stream.hip)
+// ------------------------------------------------------------------------------------------------ refine chains
 // Canonical chains threaded through 8 lanes: lane q of a group holds floats [32q, 32q+32) of its z row and of its candidate's
 // codebook row (all loads issued up front: ONE memory latency; 64 registers: this kernel runs at 128), then the k-ordered fmaf
 // chain runs as eight 32-step rounds, round q continuing from the accumulator lane q-1 produced.  Bit-identical to one 256-step chain.
@@ -558,11 +681,9 @@ __global__ __launch_bounds__(NT) void vq_stream16_kernel(const float* __restrict
 #endif
 }
 
-}  // namespace
-
-// called by dvq_vq_argmin_fast (vq_stream.hip) after argument validation
-int dvq_launch_vq_stream16(const float* z, const float* E, const void* packed, long M, int64_t* idx, unsigned long long* slow_rows,
-                           unsigned long long* dbg, hipStream_t st) {
+// called by dvq_vq_argmin_fast after argument validation
+int launch_vq_stream16(const float* z, const float* E, const void* packed, long M, int64_t* idx, unsigned long long* slow_rows,
+                       unsigned long long* dbg, hipStream_t st) {
     static DvqOncePerDevice attr_once;
     {
         const hipError_t e = attr_once.run([] {
@@ -583,9 +704,7 @@ int dvq_launch_vq_stream16(const float* z, const float* E, const void* packed, l
             return DVQ_ELAUNCH;
         }
     }
-    int cus = 0, dev = 0;
-    (void)hipGetDevice(&dev);
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
+    const int cus = dvq_num_cus();
     const long tiles = (M + TILE - 1) / TILE;
     const long per_launch = (long)cus * MAX_TILES;
     for (long t0 = 0; t0 < tiles; t0 += per_launch) {
@@ -616,4 +735,59 @@ int dvq_launch_vq_stream16(const float* z, const float* E, const void* packed, l
         DVQ_CHECK_LAUNCH("vq_stream16");
     }
     return DVQ_OK;
+}
+
+}  // namespace
+
+// K = 512 is the kernel's shape; fewer entries (a multiple of 32) run the same kernel on a padded image (vq_pack_norm_kernel)
+extern "C" int dvq_vq_fast_supported(int Kq, int Dq) { return Dq == D && Kq >= 32 && Kq <= K && Kq % 32 == 0; }
+
+extern "C" size_t dvq_vq_pack_bytes(int Kq, int Dq) { return dvq_vq_fast_supported(Kq, Dq) ? PK_BYTES : 0; }
+
+extern "C" int dvq_vq_pack(const float* E, int Kq, int Dq, void* packed, size_t packed_bytes, dvq_stream_t stream) {
+    DVQ_REQUIRE(dvq_vq_fast_supported(Kq, Dq), "vq_pack: the fast path supports K<=%d (a multiple of 32), D=%d only (got %d, %d)", K, D, Kq, Dq);
+    DVQ_REQUIRE(E && packed && dvq_aligned16(E) && dvq_aligned16(packed), "vq_pack: null/unaligned pointer");
+    DVQ_REQUIRE(packed_bytes >= PK_BYTES, "vq_pack: buffer %zu < %zu bytes", packed_bytes, PK_BYTES);
+    hipStream_t st = (hipStream_t)stream;
+    char* pk = (char*)packed;
+    DVQ_LAUNCH(vq_pack_norm_kernel, dim3(1), dim3(K), 0, st, E, Kq, (float*)(pk + PK_OFF_EE), (PackHeader*)pk);
+    DVQ_CHECK_LAUNCH("vq_pack_norm");
+    DVQ_LAUNCH(vq_pack_img_kernel, dim3((K * D + 255) / 256), dim3(256), 0, st, E, Kq, (const PackHeader*)pk,
+                       (_Float16*)(pk + PK_OFF_IMG));
+    DVQ_CHECK_LAUNCH("vq_pack_img");
+    DVQ_LAUNCH(vq_pack_err_kernel, dim3(1), dim3(K), 0, st, E, Kq, (const _Float16*)(pk + PK_OFF_IMG), (PackHeader*)pk);
+    DVQ_CHECK_LAUNCH("vq_pack_err");
+    return DVQ_OK;
+}
+
+// Fixed size (callers cache their workspace by it), at least what the DVQ_VQ16_DBG stamps write: 64 bytes per workgroup of the
+// first launch, one workgroup per CU (<= 1024).
+constexpr size_t WORKSPACE_BYTES = 1114112;
+static_assert(WORKSPACE_BYTES >= 1024 * 64, "DVQ_VQ16_DBG stamps");
+
+extern "C" size_t dvq_vq_fast_workspace_bytes(int64_t M, int Kq, int Dq) {
+    (void)M;
+    return dvq_vq_fast_supported(Kq, Dq) ? WORKSPACE_BYTES : 256;
+}
+
+extern "C" int dvq_vq_argmin_fast(const float* z, const float* E, const void* packed, int64_t M, int Kq, int Dq,
+                                  int64_t* idx, unsigned long long* slow_rows, void* workspace, size_t workspace_bytes,
+                                  dvq_stream_t stream) {
+    DVQ_REQUIRE(dvq_vq_fast_supported(Kq, Dq), "vq_argmin_fast: supports K<=%d (a multiple of 32), D=%d only (got %d, %d)", K, D, Kq, Dq);
+    DVQ_REQUIRE(M >= 0 && M < (1L << 31), "vq_argmin_fast: bad M");
+    if (M == 0) return DVQ_OK;
+    DVQ_REQUIRE(z && E && packed && idx && workspace, "vq_argmin_fast: null pointer");
+    DVQ_REQUIRE(dvq_aligned16(z) && dvq_aligned16(E) && dvq_aligned16(packed) && dvq_aligned16(workspace),
+                "vq_argmin_fast: pointers must be 16-byte aligned (z must be dense [M,256])");
+    if (workspace_bytes < dvq_vq_fast_workspace_bytes(M, Kq, Dq)) {
+        dvq_set_error("vq_argmin_fast: workspace %zu < %zu bytes", workspace_bytes, dvq_vq_fast_workspace_bytes(M, Kq, Dq));
+        return DVQ_EWORKSPACE;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    unsigned long long* dbg = nullptr;
+#ifdef DVQ_DIAG
+    if (getenv("DVQ_VQ16_DBG")) dbg = (unsigned long long*)workspace;            // phase stamps (diagnostics build only)
+#endif
+    DVQ_PROF("vq_argmin_fast", 2.0 * M * Kq * D, (double)M * D * 4 + (double)Kq * D * 4 + (double)M * 8, st);
+    return launch_vq_stream16(z, E, packed, (long)M, idx, slow_rows, dbg, st);
 }

@@ -127,8 +127,6 @@ def test_every_barrier_waits_for_the_waves_own_lds_operations():
         pytest.skip("hipcc not found: the listing checks need the compiler")
     sys.path.insert(0, os.path.join(root, "tools"))
     import check_barriers, check_hazards, check_waitcnt
-    if not os.path.exists(os.path.join(csrc, "vq_pipe_loop.h")):         # generated, not tracked (the Makefile has the same rule)
-        subprocess.run([sys.executable, os.path.join(root, "tools", "gen_vq_pipe.py")], check=True, capture_output=True)
     flags = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-slp-vectorize", "-S", "--cuda-device-only"]
     with tempfile.TemporaryDirectory() as tmp:
         def build(src):
@@ -147,7 +145,7 @@ def test_every_barrier_waits_for_the_waves_own_lds_operations():
                 if "s_barrier" in body:
                     bad += [(os.path.basename(path), name[:80], hit) for hit in check_barriers.check(body)]
                 # round 6: the same listings through tools/check_hazards.py -- producer / consumer pairs that need wait states the
-                # hardware does not insert (the compiler does not look inside the inline-asm loops: vq_pipe_loop.h is 6 000 lines of it)
+                # hardware does not insert (the compiler does not look inside inline asm)
                 hazards += [msg for _, _, msg in check_hazards.check_lines(body.splitlines(), strict=True, name=os.path.basename(path) + ":" + name[:60])]
                 # ... and tools/check_waitcnt.py: no register is read or overwritten while a load into it may be in flight on some path
                 # (s_waitcnt lgkmcnt / vmcnt re-derived from the listing: the compiler's own counts and the hand-counted ones of the asm loops)

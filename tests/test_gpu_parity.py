@@ -901,10 +901,6 @@ def test_vq_fast_padded_codebooks(K):
     for M in (1, 33, 70001):
         zz = torch.randn(M, D, device=DEV)
         _fast_vs_exact(zz, gpu(E), f"padded K={K}, M={M}")
-    # the other kernels (DVQ_VQ_KERNEL=17 / 8 / 32) must not be handed a padded image: the selection falls back to the default one
-    for kern in ("17", "8", "32"):
-        got = _with_env("DVQ_VQ_KERNEL", kern, lambda: ops.vq_argmin(gpu(z), gpu(E), fast=True))
-        assert torch.equal(got, idx), f"DVQ_VQ_KERNEL={kern} with a padded codebook"
 
 
 def test_vq_fast_scales_and_tie_prone_codebook():
@@ -1345,22 +1341,6 @@ def test_fp32_gemm_branch_matches_goldens(tmp_path):
     assert " passed" in r.stdout
 
 
-def test_pointnet_three_workgroups_per_cu_kernel(tmp_path):
-    """Diagnostics build + DVQ_PN_TRUNK3=1 (read when the library loads) puts the full tiles on pn_trunk3_kernel -- the trunk kernel laid out for three
-    workgroups per CU (168 registers, 52 KB of LDS, 32-channel chunks; measured 4.5 % slower than the default and therefore not the
-    default).  A fresh process runs the PointNet tests of this file on it: goldens, filtered == exhaustive bit for
-    bit, tail tiles, ties, non-finite inputs, the run-time checks with their fault injection, and the two full-machine stress tests --
-    the ones that caught this kernel's barrier without an LDS wait (csrc/dvq_internal.h: dvq_lds_barrier)."""
-    import os, subprocess, sys
-    env = dict(os.environ, DVQ_PN_TRUNK3="1", DVQ_DIAG_LIB="1")          # (the kernel is compiled into the diagnostics build only)
-    sel = ("test_pointnet_golden or test_pointnet_filter or test_pointnet_batched or test_pointnet_runtime_checks or "
-           "test_pointnet_large_clouds or test_pointnet_pipeline")
-    r = subprocess.run([sys.executable, "-m", "pytest", os.path.abspath(__file__), "-q", "-x", "-m", "gpu", "-k", sel,
-                        "-p", "no:cacheprovider"], env=env, capture_output=True, text=True, timeout=1200)
-    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
-    assert " passed" in r.stdout
-
-
 def test_bf16x3_gemm_branch_matches_goldens(tmp_path):
     """DVQ_GEMM=bf16x3 packs every GEMM weight as the exact three-plane bf16 split (six products, fp32's range: what the
     fp16 three-product default falls back to): a fresh process runs the same golden subset on it."""
@@ -1558,9 +1538,9 @@ def test_skinny_gemm_equals_tiled_kernels_bitwise(kind):
     assert torch.equal(a["logits"][3:4], a["logits_row3"])
 
 
-def test_vq_kernel_variants_agree():
-    """The streaming kernels (DVQ_VQ_KERNEL=16 default, 17 = round 6's generated instruction block, 32, 8) return the same indices on
-    random rows, ragged sizes (one tile, two launches), ties, near-ties, non-finite and out-of-range rows."""
+def test_vq_fast_ragged_and_degenerate_rows():
+    """The fast path with a prepacked codebook returns the exact kernel's indices on random rows, ragged sizes (one tile, two
+    launches), ties, near-ties, non-finite and out-of-range rows, and on the reference's tie-prone initial codebook."""
     torch.manual_seed(11)
     E = gpu(torch.randn(512, 256))
     cases = [gpu(torch.randn(M, 256)) for M in (1, 31, 33, 1000, 8192 + 5, 65536, 69632 + 7)]
@@ -1571,27 +1551,8 @@ def test_vq_kernel_variants_agree():
     Et = gpu((torch.rand(512, 256) * 2 - 1) / 512)                    # the reference's initial codebook: tie-prone
     pk, pkt = ops.vq_pack(E), ops.vq_pack(Et)
 
-    def run():
-        return [ops.vq_argmin(c_, E, packed=pk, fast=True) for c_ in cases] + [ops.vq_argmin(cases[3], Et, packed=pkt, fast=True)]
-    a = run()
-    for kern in ("16", "17", "32", "8"):                              # 32: rows resident, codebook streamed (vq_rows.hip)
-        b = _with_env("DVQ_VQ_KERNEL", kern, run)
-        for i, (x, y) in enumerate(zip(a, b)):
-            assert torch.equal(x, y), f"DVQ_VQ_KERNEL={kern}, case {i}: {int((x != y).sum())} rows differ"
-    assert torch.equal(a[3], ops.vq_argmin(cases[3], E, fast=False))
-
-
-def test_vq_pipe_kernel_passes_the_fast_path_tests():
-    """DVQ_VQ_KERNEL=17 (vq_pipe.hip: the prologue and the eight tile periods as one generated instruction block, a-priori rounding
-    bound, merge decided on the scalar unit) under the fast path's own tests: adversarial rows, incomplete candidate lists (pair
-    list overflow -> all-entries scan), scales and the tie-prone codebook, ragged sizes against the C oracle, 160-case fuzz, full
-    size with repeatability."""
-    def run():
-        for M in (1, 31, 32, 33, 1000, 4096):
-            test_vq_fast_equals_exact_and_canonical(M)
-        test_vq_fast_adversarial_rows()
-        test_vq_fast_incomplete_candidate_lists()
-        test_vq_fast_scales_and_tie_prone_codebook()
-        test_vq_fast_fuzz_shapes_scales_and_degenerate_rows()
-        test_vq_fast_full_size()
-    _with_env("DVQ_VQ_KERNEL", "17", run)
+    runs = [(c_, E, pk) for c_ in cases] + [(cases[3], Et, pkt)]
+    for i, (c_, E_, pk_) in enumerate(runs):
+        fast = ops.vq_argmin(c_, E_, packed=pk_, fast=True)
+        exact = ops.vq_argmin(c_, E_, fast=False)
+        assert torch.equal(fast, exact), f"case {i}: filter+refine != exact kernel on {int((fast != exact).sum())} rows"

@@ -2,7 +2,7 @@
 """Static check of gfx950 listings (`hipcc -S --cuda-device-only`, or an inline-asm text) for the data hazards the hardware does NOT
 interlock: the ones that need a number of independent instructions ("wait states": every instruction is one, `s_nop N` is N + 1)
 between a producer and a consumer.  The compiler's hazard recognizer inserts them in code it generates -- it does not look inside
-`asm volatile` blocks, which is where this library's hand-written loops live (vq_pipe_loop.h is one block of ~6 000 instructions), and
+`asm volatile` blocks, which is where this library's hand-written instructions live (the counted LDS reads of vq_stream16.hip), and
 a miscompile of this kind is one candidate for the round-3 PointNet fault (timing dependent, gone after a change of code generation).
 
 Rules (CDNA3 ISA guide section 4.5 "manually inserted wait states" and the gfx940 rows of LLVM's GCNHazardRecognizer):
