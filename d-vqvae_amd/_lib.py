@@ -22,7 +22,7 @@ _lock = threading.Lock()
 _lib = None
 
 DVQ_MAX_SRC = 8
-ABI_VERSION = 9            # DVQ_ABI_VERSION of include/dvq.h, which the struct mirrors below follow (tests/test_abi.py compares both with the library's)
+ABI_VERSION = 10           # DVQ_ABI_VERSION of include/dvq.h, which the struct mirrors below follow (tests/test_abi.py compares both with the library's)
 PLANES_BF16X3, PLANES_F16X2 = 0, 1
 
 c_f32p = C.c_void_p      # device pointers travel as integers
@@ -117,8 +117,10 @@ SIGNATURES = {
     "dvq_prof_reset": (C.c_int, []),
     "dvq_prof_read": (C.c_int, [C.POINTER(ProfEntry), C.c_int]),
     "dvq_transform_cloud": (C.c_int, [c_f32p, C.c_int64, c_f32p, c_f32p, C.c_int64, C.c_int, C.c_int, c_f32p, c_stream]),
+    "dvq_transform_clouds": (C.c_int, [c_f32p, c_i64p, C.c_int64, c_f32p, c_f32p, C.c_int64, C.c_int, C.c_int, c_f32p, c_i32p, c_stream]),
     "dvq_exp1_noise": (C.c_int, [C.c_uint64, C.c_uint32, C.c_int64, C.c_int64, C.c_int, c_f32p, c_stream]),
     "dvq_exp1_noise_rows": (C.c_int, [C.c_uint64, C.c_uint32, C.c_int64, c_i64p, C.c_int64, C.c_int, c_f32p, c_stream]),
+    "dvq_exp1_noise_keyed": (C.c_int, [C.c_uint64, c_i64p, c_i64p, C.c_int64, C.c_int, c_f32p, c_i32p, c_stream]),
     "dvq_probe_f16_subnormal": (C.c_int, [c_f32p, c_stream]),
     "dvq_nn_points": (C.c_int, [c_f32p, C.c_int64, C.c_int64, C.c_int64, c_f32p, C.c_int64, C.c_int64, C.c_int64,
                                 C.c_int64, C.c_int, C.c_int, c_f32p, c_i64p, c_stream]),

@@ -220,8 +220,20 @@ __device__ __forceinline__ void philox4x32_10(unsigned (&c)[4], unsigned k0, uns
     }
 }
 
-// out[r, 4q..4q+3] = -log(u), u = (24 random bits + 0.5) 2^-24 in (0, 1): Exp(1) variates that depend only on
-// (seed, stream, GLOBAL row row0 + r, column), not on how the rows are split into calls, batches or ranks
+// The four Exp(1) variates of column quad q of GLOBAL row `grow` of stream `stream_id`: -log(u), u = (24 random bits + 0.5) 2^-24
+// in (0, 1).  The ONE place the counter layout and the -logf expression live: both generators below call it, so a draw is the
+// same bits whichever of them makes it.
+__device__ __forceinline__ f32x4 exp1_quad(unsigned long long seed, unsigned stream_id, unsigned long long grow, unsigned q) {
+    unsigned c[4] = {q, (unsigned)grow, (unsigned)(grow >> 32), stream_id};
+    philox4x32_10(c, (unsigned)seed, (unsigned)(seed >> 32));
+    f32x4 v;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) v[i] = -logf(((float)(c[i] >> 8) + 0.5f) * 5.9604644775390625e-08f);
+    return v;
+}
+
+// out[r, 4q..4q+3] = Exp(1) variates that depend only on (seed, stream, GLOBAL row row0 + r, column), not on how the rows
+// are split into calls, batches or ranks
 // `perm` (optional): output row r holds the draws of global row row0 + perm[r] (the prior is evaluated in label order)
 __global__ void exp1_noise_kernel(unsigned long long seed, unsigned stream_id, long row0, long rows, int cols, float* __restrict__ out,
                                   const int64_t* __restrict__ perm) {
@@ -231,12 +243,88 @@ __global__ void exp1_noise_kernel(unsigned long long seed, unsigned stream_id, l
     const int q = (int)(gid % quads);
     if (r >= rows) return;
     const unsigned long long grow = (unsigned long long)(row0 + (perm ? (long)perm[r] : r));
-    unsigned c[4] = {(unsigned)q, (unsigned)grow, (unsigned)(grow >> 32), stream_id};
-    philox4x32_10(c, (unsigned)seed, (unsigned)(seed >> 32));
+    *reinterpret_cast<f32x4*>(out + r * cols + 4 * q) = exp1_quad(seed, stream_id, grow, (unsigned)q);
+}
+
+// Per-row keys: out[r, :] = the draws of (seed, stream_ids[r], row_ids[r]) -- rows of many objects in one call, each with the
+// noise its own per-object call draws.  A stream id outside [0, 2^32) or a negative row id: bit 0 of *err_flag, NaN row.
+__global__ void exp1_noise_keyed_kernel(unsigned long long seed, const int64_t* __restrict__ stream_ids, const int64_t* __restrict__ row_ids,
+                                        long rows, int cols, float* __restrict__ out, int32_t* err_flag) {
+    const int quads = cols / 4;
+    const long gid = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    const long r = gid / quads;
+    const int q = (int)(gid % quads);
+    if (r >= rows) return;
+    const int64_t sid = stream_ids[r], row = row_ids[r];
     f32x4 v;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) v[i] = -logf(((float)(c[i] >> 8) + 0.5f) * 5.9604644775390625e-08f);
+    if (sid >= 0 && sid <= (int64_t)0xFFFFFFFFLL && row >= 0) {
+        v = exp1_quad(seed, (unsigned)sid, (unsigned long long)row, (unsigned)q);
+    } else {
+        const float nan = __builtin_nanf("");
+        v = f32x4{nan, nan, nan, nan};
+        if (q == 0 && err_flag) atomicOr(err_flag, 1);
+    }
     *reinterpret_cast<f32x4*>(out + r * cols + 4 * q) = v;
+}
+
+// The rotation pre-step for rows of MANY objects: out[b, :3, :] = R[b] @ pc[obj_of_row[b], :3, :] + t, extra channels copied.
+// One workgroup per (row b, span of TC_SPAN points): the object index, R[b] and t are uniform over the workgroup and read once
+// (scalar loads), not per point.  The arithmetic is transform_cloud_kernel's, component by component in the same order, so a row
+// equals what dvq_transform_cloud writes for that object and rotation bit for bit; only the memory operations are 16 bytes wide
+// (VEC: N % 4 == 0 and 16-byte aligned bases; the scalar path takes any N).  No LDS, no barrier.  An index outside [0, O):
+// bit 0 of *err_flag, row left unwritten.
+constexpr int TC_THREADS = 256;
+constexpr int TC_SPAN = TC_THREADS * 4;              // points per workgroup on either path
+__device__ __forceinline__ float tc_component(float r0, float r1, float r2, float x, float y, float z, float t) {
+    float v = r0 * x;
+    v = fmaf(r1, y, v);
+    v = fmaf(r2, z, v);
+    return v + t;
+}
+template <bool VEC>
+__global__ void __launch_bounds__(TC_THREADS)
+transform_clouds_kernel(const float* __restrict__ pc, const int64_t* __restrict__ obj_of_row, long O, const float* __restrict__ R,
+                        const float* __restrict__ t, int spans, int C, int N, float* __restrict__ out, int32_t* err_flag) {
+    const long b = blockIdx.x / (unsigned)spans;       // grid = B * spans < 2^31 (checked by the launcher)
+    const int n0 = (int)(blockIdx.x % (unsigned)spans) * TC_SPAN;
+    const int64_t o = obj_of_row[b];
+    if (o < 0 || o >= O) {
+        if (threadIdx.x == 0 && n0 == 0 && err_flag) atomicOr(err_flag, 1);
+        return;
+    }
+    float r[9], tt[3];
+#pragma unroll
+    for (int i = 0; i < 9; ++i) r[i] = R[b * 9 + i];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) tt[i] = t ? t[i] : 0.f;
+    const float* src = pc + o * (long)C * N;
+    float* dst = out + b * (long)C * N;
+    if (VEC) {
+        const int n = n0 + (int)threadIdx.x * 4;
+        if (n >= N) return;                           // N % 4 == 0: a quad is whole or absent
+        const f32x4 x = *reinterpret_cast<const f32x4*>(src + n);
+        const f32x4 y = *reinterpret_cast<const f32x4*>(src + N + n);
+        const f32x4 z = *reinterpret_cast<const f32x4*>(src + 2 * (long)N + n);
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            f32x4 v;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) v[k] = tc_component(r[i * 3 + 0], r[i * 3 + 1], r[i * 3 + 2], x[k], y[k], z[k], tt[i]);
+            __builtin_nontemporal_store(v, reinterpret_cast<f32x4*>(dst + i * (long)N + n));
+        }
+        for (int c = 3; c < C; ++c)
+            __builtin_nontemporal_store(*reinterpret_cast<const f32x4*>(src + c * (long)N + n), reinterpret_cast<f32x4*>(dst + c * (long)N + n));
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int n = n0 + k * TC_THREADS + (int)threadIdx.x;
+            if (n >= N) break;
+            const float x = src[n], y = src[N + n], z = src[2 * (long)N + n];
+#pragma unroll
+            for (int i = 0; i < 3; ++i) dst[i * (long)N + n] = tc_component(r[i * 3 + 0], r[i * 3 + 1], r[i * 3 + 2], x, y, z, tt[i]);
+            for (int c = 3; c < C; ++c) dst[c * (long)N + n] = src[c * (long)N + n];
+        }
+    }
 }
 
 // does the matrix core keep fp16 subnormal inputs?  out[0] = sum over k of a_k b_k with a_0 = a_8 = 16 * 2^-24 (subnormal),
@@ -343,6 +431,44 @@ extern "C" int dvq_exp1_noise_rows(uint64_t seed, uint32_t stream_id, int64_t ro
                    (unsigned long long)seed, (unsigned)stream_id, (long)row0, (long)rows, cols, out, perm);
     }
     DVQ_CHECK_LAUNCH("exp1_noise");
+    return DVQ_OK;
+}
+
+extern "C" int dvq_exp1_noise_keyed(uint64_t seed, const int64_t* stream_ids, const int64_t* row_ids, int64_t rows, int cols, float* out,
+                                    int32_t* err_flag, dvq_stream_t stream) {
+    DVQ_REQUIRE(rows >= 0 && cols > 0 && cols % 4 == 0, "exp1_noise_keyed: bad shape rows=%ld cols=%d", (long)rows, cols);
+    if (rows == 0) return DVQ_OK;
+    DVQ_REQUIRE(stream_ids && row_ids && err_flag, "exp1_noise_keyed: null pointer");
+    DVQ_REQUIRE(out && dvq_aligned16(out), "exp1_noise_keyed: null/unaligned output");
+    const long total = rows * (cols / 4);
+    DVQ_REQUIRE(total < (1L << 31) * 256, "exp1_noise_keyed: too many elements");
+    {
+        DVQ_PROF("exp1_noise_keyed", 0, (double)rows * cols * 4 + (double)rows * 16, (hipStream_t)stream);
+        DVQ_LAUNCH(exp1_noise_keyed_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                   (unsigned long long)seed, stream_ids, row_ids, (long)rows, cols, out, err_flag);
+    }
+    DVQ_CHECK_LAUNCH("exp1_noise_keyed");
+    return DVQ_OK;
+}
+
+extern "C" int dvq_transform_clouds(const float* pc, const int64_t* obj_of_row, int64_t O, const float* R, const float* t, int64_t B, int C,
+                                    int N, float* out, int32_t* err_flag, dvq_stream_t stream) {
+    DVQ_REQUIRE(C >= 3 && N > 0 && O >= 0 && B >= 0, "transform_clouds: bad shape O=%ld B=%ld C=%d N=%d", (long)O, (long)B, C, N);
+    if (B == 0) return DVQ_OK;
+    DVQ_REQUIRE(pc && obj_of_row && R && out && err_flag, "transform_clouds: null pointer");
+    const int spans = (N + TC_SPAN - 1) / TC_SPAN;
+    DVQ_REQUIRE(B * spans < (1L << 31), "transform_clouds: too many rows");
+    const bool vec = N % 4 == 0 && dvq_aligned16(pc) && dvq_aligned16(out);     // every [C,N] plane then starts 16-byte aligned
+    {
+        DVQ_PROF("transform_clouds", 0, ((double)B + (double)O) * C * N * 4, (hipStream_t)stream);
+        if (vec)
+            DVQ_LAUNCH(transform_clouds_kernel<true>, dim3((unsigned)(B * spans)), dim3(TC_THREADS), 0, (hipStream_t)stream, pc, obj_of_row,
+                       (long)O, R, t, spans, C, N, out, err_flag);
+        else
+            DVQ_LAUNCH(transform_clouds_kernel<false>, dim3((unsigned)(B * spans)), dim3(TC_THREADS), 0, (hipStream_t)stream, pc, obj_of_row,
+                       (long)O, R, t, spans, C, N, out, err_flag);
+    }
+    DVQ_CHECK_LAUNCH("transform_clouds");
     return DVQ_OK;
 }
 

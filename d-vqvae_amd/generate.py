@@ -1,6 +1,7 @@
 """Generation plumbing shared by the four ``gen_diverse_grasp_*`` entry points (reference:
 gen_diverse_grasp_obman.py:194-365 and the ho3d/grab/FHAB variants): model build, checkpoint loading, per-object
-random rotations, ONE batched ``GenNet.gen`` call per object (the reference loops B=1 calls), 61-parameter
+random rotations, ONE batched ``GenNet.gen`` call for the grasps of MANY objects (the reference loops B=1 calls; every grasp
+is keyed by (seed, object index, grasp index), so it does not depend on how objects are grouped into calls), 61-parameter
 assembly, the final posed-MANO pass and the per-object JSON the downstream tools read.
 
 Out of scope: the physics / mesh metrics (pybullet, igl, trimesh, V-HACD) and the dataset
@@ -54,6 +55,9 @@ def build_parser(dataset: str) -> argparse.ArgumentParser:
     p.add_argument("--mano_model", default="./models/mano/MANO_RIGHT.pkl")
     p.add_argument("--out_dir", default=f"./diverse_grasp/{dataset}")
     p.add_argument("--device", default=None)
+    p.add_argument("--rows_per_call", type=int, default=16384,
+                   help="grasps per batched call: whole objects of one point count are grouped up to this many rows "
+                        "(0 = one call per object); the files written do not depend on it")
     return p
 
 
@@ -143,6 +147,103 @@ def generate_for_object(net: GenNet, obj4n: torch.Tensor, num_grasp: int, rotate
                      "R_list": Rt.tolist(), "trans_list": [t.reshape(3, 1).tolist()] * G, "r_list": angles.tolist()}}
 
 
+def _hand_topology(net: GenNet, n_verts: int, dev):
+    from . import contact
+    faces = np.asarray(net.rh_mano.faces)
+    if faces.size == 0 or int(faces.max()) == 0:
+        raise RuntimeError("proxies: the MANO layer has no face list (synthetic model); load MANO_RIGHT.pkl")
+    topo = getattr(net, "_hand_topology", None)
+    if topo is None or topo.faces.device != dev:
+        topo = contact.HandTopology(faces, n_verts, dev)
+        object.__setattr__(net, "_hand_topology", topo)
+    return topo
+
+
+def plan_calls(point_counts: Sequence[int], num_grasp: int, rows_per_call: int) -> List[List[int]]:
+    """Positions of the objects of each batched call.  A call needs one point count: positions are grouped by it (groups in
+    the order their first object appears, the given order inside a group) and every group is cut into calls of whole objects,
+    at most ``max(1, rows_per_call // num_grasp)`` each -- an object's grasps are never split, so ``rows_per_call < num_grasp``
+    gives one object per call.  Every position appears in exactly one call."""
+    if num_grasp < 1 or rows_per_call < 1:
+        raise ValueError(f"plan_calls: num_grasp and rows_per_call must be positive (got {num_grasp}, {rows_per_call})")
+    per_call = max(1, rows_per_call // num_grasp)
+    groups: Dict[int, List[int]] = {}
+    for pos, n in enumerate(point_counts):
+        groups.setdefault(int(n), []).append(pos)
+    return [g[i:i + per_call] for g in groups.values() for i in range(0, len(g), per_call)]
+
+
+@torch.no_grad()
+def _generate_call(net: GenNet, objs: Sequence[torch.Tensor], num_grasp: int, rotate: bool, seed: int,
+                   object_indices: Sequence[int], proxies: bool) -> List[Dict[str, object]]:
+    """One batched call: the ``num_grasp`` grasps of each of ``objs`` (all of one point count), row o * num_grasp + g = grasp g
+    of object o.  Every step is row-independent and keyed per row, so each object's slice holds the bits of its own
+    ``generate_for_object`` call."""
+    dev = next(net.parameters()).device
+    G, O = num_grasp, len(objs)
+    if rotate:                                                                     # each object's own generator, as the loop draws them
+        angles = [np.random.default_rng([seed, int(gi)]).random((G, 3)) * np.pi * 2 for gi in object_indices]
+        Rs = [rotation_xyz(a) for a in angles]
+        t = np.asarray(CANONICAL_OFFSET)
+    else:
+        angles = [np.zeros((G, 3))] * O
+        Rs = [np.tile(np.eye(3), (G, 1, 1))] * O
+        t = np.zeros(3)
+    clouds = torch.stack([o.contiguous() for o in objs]).to(dev)                 # [O,4,N]: one copy per object, none per grasp
+    obj_of_row = torch.arange(O, device=dev).repeat_interleave(G)
+    stream_ids = torch.as_tensor(np.asarray(object_indices, dtype=np.int64), device=dev).repeat_interleave(G)
+    row_ids = torch.arange(G, device=dev).repeat(O)
+    err = ops.new_err_flag(dev)                                                    # read after the parameters' copy below: no extra sync
+    batch = ops.transform_clouds(clouds, obj_of_row, torch.as_tensor(np.concatenate(Rs), dtype=torch.float32, device=dev),
+                                 torch.as_tensor(t, dtype=torch.float32, device=dev), err=err)
+    recon, pos = net.gen(batch, seed=seed, row_keys=(stream_ids, row_ids))
+    params = ops.assemble61(recon, pos)                                            # obman.py:243-247
+    final = net.rh_mano(betas=params[:, :10], global_orient=params[:, 10:13], hand_pose=params[:, 13:58],
+                        transl=params[:, 58:61])                                   # obman.py:252-253
+    host = params.cpu().numpy()                                                    # ONE device-to-host copy per call
+    if int(err.item()) != 0:
+        raise RuntimeError("generate_for_objects: object index out of range in transform_clouds")
+    topo = _hand_topology(net, final.vertices.shape[1], dev) if proxies else None
+    # the JSON fields of the whole call as Python lists in ONE pass each (a .tolist() per object costs more than the device work at
+    # one grasp per object), then the per-object split
+    B = O * G
+    p_list = host.tolist()
+    Rt_list = np.concatenate([np.concatenate(Rs), np.broadcast_to(t.reshape(1, 3, 1), (B, 3, 1))], axis=2).tolist()
+    r_list = np.concatenate(angles).tolist()
+    trans = t.reshape(3, 1).tolist()
+    p_dev, v_dev = params.split(G), final.vertices.split(G)
+    outs = []
+    for o in range(O):
+        lo, hi = o * G, (o + 1) * G
+        extra = {}
+        if proxies:                                                                # per object: the reductions see the loop's shapes
+            from . import contact
+            extra["proxies"] = contact.grasp_proxies(topo, final.vertices[lo:hi], batch[lo:hi, :3].transpose(1, 2))
+        outs.append({**extra, "params": p_dev[o], "vertices": v_dev[o],
+                     "json": {"recon_params": [[p] for p in p_list[lo:hi]],           # [[61 floats]] per grasp, as the reference
+                              "R_list": Rt_list[lo:hi], "trans_list": [trans] * G, "r_list": r_list[lo:hi]}})
+    return outs
+
+
+def generate_for_objects(net: GenNet, objs: Sequence[torch.Tensor], num_grasp: int, rotate: bool, seed: int,
+                         object_indices: Sequence[int], proxies: bool = False, rows_per_call: int = 16384) -> List[Dict[str, object]]:
+    """``num_grasp`` grasps for each of ``objs`` ([4,N] tensors) in batched calls that mix objects (plan_calls): one dict per
+    object, in the order given, equal to ``generate_for_object(net, objs[i], num_grasp, rotate,
+    np.random.default_rng([seed, object_indices[i]]), seed=seed, object_index=object_indices[i], proxies=proxies)`` --
+    tensors bit for bit, ``json`` as Python objects.  Per call: the rotations of each object's own generator, one
+    ``ops.transform_clouds``, one ``GenNet.gen(row_keys=)`` with stream = object index and row = grasp index, one ``assemble61``,
+    one posed-MANO pass, one device-to-host copy.  A call's clouds and intermediates are freed before the next call; the results
+    returned stay on the device, so hand over one call's objects at a time (as ``main`` does) when the list is long."""
+    if len(object_indices) != len(objs):
+        raise RuntimeError("generate_for_objects: one object index per object")
+    out: List[Optional[Dict[str, object]]] = [None] * len(objs)
+    for call in plan_calls([o.shape[1] for o in objs], num_grasp, rows_per_call):
+        res = _generate_call(net, [objs[p] for p in call], num_grasp, rotate, seed, [object_indices[p] for p in call], proxies)
+        for p, r in zip(call, res):
+            out[p] = r
+    return out
+
+
 def main(dataset: str, argv: Optional[Sequence[str]] = None) -> List[str]:
     args = build_parser(dataset).parse_args(argv)
     rank, local_rank, world = dist.init()
@@ -161,22 +262,48 @@ def main(dataset: str, argv: Optional[Sequence[str]] = None) -> List[str]:
     written = []
     lo, hi = dist.shard_range(len(objs), rank, world)                              # objects are independent: shard them
     total_t, total_g = 0.0, 0
-    for gi, (name, obj) in enumerate(objs[lo:hi], start=lo):
-        torch.cuda.synchronize(device)
-        t0 = time.time()
-        rng = np.random.default_rng([args.seed, gi])                                # per OBJECT: rotations independent of the sharding
-        out = generate_for_object(net, obj, args.num_grasp, DATASETS[dataset]["rotate"], rng, seed=args.seed, object_index=gi)
-        torch.cuda.synchronize(device)                                             # the reference times without a sync
-        dt = time.time() - t0
-        total_t += dt
-        total_g += args.num_grasp
-        print(f"gen_time: {dt:.4f} s for {args.num_grasp} grasps of {name}")
-        path = os.path.join(args.out_dir, f"obj_id_{name}.json")
-        with open(path, "w") as f:
-            json.dump(out["json"], f)
-        written.append(path)
+    wall0 = time.time()
+    rotate = DATASETS[dataset]["rotate"]
+    if args.rows_per_call > 0:
+        # grouped calls: one call's objects at a time, its files written before the next call starts, so the device and the host
+        # hold one call's results, not the whole list's
+        mine = objs[lo:hi]
+        paths: Dict[int, str] = {}
+        for call in plan_calls([o.shape[1] for _, o in mine], args.num_grasp, args.rows_per_call):
+            torch.cuda.synchronize(device)
+            t0 = time.time()
+            outs = generate_for_objects(net, [mine[p][1] for p in call], args.num_grasp, rotate, args.seed, [lo + p for p in call],
+                                        rows_per_call=args.rows_per_call)
+            torch.cuda.synchronize(device)
+            dt = time.time() - t0
+            total_t += dt
+            total_g += args.num_grasp * len(call)
+            print(f"gen_time: {dt:.4f} s for {args.num_grasp * len(call)} grasps of {len(call)} objects")
+            for p, out in zip(call, outs):
+                paths[p] = os.path.join(args.out_dir, f"obj_id_{mine[p][0]}.json")
+                with open(paths[p], "w") as f:
+                    json.dump(out["json"], f)
+            del outs, out
+        written = [paths[p] for p in sorted(paths)]                                # object order, whatever the grouping
+    else:
+        for gi, (name, obj) in enumerate(objs[lo:hi], start=lo):                   # --rows_per_call 0: one call per object
+            torch.cuda.synchronize(device)
+            t0 = time.time()
+            rng = np.random.default_rng([args.seed, gi])                            # per OBJECT: rotations independent of the sharding
+            out = generate_for_object(net, obj, args.num_grasp, rotate, rng, seed=args.seed, object_index=gi)
+            torch.cuda.synchronize(device)                                         # the reference times without a sync
+            dt = time.time() - t0
+            total_t += dt
+            total_g += args.num_grasp
+            print(f"gen_time: {dt:.4f} s for {args.num_grasp} grasps of {name}")
+            path = os.path.join(args.out_dir, f"obj_id_{name}.json")
+            with open(path, "w") as f:
+                json.dump(out["json"], f)
+            written.append(path)
     if total_g:
         print(f"rank {rank}: {total_g} grasps in {total_t:.3f} s ({total_g / max(total_t, 1e-9):.1f} grasps/s incl. first-call packing)")
+        wall = time.time() - wall0
+        print(f"rank {rank}: wall time {wall:.3f} s incl. JSON writing ({total_g / max(wall, 1e-9):.1f} grasps/s end to end)")
     dist.barrier()                                       # every rank's files are on disk when any rank returns
     if world > 1:
         dist.shutdown()

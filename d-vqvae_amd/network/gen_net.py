@@ -84,11 +84,22 @@ class GenNet(nn.Module):
         seed, row0, stream_id = key
         return ops.exp1_noise(B, 9 * n_in, seed, row0, stream_id, device=dev, perm=perm).view(B, 9, n_in)
 
-    def _gen_impl(self, obj, noise, key=None, rows=None):
+    def _draw_noise_keyed(self, row_keys, seed, err, sel=None):
+        """[B, 9, prior_tokens] Exp(1) variates of per-row keys (stream_ids, row_ids); with ``sel``, row r holds the draws of
+        key sel[r].  Only the two [B] key arrays are gathered, never the noise."""
+        n_in = self.GatedPixelCNN.packed().n_in
+        sid, rid = row_keys
+        if sel is not None:
+            sid, rid = sid.index_select(0, sel), rid.index_select(0, sel)
+        return ops.exp1_noise_keyed(sid, rid, 9 * n_in, seed, err=err).view(sid.shape[0], 9, n_in)
+
+    def _gen_impl(self, obj, noise, key=None, rows=None, row_keys=None):
         """The device work of gen(): no host synchronisation inside (gen() checks the error flag once at the end).
         ``noise`` None: the prior's draws come from the device generator under ``key``, drawn directly in the order the prior
         is evaluated in (no gather of the [B, 9, tokens] tensor).  ``rows`` (int64 [B] on the device): ``obj`` holds rows
-        ``rows`` of the keyed batch -- sample b draws the noise of row ``rows[b]`` (the per-row range fallback of gen())."""
+        ``rows`` of the keyed batch -- sample b draws the noise of row ``rows[b]`` (the per-row range fallback of gen()).
+        ``row_keys`` (two int64 [B0] tensors on the device, ``key`` = the seed): per-row keys instead of one stream per call --
+        sample b draws the noise of (seed, stream_ids[b], row_ids[b]), or of entry ``rows[b]`` of the two arrays under ``rows``."""
         if obj.dim() != 3:
             raise RuntimeError(f"gen: expected obj [B,4,N], got {tuple(obj.shape)}")
         B, dev = obj.shape[0], obj.device
@@ -108,14 +119,19 @@ class GenNet(nn.Module):
         # Rows are independent, so the order changes no result; the codes are scattered back.
         if B >= 512 and self.sort_by_label:
             order = torch.argsort(label, stable=True)
-            noise_s = (self._draw_noise(B, dev, key, perm=order if rows is None else rows[order].contiguous()) if noise is None
-                       else noise.index_select(0, order))
+            if noise is not None:
+                noise_s = noise.index_select(0, order)
+            elif row_keys is not None:
+                noise_s = self._draw_noise_keyed(row_keys, key, err, sel=order if rows is None else rows.index_select(0, order))
+            else:
+                noise_s = self._draw_noise(B, dev, key, perm=order if rows is None else rows[order].contiguous())
             codes_s = ops.pixelcnn_sample(pk, label[order].contiguous(), noise_s, err=err)   # :92
             codes = torch.empty_like(codes_s)
             codes[order] = codes_s
         else:
             if noise is None:
-                noise = self._draw_noise(B, dev, key, perm=rows)
+                noise = (self._draw_noise_keyed(row_keys, key, err, sel=rows) if row_keys is not None
+                         else self._draw_noise(B, dev, key, perm=rows))
             codes = ops.pixelcnn_sample(pk, label, noise.contiguous(), err=err)   # :92
         # a position drawn from all-NaN logits carries -1 (bit 2 of err is set; gen() regenerates those rows): decode token 0 there
         recon = self._decode(codes.clamp_min(0), {"z_out": z_out}, None, err)   # :95-113
@@ -129,28 +145,46 @@ class GenNet(nn.Module):
                     "gen_net.py:20-34); build GenNet(n_embeddings=...) to match the prior")
 
     @torch.no_grad()
-    def gen(self, obj, noise=None, return_aux=False, seed=None, row0=None, stream_id=None, check=True):
+    def gen(self, obj, noise=None, return_aux=False, seed=None, row0=None, stream_id=None, check=True, row_keys=None):
         """obj [B,4,N] f32 on the GPU -> (recon [B,55], recon_pos [B,6]).
         ``noise`` [B,9,prior_tokens] ~ Exp(1) fixes the prior's draws (parity runs).  Without it the draws come from the
         device Philox generator keyed by (seed, stream_id, row0 + b): a batch sharded over ranks (``row0`` = first global
         row of the shard, same ``seed`` / ``stream_id``) generates exactly what the unsharded call generates.
         Defaults: seed = set_noise_seed's, else torch.initial_seed(); one stream per call; rows of this rank
         (ops.default_noise_key), so ranks that name nothing never share noise.
+        ``row_keys`` = (stream_ids, row_ids), two int64 [B] tensors on the device: sample b draws the noise of
+        (seed, stream_ids[b], row_ids[b]) -- a call that mixes the grasps of many objects (stream = object, row = grasp index)
+        generates for each grasp the bits its own per-object call generates.  Excludes ``noise`` / ``row0`` / ``stream_id`` and
+        leaves the per-call stream counter alone.
         ``check=False``: no host synchronisation at all -- the call returns as soon as the work is enqueued (a loop of B = 1 calls
         then overlaps the host side of call i + 1 with the device side of call i); the caller gives up the index-range error
         and the fp16-range fallback below, and gets ``aux["err"]`` (device int32: bit 0 range, bit 2 all-NaN logits) to check later."""
         if obj.dim() != 3:
             raise RuntimeError(f"gen: expected obj [B,4,N], got {tuple(obj.shape)}")
-        key = self._noise_key(seed, row0, stream_id) if noise is None else None
+        if row_keys is not None:
+            if noise is not None or row0 is not None or stream_id is not None:
+                raise RuntimeError("gen: row_keys names every row's noise key itself; it excludes noise / row0 / stream_id")
+            sid, rid = row_keys
+            for k, name in ((sid, "stream_ids"), (rid, "row_ids")):
+                if (not torch.is_tensor(k) or k.dtype != torch.int64 or tuple(k.shape) != (obj.shape[0],) or k.device != obj.device
+                        or not k.is_contiguous()):
+                    raise RuntimeError(f"gen: row_keys {name} must be a contiguous int64 [B] tensor on obj's device")
+            row_keys = (sid, rid)
+            if seed is None:
+                seed = ops.default_noise_key()[0] if self.noise_seed is None else self.noise_seed
+            key = seed                                                     # the streams and rows come from row_keys
+        else:
+            key = self._noise_key(seed, row0, stream_id) if noise is None else None
         with ops.no_range_check():                                         # ONE check for the whole path, below
-            recon, recon_pos, aux, err = self._gen_impl(obj, noise, key)
+            recon, recon_pos, aux, err = self._gen_impl(obj, noise, key, row_keys=row_keys)
         aux["err"] = err
         if not check:
             return (recon, recon_pos, aux) if return_aux else (recon, recon_pos)
         # one host synchronisation per call: the index-range flag and "every parameter is finite"
         status = int((err + 2 * (~(torch.isfinite(recon).all() & torch.isfinite(recon_pos).all())).to(torch.int32)).item())
         if status & 1:
-            raise RuntimeError(self._RANGE_ERROR)
+            raise RuntimeError(self._RANGE_ERROR + ("" if row_keys is None else
+                                                    "; or a row key outside the noise generator's counter (stream id in [0, 2^32), row id >= 0)"))
         if (status & 6) and packing.gemm_kind() == _lib.PLANES_F16X2:     # non-finite parameters, or a draw from all-NaN logits (bit 2)
             # The default GEMM arithmetic splits activations into fp16 pieces: a value beyond fp16's range (|x| >= 65 520) turns its
             # ROW into NaN -- never a silently wrong number (rows do not interact anywhere on the path).  Exactly those rows -- a
@@ -162,7 +196,8 @@ class GenNet(nn.Module):
             self.range_fallbacks += 1
             self.range_fallback_rows += int(rows.numel())
             with ops.no_range_check(), packing.gemm_kind_as(_lib.PLANES_BF16X3):
-                r2, p2, aux2, err2 = self._gen_impl(obj.index_select(0, rows), None if noise is None else noise.index_select(0, rows), key, rows=rows)
+                r2, p2, aux2, err2 = self._gen_impl(obj.index_select(0, rows), None if noise is None else noise.index_select(0, rows), key, rows=rows,
+                                                    row_keys=row_keys)
                 if int(err2.item()) & 1:
                     raise RuntimeError(self._RANGE_ERROR)
             recon[rows], recon_pos[rows] = r2, p2

@@ -336,6 +336,40 @@ def exp1_noise(rows: int, cols: int, seed: int, row0: int = 0, stream_id: int = 
     return out
 
 
+def exp1_noise_keyed(stream_ids: Tensor, row_ids: Tensor, cols: int, seed: int, out: Optional[Tensor] = None,
+                     err: Optional[Tensor] = None) -> Tensor:
+    """[rows, cols] Exp(1) variates with one key per row: row r holds exactly the draws of
+    ``exp1_noise(1, cols, seed, row0=row_ids[r], stream_id=stream_ids[r])`` (dvq_exp1_noise_keyed), so a call that mixes the
+    grasps of many objects draws what the per-object calls draw.  ``stream_ids`` / ``row_ids``: contiguous int64 [rows] on the
+    device.  A stream id outside [0, 2^32) or a negative row id raises RuntimeError unless an ``err`` flag tensor is supplied
+    (then the caller checks it; the row is NaN)."""
+    lib = _lib.load()
+    dev = _require_gpu(stream_ids, row_ids, out, err)
+    _i64(stream_ids, "stream_ids"), _i64(row_ids, "row_ids")
+    if stream_ids.dim() != 1 or row_ids.shape != stream_ids.shape or not stream_ids.is_contiguous() or not row_ids.is_contiguous():
+        raise RuntimeError("exp1_noise_keyed: `stream_ids` and `row_ids` must be contiguous int64 [rows] tensors of one length")
+    rows = stream_ids.shape[0]
+    if cols % 4 != 0:                                     # the generator writes 16-byte quads: draw a padded row, keep the columns asked for
+        wide = exp1_noise_keyed(stream_ids, row_ids, (cols + 3) // 4 * 4, seed, err=err)
+        if out is None:
+            return wide[:, :cols].contiguous()
+        out.copy_(wide[:, :cols])
+        return out
+    if out is None:
+        out = torch.empty(rows, cols, dtype=torch.float32, device=dev)
+    if tuple(out.shape) != (rows, cols) or not out.is_contiguous() or out.dtype != torch.float32:
+        raise RuntimeError("exp1_noise_keyed: `out` must be a contiguous float32 [rows, cols] tensor")
+    own_err = err is None
+    if own_err:
+        err = new_err_flag(dev)
+    with torch.cuda.device(dev):
+        check(lib.dvq_exp1_noise_keyed(int(seed) & 0xFFFFFFFFFFFFFFFF, stream_ids.data_ptr(), row_ids.data_ptr(), rows, cols,
+                                       out.data_ptr(), err.data_ptr(), _stream(dev)), "dvq_exp1_noise_keyed")
+    if own_err and int(err.item()) != 0:
+        raise RuntimeError("exp1_noise_keyed: stream id outside [0, 2^32) or negative row id")
+    return out
+
+
 def default_noise_key():
     """(seed, first global row) of noise drawn without an explicit key: the seed follows torch.manual_seed (initial_seed of
     the default generator), and every rank of a process group draws rows of its own (rank * 2^40 + b), so that ranks calling
@@ -535,6 +569,34 @@ def transform_cloud(pc: Tensor, R: Tensor, t: Optional[Tensor] = None) -> Tensor
     with torch.cuda.device(dev):
         check(lib.dvq_transform_cloud(pc.data_ptr(), bstride, R.data_ptr(), t.data_ptr() if t is not None else None, B, Cc,
                                       N, out.data_ptr(), _stream(dev)), "dvq_transform_cloud")
+    return out
+
+
+def transform_clouds(pc: Tensor, obj_of_row: Tensor, R: Tensor, t: Optional[Tensor] = None, err: Optional[Tensor] = None) -> Tensor:
+    """pc [O,C,N] (one cloud per object); obj_of_row int64 [B]; R [B,3,3]; t [3] -> [B,C,N] with row b = R[b] xyz(pc[obj_of_row[b]]) + t,
+    the bits ``transform_cloud(pc[obj_of_row[b]], R[b:b+1], t)`` gives (dvq_transform_clouds); no per-grasp copy of the clouds.
+    An index outside [0, O) raises RuntimeError unless an ``err`` flag tensor is supplied (then the caller checks it; the row is
+    left unwritten)."""
+    lib = _lib.load()
+    dev = _require_gpu(pc, obj_of_row, R, t, err)
+    _f32(pc, "pc"), _f32(R, "R"), _i64(obj_of_row, "obj_of_row")
+    if t is not None and (_f32(t, "t").numel() != 3 or not t.is_contiguous()):
+        raise RuntimeError("transform_clouds: expected contiguous t [3]")
+    B = R.shape[0]
+    if pc.dim() != 3 or not pc.is_contiguous() or not R.is_contiguous() or tuple(R.shape[1:]) != (3, 3):
+        raise RuntimeError("transform_clouds: expected contiguous pc [O,C,N] and R [B,3,3]")
+    if obj_of_row.dim() != 1 or obj_of_row.shape[0] != B or not obj_of_row.is_contiguous():
+        raise RuntimeError("transform_clouds: `obj_of_row` must be a contiguous int64 [B] tensor")
+    O, Cc, N = pc.shape
+    out = torch.empty(B, Cc, N, dtype=torch.float32, device=dev)
+    own_err = err is None
+    if own_err:
+        err = new_err_flag(dev)
+    with torch.cuda.device(dev):
+        check(lib.dvq_transform_clouds(pc.data_ptr(), obj_of_row.data_ptr(), O, R.data_ptr(), t.data_ptr() if t is not None else None,
+                                       B, Cc, N, out.data_ptr(), err.data_ptr(), _stream(dev)), "dvq_transform_clouds")
+    if own_err and int(err.item()) != 0:
+        raise RuntimeError(f"transform_clouds: object index out of bounds for {O} clouds")
     return out
 
 

@@ -39,7 +39,7 @@ typedef enum {
 
 /* The version of this header.  dvq_abi_version() returns the library's: a binding checks the two for equality at load time
  * (struct layouts change between versions). */
-#define DVQ_ABI_VERSION 9
+#define DVQ_ABI_VERSION 10
 int dvq_abi_version(void);
 const char* dvq_last_error(void);
 /* number of visible HIP devices, or -1; does not create a context */
@@ -286,6 +286,17 @@ int dvq_assemble61(const float* recon /* [B,55] */, const float* recon_pos /* [B
 int dvq_transform_cloud(const float* pc /* [C,N] or [B,C,N] */, int64_t pc_batch_stride, const float* R /* [B,3,3] */,
                         const float* t /* [3] */, int64_t B, int C, int N, float* out /* [B,C,N] */,
                         dvq_stream_t stream);
+/* The same pre-step for rows of MANY objects in one call (the batched form of the per-object loops of
+ * gen_diverse_grasp_ho3d.py:205-248 / gen_diverse_grasp_obman.py:233-247):
+ * out[b,:3,:] = R[b] @ pc[obj_of_row[b],:3,:] + t ; extra channels copied.  The arithmetic per component is
+ * dvq_transform_cloud's in the same order, so row b holds the bits that call writes for object obj_of_row[b] and rotation
+ * R[b]; the object clouds are not replicated per grasp.  One workgroup per (row, span of points) reads the row's index, matrix
+ * and `t` once; loads and stores are 16 bytes wide when N % 4 == 0 and `pc` / `out` are 16-byte aligned, any other N takes a
+ * scalar path.  An index outside [0, O) sets bit 0 of *err_flag (device int32, zeroed by the caller) and leaves that row of
+ * `out` unwritten. */
+int dvq_transform_clouds(const float* pc /* [O,C,N] */, const int64_t* obj_of_row /* device [B] */, int64_t O,
+                         const float* R /* [B,3,3] */, const float* t /* [3] or NULL */, int64_t B, int C, int N,
+                         float* out /* [B,C,N] */, int32_t* err_flag, dvq_stream_t stream);
 
 /* ------------------------------------------------------------------ sampling noise of the prior
  * GatedPixelCNN.generate draws with probs.multinomial(1) (network/pixelcnn/models.py:190-197), i.e. argmax_k p_k / q_k with
@@ -299,6 +310,14 @@ int dvq_exp1_noise(uint64_t seed, uint32_t stream_id, int64_t row0, int64_t rows
  * gather of the whole [B, 9 * 512] tensor. */
 int dvq_exp1_noise_rows(uint64_t seed, uint32_t stream_id, int64_t row0, const int64_t* perm, int64_t rows, int cols,
                         float* out /* [rows,cols] */, dvq_stream_t stream);
+/* Per-row keys: out[r, :] = exactly what dvq_exp1_noise(seed, stream_ids[r], row_ids[r], 1, cols, ...) writes (same counter,
+ * key and -logf expression: the two kernels share one device function), so a call that mixes the grasps of many objects draws,
+ * for every grasp, the noise of its own (seed, object, grasp index) -- what the per-object loops of
+ * gen_diverse_grasp_ho3d.py:205-248 / gen_diverse_grasp_obman.py:233-247 draw one object at a time.  A stream id outside
+ * [0, 2^32) or a negative row id sets bit 0 of *err_flag (device int32, zeroed by the caller) and fills that row with NaN.
+ * cols % 4 == 0. */
+int dvq_exp1_noise_keyed(uint64_t seed, const int64_t* stream_ids /* device [rows] */, const int64_t* row_ids /* device [rows] */,
+                         int64_t rows, int cols, float* out /* [rows,cols] */, int32_t* err_flag, dvq_stream_t stream);
 
 /* Self-test: out[0] (device) = an fp16 MFMA product with a SUBNORMAL input, out[1] = its exact value.  The fast VQ kernel's
  * error bound assumes the matrix core keeps fp16 subnormals (measured so on gfx950); tests assert out[0] == out[1]. */
