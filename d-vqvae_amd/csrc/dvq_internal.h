@@ -8,14 +8,11 @@
 #include <mutex>
 #include "../../include/dvq.h"
 
-// Diagnostics build (make EXTRA=-DDVQ_DIAG): timing-only ablation variants (DVQ_VQ16_ABL, DVQ_PN_ABL, DVQ_GEMM_ABL: results
+// Diagnostics build (make diag, -DDVQ_DIAG): timing-only ablation variants (DVQ_VQ16_ABL, DVQ_PN_ABL, DVQ_GEMM_ABL: results
 // INVALID), phase stamps (DVQ_VQ16_DBG, DVQ_GEMM_CLK) and the DVQ_GEMM_NODMA switch exist only there.  The shipped library
 // never reads those variables: a stray one in the environment cannot change a result.
 #ifdef DVQ_DIAG
 #define DVQ_DIAG_ON 1
-#ifndef DVQ_GEMM_DIAG
-#define DVQ_GEMM_DIAG
-#endif
 #else
 #define DVQ_DIAG_ON 0
 #endif
@@ -209,16 +206,14 @@ int dvq_launch_gemm_f16x2_gate_group(const GemmParams* ps, int n, hipStream_t st
 // 0 = fp32 MFMA (v_mfma_f32_32x32x2_f32), 1 = split-bf16 (default); env DVQ_GEMM=fp32|bf16x3
 int dvq_gemm_mode();
 
-// Behaviour knobs read from the environment ONCE (first use) -- DVQ_GEMM_WIDE, DVQ_GEMM_DEPHASE, DVQ_GEMM_SKINNY, DVQ_PN_FILTER, DVQ_PN_EXHAUSTIVE,
+// Behaviour knobs read from the environment ONCE (first use) -- DVQ_GEMM_WIDE, DVQ_GEMM_DEPHASE, DVQ_GEMM_TN, DVQ_GEMM_SKINNY, DVQ_PN_FILTER, DVQ_PN_EXHAUSTIVE,
 // DVQ_PN_CAPS, DVQ_PN_CHUNK, DVQ_PN_STATS, DVQ_PIXELCNN_CHUNK -- none of them changes a result (tile shapes, chunk sizes, the
 // exhaustive PointNet evaluation the filter is tested against).  dvq_reload_env() re-reads them (tests flip them in-process).
 struct DvqKnobs {
     int gemm_wide;        // 0: 128 x 128 kernels only
-    int gemm_dephase;
+    int gemm_dephase;     // 0: the wide bf16x3 kernel's lock-step schedule (DVQ_GEMM_DEPHASE=0; launch_wide only)
     int gemm_tn;          // 0 (default): the tiled f16x2 kernel picks 128 x 256 or 128 x 128 tiles per launch; 128 / 256 force one (DVQ_GEMM_TN)
-    int gemm_skinny_prefetch;   // 0: no helper workgroups (DVQ_GEMM_SKINNY_PREFETCH=0)
     int gemm_skinny;      // 0: tiled kernels also for M <= 256 (DVQ_GEMM_SKINNY=0; the two must agree bitwise)
-    int gemm_skinny_cols; // f16x2 skinny kernel: output columns per wave, 16 / 8 / 4 (DVQ_GEMM_SKINNY_COLS; 0 = by the launch's size; same bits)
     int pn_filter;        // 0 six-product trunk, 1 default, 2 filtered trunk whatever the tile fill
     int pn_tail;          // 1 (default): a cloud's 1 .. 32 points beyond a multiple of 256 as a one-block tail tile (DVQ_PN_TAIL=0: a full tile)
     int pn_exhaustive;    // 1: exact stage evaluates every point (what the filter must reproduce bit for bit)

@@ -20,9 +20,9 @@
 #include "gemm_common.h"
 #include <vector>
 
-// Diagnostics (per-block phase stamps, loop ablations: tools/gemm_phase_stamps.py) are compiled in only with
-// -DDVQ_GEMM_DIAG (make EXTRA=-DDVQ_GEMM_DIAG): in the shipped build the predicates below are constant false.
-#ifdef DVQ_GEMM_DIAG
+// Diagnostics (per-block phase stamps, loop ablations: tools/gemm_phase_stamps.py) are compiled in only with -DDVQ_DIAG
+// (make diag): in the shipped build the predicates below are constant false.
+#ifdef DVQ_DIAG
 #define DVQ_ABL_IS(p, v) ((p).dbg_abl == (v))
 #define DVQ_CLK(p) ((p).dbg_clk)
 #else
@@ -444,32 +444,19 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16x3_dma_kernel(const GemmParam
 template <int EPI>
 int launch_dma(const GemmParams& p, hipStream_t stream) {
     static DvqOncePerDevice attr_once;
-    {
-        const hipError_t e = attr_once.run([] {
-            return hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_bf16x3_dma_kernel<EPI>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)D_SMEM);
-        });
-        if (e != hipSuccess) {
-            dvq_set_error("gemm_bf16x3: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
-            return DVQ_ELAUNCH;
-        }
-    }
-    const long tiles_m = (p.M + BM - 1) / BM;
-    const long tiles_n = (p.N + BN - 1) / BN;
-    const long grid = ((tiles_m + 7) / 8) * 8 * tiles_n;
-    static const char* const names[] = {"gemm_bias", "gemm_resid", "gemm_gate", "gemm_colmax", "gemm_argmin"};
-    double ksum = 0;
-    for (int s = 0; s < p.nsrc; ++s) ksum += p.src[s].K;
+    DVQ_PROPAGATE(gemm_lds_limit(attr_once, reinterpret_cast<const void*>(&gemm_bf16x3_dma_kernel<EPI>), D_SMEM, "gemm_bf16x3"));
+    const long grid = gemm_padded_grid((p.M + BM - 1) / BM, (p.N + BN - 1) / BN);
+    const double ksum = gemm_ksum(p);
     static unsigned long long* clk_buf = nullptr;
     GemmParams q = p;
-#ifdef DVQ_GEMM_DIAG
+#ifdef DVQ_DIAG
     if (getenv("DVQ_GEMM_CLK")) {
         if (!clk_buf) (void)hipMalloc(&clk_buf, 64 + 32 * 65536);
         q.dbg_clk = clk_buf;
     }
 #endif
     {
-        DVQ_PROF(names[EPI], 2.0 * (double)p.M * p.N * ksum, ((double)p.M + p.N) * ksum * 4, stream);
+        DVQ_PROF(gemm_prof_name(EPI, 0), 2.0 * (double)p.M * p.N * ksum, ((double)p.M + p.N) * ksum * 4, stream);
         DVQ_LAUNCH((gemm_bf16x3_dma_kernel<EPI>), dim3((unsigned)grid), dim3(256), D_SMEM, stream, q);
     }
     if (q.dbg_clk) {
@@ -662,29 +649,17 @@ __global__ __launch_bounds__(512, 1) void gemm_bf16x3_wide_kernel(const GemmPara
 
 template <int EPI>
 int launch_wide(const GemmParams& p, hipStream_t stream) {
-    static DvqOncePerDevice attr_once;
+    // DVQ_GEMM_DEPHASE=0: the lock-step schedule (every wave feeds the next stage at the top of the tile)
+    const bool dephase = dvq_knobs().gemm_dephase != 0;
+    static DvqOncePerDevice attr_once[2];
+    const void* const kernel = dephase ? reinterpret_cast<const void*>(&gemm_bf16x3_wide_kernel<EPI, true>)
+                                       : reinterpret_cast<const void*>(&gemm_bf16x3_wide_kernel<EPI, false>);
+    DVQ_PROPAGATE(gemm_lds_limit(attr_once[dephase], kernel, W_SMEM, "gemm_bf16x3"));
+    const long grid = gemm_padded_grid((p.M + 127) / 128, p.N / 256);
+    const double ksum = gemm_ksum(p);
     {
-        const hipError_t e = attr_once.run([] {
-            const hipError_t e0 = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_bf16x3_wide_kernel<EPI, false>),
-                                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)W_SMEM);
-            const hipError_t e1 = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_bf16x3_wide_kernel<EPI, true>),
-                                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)W_SMEM);
-            return e0 != hipSuccess ? e0 : e1;
-        });
-        if (e != hipSuccess) {
-            dvq_set_error("gemm_bf16x3: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
-            return DVQ_ELAUNCH;
-        }
-    }
-    const long tiles_m = (p.M + 127) / 128;
-    const long tiles_n = p.N / 256;
-    const long grid = ((tiles_m + 7) / 8) * 8 * tiles_n;
-    static const char* const names[] = {"gemm_bias", "gemm_resid", "gemm_gate"};
-    double ksum = 0;
-    for (int s = 0; s < p.nsrc; ++s) ksum += p.src[s].K;
-    {
-        DVQ_PROF(names[EPI], 2.0 * (double)p.M * p.N * ksum, ((double)p.M + p.N) * ksum * 4, stream);
-        if (dvq_knobs().gemm_dephase) DVQ_LAUNCH((gemm_bf16x3_wide_kernel<EPI, true>), dim3((unsigned)grid), dim3(512), W_SMEM, stream, p);
+        DVQ_PROF(gemm_prof_name(EPI, 0), 2.0 * (double)p.M * p.N * ksum, ((double)p.M + p.N) * ksum * 4, stream);
+        if (dephase) DVQ_LAUNCH((gemm_bf16x3_wide_kernel<EPI, true>), dim3((unsigned)grid), dim3(512), W_SMEM, stream, p);
         else DVQ_LAUNCH((gemm_bf16x3_wide_kernel<EPI, false>), dim3((unsigned)grid), dim3(512), W_SMEM, stream, p);
     }
     DVQ_CHECK_LAUNCH("gemm_bf16x3_wide");
@@ -692,138 +667,46 @@ int launch_wide(const GemmParams& p, hipStream_t stream) {
 }
 
 // ================================================================================================================
-// Skinny variant for small M (the reference's own call pattern: GenNet.gen with B = 1 per call, 1 / 20 / 49 / 100 grasps per
+// Skinny kernel for small M (the reference's own call pattern: GenNet.gen with B = 1 per call, 1 / 20 / 49 / 100 grasps per
 // object, gen_diverse_grasp_ho3d.py:212-236).  With M <= 128 the tiled kernels above run one workgroup per 128 or 256 output
 // columns, each streaming its whole weight panel through ONE CU (125 us per gated GEMM at M = 1: 4 workgroups busy).  Here every
-// WAVE owns one 32 x 32 output block over the full K: weights go global -> registers (three bf16 planes), the activation
-// fragment is split in registers, and the six partial products run in EXACTLY the order of the tiled kernels -- the same MFMA
-// sequence on the same operands, so the result is bit-identical to the batched path (tests: skinny == tiled bitwise, gen
-// batched == loop of B = 1 calls).  A workgroup is two waves: two adjacent column blocks, which for the gate epilogue are a
-// tanh block and its sigmoid partner (exchanged through 4 KB of LDS).  Grid = (N / 64) x (M / 32) workgroups.
+// multiplying WAVE owns one 32 x 32 output block over the full K, and the six partial products run in EXACTLY the order of the
+// tiled kernels -- the same MFMA sequence on the same operands, so the result is bit-identical to the batched path (tests: skinny
+// == tiled bitwise, gen batched == loop of B = 1 calls).  A workgroup multiplies two adjacent column blocks, which for the gate
+// epilogue are a tanh block and its sigmoid partner (exchanged through 4 KB of LDS).  Grid = (N / 64) x (M / 32) workgroups.
 //
-// Loads are shaped in whole 128-byte lines: a lane (row r, half h) fetches 64 contiguous bytes of its weight row per plane
-// (four k-steps of 16) and 128 bytes of its activation row with back-to-back 16-byte loads, so every line is touched by
-// consecutive instructions and crosses L2 -> L1 once.  The 16-byte pieces then sit in the wrong lane half for two of the four
-// k-steps; v_permlane32_swap puts them where the MFMA operand layout wants them (lane half h <-> k = 8h .. 8h+7).
-// Measured (tools/gemm_skinny_bench.py, M = 1, N = 1024, K = 2048, launches issued from Python): 30.5 us against 125 us for
-// the tiled kernel, the same on L2-warm and on rotating panels (not memory-bound: a k-step costs ~370 cycles -- six dependent
-// MFMAs = 192, and ~55 vector instructions (split 44, swaps 10) that the in-order wave issues between them).  Tried: one
-// k-step per load (32 bytes of each of 32 lines per instruction: 4x the L1 fill traffic, 590 cycles per k-step), 12 k-steps
-// in flight (no change), four waves sharing the split through the LDS with a barrier per chunk (49.8 us: the round trip
-// serialises), prefetch helper workgroups sweeping the panel into the Infinity Cache (-7 %, kept).
-struct SkinnyChunk {
-    uint4 w[3][4];      // after load: piece 4h+q of the row's 128 bytes; after fix(): [0],[2],[1],[3] = k-steps 0,1,2,3
-    f32x4 a[8];         // after load: piece 8h+q of the row's 256 bytes; after fix(): (a[0],a[1]),(a[4],a[5]),(a[2],a[3]),(a[6],a[7])
-};
+// Both operands are staged through the LDS in chunks of 64 k (four k-steps of 16), with COALESCED loads: eight lanes per
+// 128-byte weight line, sixteen per 256 bytes of an activation row.  Why: the first version (rounds 2-3)
+// went global -> registers, a lane (row r, half h) fetching 64 contiguous bytes of its weight row per plane and 128
+// bytes of its activation row with back-to-back 16-byte loads, v_permlane32_swap putting the pieces into the lane half the MFMA
+// operand layout wants, the split of the next k-step's fragment placed in the gaps of the MFMA chain.  It measured
+// (tools/gemm_skinny_bench.py, M = 1, N = 1024, K = 2048, launches issued from Python) 30.5 us against 125 us for the tiled
+// kernel, the same on L2-warm and on rotating panels (not memory-bound: a k-step cost ~370 cycles -- six dependent MFMAs = 192,
+// and ~55 vector instructions (split 44, swaps 10) that the in-order wave issues between them).  But every one of its load
+// instructions touched 32 different lines: 640 line accesses per 64-k chunk and wave, 1 280 per CU -- and a chunk took 4 x 320 =
+// 1 280 cycles whatever the split arithmetic or the prefetch depth: one cache line per clock, the vector memory path's tag
+// rate.  Coalescing makes 4x fewer line accesses; in the step's per-launch breakdown the register version took 14.5 us mean per
+// launch, this one 11.0 us.  Also tried on the register version: one k-step per load (32 bytes of each of 32 lines per
+// instruction: 4x the L1 fill traffic, 590 cycles per k-step), 12 k-steps in flight (no change), four waves sharing the split
+// through the LDS with a barrier per chunk (49.8 us: the round trip serialises), prefetch helper workgroups sweeping the panel
+// into the Infinity Cache (-7 %, kept: skinny_prefetch).
+//
+// The LDS reads produce the MFMA operand layout (conflict-free through an XOR of the 16-byte piece index with (row >> 1) & 7).
+// Weights: private to the column block that multiplies them (source-side swizzle, lane-linear writes).  Activations: the two
+// column blocks of the workgroup multiply the SAME rows, so each block's staging waves load and split half of the chunk (16 rows)
+// into bf16 planes in a shared slot -- half the split arithmetic per block, none in the MFMA loop -- with one barrier per chunk.
+// A single in-order wave per SIMD can issue ~48 instructions in the 192 cycles of a k-step's six dependent MFMAs: the loop has
+// 6 MFMAs + 6 LDS reads per k-step and ~35 more per k-step for the next chunk.
 
-__device__ __forceinline__ void swap_halves(uint4& x, uint4& y) {      // x.hi <-> y.lo (per dword)
-    unsigned* px = reinterpret_cast<unsigned*>(&x);
-    unsigned* py = reinterpret_cast<unsigned*>(&y);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const auto r = __builtin_amdgcn_permlane32_swap(px[i], py[i], false, false);
-        px[i] = r[0];
-        py[i] = r[1];
-    }
-}
-__device__ __forceinline__ void swap_halves(f32x4& x, f32x4& y) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(x[i]), __float_as_uint(y[i]), false, false);
-        x[i] = __uint_as_float(r[0]);
-        y[i] = __uint_as_float(r[1]);
-    }
-}
-
-struct SkinnyCursor {
-    int s, k_left;
-    const float* a_ptr;
-    const uint16_t* w_ptr[3];
-
-    __device__ __forceinline__ void open(const GemmParams& p, int src_i, long m, int n, int h) {
-        s = src_i;
-        if (s >= p.nsrc) { k_left = 0; return; }
-        const GemmSrc& src = p.src[s];
-        k_left = src.K;
-        a_ptr = src.A + m * src.lda + 32 * h;
-#pragma unroll
-        for (int pl = 0; pl < 3; ++pl) w_ptr[pl] = src.Wp + pl * src.wp_plane + (long)n * src.ldw + 32 * h;
-    }
-    __device__ __forceinline__ void load(const GemmParams& p, long m, int n, int h, SkinnyChunk& t) {
-#pragma unroll
-        for (int pl = 0; pl < 3; ++pl) {
-#pragma unroll
-            for (int q = 0; q < 4; ++q) t.w[pl][q] = *reinterpret_cast<const uint4*>(w_ptr[pl] + 8 * q);
-            w_ptr[pl] += 64;
-        }
-#pragma unroll
-        for (int q = 0; q < 8; ++q) t.a[q] = *reinterpret_cast<const f32x4*>(a_ptr + 4 * q);
-        a_ptr += 64;
-        k_left -= 64;
-        if (k_left <= 0) open(p, s + 1, m, n, h);
-    }
-};
-
-__device__ __forceinline__ void skinny_fix(SkinnyChunk& t) {
-#pragma unroll
-    for (int pl = 0; pl < 3; ++pl) {
-        swap_halves(t.w[pl][0], t.w[pl][1]);     // -> k-steps 0 and 2
-        swap_halves(t.w[pl][2], t.w[pl][3]);     // -> k-steps 1 and 3
-    }
-    swap_halves(t.a[0], t.a[2]);                 // -> k-step 0 low, k-step 2 low
-    swap_halves(t.a[1], t.a[3]);
-    swap_halves(t.a[4], t.a[6]);                 // -> k-step 1 low, k-step 3 low
-    swap_halves(t.a[5], t.a[7]);
-}
-
+// the six partial products of one k-step in the tiled kernels' order (weights as operand A)
 __device__ __forceinline__ void skinny_mfma(const uint4& u0, const uint4& u1, const uint4& u2, const bf16x8 (&a)[3], f32x16& c) {
     const bf16x8 w0 = __builtin_bit_cast(bf16x8, u0), w1 = __builtin_bit_cast(bf16x8, u1), w2 = __builtin_bit_cast(bf16x8, u2);
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w0, a[2], c, 0, 0, 0);       // the tiled kernels' order (weights as operand A)
+    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w0, a[2], c, 0, 0, 0);
     c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w2, a[0], c, 0, 0, 0);
     c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w1, a[1], c, 0, 0, 0);
     c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w0, a[1], c, 0, 0, 0);
     c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w1, a[0], c, 0, 0, 0);
     c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w0, a[0], c, 0, 0, 0);
-}
-// one dependent chain of six MFMAs; the in-order wave issues nothing between them unless it is PLACED there: the split of the
-// next k-step's activation fragment (44 vector instructions) goes into the six gaps, 1 MFMA : 8 VALU
-#define DVQ_SK_INTERLEAVE()                                           \
-    _Pragma("unroll") for (int i_ = 0; i_ < 6; ++i_) {                \
-        __builtin_amdgcn_sched_group_barrier(0x8, 1, 0);              \
-        __builtin_amdgcn_sched_group_barrier(0x2, 8, 0);              \
-    }
-// four k-steps of a chunk, in k order; `a0` = the split fragment of its first k-step (prepared under the previous chunk's last
-// MFMAs), `next` = the chunk that follows (its lane fix-up and first split are prepared under this chunk's last MFMAs)
-__device__ __forceinline__ void skinny_chunk(SkinnyChunk& t, SkinnyChunk& next, bf16x8 (&a0)[3], f32x16& c) {
-    bf16x8 a1[3], a2[3], a3[3];
-    split_frag(t.a[4], t.a[5], a1);
-    skinny_mfma(t.w[0][0], t.w[1][0], t.w[2][0], a0, c);
-    DVQ_SK_INTERLEAVE();
-    split_frag(t.a[2], t.a[3], a2);
-    skinny_mfma(t.w[0][2], t.w[1][2], t.w[2][2], a1, c);
-    DVQ_SK_INTERLEAVE();
-    split_frag(t.a[6], t.a[7], a3);
-    skinny_mfma(t.w[0][1], t.w[1][1], t.w[2][1], a2, c);
-    DVQ_SK_INTERLEAVE();
-    skinny_fix(next);
-    split_frag(next.a[0], next.a[1], a0);
-    skinny_mfma(t.w[0][3], t.w[1][3], t.w[2][3], a3, c);
-#pragma unroll
-    for (int i_ = 0; i_ < 6; ++i_) {
-        __builtin_amdgcn_sched_group_barrier(0x8, 1, 0);
-        __builtin_amdgcn_sched_group_barrier(0x2, 14, 0);
-    }
-}
-// the same without a successor
-__device__ __forceinline__ void skinny_chunk_last(SkinnyChunk& t, bf16x8 (&a0)[3], f32x16& c) {
-    bf16x8 a1[3], a2[3], a3[3];
-    split_frag(t.a[4], t.a[5], a1);
-    skinny_mfma(t.w[0][0], t.w[1][0], t.w[2][0], a0, c);
-    split_frag(t.a[2], t.a[3], a2);
-    skinny_mfma(t.w[0][2], t.w[1][2], t.w[2][2], a1, c);
-    split_frag(t.a[6], t.a[7], a3);
-    skinny_mfma(t.w[0][1], t.w[1][1], t.w[2][1], a2, c);
-    skinny_mfma(t.w[0][3], t.w[1][3], t.w[2][3], a3, c);
 }
 
 // Helper workgroups (blockIdx.x >= n_work): a gated GEMM at M <= 32 occupies 16 of the 256 CUs.  The idle CUs sweep the launch's
@@ -851,7 +734,7 @@ __device__ __forceinline__ void skinny_prefetch(const GemmParams& p, int helper,
     if (sink == 0x9e3779b9u && p.M < 0) p.out[0] = 0.f;                   // never true: keeps the loads alive
 }
 
-// Epilogues of the skinny kernels: lane <-> row m, registers 4g..4g+3 <-> four consecutive columns nb0 + 8g + 4h (gemm_common.h,
+// Epilogues of the skinny kernel: lane <-> row m, registers 4g..4g+3 <-> four consecutive columns nb0 + 8g + 4h (gemm_common.h,
 // gemm_epilogue_t_at: the same arithmetic in the same order).  `xch`: 4 KB of LDS for the gate's tanh / sigmoid exchange.
 template <int EPI>
 __device__ __forceinline__ void skinny_epilogue(const GemmParams& p, const f32x16& c, float* xch, long m0, int n0, int nb0, int r, int h,
@@ -919,80 +802,7 @@ __device__ __forceinline__ void skinny_epilogue(const GemmParams& p, const f32x1
     }
 }
 
-template <int EPI>
-__global__ __launch_bounds__(128) void gemm_bf16x3_skinny_kernel(const GemmParams p, int n_col_wgs, int n_work) {
-    __shared__ __attribute__((aligned(16))) float xch[64 * 16];          // gate: the sigmoid block's 16 values per lane
-    const int tid = threadIdx.x;
-    if ((int)blockIdx.x >= n_work) {
-        skinny_prefetch(p, (int)blockIdx.x - n_work, (int)gridDim.x - n_work, tid);
-        return;
-    }
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int r = lane & 31, h = lane >> 5;
-    const long m0 = (long)((int)blockIdx.x / n_col_wgs) * 32;
-    const int n0 = ((int)blockIdx.x % n_col_wgs) * 64;                   // two 32-column blocks per workgroup
-    const int nb0 = n0 + 32 * wave;                                      // this wave's block
-    long m = m0 + r;
-    const bool m_ok = m < p.M;
-    if (!m_ok) m = p.M - 1;                                              // clamped rows / columns only feed masked outputs
-    int nrow = nb0 + r;
-    if (nrow >= p.N) nrow = p.N - 1;
-
-    f32x16 c;
-#pragma unroll
-    for (int e = 0; e < 16; ++e) c[e] = 0.f;
-    SkinnyCursor cur;
-    cur.open(p, 0, m, nrow, h);
-    // two chunks (eight k-steps) in flight behind the one being multiplied; every K is a multiple of 64 here (launch check).
-    // The steady state has no branch around a load: with one the compiler's wait insertion falls back to vmcnt(0) before every
-    // use, i.e. one full memory latency per chunk.
-    int chunks = 0;
-    for (int s2 = 0; s2 < p.nsrc; ++s2) chunks += p.src[s2].K >> 6;
-    SkinnyChunk q0, q1, q2;
-    bf16x8 a0[3];
-    if (chunks >= 3) {
-        cur.load(p, m, nrow, h, q0);
-        cur.load(p, m, nrow, h, q1);
-        cur.load(p, m, nrow, h, q2);
-        skinny_fix(q0);
-        split_frag(q0.a[0], q0.a[1], a0);
-        int t = 0;
-        for (; t + 6 <= chunks; t += 3) {
-            // q0's successor q1 is already in flight; q0 itself is re-loaded only AFTER q1's fix-up has read ... nothing of q0
-            skinny_chunk(q0, q1, a0, c); cur.load(p, m, nrow, h, q0);
-            skinny_chunk(q1, q2, a0, c); cur.load(p, m, nrow, h, q1);
-            // q2's successor is the q0 just loaded: its fix-up waits for that load (two chunks of MFMAs behind it)
-            skinny_chunk(q2, q0, a0, c); cur.load(p, m, nrow, h, q2);
-        }
-        const int rem = chunks - t - 3;                                  // 0 .. 2 chunks not yet loaded; q0 is fixed and split
-        skinny_chunk(q0, q1, a0, c); if (rem > 0) cur.load(p, m, nrow, h, q0);
-        skinny_chunk(q1, q2, a0, c); if (rem > 1) cur.load(p, m, nrow, h, q1);
-        if (rem > 0) {
-            skinny_chunk(q2, q0, a0, c);
-            if (rem > 1) { skinny_chunk(q0, q1, a0, c); skinny_chunk_last(q1, a0, c); }
-            else skinny_chunk_last(q0, a0, c);
-        } else skinny_chunk_last(q2, a0, c);
-    } else {
-        if (chunks > 0) cur.load(p, m, nrow, h, q0);
-        if (chunks > 1) cur.load(p, m, nrow, h, q1);
-        if (chunks > 0) { skinny_fix(q0); split_frag(q0.a[0], q0.a[1], a0); }
-        if (chunks > 1) { skinny_chunk(q0, q1, a0, c); skinny_chunk_last(q1, a0, c); }
-        else if (chunks > 0) skinny_chunk_last(q0, a0, c);
-    }
-    skinny_epilogue<EPI>(p, c, xch, m0, n0, nb0, r, h, lane, wave, m_ok);
-}
-
-// ---- LDS-staged variant (round 3).  The register variant above fetches a lane's 128-byte line in four 16-byte pieces with four
-// instructions, each touching 32 different lines: 640 line accesses per 64-k chunk and wave, 1 280 per CU -- and a chunk took
-// 4 x 320 = 1 280 cycles whatever the split arithmetic or the prefetch depth: one cache line per clock, the vector memory
-// path's tag rate.  Here the loads are COALESCED (eight lanes per weight line, sixteen per activation row: 4x fewer line
-// accesses) and go through the LDS, whose reads produce the MFMA operand layout (conflict-free through an XOR of the 16-byte
-// piece index with (row >> 1) & 7).  Weights: private to the wave that multiplies them (source-side swizzle, lane-linear
-// writes, no synchronisation).  Activations: the two waves of the workgroup multiply the SAME rows, so each loads and splits
-// half of the chunk (16 rows) into bf16 planes in a shared slot -- half the split arithmetic per wave, none in the MFMA
-// loop -- with one two-wave barrier per chunk.  A single in-order wave per SIMD can issue ~48 instructions in the 192 cycles of
-// a k-step's six dependent MFMAs: the loop has 6 MFMAs + 6 LDS reads per k-step and ~35 more per k-step for the next chunk.
+// ---- staging through the LDS
 typedef unsigned sk2_u4 __attribute__((ext_vector_type(4)));   // a native vector (HIP's uint4 is a struct: its copies become memcpy calls
 typedef unsigned sk2_u2 __attribute__((ext_vector_type(2)));   // that keep a load -> LDS-store buffer in scratch memory)
 constexpr int SK2_PL = 32 * 128;                            // one plane of one operand: 32 rows x 64 k bf16
@@ -1093,19 +903,6 @@ __device__ __forceinline__ void sk2_mfma(const Sk2Frag& f, f32x16& c) {
     const bf16x8 a[3] = {__builtin_bit_cast(bf16x8, f.a[0]), __builtin_bit_cast(bf16x8, f.a[1]), __builtin_bit_cast(bf16x8, f.a[2])};
     skinny_mfma(__builtin_bit_cast(uint4, f.w[0]), __builtin_bit_cast(uint4, f.w[1]), __builtin_bit_cast(uint4, f.w[2]), a, c);
 }
-// the four k-steps of one chunk; the reads of k-step j + 1 are issued before the six MFMAs of k-step j
-__device__ __forceinline__ void sk2_chunk(const char* wslot, const char* aslot, int r, int h, f32x16& c) {
-    Sk2Frag f0, f1;
-    sk2_read(wslot, aslot, 0, r, h, f0);
-    sk2_read(wslot, aslot, 1, r, h, f1);
-    sk2_mfma(f0, c);
-    sk2_read(wslot, aslot, 2, r, h, f0);
-    sk2_mfma(f1, c);
-    sk2_read(wslot, aslot, 3, r, h, f1);
-    sk2_mfma(f0, c);
-    sk2_mfma(f1, c);
-}
-
 template <int EPI>
 __global__ __launch_bounds__(128 + 128 * SK2_NP) void gemm_bf16x3_skinny2_kernel(const GemmParams p, int n_col_wgs, int n_work) {
     extern __shared__ __attribute__((aligned(16))) char sk2_smem[];
@@ -1217,29 +1014,16 @@ constexpr long SKINNY_MAX_M = 256;     // above this the tiled kernels win (ever
 
 template <int EPI>
 int launch_skinny(const GemmParams& p, hipStream_t stream) {
-    static const char* const names[] = {"gemm_bias", "gemm_resid", "gemm_gate"};
-    double ksum = 0;
-    for (int s = 0; s < p.nsrc; ++s) ksum += p.src[s].K;
+    static DvqOncePerDevice attr_once;
+    DVQ_PROPAGATE(gemm_lds_limit(attr_once, reinterpret_cast<const void*>(&gemm_bf16x3_skinny2_kernel<EPI>), SK2_SMEM, "gemm_bf16x3"));
+    const double ksum = gemm_ksum(p);
     {
-        DVQ_PROF(names[EPI], 2.0 * (double)p.M * p.N * ksum, ((double)p.M + p.N) * ksum * 4, stream);
+        DVQ_PROF(gemm_prof_name(EPI, 0), 2.0 * (double)p.M * p.N * ksum, ((double)p.M + p.N) * ksum * 4, stream);
         const int n_col = (int)((p.N + 63) / 64), n_work = n_col * (int)((p.M + 31) / 32);
         // helpers only where most of the chip would idle AND the panel is worth it (>= 1 MB of planes)
         const bool big = 6.0 * p.N * ksum >= 1.0e6;
-        const int helpers = (dvq_knobs().gemm_skinny_prefetch && big && n_work <= 64) ? 192 : 0;
-        if (dvq_knobs().gemm_skinny == 2) {                               // the register-staged variant (A/B runs)
-            DVQ_LAUNCH((gemm_bf16x3_skinny_kernel<EPI>), dim3((unsigned)(n_work + helpers)), dim3(128), 0, stream, p, n_col, n_work);
-        } else {
-            static DvqOncePerDevice attr_once;
-            const hipError_t e = attr_once.run([] {
-                return hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_bf16x3_skinny2_kernel<EPI>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, SK2_SMEM);
-            });
-            if (e != hipSuccess) {
-                dvq_set_error("gemm_bf16x3: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
-                return DVQ_ELAUNCH;
-            }
-            DVQ_LAUNCH((gemm_bf16x3_skinny2_kernel<EPI>), dim3((unsigned)(n_work + helpers)), dim3(128 + 128 * SK2_NP), SK2_SMEM, stream, p, n_col, n_work);
-        }
+        const int helpers = (big && n_work <= 64) ? 192 : 0;
+        DVQ_LAUNCH((gemm_bf16x3_skinny2_kernel<EPI>), dim3((unsigned)(n_work + helpers)), dim3(128 + 128 * SK2_NP), SK2_SMEM, stream, p, n_col, n_work);
     }
     DVQ_CHECK_LAUNCH("gemm_bf16x3_skinny");
     return DVQ_OK;
@@ -1261,24 +1045,11 @@ __global__ void split_bf16x3_kernel(const float* __restrict__ w, long n, uint16_
 template <int EPI, bool WPLANES>
 int launch(const GemmParams& p, hipStream_t stream) {
     static DvqOncePerDevice attr_once;
+    DVQ_PROPAGATE(gemm_lds_limit(attr_once, reinterpret_cast<const void*>(&gemm_bf16x3_kernel<EPI, WPLANES>), SMEM_BYTES, "gemm_bf16x3"));
+    const long grid = gemm_padded_grid((p.M + BM - 1) / BM, (p.N + BN - 1) / BN);
+    const double ksum = gemm_ksum(p);
     {
-        const hipError_t e = attr_once.run([] {
-            return hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_bf16x3_kernel<EPI, WPLANES>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)SMEM_BYTES);
-        });
-        if (e != hipSuccess) {
-            dvq_set_error("gemm_bf16x3: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
-            return DVQ_ELAUNCH;
-        }
-    }
-    const long tiles_m = (p.M + BM - 1) / BM;
-    const long tiles_n = (p.N + BN - 1) / BN;
-    const long grid = ((tiles_m + 7) / 8) * 8 * tiles_n;
-    static const char* const names[] = {"gemm_bias", "gemm_resid", "gemm_gate", "gemm_colmax", "gemm_argmin"};
-    double ksum = 0;
-    for (int s = 0; s < p.nsrc; ++s) ksum += p.src[s].K;
-    {
-        DVQ_PROF(names[EPI], 2.0 * (double)p.M * p.N * ksum, ((double)p.M + p.N) * ksum * 4, stream);
+        DVQ_PROF(gemm_prof_name(EPI, 0), 2.0 * (double)p.M * p.N * ksum, ((double)p.M + p.N) * ksum * 4, stream);
         DVQ_LAUNCH((gemm_bf16x3_kernel<EPI, WPLANES>), dim3((unsigned)grid), dim3(256), SMEM_BYTES, stream, p);
     }
     DVQ_CHECK_LAUNCH("gemm_bf16x3");
@@ -1289,7 +1060,7 @@ int launch(const GemmParams& p, hipStream_t stream) {
 
 // Called by dvq_launch_gemm (gemm_f32.hip) after argument validation.  K of every source must be a multiple of 16.
 int dvq_launch_gemm_bf16x3(const GemmParams& p, GemmEpilogue epi, hipStream_t stream) {
-#ifdef DVQ_GEMM_DIAG
+#ifdef DVQ_DIAG
     if (const char* e = getenv("DVQ_GEMM_ABL")) const_cast<GemmParams&>(p).dbg_abl = atoi(e);
     static const bool use_dma = !(getenv("DVQ_GEMM_NODMA") && getenv("DVQ_GEMM_NODMA")[0] == '1');
 #else

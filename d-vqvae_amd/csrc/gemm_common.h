@@ -208,3 +208,42 @@ __device__ __forceinline__ void gemm_epilogue_t_at(const GemmParams& p, f32x16 (
         }
     }
 }
+
+// ---------------------------------------------------------------------------------------------------------------
+// Host side: what the launchers of gemm_f32.hip, gemm_bf16x3.hip and gemm_f16x2.hip share.
+
+// K summed over the launch's sources (the launch's FLOPs are 2 M N ksum)
+static inline double gemm_ksum(const GemmParams& p) {
+    double ksum = 0;
+    for (int s = 0; s < p.nsrc; ++s) ksum += p.src[s].K;
+    return ksum;
+}
+// ... and its K-tiles of `bk` (every K is a multiple of bk: check_gemm)
+static inline int gemm_ktiles(const GemmParams& p, int bk) {
+    int t = 0;
+    for (int s = 0; s < p.nsrc; ++s) t += p.src[s].K / bk;
+    return t;
+}
+
+// Kind of a launch in the per-launch breakdown (dvq_prof_read; bench.py keys on these strings).  prof_cls: a launch on a class
+// table's rows, told apart by the fp16-plane launchers only (the others pass 0).
+static inline const char* gemm_prof_name(int epi, int prof_cls) {
+    static const char* const names[][2] = {{"gemm_bias", "gemm_bias_cls"}, {"gemm_resid", "gemm_resid_cls"}, {"gemm_gate", "gemm_gate_cls"},
+                                           {"gemm_colmax", "gemm_colmax"}, {"gemm_argmin", "gemm_argmin"}, {"gemm_state", "gemm_state"}};
+    return names[epi][prof_cls ? 1 : 0];
+}
+
+// Workgroups of the XCD-aware block -> tile map (blocks b and b + 8 share an XCD; row panel = 8 * (j / tiles_n) + b % 8 with
+// j = b / 8): the row panels are padded to a multiple of eight, the surplus blocks return at once.
+static inline long gemm_padded_grid(long tiles_m, long tiles_n) { return (tiles_m + 7) / 8 * 8 * tiles_n; }
+
+// Raises the dynamic-LDS limit of `kernel` to `bytes`, once per device (`once`: a static of the calling launcher, one per kernel).
+// `file` names the caller in the error message.
+static inline int gemm_lds_limit(DvqOncePerDevice& once, const void* kernel, size_t bytes, const char* file) {
+    const hipError_t e = once.run([&] { return hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes); });
+    if (e != hipSuccess) {
+        dvq_set_error("%s: hipFuncSetAttribute failed: %s", file, hipGetErrorString(e));
+        return DVQ_ELAUNCH;
+    }
+    return DVQ_OK;
+}

@@ -17,8 +17,9 @@
 // Shape: the 16x16x32 instruction holds a higher clock than 32x32x16 at equal cycles per FLOP (MI355X_MICROARCH.md, DVFS
 // give-back item 7): measured here 288 against 262 TFLOP/s on the gated PixelCNN shape (M = 16 384, N = 1024, K = 1536).
 //
-// Tiled kernel: 128 x 256 output tile, eight waves as 2 (M) x 4 (N) of 64 x 64, one workgroup per CU, K-tiles of 32, two LDS
-// stages of 48 KiB: both operands as fp16 planes with 64-byte rows, the 16-byte chunk c of row r stored at c ^ ((4 - (r >> 2)) & 3)
+// Tiled kernel (gemm_f16x2_pp_kernel): 128 x 256 output tile, eight waves as 2 (M) x 4 (N) of 64 x 64, one workgroup per CU, K-tiles
+// of 32, three LDS stages of 48 KiB (the schedule: at the kernel): both operands as fp16 planes with 64-byte rows, the 16-byte chunk c
+// of row r stored at c ^ ((4 - (r >> 2)) & 3)
 // (conflict-free ds_read_b128 in the 16-row fragment shape: the four lane groups of a read hit sixteen different 16-byte bank
 // groups).  Activations go global -> registers -> split -> LDS (once per element), weight planes by LDS-DMA with the swizzle on
 // the source address.  Weights are MFMA operand A: a lane owns ONE output row m and four consecutive columns per block, so
@@ -38,7 +39,6 @@ constexpr int TM = 128, TN = 256, BK = 32;
 constexpr int A_PL = TM * 64;                               // one activation plane [128][32] fp16
 constexpr int W_PL = TN * 64;                               // one weight plane [256][32] fp16
 constexpr int STAGE = 2 * A_PL + 2 * W_PL;                  // 49 152 B
-constexpr size_t SMEM = 2 * STAGE;                          // 98 304 B: one workgroup per CU (eight waves, <= 256 registers)
 constexpr float LO_SCALE = 1.0f / 2048.0f;
 
 __device__ __forceinline__ int swz16(int row) { return (4 - ((row >> 2) & 3)) & 3; }
@@ -61,51 +61,6 @@ __device__ __forceinline__ void split2(const f32x4& lo, const f32x4& hi, h8& p1,
     p1 = __builtin_bit_cast(h8, uint4{hb[0], hb[1], hb[2], hb[3]});
     p2 = __builtin_bit_cast(h8, uint4{lb[0], lb[1], lb[2], lb[3]});
 }
-
-struct TileCursor {
-    int s, k_left;
-    const float* a_ptr;
-    const uint16_t* w_ptr[4];
-
-    __device__ __forceinline__ void open(const GemmParams& p, int src_i, long m0, int n0, int tid, int wave, int lane) {
-        s = src_i;
-        if (s >= p.nsrc) { k_left = 0; return; }
-        const GemmSrc& src = p.src[s];
-        k_left = src.K;
-        {
-            long m = m0 + (tid >> 2);
-            if (m >= p.M) m = p.M - 1;                     // clamped rows / columns only feed outputs the epilogue masks
-            if (src.arow) m = src.arow[m];
-            a_ptr = src.A + m * src.lda + 8 * (tid & 3);
-        }
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {                      // 32 pieces of 16 rows x 64 B (two planes x 256 rows), four per wave
-            const int id = wave * 4 + i;
-            const int pl = id >> 4, rb = id & 15;
-            const int row = rb * 16 + (lane >> 2);
-            int n = n0 + row;
-            if (n >= p.N) n = p.N - 1;
-            w_ptr[i] = src.Wp + pl * src.wp_plane + (long)n * src.ldw + 8 * ((lane & 3) ^ swz16(row));
-        }
-    }
-    __device__ __forceinline__ bool valid() const { return k_left > 0; }
-    __device__ __forceinline__ void issue_w(char* stage, int wave) const {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int id = wave * 4 + i;
-            const int pl = id >> 4, rb = id & 15;
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)w_ptr[i],
-                                             (__attribute__((address_space(3))) void*)(stage + 2 * A_PL + pl * W_PL + rb * 1024), 16, 0, 0);
-        }
-    }
-    __device__ __forceinline__ void advance(const GemmParams& p, long m0, int n0, int tid, int wave, int lane) {
-        a_ptr += BK;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) w_ptr[i] += BK;
-        k_left -= BK;
-        if (k_left <= 0) open(p, s + 1, m0, n0, tid, wave, lane);
-    }
-};
 
 // Epilogue of a wave's 64 x 64 block held as 4 x 4 blocks of 16 x 16: hi / lo [jn][i][e] = column n0w + 16 jn + 4 (lane >> 4) + e of
 // row m0w + 16 i + (lane & 15).  The arithmetic per element -- (hi + lo * 2^-11) * scale, + bias, ... in this order -- is shared
@@ -241,104 +196,25 @@ __device__ __forceinline__ void f16x2_epilogue(const GemmParams& p, f32x4 (&hi)[
     }
 }
 
-template <int EPI, bool DEPHASE, bool INIT>
-__global__ __launch_bounds__(512, 1) void gemm_f16x2_kernel(const GemmParams p) {
-    extern __shared__ __attribute__((aligned(16))) char smem_c[];
-    const int tid = threadIdx.x;
-    const int tiles_n = (p.N + TN - 1) / TN;
-    const long tiles_m = (p.M + TM - 1) / TM;
-    const long b = blockIdx.x;
-    const long j = b >> 3;                                  // XCD-aware map: the column tiles of a 128-row panel run on one XCD
-    const long mt = (j / tiles_n) * 8 + (b & 7);
-    const int nt = (int)(j % tiles_n);
-    if (mt >= tiles_m) return;
-    const long m0 = mt * TM;
-    const int n0 = nt * TN;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wm = wave >> 2, wn = wave & 3;
-
-    f32x4 hi[4][4], lo[4][4];                               // [jn][i]
-    f16x2_init_acc<4, INIT>(p, hi, lo, m0 + wm * 64, n0 + wn * 64, lane);
-
-    TileCursor cur;
-    cur.open(p, 0, m0, n0, tid, wave, lane);
-    const int a_dst = (tid >> 2) * 64 + 16 * ((tid & 3) ^ swz16(tid >> 2));
-    f32x4 alo, ahi;
-    auto load_a = [&]() {
-        alo = *reinterpret_cast<const f32x4*>(cur.a_ptr);
-        ahi = *reinterpret_cast<const f32x4*>(cur.a_ptr + 4);
-    };
-    auto store_a = [&](char* stage) {
-        h8 p1, p2;
-        split2(alo, ahi, p1, p2);
-        *reinterpret_cast<h8*>(stage + a_dst) = p1;
-        *reinterpret_cast<h8*>(stage + A_PL + a_dst) = p2;
-    };
-    load_a();
-    cur.issue_w(smem_c, wave);
-    cur.advance(p, m0, n0, tid, wave, lane);
-    store_a(smem_c);
-    bool more = cur.valid();
-    if (more) load_a();                                     // tile 1's activations: written into the other stage during tile 0
-
-    const int rd = (lane & 15) * 64 + 16 * ((lane >> 4) ^ swz16(lane & 15));       // fragment read: row lane & 15, chunk lane >> 4
-    int stage = 0;
-    while (true) {
-        dvq_dma_barrier();                                  // this stage is complete (weight DMA landed, activation planes written);
-                                                            // everybody is done reading the other stage
-        const char* st = smem_c + stage * STAGE;
-        char* nx = smem_c + (stage ^ 1) * STAGE;
-        // The two waves of a SIMD (w and w + 4) move in lock step: waves 0..3 feed the next stage at the top of the tile, waves 4..7
-        // half way, so that one of the pair runs MFMAs while the other sits in the DMA issue.
-        auto feed = [&]() {
-            store_a(nx);                                    // loaded a K-tile ago; before the DMA issue (vmcnt counts in order)
-            cur.issue_w(nx, wave);
-            cur.advance(p, m0, n0, tid, wave, lane);
-            if (cur.valid()) load_a();
-        };
-        if (more && (wave < 4 || !DEPHASE)) feed();
-        h8 af[4][2];
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int pl = 0; pl < 2; ++pl) af[i][pl] = *reinterpret_cast<const h8*>(st + pl * A_PL + (wm * 64 + i * 16) * 64 + rd);
-#pragma unroll
-        for (int jn = 0; jn < 4; ++jn) {
-            if (DEPHASE && jn == 2 && more && wave >= 4) feed();
-            const h8 w1 = *reinterpret_cast<const h8*>(st + 2 * A_PL + (wn * 64 + jn * 16) * 64 + rd);
-            const h8 w2 = *reinterpret_cast<const h8*>(st + 2 * A_PL + W_PL + (wn * 64 + jn * 16) * 64 + rd);
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                hi[jn][i] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w1, af[i][0], hi[jn][i], 0, 0, 0);
-                lo[jn][i] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w2, af[i][0], lo[jn][i], 0, 0, 0);
-                lo[jn][i] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w1, af[i][1], lo[jn][i], 0, 0, 0);
-            }
-        }
-        if (!more) break;
-        more = cur.valid();
-        stage ^= 1;
-    }
-    f16x2_epilogue<EPI>(p, hi, lo, m0 + wm * 64, n0 + wn * 64, (n0 >> 1) + wn * 32, lane);
-}
-
 // ---------------------------------------------------------------------------------------------------------------------------
-// Ping-pong schedule of the same tile (the default): the two waves of a SIMD -- w and w + 4, rows 0..63 and 64..127 of the tile --
-// alternate between a LOAD phase (the sixteen fragment reads of K-tile t; conversion + LDS write of this thread's share of tile
-// t + 2, whose activations it loaded a period ago; LDS-DMA of tile t + 2's weight planes; global loads of tile t + 3's activations)
-// and a COMPUTE phase (the 48 MFMAs of tile t on the fragments in registers, at s_setprio 1), one workgroup barrier per phase,
-// waves 4..7 half a period behind: one wave of every SIMD always has MFMAs to issue.  Three LDS stages (144 KiB): what a load
-// phase issues has two phases to land, and the stage it writes was last read two phases earlier.  Same operands into the same
-// MFMA sequence per output as gemm_f16x2_kernel: bit-identical.  Measured on the gated shape (M 16 384, N 1024, K 1536):
-// 300-307 TFLOP/s against 286-293 for the two-stage dephased kernel; in-kernel stamps (tools/microbench/gemm_f16x2_wide.hip):
-// load phase ~850 cycles + loop overhead against 803 for the compute phase at an in-kernel clock of 1.74 GHz; moving the split
-// into the compute phase's MFMA gaps (1 MFMA : 2 vector instructions) measured SLOWER (273).  Hand-counted waits (activation
-// loads as inline asm, vmcnt(4) / vmcnt(6) so that neither stream waits for the other's younger requests) measured 327 on the
-// microbench, where the activations stream from HBM, and NOTHING in the benchmark step (gated GEMMs 199.6 -> 200.5 ms: their
-// activations were written by the previous launch); the variant tried also let waves 0-3 read a tile whose DMA pieces waves 4-7
-// had not waited for yet (one differing result hash in four bench runs) -- not kept: every load phase starts with vmcnt(0).
+// The tiled kernel's ping-pong schedule: the two waves of a SIMD -- w and w + 4, rows 0..63 and 64..127 of the tile -- alternate
+// between a LOAD phase (the sixteen fragment reads of K-tile t; conversion + LDS write of this thread's share of tile t + 2, whose
+// activations it loaded a period ago; LDS-DMA of tile t + 2's weight planes; global loads of tile t + 3's activations) and a
+// COMPUTE phase (the 48 MFMAs of tile t on the fragments in registers, at s_setprio 1), one workgroup barrier per phase, waves
+// 4..7 half a period behind: one wave of every SIMD always has MFMAs to issue.  Three LDS stages (144 KiB): what a load phase
+// issues has two phases to land, and the stage it writes was last read two phases earlier.  Measured on the gated shape
+// (M 16 384, N 1024, K 1536): 300-307 TFLOP/s.  The kernel this one replaced in round 4 had two
+// LDS stages and one barrier per K-tile, every wave feeding the next stage and multiplying within the same K-tile, waves 4..7 feeding
+// half a tile after waves 0..3: 286-293 TFLOP/s, and the same bits (the same operands into the same MFMA sequence per output).
+// In-kernel stamps (tools/microbench/gemm_f16x2_wide.hip): load phase ~850 cycles + loop overhead against 803 for the compute
+// phase at an in-kernel clock of 1.74 GHz; moving the split into the compute phase's MFMA gaps (1 MFMA : 2 vector instructions)
+// measured SLOWER (273).  Hand-counted waits (activation loads as inline asm, vmcnt(4) / vmcnt(6) so that neither stream waits for
+// the other's younger requests) measured 327 on the microbench, where the activations stream from HBM, and NOTHING in the benchmark
+// step (gated GEMMs 199.6 -> 200.5 ms: their activations were written by the previous launch); the variant tried also let waves 0-3
+// read a tile whose DMA pieces waves 4-7 had not waited for yet (one differing result hash in four bench runs) -- not kept: every
+// load phase starts with vmcnt(0).
 constexpr int PP_STAGES = 3;
-constexpr size_t PP_SMEM = PP_STAGES * STAGE;               // 147 456 B
+constexpr size_t PP_SMEM = PP_STAGES * STAGE;               // 147 456 B: one workgroup per CU (eight waves, <= 256 registers)
 constexpr size_t PP_SMEM_N128 = PP_STAGES * (2 * A_PL + 2 * 128 * 64);   // 98 304 B (128 x 128 tile)
 
 struct PpCursorA {
@@ -492,7 +368,7 @@ __global__ __launch_bounds__(512, 1) void gemm_f16x2_pp_kernel(const GemmParams 
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // fragments in registers (and the plane writes retired) before the phase ends
         __builtin_amdgcn_s_barrier();
-        // ---- compute phase: hi: (a1 w1); lo: (a1 w2) then (a2 w1) -- per output the order of gemm_f16x2_kernel
+        // ---- compute phase: hi: (a1 w1); lo: (a1 w2) then (a2 w1) -- per output the order the file header gives
         __builtin_amdgcn_s_setprio(1);
         if (DVQ_DIAG_ON && (p.dbg_abl & 2)) {               // timing only: no matrix work (the operands still have to arrive)
 #pragma unroll
@@ -530,60 +406,34 @@ __global__ __launch_bounds__(512, 1) void gemm_f16x2_pp_kernel(const GemmParams 
 // workgroup of those launches moves ~1 MB (activations 256 KB, weight planes 512 KB from L2, residual in, tile out) in 46 us =
 // 22 GB/s per CU, the rate one CU sustains from beyond L2 (MI355X_MICROARCH.md: 23-33 GB/s): they are bound by the per-CU memory
 // path, not by the overlap of prologue and epilogue, and the smaller tile reads every activation row twice as often.
-template <int EPI, bool INIT = false>
-int launch_tiled(const GemmParams& p, hipStream_t stream) {
+template <int EPI, int NJ, bool INIT>
+int launch_pp(const GemmParams& p, hipStream_t stream) {
+    constexpr size_t smem = NJ == 4 ? PP_SMEM : PP_SMEM_N128;
     static DvqOncePerDevice attr_once;
+    DVQ_PROPAGATE(gemm_lds_limit(attr_once, reinterpret_cast<const void*>(&gemm_f16x2_pp_kernel<EPI, NJ, INIT>), smem, "gemm_f16x2"));
+    const long grid = gemm_padded_grid((p.M + TM - 1) / TM, (p.N + 64 * NJ - 1) / (64 * NJ));
+    const double ksum = gemm_ksum(p);
     {
-        const hipError_t e = attr_once.run([] {
-            const hipError_t e0 = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_f16x2_kernel<EPI, false, INIT>),
-                                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)SMEM);
-            const hipError_t e1 = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_f16x2_kernel<EPI, true, INIT>),
-                                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)SMEM);
-            hipError_t e2 = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_f16x2_pp_kernel<EPI, 4, INIT>),
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)PP_SMEM);
-            if constexpr (EPI != EPI_GATE)
-                if (e2 == hipSuccess) e2 = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_f16x2_pp_kernel<EPI, 2, INIT>),
-                                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)PP_SMEM_N128);
-            return e0 != hipSuccess ? e0 : (e1 != hipSuccess ? e1 : e2);
-        });
-        if (e != hipSuccess) {
-            dvq_set_error("gemm_f16x2: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
-            return DVQ_ELAUNCH;
-        }
-    }
-    const long tiles_m = (p.M + TM - 1) / TM;
-    const long tiles_n = (p.N + TN - 1) / TN;
-    const long grid = ((tiles_m + 7) / 8) * 8 * tiles_n;
-    // 128 x 128 tiles where they take fewer rounds of workgroups per unit of work (one workgroup per CU either way): e.g. M = 8 192,
-    // N = 512 is 128 tiles of 128 x 256 -- half the chip -- or 256 of 128 x 128.  DVQ_GEMM_TN=128 / 256 forces one (A/B runs, same bits).
-    bool narrow = false;
-    if constexpr (EPI != EPI_GATE) {
-        const long tiles_n2 = (p.N + 127) / 128, cus = dvq_num_cus();
-        const long r256 = (tiles_m * tiles_n + cus - 1) / cus, r128 = (tiles_m * tiles_n2 + cus - 1) / cus;
-        narrow = r128 < 2 * r256;
-        if (dvq_knobs().gemm_tn == 128) narrow = true;
-        if (dvq_knobs().gemm_tn == 256) narrow = false;
-    }
-    static const char* const names_row[] = {"gemm_bias", "gemm_resid", "gemm_gate", "", "", "gemm_state"};
-    static const char* const names_cls[] = {"gemm_bias_cls", "gemm_resid_cls", "gemm_gate_cls", "", "", "gemm_state"};
-    const char* const* names = p.prof_cls ? names_cls : names_row;
-    double ksum = 0;
-    int T = 0;
-    for (int s = 0; s < p.nsrc; ++s) { ksum += p.src[s].K; T += p.src[s].K / BK; }
-    {
-        DVQ_PROF(names[EPI], 2.0 * (double)p.M * p.N * ksum, ((double)p.M + p.N) * ksum * 4, stream);
-        const int mode = dvq_knobs().gemm_dephase;          // DVQ_GEMM_DEPHASE: 2 (default) ping-pong, 1 two stages dephased, 0 two stages in lock step
-        if (mode == 2 && narrow) {
-            if constexpr (EPI != EPI_GATE) {
-                const long grid2 = ((tiles_m + 7) / 8) * 8 * ((p.N + 127) / 128);
-                DVQ_LAUNCH((gemm_f16x2_pp_kernel<EPI, 2, INIT>), dim3((unsigned)grid2), dim3(512), PP_SMEM_N128, stream, p, T);
-            }
-        } else if (mode == 2) DVQ_LAUNCH((gemm_f16x2_pp_kernel<EPI, 4, INIT>), dim3((unsigned)grid), dim3(512), PP_SMEM, stream, p, T);
-        else if (mode == 1) DVQ_LAUNCH((gemm_f16x2_kernel<EPI, true, INIT>), dim3((unsigned)grid), dim3(512), SMEM, stream, p);
-        else DVQ_LAUNCH((gemm_f16x2_kernel<EPI, false, INIT>), dim3((unsigned)grid), dim3(512), SMEM, stream, p);
+        DVQ_PROF(gemm_prof_name(EPI, p.prof_cls), 2.0 * (double)p.M * p.N * ksum, ((double)p.M + p.N) * ksum * 4, stream);
+        DVQ_LAUNCH((gemm_f16x2_pp_kernel<EPI, NJ, INIT>), dim3((unsigned)grid), dim3(512), smem, stream, p, gemm_ktiles(p, BK));
     }
     DVQ_CHECK_LAUNCH("gemm_f16x2");
     return DVQ_OK;
+}
+
+template <int EPI, bool INIT = false>
+int launch_tiled(const GemmParams& p, hipStream_t stream) {
+    // 128 x 128 tiles where they take fewer rounds of workgroups per unit of work (one workgroup per CU either way): e.g. M = 8 192,
+    // N = 512 is 128 tiles of 128 x 256 -- half the chip -- or 256 of 128 x 128.  DVQ_GEMM_TN=128 / 256 forces one (A/B runs, same bits).
+    if constexpr (EPI != EPI_GATE) {
+        const long tiles_m = (p.M + TM - 1) / TM, tiles_n = (p.N + TN - 1) / TN, tiles_n2 = (p.N + 127) / 128, cus = dvq_num_cus();
+        const long r256 = (tiles_m * tiles_n + cus - 1) / cus, r128 = (tiles_m * tiles_n2 + cus - 1) / cus;
+        bool narrow = r128 < 2 * r256;
+        if (dvq_knobs().gemm_tn == 128) narrow = true;
+        if (dvq_knobs().gemm_tn == 256) narrow = false;
+        if (narrow) return launch_pp<EPI, 2, INIT>(p, stream);
+    }
+    return launch_pp<EPI, 4, INIT>(p, stream);
 }
 
 // ================================================================================================================
@@ -592,10 +442,11 @@ int launch_tiled(const GemmParams& p, hipStream_t stream) {
 // time of ONE small launch, not throughput.  Measured (gated launch, K = 3072, M = 1): 13.5 us whether a wave owns 16, 8 or 4
 // columns (32 / 64 / 128 waves), with 24 or 48 KB of loads in flight, with or without 192 helper workgroups sweeping the rows
 // into the XCD's L2: not the weight stream but the wave's own instruction stream, ~70 instructions per k-step of which 32 split
-// the activations.  One single-wave workgroup per R output columns (R = 16, 8 or 4: the MFMA's sixteen weight rows are R real
-// rows and repeats, whose outputs nobody reads) and per 16 rows of M; for the gate the block's rows are R tanh columns
-// followed by their R sigmoid partners (R = 8 or 4), exchanged by a lane shuffle in the epilogue.  No LDS, no barrier: the
-// wave streams its weight rows HBM -> registers in the MFMA fragment shape (lane = row l & 15, 16-byte chunk l >> 4 of a
+// the activations.  So the width is the widest block, fixed per epilogue (skinny_cols).  One single-wave workgroup per R output
+// columns (where R < 16 the MFMA's sixteen weight rows are R real rows and repeats, whose outputs nobody reads) and per 16 rows
+// of M; for the gate the block's rows are R = 8 tanh columns followed by their 8 sigmoid partners, exchanged by a lane shuffle in
+// the epilogue.  No LDS, no barrier: the wave
+// streams its weight rows HBM -> registers in the MFMA fragment shape (lane = row l & 15, 16-byte chunk l >> 4 of a
 // 64-byte k-step), its activation rows in whole 128-byte lines, PF k-steps ahead through a ring of register sets (no branch
 // around a load: steps past the end re-load the last tile), splits the activations in registers and runs the tiled kernel's
 // MFMA sequence per output -- hi: (a1 w1), lo: (a1 w2) then (a2 w1), k-steps in source order -- so the result is bit-identical
@@ -776,65 +627,46 @@ constexpr long SKINNY_MAX_M = 256;     // above this the tiled kernel wins (ever
 // up to more rows: 512 rows measured 7.0 -> 4.6 ms per call
 inline long skinny_max_m(const GemmParams& p) { return p.prof_cls ? 4 * SKINNY_MAX_M : SKINNY_MAX_M; }
 
-template <int EPI, int R>
-void launch_skinny_r(const GemmParams& p, int T, int gy, hipStream_t stream) {
-    const int groups = EPI == EPI_GATE ? (p.N / 64) * (32 / R) : (p.N + R - 1) / R;
-    if (gy >= 3) DVQ_LAUNCH((gemm_f16x2_skinny_kernel<EPI, R, 2, 4>), dim3((unsigned)((groups + 1) / 2), (unsigned)gy), dim3(64), 0, stream, p, T, groups);
-    else DVQ_LAUNCH((gemm_f16x2_skinny_kernel<EPI, R, 1, 8>), dim3((unsigned)groups, (unsigned)gy), dim3(64), 0, stream, p, T, groups);
-}
+// output columns per wave: the MFMA's sixteen rows, which for the gate are 8 tanh columns + their 8 sigmoid partners
+template <int EPI>
+constexpr int skinny_cols = EPI == EPI_GATE ? 8 : 16;
 
+// One row group (M <= 16): the launch waits for the single instruction stream of a wave (~70 instructions per k-step), one block
+// per wave, eight k-steps in flight.  Three or more row groups: two blocks per wave (they share the activation split).
 template <int EPI>
 int launch_skinny(const GemmParams& p, hipStream_t stream) {
-    static const char* const names_row[] = {"gemm_bias", "gemm_resid", "gemm_gate", "", "", "gemm_state"};
-    static const char* const names_cls[] = {"gemm_bias_cls", "gemm_resid_cls", "gemm_gate_cls", "", "", "gemm_state"};
-    const char* const* names = p.prof_cls ? names_cls : names_row;
-    double ksum = 0;
-    int T = 0;
-    for (int s = 0; s < p.nsrc; ++s) { ksum += p.src[s].K; T += p.src[s].K / BK; }
+    constexpr int R = skinny_cols<EPI>;
+    const double ksum = gemm_ksum(p);
+    const int T = gemm_ktiles(p, BK);
     const int gy = (int)((p.M + 15) / 16);
-    // Columns per wave.  One row group (M <= 16): the launch waits for the single instruction stream of a wave (~70 instructions
-    // per k-step), whatever its width: 8 + 8 gate columns / 16 plain columns per wave.  More row groups: the widest blocks, two
-    // per wave (DVQ_GEMM_SKINNY_COLS = 16 / 8 / 4 forces a width: A/B runs, same bits).
-    const int want = dvq_knobs().gemm_skinny_cols;
-    int R = 16;
-    if (want == 4 || want == 8 || want == 16) R = want;
-    if (EPI == EPI_GATE && R == 16) R = 8;
+    const int groups = EPI == EPI_GATE ? (p.N / 64) * (32 / R) : (p.N + R - 1) / R;
     {
-        DVQ_PROF(names[EPI], 2.0 * (double)p.M * p.N * ksum, ((double)p.M + p.N) * ksum * 4, stream);
-        if constexpr (EPI == EPI_GATE) {
-            if (R == 4) launch_skinny_r<EPI, 4>(p, T, gy, stream); else launch_skinny_r<EPI, 8>(p, T, gy, stream);
-        } else {
-            if (R == 4) launch_skinny_r<EPI, 4>(p, T, gy, stream);
-            else if (R == 8) launch_skinny_r<EPI, 8>(p, T, gy, stream);
-            else launch_skinny_r<EPI, 16>(p, T, gy, stream);
-        }
+        DVQ_PROF(gemm_prof_name(EPI, p.prof_cls), 2.0 * (double)p.M * p.N * ksum, ((double)p.M + p.N) * ksum * 4, stream);
+        if (gy >= 3) DVQ_LAUNCH((gemm_f16x2_skinny_kernel<EPI, R, 2, 4>), dim3((unsigned)((groups + 1) / 2), (unsigned)gy), dim3(64), 0, stream, p, T, groups);
+        else DVQ_LAUNCH((gemm_f16x2_skinny_kernel<EPI, R, 1, 8>), dim3((unsigned)groups, (unsigned)gy), dim3(64), 0, stream, p, T, groups);
     }
     DVQ_CHECK_LAUNCH("gemm_f16x2_skinny");
     return DVQ_OK;
 }
 
-template <int R>
-void launch_skinny_gate_group_r(const GemmGroup& g, int n, int gy, hipStream_t stream) {
-    const int groups = (g.p[0].N / 64) * (32 / R);
-    if (gy >= 3) DVQ_LAUNCH((gemm_f16x2_skinny_gate_group_kernel<R, 2, 4>), dim3((unsigned)((groups + 1) / 2), (unsigned)gy, (unsigned)n), dim3(64), 0, stream, g, groups);
-    else DVQ_LAUNCH((gemm_f16x2_skinny_gate_group_kernel<R, 1, 8>), dim3((unsigned)groups, (unsigned)gy, (unsigned)n), dim3(64), 0, stream, g, groups);
-}
-
+// as launch_skinny<EPI_GATE>: the same width and launch shape, hence the same kernel body per output
 int launch_skinny_gate_group(const GemmParams* ps, int n, hipStream_t stream) {
+    constexpr int R = skinny_cols<EPI_GATE>;
     GemmGroup g = {};
     double flops = 0, bytes = 0;
     for (int i = 0; i < n; ++i) {
         g.p[i] = ps[i];
-        double ksum = 0;
-        for (int s = 0; s < ps[i].nsrc; ++s) { ksum += ps[i].src[s].K; g.T[i] += ps[i].src[s].K / BK; }
+        g.T[i] = gemm_ktiles(ps[i], BK);
+        const double ksum = gemm_ksum(ps[i]);
         flops += 2.0 * (double)ps[i].M * ps[i].N * ksum;
         bytes += ((double)ps[i].M + ps[i].N) * ksum * 4;
     }
     const int gy = (int)((ps[0].M + 15) / 16);
-    const int want = dvq_knobs().gemm_skinny_cols;          // as launch_skinny: the same width, hence the same kernel body per output
+    const int groups = (ps[0].N / 64) * (32 / R);
     {
-        DVQ_PROF(ps[0].prof_cls ? "gemm_gate_cls" : "gemm_gate", flops, bytes, stream);
-        if (want == 4) launch_skinny_gate_group_r<4>(g, n, gy, stream); else launch_skinny_gate_group_r<8>(g, n, gy, stream);
+        DVQ_PROF(gemm_prof_name(EPI_GATE, ps[0].prof_cls), flops, bytes, stream);
+        if (gy >= 3) DVQ_LAUNCH((gemm_f16x2_skinny_gate_group_kernel<R, 2, 4>), dim3((unsigned)((groups + 1) / 2), (unsigned)gy, (unsigned)n), dim3(64), 0, stream, g, groups);
+        else DVQ_LAUNCH((gemm_f16x2_skinny_gate_group_kernel<R, 1, 8>), dim3((unsigned)groups, (unsigned)gy, (unsigned)n), dim3(64), 0, stream, g, groups);
     }
     DVQ_CHECK_LAUNCH("gemm_f16x2_skinny_group");
     return DVQ_OK;

@@ -138,27 +138,17 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_kernel(const GemmParams p) {
     gemm_epilogue<EPI>(p, acc, m0, n0, mt, nt, tid, smem);
 }
 
+// workgroups of gemm_f32_kernel's two block -> tile maps
+inline long f32_grid(long tiles_m, long tiles_n) { return tiles_m < 8 ? tiles_m * ((tiles_n + 7) / 8 * 8) : gemm_padded_grid(tiles_m, tiles_n); }
+
 template <int EPI>
 int launch(const GemmParams& p, hipStream_t stream) {
     static DvqOncePerDevice attr_once;
+    DVQ_PROPAGATE(gemm_lds_limit(attr_once, reinterpret_cast<const void*>(&gemm_f32_kernel<EPI>), SMEM_BYTES, "gemm"));
+    const long grid = f32_grid((p.M + BM - 1) / BM, (p.N + BN - 1) / BN);
+    const double ksum = gemm_ksum(p);
     {
-        const hipError_t e = attr_once.run([] {
-            return hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_f32_kernel<EPI>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)SMEM_BYTES);
-        });
-        if (e != hipSuccess) {
-            dvq_set_error("gemm: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
-            return DVQ_ELAUNCH;
-        }
-    }
-    const long tiles_m = (p.M + BM - 1) / BM;
-    const long tiles_n = (p.N + BN - 1) / BN;
-    const long grid = tiles_m < 8 ? tiles_m * ((tiles_n + 7) / 8) * 8 : ((tiles_m + 7) / 8) * 8 * tiles_n;   // (the kernel's two block -> tile maps)
-    static const char* const names[] = {"gemm_bias", "gemm_resid", "gemm_gate", "gemm_colmax", "gemm_argmin"};
-    double ksum = 0;
-    for (int s = 0; s < p.nsrc; ++s) ksum += p.src[s].K;
-    {
-        DVQ_PROF(names[EPI], 2.0 * (double)p.M * p.N * ksum, ((double)p.M + p.N) * ksum * 4, stream);
+        DVQ_PROF(gemm_prof_name(EPI, 0), 2.0 * (double)p.M * p.N * ksum, ((double)p.M + p.N) * ksum * 4, stream);
         DVQ_LAUNCH(gemm_f32_kernel<EPI>, dim3((unsigned)grid), dim3(256), SMEM_BYTES, stream, p);
     }
     DVQ_CHECK_LAUNCH("gemm_f32");
@@ -179,7 +169,10 @@ int dvq_gemm_mode() {
 static int check_gemm(const GemmParams& p) {
     DVQ_REQUIRE(p.nsrc >= 1 && p.nsrc <= DVQ_MAX_SRC, "gemm: nsrc=%d out of range", p.nsrc);
     DVQ_REQUIRE(p.M > 0 && p.N > 0, "gemm: empty problem M=%ld N=%d", p.M, p.N);
-    DVQ_REQUIRE(((p.M + BM - 1) / BM + 7) / 8 * 8 * ((p.N + BN - 1) / BN) < (1L << 31), "gemm: grid too large");
+    // every kernel of the three files tiles 128 rows and >= 128 columns: the fp32 kernel's grid (either of its maps) and the padded
+    // grid of the 128 x 128 kernels bound them all
+    const long tiles_m = (p.M + BM - 1) / BM, tiles_n = (p.N + BN - 1) / BN;
+    DVQ_REQUIRE(f32_grid(tiles_m, tiles_n) < (1L << 31) && gemm_padded_grid(tiles_m, tiles_n) < (1L << 31), "gemm: grid too large");
     for (int s = 0; s < p.nsrc; ++s) {
         const GemmSrc& g = p.src[s];
         DVQ_REQUIRE(g.A && g.W, "gemm: null operand in source %d", s);

@@ -24,10 +24,8 @@ DvqKnobs* read_knobs() {
     auto num = [](const char* name) { const char* e = getenv(name); return e ? atol(e) : 0L; };
     k->gemm_wide = !is("DVQ_GEMM_WIDE", '0');
     k->gemm_tn = (int)num("DVQ_GEMM_TN");
-    k->gemm_dephase = is("DVQ_GEMM_DEPHASE", '0') ? 0 : (is("DVQ_GEMM_DEPHASE", '1') ? 1 : 2);    // f16x2 tiled kernel: 2 = ping-pong (default)
-    k->gemm_skinny = is("DVQ_GEMM_SKINNY", '0') ? 0 : (is("DVQ_GEMM_SKINNY", '2') ? 2 : 1);   // 2: the register-staged variant
-    k->gemm_skinny_prefetch = !is("DVQ_GEMM_SKINNY_PREFETCH", '0');
-    k->gemm_skinny_cols = (int)num("DVQ_GEMM_SKINNY_COLS");
+    k->gemm_dephase = !is("DVQ_GEMM_DEPHASE", '0');
+    k->gemm_skinny = !is("DVQ_GEMM_SKINNY", '0');
     k->pn_filter = is("DVQ_PN_FILTER", '0') ? 0 : (is("DVQ_PN_FILTER", '2') ? 2 : 1);
     k->pn_tail = is("DVQ_PN_TAIL", '0') ? 0 : 1;
     k->pn_exhaustive = is("DVQ_PN_EXHAUSTIVE", '1');

@@ -1378,22 +1378,19 @@ torch.save(out, sys.argv[1])
 
 def test_gemm_tile_variants_agree_bitwise(tmp_path):
     """Six-product kernels (DVQ_GEMM=bf16x3): the 128x256 eight-wave tile (default where N % 256 == 0, N >= 512) and the 128x128
-    tile (DVQ_GEMM_WIDE=0) use the same accumulation order.  Three-product kernels (default): the two feeding schedules of the
-    tiled kernel (DVQ_GEMM_DEPHASE: ping-pong over three LDS stages = the default, two stages dephased, two stages in lock
-    step).  Bias/ReLU GEMMs and the full 15-layer PixelCNN forward (gate, residual, multi-tap sources,
-    ragged M) must agree bit for bit -- and repeat bit for bit (a missing wait before the K-loop barrier showed up as
-    run-to-run noise)."""
+    tile (DVQ_GEMM_WIDE=0) use the same accumulation order.  Three-product kernels (default): the two tile widths of the tiled
+    kernel (DVQ_GEMM_TN: 128 x 128 / 128 x 256 forced; default = chosen per launch).  Bias/ReLU GEMMs and the full 15-layer
+    PixelCNN forward (gate, residual, multi-tap sources, ragged M) must agree bit for bit -- and repeat bit for bit (a missing
+    wait before the K-loop barrier showed up as run-to-run noise)."""
     import os, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    for mode, knob in (("bf16x3", "DVQ_GEMM_WIDE"), ("f16x2", "DVQ_GEMM_DEPHASE")):
+    legs = (("bf16x3", "DVQ_GEMM_WIDE", (("a", {"DVQ_GEMM_WIDE": "1"}), ("b", {"DVQ_GEMM_WIDE": "0"}), ("a2", {"DVQ_GEMM_WIDE": "1"}))),
+            ("f16x2", "DVQ_GEMM_TN", (("default", {}), ("default2", {}), ("tn128", {"DVQ_GEMM_TN": "128"}), ("tn256", {"DVQ_GEMM_TN": "256"}))))
+    for mode, knob, variants in legs:
         outs = []
-        # f16x2 also: the ping-pong kernel's tile width (DVQ_GEMM_TN: 128 x 128 / 128 x 256 forced; default = chosen per launch)
-        variants = ((("a", "1"), ("b", "0"), ("a2", "1")) if mode == "bf16x3" else
-                    (("pp", "2"), ("two-stage", "0"), ("pp2", "2"), ("dephased", "1"), ("tn128", "2"), ("tn256", "2")))
-        for tag, val in variants:
+        for tag, extra in variants:
             path = str(tmp_path / f"{mode}_{tag}.pt")
-            extra = {"DVQ_GEMM_TN": tag[2:]} if tag.startswith("tn") else {}
-            r = subprocess.run([sys.executable, "-c", _GEMM_VARIANT_SCRIPT, path, root], env=dict(os.environ, DVQ_GEMM=mode, **{knob: val}, **extra),
+            r = subprocess.run([sys.executable, "-c", _GEMM_VARIANT_SCRIPT, path, root], env=dict(os.environ, DVQ_GEMM=mode, **extra),
                                capture_output=True, text=True, timeout=600)
             assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
             outs.append(torch.load(path))
@@ -1531,10 +1528,6 @@ def test_skinny_gemm_equals_tiled_kernels_bitwise(kind):
     b = _with_env("DVQ_GEMM", kind, lambda: _with_env("DVQ_GEMM_SKINNY", "0", run))
     for key in a:
         assert torch.equal(a[key], b[key]), f"{key}: skinny kernel != tiled kernel"
-    if kind == "bf16x3":
-        c = _with_env("DVQ_GEMM", kind, lambda: _with_env("DVQ_GEMM_SKINNY", "2", run))   # the register-staged variant of the skinny kernel
-        for key in a:
-            assert torch.equal(a[key], c[key]), f"{key}: LDS-staged skinny kernel != register-staged one"
     assert torch.equal(a["logits"][3:4], a["logits_row3"])
 
 

@@ -22,8 +22,8 @@ for M in (1, 8, 100, 256):
         pls = [packing.split_bf16x3(w) for w in ws]
         out = torch.empty(M, N, device=dev)
         res = {}
-        for mode in ("1", "2", "0"):
+        for mode in ("1", "0"):
             os.environ["DVQ_GEMM_SKINNY"] = mode; lib.dvq_reload_env()
             res[mode] = (timed(lambda i: ops.linear(x, ws[0], b, out=out, planes=pls[0]), 96),
                          timed(lambda i: ops.linear(x, ws[i % 48], b, out=out, planes=pls[i % 48]), 96))
-        print(f"M={M:4d} N={N} K={K}: skinny (LDS-staged) warm {res['1'][0]:6.1f} us, rotating {res['1'][1]:6.1f} us | register-staged warm {res['2'][0]:6.1f} us, rotating {res['2'][1]:6.1f} us | tiled warm {res['0'][0]:6.1f} us, rotating {res['0'][1]:6.1f} us", flush=True)
+        print(f"M={M:4d} N={N} K={K}: skinny warm {res['1'][0]:6.1f} us, rotating {res['1'][1]:6.1f} us | tiled warm {res['0'][0]:6.1f} us, rotating {res['0'][1]:6.1f} us", flush=True)
