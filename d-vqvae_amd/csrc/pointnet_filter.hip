@@ -5,7 +5,7 @@
 //      pn_trunk_kernel; the fp32 h2 rows [point][128] go to HBM.  conv3 (94 % of the trunk's FLOPs) is then evaluated as ONE
 //      fp16 product per term on CENTRED rows: d_p = h2_p - c (c = pn_center_kernel's mean of four rows of the sample; the
 //      argmax over the points does not depend on it), d scaled by a per-wave power of two, W3 by a per-channel power of
-//      two, both rounded to fp16.  Every lane keeps, per 32 x 32 accumulator block (its 16 points of one channel), the TWO largest
+//      two, both rounded to fp16.  Every lane keeps, per 16-channel column block (its 16 points of one channel: four per row block), the TWO largest
 //      approximate scores with the id of their point in the low mantissa bits; per (sample, 256-point tile, channel) the kernel
 //      emits the FIVE largest of those 32 values and one flag per 16-point group that may hold further points in range whose
 //      ids were not kept.
@@ -19,10 +19,12 @@
 //      maximum of exact_dot over ALL points (tests: DVQ_PN_EXHAUSTIVE=1 evaluates exactly that).  The 16 points of a flagged
 //      group are all evaluated.
 //
-// Matrix-core cost per (32 points x 32 channels x K=128): 8 x v_mfma_f32_32x32x16_f16 instead of 48 bf16 MFMAs; the
+// Matrix-core cost per (32 points x 32 channels x K=128): 16 x v_mfma_f32_16x16x32_f16 (the matrix cycles of eight 32x32x16: the
+// chip holds a higher clock on the small shape, tools/microbench/pn_loop_shape.hip) instead of 48 bf16 MFMAs; the
 // kernel is bound by vector-instruction issue: 2.5 instructions per score (id; max3 / med3 per group of three) since round 6 -- a top-two per 16-point
 // group flags about as many points for re-evaluation as the top-three per 32 points of round 4 did.
 #include "dvq_internal.h"
+#include "pn_slots.h"
 #include <vector>
 
 namespace {
@@ -34,7 +36,8 @@ typedef float qf32x2 __attribute__((ext_vector_type(2)));
 
 // beyond the two measured rounding residuals, relative to |w| max|d|: the 8 id bits 2^-15 (3.05e-5); the matrix core's fp32
 // accumulation of the 128 exact products -- at most 128 additions of 2^-23 each even if they truncated (1.53e-5; round to
-// nearest: half of that); the product of the two residuals (2^-22); rounded up
+// nearest: half of that); the product of the two residuals (2^-22); rounded up.  Nothing in it depends on the ORDER in which the
+// instruction sums its products: the same constant held for v_mfma_f32_32x32x16_f16 (8 steps of 16) and holds for 16x16x32 (4 of 32)
 constexpr float C_ID = 5.0e-5f;
 // |exact_dot(w, h) - w.h| <= DELTA |w| |h|: 8 chained FMAs + 4 butterfly adds = 12 roundings (7.2e-7), + the fp32 add of
 // the centre term
@@ -48,7 +51,7 @@ constexpr int F_STAGE2 = 2 * 64 * 128;                    // conv2: one half of 
 constexpr int IMG_OFF_TI = 1024 * 256, IMG_OFF_WN = IMG_OFF_TI + 4096, IMG_OFF_RN = IMG_OFF_WN + 4096;
 constexpr int IMG_OFF_W2 = IMG_OFF_RN + 4096, IMG_OFF_K2 = IMG_OFF_W2 + 2 * 128 * 128, IMG_BYTES = IMG_OFF_K2 + 512;
 constexpr int F_STAGE3 = 64 * 256;                        // conv3: 64 channels x 128 k fp16
-constexpr int F_OFF_TB = 2 * F_STAGE3;                    // conv3 phase: record ring [4 chunks][4 waves][2 point blocks][2 halves][2][64] fp32 (32 KiB) behind the two W3 stages
+constexpr int F_OFF_TB = 2 * F_STAGE3;                    // conv3 phase: record ring [4 chunks][4 waves][4 lane quarters][2][64] fp32 (32 KiB) behind the two W3 stages
 constexpr int F_SLOT = 4 * 2 * 2 * 2 * 64;                // floats per chunk slot of the ring
 constexpr int F_OFF_W1 = F_OFF_TB + 8 * 4 * 4 * 64 * 4;   // [64][4] fp32
 constexpr int F_OFF_B1 = F_OFF_W1 + 64 * 4 * 4;           // [64]
@@ -147,19 +150,7 @@ __device__ __forceinline__ float wave_max(float v) {
     return v;
 }
 
-// Points are dealt to the tiles round robin and to the 256 slots of a tile (wave, block, lane) through a multiplicative
-// permutation: neighbours in the cloud's order -- often neighbours in space, i.e. near ties -- land in different waves.
-// ``deal`` tiles share the first 256 * deal points this way.  A cloud with 1 .. 32 points beyond a multiple of 256 (the 778 hand
-// vertices: 3 * 256 + 10) gets them as a TAIL tile (index deal) of ONE 32-point block instead of a fourth full tile that is
-// three quarters padding: point 256 * deal + (slot & 31) (callers fold indices >= N back with % N, as for every padding slot).
-__device__ __forceinline__ int point_of_slot(int tile, int slot, int deal) {
-    return tile < deal ? ((slot * 67) & 255) * deal + tile : 256 * deal + (slot & 31);
-}
-// id bits of a tracked score: [3:0] accumulator register, [4] point block, [5] lane half, [7:6] wave -> slot inside the tile
-__device__ __forceinline__ int slot_of_id(unsigned id) {
-    const int e = id & 15, pb = (id >> 4) & 1, h = (id >> 5) & 1, w = (id >> 6) & 3;
-    return w * 64 + pb * 32 + 8 * (e >> 2) + 4 * h + (e & 3);
-}
+// (point_of_slot, slot_of_id and the groups of a tile: csrc/pn_slots.h)
 
 // Wave reductions without ds_bpermute (__shfl_xor: an LDS-crossbar instruction, an lgkmcnt wait and an address register per pattern):
 // lanes l and l ^ 32 through v_permlane32_swap, rows through DPP, the four rows through v_readlane.
@@ -416,11 +407,36 @@ __global__ __launch_bounds__(256, 2) void pn_trunk_filter_kernel(const float* __
         rn2 = fmaxf(rn2, sq);
     }
     rn2 = g_wave_max(rn2);
+    // conv3 runs on v_mfma_f32_16x16x32_f16: an A fragment wants lane (quarter q, row l) to hold 8 k of row l of ONE 16-point row
+    // block, the four quarters four different k chunks.  Here lane rows {0, 2} (h = 0, 1) hold points 0 .. 15 of the point block and
+    // rows {1, 3} points 16 .. 31, each 8 k per step st.  v_permlane16_swap_b32 exchanges the odd rows of its first operand with
+    // the even rows of its second: applied to the steps (2 ks, 2 ks + 1) it leaves in a3[pb][2 ks + hb] the complete fragment of row
+    // block 2 pb + hb and MFMA step ks -- quarter q with the k chunk of step 2 ks + (q & 1), lane half q >> 1, i.e. chunk
+    // 4 ks + 2 (q & 1) + (q >> 1) of W3's image, which is how the loop reads its B fragments (the image keeps its order).
+    // 16 swaps per point block, once per tile; the per-point reductions above ran on conv2's layout.
+#pragma unroll
+    for (int pb = 0; pb < NPB; ++pb)
+#pragma unroll
+        for (int ks = 0; ks < 4; ++ks) {
+            uint4 x = __builtin_bit_cast(uint4, a3[pb][2 * ks]), y = __builtin_bit_cast(uint4, a3[pb][2 * ks + 1]);
+            unsigned* xp = reinterpret_cast<unsigned*>(&x);
+            unsigned* yp = reinterpret_cast<unsigned*>(&y);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const auto sw = __builtin_amdgcn_permlane16_swap(xp[j], yp[j], false, false);
+                xp[j] = sw[0];
+                yp[j] = sw[1];
+            }
+            a3[pb][2 * ks] = __builtin_bit_cast(qf16x8, x);
+            a3[pb][2 * ks + 1] = __builtin_bit_cast(qf16x8, y);
+        }
+    const int l16 = lane & 15, q4 = lane >> 4;             // conv3: column (channel of a column block) and lane quarter
     // conv3's first W3 chunk: requested BEFORE the three atomics below -- the wait for these loads then leaves the atomics (younger,
     // in the in-order counter) pending instead of sitting out their round trip (600 .. 3 000 cycles each under load)
     const char* w3h = w3f;
     W3Regs wreg = w3_load(w3h, 0, wave, lane);
     const bool any_bad = __any(badpt);
+    static_assert(F_SLOT == PN_GROUPS * 2 * 64, "ring slot: a pair of 64 channels per group");
     if (lane == 0) {              // per-tile maxima; non-negative floats (and NaN, above all of them) order as integers
         const float dmx = sqrtf(dn2), rdm = sqrtf(rn2) / s_w;
         const float hm = (dmx + cnorm) * 1.0001f;          // |h_p| <= |h_p - c| + |c|
@@ -464,23 +480,23 @@ __global__ __launch_bounds__(256, 2) void pn_trunk_filter_kernel(const float* __
             }
         }
     }
-    // Per channel of chunk c the publishing wave merges the sorted PAIRS of the sixteen 16-point groups (4 waves x 2 point blocks x 2
-    // lane halves) into the tile's FIVE largest id-carrying scores (real units: three + the flags in a 16-byte record, the fourth and
+    // Per channel of chunk c the publishing wave merges the sorted PAIRS of the sixteen 16-point groups (4 waves x 4 lane
+    // quarters) into the tile's FIVE largest id-carrying scores (real units: three + the flags in a 16-byte record, the fourth and
     // fifth in an 8-byte one that pn_exact_kernel reads only where the third is in range) and one flag per group "may hold a point
     // within 2 E of the tile's largest score that is not among the five".  The ring holds four chunks: after chunks 3, 7, 11 and 15
     // every wave publishes one (all four busy at the same time: no wave waits for a publisher at the chunk barriers).
     auto publish = [&](int c) {
-        const float* src = tb + (c & 3) * F_SLOT;          // [wave][point block][half][k][channel]: every lane's own sorted pair, as finish() left it
+        const float* src = tb + (c & 3) * F_SLOT;          // [wave][lane quarter][k][channel]: every lane's own sorted pair, as finish() left it
         const float ti = tis[64 * c + lane];
-        // all sixteen pairs first (one trip to the LDS), in real units, with the rest of their ids: bits [4:0] point block + register
-        // (the chain's), 5 lane half, [7:6] wave
-        constexpr int NG = TAIL ? 2 : 16;                  // groups: 4 w + 2 pb + hh (TAIL: the publishing wave's two lane halves, "wave 0")
+        // all sixteen pairs first (one trip to the LDS), in real units, with the rest of their ids: bits [3:0] row block + register
+        // (the chain's), [5:4] lane quarter, [7:6] wave (pn_slots.h)
+        constexpr int NG = TAIL ? 4 : PN_GROUPS;           // groups: 4 w + quarter (TAIL: the publishing wave's four lane quarters, "wave 0")
         float t1[NG], t2[NG];
 #pragma unroll
         for (int gi = 0; gi < NG; ++gi) {
-            const int w = TAIL ? 0 : gi >> 2, pb = TAIL ? 0 : (gi >> 1) & 1, hh = gi & 1;
+            const int w = TAIL ? 0 : gi >> 2, qq = gi & 3;
             const int ws = TAIL ? wave : w;                // whose pairs (TAIL: one wave = the whole tile)
-            const float* q = src + (((ws * 2 + pb) * 2 + hh) * 2) * 64 + lane;
+            const float* q = src + ((ws * 4 + qq) * 2) * 64 + ((lane + 16 * qq) & 63);   // finish()'s rotation
             t1[gi] = q[0];
             t2[gi] = q[64];
         }
@@ -493,14 +509,14 @@ __global__ __launch_bounds__(256, 2) void pn_trunk_filter_kernel(const float* __
         for (int gi = 0; gi + 1 < NG; gi += 2)             // v_xor_b32 + v_or3_b32 per two groups
             tagdiff = tagdiff | (__float_as_uint(t1[gi]) ^ (unsigned)(((c >> 2) & 3) << 5)) | (__float_as_uint(t1[gi]) ^ __float_as_uint(t1[gi + 1]));
         const bool suspect = (tagdiff & 0x60u) != 0;
-        unsigned tag_mask = ~0xE0u;
+        unsigned tag_mask = ~0xF0u;
         asm volatile("" : "+v"(tag_mask));
 #pragma unroll
         for (int gi = 0; gi < NG; ++gi) {
-            const int w = TAIL ? 0 : gi >> 2, hh = gi & 1;
+            const int w = TAIL ? 0 : gi >> 2, qq = gi & 3;
             const float sc = scs[TAIL ? wave : w] * ti;     // a power of two
-            unsigned tag;                                   // (w << 6) | (hh << 5) as a SCALAR and the mask in a vector register: one
-            asm("s_mov_b32 %0, %1" : "=s"(tag) : "i"((w << 6) | (hh << 5)));   // v_and_or_b32 per value instead of v_and + v_or
+            unsigned tag;                                   // pn_group_tag(w, qq) as a SCALAR and the mask in a vector register: one
+            asm("s_mov_b32 %0, %1" : "=s"(tag) : "i"((w << 6) | (qq << 4)));   // v_and_or_b32 per value instead of v_and + v_or
             t1[gi] = __uint_as_float((__float_as_uint(t1[gi] * sc) & tag_mask) | tag);
             t2[gi] = __uint_as_float((__float_as_uint(t2[gi] * sc) & tag_mask) | tag);
         }
@@ -516,7 +532,7 @@ __global__ __launch_bounds__(256, 2) void pn_trunk_filter_kernel(const float* __
             c3 = __builtin_amdgcn_fmed3f(c2, c3, x); c2 = __builtin_amdgcn_fmed3f(c1, c2, x);
         }
         const float thr = c1 - e2;                         // NaN -> no flag here; pn_exact_kernel sees the non-finite bound
-        // bit 4 w + 2 pb + h: that 16-point group may hold a point in range that is not among the five: its SECOND is in range (a
+        // bit 4 w + quarter: that 16-point group may hold a point in range that is not among the five: its SECOND is in range (a
         // third could be: the lanes keep two), or its first is in range and was not kept (six in range in the tile).  With t1 >= t2
         // that is "u >= thr" for u = t1 if t1 was not kept (t1 < c5), else t2 -- no branches, no second trip to the LDS.
         unsigned flags = 0;
@@ -532,59 +548,77 @@ __global__ __launch_bounds__(256, 2) void pn_trunk_filter_kernel(const float* __
             part2[rec * 1024 + 64 * c + lane] = qf32x2{c4, c5};
         }
     };
-    // one 32-point x 32-channel block: 8 MFMAs; its 16 scores per lane go through the top-two chain (3 vector instructions per
-    // score) while the NEXT block's MFMAs run: 1 MFMA (32 cycles of the matrix pipe) per 6 chain instructions
-#define F_MFMA_BLOCK(ACC, PB, WF)                                                                              \
+    // one column block of a chunk: 16 channels x the wave's NRB row blocks of 16 points, K = 128 in four steps of
+    // v_mfma_f32_16x16x32_f16 (4 passes each: 16 MFMAs are the matrix cycles of eight 32x32x16) -- NRB accumulators of four registers;
+    // the fragment of row block rb and step ks is a3[rb >> 1][2 ks + (rb & 1)] (see the swaps above).  The lane's 4 NRB scores
+    // (ONE channel, rows 4 q + e of every row block) go through the top-two chain (2.5 vector instructions per score) while the
+    // NEXT column block's MFMAs run: 16 MFMAs per 40 chain instructions
+    constexpr int NRB = TAIL ? 2 : 4;                      // 16-point row blocks per wave
+#define F_MFMA_BLOCK(ACC, WF)                                                                                  \
     do {                                                                                                       \
-        _Pragma("unroll") for (int e = 0; e < 16; ++e) ACC[e] = 0.f;                                           \
-        _Pragma("unroll") for (int s = 0; s < 8; ++s)                                                          \
-            ACC = __builtin_amdgcn_mfma_f32_32x32x16_f16(a3[PB][s], WF[s], ACC, 0, 0, 0);                      \
+        _Pragma("unroll") for (int rb = 0; rb < NRB; ++rb) ACC[rb] = f32x4{0.f, 0.f, 0.f, 0.f};                \
+        _Pragma("unroll") for (int ks = 0; ks < 4; ++ks)                                                       \
+            _Pragma("unroll") for (int rb = 0; rb < NRB; ++rb)                                                 \
+                ACC[rb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a3[rb >> 1][2 * ks + (rb & 1)], WF[ks], ACC[rb], 0, 0, 0); \
     } while (0)
-    /* CT: the ring tag of the chunk (bits [6:5], uniform): set HERE, with the id, by the one instruction per score that is needed    */ \
-    /* anyway -- finish() used to set it on the block's winner with an instruction of its own                                        */
-#define F_CHAIN_BLOCK(ACC, PB, M1, M2, CT)                                                                     \
+    /* CT: id (4 rb + e, pn_chain_id) | the ring tag of the chunk (bits [6:5], uniform): set HERE, with the id, by the one instruction */ \
+    /* per score that is needed anyway -- finish() used to set the tag on the block's winner with an instruction of its own           */
+#define F_CHAIN_BLOCK(ACC, M1, M2, CT)                                                                         \
     do {                                                                                                       \
-        if (abl & 128) { M1 = ACC[0]; M2 = ACC[15]; } else   /* timing only: no chain */                       \
+        if (abl & 128) { M1 = ACC[0][0]; M2 = ACC[NRB - 1][3]; } else   /* timing only: no chain */            \
         {                                                                                                      \
             /* round 6: groups of three -- v_max3 / v_med3 give a group's two largest, merged into the running pair by          */ \
             /* second = med3(M1, g1, max(M2, g2)): 40 instead of 48 instructions per 16 scores, the same pair                    */ \
-            float x_[16];                                                                                      \
-            _Pragma("unroll") for (int e = 0; e < 16; ++e)                                                     \
-                x_[e] = __uint_as_float((__float_as_uint(ACC[e]) & id_mask) | (CT)[16 * (PB) + e]);           \
+            constexpr int NS_ = 4 * NRB;                                                                       \
+            float x_[NS_];                                                                                     \
+            _Pragma("unroll") for (int e = 0; e < NS_; ++e)                                                    \
+                x_[e] = __uint_as_float((__float_as_uint(ACC[e >> 2][e & 3]) & id_mask) | (CT)[e]);           \
             M1 = fmaxf(fmaxf(x_[0], x_[1]), x_[2]);                                                            \
             M2 = __builtin_amdgcn_fmed3f(x_[0], x_[1], x_[2]);                                                 \
-            _Pragma("unroll") for (int g = 3; g < 15; g += 3) {                                                \
+            _Pragma("unroll") for (int g = 3; g + 2 < NS_; g += 3) {                                           \
                 const float g1_ = fmaxf(fmaxf(x_[g], x_[g + 1]), x_[g + 2]);                                   \
                 const float g2_ = max_nc(M2, __builtin_amdgcn_fmed3f(x_[g], x_[g + 1], x_[g + 2]));            \
                 M2 = __builtin_amdgcn_fmed3f(M1, g1_, g2_);                                                    \
                 M1 = max_nc(M1, g1_);                                                                          \
             }                                                                                                  \
-            M2 = __builtin_amdgcn_fmed3f(M1, M2, x_[15]);                                                      \
-            M1 = max_nc(M1, x_[15]);                                                                           \
+            _Pragma("unroll") for (int e = 3 * (NS_ / 3); e < NS_; ++e) {                                      \
+                M2 = __builtin_amdgcn_fmed3f(M1, M2, x_[e]);                                                   \
+                M1 = max_nc(M1, x_[e]);                                                                        \
+            }                                                                                                  \
         }                                                                                                      \
     } while (0)
+    /* twice as many, half as long MFMAs as on 32x32x16: one MFMA per 2.5 chain instructions */
 #define F_INTERLEAVE()                                                                                         \
     do {                                                                                                       \
-        _Pragma("unroll") for (int i = 0; i < 8; ++i) {                                                        \
+        _Pragma("unroll") for (int i = 0; i < 2 * NRB; ++i) {                                                  \
             __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                                                 \
-            __builtin_amdgcn_sched_group_barrier(0x002, 5, 0);                                                 \
+            __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);                                                 \
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                                                 \
+            __builtin_amdgcn_sched_group_barrier(0x002, 3, 0);                                                 \
         }                                                                                                      \
     } while (0)
-    // every lane hands its own sorted pair of a block over (16 points of one channel); the publishing wave merges the sixteen groups
-    // of a (tile, channel) -- one lane per channel there
-    auto finish = [&](int c, int jn, int pb, float m1, float m2) {
-        if ((abl & 65536) && c == 9 && wave == 2 && jn == 0) return;   // diagnostics: a hand-over that does not happen
-        float* dst = tb + (c & 3) * F_SLOT + ((wave * 2 + pb) * 2 + h) * 128 + 32 * jn + r;
+    // every lane hands its own sorted pair of a column block over (its NRB x 4 points of one channel); the publishing wave merges the
+    // sixteen groups of a (tile, channel) -- one lane per channel there
+    // (a group's row of 64 channels is rotated by 16 per lane quarter: the quarters of a store then hit different banks)
+    const int fin_row = (wave * 4 + q4) * 128, fin_rot = 16 * q4 + l16;
+    auto finish = [&](int c, int cb, float m1, float m2) {
+        if ((abl & 65536) && c == 9 && wave == 2 && cb == 0) return;   // diagnostics: a hand-over that does not happen
+        float* dst = tb + (c & 3) * F_SLOT + fin_row + ((16 * cb + fin_rot) & 63);
         dst[0] = m1;                                        // bits [6:5] of both: the chunk's ring tag (F_CHAIN_BLOCK), checked by publish()
         dst[64] = m2;
     };
     // (the mask in a vector register: id | tag is a scalar, and one v_and_or_b32 takes one scalar operand)
     unsigned id_mask = ~127u;
     asm volatile("" : "+v"(id_mask));
+    // B fragments of a chunk: column block cb, step ks -- channel row 16 cb + l16, chunk 4 ks + 2 (q & 1) + (q >> 1) of the row (the
+    // k the swapped A fragment holds in this quarter).  Conflict-free under the image's swizzle (chunk ^ (row & 15)): a 16-lane
+    // group of a ds_read_b128 ({0-3, 12-15, 20-27}, ...) covers rows {0-3, 12-15} of one chunk and rows {4-11} of the chunk 2 further
+    // -- chunk ^ row takes sixteen different values.
+    const int qchunk = 2 * (q4 & 1) + (q4 >> 1);
     int stage = 0;
     if constexpr (TAIL) {
-        // one point block per wave: two MFMA blocks (channels 0..31, 32..63) and two chains per chunk; every wave publishes the
-        // eight chunks of ITS sample after chunk 7 and after chunk 15
+        // one point block (two row blocks) per wave: four MFMA blocks of 8 and four chains of 8 scores per chunk; every wave
+        // publishes the eight chunks of ITS sample after chunk 7 and after chunk 15
 #pragma unroll 1
         for (int c = 0; c < 16; ++c) {
             dvq_lds_barrier();                              // chunk c is in its stage; the other stage and tb parity are free
@@ -595,39 +629,47 @@ __global__ __launch_bounds__(256, 2) void pn_trunk_filter_kernel(const float* __
                 dvq_lds_barrier();                          // before this chunk's pairs overwrite slot 0
             }
             const char* st = fl + stage * F_STAGE3;
-            qf16x8 wf0[8], wf1[8];
+            qf16x8 wf[4][4];
 #pragma unroll
-            for (int s = 0; s < 8; ++s) wf0[s] = w3_frag(st, r, 2 * s + h);
+            for (int cb = 0; cb < 4; ++cb)
 #pragma unroll
-            for (int s = 0; s < 8; ++s) wf1[s] = w3_frag(st, 32 + r, 2 * s + h);
-            f32x16 accA, accB;
-            float a1, a2, q1, q2;
-            F_MFMA_BLOCK(accA, 0, wf0);
-            F_MFMA_BLOCK(accB, 0, wf1);
-            unsigned ctag_c[32];                          // id | ring tag per accumulator register, as scalars (see sid4 below)
+                for (int ks = 0; ks < 4; ++ks) wf[cb][ks] = w3_frag(st, 16 * cb + l16, 4 * ks + qchunk);
+            f32x4 accA[NRB], accB[NRB];
+            float m1, m2;
+            unsigned ctag_c[16];                          // id | ring tag per accumulator register, as scalars (see ctag4 below)
 #pragma unroll
             for (int e = 0; e < 16; ++e) asm("s_or_b32 %0, %1, %2" : "=s"(ctag_c[e]) : "s"((unsigned)(((c >> 2) & 3) << 5)), "i"(e));
-            F_CHAIN_BLOCK(accA, 0, a1, a2, ctag_c);
+            F_MFMA_BLOCK(accA, wf[0]);
+            F_MFMA_BLOCK(accB, wf[1]);
+            F_CHAIN_BLOCK(accA, m1, m2, ctag_c);
             F_INTERLEAVE();
-            F_CHAIN_BLOCK(accB, 0, q1, q2, ctag_c);
-            finish(c, 0, 0, a1, a2);
-            finish(c, 1, 0, q1, q2);
+            finish(c, 0, m1, m2);
+            F_MFMA_BLOCK(accA, wf[2]);
+            F_CHAIN_BLOCK(accB, m1, m2, ctag_c);
+            F_INTERLEAVE();
+            finish(c, 1, m1, m2);
+            F_MFMA_BLOCK(accB, wf[3]);
+            F_CHAIN_BLOCK(accA, m1, m2, ctag_c);
+            F_INTERLEAVE();
+            finish(c, 2, m1, m2);
+            F_CHAIN_BLOCK(accB, m1, m2, ctag_c);
+            finish(c, 3, m1, m2);
             if (c + 1 < 16) w3_store(fl + (stage ^ 1) * F_STAGE3, wave, lane, wreg);
             stage ^= 1;
         }
     } else {
-    f32x16 accP;                                          // the chunk's last accumulator block, scored under the next chunk's first MFMAs
+    f32x4 accP[NRB];                                      // the chunk's last accumulator block, scored under the next chunk's first MFMAs
     // Four chunks per trip of the rolled loop, the four written out: the ring slot (c & 3), the stage (c & 1), "is a chain pending"
     // and "is this a publishing chunk" are compile-time constants then -- LDS addresses become instruction offsets instead of vector
     // additions per access, the conditions disappear (round 5: the kernel is vector-issue bound).
 #pragma unroll 1
     for (int c4 = 0; c4 < ((abl & 2) ? 0 : 16); c4 += 4) {
-    // id (point block, register) | ring tag of this trip's four chunks, one SCALAR per accumulator register: the chain's one instruction
+    // id (row block, register) | ring tag of this trip's four chunks, one SCALAR per accumulator register: the chain's one instruction
     // per score is then v_and_or_b32 (score, mask in a vector register, this scalar).  (Written as "id | tag" in the expression the
     // compiler makes it v_and_b32 + v_or3_b32: two vector instructions per score.)
-    unsigned ctag4[32];
+    unsigned ctag4[16];
 #pragma unroll
-    for (int e = 0; e < 32; ++e) asm("s_or_b32 %0, %1, %2" : "=s"(ctag4[e]) : "s"((unsigned)(((c4 >> 2) & 3) << 5)), "i"(e));
+    for (int e = 0; e < 16; ++e) asm("s_or_b32 %0, %1, %2" : "=s"(ctag4[e]) : "s"((unsigned)(((c4 >> 2) & 3) << 5)), "i"(e));
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
         const int c = c4 + u;
@@ -640,41 +682,41 @@ __global__ __launch_bounds__(256, 2) void pn_trunk_filter_kernel(const float* __
             dvq_lds_barrier();                              // before this chunk's pairs overwrite slot 0
         }
         const char* st = fl + stage * F_STAGE3;
-        qf16x8 wf0[8], wf1[8];
+        qf16x8 wf[4][4];
 #pragma unroll
-        for (int s = 0; s < 8; ++s) wf0[s] = w3_frag(st, r, 2 * s + h);
+        for (int cb = 0; cb < 4; ++cb)
 #pragma unroll
-        for (int s = 0; s < 8; ++s) wf1[s] = w3_frag(st, 32 + r, 2 * s + h);
-        // Four MFMA blocks and four chain blocks per chunk, each chain under the MFMAs of the block that follows its own.  The last
-        // chain of a chunk (second point block x channels 32..63: accP) has no successor inside the chunk: it runs under the FIRST
-        // MFMA block of the next chunk (8 dependent MFMAs that had nothing to cover them), except before a publish (c = 3, 7, 11, 15).
-        f32x16 accA, accB;
+            for (int ks = 0; ks < 4; ++ks) wf[cb][ks] = w3_frag(st, 16 * cb + l16, 4 * ks + qchunk);
+        // Four MFMA blocks (column blocks) and four chain blocks per chunk, each chain under the MFMAs of the block that follows its
+        // own.  The last chain of a chunk (channels 48..63: accP) has no successor inside the chunk: it runs under the FIRST MFMA
+        // block of the next chunk, except before a publish (c = 3, 7, 11, 15).
+        f32x4 accA[NRB], accB[NRB];
         float m1, m2;
-        F_MFMA_BLOCK(accA, 0, wf0);
+        F_MFMA_BLOCK(accA, wf[0]);
         if (pending) {
-            F_CHAIN_BLOCK(accP, 1, m1, m2, ctag4);
+            F_CHAIN_BLOCK(accP, m1, m2, ctag4);
             F_INTERLEAVE();
-            if (!(abl & 512)) finish(c - 1, 1, 1, m1, m2);
+            if (!(abl & 512)) finish(c - 1, 3, m1, m2);
             else if (m1 + m2 == 12345.f) tb[lane] = m1;
         }
-        F_MFMA_BLOCK(accB, 1, wf0);
-        F_CHAIN_BLOCK(accA, 0, m1, m2, ctag4);
+        F_MFMA_BLOCK(accB, wf[1]);
+        F_CHAIN_BLOCK(accA, m1, m2, ctag4);
         F_INTERLEAVE();
-        if (!(abl & 512)) finish(c, 0, 0, m1, m2);
+        if (!(abl & 512)) finish(c, 0, m1, m2);
         else if (m1 + m2 == 12345.f) tb[lane] = m1;
-        F_MFMA_BLOCK(accA, 0, wf1);
-        F_CHAIN_BLOCK(accB, 1, m1, m2, ctag4);
+        F_MFMA_BLOCK(accA, wf[2]);
+        F_CHAIN_BLOCK(accB, m1, m2, ctag4);
         F_INTERLEAVE();
-        if (!(abl & 512)) finish(c, 0, 1, m1, m2);
+        if (!(abl & 512)) finish(c, 1, m1, m2);
         else if (m1 + m2 == 12345.f) tb[lane] = m1;
-        F_MFMA_BLOCK(accP, 1, wf1);
-        F_CHAIN_BLOCK(accA, 0, m1, m2, ctag4);
+        F_MFMA_BLOCK(accP, wf[3]);
+        F_CHAIN_BLOCK(accA, m1, m2, ctag4);
         F_INTERLEAVE();
-        if (!(abl & 512)) finish(c, 1, 0, m1, m2);
+        if (!(abl & 512)) finish(c, 2, m1, m2);
         else if (m1 + m2 == 12345.f) tb[lane] = m1;
         if (u == 3) {                                     // nothing to cover it before a publish
-            F_CHAIN_BLOCK(accP, 1, m1, m2, ctag4);
-            if (!(abl & 512)) finish(c, 1, 1, m1, m2);
+            F_CHAIN_BLOCK(accP, m1, m2, ctag4);
+            if (!(abl & 512)) finish(c, 3, m1, m2);
             else if (m1 + m2 == 12345.f) tb[lane] = m1;
         }
         if (c + 1 < 16 && !(abl & 1024)) w3_store(fl + (stage ^ 1) * F_STAGE3, wave, lane, wreg);
@@ -875,7 +917,7 @@ __global__ __launch_bounds__(256, 4) void pn_exact_kernel(const f32x4* __restric
             // the tile's largest score is out of range: so is the rest of it -- unless the record is suspect: then its scores prove
             // nothing about the tile and all its points are evaluated (a bogus top score that RAISES lb is caught by the check below)
             if (!suspect && !(q[0] + et >= lb)) return;
-            unsigned flags = __float_as_uint(q[3]) & 0xFFFFu;   // one bit per 16-point group: 4 wave + 2 point block + lane half
+            unsigned flags = __float_as_uint(q[3]) & 0xFFFFu;   // one bit per 16-point group: 4 wave + lane quarter (pn_slots.h)
             // a kept score in range: its point becomes a candidate of the channel.  (No search for a point that is already one: only
             // padding slots repeat a point, a repeated candidate costs one more dot, and the search was a third of this phase.)
             auto take = [&](float v) {
@@ -888,7 +930,7 @@ __global__ __launch_bounds__(256, 4) void pn_exact_kernel(const f32x4* __restric
                     if (slot < pair_cap) pair_list[slot] = n | (p << 10);
                     else {                                       // list full (never seen): evaluate its 16-point group instead
                         const unsigned id = __float_as_uint(v);
-                        flags |= 1u << (4 * ((id >> 6) & 3u) + 2 * ((id >> 4) & 1u) + ((id >> 5) & 1u));
+                        flags |= 1u << pn_group_of_id(id);
                     }
                 }
                 ++cands;
@@ -902,7 +944,7 @@ __global__ __launch_bounds__(256, 4) void pn_exact_kernel(const f32x4* __restric
                 take(v);
             }
             while (flags) {
-                const int wh = __ffs(flags) - 1;             // 4 * wave + 2 * point block + lane half
+                const int wh = __ffs(flags) - 1;             // the group: 4 * wave + lane quarter
                 flags &= flags - 1;
                 const int slot = atomicAdd(&fb_count, 1);
                 if (slot < fb_cap) fb_list[slot] = n | (t << 10) | (wh << 20);
@@ -1067,16 +1109,15 @@ __global__ __launch_bounds__(256, 4) void pn_exact_kernel(const f32x4* __restric
     const int nfb = (abl & 32) ? 0 : min(fb_count, fb_cap);
     for (int i = tid >> 6; i < nfb; i += 4) {
         const int code = fb_list[i];
-        const int n = code & 1023, t = (code >> 10) & 1023, w = (code >> 22) & 3, pb = (code >> 21) & 1, hh = (code >> 20) & 1;
+        const int n = code & 1023, t = (code >> 10) & 1023, grp = (code >> 20) & 15;
         const float* wr = reinterpret_cast<const float*>(reinterpret_cast<const char*>(w3) + ((unsigned)n * 512u + 16u * (unsigned)j));
         const f32x4 w0 = *reinterpret_cast<const f32x4*>(wr), w1 = *reinterpret_cast<const f32x4*>(wr + 64);
         float best = NEG_BIG;
         {
             f32x4 ha[4], hb[4];
 #pragma unroll
-            for (int u = 0; u < 4; ++u) {                   // this lane group's 4 of the group's 16 points (accumulator registers e)
-                const int e = 4 * (g & 3) + u;
-                int p = point_of_slot(t, 64 * w + 32 * pb + 8 * (e >> 2) + 4 * hh + (e & 3), deal);   // tail tile: one block, pb = 0
+            for (int u = 0; u < 4; ++u) {                   // this lane group's 4 of the group's 16 points: row block g & 3, register u
+                int p = point_of_slot(t, pn_group_slot(grp, 4 * (g & 3) + u), deal);   // tail tile: row blocks 2, 3 repeat 0, 1
                 if (p >= N) p %= N;
                 const float* hr = reinterpret_cast<const float*>(reinterpret_cast<const char*>(h2) + ((unsigned)p * 512u + 16u * (unsigned)j));
                 ha[u] = *reinterpret_cast<const f32x4*>(hr);

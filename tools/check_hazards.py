@@ -16,6 +16,7 @@ Rules (CDNA3 ISA guide section 4.5 "manually inserted wait states" and the gfx94
                                               (4 / 8 passes), 32x32 11 / 19 (8 / 16 passes)
   R8  VALU writes VCC                      -> v_div_fmas                                            4
   R9  SALU writes M0                       -> LDS DMA (buffer/global_load ... lds), s_sendmsg, ds_*_addtid 1
+  R10 VALU writes a VGPR                   -> v_permlane16_swap / v_permlane32_swap reads it (BOTH operands are read and written)  2
 Within a basic block the scan is exact; at a label the history is cleared when `--strict` is not given (a branch costs more than any
 of these counts), with `--strict` it is kept across fall-through edges.
 
@@ -142,6 +143,8 @@ def check_lines(lines, strict=False, name="?"):
                 src = set().union(*[regs(o) for o in ops]) if ops else set()
             elif op.startswith(("v_readlane", "v_readfirstlane")):
                 dst = regs(ops[0]); src = set().union(*[regs(o) for o in ops[1:]])
+            elif op.startswith(("v_permlane16_swap", "v_permlane32_swap")):
+                dst = set().union(*[regs(o) for o in ops[:2]]); src = set(dst)     # an exchange: both registers are read and written
             else:
                 dst = regs(ops[0]) if ops else set()
                 src = set().union(*[regs(o) for o in ops[1:]]) if len(ops) > 1 else set()
@@ -195,6 +198,8 @@ def check_lines(lines, strict=False, name="?"):
                     viol("R6", h, 1)
                 if op.startswith("v_div_fmas") and a < 4 and ("vcc",) in h["dst"]:
                     viol("R8", h, 4)
+                if op.startswith(("v_permlane16_swap", "v_permlane32_swap")) and a < 2 and {r for r in h["dst"] if r[0] == "v"} & src:
+                    viol("R10", h, 2)
             elif h["kind"] == "mfma":
                 need = MFMA_WAIT[h["passes"]]
                 d = {r for r in h["dst"] if r[0] in ("v", "a")}
