@@ -97,6 +97,17 @@ struct DvqOncePerDevice {
         if (rc__ != DVQ_OK) return rc__; \
     } while (0)
 
+// Raises the dynamic-LDS limit of `kernel` to `bytes`, once per device (`once`: a static of the calling launcher, one per kernel).
+// `file` names the caller in the error message.
+static inline int dvq_lds_limit(DvqOncePerDevice& once, const void* kernel, size_t bytes, const char* file) {
+    const hipError_t e = once.run([&] { return hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes); });
+    if (e != hipSuccess) {
+        dvq_set_error("%s: hipFuncSetAttribute failed: %s", file, hipGetErrorString(e));
+        return DVQ_ELAUNCH;
+    }
+    return DVQ_OK;
+}
+
 static inline bool dvq_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 static inline size_t dvq_round_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
@@ -206,24 +217,24 @@ int dvq_launch_gemm_f16x2_gate_group(const GemmParams* ps, int n, hipStream_t st
 // 0 = fp32 MFMA (v_mfma_f32_32x32x2_f32), 1 = split-bf16 (default); env DVQ_GEMM=fp32|bf16x3
 int dvq_gemm_mode();
 
-// Behaviour knobs read from the environment ONCE (first use) -- DVQ_GEMM_WIDE, DVQ_GEMM_DEPHASE, DVQ_GEMM_TN, DVQ_GEMM_SKINNY, DVQ_PN_FILTER, DVQ_PN_EXHAUSTIVE,
-// DVQ_PN_CAPS, DVQ_PN_CHUNK, DVQ_PN_STATS, DVQ_PIXELCNN_CHUNK -- none of them changes a result (tile shapes, chunk sizes, the
-// exhaustive PointNet evaluation the filter is tested against).  dvq_reload_env() re-reads them (tests flip them in-process).
+// Behaviour knobs read from the environment ONCE (first use; every field names its variable).  None of them changes a result: tile
+// shapes, chunk sizes, the exhaustive PointNet evaluation the filter is tested against.  dvq_reload_env() re-reads them (tests flip
+// them in-process).
 struct DvqKnobs {
-    int gemm_wide;        // 0: 128 x 128 kernels only
-    int gemm_dephase;     // 0: the wide bf16x3 kernel's lock-step schedule (DVQ_GEMM_DEPHASE=0; launch_wide only)
-    int gemm_tn;          // 0 (default): the tiled f16x2 kernel picks 128 x 256 or 128 x 128 tiles per launch; 128 / 256 force one (DVQ_GEMM_TN)
-    int gemm_skinny;      // 0: tiled kernels also for M <= 256 (DVQ_GEMM_SKINNY=0; the two must agree bitwise)
-    int pn_filter;        // 0 six-product trunk, 1 default, 2 filtered trunk whatever the tile fill
-    int pn_tail;          // 1 (default): a cloud's 1 .. 32 points beyond a multiple of 256 as a one-block tail tile (DVQ_PN_TAIL=0: a full tile)
-    int pn_exhaustive;    // 1: exact stage evaluates every point (what the filter must reproduce bit for bit)
-    int pn_caps[2];       // candidate-list capacities (tests shrink them to reach the overflow paths); <= 0: default
-    long pn_chunk;        // samples per PointNet launch (<= 0: at most 4 096, at least four launches per pass; DVQ_PN_CHUNK)
-    int pn_streams;       // 1 (default): the exact stage / STN FCs of a launch on a second stream beside the next launch's trunk kernel (DVQ_PN_STREAMS=0: one stream)
-    int pn_slots;         // scratch sets the launches rotate through (<= 0: 2; DVQ_PN_SLOTS)
-    int pn_stats;
-    long pixelcnn_chunk;  // <= 0: default
-    int pixelcnn_tables;  // 1 (default): what depends on the class label only is evaluated once per class (DVQ_PIXELCNN_TABLES=0: per row)
+    int gemm_wide;        // DVQ_GEMM_WIDE=0: 128 x 128 kernels only
+    int gemm_dephase;     // DVQ_GEMM_DEPHASE=0: the wide bf16x3 kernel's lock-step schedule (launch_wide only)
+    int gemm_tn;          // DVQ_GEMM_TN: 0 (default): the tiled f16x2 kernel picks 128 x 256 or 128 x 128 tiles per launch; 128 / 256 force one
+    int gemm_skinny;      // DVQ_GEMM_SKINNY=0: tiled kernels also for M <= 256 (the two must agree bitwise)
+    int pn_filter;        // DVQ_PN_FILTER: 0 six-product trunk, 1 default, 2 filtered trunk whatever the tile fill
+    int pn_tail;          // DVQ_PN_TAIL: 1 (default): a cloud's 1 .. 32 points beyond a multiple of 256 as a one-block tail tile; 0: a full tile
+    int pn_exhaustive;    // DVQ_PN_EXHAUSTIVE=1: exact stage evaluates every point (what the filter must reproduce bit for bit)
+    int pn_caps[2];       // DVQ_PN_CAPS=a,b: candidate-list capacities (tests shrink them to reach the overflow paths); < 0: default
+    long pn_chunk;        // DVQ_PN_CHUNK: samples per PointNet launch (<= 0: at most 4 096, at least four launches per pass)
+    int pn_streams;       // DVQ_PN_STREAMS: 1 (default): the exact stage / STN FCs of a launch on a second stream beside the next launch's trunk kernel; 0: one stream
+    int pn_slots;         // DVQ_PN_SLOTS: scratch sets the launches rotate through (<= 0: 2)
+    int pn_stats;         // DVQ_PN_STATS set: candidate statistics of the exact stage on stderr (synchronises; one stream)
+    long pixelcnn_chunk;  // DVQ_PIXELCNN_CHUNK; <= 0: default
+    int pixelcnn_tables;  // DVQ_PIXELCNN_TABLES: 1 (default): what depends on the class label only is evaluated once per class; 0: per row
 };
 const DvqKnobs& dvq_knobs();
 // simple helpers implemented in misc.hip

@@ -444,7 +444,7 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16x3_dma_kernel(const GemmParam
 template <int EPI>
 int launch_dma(const GemmParams& p, hipStream_t stream) {
     static DvqOncePerDevice attr_once;
-    DVQ_PROPAGATE(gemm_lds_limit(attr_once, reinterpret_cast<const void*>(&gemm_bf16x3_dma_kernel<EPI>), D_SMEM, "gemm_bf16x3"));
+    DVQ_PROPAGATE(dvq_lds_limit(attr_once, reinterpret_cast<const void*>(&gemm_bf16x3_dma_kernel<EPI>), D_SMEM, "gemm_bf16x3"));
     const long grid = gemm_padded_grid((p.M + BM - 1) / BM, (p.N + BN - 1) / BN);
     const double ksum = gemm_ksum(p);
     static unsigned long long* clk_buf = nullptr;
@@ -654,7 +654,7 @@ int launch_wide(const GemmParams& p, hipStream_t stream) {
     static DvqOncePerDevice attr_once[2];
     const void* const kernel = dephase ? reinterpret_cast<const void*>(&gemm_bf16x3_wide_kernel<EPI, true>)
                                        : reinterpret_cast<const void*>(&gemm_bf16x3_wide_kernel<EPI, false>);
-    DVQ_PROPAGATE(gemm_lds_limit(attr_once[dephase], kernel, W_SMEM, "gemm_bf16x3"));
+    DVQ_PROPAGATE(dvq_lds_limit(attr_once[dephase], kernel, W_SMEM, "gemm_bf16x3"));
     const long grid = gemm_padded_grid((p.M + 127) / 128, p.N / 256);
     const double ksum = gemm_ksum(p);
     {
@@ -1015,7 +1015,7 @@ constexpr long SKINNY_MAX_M = 256;     // above this the tiled kernels win (ever
 template <int EPI>
 int launch_skinny(const GemmParams& p, hipStream_t stream) {
     static DvqOncePerDevice attr_once;
-    DVQ_PROPAGATE(gemm_lds_limit(attr_once, reinterpret_cast<const void*>(&gemm_bf16x3_skinny2_kernel<EPI>), SK2_SMEM, "gemm_bf16x3"));
+    DVQ_PROPAGATE(dvq_lds_limit(attr_once, reinterpret_cast<const void*>(&gemm_bf16x3_skinny2_kernel<EPI>), SK2_SMEM, "gemm_bf16x3"));
     const double ksum = gemm_ksum(p);
     {
         DVQ_PROF(gemm_prof_name(EPI, 0), 2.0 * (double)p.M * p.N * ksum, ((double)p.M + p.N) * ksum * 4, stream);
@@ -1045,7 +1045,7 @@ __global__ void split_bf16x3_kernel(const float* __restrict__ w, long n, uint16_
 template <int EPI, bool WPLANES>
 int launch(const GemmParams& p, hipStream_t stream) {
     static DvqOncePerDevice attr_once;
-    DVQ_PROPAGATE(gemm_lds_limit(attr_once, reinterpret_cast<const void*>(&gemm_bf16x3_kernel<EPI, WPLANES>), SMEM_BYTES, "gemm_bf16x3"));
+    DVQ_PROPAGATE(dvq_lds_limit(attr_once, reinterpret_cast<const void*>(&gemm_bf16x3_kernel<EPI, WPLANES>), SMEM_BYTES, "gemm_bf16x3"));
     const long grid = gemm_padded_grid((p.M + BM - 1) / BM, (p.N + BN - 1) / BN);
     const double ksum = gemm_ksum(p);
     {

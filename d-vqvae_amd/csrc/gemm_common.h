@@ -236,14 +236,3 @@ static inline const char* gemm_prof_name(int epi, int prof_cls) {
 // Workgroups of the XCD-aware block -> tile map (blocks b and b + 8 share an XCD; row panel = 8 * (j / tiles_n) + b % 8 with
 // j = b / 8): the row panels are padded to a multiple of eight, the surplus blocks return at once.
 static inline long gemm_padded_grid(long tiles_m, long tiles_n) { return (tiles_m + 7) / 8 * 8 * tiles_n; }
-
-// Raises the dynamic-LDS limit of `kernel` to `bytes`, once per device (`once`: a static of the calling launcher, one per kernel).
-// `file` names the caller in the error message.
-static inline int gemm_lds_limit(DvqOncePerDevice& once, const void* kernel, size_t bytes, const char* file) {
-    const hipError_t e = once.run([&] { return hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes); });
-    if (e != hipSuccess) {
-        dvq_set_error("%s: hipFuncSetAttribute failed: %s", file, hipGetErrorString(e));
-        return DVQ_ELAUNCH;
-    }
-    return DVQ_OK;
-}

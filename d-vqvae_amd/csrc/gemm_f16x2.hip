@@ -410,7 +410,7 @@ template <int EPI, int NJ, bool INIT>
 int launch_pp(const GemmParams& p, hipStream_t stream) {
     constexpr size_t smem = NJ == 4 ? PP_SMEM : PP_SMEM_N128;
     static DvqOncePerDevice attr_once;
-    DVQ_PROPAGATE(gemm_lds_limit(attr_once, reinterpret_cast<const void*>(&gemm_f16x2_pp_kernel<EPI, NJ, INIT>), smem, "gemm_f16x2"));
+    DVQ_PROPAGATE(dvq_lds_limit(attr_once, reinterpret_cast<const void*>(&gemm_f16x2_pp_kernel<EPI, NJ, INIT>), smem, "gemm_f16x2"));
     const long grid = gemm_padded_grid((p.M + TM - 1) / TM, (p.N + 64 * NJ - 1) / (64 * NJ));
     const double ksum = gemm_ksum(p);
     {

@@ -144,7 +144,7 @@ inline long f32_grid(long tiles_m, long tiles_n) { return tiles_m < 8 ? tiles_m 
 template <int EPI>
 int launch(const GemmParams& p, hipStream_t stream) {
     static DvqOncePerDevice attr_once;
-    DVQ_PROPAGATE(gemm_lds_limit(attr_once, reinterpret_cast<const void*>(&gemm_f32_kernel<EPI>), SMEM_BYTES, "gemm"));
+    DVQ_PROPAGATE(dvq_lds_limit(attr_once, reinterpret_cast<const void*>(&gemm_f32_kernel<EPI>), SMEM_BYTES, "gemm"));
     const long grid = f32_grid((p.M + BM - 1) / BM, (p.N + BN - 1) / BN);
     const double ksum = gemm_ksum(p);
     {

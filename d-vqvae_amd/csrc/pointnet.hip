@@ -1,33 +1,18 @@
-// PointNet encoder (PointNetEncoder.forward, network/pointnet_encoder.py:140-169; STN3d.forward :27-45).
-// Default path: ONE fused trunk kernel per encoder pass (pn_trunk_kernel, below): conv1 (C -> 64, vector ALU, with the 3x3
-// input transform xyz @ trans) -> conv2 (64 -> 128) -> conv3 (128 -> 1024) -> max over the points, on the split-bf16
+// PointNet encoder (PointNetEncoder.forward, network/pointnet_encoder.py:140-169; STN3d.forward :27-45): its two passes (STN, main)
+// over the launches of a batch.  Default path: the FILTERED trunk of pointnet_filter.hip, front and back of a launch on two streams
+// (encode_two_streams, below); it takes clouds whose 256-point tiles are at least 3/4 full.
+// Other shapes, or weights without a filter image: ONE fused trunk kernel per pass (pn_trunk_kernel, below): conv1 (C -> 64, vector
+// ALU, with the 3x3 input transform xyz @ trans) -> conv2 (64 -> 128) -> conv3 (128 -> 1024) -> max over the points, on the split-bf16
 // (bf16x3) matrix-core arithmetic; no per-point activation ever leaves the CU, the kernel writes one row of column maxima
 // per 128 points and colmax_reduce_kernel finishes the max.  The STN's FC layers (1024 -> 512 -> 256 -> 9) use the GEMM.
 // With DVQ_GEMM=fp32 (exercised by tests/test_gpu_parity.py::test_fp32_gemm_branch_matches_goldens) the trunk runs
 // unfused instead: pn_layer1_kernel (vector ALU) + two fp32-MFMA GEMMs, the second with the column-max epilogue.
 // BatchNorm (eval) is folded into the weights by the packer (packing.py, fp64 fold, rounded once).
 #include "dvq_internal.h"
+#include "pn_filter.h"
 #include <map>
 #include <utility>
 #include <vector>
-
-int dvq_launch_pn_trunk(const float* pc, int C, int N, long B, const float* trans, const float* W1, const float* b1,
-                        const uint16_t* W2p, const float* b2, const uint16_t* W3p, const float* b3, float* partial,
-                        hipStream_t st);
-// pointnet_filter.hip
-size_t dvq_pn_filter_image_bytes();
-int dvq_launch_pn_filter_pack(const float* w2, const float* w3, void* image, hipStream_t st);
-int dvq_launch_pn_trunk_filter(const float* pc, int C, int N, int Npad, long B, const float* trans, const float* W1, const float* b1,
-                               const float* W2, const uint16_t* W2p, const float* b2, const void* w3f, const float* w3, const float* b3,
-                               int relu, float* h2buf, void* part, unsigned* tstat, float* cbuf, float* feat, long ld_feat,
-                               unsigned long long* stats, hipStream_t st);
-int dvq_launch_pn_filter_front(const float* pc, int C, int N, int Npad, long B, const float* trans, const float* W1, const float* b1,
-                               const float* W2, const uint16_t* W2p, const float* b2, const void* w3f, float* h2buf, void* part,
-                               unsigned* tstat, float* cbuf, unsigned long long* stats, hipStream_t st);
-int dvq_launch_pn_filter_back(int N, int Npad, long B, const void* w3f, const float* w3, const float* b3, int relu, const float* h2buf,
-                              const void* part, const unsigned* tstat, const float* cbuf, float* feat, long ld_feat, unsigned long long* stats,
-                              hipStream_t st);
-int dvq_pn_fault_counters(unsigned long long* out2, int reset);
 
 namespace {
 
@@ -68,27 +53,23 @@ __global__ void pn_layer1_kernel(const float* __restrict__ pc, int C, int N, int
 
 // Scratch of one encode call.  The filtered trunk works in LAUNCHES of ``chunk`` samples; a launch's trunk kernel ("front": centres,
 // conv1/conv2/conv3 filter, h2 rows + tile records) and its exact stage ("back": pn_exact_kernel, which reads them) use one of
-// ``slots`` scratch sets, so that the back of launch i can run on a second stream beside the front of launch i + 1 (below).
-struct PnSlot {
-    float *h2, *part, *cbuf;
-    unsigned* tstat;
-};
+// ``slots`` scratch sets (PnSlot; pn_filter.h defines their layout), so that the back of launch i can run on a second stream beside the
+// front of launch i + 1 (below).
 struct PnScratch {
     PnSlot slot[4];
     int slots;
     float *h1, *f0, *f1, *f2, *tr;
     unsigned long long* stats;
     long chunk;
-    int Npad;
+    PnGeometry g;
     size_t bytes;
 };
 
 PnScratch plan(int64_t B, int N, void* ws) {
-    PnScratch s;
-    s.Npad = (N + 255) / 256 * 256;                       // tiles of 128 (fused / unfused trunk) and of 256 (filtered trunk)
-    const size_t per_sample = (size_t)s.Npad * 128 * 4 + (size_t)s.Npad * 96 + (size_t)(s.Npad / 256) * 16 + 512;
+    PnScratch s = {};
+    s.g = pn_geometry(N, dvq_knobs().pn_tail != 0);       // Npad: tiles of 128 (fused / unfused trunk) and of 256 (filtered trunk); the sizes do not depend on the tail tile
     const size_t budget = (size_t)9 << 29;                // 4.5 GB per scratch set: 7 282 samples of 1 024 points
-    long chunk = (long)(budget / per_sample);
+    long chunk = (long)(budget / s.g.per_sample());
     {                                                     // samples per launch (DVQ_PN_CHUNK)
         const long v = dvq_knobs().pn_chunk;
         if (v > 0 && v < chunk) chunk = v;
@@ -110,17 +91,15 @@ PnScratch plan(int64_t B, int N, void* ws) {
     if (s.slots > 2 * launches) s.slots = (int)(2 * launches);
     char* p = (char*)ws;
     auto take = [&](size_t n) { char* q = p; p += dvq_round_up(n, 256); return (float*)q; };
-    for (int i = 0; i < 4; ++i) s.slot[i] = PnSlot{nullptr, nullptr, nullptr, nullptr};
+    const PnSetLayout l = pn_set_layout(s.g, (size_t)chunk);
     for (int i = 0; i < s.slots; ++i) {
-        s.slot[i].h2 = take((size_t)chunk * s.Npad * 128 * 4);
-        s.slot[i].part = take((size_t)chunk * s.Npad * 96);   // [tiles128][1024] floats, or [tiles256][1024] float4 + [tiles256][1024] float2
-        s.slot[i].tstat = (unsigned*)take((size_t)chunk * (s.Npad / 256) * 16);
-        s.slot[i].cbuf = take((size_t)chunk * 128 * 4);
+        char* set = (char*)take(l.bytes);
+        s.slot[i] = PnSlot{(float*)(set + l.h2), (float*)(set + l.part), (float*)(set + l.cbuf), set + l.part2, (unsigned*)(set + l.tstat)};
     }
     // conv1 rows of the UNFUSED trunk: DVQ_GEMM=fp32, or a weights struct without bf16 planes (include/dvq.h: the planes are optional).
     // That trunk runs on one stream and one scratch set, so with two sets it borrows the second set's conv2 rows (twice its size);
     // with one set (a single launch) it gets rows of its own.
-    s.h1 = s.slots >= 2 ? s.slot[1].h2 : take((size_t)chunk * s.Npad * 64 * 4);
+    s.h1 = s.slots >= 2 ? s.slot[1].h2 : take((size_t)chunk * s.g.Npad * 64 * 4);
     s.stats = (unsigned long long*)take(64);
     s.f0 = take((size_t)chunk * 1024 * 4);
     s.f1 = take((size_t)chunk * 512 * 4);
@@ -130,67 +109,70 @@ PnScratch plan(int64_t B, int N, void* ws) {
     return s;
 }
 
-int dense(const float* x, long ldx, int K, const float* w, const uint16_t* wp, const float* b, long M, int N, int relu,
-          float* y, long ldy, hipStream_t st) {
+// y [M][N] = act(x [M][K] @ w [N][K]^T + b), rows contiguous
+int dense(const float* x, int K, const float* w, const uint16_t* wp, const float* b, long M, int N, int relu, float* y, hipStream_t st) {
     GemmParams p = {};
-    p.src[0] = GemmSrc{x, w, ldx, (long)K, K, 0, wp, (long)N * K};
+    p.src[0] = GemmSrc{x, w, (long)K, (long)K, K, 0, wp, (long)N * K};
     p.nsrc = 1;
     p.M = M;
     p.N = N;
     p.bias = b;
     p.out = y;
-    p.ldo = ldy;
+    p.ldo = N;
     p.relu = relu;
     return dvq_launch_gemm(p, EPI_BIAS, st);
 }
 
-// DVQ_PN_FILTER: 0 = six-product trunk everywhere, 2 = filtered trunk whatever the fill of its tiles (tests), default 1
-int filter_mode() { return dvq_knobs().pn_filter; }
-
 // does the filtered trunk (pointnet_filter.hip) take this shape?  When its 256-point tiles are at least 3/4 full: padding slots repeat
 // real points, and many repeats mean many ties for the exact stage (N = 300 in two tiles: 4.6 ms against 3.6 ms for the six-product trunk)
 bool use_filter(const dvq_pointnet_weights* w, int N) {
-    const int fm = filter_mode();
-    const int tiles256 = (N + 255) / 256, over = N - 256 * (tiles256 - 1);
-    // slots the filtered trunk evaluates: whole tiles, or whole tiles + a 32-point tail block (pointnet_filter.hip)
-    const long slots = (tiles256 >= 2 && over <= 32 && dvq_knobs().pn_tail) ? 256L * (tiles256 - 1) + 32 : 256L * tiles256;
-    return w->w2p && w->w3f && w->s_w2p && w->s_w3f && dvq_gemm_mode() == 1 && fm && N <= 16384 && (fm == 2 || 4L * N >= 3L * slots);
+    const int fm = dvq_knobs().pn_filter;   // DVQ_PN_FILTER: 0 = six-product trunk everywhere, 2 = filtered trunk whatever the fill of its tiles (tests), default 1
+    const long slots = pn_geometry(N, dvq_knobs().pn_tail != 0).slots;   // what the filtered trunk evaluates: whole tiles (+ a 32-point tail block)
+    return w->w2p && w->w3f && w->s_w2p && w->s_w3f && dvq_gemm_mode() == 1 && fm && N <= PN_MAX_POINTS && (fm == 2 || 4L * N >= 3L * slots);
 }
 
-int trunk(const float* pc, int C, int N, long Bc, const float* trans, const float* w1, const float* b1, const float* w2,
-          const uint16_t* w2p, const float* b2, const float* w3, const uint16_t* w3p, const void* w3f, const float* b3, int relu3,
-          bool filtered, const PnScratch& s, float* feat, long ld_feat, hipStream_t st) {
+// one trunk over the clouds of a launch, on scratch set 0 and one stream -> feat [B][ld_feat]
+int trunk(const PnTrunkWeights& w, const PnBatch& in, bool filtered, const PnScratch& s, float* feat, long ld_feat, hipStream_t st) {
     const PnSlot& sl = s.slot[0];
-    if (filtered)
-        return dvq_launch_pn_trunk_filter(pc, C, N, s.Npad, Bc, trans, w1, b1, w2, w2p, b2, w3f, w3, b3, relu3, sl.h2, sl.part, sl.tstat,
-                                          sl.cbuf, feat, ld_feat, dvq_knobs().pn_stats ? s.stats : nullptr, st);
-    if (w2p && w3p && dvq_gemm_mode() == 1) {       // fused trunk; w3p is the k-permuted plane image (see pn_trunk_kernel)
-        DVQ_PROPAGATE(dvq_launch_pn_trunk(pc, C, N, Bc, trans, w1, b1, w2p, b2, w3p, b3, sl.part, st));
-        return dvq_launch_colmax_reduce(sl.part, Bc, (N + 127) / 128, 1024, relu3, feat, ld_feat, st);   // the kernel's own tiling
+    const int N = in.N;
+    if (filtered) {
+        unsigned long long* stats = dvq_knobs().pn_stats ? s.stats : nullptr;
+        DVQ_PROPAGATE(dvq_launch_pn_filter_front(in, w, sl, stats, st));
+        return dvq_launch_pn_filter_back(in, w, sl, feat, ld_feat, stats, st);
     }
-    w3p = nullptr;                                  // the unfused GEMM path takes natural-order planes only: split on the fly
+    if (w.w2p && w.w3p && dvq_gemm_mode() == 1) {   // fused trunk; w3p is the k-permuted plane image (see pn_trunk_kernel)
+        DVQ_PROPAGATE(dvq_launch_pn_trunk(in, w, sl.part, st));
+        return dvq_launch_colmax_reduce(sl.part, in.B, (N + 127) / 128, 1024, w.relu3, feat, ld_feat, st);   // the kernel's own tiling
+    }
     DVQ_REQUIRE(s.h1, "pointnet: no scratch for the unfused trunk");
-    const long rows = Bc * s.Npad;
-    const long threads = rows * 16;
+    const int Npad = s.g.Npad;
+    const long rows = in.B * Npad, threads = rows * 16;
     {
         DVQ_PROF("pn_layer1", 2.0 * rows * 64 * 4, (double)rows * (16 + 256), st);
-        DVQ_LAUNCH(pn_layer1_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st, pc, C, N, s.Npad, Bc,
-                           trans, w1, b1, s.h1);
+        DVQ_LAUNCH(pn_layer1_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st, in.pc, in.C, N, Npad, in.B,
+                           in.trans, w.w1, w.b1, s.h1);
     }
     DVQ_CHECK_LAUNCH("pn_layer1");
-    DVQ_PROPAGATE(dense(s.h1, 64, 64, w2, w2p, b2, rows, 128, 1, sl.h2, 128, st));
+    DVQ_PROPAGATE(dense(s.h1, 64, w.w2, w.w2p, w.b2, rows, 128, 1, sl.h2, st));
     GemmParams p = {};
-    p.src[0] = GemmSrc{sl.h2, w3, 128, 128, 128, 0, w3p, 1024L * 128};
+    p.src[0] = GemmSrc{sl.h2, w.w3, 128, 128, 128, 0, nullptr, 1024L * 128};   // no planes: the GEMM takes natural-order ones only (w3p is k-permuted) and splits on the fly
     p.nsrc = 1;
     p.M = rows;
     p.N = 1024;
-    p.bias = b3;
+    p.bias = w.b3;
     p.relu = 0;                  // max(relu(x)) == relu(max(x)): the ReLU is applied by the reduction
-    p.rows_per_group = s.Npad;
+    p.rows_per_group = Npad;
     p.valid_rows = N;
     p.partial = sl.part;
     DVQ_PROPAGATE(dvq_launch_gemm(p, EPI_COLMAX, st));
-    return dvq_launch_colmax_reduce(sl.part, Bc, s.Npad / 128, 1024, relu3, feat, ld_feat, st);
+    return dvq_launch_colmax_reduce(sl.part, in.B, Npad / 128, 1024, w.relu3, feat, ld_feat, st);
+}
+
+// STN3d's head on the STN trunk's features s.f0: fc1 / fc2 (BN folded, ReLU) and fc3 (+identity) -> the launch's transforms tr [Bc][9]
+int stn_head(const dvq_pointnet_weights* w, const PnScratch& s, long Bc, float* tr, hipStream_t st) {
+    DVQ_PROPAGATE(dense(s.f0, 1024, w->s_f1, w->s_f1p, w->s_c1, Bc, 512, 1, s.f1, st));
+    DVQ_PROPAGATE(dense(s.f1, 512, w->s_f2, w->s_f2p, w->s_c2, Bc, 256, 1, s.f2, st));
+    return dense(s.f2, 256, w->s_f3, w->s_f3p, w->s_c3, Bc, 9, 0, tr, st);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -235,15 +217,6 @@ PnSide* side_for(hipStream_t st) {
     return sd;
 }
 
-#define PN_HIP(call, what)                                                                  \
-    do {                                                                                    \
-        const hipError_t e__ = (call);                                                      \
-        if (e__ != hipSuccess) {                                                            \
-            dvq_set_error("pointnet_encode: %s failed: %s", what, hipGetErrorString(e__)); \
-            return DVQ_ELAUNCH;                                                             \
-        }                                                                                   \
-    } while (0)
-
 // Both passes (STN, main) of the filtered trunk over the launches of a batch, two streams:
 //   S1 (the caller's): front(i) = centres + trunk kernel into scratch set i % slots
 //   S2:                back(i) = pn_exact_kernel of that set -> features; pass 1: the STN's FCs of the launch -> its transforms
@@ -257,13 +230,11 @@ int encode_two_streams(const dvq_pointnet_weights* w, const float* pc, int64_t B
     // events: [0] start / join, [1 .. slots] front done, [1 + slots .. 2 slots] set free, then one per launch: transforms ready
     const size_t e_front = 1, e_free = 1 + s.slots, e_tr = 1 + 2 * s.slots;
     DVQ_REQUIRE(sd->event(e_tr + launches), "pointnet_encode: event creation failed");
-    unsigned long long* stats = dvq_knobs().pn_stats ? s.stats : nullptr;
-    PN_HIP(hipEventRecord(sd->event(0), st), "hipEventRecord");
-    PN_HIP(hipStreamWaitEvent(s2, sd->event(0), 0), "hipStreamWaitEvent");        // S2 starts behind everything enqueued on S1 so far
     float* tr_all = trans_out ? trans_out : s.tr;
+    const PnTrunkWeights tw[2] = {pn_stn_trunk(w), pn_main_trunk(w)};   // pass 0: STN3d's trunk (ReLU on the last layer), pass 1: the main trunk (none, pointnet_encoder.py:162)
     int rc = DVQ_OK;
-    // inside the loops a failed event / wait call sets rc and leaves them: the join below is ALWAYS attempted, so that nothing S2 still
-    // has in flight can touch the caller's workspace, features or transforms after this function has returned
+    // a failed event / wait call sets rc and ends the loops: the join below is ALWAYS attempted, so that nothing S2 still has in flight
+    // can touch the caller's workspace, features or transforms after this function has returned
 #define PN_TRY(call, what)                                                                      \
     if (rc == DVQ_OK) {                                                                         \
         const hipError_t e__ = (call);                                                          \
@@ -272,36 +243,28 @@ int encode_two_streams(const dvq_pointnet_weights* w, const float* pc, int64_t B
             rc = DVQ_ELAUNCH;                                                                   \
         }                                                                                       \
     }
+    PN_TRY(hipEventRecord(sd->event(0), st), "hipEventRecord");
+    PN_TRY(hipStreamWaitEvent(s2, sd->event(0), 0), "hipStreamWaitEvent");        // S2 starts behind everything enqueued on S1 so far
     long idx = 0;
     for (int pass = 0; pass < 2 && rc == DVQ_OK; ++pass)
         for (long c = 0; c < launches && rc == DVQ_OK; ++c, ++idx) {
             const int64_t b0 = c * s.chunk;
             const long Bc = (long)((B - b0 < s.chunk) ? (B - b0) : s.chunk);
-            const float* pcb = pc + b0 * (long)w->C * N;
             const PnSlot& sl = s.slot[idx % s.slots];
             float* tr = tr_all + b0 * 9;
+            const PnBatch in = {pc + b0 * (long)w->C * N, pass == 0 ? nullptr : tr, w->C, N, Bc};   // pass 1 runs on the transformed cloud
             if (idx >= s.slots) PN_TRY(hipStreamWaitEvent(st, sd->event(e_free + idx % s.slots), 0), "hipStreamWaitEvent");
             if (pass == 1) PN_TRY(hipStreamWaitEvent(st, sd->event(e_tr + c), 0), "hipStreamWaitEvent");
-            if (rc == DVQ_OK)
-                rc = pass == 0 ? dvq_launch_pn_filter_front(pcb, w->C, N, s.Npad, Bc, nullptr, w->s_w1, w->s_b1, w->s_w2, w->s_w2p, w->s_b2, w->s_w3f,
-                                                        sl.h2, sl.part, sl.tstat, sl.cbuf, stats, st)
-                           : dvq_launch_pn_filter_front(pcb, w->C, N, s.Npad, Bc, tr, w->w1, w->b1, w->w2, w->w2p, w->b2, w->w3f, sl.h2, sl.part,
-                                                        sl.tstat, sl.cbuf, stats, st);
+            if (rc == DVQ_OK) rc = dvq_launch_pn_filter_front(in, tw[pass], sl, nullptr, st);
             if (rc != DVQ_OK) break;
             PN_TRY(hipEventRecord(sd->event(e_front + idx % s.slots), st), "hipEventRecord");
             PN_TRY(hipStreamWaitEvent(s2, sd->event(e_front + idx % s.slots), 0), "hipStreamWaitEvent");
-            if (pass == 0) {
-                // STN3d: trunk with ReLU on the last layer, then fc1/fc2 (BN folded, ReLU) and fc3 (+identity)
-                if (rc == DVQ_OK) rc = dvq_launch_pn_filter_back(N, s.Npad, Bc, w->s_w3f, w->s_w3, w->s_b3, 1, sl.h2, sl.part, sl.tstat, sl.cbuf, s.f0, 1024, stats, s2);
-                PN_TRY(hipEventRecord(sd->event(e_free + idx % s.slots), s2), "hipEventRecord");
-                if (rc == DVQ_OK) rc = dense(s.f0, 1024, 1024, w->s_f1, w->s_f1p, w->s_c1, Bc, 512, 1, s.f1, 512, s2);
-                if (rc == DVQ_OK) rc = dense(s.f1, 512, 512, w->s_f2, w->s_f2p, w->s_c2, Bc, 256, 1, s.f2, 256, s2);
-                if (rc == DVQ_OK) rc = dense(s.f2, 256, 256, w->s_f3, w->s_f3p, w->s_c3, Bc, 9, 0, tr, 9, s2);
+            if (rc == DVQ_OK) rc = pass == 0 ? dvq_launch_pn_filter_back(in, tw[0], sl, s.f0, 1024, nullptr, s2)
+                                             : dvq_launch_pn_filter_back(in, tw[1], sl, feat + b0 * ld_feat, ld_feat, nullptr, s2);
+            PN_TRY(hipEventRecord(sd->event(e_free + idx % s.slots), s2), "hipEventRecord");
+            if (pass == 0) {                                // the STN's FCs of the launch -> its transforms
+                if (rc == DVQ_OK) rc = stn_head(w, s, Bc, tr, s2);
                 PN_TRY(hipEventRecord(sd->event(e_tr + c), s2), "hipEventRecord");
-            } else {
-                // main trunk on the transformed cloud; no ReLU after the last BN (pointnet_encoder.py:162)
-                if (rc == DVQ_OK) rc = dvq_launch_pn_filter_back(N, s.Npad, Bc, w->w3f, w->w3, w->b3, 0, sl.h2, sl.part, sl.tstat, sl.cbuf, feat + b0 * ld_feat, ld_feat, stats, s2);
-                PN_TRY(hipEventRecord(sd->event(e_free + idx % s.slots), s2), "hipEventRecord");
             }
         }
 #undef PN_TRY
@@ -341,19 +304,16 @@ extern "C" int dvq_pointnet_encode(const dvq_pointnet_weights* w, const float* p
     hipStream_t st = (hipStream_t)stream;
     const bool filtered = use_filter(w, N);
     if (filtered && s.slots >= 2 && dvq_knobs().pn_streams && !dvq_knobs().pn_stats) return encode_two_streams(w, pc, B, N, feat, ld_feat, trans_out, s, st);
+    const PnTrunkWeights stn = pn_stn_trunk(w), main_trunk = pn_main_trunk(w);
     for (int64_t b0 = 0; b0 < B; b0 += s.chunk) {
         const long Bc = (long)((B - b0 < s.chunk) ? (B - b0) : s.chunk);
         const float* pcb = pc + b0 * (long)w->C * N;
-        // STN3d: trunk with ReLU on the last layer, then fc1/fc2 (BN folded, ReLU) and fc3 (+identity)
-        DVQ_PROPAGATE(trunk(pcb, w->C, N, Bc, nullptr, w->s_w1, w->s_b1, w->s_w2, w->s_w2p, w->s_b2, w->s_w3, w->s_w3p, w->s_w3f, w->s_b3,
-                            1, filtered, s, s.f0, 1024, st));
-        DVQ_PROPAGATE(dense(s.f0, 1024, 1024, w->s_f1, w->s_f1p, w->s_c1, Bc, 512, 1, s.f1, 512, st));
-        DVQ_PROPAGATE(dense(s.f1, 512, 512, w->s_f2, w->s_f2p, w->s_c2, Bc, 256, 1, s.f2, 256, st));
         float* tr = (trans_out ? trans_out : s.tr) + b0 * 9;
-        DVQ_PROPAGATE(dense(s.f2, 256, 256, w->s_f3, w->s_f3p, w->s_c3, Bc, 9, 0, tr, 9, st));
+        // STN3d: trunk with ReLU on the last layer, then its FC head -> the transforms
+        DVQ_PROPAGATE(trunk(stn, PnBatch{pcb, nullptr, w->C, N, Bc}, filtered, s, s.f0, 1024, st));
+        DVQ_PROPAGATE(stn_head(w, s, Bc, tr, st));
         // main trunk on the transformed cloud; no ReLU after the last BN (pointnet_encoder.py:162)
-        DVQ_PROPAGATE(trunk(pcb, w->C, N, Bc, tr, w->w1, w->b1, w->w2, w->w2p, w->b2, w->w3, w->w3p, w->w3f, w->b3, 0, filtered, s,
-                            feat + b0 * ld_feat, ld_feat, st));
+        DVQ_PROPAGATE(trunk(main_trunk, PnBatch{pcb, tr, w->C, N, Bc}, filtered, s, feat + b0 * ld_feat, ld_feat, st));
     }
     return DVQ_OK;
 }
@@ -573,33 +533,17 @@ __global__ __launch_bounds__(256, 2) void pn_trunk_kernel(const float* __restric
 
 }  // namespace
 
-int dvq_launch_pn_trunk(const float* pc, int C, int N, long B, const float* trans, const float* W1, const float* b1,
-                        const uint16_t* W2p, const float* b2, const uint16_t* W3p, const float* b3, float* partial,
-                        hipStream_t st) {
-    const int tiles = (N + 127) / 128;
-    static DvqOncePerDevice attr_once;
-    {
-        const hipError_t e = attr_once.run([] {
-            const hipError_t e3 = hipFuncSetAttribute(reinterpret_cast<const void*>(&pn_trunk_kernel<3>),
-                                                      hipFuncAttributeMaxDynamicSharedMemorySize, T_LDS);
-            const hipError_t e4 = hipFuncSetAttribute(reinterpret_cast<const void*>(&pn_trunk_kernel<4>),
-                                                      hipFuncAttributeMaxDynamicSharedMemorySize, T_LDS);
-            return e3 != hipSuccess ? e3 : e4;
-        });
-        if (e != hipSuccess) {
-            dvq_set_error("pointnet: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
-            return DVQ_ELAUNCH;
-        }
-    }
-    const long grid = B * tiles;
+int dvq_launch_pn_trunk(const PnBatch& in, const PnTrunkWeights& w, float* partial, hipStream_t st) {
+    const int tiles = (in.N + 127) / 128;
+    const auto kernel = in.C == 3 ? &pn_trunk_kernel<3> : &pn_trunk_kernel<4>;
+    static DvqOncePerDevice attr_once[2];
+    DVQ_PROPAGATE(dvq_lds_limit(attr_once[in.C == 3], reinterpret_cast<const void*>(kernel), T_LDS, "pointnet"));
+    const long grid = in.B * tiles;
     DVQ_REQUIRE(grid < (1L << 31), "pointnet: grid too large");
-    const double pts = (double)B * tiles * 128;
+    const double pts = (double)grid * 128;
     {
         DVQ_PROF("pn_trunk", 2.0 * pts * (4.0 * 64 + 64.0 * 128 + 128.0 * 1024), pts * 16 + (double)grid * 4096, st);
-        if (C == 3)
-            DVQ_LAUNCH(pn_trunk_kernel<3>, dim3((unsigned)grid), dim3(256), T_LDS, st, pc, trans, N, tiles, W1, b1, W2p, b2, W3p, b3, partial);
-        else
-            DVQ_LAUNCH(pn_trunk_kernel<4>, dim3((unsigned)grid), dim3(256), T_LDS, st, pc, trans, N, tiles, W1, b1, W2p, b2, W3p, b3, partial);
+        DVQ_LAUNCH(kernel, dim3((unsigned)grid), dim3(256), T_LDS, st, in.pc, in.trans, in.N, tiles, w.w1, w.b1, w.w2p, w.b2, w.w3p, w.b3, partial);
     }
     DVQ_CHECK_LAUNCH("pn_trunk");
     return DVQ_OK;

@@ -24,7 +24,7 @@
 // kernel is bound by vector-instruction issue: 2.5 instructions per score (id; max3 / med3 per group of three) since round 6 -- a top-two per 16-point
 // group flags about as many points for re-evaluation as the top-three per 32 points of round 4 did.
 #include "dvq_internal.h"
-#include "pn_slots.h"
+#include "pn_filter.h"
 #include <vector>
 
 namespace {
@@ -43,7 +43,6 @@ constexpr float C_ID = 5.0e-5f;
 // the centre term
 constexpr float DELTA = 1.0e-6f;
 constexpr float NEG_BIG = -3.0e38f;
-constexpr int MAX_TILES = 64;                             // filtered trunk: N <= 16384 points
 
 constexpr int F_STAGE2 = 2 * 64 * 128;                    // conv2: one half of W2's two fp16 planes (2 x 64 rows x 128 B)
 // the filter image of a trunk (dvq_pointnet_pack_filter): conv3 [1024][128] fp16 | 1 / scale [1024] | |w_n| [1024] | |w_n - image| [1024]
@@ -219,8 +218,8 @@ __global__ __launch_bounds__(256, 2) void pn_trunk_filter_kernel(const float* __
     float* cs = reinterpret_cast<float*>(fl + (TAIL ? F_LDS + 3 * 4096 + 512 * wave : F_OFF_CS));
     float* e2s = reinterpret_cast<float*>(fl + F_OFF_E2) + (TAIL ? 1024 * wave : 0);
 
-    const unsigned long long t_start = (abl & 4096) ? __builtin_amdgcn_s_memtime() : 0ull;
-    const unsigned long long r_start = (abl & 8192) ? __builtin_amdgcn_s_memrealtime() : 0ull;   // 100 MHz: with 4096 | 8192 the record's word 3 holds the CLOCK
+    const unsigned long long t_start = (abl & PN_ABL_STAMPS) ? __builtin_amdgcn_s_memtime() : 0ull;
+    const unsigned long long r_start = (abl & PN_ABL_CLOCK) ? __builtin_amdgcn_s_memrealtime() : 0ull;   // 100 MHz: with 4096 | 8192 the record's word 3 holds the CLOCK
     unsigned long long t_a = 0, t_b = 0, t_c = 0;
     const uint16_t* w2pl = reinterpret_cast<const uint16_t*>(w3f + IMG_OFF_W2);
     w2_issue(w2pl, 0, fl, wave, lane);
@@ -267,7 +266,7 @@ __global__ __launch_bounds__(256, 2) void pn_trunk_filter_kernel(const float* __
     // paths, and the wave waits for thirteen of its sixteen stores to be ACKNOWLEDGED before it goes on (round 5: -11 % of the kernel
     // with the stores ablated, all of it this wait).
     __builtin_amdgcn_s_waitcnt(0x0F70);
-    if (abl & 4096) t_a = __builtin_amdgcn_s_memtime();
+    if (abl & PN_ABL_STAMPS) t_a = __builtin_amdgcn_s_memtime();
     float cnorm;                                          // |c| (every wave for itself: no ordering between the waves needed)
     {
         const float cq = fmaf(cs[lane], cs[lane], cs[64 + lane] * cs[64 + lane]);
@@ -280,7 +279,7 @@ __global__ __launch_bounds__(256, 2) void pn_trunk_filter_kernel(const float* __
     // [2^14, 2^15) -- a function of the point alone, so a row's bits do not depend on which points share its wave (tail tile ==
     // full tile, batched == single); acc = a1 w2 + a2 w1 + a1 w1 in ONE fp32 accumulator (second pieces unscaled), h2 = acc / s_p 2^-t_n + b2.
     float hv[NPB][64];
-    if (abl & 131072) {                                    // timing only: a "consumer" workgroup -- no conv1 / conv2, rows from thin air
+    if (abl & PN_ABL_CONSUMER) {                                    // timing only: a "consumer" workgroup -- no conv1 / conv2, rows from thin air
 #pragma unroll
         for (int pb = 0; pb < NPB; ++pb)
 #pragma unroll
@@ -339,7 +338,7 @@ __global__ __launch_bounds__(256, 2) void pn_trunk_filter_kernel(const float* __
                 const int ch = 32 * t4 + (e & 3) + 8 * (e >> 2);       // + 4 h
                 hv[pb][16 * t4 + e] = fmaxf(fmaf(acc[e] * r_p, (k2s + 4 * h_op)[ch], (b2s + 4 * h_op)[ch]), 0.f);
             }
-            if (pidx[pb] < N && live && !(abl & 1)) {     // natural channel order: 4 consecutive channels per 16-byte store
+            if (pidx[pb] < N && live && !(abl & PN_ABL_NO_H2_STORE)) {     // natural channel order: 4 consecutive channels per 16-byte store
                 float* dst = h2buf + ((b * Npad + pidx[pb]) * 128 + 32 * t4 + 4 * h);
 #pragma unroll
                 for (int g = 0; g < 4; ++g)
@@ -348,7 +347,7 @@ __global__ __launch_bounds__(256, 2) void pn_trunk_filter_kernel(const float* __
             }
         }
     }
-    if (abl & 4096) t_b = __builtin_amdgcn_s_memtime();
+    if (abl & PN_ABL_STAMPS) t_b = __builtin_amdgcn_s_memtime();
     // ---- centre the rows on the sample's centre (pn_center_kernel)
     float dn2 = 0.f;
 #pragma unroll
@@ -443,14 +442,14 @@ __global__ __launch_bounds__(256, 2) void pn_trunk_filter_kernel(const float* __
         scs[wave] = 1.0f / s_w;
         wst[wave] = hm; wst[4 + wave] = dmx; wst[8 + wave] = rdm;
         if (live) {
-            if (any_bad && !(abl & 4096)) atomicMax(tstat + 4 * rec + 3, 1u);
+            if (any_bad && !(abl & PN_ABL_STAMPS)) atomicMax(tstat + 4 * rec + 3, 1u);
             atomicMax(tstat + 4 * rec + 0, __float_as_uint(hm));
             atomicMax(tstat + 4 * rec + 1, __float_as_uint(dmx));
             atomicMax(tstat + 4 * rec + 2, __float_as_uint(rdm));
         }
     }
     dvq_lds_barrier();                                      // everybody is done with W2 in the stages; scs visible
-    if (abl & 4096) t_c = __builtin_amdgcn_s_memtime();
+    if (abl & PN_ABL_STAMPS) t_c = __builtin_amdgcn_s_memtime();
 
     // ---- conv3, filtered: 16 chunks of 64 channels, one fp16 product, top two scores per channel and 16-point group
     w3_store(fl, wave, lane, wreg);
@@ -542,7 +541,7 @@ __global__ __launch_bounds__(256, 2) void pn_trunk_filter_kernel(const float* __
             flags = flags + flags + (unsigned)(u >= thr);
         }
         if (suspect) flags = 0x1FFFFu;
-        if ((abl & 32768) && c == 5 && lane == 7) c1 = fabsf(c1) * 1.0e3f + 1.0f;   // diagnostics: a record that lies about its tile
+        if ((abl & PN_ABL_INJECT_LIE) && c == 5 && lane == 7) c1 = fabsf(c1) * 1.0e3f + 1.0f;   // diagnostics: a record that lies about its tile
         if (live) {
             part[rec * 1024 + 64 * c + lane] = f32x4{c1, c2, c3, __uint_as_float(flags)};
             part2[rec * 1024 + 64 * c + lane] = qf32x2{c4, c5};
@@ -565,7 +564,7 @@ __global__ __launch_bounds__(256, 2) void pn_trunk_filter_kernel(const float* __
     /* per score that is needed anyway -- finish() used to set the tag on the block's winner with an instruction of its own           */
 #define F_CHAIN_BLOCK(ACC, M1, M2, CT)                                                                         \
     do {                                                                                                       \
-        if (abl & 128) { M1 = ACC[0][0]; M2 = ACC[NRB - 1][3]; } else   /* timing only: no chain */            \
+        if (abl & PN_ABL_NO_CHAIN) { M1 = ACC[0][0]; M2 = ACC[NRB - 1][3]; } else   /* timing only: no chain */            \
         {                                                                                                      \
             /* round 6: groups of three -- v_max3 / v_med3 give a group's two largest, merged into the running pair by          */ \
             /* second = med3(M1, g1, max(M2, g2)): 40 instead of 48 instructions per 16 scores, the same pair                    */ \
@@ -602,7 +601,7 @@ __global__ __launch_bounds__(256, 2) void pn_trunk_filter_kernel(const float* __
     // (a group's row of 64 channels is rotated by 16 per lane quarter: the quarters of a store then hit different banks)
     const int fin_row = (wave * 4 + q4) * 128, fin_rot = 16 * q4 + l16;
     auto finish = [&](int c, int cb, float m1, float m2) {
-        if ((abl & 65536) && c == 9 && wave == 2 && cb == 0) return;   // diagnostics: a hand-over that does not happen
+        if ((abl & PN_ABL_INJECT_LOST) && c == 9 && wave == 2 && cb == 0) return;   // diagnostics: a hand-over that does not happen
         float* dst = tb + (c & 3) * F_SLOT + fin_row + ((16 * cb + fin_rot) & 63);
         dst[0] = m1;                                        // bits [6:5] of both: the chunk's ring tag (F_CHAIN_BLOCK), checked by publish()
         dst[64] = m2;
@@ -663,7 +662,7 @@ __global__ __launch_bounds__(256, 2) void pn_trunk_filter_kernel(const float* __
     // and "is this a publishing chunk" are compile-time constants then -- LDS addresses become instruction offsets instead of vector
     // additions per access, the conditions disappear (round 5: the kernel is vector-issue bound).
 #pragma unroll 1
-    for (int c4 = 0; c4 < ((abl & 2) ? 0 : 16); c4 += 4) {
+    for (int c4 = 0; c4 < ((abl & PN_ABL_NO_CONV3) ? 0 : 16); c4 += 4) {
     // id (row block, register) | ring tag of this trip's four chunks, one SCALAR per accumulator register: the chain's one instruction
     // per score is then v_and_or_b32 (score, mask in a vector register, this scalar).  (Written as "id | tag" in the expression the
     // compiler makes it v_and_b32 + v_or3_b32: two vector instructions per score.)
@@ -675,9 +674,9 @@ __global__ __launch_bounds__(256, 2) void pn_trunk_filter_kernel(const float* __
         const int c = c4 + u;
         const int stage = u & 1;
         const bool pending = u != 0;
-        if (!(abl & 16384)) dvq_lds_barrier();              // chunk c is in its stage; the other stage and tb parity are free
-        if (c + 1 < 16 && !(abl & 1024)) wreg = w3_load(w3h, 64 * (c + 1), wave, lane);
-        if (u == 0 && c > 0 && !(abl & 256)) {              // the ring's four chunks are complete (barrier above): one per wave
+        if (!(abl & PN_ABL_NO_CHUNK_BARRIER)) dvq_lds_barrier();              // chunk c is in its stage; the other stage and tb parity are free
+        if (c + 1 < 16 && !(abl & PN_ABL_NO_W3_LOADS)) wreg = w3_load(w3h, 64 * (c + 1), wave, lane);
+        if (u == 0 && c > 0 && !(abl & PN_ABL_NO_PUBLISH)) {              // the ring's four chunks are complete (barrier above): one per wave
             publish(c - 4 + wave);
             dvq_lds_barrier();                              // before this chunk's pairs overwrite slot 0
         }
@@ -696,30 +695,30 @@ __global__ __launch_bounds__(256, 2) void pn_trunk_filter_kernel(const float* __
         if (pending) {
             F_CHAIN_BLOCK(accP, m1, m2, ctag4);
             F_INTERLEAVE();
-            if (!(abl & 512)) finish(c - 1, 3, m1, m2);
+            if (!(abl & PN_ABL_NO_HANDOVER)) finish(c - 1, 3, m1, m2);
             else if (m1 + m2 == 12345.f) tb[lane] = m1;
         }
         F_MFMA_BLOCK(accB, wf[1]);
         F_CHAIN_BLOCK(accA, m1, m2, ctag4);
         F_INTERLEAVE();
-        if (!(abl & 512)) finish(c, 0, m1, m2);
+        if (!(abl & PN_ABL_NO_HANDOVER)) finish(c, 0, m1, m2);
         else if (m1 + m2 == 12345.f) tb[lane] = m1;
         F_MFMA_BLOCK(accA, wf[2]);
         F_CHAIN_BLOCK(accB, m1, m2, ctag4);
         F_INTERLEAVE();
-        if (!(abl & 512)) finish(c, 1, m1, m2);
+        if (!(abl & PN_ABL_NO_HANDOVER)) finish(c, 1, m1, m2);
         else if (m1 + m2 == 12345.f) tb[lane] = m1;
         F_MFMA_BLOCK(accP, wf[3]);
         F_CHAIN_BLOCK(accA, m1, m2, ctag4);
         F_INTERLEAVE();
-        if (!(abl & 512)) finish(c, 2, m1, m2);
+        if (!(abl & PN_ABL_NO_HANDOVER)) finish(c, 2, m1, m2);
         else if (m1 + m2 == 12345.f) tb[lane] = m1;
         if (u == 3) {                                     // nothing to cover it before a publish
             F_CHAIN_BLOCK(accP, m1, m2, ctag4);
-            if (!(abl & 512)) finish(c, 3, m1, m2);
+            if (!(abl & PN_ABL_NO_HANDOVER)) finish(c, 3, m1, m2);
             else if (m1 + m2 == 12345.f) tb[lane] = m1;
         }
-        if (c + 1 < 16 && !(abl & 1024)) w3_store(fl + (stage ^ 1) * F_STAGE3, wave, lane, wreg);
+        if (c + 1 < 16 && !(abl & PN_ABL_NO_W3_LOADS)) w3_store(fl + (stage ^ 1) * F_STAGE3, wave, lane, wreg);
     }
     }
     }
@@ -730,14 +729,14 @@ __global__ __launch_bounds__(256, 2) void pn_trunk_filter_kernel(const float* __
     if constexpr (TAIL) {
 #pragma unroll 1
         for (int q = 12; q < 16; ++q) publish(q);
-    } else if (!(abl & 256)) {
+    } else if (!(abl & PN_ABL_NO_PUBLISH)) {
         publish(12 + wave);
     }
-    if ((abl & 4096) && tid == 0) {                        // diagnostics: phase durations in units of 64 ticks, 8 bits each
+    if ((abl & PN_ABL_STAMPS) && tid == 0) {                        // diagnostics: phase durations in units of 64 ticks, 8 bits each
         const unsigned long long t_end = __builtin_amdgcn_s_memtime();
         auto q = [](unsigned long long d) { d >>= 6; return (unsigned)(d > 255 ? 255 : d); };
         tstat[4 * rec + 3] = q(t_a - t_start) | (q(t_b - t_a) << 8) | (q(t_c - t_b) << 16) | (q((t_end - t_c) >> 3) << 24);
-        if (abl & 8192) {                                   // in-kernel clock in MHz: shader cycles per 100 MHz tick over the workgroup's life
+        if (abl & PN_ABL_CLOCK) {                                   // in-kernel clock in MHz: shader cycles per 100 MHz tick over the workgroup's life
             const unsigned long long r_end = __builtin_amdgcn_s_memrealtime();
             tstat[4 * rec + 3] = (unsigned)((t_end - t_start) * 100ull / (r_end - r_start + 1));
         }
@@ -813,7 +812,7 @@ __global__ __launch_bounds__(256, 4) void pn_exact_kernel(const f32x4* __restric
     __shared__ short all_list[1024];
     __shared__ int pair_count, fb_count, all_count;
     __shared__ float fb_part[4][16];
-    __shared__ float hm[MAX_TILES], dm[MAX_TILES], rd[MAX_TILES];
+    __shared__ float hm[PN_MAX_TILES], dm[PN_MAX_TILES], rd[PN_MAX_TILES];
     __shared__ unsigned best_k[1024];
     __shared__ int pcnt[1024];                             // pairs per point -> first slot of the point -> fill cursor
     __shared__ unsigned sorted[SORT_CAP];                  // channel | point << 10, grouped by point
@@ -831,7 +830,7 @@ __global__ __launch_bounds__(256, 4) void pn_exact_kernel(const f32x4* __restric
         hm[tid] = __uint_as_float(ts[0]) * 1.00001f;
         dm[tid] = __uint_as_float(ts[1]) * 1.00001f;
         rd[tid] = __uint_as_float(ts[2]) * 1.00001f;
-        nonfinite_point = ts[3] != 0 && !(abl & 4096);      // (word 3 holds the phase stamps of the diagnostics build otherwise)
+        nonfinite_point = ts[3] != 0 && !(abl & PN_ABL_STAMPS);      // (word 3 holds the phase stamps of the diagnostics build otherwise)
     }
     if (__syncthreads_or(nonfinite_point)) {
         // a cloud with a NaN / Inf coordinate: NaN in every channel, as the reference's affine layers and torch.max make it (the trunk
@@ -844,7 +843,7 @@ __global__ __launch_bounds__(256, 4) void pn_exact_kernel(const f32x4* __restric
     const f32x4* pt = part + b * (long)tiles * 1024;
     const qf32x2* pt2 = part2 + b * (long)tiles * 1024;     // the fourth and fifth id-carrying scores: read only where the third is in range
     // ---- phase A
-    const bool stamps = DVQ_DIAG_ON && stats && (abl & 4096);   // diagnostics: cycles per phase (tid 0's clock), summed into stats[4..7]
+    const bool stamps = DVQ_DIAG_ON && stats && (abl & PN_ABL_STAMPS);   // diagnostics: cycles per phase (tid 0's clock), summed into stats[4..7]
     unsigned long long tp0 = stamps ? __builtin_amdgcn_s_memtime() : 0ull, tp1 = 0, tp2 = 0, tp3 = 0;
     unsigned n_single = 0, n_multi = 0, n_cand = 0, n_wave = 0, n_suspect = 0;
     // the interval the records promise for (max - w.c) of channels tid + 256 i; lo > hi: not checked.  Eight scalars updated through
@@ -923,7 +922,7 @@ __global__ __launch_bounds__(256, 4) void pn_exact_kernel(const f32x4* __restric
             auto take = [&](float v) {
                 int p = point_of_slot(t, slot_of_id(__float_as_uint(v) & 255u), deal);
                 if (p >= N) p = wrap_small ? p - N : p % N;  // a padding slot: the real point it repeats
-                if (abl & 16) p &= 63;
+                if (abl & PN_ABL_FEW_ROWS) p &= 63;
                 if (cands < 4) cand[n][cands] = (unsigned short)p;
                 else {
                     const int slot = atomicAdd(&pair_count, 1);
@@ -1015,7 +1014,7 @@ __global__ __launch_bounds__(256, 4) void pn_exact_kernel(const f32x4* __restric
         pcnt[4 * tid + 3] = excl + c0 + c1 + c2;
     }
     dvq_lds_barrier();
-    const bool by_point = total <= SORT_CAP && !(abl & 64);
+    const bool by_point = total <= SORT_CAP && !(abl & PN_ABL_NO_DOTS);
     if (by_point) {
         for (int n = tid; n < 1024; n += 256)
             for (int k = 0; k < cand_n[n]; ++k) {
@@ -1059,7 +1058,7 @@ __global__ __launch_bounds__(256, 4) void pn_exact_kernel(const f32x4* __restric
     }
     // ---- phase B, channel order (more pairs than the sorted list holds): table; four channels of a group in flight (first
     // candidates), further candidates afterwards
-    for (int n0 = g; n0 < ((abl & 64) || by_point ? 0 : 1024); n0 += 64) {
+    for (int n0 = g; n0 < ((abl & PN_ABL_NO_DOTS) || by_point ? 0 : 1024); n0 += 64) {
         f32x4 w0[4], w1[4], ha[4], hb[4];
         int cn[4];
 #pragma unroll
@@ -1106,7 +1105,7 @@ __global__ __launch_bounds__(256, 4) void pn_exact_kernel(const f32x4* __restric
     }
     if (stamps) tp3 = __builtin_amdgcn_s_memtime();
     // ---- phase C: flagged 16-point groups, one wave of the workgroup per entry, its four 16-lane groups take 4 points each
-    const int nfb = (abl & 32) ? 0 : min(fb_count, fb_cap);
+    const int nfb = (abl & PN_ABL_NO_GROUPS) ? 0 : min(fb_count, fb_cap);
     for (int i = tid >> 6; i < nfb; i += 4) {
         const int code = fb_list[i];
         const int n = code & 1023, t = (code >> 10) & 1023, grp = (code >> 20) & 15;
@@ -1178,7 +1177,7 @@ __global__ __launch_bounds__(256, 4) void pn_exact_kernel(const f32x4* __restric
     for (int ci = 0; ci < 4; ++ci) {
         const int n = tid + 256 * ci;
         const float lo_c = ci == 0 ? lo_0 : ci == 1 ? lo_1 : ci == 2 ? lo_2 : lo_3, hi_c = ci == 0 ? hi_0 : ci == 1 ? hi_1 : ci == 2 ? hi_2 : hi_3;
-        if (!(lo_c <= hi_c) || (abl & ~(4096 | 8192 | 32768 | 65536 | 524288))) continue;   // (the timing ablations -- of either kernel -- leave maxima that are not maxima)
+        if (!(lo_c <= hi_c) || (abl & ~PN_ABL_VALID)) continue;   // (the timing ablations -- of either kernel -- leave maxima that are not maxima)
         const float v = key2f(best_k[n]), wc = wcs[n];
         const float x = v - wc, slack = 4.0e-7f * (fabsf(v) + fabsf(wc));   // the subtraction's own rounding
         if (!(x >= lo_c - slack && x <= hi_c + slack)) {
@@ -1330,112 +1329,87 @@ int dvq_launch_pn_filter_pack(const float* w2, const float* w3, void* image, hip
     return DVQ_OK;
 }
 
-// tiles of 256 points; h2buf [B][Npad][128] fp32, part [B][tiles][1024] float4 (+ float2 behind them), tstat [B][tiles][4] (zeroed by pn_center_kernel).
-// Two halves, so that the caller may put them on different streams (pointnet.hip: the exact stage of one launch runs beside the trunk
-// kernel of the next): dvq_launch_pn_filter_front = centres + trunk kernel(s), dvq_launch_pn_filter_back = pn_exact_kernel.
-static int pn_filter_geometry(int N, int* tiles, int* deal) {
-    *tiles = (N + 255) / 256;
-    DVQ_REQUIRE(*tiles <= MAX_TILES, "pointnet: the filtered trunk takes at most %d points", MAX_TILES * 256);
-    // 1 .. 32 points beyond a multiple of 256 (the 778 MANO vertices: 3 x 256 + 10): a tail tile of one block, four samples per
-    // workgroup, instead of a last full tile of padding (DVQ_PN_TAIL=0: the full tile, for A/B runs; same features bit for bit)
-    const int over = N - 256 * (*tiles - 1);
-    *deal = (*tiles >= 2 && over <= 32 && dvq_knobs().pn_tail) ? *tiles - 1 : *tiles;
+// The scratch set of a launch (pn_filter.h): h2 [B][Npad][128] fp32, part [B][tiles][1024] float4, part2 [B][tiles][1024] float2, tstat
+// [B][tiles][4] (zeroed by pn_center_kernel), cbuf [B][128].
+static int filter_geometry(int N, PnGeometry* g) {
+    *g = pn_geometry(N, dvq_knobs().pn_tail != 0);
+    DVQ_REQUIRE(g->tiles <= PN_MAX_TILES, "pointnet: the filtered trunk takes at most %d points", PN_MAX_POINTS);
     return DVQ_OK;
 }
 #ifdef DVQ_DIAG
-static int pn_abl() { const char* e = getenv("DVQ_PN_ABL"); return e ? atoi(e) : 0; }   // timing-only ablations / phase stamps: diagnostics build only
+static int pn_abl() { const char* e = getenv("DVQ_PN_ABL"); return e ? atoi(e) : 0; }   // a sum of PnAbl bits (pn_filter.h): diagnostics build only
 #else
 static constexpr int pn_abl() { return 0; }
 #endif
 
-int dvq_launch_pn_filter_front(const float* pc, int C, int N, int Npad, long B, const float* trans, const float* W1, const float* b1,
-                               const float* W2, const uint16_t* W2p, const float* b2, const void* w3f, float* h2buf, void* part,
-                               unsigned* tstat, float* cbuf, unsigned long long* stats, hipStream_t st) {
-    int tiles, deal;
-    DVQ_PROPAGATE(pn_filter_geometry(N, &tiles, &deal));
-    static DvqOncePerDevice attr_once;
-    {
-        const hipError_t e = attr_once.run([] {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&pn_trunk_filter_kernel<3, false>),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, DVQ_DIAG_ON ? 100 * 1024 : F_LDS);
-            if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&pn_trunk_filter_kernel<4, false>),
-                                                         hipFuncAttributeMaxDynamicSharedMemorySize, DVQ_DIAG_ON ? 100 * 1024 : F_LDS);
-            if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&pn_trunk_filter_kernel<3, true>),
-                                                         hipFuncAttributeMaxDynamicSharedMemorySize, F_LDS_TAIL);
-            if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&pn_trunk_filter_kernel<4, true>),
-                                                         hipFuncAttributeMaxDynamicSharedMemorySize, F_LDS_TAIL);
-            return e;
-        });
-        if (e != hipSuccess) {
-            dvq_set_error("pointnet: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
-            return DVQ_ELAUNCH;
-        }
-    }
-    qf32x2* part2 = reinterpret_cast<qf32x2*>((char*)part + (size_t)B * tiles * 1024 * 16);   // behind the float4 records (pointnet.hip: 96 B per padded point)
-    const long grid = B * deal;
-    DVQ_REQUIRE(B * tiles < (1L << 31), "pointnet: grid too large");
-    DVQ_REQUIRE(Npad >= N, "pointnet: bad padded row count");
+// the instances of the two kernels templated on the channel count (3 or 4)
+using TrunkFilterKernel = decltype(&pn_trunk_filter_kernel<3, false>);
+static TrunkFilterKernel trunk_filter_kernel(int C, bool tail) {
+    static const TrunkFilterKernel k[2][2] = {{&pn_trunk_filter_kernel<3, false>, &pn_trunk_filter_kernel<3, true>},
+                                              {&pn_trunk_filter_kernel<4, false>, &pn_trunk_filter_kernel<4, true>}};
+    return k[C == 4][tail];
+}
+static decltype(&pn_center_kernel<3>) center_kernel(int C) { return C == 4 ? &pn_center_kernel<4> : &pn_center_kernel<3>; }
+
+int dvq_launch_pn_filter_front(const PnBatch& in, const PnTrunkWeights& w, const PnSlot& sl, unsigned long long* stats, hipStream_t st) {
+    PnGeometry g;
+    DVQ_PROPAGATE(filter_geometry(in.N, &g));
+    static DvqOncePerDevice attr_once[2][2];
+    for (int c = 0; c < 2; ++c)
+        for (int tail = 0; tail < 2; ++tail)
+            DVQ_PROPAGATE(dvq_lds_limit(attr_once[c][tail], reinterpret_cast<const void*>(trunk_filter_kernel(3 + c, tail)),
+                                        tail ? F_LDS_TAIL : (DVQ_DIAG_ON ? 100 * 1024 : F_LDS), "pointnet"));
+    const long B = in.B, grid = B * g.deal;
+    DVQ_REQUIRE(B * g.tiles < (1L << 31), "pointnet: grid too large");
     if (stats && hipMemsetAsync(stats, 0, 64, st) != hipSuccess) {       // statistics runs only; tstat is zeroed by pn_center_kernel
         dvq_set_error("pointnet: hipMemsetAsync failed");
         return DVQ_ELAUNCH;
     }
     {
         DVQ_PROF("pn_center", 2.0 * (double)B * 4 * (4.0 * 64 + 64.0 * 128), (double)B * (64 + 512), st);
-        const unsigned cgrid = (unsigned)((B + CENTER_SPB - 1) / CENTER_SPB);
-        if (C == 3) DVQ_LAUNCH(pn_center_kernel<3>, dim3(cgrid), dim3(256), 0, st, pc, trans, N, B, W1, b1, W2, b2, cbuf, tstat, tiles);
-        else DVQ_LAUNCH(pn_center_kernel<4>, dim3(cgrid), dim3(256), 0, st, pc, trans, N, B, W1, b1, W2, b2, cbuf, tstat, tiles);
+        DVQ_LAUNCH(center_kernel(in.C), dim3((unsigned)((B + CENTER_SPB - 1) / CENTER_SPB)), dim3(256), 0, st, in.pc, in.trans, in.N, B, w.w1,
+                   w.b1, w.w2, w.b2, sl.cbuf, sl.tstat, g.tiles);
     }
     DVQ_CHECK_LAUNCH("pn_center");
-    const double pts = (double)B * (deal * 256 + (deal < tiles ? 32 : 0));
+    const double pts = (double)B * g.slots;
     const int abl = pn_abl();
-#ifdef DVQ_DIAG
-    if ((abl & 262144) && C == 4) {
-        // timing only (results INVALID): what splitting the trunk into a producer kernel (conv1 / conv2 / centring / conversion) and a
-        // consumer kernel (conv3 loop) would buy if the two ran BESIDE each other: the same grid twice, the halves of the work on two streams
-        static hipStream_t side = nullptr;
-        static hipEvent_t ev0 = nullptr, ev1 = nullptr;
-        if (!side) { (void)hipStreamCreateWithFlags(&side, hipStreamNonBlocking); (void)hipEventCreateWithFlags(&ev0, hipEventDisableTiming); (void)hipEventCreateWithFlags(&ev1, hipEventDisableTiming); }
-        DVQ_PROF("pn_trunk", 2.0 * pts * (4.0 * 64 + 64.0 * 128 + 128.0 * 1024), pts * (16 + 512) + (double)grid * 16384, st);
-        (void)hipEventRecord(ev0, st);
-        (void)hipStreamWaitEvent(side, ev0, 0);
-        DVQ_LAUNCH((pn_trunk_filter_kernel<4, false>), dim3((unsigned)grid), dim3(256), F_LDS, st, pc, trans, N, Npad, tiles, deal, B, W1, b1,
-                   b2, (const char*)w3f, h2buf, (f32x4*)part, part2, tstat, cbuf, (abl & ~262144) | 2);
-        DVQ_LAUNCH((pn_trunk_filter_kernel<4, false>), dim3((unsigned)grid), dim3(256), F_LDS, side, pc, trans, N, Npad, tiles, deal, B, W1, b1,
-                   b2, (const char*)w3f, h2buf, (f32x4*)part, part2, tstat, cbuf, (abl & ~262144) | 131072 | 1);
-        (void)hipEventRecord(ev1, side);
-        (void)hipStreamWaitEvent(st, ev1, 0);
-        return DVQ_OK;
-    }
-#endif
+    // one launch of the trunk kernel: the full-tile grid (a workgroup per sample and dealt tile) or the tail grid (four samples each)
+    auto launch = [&](bool tail, int lds, hipStream_t s, int abl_arg) {
+        DVQ_LAUNCH(trunk_filter_kernel(in.C, tail), dim3((unsigned)(tail ? (B + 3) / 4 : grid)), dim3(256), lds, s, in.pc, in.trans, in.N, g.Npad,
+                   g.tiles, g.deal, B, w.w1, w.b1, w.b2, (const char*)w.w3f, sl.h2, (f32x4*)sl.part, (qf32x2*)sl.part2, sl.tstat, sl.cbuf, abl_arg);
+    };
     {
         DVQ_PROF("pn_trunk", 2.0 * pts * (4.0 * 64 + 64.0 * 128 + 128.0 * 1024), pts * (16 + 512) + (double)grid * 16384, st);
-        const int lds_main = (abl & 524288) ? 100 * 1024 : F_LDS;   // diagnostics: ONE workgroup per CU (what a wave costs when it has its SIMD to itself)
-        if (C == 3)
-            DVQ_LAUNCH((pn_trunk_filter_kernel<3, false>), dim3((unsigned)grid), dim3(256), lds_main, st, pc, trans, N, Npad, tiles, deal, B, W1, b1,
-                       b2, (const char*)w3f, h2buf, (f32x4*)part, part2, tstat, cbuf, abl);
-        else
-            DVQ_LAUNCH((pn_trunk_filter_kernel<4, false>), dim3((unsigned)grid), dim3(256), lds_main, st, pc, trans, N, Npad, tiles, deal, B, W1, b1,
-                       b2, (const char*)w3f, h2buf, (f32x4*)part, part2, tstat, cbuf, abl);
-        if (deal < tiles) {
-            const unsigned tgrid = (unsigned)((B + 3) / 4);
-            if (C == 3)
-                DVQ_LAUNCH((pn_trunk_filter_kernel<3, true>), dim3(tgrid), dim3(256), F_LDS_TAIL, st, pc, trans, N, Npad, tiles, deal, B, W1, b1,
-                           b2, (const char*)w3f, h2buf, (f32x4*)part, part2, tstat, cbuf, abl);
-            else
-                DVQ_LAUNCH((pn_trunk_filter_kernel<4, true>), dim3(tgrid), dim3(256), F_LDS_TAIL, st, pc, trans, N, Npad, tiles, deal, B, W1, b1,
-                           b2, (const char*)w3f, h2buf, (f32x4*)part, part2, tstat, cbuf, abl);
+#ifdef DVQ_DIAG
+        if ((abl & PN_ABL_SPLIT) && in.C == 4) {
+            // timing only (results INVALID): what splitting the trunk into a producer kernel (conv1 / conv2 / centring / conversion) and a
+            // consumer kernel (conv3 loop) would buy if the two ran BESIDE each other: the same grid twice, the halves of the work on two streams
+            static hipStream_t side = nullptr;
+            static hipEvent_t ev0 = nullptr, ev1 = nullptr;
+            if (!side) { (void)hipStreamCreateWithFlags(&side, hipStreamNonBlocking); (void)hipEventCreateWithFlags(&ev0, hipEventDisableTiming); (void)hipEventCreateWithFlags(&ev1, hipEventDisableTiming); }
+            (void)hipEventRecord(ev0, st);
+            (void)hipStreamWaitEvent(side, ev0, 0);
+            launch(false, F_LDS, st, (abl & ~PN_ABL_SPLIT) | PN_ABL_NO_CONV3);
+            launch(false, F_LDS, side, (abl & ~PN_ABL_SPLIT) | PN_ABL_CONSUMER | PN_ABL_NO_H2_STORE);
+            (void)hipEventRecord(ev1, side);
+            (void)hipStreamWaitEvent(st, ev1, 0);
+            return DVQ_OK;
         }
+#endif
+        launch(false, (abl & PN_ABL_ONE_PER_CU) ? 100 * 1024 : F_LDS, st, abl);
+        if (g.has_tail()) launch(true, F_LDS_TAIL, st, abl);
     }
     DVQ_CHECK_LAUNCH("pn_trunk_filter");
     return DVQ_OK;
 }
 
-int dvq_launch_pn_filter_back(int N, int Npad, long B, const void* w3f, const float* w3, const float* b3, int relu, const float* h2buf,
-                              const void* part, const unsigned* tstat, const float* cbuf, float* feat, long ld_feat, unsigned long long* stats,
-                              hipStream_t st) {
-    int tiles, deal;
-    DVQ_PROPAGATE(pn_filter_geometry(N, &tiles, &deal));
-    const qf32x2* part2 = reinterpret_cast<const qf32x2*>((const char*)part + (size_t)B * tiles * 1024 * 16);
+int dvq_launch_pn_filter_back(const PnBatch& in, const PnTrunkWeights& w, const PnSlot& sl, float* feat, long ld_feat,
+                              unsigned long long* stats, hipStream_t st) {
+    PnGeometry g;
+    DVQ_PROPAGATE(filter_geometry(in.N, &g));
+    const long B = in.B;
+    const int N = in.N, tiles = g.tiles;
+    const unsigned* tstat = sl.tstat;
     const int abl = pn_abl();
     const DvqKnobs& kn = dvq_knobs();
     const int exhaustive = kn.pn_exhaustive;
@@ -1446,13 +1420,13 @@ int dvq_launch_pn_filter_back(int N, int Npad, long B, const void* w3f, const fl
     }
     {
         DVQ_PROF("pn_exact", 2.0 * (double)B * 1024 * 128, (double)B * (tiles * 16384.0 + 1024.0 * 512 + 4096), st);
-        DVQ_LAUNCH(pn_exact_kernel, dim3((unsigned)B), dim3(256), 0, st, (const f32x4*)part, part2, tiles, deal, h2buf, N, Npad, w3, b3,
-                   reinterpret_cast<const float*>((const char*)w3f + IMG_OFF_WN),
-                   reinterpret_cast<const float*>((const char*)w3f + IMG_OFF_RN), tstat, cbuf, relu, exhaustive, pair_cap, fb_cap,
+        DVQ_LAUNCH(pn_exact_kernel, dim3((unsigned)B), dim3(256), 0, st, (const f32x4*)sl.part, (const qf32x2*)sl.part2, tiles, g.deal, sl.h2, N,
+                   g.Npad, w.w3, w.b3, reinterpret_cast<const float*>((const char*)w.w3f + IMG_OFF_WN),
+                   reinterpret_cast<const float*>((const char*)w.w3f + IMG_OFF_RN), tstat, sl.cbuf, w.relu3, exhaustive, pair_cap, fb_cap,
                    feat, ld_feat, stats, abl);
     }
     DVQ_CHECK_LAUNCH("pn_exact");
-    if (stats && (abl & 4096)) {
+    if (stats && (abl & PN_ABL_STAMPS)) {
         const long nrec = B * tiles;                       // a tail tile's record carries its workgroup's stamps too
         std::vector<unsigned> ts((size_t)nrec * 4);
         (void)hipStreamSynchronize(st);
@@ -1462,7 +1436,7 @@ int dvq_launch_pn_filter_back(int N, int Npad, long B, const void* w3f, const fl
             const unsigned v = ts[4 * i + 3];
             a += v & 255; b2_ += (v >> 8) & 255; c += (v >> 16) & 255; d += (v >> 24) & 255;
         }
-        if (abl & 8192) {
+        if (abl & PN_ABL_CLOCK) {
             double mhz = 0;
             for (long i = 0; i < nrec; ++i) mhz += ts[4 * i + 3];
             fprintf(stderr, "[dvq pn] in-kernel clock of the trunk kernel: %.0f MHz (s_memtime over s_memrealtime, mean over %ld workgroups)\n", mhz / nrec, nrec);
@@ -1478,19 +1452,11 @@ int dvq_launch_pn_filter_back(int N, int Npad, long B, const void* w3f, const fl
         const double tot = (double)B * 1024;
         fprintf(stderr, "[dvq pn] B=%ld N=%d: one candidate %.4f, other counts %.4f of the channels, flagged 16-point groups %.5f per channel; %.3f candidate dots per channel\n",
                 B, N, h[0] / tot, h[1] / tot, h[2] / tot, h[3] / tot);
-        if (abl & 4096)
+        if (abl & PN_ABL_STAMPS)
             fprintf(stderr, "[dvq pn] exact stage, mean cycles per workgroup: records -> candidates %.0f, sort by point %.0f, candidate dots %.0f, flagged groups + checks + store %.0f\n",
                     (double)h[4] / B, (double)h[5] / B, (double)h[6] / B, (double)h[7] / B);
     }
     return DVQ_OK;
-}
-
-int dvq_launch_pn_trunk_filter(const float* pc, int C, int N, int Npad, long B, const float* trans, const float* W1, const float* b1,
-                               const float* W2, const uint16_t* W2p, const float* b2, const void* w3f, const float* w3, const float* b3,
-                               int relu, float* h2buf, void* part, unsigned* tstat, float* cbuf, float* feat, long ld_feat,
-                               unsigned long long* stats, hipStream_t st) {
-    DVQ_PROPAGATE(dvq_launch_pn_filter_front(pc, C, N, Npad, B, trans, W1, b1, W2, W2p, b2, w3f, h2buf, part, tstat, cbuf, stats, st));
-    return dvq_launch_pn_filter_back(N, Npad, B, w3f, w3, b3, relu, h2buf, part, tstat, cbuf, feat, ld_feat, stats, st);
 }
 
 // host side of the consistency counters: [0] suspect tile records, [1] channels outside their records' interval (per device)

@@ -37,6 +37,34 @@ def test_workspace_queries_need_no_gpu():
     assert lib.dvq_pointnet_workspace_bytes(0, 1024) > 0
 
 
+# dvq_pointnet_workspace_bytes(B, N), default environment, as the library of commit e2b29a1 (before the plan's arithmetic moved into
+# csrc/pn_filter.h) answered: rows B, columns _WS_N
+_WS_N = (1, 64, 100, 257, 300, 778, 1024, 1290, 3000, 16384, 16385)
+_WS_BYTES = {
+    1: (229632, 229632, 229632, 450816, 450816, 893184, 893184, 1335552, 2662656, 14164992, 14386432),
+    2: (458496, 458496, 458496, 900864, 900864, 1785600, 1785600, 2670336, 5324800, 28329472, 28772096),
+    5: (1145344, 1145344, 1145344, 2251264, 2251264, 4463360, 4463360, 6675200, 13311232, 70823168, 71929344),
+    2047: (468648704, 468648704, 468648704, 921445120, 921445120, 1827037952, 1827037952, 2732630784, 5449409280, 8172736768, 8300381440),
+    2048: (163725568, 163725568, 163725568, 323125504, 323125504, 641925376, 641925376, 960725248, 1917124864, 8172736768, 8300381440),
+    4096: (327450880, 327450880, 327450880, 646250752, 646250752, 1283850496, 1283850496, 1921450240, 3834249472, 9089794304, 9231760128),
+    7282: (582312448, 582312448, 582312448, 1149240832, 1149240832, 2283097600, 2283097600, 3416953856, 6818523648, 9089998336, 9231964160),
+    8192: (654901504, 654901504, 654901504, 1292501248, 1292501248, 2567700736, 2567700736, 3842900224, 7668498688, 9608319232, 9232022272),
+    65536: (1312948480, 1312948480, 1312948480, 2588147968, 2588147968, 5138546944, 5138546944, 7688945920, 9443141376, 9611989248, 9620337920),
+}
+
+
+def test_pointnet_workspace_plan_is_pinned():
+    """The PointNet workspace plan byte for byte (samples per launch, scratch sets, every array's size and alignment) over batch
+    sizes on both sides of the launch-splitting thresholds and cloud sizes with and without padding, tail tile and beyond the filtered
+    trunk's limit.  No GPU."""
+    lib = _lib.load()
+    assert "DVQ_PN_CHUNK" not in os.environ and "DVQ_PN_SLOTS" not in os.environ, "the table holds for the default plan"
+    for B, row in _WS_BYTES.items():
+        assert len(row) == len(_WS_N)
+        for N, want in zip(_WS_N, row):
+            assert lib.dvq_pointnet_workspace_bytes(B, N) == want, (B, N)
+
+
 def test_ops_refuse_cpu_tensors():
     import pytest
     import torch

@@ -1,5 +1,6 @@
 """The slot / id / group layout of the filtered PointNet trunk on v_mfma_f32_16x16x32_f16 (csrc/pn_slots.h, shared by
-pn_trunk_filter_kernel and pn_exact_kernel): a host program checks the maps for whole clouds, the wait-state rule of the
+pn_trunk_filter_kernel and pn_exact_kernel) and its tile geometry and scratch layout (csrc/pn_filter.h, shared by the launchers and
+the workspace plan): a host program checks the maps for whole clouds and the scratch arrays of a set, the wait-state rule of the
 v_permlane16_swap_b32 relayout is unit-tested, and on the GPU the filtered features equal the exhaustive evaluation bit for bit at
 sizes that put tile, row-block and lane-quarter boundaries on real points."""
 import os
@@ -13,20 +14,13 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "d-vqvae_amd", "csrc")
 
 HOST_PROGRAM = r"""
-#include "pn_slots.h"
+#include "pn_filter.h"
 #include <cstdio>
 #include <cstdlib>
 #include <set>
 #include <vector>
 static int fails = 0;
 #define CHECK(cond, ...) do { if (!(cond)) { if (fails < 20) { printf("FAIL %s: ", #cond); printf(__VA_ARGS__); printf("\n"); } ++fails; } } while (0)
-
-// the geometry of dvq_launch_pn_filter_front (pn_filter_geometry)
-static void geometry(int N, bool tail, int* tiles, int* deal) {
-    *tiles = (N + 255) / 256;
-    const int over = N - 256 * (*tiles - 1);
-    *deal = (*tiles >= 2 && over <= 32 && tail) ? *tiles - 1 : *tiles;
-}
 
 static void check_tile_maps() {
     // (wave, row block, quarter, register) <-> slot: a bijection onto 0 .. 255; the lane that feeds conv1 / conv2 with the point of
@@ -58,8 +52,8 @@ static void check_tile_maps() {
 }
 
 static void check_cloud(int N, bool tail) {
-    int tiles, deal;
-    geometry(N, tail, &tiles, &deal);
+    const PnGeometry g = pn_geometry(N, tail);              // the library's own geometry (launchers, workspace plan)
+    const int tiles = g.tiles, deal = g.deal;
     std::vector<int> hits(N, 0);
     for (int t = 0; t < tiles; ++t) {
         std::set<int> pts;
@@ -95,10 +89,35 @@ static void check_cloud(int N, bool tail) {
     for (int p = 0; p < N; ++p) CHECK(hits[p] >= 1, "N %d (tail %d): point %d is in no slot", N, (int)tail, p);
 }
 
+// the arrays of a scratch set (pn_set_layout): in order, 256-byte aligned, none reaching into the next; per sample they add up to what
+// the workspace plan has always reserved -- 512 B of conv2 row and 96 B of tile records per padded point, 16 B of tile maxima per tile,
+// 512 B of centre -- and the evaluated slots are the dealt tiles' 256 each + the tail tile's 32
+static void check_scratch(int N, bool tail) {
+    const PnGeometry g = pn_geometry(N, tail);
+    CHECK(g.Npad == 256 * g.tiles && g.Npad >= N && g.Npad - N < 256, "N %d: Npad %d", N, g.Npad);
+    CHECK(g.slots == 256L * g.deal + (g.deal < g.tiles ? 32 : 0), "N %d: slots %ld", N, g.slots);
+    CHECK(g.per_sample() == (size_t)g.Npad * 128 * 4 + (size_t)g.Npad * 96 + (size_t)(g.Npad / 256) * 16 + 512, "N %d: %zu B per sample", N, g.per_sample());
+    CHECK(g.part() >= (size_t)(g.Npad / 128) * 1024 * 4, "N %d: part does not hold the fused trunk's [tiles128][1024] floats", N);
+    const size_t counts[] = {1, 5, 300};                    // (launch sizes below the plan's 4.5 GB per set at every N walked)
+    for (size_t n : counts) {
+        const PnSetLayout l = pn_set_layout(g, n);
+        const size_t off[6] = {l.h2, l.part, l.part2, l.tstat, l.cbuf, l.bytes};
+        const size_t len[5] = {n * g.h2, n * g.rec4, n * g.rec2, n * g.tstat, n * g.cbuf};
+        CHECK(off[0] == 0, "N %d: the set starts at %zu", N, off[0]);
+        for (int i = 0; i < 5; ++i) {
+            CHECK(off[i] + len[i] <= off[i + 1], "N %d, %zu samples: array %d [%zu, +%zu) reaches into the next at %zu", N, n, i, off[i], len[i], off[i + 1]);
+            CHECK(off[i] % (i == 2 ? 16 : 256) == 0, "N %d, %zu samples: array %d at %zu", N, n, i, off[i]);
+        }
+        CHECK(l.part2 == l.part + n * g.rec4, "N %d: the float2 records do not follow the float4 records", N);
+        CHECK(l.bytes - n * g.per_sample() < 4 * 256, "N %d, %zu samples: %zu B for %zu B of arrays", N, n, l.bytes, n * g.per_sample());
+        if (tail) printf("SET %d %zu %zu\n", N, n, l.bytes);
+    }
+}
+
 int main() {
     check_tile_maps();
     const int sizes[] = {1024, 778, 3000, 16, 17, 33, 255, 256, 257, 288, 289};
-    for (int N : sizes) { check_cloud(N, true); check_cloud(N, false); }
+    for (int N : sizes) { check_cloud(N, true); check_cloud(N, false); check_scratch(N, true); check_scratch(N, false); }
     if (fails) printf("%d check(s) failed\n", fails);
     else printf("OK\n");
     return fails ? 1 : 0;
@@ -116,11 +135,7 @@ def _host_compiler():
     return None
 
 
-def test_slot_id_and_group_maps_on_the_host(tmp_path):
-    """csrc/pn_slots.h compiled for the host: slot <-> (wave, row block, lane quarter, register) <-> point is a bijection onto a
-    tile's points (padding slots fold onto real points), slot_of_id inverts the id the chain and the publishing wave write, and a
-    flagged group's sixteen slots are the sixteen points one lane scored -- for every tile of N = 1024, 778 (tail tile) and 3000,
-    with and without the tail tile, and for small clouds."""
+def _run_host_program(tmp_path):
     cc = _host_compiler()
     if cc is None:
         pytest.skip("no host C++ compiler (g++ / hipcc) found")
@@ -131,6 +146,45 @@ def test_slot_id_and_group_maps_on_the_host(tmp_path):
     assert r.returncode == 0, r.stderr[-3000:]
     r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0 and r.stdout.strip().endswith("OK"), r.stdout[-3000:] + r.stderr[-1000:]
+    return r.stdout
+
+
+def test_slot_id_and_group_maps_on_the_host(tmp_path):
+    """csrc/pn_slots.h compiled for the host: slot <-> (wave, row block, lane quarter, register) <-> point is a bijection onto a
+    tile's points (padding slots fold onto real points), slot_of_id inverts the id the chain and the publishing wave write, and a
+    flagged group's sixteen slots are the sixteen points one lane scored -- for every tile of N = 1024, 778 (tail tile) and 3000,
+    with and without the tail tile, and for small clouds.  The geometry is the library's own (csrc/pn_filter.h: pn_geometry)."""
+    _run_host_program(tmp_path)
+
+
+def test_scratch_set_layout_is_what_the_workspace_plan_reserves(tmp_path):
+    """csrc/pn_filter.h compiled for the host, for the same sizes and both tail settings: the arrays of a scratch set (conv2 rows,
+    float4 and float2 tile records, tile maxima, centres) lie in order without overlap and add up, per sample, to the bytes the plan
+    reserves; and the library's dvq_pointnet_workspace_bytes grows by exactly pn_set_layout(...).bytes per additional scratch set
+    (DVQ_PN_SLOTS 2 -> 3 at a fixed launch size).  No GPU."""
+    from dvqvae_amd import _lib
+    lib = _lib.load()
+    sets = [tuple(int(v) for v in ln.split()[1:]) for ln in _run_host_program(tmp_path).splitlines() if ln.startswith("SET ")]
+    assert len(sets) == 11 * 3
+
+    def workspace(env, B, N):
+        old = {k: os.environ.get(k) for k in env}
+        os.environ.update(env)
+        lib.dvq_reload_env()
+        try:
+            return lib.dvq_pointnet_workspace_bytes(B, N)
+        finally:
+            for k, v in old.items():
+                if v is None:
+                    del os.environ[k]
+                else:
+                    os.environ[k] = v
+            lib.dvq_reload_env()
+    for N, samples, set_bytes in sets:
+        env = {"DVQ_PN_CHUNK": str(samples)}
+        two = workspace(dict(env, DVQ_PN_SLOTS="2"), 4 * samples, N)
+        three = workspace(dict(env, DVQ_PN_SLOTS="3"), 4 * samples, N)
+        assert three - two == set_bytes, (N, samples, two, three, set_bytes)
 
 
 def test_hazard_checker_permlane_swap_rule():
