@@ -22,7 +22,7 @@ _lock = threading.Lock()
 _lib = None
 
 DVQ_MAX_SRC = 8
-ABI_VERSION = 10           # DVQ_ABI_VERSION of include/dvq.h, which the struct mirrors below follow (tests/test_abi.py compares both with the library's)
+ABI_VERSION = 10           # DVQ_ABI_VERSION of include/dvq.h (dvq_pixelcnn_sample_ctl: an added symbol, same version), which the struct mirrors below follow (tests/test_abi.py compares both with the library's)
 PLANES_BF16X3, PLANES_F16X2 = 0, 1
 
 c_f32p = C.c_void_p      # device pointers travel as integers
@@ -60,6 +60,11 @@ class PixelcnnWeights(C.Structure):
                 ("layers_host", C.POINTER(PixelcnnLayer)), ("w0", C.c_void_p), ("b0", C.c_void_p),
                 ("w2", C.c_void_p), ("b2", C.c_void_p), ("w0_p", C.c_void_p), ("w2_p", C.c_void_p),
                 ("s0", C.c_void_p), ("s2", C.c_void_p), ("class_tables", C.c_void_p)]
+
+
+class PixelcnnCtl(C.Structure):
+    _fields_ = [("temperature", C.c_float), ("top_k", C.c_int32), ("given", C.c_void_p), ("logp_model_out", C.c_void_p),
+                ("logp_draw_out", C.c_void_p)]
 
 
 class ManoModel(C.Structure):
@@ -106,6 +111,8 @@ SIGNATURES = {
     "dvq_pixelcnn_workspace_bytes": (C.c_size_t, [C.POINTER(PixelcnnWeights), C.c_int64]),
     "dvq_pixelcnn_sample": (C.c_int, [C.POINTER(PixelcnnWeights), c_i64p, c_f32p, C.c_int64, c_i64p, c_f32p, c_i32p,
                                       C.c_void_p, C.c_size_t, c_stream]),
+    "dvq_pixelcnn_sample_ctl": (C.c_int, [C.POINTER(PixelcnnWeights), c_i64p, c_f32p, C.c_int64, C.POINTER(PixelcnnCtl), c_i64p, c_f32p,
+                                          c_i32p, C.c_void_p, C.c_size_t, c_stream]),
     "dvq_pixelcnn_forward": (C.c_int, [C.POINTER(PixelcnnWeights), c_i64p, c_i64p, C.c_int64, c_f32p, c_i32p, C.c_void_p,
                                        C.c_size_t, c_stream]),
     "dvq_mano_workspace_bytes": (C.c_size_t, [C.c_int64]),

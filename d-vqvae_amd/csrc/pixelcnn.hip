@@ -105,6 +105,185 @@ __global__ void sample_kernel(const float* __restrict__ logits, const float* __r
     for (int c = lane * 4; c < dim; c += 256) *reinterpret_cast<f32x4*>(x0 + b * dim + c) = *reinterpret_cast<const f32x4*>(e + c);
 }
 
+// ---- the controlled draw (dvq_pixelcnn_sample_ctl): temperature, top-k, per-position given codes, log-probabilities.
+// Unsigned key whose integer order is the float order (-0 counts as +0; rows with a NaN never use their keys).
+__device__ __forceinline__ uint32_t order_key(float v) {
+    if (v == 0.f) v = 0.f;
+    const uint32_t u = __float_as_uint(v);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
+// One wave per sample, lane ``lane`` owns tokens k = lane + 64 j (sample_kernel's striding, so the per-lane and the butterfly
+// reduction orders are sample_kernel's).  s = l / T.  Top-k: the top_k-th largest key is found bit by bit from the top (a bit stays
+// set when at least top_k keys are >= the candidate: one ballot + population count per 64 tokens and bit); keys above it are kept,
+// and of the keys equal to it the first ``need`` in index order (their rank = equal keys in lower j + equal lanes below this one).
+// Softmax and race run over the kept set with excluded terms adding +0.0f.  REG: n_in <= 512, s lives in registers.  No LDS, no
+// barrier; every loop that holds a ballot has a wave-uniform trip count.
+template <bool REG>
+__global__ void sample_ctl_kernel(const float* __restrict__ logits, const float* __restrict__ noise /* [B,9,n_in] at this chunk, or null */,
+                                  int pos, int n_in, long Bc, const int64_t* __restrict__ given /* [B,9] (< 0: draw) or null */,
+                                  int64_t* __restrict__ codes /* [B,9] */, const float* __restrict__ tok_emb, int dim,
+                                  float* __restrict__ x0 /* [Bc,dim] */, float* __restrict__ logits_out /* [B,9,n_in] or null */,
+                                  int32_t* err_flag, const int64_t* __restrict__ lrow, float T, int top_k,
+                                  float* __restrict__ logp_model /* [B,9] or null */, float* __restrict__ logp_draw /* [B,9] or null */) {
+    constexpr int NJ = 8;
+    const int lane = threadIdx.x & 63;
+    const long b = (long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    if (b >= Bc) return;
+    const float* lg = logits + (lrow ? lrow[b] : b) * n_in;
+    if (logits_out)
+        for (int k = lane; k < n_in; k += 64) logits_out[(b * NPOS + pos) * n_in + k] = lg[k];
+    int64_t gv = given ? given[b * NPOS + pos] : -1;
+    bool is_given = gv >= 0;
+    if (gv >= n_in || (!is_given && !noise)) {             // a token out of range; or a draw asked of a call that brought no noise
+        if (lane == 0 && err_flag) atomicOr(err_flag, 1);
+        gv = 0;
+        is_given = true;
+    }
+    const bool sel = top_k > 0 && top_k < n_in;
+    const int nj = REG ? NJ : (n_in + 63) / 64;
+    float sreg[NJ];
+    if constexpr (REG) {
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) {
+            const int k = lane + 64 * j;
+            sreg[j] = k < n_in ? lg[k] / T : -INFINITY;
+        }
+    }
+    auto sval = [&](int j, int k) -> float {               // k = lane + 64 j < n_in
+        if constexpr (REG) return sreg[j];
+        else return lg[k] / T;
+    };
+    float mx = -INFINITY;
+    unsigned long long nan_lanes = 0;
+#pragma unroll
+    for (int j = 0; j < nj; ++j) {
+        const int k = lane + 64 * j;
+        const bool valid = k < n_in;
+        const float s = valid ? sval(j, k) : -INFINITY;
+        mx = fmaxf(mx, s);
+        nan_lanes |= __ballot(s != s);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
+    const bool nan_row = nan_lanes != 0;
+    uint32_t thr = 0;
+    int need = 0;
+    if (sel) {
+        for (int bit = 31; bit >= 0; --bit) {
+            const uint32_t cand = thr | (1u << bit);
+            int cnt = 0;
+#pragma unroll
+            for (int j = 0; j < nj; ++j) {
+                const int k = lane + 64 * j;
+                const bool valid = k < n_in;
+                const uint32_t key = valid ? order_key(sval(j, k)) : 0u;
+                cnt += __popcll(__ballot(key >= cand));
+            }
+            if (cnt >= top_k) thr = cand;
+        }
+        int gt = 0;
+#pragma unroll
+        for (int j = 0; j < nj; ++j) {
+            const int k = lane + 64 * j;
+            const bool valid = k < n_in;
+            const uint32_t key = valid ? order_key(sval(j, k)) : 0u;
+            gt += __popcll(__ballot(valid && key > thr));
+        }
+        need = top_k - gt;
+    }
+    const unsigned long long below = (1ull << lane) - 1ull;
+    // kept(j): is token lane + 64 j in the kept set; ``eq_before`` carries the equal keys of lower j (wave-uniform)
+    auto kept_at = [&](int j, int k, bool valid, float s, int& eq_before) -> bool {
+        if (!sel) return valid;
+        const uint32_t key = valid ? order_key(s) : 0u;
+        const bool eq = valid && key == thr;
+        const unsigned long long m = __ballot(eq);
+        const int rank = eq_before + __popcll(m & below);
+        eq_before += __popcll(m);
+        return valid && (key > thr || (eq && rank < need));
+    };
+    float sum = 0.f;
+    int given_kept = 0;
+    {
+        int eqb = 0;
+#pragma unroll
+        for (int j = 0; j < nj; ++j) {
+            const int k = lane + 64 * j;
+            const bool valid = k < n_in;
+            const float s = valid ? sval(j, k) : -INFINITY;
+            const bool kept = kept_at(j, k, valid, s, eqb);
+            if (valid) sum += kept ? expf(s - mx) : 0.0f;
+            if (kept && is_given && k == (int)gv) given_kept = 1;
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
+    int64_t code;
+    bool nan_draw = false, code_kept;
+    if (is_given) {
+        code = gv;
+        code_kept = __ballot(given_kept != 0) != 0;
+        if (lane == 0) codes[b * NPOS + pos] = code;
+    } else {
+        const float* q = noise + (b * NPOS + pos) * n_in;
+        float best = -INFINITY;
+        int bi = 0x7fffffff;
+        int eqb = 0;
+#pragma unroll
+        for (int j = 0; j < nj; ++j) {
+            const int k = lane + 64 * j;
+            const bool valid = k < n_in;
+            const float sv = valid ? sval(j, k) : -INFINITY;
+            const bool kept = kept_at(j, k, valid, sv, eqb);
+            if (kept) {
+                const float p = expf(sv - mx) / sum;
+                const float s = p / q[k];
+                if (s > best || (s == best && k < bi)) { best = s; bi = k; }
+            }
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const float ob = __shfl_xor(best, o);
+            const int oi = __shfl_xor(bi, o);
+            if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
+        }
+        nan_draw = nan_row || bi == 0x7fffffff;            // as sample_kernel: -1 to the caller, bit 2, the sampler goes on from token 0
+        if (nan_draw) {
+            bi = 0;
+            if (lane == 0 && err_flag) atomicOr(err_flag, 4);
+        }
+        code = bi;
+        code_kept = true;
+        if (lane == 0) codes[b * NPOS + pos] = nan_draw ? -1 : code;
+    }
+    if (logp_model || logp_draw) {
+        const float lc = lg[code];
+        const float sc = lc / T;
+        float lm, ld = code_kept ? (sc - mx) - logf(sum) : -INFINITY;
+        if (T == 1.0f && !sel) {
+            lm = ld;                                        // s = l and the kept set is everything
+        } else {
+            float mxl = -INFINITY;
+            for (int k = lane; k < n_in; k += 64) mxl = fmaxf(mxl, lg[k]);
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) mxl = fmaxf(mxl, __shfl_xor(mxl, o));
+            float suml = 0.f;
+            for (int k = lane; k < n_in; k += 64) suml += expf(lg[k] - mxl);
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) suml += __shfl_xor(suml, o);
+            lm = (lc - mxl) - logf(suml);
+        }
+        if (nan_row || nan_draw) lm = ld = __builtin_nanf("");
+        if (lane == 0) {
+            if (logp_model) logp_model[b * NPOS + pos] = lm;
+            if (logp_draw) logp_draw[b * NPOS + pos] = ld;
+        }
+    }
+    const float* e = tok_emb + code * dim;
+    for (int c = lane * 4; c < dim; c += 256) *reinterpret_cast<f32x4*>(x0 + b * dim + c) = *reinterpret_cast<const f32x4*>(e + c);
+}
+
 __global__ void iota_kernel(int64_t* __restrict__ out, int n) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) out[i] = i;
@@ -210,8 +389,10 @@ int check_weights(const dvq_pixelcnn_weights* w) {
 }
 
 // ``build`` non-null: only the class tables of ``w``, into that buffer (dvq_pixelcnn_build_tables)
+// ``ctl`` non-null: the draws of dvq_pixelcnn_sample_ctl (sample_ctl_kernel in sample_kernel's place; ``forced`` is null then)
 int run(const dvq_pixelcnn_weights* w, const int64_t* label, const float* noise, const int64_t* forced, int64_t B,
-        int64_t* codes, float* logits_out, int32_t* err_flag, void* ws, size_t ws_bytes, hipStream_t st, void* build = nullptr) {
+        int64_t* codes, float* logits_out, int32_t* err_flag, void* ws, size_t ws_bytes, hipStream_t st, void* build = nullptr,
+        const dvq_pixelcnn_ctl* ctl = nullptr) {
     DVQ_PROPAGATE(check_weights(w));
     Plan pl;
     if (build) {
@@ -223,7 +404,7 @@ int run(const dvq_pixelcnn_weights* w, const int64_t* label, const float* noise,
     } else {
         DVQ_REQUIRE(B >= 0, "pixelcnn: negative batch");
         if (B == 0) return DVQ_OK;
-        DVQ_REQUIRE(label && (forced || (noise && codes)), "pixelcnn: null input");
+        DVQ_REQUIRE(label && (forced || (codes && (noise || (ctl && ctl->given)))), "pixelcnn: null input");
         DVQ_REQUIRE(ws && dvq_aligned16(ws), "pixelcnn: null/unaligned workspace");
         pl = make_plan(w, B, ws);
         if (ws_bytes < pl.bytes) {
@@ -478,7 +659,23 @@ int run(const dvq_pixelcnn_weights* w, const int64_t* label, const float* noise,
                                                       [&](int level) { return pl.XH(level, pos); }, pl.g, pl.hid, pl.lg,
                                                       (pl.tab && r == 0) ? 2 : 0,
                                                       [&](int layer, int which) { return pl.SH(layer, c, which); }));
-                {
+                if (ctl) {
+                    DVQ_PROF("pixelcnn_draw", 0, (double)Bc * (2.0 * w->n_in + dim) * 4, st);
+                    const dim3 grid((unsigned)((Bc + 3) / 4)), block(256);
+                    const float* lgp = from_table ? pl.lgc : pl.lg;
+                    const float* qp = noise ? noise + b0 * NPOS * w->n_in : nullptr;
+                    const int64_t* gp = ctl->given ? ctl->given + b0 * NPOS : nullptr;
+                    float* lo = logits_out ? logits_out + b0 * NPOS * w->n_in : nullptr;
+                    float* pm = ctl->logp_model_out ? ctl->logp_model_out + b0 * NPOS : nullptr;
+                    float* pd = ctl->logp_draw_out ? ctl->logp_draw_out + b0 * NPOS : nullptr;
+                    const int64_t* lr = from_table ? pl.lab : nullptr;
+                    if (w->n_in <= 512)
+                        DVQ_LAUNCH(sample_ctl_kernel<true>, grid, block, 0, st, lgp, qp, pos, w->n_in, Bc, gp, codes + b0 * NPOS, w->tok_emb,
+                                   dim, pl.XV(0, pos), lo, err_flag, lr, ctl->temperature, ctl->top_k, pm, pd);
+                    else
+                        DVQ_LAUNCH(sample_ctl_kernel<false>, grid, block, 0, st, lgp, qp, pos, w->n_in, Bc, gp, codes + b0 * NPOS, w->tok_emb,
+                                   dim, pl.XV(0, pos), lo, err_flag, lr, ctl->temperature, ctl->top_k, pm, pd);
+                } else {
                 DVQ_PROF("pixelcnn_draw", 0, (double)Bc * (2.0 * w->n_in + dim) * 4, st);
                 DVQ_LAUNCH(sample_kernel, dim3((unsigned)((Bc + 3) / 4)), dim3(256), 0, st, from_table ? pl.lgc : pl.lg,
                                    noise ? noise + b0 * NPOS * w->n_in : nullptr, pos, w->n_in, Bc,
@@ -519,6 +716,16 @@ extern "C" int dvq_pixelcnn_sample(const dvq_pixelcnn_weights* w, const int64_t*
                                    int64_t* codes, float* logits_out, int32_t* err_flag, void* workspace,
                                    size_t workspace_bytes, dvq_stream_t stream) {
     return run(w, label, noise, nullptr, B, codes, logits_out, err_flag, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+extern "C" int dvq_pixelcnn_sample_ctl(const dvq_pixelcnn_weights* w, const int64_t* label, const float* noise, int64_t B,
+                                       const dvq_pixelcnn_ctl* ctl, int64_t* codes, float* logits_out, int32_t* err_flag,
+                                       void* workspace, size_t workspace_bytes, dvq_stream_t stream) {
+    DVQ_REQUIRE(ctl, "pixelcnn_sample_ctl: null controls");
+    DVQ_REQUIRE(ctl->temperature > 0.f && ctl->temperature <= 3.4028234664e38f, "pixelcnn_sample_ctl: temperature must be finite and > 0");
+    DVQ_REQUIRE(ctl->top_k >= 0, "pixelcnn_sample_ctl: top_k must be >= 0 (0: off)");
+    DVQ_REQUIRE(codes, "pixelcnn_sample_ctl: null codes");
+    return run(w, label, noise, nullptr, B, codes, logits_out, err_flag, workspace, workspace_bytes, (hipStream_t)stream, nullptr, ctl);
 }
 
 extern "C" int dvq_pixelcnn_forward(const dvq_pixelcnn_weights* w, const int64_t* x, const int64_t* label, int64_t B,

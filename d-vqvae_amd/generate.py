@@ -58,7 +58,28 @@ def build_parser(dataset: str) -> argparse.ArgumentParser:
     p.add_argument("--rows_per_call", type=int, default=16384,
                    help="grasps per batched call: whole objects of one point count are grouped up to this many rows "
                         "(0 = one call per object); the files written do not depend on it")
+    p.add_argument("--temperature", type=float, default=1.0,
+                   help="divides the prior's logits before each draw: below 1 likelier and less diverse grasps, above 1 the opposite")
+    p.add_argument("--top_k", type=int, default=0, help="draw every grid position from its top_k likeliest codes (0 = all)")
+    p.add_argument("--log_prob", type=int, default=0,
+                   help="1: every object's JSON gains \"log_prob\", each grasp's log-likelihood under the (untempered) prior")
     return p
+
+
+def _prior_controls(temperature: float, top_k: int, log_prob: bool) -> Dict[str, object]:
+    """Keyword arguments of GenNet.gen for the entry points' three flags: none at their defaults (today's call)."""
+    if float(temperature) == 1.0 and int(top_k) == 0 and not log_prob:
+        return {}
+    return dict(temperature=float(temperature), top_k=int(top_k), log_prob=bool(log_prob), return_aux=True)
+
+
+def grasp_log_prob(logp_model: torch.Tensor) -> torch.Tensor:
+    """[B,9] per-position log-probabilities -> [B] per grasp: fp32 additions in raster order, written out so that a grasp's
+    sum is the same bits in a call of any size (a library reduction may pick its order by the shape)."""
+    total = logp_model[:, 0].clone()
+    for i in range(1, logp_model.shape[1]):
+        total = total + logp_model[:, i]
+    return total
 
 
 def rotation_xyz(angles: np.ndarray) -> np.ndarray:
@@ -108,12 +129,15 @@ def load_model(args, device) -> GenNet:
 @torch.no_grad()
 def generate_for_object(net: GenNet, obj4n: torch.Tensor, num_grasp: int, rotate: bool, rng: np.random.Generator,
                         noise: Optional[torch.Tensor] = None, proxies: bool = False, seed: Optional[int] = None,
-                        object_index: Optional[int] = None, row0: int = 0) -> Dict[str, object]:
+                        object_index: Optional[int] = None, row0: int = 0, temperature: float = 1.0, top_k: int = 0,
+                        log_prob: bool = False) -> Dict[str, object]:
     """num_grasp grasps for one object in ONE batched call.  Returns the reference's JSON fields plus tensors.
     ``seed`` / ``object_index`` / ``row0`` key the prior's device noise (seed, stream = object, global grasp row), so the
     grasps of an object do not depend on which rank generates it or on how its grasps are split into calls.
     ``proxies``: also the per-grasp penetration / contact proxies (contact.grasp_proxies) of the posed hands against
-    the (rotated) object clouds -- the cheap on-device stand-in for the scripts' trimesh / pybullet metrics."""
+    the (rotated) object clouds -- the cheap on-device stand-in for the scripts' trimesh / pybullet metrics.
+    ``temperature`` / ``top_k``: controls on the prior's draws (GenNet.gen); ``log_prob``: also ``"log_prob"`` [G], each grasp's
+    log-likelihood under the untempered prior (grasp_log_prob of aux["logp_model"]), and in the JSON."""
     dev = next(net.parameters()).device
     G = num_grasp
     if rotate:
@@ -126,12 +150,16 @@ def generate_for_object(net: GenNet, obj4n: torch.Tensor, num_grasp: int, rotate
         t = np.zeros(3)
     batch = ops.transform_cloud(obj4n.to(dev).contiguous(), torch.as_tensor(R, dtype=torch.float32, device=dev),
                                 torch.as_tensor(t, dtype=torch.float32, device=dev))
-    recon, pos = net.gen(batch, noise=noise, seed=seed, row0=row0, stream_id=object_index)
+    recon, pos, *rest = net.gen(batch, noise=noise, seed=seed, row0=row0, stream_id=object_index,
+                                **_prior_controls(temperature, top_k, log_prob))
     params = ops.assemble61(recon, pos)                                            # obman.py:243-247
     final = net.rh_mano(betas=params[:, :10], global_orient=params[:, 10:13], hand_pose=params[:, 13:58],
                         transl=params[:, 58:61])                                   # obman.py:252-253
     Rt = np.concatenate([R, np.broadcast_to(t.reshape(1, 3, 1), (G, 3, 1))], axis=2)
-    extra = {}
+    extra, extra_json = {}, {}
+    if log_prob:
+        extra["log_prob"] = grasp_log_prob(rest[0]["logp_model"])
+        extra_json["log_prob"] = extra["log_prob"].cpu().numpy().tolist()
     if proxies:
         from . import contact
         faces = np.asarray(net.rh_mano.faces)
@@ -144,7 +172,7 @@ def generate_for_object(net: GenNet, obj4n: torch.Tensor, num_grasp: int, rotate
         extra["proxies"] = contact.grasp_proxies(topo, final.vertices, batch[:, :3].transpose(1, 2))
     return {**extra, "params": params, "vertices": final.vertices,
             "json": {"recon_params": [[p] for p in params.cpu().numpy().tolist()],   # [[61 floats]] per grasp, as the reference
-                     "R_list": Rt.tolist(), "trans_list": [t.reshape(3, 1).tolist()] * G, "r_list": angles.tolist()}}
+                     "R_list": Rt.tolist(), "trans_list": [t.reshape(3, 1).tolist()] * G, "r_list": angles.tolist(), **extra_json}}
 
 
 def _hand_topology(net: GenNet, n_verts: int, dev):
@@ -175,7 +203,8 @@ def plan_calls(point_counts: Sequence[int], num_grasp: int, rows_per_call: int) 
 
 @torch.no_grad()
 def _generate_call(net: GenNet, objs: Sequence[torch.Tensor], num_grasp: int, rotate: bool, seed: int,
-                   object_indices: Sequence[int], proxies: bool) -> List[Dict[str, object]]:
+                   object_indices: Sequence[int], proxies: bool, temperature: float = 1.0, top_k: int = 0,
+                   log_prob: bool = False) -> List[Dict[str, object]]:
     """One batched call: the ``num_grasp`` grasps of each of ``objs`` (all of one point count), row o * num_grasp + g = grasp g
     of object o.  Every step is row-independent and keyed per row, so each object's slice holds the bits of its own
     ``generate_for_object`` call."""
@@ -196,7 +225,8 @@ def _generate_call(net: GenNet, objs: Sequence[torch.Tensor], num_grasp: int, ro
     err = ops.new_err_flag(dev)                                                    # read after the parameters' copy below: no extra sync
     batch = ops.transform_clouds(clouds, obj_of_row, torch.as_tensor(np.concatenate(Rs), dtype=torch.float32, device=dev),
                                  torch.as_tensor(t, dtype=torch.float32, device=dev), err=err)
-    recon, pos = net.gen(batch, seed=seed, row_keys=(stream_ids, row_ids))
+    recon, pos, *rest = net.gen(batch, seed=seed, row_keys=(stream_ids, row_ids), **_prior_controls(temperature, top_k, log_prob))
+    logp = grasp_log_prob(rest[0]["logp_model"]) if log_prob else None
     params = ops.assemble61(recon, pos)                                            # obman.py:243-247
     final = net.rh_mano(betas=params[:, :10], global_orient=params[:, 10:13], hand_pose=params[:, 13:58],
                         transl=params[:, 58:61])                                   # obman.py:252-253
@@ -212,24 +242,30 @@ def _generate_call(net: GenNet, objs: Sequence[torch.Tensor], num_grasp: int, ro
     r_list = np.concatenate(angles).tolist()
     trans = t.reshape(3, 1).tolist()
     p_dev, v_dev = params.split(G), final.vertices.split(G)
+    lp_list = logp.cpu().numpy().tolist() if log_prob else None
     outs = []
     for o in range(O):
         lo, hi = o * G, (o + 1) * G
-        extra = {}
+        extra, extra_json = {}, {}
+        if log_prob:
+            extra["log_prob"] = logp[lo:hi]
+            extra_json["log_prob"] = lp_list[lo:hi]
         if proxies:                                                                # per object: the reductions see the loop's shapes
             from . import contact
             extra["proxies"] = contact.grasp_proxies(topo, final.vertices[lo:hi], batch[lo:hi, :3].transpose(1, 2))
         outs.append({**extra, "params": p_dev[o], "vertices": v_dev[o],
                      "json": {"recon_params": [[p] for p in p_list[lo:hi]],           # [[61 floats]] per grasp, as the reference
-                              "R_list": Rt_list[lo:hi], "trans_list": [trans] * G, "r_list": r_list[lo:hi]}})
+                              "R_list": Rt_list[lo:hi], "trans_list": [trans] * G, "r_list": r_list[lo:hi], **extra_json}})
     return outs
 
 
 def generate_for_objects(net: GenNet, objs: Sequence[torch.Tensor], num_grasp: int, rotate: bool, seed: int,
-                         object_indices: Sequence[int], proxies: bool = False, rows_per_call: int = 16384) -> List[Dict[str, object]]:
+                         object_indices: Sequence[int], proxies: bool = False, rows_per_call: int = 16384, temperature: float = 1.0,
+                         top_k: int = 0, log_prob: bool = False) -> List[Dict[str, object]]:
     """``num_grasp`` grasps for each of ``objs`` ([4,N] tensors) in batched calls that mix objects (plan_calls): one dict per
     object, in the order given, equal to ``generate_for_object(net, objs[i], num_grasp, rotate,
-    np.random.default_rng([seed, object_indices[i]]), seed=seed, object_index=object_indices[i], proxies=proxies)`` --
+    np.random.default_rng([seed, object_indices[i]]), seed=seed, object_index=object_indices[i], proxies=proxies)`` (and the same
+    ``temperature`` / ``top_k`` / ``log_prob``) --
     tensors bit for bit, ``json`` as Python objects.  Per call: the rotations of each object's own generator, one
     ``ops.transform_clouds``, one ``GenNet.gen(row_keys=)`` with stream = object index and row = grasp index, one ``assemble61``,
     one posed-MANO pass, one device-to-host copy.  A call's clouds and intermediates are freed before the next call; the results
@@ -238,7 +274,8 @@ def generate_for_objects(net: GenNet, objs: Sequence[torch.Tensor], num_grasp: i
         raise RuntimeError("generate_for_objects: one object index per object")
     out: List[Optional[Dict[str, object]]] = [None] * len(objs)
     for call in plan_calls([o.shape[1] for o in objs], num_grasp, rows_per_call):
-        res = _generate_call(net, [objs[p] for p in call], num_grasp, rotate, seed, [object_indices[p] for p in call], proxies)
+        res = _generate_call(net, [objs[p] for p in call], num_grasp, rotate, seed, [object_indices[p] for p in call], proxies,
+                             temperature, top_k, log_prob)
         for p, r in zip(call, res):
             out[p] = r
     return out
@@ -273,7 +310,8 @@ def main(dataset: str, argv: Optional[Sequence[str]] = None) -> List[str]:
             torch.cuda.synchronize(device)
             t0 = time.time()
             outs = generate_for_objects(net, [mine[p][1] for p in call], args.num_grasp, rotate, args.seed, [lo + p for p in call],
-                                        rows_per_call=args.rows_per_call)
+                                        rows_per_call=args.rows_per_call, temperature=args.temperature, top_k=args.top_k,
+                                        log_prob=bool(args.log_prob))
             torch.cuda.synchronize(device)
             dt = time.time() - t0
             total_t += dt
@@ -290,7 +328,8 @@ def main(dataset: str, argv: Optional[Sequence[str]] = None) -> List[str]:
             torch.cuda.synchronize(device)
             t0 = time.time()
             rng = np.random.default_rng([args.seed, gi])                            # per OBJECT: rotations independent of the sharding
-            out = generate_for_object(net, obj, args.num_grasp, rotate, rng, seed=args.seed, object_index=gi)
+            out = generate_for_object(net, obj, args.num_grasp, rotate, rng, seed=args.seed, object_index=gi,
+                                      temperature=args.temperature, top_k=args.top_k, log_prob=bool(args.log_prob))
             torch.cuda.synchronize(device)                                         # the reference times without a sync
             dt = time.time() - t0
             total_t += dt

@@ -15,6 +15,20 @@ from .pointnet_encoder import PointNetEncoder
 CODE_SLOTS = ((0, 1), (0, 2), (1, 1), (1, 2), (2, 1), (2, 2))     # grid position -> vqvae0..5 (gen_net.py:95-100)
 
 
+def code_grid(part_codes, device=None):
+    """Six hand-part codes per grasp [B,6] int64 (column k = vqvae{k}; from DVQVAE.forward's emb_idx [7B,1]:
+    ``emb_idx.view(7, B)[1:].t()``) -> the prior's [B,3,3] grid with the codes at CODE_SLOTS and -1 in the context column
+    (column 0, which gen() never decodes): as ``codes=`` of GenNet.gen the six parts are kept and the context is drawn; overwrite
+    entries with -1 to resample those parts."""
+    part_codes = torch.as_tensor(part_codes, dtype=torch.int64, device=device)
+    if part_codes.dim() != 2 or part_codes.shape[1] != len(CODE_SLOTS):
+        raise RuntimeError(f"code_grid: expected [B,{len(CODE_SLOTS)}] part codes, got {tuple(part_codes.shape)}")
+    grid = torch.full((part_codes.shape[0], 3, 3), -1, dtype=torch.int64, device=part_codes.device)
+    for k, (i, j) in enumerate(CODE_SLOTS):
+        grid[:, i, j] = part_codes[:, k]
+    return grid
+
+
 class GenNet(nn.Module):
     def __init__(self, n_embeddings=128, prior_tokens=512, prior_dim=512, prior_layers=15, prior_classes=128):
         """Defaults are the reference's fixed sizes (gen_net.py:17-34).  ``n_embeddings`` = 512 builds the
@@ -93,13 +107,15 @@ class GenNet(nn.Module):
             sid, rid = sid.index_select(0, sel), rid.index_select(0, sel)
         return ops.exp1_noise_keyed(sid, rid, 9 * n_in, seed, err=err).view(sid.shape[0], 9, n_in)
 
-    def _gen_impl(self, obj, noise, key=None, rows=None, row_keys=None):
+    def _gen_impl(self, obj, noise, key=None, rows=None, row_keys=None, ctl=None):
         """The device work of gen(): no host synchronisation inside (gen() checks the error flag once at the end).
         ``noise`` None: the prior's draws come from the device generator under ``key``, drawn directly in the order the prior
         is evaluated in (no gather of the [B, 9, tokens] tensor).  ``rows`` (int64 [B] on the device): ``obj`` holds rows
         ``rows`` of the keyed batch -- sample b draws the noise of row ``rows[b]`` (the per-row range fallback of gen()).
         ``row_keys`` (two int64 [B0] tensors on the device, ``key`` = the seed): per-row keys instead of one stream per call --
-        sample b draws the noise of (seed, stream_ids[b], row_ids[b]), or of entry ``rows[b]`` of the two arrays under ``rows``."""
+        sample b draws the noise of (seed, stream_ids[b], row_ids[b]), or of entry ``rows[b]`` of the two arrays under ``rows``.
+        ``ctl`` = (temperature, top_k, given [B,9] or None): the controlled draw (ops.pixelcnn_sample) with the log-probabilities in
+        ``aux``; ``given`` holds the rows of ``obj``.  None: the plain draw, the launches of every call before the controls."""
         if obj.dim() != 3:
             raise RuntimeError(f"gen: expected obj [B,4,N], got {tuple(obj.shape)}")
         B, dev = obj.shape[0], obj.device
@@ -113,6 +129,14 @@ class GenNet(nn.Module):
         label = idx6[:, 0].contiguous()                                    # per-sample label
         err = ops.new_err_flag(dev)
         pk = self.GatedPixelCNN.packed()
+        logp = None
+
+        def draw(lab, q, given):
+            if ctl is None:
+                return ops.pixelcnn_sample(pk, lab, q, err=err), None                      # :92
+            c, lm, ld = ops.pixelcnn_sample(pk, lab, q, err=err, temperature=ctl[0], top_k=ctl[1], given=given, return_logp=True)
+            return c, (lm, ld)
+        given = None if ctl is None else ctl[2]
         # The gated GEMMs add the class-conditional row cls[label[m]] in their epilogue: with rows in arrival order every lane of a
         # store instruction gathers from a different 4 KB row of the table; sorted by label a 128-row tile holds one or two labels
         # and the gather is a broadcast again (measured: -10 % on the gated GEMMs at 65 536 grasps with 123 distinct object codes).
@@ -125,27 +149,34 @@ class GenNet(nn.Module):
                 noise_s = self._draw_noise_keyed(row_keys, key, err, sel=order if rows is None else rows.index_select(0, order))
             else:
                 noise_s = self._draw_noise(B, dev, key, perm=order if rows is None else rows[order].contiguous())
-            codes_s = ops.pixelcnn_sample(pk, label[order].contiguous(), noise_s, err=err)   # :92
+            codes_s, logp_s = draw(label[order].contiguous(), noise_s, None if given is None else given.index_select(0, order))
             codes = torch.empty_like(codes_s)
             codes[order] = codes_s
+            if logp_s is not None:                                         # the log-probabilities travel with their rows
+                logp = tuple(torch.empty_like(t) for t in logp_s)
+                for dst, src in zip(logp, logp_s):
+                    dst[order] = src
         else:
             if noise is None:
                 noise = (self._draw_noise_keyed(row_keys, key, err, sel=rows) if row_keys is not None
                          else self._draw_noise(B, dev, key, perm=rows))
-            codes = ops.pixelcnn_sample(pk, label, noise.contiguous(), err=err)   # :92
+            codes, logp = draw(label, noise.contiguous(), given)
         # a position drawn from all-NaN logits carries -1 (bit 2 of err is set; gen() regenerates those rows): decode token 0 there
         recon = self._decode(codes.clamp_min(0), {"z_out": z_out}, None, err)   # :95-113
         verts = self._hand_vertices(recon)                                 # :116-118
         self.recon_encoder(verts, out=z_pos[:, :1024])                     # :120
         recon_pos = self.pos_decoder(z_pos).view(B, 6)                     # :122-123
         aux = dict(idx6=idx6, codes=codes, feat_type=feat_type, feat_pos=z_pos[:, 1024:], verts=verts, hand_feat=z_pos[:, :1024])
+        if logp is not None:
+            aux["logp_model"], aux["logp_draw"] = logp
         return recon, recon_pos, aux, err
 
     _RANGE_ERROR = ("GenNet.gen: code or label index out of range (prior classes vs codebook rows, "
                     "gen_net.py:20-34); build GenNet(n_embeddings=...) to match the prior")
 
     @torch.no_grad()
-    def gen(self, obj, noise=None, return_aux=False, seed=None, row0=None, stream_id=None, check=True, row_keys=None):
+    def gen(self, obj, noise=None, return_aux=False, seed=None, row0=None, stream_id=None, check=True, row_keys=None,
+            temperature=1.0, top_k=0, codes=None, log_prob=False):
         """obj [B,4,N] f32 on the GPU -> (recon [B,55], recon_pos [B,6]).
         ``noise`` [B,9,prior_tokens] ~ Exp(1) fixes the prior's draws (parity runs).  Without it the draws come from the
         device Philox generator keyed by (seed, stream_id, row0 + b): a batch sharded over ranks (``row0`` = first global
@@ -158,9 +189,24 @@ class GenNet(nn.Module):
         leaves the per-call stream counter alone.
         ``check=False``: no host synchronisation at all -- the call returns as soon as the work is enqueued (a loop of B = 1 calls
         then overlaps the host side of call i + 1 with the device side of call i); the caller gives up the index-range error
-        and the fp16-range fallback below, and gets ``aux["err"]`` (device int32: bit 0 range, bit 2 all-NaN logits) to check later."""
+        and the fp16-range fallback below, and gets ``aux["err"]`` (device int32: bit 0 range, bit 2 all-NaN logits) to check later.
+        Controls on the prior's draw: ``temperature`` > 0 divides the logits (below 1: likelier, less diverse
+        grasps), ``top_k`` > 0 draws from the top_k likeliest codes of each position, ``codes`` int64 [B,3,3] / [B,9] fixes the
+        grid positions whose entry is >= 0 and draws the rest (code_grid builds one from six part codes).  With any of them, or
+        ``log_prob=True``, ``aux`` gains ``logp_model`` and ``logp_draw`` [B,9]: each position's log-probability under the
+        untempered prior and under the distribution it was drawn from; a grasp's prior log-likelihood is ``logp_model.sum(1)``.
+        Keys, sharding, ``row_keys``, ``check=False`` and the range fallback work as without them; at the defaults the call runs
+        the launches it always ran."""
         if obj.dim() != 3:
             raise RuntimeError(f"gen: expected obj [B,4,N], got {tuple(obj.shape)}")
+        ctl = None
+        if float(temperature) != 1.0 or top_k != 0 or codes is not None or log_prob:
+            if codes is not None:
+                if (not torch.is_tensor(codes) or codes.dtype != torch.int64 or codes.device != obj.device
+                        or tuple(codes.shape) not in ((obj.shape[0], 9), (obj.shape[0], 3, 3))):
+                    raise RuntimeError("gen: codes must be an int64 [B,3,3] or [B,9] tensor on obj's device")
+                codes = codes.reshape(obj.shape[0], 9).contiguous()
+            ctl = (temperature, top_k, codes)
         if row_keys is not None:
             if noise is not None or row0 is not None or stream_id is not None:
                 raise RuntimeError("gen: row_keys names every row's noise key itself; it excludes noise / row0 / stream_id")
@@ -176,12 +222,15 @@ class GenNet(nn.Module):
         else:
             key = self._noise_key(seed, row0, stream_id) if noise is None else None
         with ops.no_range_check():                                         # ONE check for the whole path, below
-            recon, recon_pos, aux, err = self._gen_impl(obj, noise, key, row_keys=row_keys)
+            recon, recon_pos, aux, err = self._gen_impl(obj, noise, key, row_keys=row_keys, ctl=ctl)
         aux["err"] = err
         if not check:
             return (recon, recon_pos, aux) if return_aux else (recon, recon_pos)
         # one host synchronisation per call: the index-range flag and "every parameter is finite"
-        status = int((err + 2 * (~(torch.isfinite(recon).all() & torch.isfinite(recon_pos).all())).to(torch.int32)).item())
+        finite = torch.isfinite(recon).all() & torch.isfinite(recon_pos).all()
+        if ctl is not None:                # a given code is never -1: NaN logits at its position show in its log-probability alone
+            finite = finite & torch.isfinite(aux["logp_model"]).all()
+        status = int((err + 2 * (~finite).to(torch.int32)).item())
         if status & 1:
             raise RuntimeError(self._RANGE_ERROR + ("" if row_keys is None else
                                                     "; or a row key outside the noise generator's counter (stream id in [0, 2^32), row id >= 0)"))
@@ -192,16 +241,19 @@ class GenNet(nn.Module):
             # split, which has fp32's range (csrc/gemm_f16x2.hip), under the same noise keys, and scattered back; every other row keeps
             # its bits.  NaN / Inf INPUTS come out non-finite there too, as in the reference.
             bad = ~(torch.isfinite(recon).all(dim=1) & torch.isfinite(recon_pos).all(dim=1)) | (aux["codes"].reshape(obj.shape[0], -1) < 0).any(dim=1)
+            if ctl is not None:
+                bad = bad | ~torch.isfinite(aux["logp_model"]).all(dim=1)
             rows = bad.nonzero().reshape(-1)
             self.range_fallbacks += 1
             self.range_fallback_rows += int(rows.numel())
             with ops.no_range_check(), packing.gemm_kind_as(_lib.PLANES_BF16X3):
+                ctl2 = ctl if ctl is None or ctl[2] is None else (ctl[0], ctl[1], ctl[2].index_select(0, rows))
                 r2, p2, aux2, err2 = self._gen_impl(obj.index_select(0, rows), None if noise is None else noise.index_select(0, rows), key, rows=rows,
-                                                    row_keys=row_keys)
+                                                    row_keys=row_keys, ctl=ctl2)
                 if int(err2.item()) & 1:
                     raise RuntimeError(self._RANGE_ERROR)
             recon[rows], recon_pos[rows] = r2, p2
-            for k in ("idx6", "codes", "feat_type", "feat_pos", "verts", "hand_feat"):
+            for k in ("idx6", "codes", "feat_type", "feat_pos", "verts", "hand_feat") + (() if ctl is None else ("logp_model", "logp_draw")):
                 aux[k][rows] = aux2[k]
             aux["err"] = err2
             aux["fallback_rows"] = rows

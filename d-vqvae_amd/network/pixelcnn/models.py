@@ -46,13 +46,16 @@ class GatedPixelCNN(PackedModule):
         return ops.pixelcnn_forward(self.packed(), x, label)
 
     def generate(self, x_start, label, shape=(3, 3), batch_size=64, noise=None, return_logits=False, seed=None, row0=None,
-                 stream_id=None):
+                 stream_id=None, temperature=1.0, top_k=0, given=None, return_logp=False):
         """Raster-order sampling of the 3x3 grid -> int64 [B,3,3].  ``x_start`` is ignored (as in the
         reference, models.py:186).  ``noise`` [B,9,input_dim] ~ Exp(1) makes the draw reproducible
         (argmax softmax/noise == multinomial(1)); drawn by the device Philox generator keyed by (seed, stream_id,
         row0 + b) when omitted (ops.exp1_noise).  Like the reference's multinomial draws, calls that name nothing draw FRESH
         noise every time: seed = torch.initial_seed() (so torch.manual_seed governs it), one stream per call, rows of this
-        rank (ops.default_noise_key)."""
+        rank (ops.default_noise_key).
+        Controls on the draw (ops.pixelcnn_sample): ``temperature`` > 0 divides the logits, ``top_k`` > 0 keeps the top_k largest,
+        ``given`` int64 [B,3,3] / [B,9] fixes the positions whose entry is >= 0 and draws the others, ``return_logp`` appends
+        (logp_model, logp_draw) [B,9].  At their defaults the call is what it was."""
         if tuple(shape) != (3, 3):
             raise NotImplementedError("the grasp path samples a 3x3 latent grid (gen_net.py:92)")
         label = label.reshape(-1).contiguous()
@@ -66,4 +69,14 @@ class GatedPixelCNN(PackedModule):
                 self._noise_stream += 1
             noise = ops.exp1_noise(batch_size, 9 * pk.n_in, dseed if seed is None else seed, drow if row0 is None else row0,
                                    stream_id, device=label.device).view(batch_size, 9, pk.n_in)
-        return ops.pixelcnn_sample(pk, label, noise.contiguous(), return_logits=return_logits)
+        return ops.pixelcnn_sample(pk, label, noise.contiguous(), return_logits=return_logits, temperature=temperature, top_k=top_k,
+                                   given=given, return_logp=return_logp)
+
+    def log_prob(self, x, label):
+        """log p(x[b, position] | earlier positions, label[b]) under the prior, [B,9] fp32 in raster order, for code grids
+        x [B,3,3] / [B,9] int64: every position given to the controlled sampler, read as logp_model (no noise is drawn)."""
+        label = label.reshape(-1).contiguous()
+        x = x.reshape(label.shape[0], 9).contiguous()
+        if bool((x < 0).any()):
+            raise RuntimeError("log_prob: every position needs a code >= 0")
+        return ops.pixelcnn_sample(self.packed(), label, None, given=x, return_logp=True)[1]

@@ -6,6 +6,7 @@ torch caching allocator and enqueues the HIP work on torch's *current* stream.  
 """
 from __future__ import annotations
 
+import math
 import ctypes as C
 from typing import Dict, List, Optional, Sequence, Tuple
 
@@ -426,41 +427,73 @@ def pointnet_fault_counters(reset: bool = False) -> Tuple[int, int]:
 
 
 # ------------------------------------------------------------------------------------------ PixelCNN
-def pixelcnn_sample(packed, label: Tensor, noise: Tensor, return_logits: bool = False, err: Optional[Tensor] = None, _retry: bool = False):
-    """label [B] int64, noise [B,9,n_in] Exp(1) -> codes [B,3,3] int64 (+ logits [B,9,n_in]).
+def pixelcnn_sample(packed, label: Tensor, noise: Optional[Tensor], return_logits: bool = False, err: Optional[Tensor] = None,
+                    _retry: bool = False, temperature: float = 1.0, top_k: int = 0, given: Optional[Tensor] = None,
+                    return_logp: bool = False):
+    """label [B] int64, noise [B,9,n_in] Exp(1) -> codes [B,3,3] int64 (+ logits [B,9,n_in]) (+ logp_model, logp_draw [B,9]).
     With a caller-supplied ``err`` flag nothing synchronises here: a draw from all-NaN logits (fp16 range, bit 2 of the flag) leaves
-    -1 at its position of ``codes`` and the caller deals with those rows (GenNet.gen regenerates them on the bf16x3 images)."""
-    lib = _lib.load()
-    dev = _require_gpu(label, noise, err)
-    _i64(label, "label"), _f32(noise, "noise")
-    packed.to(dev)
+    -1 at its position of ``codes`` and the caller deals with those rows (GenNet.gen regenerates them on the bf16x3 images).
+    Controls on the draw (include/dvq.h: dvq_pixelcnn_sample_ctl): ``temperature`` T > 0 divides the logits, ``top_k`` > 0 keeps
+    the top_k largest (ties towards the lowest index), ``given`` int64 [B,9] / [B,3,3] fixes the positions whose entry is >= 0
+    and draws the negative ones (``noise`` may be None when nothing is drawn), ``return_logp`` appends the log-probability of
+    every position's code under the untempered prior (logp_model) and under the distribution drawn from (logp_draw).  With all
+    four at their defaults this is the call to dvq_pixelcnn_sample it always was."""
+    _i64(label, "label")
+    if isinstance(temperature, bool) or not isinstance(temperature, (int, float)) or not math.isfinite(temperature) or not temperature > 0:
+        raise RuntimeError(f"pixelcnn_sample: temperature must be a finite number > 0, got {temperature!r}")
+    if isinstance(top_k, bool) or not isinstance(top_k, int) or top_k < 0:
+        raise RuntimeError(f"pixelcnn_sample: top_k must be an integer >= 0 (0: off), got {top_k!r}")
     B = label.shape[0]
     if label.dim() != 1 or not label.is_contiguous():
         raise RuntimeError("pixelcnn_sample: label must be a contiguous [B] tensor")
-    if tuple(noise.shape) != (B, 9, packed.n_in) or not noise.is_contiguous():
+    if given is not None:
+        if (not torch.is_tensor(given) or given.dtype != torch.int64 or tuple(given.shape) not in ((B, 9), (B, 3, 3))
+                or not given.is_contiguous() or given.device != label.device):
+            raise RuntimeError("pixelcnn_sample: given must be a contiguous int64 [B,9] or [B,3,3] tensor on label's device")
+    controlled = float(temperature) != 1.0 or top_k != 0 or given is not None or return_logp
+    if noise is None:
+        if given is None:
+            raise RuntimeError("pixelcnn_sample: noise may be omitted only when given codes are passed")
+    else:
+        _f32(noise, "noise")
+    lib = _lib.load()
+    dev = _require_gpu(label, noise, given, err)
+    if noise is not None and (tuple(noise.shape) != (B, 9, packed.n_in) or not noise.is_contiguous()):
         raise RuntimeError(f"pixelcnn_sample: noise must be contiguous [B,9,{packed.n_in}], got {tuple(noise.shape)}")
+    packed.to(dev)
     codes = torch.empty(B, 3, 3, dtype=torch.int64, device=dev)
     logits = torch.empty(B, 9, packed.n_in, dtype=torch.float32, device=dev) if return_logits else None
+    logp = torch.empty(2, B, 9, dtype=torch.float32, device=dev) if return_logp else None
     own_err = err is None
     if own_err:
         err = new_err_flag(dev)
     nws = lib.dvq_pixelcnn_workspace_bytes(C.byref(packed.cstruct), B)
     ws = workspace(nws, dev)
     with torch.cuda.device(dev):
-        check(lib.dvq_pixelcnn_sample(C.byref(packed.cstruct), label.data_ptr(), noise.data_ptr(), B, codes.data_ptr(),
-                                      logits.data_ptr() if return_logits else None, err.data_ptr(), ws.data_ptr(),
-                                      ws.numel(), _stream(dev)), "dvq_pixelcnn_sample")
+        if not controlled:
+            check(lib.dvq_pixelcnn_sample(C.byref(packed.cstruct), label.data_ptr(), noise.data_ptr(), B, codes.data_ptr(),
+                                          logits.data_ptr() if return_logits else None, err.data_ptr(), ws.data_ptr(),
+                                          ws.numel(), _stream(dev)), "dvq_pixelcnn_sample")
+        else:
+            ctl = _lib.PixelcnnCtl(float(temperature), int(min(top_k, 2 ** 31 - 1)), given.data_ptr() if given is not None else None,
+                                   logp[0].data_ptr() if return_logp else None, logp[1].data_ptr() if return_logp else None)
+            check(lib.dvq_pixelcnn_sample_ctl(C.byref(packed.cstruct), label.data_ptr(), noise.data_ptr() if noise is not None else None,
+                                              B, C.byref(ctl), codes.data_ptr(), logits.data_ptr() if return_logits else None,
+                                              err.data_ptr(), ws.data_ptr(), ws.numel(), _stream(dev)), "dvq_pixelcnn_sample_ctl")
     if own_err:
         e = int(err.item())
         if e & 1:
-            raise RuntimeError(f"label out of range for the prior's {packed.n_classes} classes")
+            raise RuntimeError(f"label or given code out of range for the prior's {packed.n_classes} classes / {packed.n_in} tokens"
+                               if controlled else f"label out of range for the prior's {packed.n_classes} classes")
         if (e & 4) and packed.kind == _lib.PLANES_F16X2 and not _retry:
             # non-finite logits under the fp16 weight images: an activation left fp16's range (or the input is not finite): once
             # more on the six-product bf16 split, which has fp32's range; the images return to the default kind at the next use
             from . import packing
             with packing.gemm_kind_as(_lib.PLANES_BF16X3):
-                return pixelcnn_sample(packed, label, noise, return_logits=return_logits, _retry=True)
-    return (codes, logits) if return_logits else codes
+                return pixelcnn_sample(packed, label, noise, return_logits=return_logits, _retry=True, temperature=temperature,
+                                       top_k=top_k, given=given, return_logp=return_logp)
+    out = (codes,) + ((logits,) if return_logits else ()) + ((logp[0], logp[1]) if return_logp else ())
+    return out if len(out) > 1 else codes
 
 
 def pixelcnn_forward(packed, x: Tensor, label: Tensor) -> Tensor:

@@ -40,6 +40,8 @@ typedef enum {
 /* The version of this header.  dvq_abi_version() returns the library's: a binding checks the two for equality at load time
  * (struct layouts change between versions). */
 #define DVQ_ABI_VERSION 10
+/* Entry points added since 10 without touching a struct or a signature of it (a compatible extension: bindings of 10 keep
+ * working, the version stays): dvq_pixelcnn_sample_ctl. */
 int dvq_abi_version(void);
 const char* dvq_last_error(void);
 /* number of visible HIP devices, or -1; does not create a context */
@@ -239,6 +241,27 @@ size_t dvq_pixelcnn_workspace_bytes(const dvq_pixelcnn_weights* w_host, int64_t 
 int dvq_pixelcnn_sample(const dvq_pixelcnn_weights* w_host, const int64_t* label, const float* noise,
                         int64_t B, int64_t* codes, float* logits_out, int32_t* err_flag,
                         void* workspace, size_t workspace_bytes, dvq_stream_t stream);
+/* The same sampler with controls on the draw (models.py:186-196 draws from softmax(logits) as it is).  Per grid position, l = the
+ * fp32 logits, q = the row's noise, s = l / temperature (fp32 division; 1: s = l bit for bit):
+ *   top_k in (0, n_in): the kept set S = the top_k largest s, ties towards the lowest index (|S| = top_k); 0 or >= n_in: all.
+ *   code = argmax_{k in S} p_k / q_k, lowest k on ties, p = softmax of s over S (max-subtracted, excluded terms add +0.0f).
+ *   given [B,9] int64 (optional): an entry >= 0 IS that position's code (range-checked: bit 0 of the flag), a negative one is
+ *     drawn; positions mix freely in a row.  The network is exactly causal: a given code changes no earlier position's draw.
+ *   logp_model_out [B,9] (optional) = l[c] - logsumexp_k l[k]: the untempered prior's log-likelihood of the code c, drawn or given.
+ *   logp_draw_out  [B,9] (optional) = s[c] - logsumexp_{k in S} s[k]: -inf for a given code outside S, 0 when top_k = 1.
+ * A row whose logits hold a NaN at a drawn position: code -1, bit 2, as dvq_pixelcnn_sample; both log-probabilities NaN there.
+ * With temperature 1, top_k 0 and no given codes the codes and logits_out are dvq_pixelcnn_sample's, bit for bit.
+ * noise may be null when given is not: a negative entry then counts as a token out of range (bit 0). */
+typedef struct {
+    float temperature;        /* finite, > 0 */
+    int32_t top_k;            /* >= 0 */
+    const int64_t* given;     /* optional [B,9], raster order */
+    float* logp_model_out;    /* optional [B,9] */
+    float* logp_draw_out;     /* optional [B,9] */
+} dvq_pixelcnn_ctl;
+int dvq_pixelcnn_sample_ctl(const dvq_pixelcnn_weights* w_host, const int64_t* label, const float* noise,
+                            int64_t B, const dvq_pixelcnn_ctl* ctl, int64_t* codes, float* logits_out, int32_t* err_flag,
+                            void* workspace, size_t workspace_bytes, dvq_stream_t stream);
 /* GatedPixelCNN.forward (models.py:161-174) for given tokens x [B,9] (raster order): logits [B,9,n_in]
  * (position-major; the host mirror permutes to the reference's [B,n_in,3,3]) */
 int dvq_pixelcnn_forward(const dvq_pixelcnn_weights* w_host, const int64_t* x, const int64_t* label,
