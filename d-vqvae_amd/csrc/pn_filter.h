@@ -70,9 +70,13 @@ enum PnAbl : int {
     PN_ABL_CONSUMER = 131072,       // trunk (both): no conv1 / conv2, rows from thin air
     PN_ABL_SPLIT = 262144,          // front (C = 4): producer and consumer halves of the trunk as two launches on two streams
     PN_ABL_ONE_PER_CU = 524288,     // front: 100 KB of LDS asked for, ONE workgroup per CU
+    PN_ABL_NO_RULE1 = 1048576,      // exact: flagged groups are not gated on what their hidden points can reach (the counts without rule 1)
+    PN_ABL_NO_RULE2 = 2097152,      // exact: the anchor's exact score does not raise the lower bound (the counts without rule 2)
     // bits that leave the features valid: the exact stage's consistency check runs only under these
-    PN_ABL_VALID = PN_ABL_STAMPS | PN_ABL_CLOCK | PN_ABL_INJECT_LIE | PN_ABL_INJECT_LOST | PN_ABL_ONE_PER_CU
+    PN_ABL_VALID = PN_ABL_STAMPS | PN_ABL_CLOCK | PN_ABL_INJECT_LIE | PN_ABL_INJECT_LOST | PN_ABL_ONE_PER_CU | PN_ABL_NO_RULE1 | PN_ABL_NO_RULE2
 };
+
+constexpr size_t PN_STATS_BYTES = 128;                     // the exact stage's statistics (DVQ_PN_STATS): sixteen 64-bit counters
 
 // One scratch set (pointnet.hip's plan() places it by pn_set_layout)
 struct PnSlot { float *h2, *part, *cbuf; void* part2; unsigned* tstat; };

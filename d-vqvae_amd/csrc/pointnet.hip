@@ -100,7 +100,7 @@ PnScratch plan(int64_t B, int N, void* ws) {
     // That trunk runs on one stream and one scratch set, so with two sets it borrows the second set's conv2 rows (twice its size);
     // with one set (a single launch) it gets rows of its own.
     s.h1 = s.slots >= 2 ? s.slot[1].h2 : take((size_t)chunk * s.g.Npad * 64 * 4);
-    s.stats = (unsigned long long*)take(64);
+    s.stats = (unsigned long long*)take(PN_STATS_BYTES);
     s.f0 = take((size_t)chunk * 1024 * 4);
     s.f1 = take((size_t)chunk * 512 * 4);
     s.f2 = take((size_t)chunk * 256 * 4);

@@ -787,16 +787,18 @@ __device__ __forceinline__ float key2f(unsigned k) { return __uint_as_float((k &
 __device__ unsigned long long g_pn_faults[2];
 
 // One workgroup per sample, 16 groups of 16 lanes.
-//   phase A (one thread per channel): best lower bound over the tiles; every kept score whose upper bound reaches it
-//           becomes a candidate point of the channel (table of 4 per channel, the rest in a list); flagged 16-point groups of tiles
-//           in contention become (channel, tile, group) entries;
-//   phase B (one group per channel): the weight row once, its candidates' rows together, exact_dot, maximum;
+//   phase A1 (one thread per channel): best lower bound lb over the tiles and the ANCHOR of the channel, the top kept point of the
+//           tile that sets lb (always in range); the anchors in point order, exact_dot of each: x1, an exact score of the channel;
+//   phase A2 (one thread per channel): every other kept score whose upper bound reaches L = max(lb, x1 - w.c) becomes a
+//           (channel, point) pair; flagged 16-point groups of tiles in contention whose hidden points can still reach L become
+//           (channel, tile, group) entries (rules 1 and 2);
+//   phase B (one group per pair, point order): exact_dot, maximum;
 //   phase C (one wave per entry, no barrier): the 16 points of a flagged group; then, whole workgroup per channel, every
 //           point for the channels on the "everything" list (DVQ_PN_EXHAUSTIVE / non-finite inputs).
-// stats (optional): channels with one candidate, with another count, wave entries, candidates.
-constexpr int PAIR_CAP = 1024;
+// stats (optional): channels with one candidate, with another count, wave entries, candidates; phase cycles; distinct rows, clouds.
+constexpr int PAIR_CAP = 2048;                            // (channel, point) pairs beyond the anchors; more: their 16-point groups instead
 constexpr int FB_CAP = 512;
-constexpr int SORT_CAP = 3072;                            // (channel, point) pairs evaluated in point order; more: channel order
+constexpr unsigned short NO_ANCHOR = 0xFFFFu;              // a channel on the "everything" list
 __global__ __launch_bounds__(256, 4) void pn_exact_kernel(const f32x4* __restrict__ part, const qf32x2* __restrict__ part2, int tiles, int deal,
                                                        const float* __restrict__ h2buf,
                                                        int N, int Npad, const float* __restrict__ w3, const float* __restrict__ b3,
@@ -805,8 +807,7 @@ __global__ __launch_bounds__(256, 4) void pn_exact_kernel(const f32x4* __restric
                                                        int pair_cap, int fb_cap, float* __restrict__ feat, long ld_feat,
                                                        unsigned long long* __restrict__ stats, int abl_arg) {
     const int abl = DVQ_DIAG_ON ? abl_arg : 0;
-    __shared__ unsigned short cand[1024][4];
-    __shared__ unsigned char cand_n[1024];
+    __shared__ unsigned short anchor[1024];                // the channel's anchor point
     __shared__ int pair_list[PAIR_CAP];
     __shared__ int fb_list[FB_CAP];
     __shared__ short all_list[1024];
@@ -814,14 +815,17 @@ __global__ __launch_bounds__(256, 4) void pn_exact_kernel(const f32x4* __restric
     __shared__ float fb_part[4][16];
     __shared__ float hm[PN_MAX_TILES], dm[PN_MAX_TILES], rd[PN_MAX_TILES];
     __shared__ unsigned best_k[1024];
+    __shared__ float wcs[1024];                            // w_n . c per channel (rule 2, consistency check)
     __shared__ int pcnt[1024];                             // pairs per point -> first slot of the point -> fill cursor
-    __shared__ unsigned sorted[SORT_CAP];                  // channel | point << 10, grouped by point
+    __shared__ unsigned sorted[PAIR_CAP];                  // channel | point << 10, grouped by point: the anchors, then the pairs
     __shared__ int wave_tot[4];
+    __shared__ unsigned row_mask[32];                      // statistics: points that were somebody's anchor
+    static_assert(PAIR_CAP >= 1024, "sorted[] holds the 1 024 anchors");
     const int tid = threadIdx.x, g = tid >> 4, j = tid & 15;
     const long b = blockIdx.x;
-    float* wcs = reinterpret_cast<float*>(pcnt);           // w_n . c per channel (consistency check): pcnt is dead once the pairs are sorted
     const f32x4 cen_a = *reinterpret_cast<const f32x4*>(cbuf + b * 128 + 4 * j), cen_b = *reinterpret_cast<const f32x4*>(cbuf + b * 128 + 4 * j + 64);
     if (tid == 0) { pair_count = 0; fb_count = 0; all_count = 0; }
+    if (tid < 32) row_mask[tid] = 0;
 #pragma unroll
     for (int i = 0; i < 4; ++i) pcnt[tid + 256 * i] = 0;
     int nonfinite_point = 0;
@@ -841,11 +845,169 @@ __global__ __launch_bounds__(256, 4) void pn_exact_kernel(const f32x4* __restric
     const float* h2 = h2buf + b * (long)Npad * 128;
     const bool wrap_small = Npad <= 2 * N;                  // a padding slot's index is below 2 N: one subtraction instead of a division
     const f32x4* pt = part + b * (long)tiles * 1024;
-    const qf32x2* pt2 = part2 + b * (long)tiles * 1024;     // the fourth and fifth id-carrying scores: read only where the third is in range
-    // ---- phase A
+    const qf32x2* pt2 = part2 + b * (long)tiles * 1024;     // the fourth and fifth id-carrying scores
     const bool stamps = DVQ_DIAG_ON && stats && (abl & PN_ABL_STAMPS);   // diagnostics: cycles per phase (tid 0's clock), summed into stats[4..7]
-    unsigned long long tp0 = stamps ? __builtin_amdgcn_s_memtime() : 0ull, tp1 = 0, tp2 = 0, tp3 = 0;
-    unsigned n_single = 0, n_multi = 0, n_cand = 0, n_wave = 0, n_suspect = 0;
+    unsigned long long tp[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (stamps) tp[0] = __builtin_amdgcn_s_memtime();
+    unsigned n_single = 0, n_multi = 0, n_cand = 0, n_wave = 0, n_suspect = 0, n_rows = 0;
+    // E_t of channel (wn, rn)
+    auto bound_of = [&](float wn, float rn, int t) { return fmaf(rn, dm[t], fmaf(wn, rd[t], fmaf(C_ID * wn, dm[t], 2.0f * DELTA * wn * hm[t]))); };
+    // The interval the records promise for (max - w.c) of channel n: lb = max_t (c1_t - E_t), ub = max_t (c1_t + E_t); the first tile
+    // that attains lb and its top score (the anchor); the largest bound.  top0 .. top3: c1 of the first four tiles (N <= 1024: all of
+    // them), requested by the caller ahead of time; the tiles beyond are read here, in blocks of four.  A non-finite bound or top score
+    // in ANY tile sends the channel to the "everything" path (fmaxf drops a NaN: tested apart).  Phases A1 and A2 both call this: the
+    // same instructions on the same inputs, the same lb and anchor.
+    struct Scan { float lb, ub, e_all, top_star; int t_star; bool all; };
+    auto scan_tiles = [&](int n, float wn, float rn, float top0, float top1, float top2, float top3) {
+        Scan s;
+        bool nonfinite = false;
+        auto fold = [&](int t, float top) {
+            const float e = bound_of(wn, rn, t), l = top - e;
+            nonfinite = nonfinite || !(e < 3.0e38f) || !(fabsf(top) < 3.0e38f);
+            s.e_all = fmaxf(s.e_all, e);
+            if (l > s.lb) { s.t_star = t; s.top_star = top; }
+            s.lb = fmaxf(s.lb, l);
+            s.ub = fmaxf(s.ub, top + e);
+        };
+        {
+            const float e0 = bound_of(wn, rn, 0);
+            s.e_all = e0;
+            s.lb = top0 - e0;
+            s.ub = top0 + e0;
+            s.t_star = 0;
+            s.top_star = top0;
+            nonfinite = !(e0 < 3.0e38f) || !(fabsf(top0) < 3.0e38f);
+            if (tiles > 1) fold(1, top1);
+            if (tiles > 2) fold(2, top2);
+            if (tiles > 3) fold(3, top3);
+        }
+        for (int t0 = 4; t0 < tiles; t0 += 4) {
+            float top[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) top[u] = pt[min(t0 + u, tiles - 1) * 1024 + n][0];
+#pragma unroll
+            for (int u = 0; u < 4; ++u)
+                if (t0 + u < tiles) fold(t0 + u, top[u]);
+        }
+        s.all = exhaustive || nonfinite || !(s.e_all < 3.0e38f) || !(s.lb > NEG_BIG) || !(s.lb < 3.0e38f);   // non-finite inputs: evaluate everything
+        return s;
+    };
+    // the point of a kept score of tile t
+    auto point_of_score = [&](int t, float v) {
+        int p = point_of_slot(t, slot_of_id(__float_as_uint(v) & 255u), deal);
+        if (p >= N) p = wrap_small ? p - N : p % N;      // a padding slot: the real point it repeats
+        if (abl & PN_ABL_FEW_ROWS) p &= 63;
+        return p;
+    };
+    // Counting sort in the LDS of count codes (channel | point << 10; ~0u: none) by point into sorted[]; pcnt is zero on entry.  A
+    // cloud's 1 024 channels take their maxima at ~100-200 distinct points: evaluated channel by channel every pair fetched its
+    // 512-byte row from HBM again (the kernel ran at the HBM roofline); grouped by point a row is fetched once and found in the
+    // L1 by the pairs that follow.  Returns the number of codes.
+    auto sort_by_point = [&](auto code_at, int count, bool first) {
+        for (int i = tid; i < count; i += 256) {
+            const unsigned code = code_at(i);
+            if (code != ~0u) atomicAdd(&pcnt[(code >> 10) & 1023], 1);       // N > 1024: points 1024 apart share a slot range
+        }
+        dvq_lds_barrier();
+        const int c0 = pcnt[4 * tid], c1 = pcnt[4 * tid + 1], c2 = pcnt[4 * tid + 2], c3 = pcnt[4 * tid + 3];
+        if (stats) {                                        // distinct rows: points with an anchor, then points with pairs only
+            const unsigned m = (unsigned)(c0 != 0) | (unsigned)(c1 != 0) << 1 | (unsigned)(c2 != 0) << 2 | (unsigned)(c3 != 0) << 3;
+            const int sh = 4 * (tid & 7);
+            if (first) { if (m) atomicOr(&row_mask[tid >> 3], m << sh); n_rows += __popc(m); }
+            else n_rows += __popc(m & ~(row_mask[tid >> 3] >> sh));
+        }
+        int incl = c0 + c1 + c2 + c3;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const int v = __shfl_up(incl, o);
+            if ((tid & 63) >= o) incl += v;
+        }
+        if ((tid & 63) == 63) wave_tot[tid >> 6] = incl;
+        dvq_lds_barrier();
+        int base = 0;
+        for (int w = 0; w < (tid >> 6); ++w) base += wave_tot[w];
+        const int total = wave_tot[0] + wave_tot[1] + wave_tot[2] + wave_tot[3];
+        const int excl = base + incl - (c0 + c1 + c2 + c3);
+        pcnt[4 * tid] = excl;
+        pcnt[4 * tid + 1] = excl + c0;
+        pcnt[4 * tid + 2] = excl + c0 + c1;
+        pcnt[4 * tid + 3] = excl + c0 + c1 + c2;
+        dvq_lds_barrier();
+        for (int i = tid; i < count; i += 256) {
+            const unsigned code = code_at(i);
+            if (code != ~0u) sorted[atomicAdd(&pcnt[(code >> 10) & 1023], 1)] = code;
+        }
+        dvq_lds_barrier();
+        return total;
+    };
+    // The first ``total`` entries of sorted[]: every 16-lane group takes a contiguous share of the list, four pairs in flight.
+    // first: the anchors -- one per channel: plain stores, and the centre term of the channel with them.
+    auto dots = [&](int total, bool first) {
+        const int per = (total + 15) >> 4, i0 = g * per, i1 = min(total, i0 + per);
+        for (int i = i0; i < i1; i += 4) {
+            f32x4 w0[4], w1[4], ha[4], hb[4];
+            int nn[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const unsigned code = sorted[min(i + u, i1 - 1)];
+                nn[u] = (int)(code & 1023u);
+                // (uniform base + 32-bit offset: the loads take the base from scalar registers, no 64-bit vector add per row)
+                const unsigned woff = (code & 1023u) * 512u + 16u * (unsigned)j, hoff = (code >> 10) * 512u + 16u * (unsigned)j;
+                w0[u] = *reinterpret_cast<const f32x4*>(reinterpret_cast<const char*>(w3) + woff);
+                w1[u] = *reinterpret_cast<const f32x4*>(reinterpret_cast<const char*>(w3) + woff + 256);
+                ha[u] = *reinterpret_cast<const f32x4*>(reinterpret_cast<const char*>(h2) + hoff);
+                hb[u] = *reinterpret_cast<const f32x4*>(reinterpret_cast<const char*>(h2) + hoff + 256);
+            }
+            float v[4], wc[4];                              // all the chains first (independent: they interleave), the LDS updates after
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                v[u] = exact_dot_regs(w0[u], w1[u], ha[u], hb[u]);
+                wc[u] = first ? exact_dot_regs(w0[u], w1[u], cen_a, cen_b) : 0.f;
+            }
+            if (j == 0) {
+#pragma unroll
+                for (int u = 0; u < 4; ++u)
+                    if (i + u < i1) {
+                        if (first) { best_k[nn[u]] = f2key(v[u]); wcs[nn[u]] = wc[u]; }
+                        else atomicMax(&best_k[nn[u]], f2key(v[u]));
+                    }
+            }
+        }
+    };
+    // ---- phase A1: lower bound and anchor of every channel
+    {
+        float top[4][4], wn[4], rn[4];
+#pragma unroll
+        for (int ci = 0; ci < 4; ++ci) {
+            const int n = tid + 256 * ci;
+#pragma unroll
+            for (int u = 0; u < 4; ++u) top[ci][u] = pt[min(u, tiles - 1) * 1024 + n][0];
+            wn[ci] = wnorm[n]; rn[ci] = rnorm[n];
+        }
+#pragma unroll
+        for (int ci = 0; ci < 4; ++ci) {
+            const int n = tid + 256 * ci;
+            const Scan s = scan_tiles(n, wn[ci], rn[ci], top[ci][0], top[ci][1], top[ci][2], top[ci][3]);
+            best_k[n] = f2key(NEG_BIG);
+            wcs[n] = 0.f;
+            if (s.all) {
+                all_list[atomicAdd(&all_count, 1)] = (short)n;
+                anchor[n] = NO_ANCHOR;
+            } else
+                anchor[n] = (unsigned short)point_of_score(s.t_star, s.top_star);
+        }
+    }
+    dvq_lds_barrier();
+    if (stamps) tp[1] = __builtin_amdgcn_s_memtime();
+    auto anchor_code = [&](int n) { const unsigned p = anchor[n]; return p == NO_ANCHOR ? ~0u : (unsigned)n | (p << 10); };
+    const int n_anchor = sort_by_point(anchor_code, 1024, true);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) pcnt[tid + 256 * i] = 0;   // (the next sort's histogram: after the barrier that ends this one)
+    if (stamps) tp[2] = __builtin_amdgcn_s_memtime();
+    if (!(abl & PN_ABL_NO_DOTS)) dots(n_anchor, true);
+    dvq_lds_barrier();
+    if (stamps) tp[3] = __builtin_amdgcn_s_memtime();
+    // ---- phase A2
     // the interval the records promise for (max - w.c) of channels tid + 256 i; lo > hi: not checked.  Eight scalars updated through
     // selects: the channel loop below stays ROLLED (unrolled it was 12 k instructions, 80 KB of code for a 64 KB instruction cache
     // shared by two CUs) without turning an indexed array into scratch memory.
@@ -860,7 +1022,6 @@ __global__ __launch_bounds__(256, 4) void pn_exact_kernel(const f32x4* __restric
 #pragma unroll 1
     for (int ci = 0; ci < 4; ++ci) {
         const int n = tid + 256 * ci;
-        best_k[n] = f2key(NEG_BIG);
         const float wn = nwn, rn = nrn;
         const f32x4 f0 = nf0, f1 = nf1, f2 = nf2, f3 = nf3;
         const qf32x2 g0 = ng0, g1 = ng1, g2 = ng2, g3 = ng3;
@@ -870,81 +1031,64 @@ __global__ __launch_bounds__(256, 4) void pn_exact_kernel(const f32x4* __restric
             ng0 = pt2[nx]; ng1 = pt2[min(1, tiles - 1) * 1024 + nx]; ng2 = pt2[min(2, tiles - 1) * 1024 + nx]; ng3 = pt2[min(3, tiles - 1) * 1024 + nx];
             nwn = wnorm[nx]; nrn = rnorm[nx];
         }
-        float lb, e_all;
-        auto bound = [&](int t) { return fmaf(rn, dm[t], fmaf(wn, rd[t], fmaf(C_ID * wn, dm[t], 2.0f * DELTA * wn * hm[t]))); };
-        // (tiles beyond the first four: in blocks of four, below)
-        // a non-finite bound or top score in ANY tile sends the channel to the "everything" path (fmaxf drops a NaN: tested apart)
-        bool nonfinite = false;
-        float ub;
-        auto fold = [&](float e, float top) {
-            nonfinite = nonfinite || !(e < 3.0e38f) || !(fabsf(top) < 3.0e38f);
-            e_all = fmaxf(e_all, e);
-            lb = fmaxf(lb, top - e);
-            ub = fmaxf(ub, top + e);
-        };
-        {
-            const float e0 = bound(0);
-            e_all = e0;
-            lb = f0[0] - e0;
-            ub = f0[0] + e0;
-            nonfinite = !(e0 < 3.0e38f) || !(fabsf(f0[0]) < 3.0e38f);
-            if (tiles > 1) fold(bound(1), f1[0]);
-            if (tiles > 2) fold(bound(2), f2[0]);
-            if (tiles > 3) fold(bound(3), f3[0]);
+        const Scan s = scan_tiles(n, wn, rn, f0[0], f1[0], f2[0], f3[0]);
+        if (s.all) continue;                               // on the "everything" list since phase A1
+        const float lb = s.lb;
+        // Rule 2: x1 = exact_dot(w_n, h2[anchor]) - w_n . c is the score of a point of the set the feature is the maximum over, so
+        // nothing whose upper bound is below it can change that maximum.  The slack (the form of the consistency check's) keeps the
+        // fp32 subtraction's own rounding from lifting L above x1's real value; a NaN (Inf - Inf) leaves lb: fmaxf drops it.
+        float L = lb;
+        if (!(abl & PN_ABL_NO_RULE2)) {
+            const float v1 = key2f(best_k[n]), wc1 = wcs[n];
+            L = fmaxf(lb, (v1 - wc1) - 4.0e-7f * (fabsf(v1) + fabsf(wc1)));
         }
-        for (int t0 = 4; t0 < tiles; t0 += 4) {
-            float top[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) top[u] = pt[min(t0 + u, tiles - 1) * 1024 + n][0];
-#pragma unroll
-            for (int u = 0; u < 4; ++u)
-                if (t0 + u < tiles) fold(bound(t0 + u), top[u]);
-        }
-        int cands = 0;
+        int cands = 1;                                     // the anchor
         bool whole = false;
-        const bool all = exhaustive || nonfinite || !(e_all < 3.0e38f) || !(lb > NEG_BIG) || !(lb < 3.0e38f);   // non-finite inputs: evaluate everything
-        if (all) {
-            all_list[atomicAdd(&all_count, 1)] = (short)n;
-            cand_n[n] = 0;
-            continue;
-        }
-        float lo_c = lb, hi_c = ub;
+        float lo_c = lb, hi_c = s.ub;
         auto consider = [&](int t, const f32x4& q, const qf32x2& q45) {
-            const float et = bound(t);
+            const float et = bound_of(wn, rn, t);
             const unsigned suspect = (__float_as_uint(q[3]) >> 16) & 1u;   // the trunk kernel did not trust its own merge: it flagged every group
             n_suspect += suspect;
             // the tile's largest score is out of range: so is the rest of it -- unless the record is suspect: then its scores prove
             // nothing about the tile and all its points are evaluated (a bogus top score that RAISES lb is caught by the check below)
-            if (!suspect && !(q[0] + et >= lb)) return;
+            if (!suspect && !(q[0] + et >= L)) return;
             unsigned flags = __float_as_uint(q[3]) & 0xFFFFu;   // one bit per 16-point group: 4 wave + lane quarter (pn_slots.h)
-            // a kept score in range: its point becomes a candidate of the channel.  (No search for a point that is already one: only
+            unsigned forced = suspect ? 0xFFFFu : 0u;           // groups that rule 1 must not gate
+            // a kept score in range: its point becomes a pair of the channel.  (No search for a point that is already one: only
             // padding slots repeat a point, a repeated candidate costs one more dot, and the search was a third of this phase.)
             auto take = [&](float v) {
-                int p = point_of_slot(t, slot_of_id(__float_as_uint(v) & 255u), deal);
-                if (p >= N) p = wrap_small ? p - N : p % N;  // a padding slot: the real point it repeats
-                if (abl & PN_ABL_FEW_ROWS) p &= 63;
-                if (cands < 4) cand[n][cands] = (unsigned short)p;
-                else {
-                    const int slot = atomicAdd(&pair_count, 1);
-                    if (slot < pair_cap) pair_list[slot] = n | (p << 10);
-                    else {                                       // list full (never seen): evaluate its 16-point group instead
-                        const unsigned id = __float_as_uint(v);
-                        flags |= 1u << pn_group_of_id(id);
-                    }
+                const int p = point_of_score(t, v);
+                const int slot = atomicAdd(&pair_count, 1);
+                if (slot < pair_cap) pair_list[slot] = n | (p << 10);
+                else {                                           // list full (never seen): evaluate its 16-point group instead
+                    const unsigned bit = 1u << pn_group_of_id(__float_as_uint(v));
+                    flags |= bit;
+                    forced |= bit;
                 }
                 ++cands;
             };
-            // descending scores: the ones in range are a prefix of (c1 .. c5)
+            // descending scores: the ones in range are a prefix of (c1 .. c5); the anchor has been evaluated
             const float sc5[5] = {q[0], q[1], q[2], q45[0], q45[1]};
 #pragma unroll 1
-            for (int k = 0; k < 5; ++k) {
+            for (int k = (t == s.t_star ? 1 : 0); k < 5; ++k) {
                 const float v = k == 0 ? sc5[0] : k == 1 ? sc5[1] : k == 2 ? sc5[2] : k == 3 ? sc5[3] : sc5[4];
-                if (!(v + et >= lb)) break;
+                if (!(v + et >= L)) break;
                 take(v);
             }
             while (flags) {
                 const int wh = __ffs(flags) - 1;             // the group: 4 * wave + lane quarter
                 flags &= flags - 1;
+                if (!((forced >> wh) & 1u) && !(abl & PN_ABL_NO_RULE1)) {
+                    // Rule 1: a point of group wh that is not among the five scores at most u: the smaller of the group's published
+                    // pair where both were kept (its third is bounded by its second only -- and may well exceed c5), else c5 (one
+                    // of the pair did not make the five).  Descending scores: the LAST one of the group is its second.  Written so
+                    // that a NaN keeps the group.
+                    auto of_group = [&](float v) { return pn_group_of_id(__float_as_uint(v)) == wh; };
+                    const bool m0 = of_group(sc5[0]), m1 = of_group(sc5[1]), m2 = of_group(sc5[2]), m3 = of_group(sc5[3]), m4 = of_group(sc5[4]);
+                    const float second = m4 ? sc5[4] : m3 ? sc5[3] : m2 ? sc5[2] : m1 ? sc5[1] : sc5[0];
+                    const float u = (int)m0 + (int)m1 + (int)m2 + (int)m3 + (int)m4 >= 2 ? second : sc5[4];
+                    if (u + et < L) continue;
+                }
                 const int slot = atomicAdd(&fb_count, 1);
                 if (slot < fb_cap) fb_list[slot] = n | (t << 10) | (wh << 20);
                 else if (!whole) {                           // list full (never seen): the channel goes on the "everything" list
@@ -972,7 +1116,6 @@ __global__ __launch_bounds__(256, 4) void pn_exact_kernel(const f32x4* __restric
                 consider(t0 + u, q, q45);
             }
         }
-        cand_n[n] = whole ? 0 : (unsigned char)min(cands, 4);
         if (whole) { lo_c = 1.f; hi_c = 0.f; }              // evaluated in full below: nothing to check
         lo_0 = ci == 0 ? lo_c : lo_0; hi_0 = ci == 0 ? hi_c : hi_0;
         lo_1 = ci == 1 ? lo_c : lo_1; hi_1 = ci == 1 ? hi_c : hi_1;
@@ -983,127 +1126,13 @@ __global__ __launch_bounds__(256, 4) void pn_exact_kernel(const f32x4* __restric
         n_cand += cands;
     }
     dvq_lds_barrier();
-    if (stamps) tp1 = __builtin_amdgcn_s_memtime();
-    // ---- phase A2: the pairs in POINT order (counting sort in the LDS).  A cloud's 1 024 channels take their maxima at ~100-200
-    // distinct points, so ~1 500 candidate pairs name each conv2 row ~10 times: evaluated channel by channel every pair fetched
-    // its 512-byte row from HBM again (0.74 MB per cloud, the kernel ran at the HBM roofline); grouped by point a row is
-    // fetched once and found in the L1 by the pairs that follow.
+    if (stamps) tp[4] = __builtin_amdgcn_s_memtime();
+    // ---- phase B: the pairs in point order
     const int npairs = min(pair_count, pair_cap);
-    for (int n = tid; n < 1024; n += 256)
-        for (int k = 0; k < cand_n[n]; ++k) atomicAdd(&pcnt[cand[n][k] & 1023], 1);     // N > 1024: points 1024 apart share a slot range
-    for (int i = tid; i < npairs; i += 256) atomicAdd(&pcnt[(pair_list[i] >> 10) & 1023], 1);
-    dvq_lds_barrier();
-    int total;
-    {
-        const int c0 = pcnt[4 * tid], c1 = pcnt[4 * tid + 1], c2 = pcnt[4 * tid + 2], c3 = pcnt[4 * tid + 3];
-        int incl = c0 + c1 + c2 + c3;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const int v = __shfl_up(incl, o);
-            if ((tid & 63) >= o) incl += v;
-        }
-        if ((tid & 63) == 63) wave_tot[tid >> 6] = incl;
-        dvq_lds_barrier();
-        int base = 0;
-        for (int w = 0; w < (tid >> 6); ++w) base += wave_tot[w];
-        total = wave_tot[0] + wave_tot[1] + wave_tot[2] + wave_tot[3];
-        const int excl = base + incl - (c0 + c1 + c2 + c3);
-        pcnt[4 * tid] = excl;
-        pcnt[4 * tid + 1] = excl + c0;
-        pcnt[4 * tid + 2] = excl + c0 + c1;
-        pcnt[4 * tid + 3] = excl + c0 + c1 + c2;
-    }
-    dvq_lds_barrier();
-    const bool by_point = total <= SORT_CAP && !(abl & PN_ABL_NO_DOTS);
-    if (by_point) {
-        for (int n = tid; n < 1024; n += 256)
-            for (int k = 0; k < cand_n[n]; ++k) {
-                const int p = cand[n][k];
-                sorted[atomicAdd(&pcnt[p & 1023], 1)] = (unsigned)n | ((unsigned)p << 10);
-            }
-        for (int i = tid; i < npairs; i += 256) {
-            const int code = pair_list[i];
-            sorted[atomicAdd(&pcnt[(code >> 10) & 1023], 1)] = (unsigned)code;
-        }
-        dvq_lds_barrier();
-        if (stamps) tp2 = __builtin_amdgcn_s_memtime();
-        // ---- phase B, point order: every 16-lane group takes a contiguous share of the list, four pairs in flight
-        const int per = (total + 15) >> 4, i0 = g * per, i1 = min(total, i0 + per);
-        for (int i = i0; i < i1; i += 4) {
-            f32x4 w0[4], w1[4], ha[4], hb[4];
-            int nn[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const unsigned code = sorted[min(i + u, i1 - 1)];
-                nn[u] = (int)(code & 1023u);
-                // (uniform base + 32-bit offset: the loads take the base from scalar registers, no 64-bit vector add per row)
-                const unsigned woff = (code & 1023u) * 512u + 16u * (unsigned)j, hoff = (code >> 10) * 512u + 16u * (unsigned)j;
-                w0[u] = *reinterpret_cast<const f32x4*>(reinterpret_cast<const char*>(w3) + woff);
-                w1[u] = *reinterpret_cast<const f32x4*>(reinterpret_cast<const char*>(w3) + woff + 256);
-                ha[u] = *reinterpret_cast<const f32x4*>(reinterpret_cast<const char*>(h2) + hoff);
-                hb[u] = *reinterpret_cast<const f32x4*>(reinterpret_cast<const char*>(h2) + hoff + 256);
-            }
-            float v[4], wc[4];                              // all eight chains first (independent: they interleave), the LDS updates after
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                v[u] = exact_dot_regs(w0[u], w1[u], ha[u], hb[u]);
-                wc[u] = exact_dot_regs(w0[u], w1[u], cen_a, cen_b);             // the centre term of this channel (check below)
-            }
-            if (j == 0) {
-#pragma unroll
-                for (int u = 0; u < 4; ++u)
-                    if (i + u < i1) { atomicMax(&best_k[nn[u]], f2key(v[u])); wcs[nn[u]] = wc[u]; }
-            }
-        }
-    }
-    // ---- phase B, channel order (more pairs than the sorted list holds): table; four channels of a group in flight (first
-    // candidates), further candidates afterwards
-    for (int n0 = g; n0 < ((abl & PN_ABL_NO_DOTS) || by_point ? 0 : 1024); n0 += 64) {
-        f32x4 w0[4], w1[4], ha[4], hb[4];
-        int cn[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int n = n0 + 16 * u;
-            cn[u] = cand_n[n];
-            const float* wr = reinterpret_cast<const float*>(reinterpret_cast<const char*>(w3) + ((unsigned)n * 512u + 16u * (unsigned)j));
-            w0[u] = *reinterpret_cast<const f32x4*>(wr);
-            w1[u] = *reinterpret_cast<const f32x4*>(wr + 64);
-            const float* hr = h2 + (long)(cn[u] ? cand[n][0] : 0) * 128 + 4 * j;
-            ha[u] = *reinterpret_cast<const f32x4*>(hr);
-            hb[u] = *reinterpret_cast<const f32x4*>(hr + 64);
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int n = n0 + 16 * u;
-            if (cn[u] == 0) continue;
-            float best = exact_dot_regs(w0[u], w1[u], ha[u], hb[u]);
-            const float wc = exact_dot_regs(w0[u], w1[u], cen_a, cen_b);
-            if (j == 0) wcs[n] = wc;
-            if (cn[u] > 1) {
-                f32x4 xa[3], xb[3];
-#pragma unroll
-                for (int k = 1; k < 4; ++k)
-                    if (k < cn[u]) {
-                        const float* hr = h2 + (long)cand[n][k] * 128 + 4 * j;
-                        xa[k - 1] = *reinterpret_cast<const f32x4*>(hr);
-                        xb[k - 1] = *reinterpret_cast<const f32x4*>(hr + 64);
-                    }
-#pragma unroll
-                for (int k = 1; k < 4; ++k)
-                    if (k < cn[u]) best = fmaxf(best, exact_dot_regs(w0[u], w1[u], xa[k - 1], xb[k - 1]));
-            }
-            if (j == 0) atomicMax(&best_k[n], f2key(best));
-        }
-    }
-    // ---- phase B, channel order: overflow list
-    for (int i = g; i < (by_point ? 0 : npairs); i += 16) {
-        const int code = pair_list[i];
-        const int n = code & 1023;
-        const float* wr = reinterpret_cast<const float*>(reinterpret_cast<const char*>(w3) + ((unsigned)n * 512u + 16u * (unsigned)j));
-        const float v = exact_dot(*reinterpret_cast<const f32x4*>(wr), *reinterpret_cast<const f32x4*>(wr + 64), h2 + (long)(code >> 10) * 128, j);
-        if (j == 0) atomicMax(&best_k[n], f2key(v));
-    }
-    if (stamps) tp3 = __builtin_amdgcn_s_memtime();
+    const int n_sorted = sort_by_point([&](int i) { return (unsigned)pair_list[i]; }, npairs, false);
+    if (stamps) tp[5] = __builtin_amdgcn_s_memtime();
+    if (!(abl & PN_ABL_NO_DOTS)) dots(n_sorted, false);
+    if (stamps) tp[6] = __builtin_amdgcn_s_memtime();
     // ---- phase C: flagged 16-point groups, one wave of the workgroup per entry, its four 16-lane groups take 4 points each
     const int nfb = (abl & PN_ABL_NO_GROUPS) ? 0 : min(fb_count, fb_cap);
     for (int i = tid >> 6; i < nfb; i += 4) {
@@ -1196,9 +1225,12 @@ __global__ __launch_bounds__(256, 4) void pn_exact_kernel(const f32x4* __restric
     }
     if (stamps && tid == 0) {
         const unsigned long long t_end = __builtin_amdgcn_s_memtime();
-        atomicAdd(stats + 4, tp1 - tp0); atomicAdd(stats + 5, tp2 - tp1); atomicAdd(stats + 6, tp3 - tp2); atomicAdd(stats + 7, t_end - tp3);
+        atomicAdd(stats + 4, (tp[1] - tp[0]) + (tp[4] - tp[3])); atomicAdd(stats + 5, (tp[2] - tp[1]) + (tp[5] - tp[4]));
+        atomicAdd(stats + 6, (tp[3] - tp[2]) + (tp[6] - tp[5])); atomicAdd(stats + 7, t_end - tp[6]);
+        atomicAdd(stats + 9, tp[3] - tp[0]);               // of the above: lower bounds, anchors, their sort and dots (rule 2's extra pass)
     }
     if (stats) {
+        if (n_rows) atomicAdd(stats + 8, (unsigned long long)n_rows);
         if (n_single) atomicAdd(stats + 0, (unsigned long long)n_single);
         if (n_multi) atomicAdd(stats + 1, (unsigned long long)n_multi);
         if (n_wave) atomicAdd(stats + 2, (unsigned long long)n_wave);
@@ -1361,7 +1393,7 @@ int dvq_launch_pn_filter_front(const PnBatch& in, const PnTrunkWeights& w, const
                                         tail ? F_LDS_TAIL : (DVQ_DIAG_ON ? 100 * 1024 : F_LDS), "pointnet"));
     const long B = in.B, grid = B * g.deal;
     DVQ_REQUIRE(B * g.tiles < (1L << 31), "pointnet: grid too large");
-    if (stats && hipMemsetAsync(stats, 0, 64, st) != hipSuccess) {       // statistics runs only; tstat is zeroed by pn_center_kernel
+    if (stats && hipMemsetAsync(stats, 0, PN_STATS_BYTES, st) != hipSuccess) {       // statistics runs only; tstat is zeroed by pn_center_kernel
         dvq_set_error("pointnet: hipMemsetAsync failed");
         return DVQ_ELAUNCH;
     }
@@ -1445,16 +1477,19 @@ int dvq_launch_pn_filter_back(const PnBatch& in, const PnTrunkWeights& w, const 
                 a / nrec * 64, b2_ / nrec * 64, c / nrec * 64, d / nrec * 512);
     }
     if (stats) {                                          // diagnostics (DVQ_PN_STATS=1): synchronises
-        unsigned long long h[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        unsigned long long h[PN_STATS_BYTES / 8] = {};
         (void)hipStreamSynchronize(st);
         (void)hipMemcpy(h, stats, sizeof h, hipMemcpyDeviceToHost);
         (void)hipMemset((void*)stats, 0, sizeof h);
         const double tot = (double)B * 1024;
         fprintf(stderr, "[dvq pn] B=%ld N=%d: one candidate %.4f, other counts %.4f of the channels, flagged 16-point groups %.5f per channel; %.3f candidate dots per channel\n",
                 B, N, h[0] / tot, h[1] / tot, h[2] / tot, h[3] / tot);
+        // the non-empty slots of the point histograms + 16 per flagged group (an upper bound: a group's points may be candidates too)
+        fprintf(stderr, "[dvq pn] B=%ld N=%d: distinct conv2 rows fetched per cloud <= %.1f (%.1f candidate points + 16 per flagged group)\n",
+                B, N, (double)(h[8] + 16 * h[2]) / B, (double)h[8] / B);
         if (abl & PN_ABL_STAMPS)
-            fprintf(stderr, "[dvq pn] exact stage, mean cycles per workgroup: records -> candidates %.0f, sort by point %.0f, candidate dots %.0f, flagged groups + checks + store %.0f\n",
-                    (double)h[4] / B, (double)h[5] / B, (double)h[6] / B, (double)h[7] / B);
+            fprintf(stderr, "[dvq pn] exact stage, mean cycles per workgroup: records -> candidates %.0f, sort by point %.0f, candidate dots %.0f, flagged groups + checks + store %.0f; of these the anchor pass %.0f\n",
+                    (double)h[4] / B, (double)h[5] / B, (double)h[6] / B, (double)h[7] / B, (double)h[9] / B);
     }
     return DVQ_OK;
 }
