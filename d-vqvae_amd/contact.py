@@ -60,3 +60,32 @@ def grasp_proxies(topology, hand_xyz, obj_xyz, contact_threshold=0.02 ** 2):
     return {"penetration": torch.where(inside, nn_dist, zero).sum(dim=1), "n_interior": inside.sum(dim=1),
             "n_contact": (nn_dist < contact_threshold).sum(dim=1), "nn_dist": nn_dist, "nn_idx": nn_idx,
             "interior": inside, "normals": normals}
+
+
+def grasp_scores(topology, hand_xyz, obj_xyz, contact_threshold=0.02 ** 2):
+    """``penetration`` [B] f32, ``n_interior`` [B] i32, ``n_contact`` [B] i32 of ``grasp_proxies`` from ONE fused kernel
+    (ops.grasp_scores): no [B,N] tensor is made.  Per object point the same bits; the sums in a fixed order (256 strided partial
+    sums, then a binary tree), so a grasp's scores do not depend on the batch it is in -- ``grasp_proxies``' penetration is a
+    torch reduction and agrees to rounding.  A grasp with a NaN distance reports NaN."""
+    pen, n_in, n_ct = ops.grasp_scores(hand_xyz.contiguous(), topology.faces, topology.vf_off, topology.vf_face, obj_xyz,
+                                       contact_threshold)
+    return {"penetration": pen, "n_interior": n_in, "n_contact": n_ct}
+
+
+SELECT_BY = ("penetration", "log_prob")
+
+
+def select_keys(scores, select_by, min_contact, log_prob=None):
+    """(cls int32 [B], key f32 [B]) for ``ops.segment_topk`` -- smaller is better, row by row:
+    ``"penetration"``: cls 2 where the penetration is NaN, else 1 where the hand touches fewer than ``min_contact`` object
+    points (a hand far from the object penetrates nothing), else 0; key = penetration.
+    ``"log_prob"``: cls 2 where it is NaN, else 0; key = -log_prob (likeliest first)."""
+    if select_by == "penetration":
+        pen = scores["penetration"]
+        cls = torch.where(torch.isnan(pen), 2, torch.where(scores["n_contact"] < int(min_contact), 1, 0))
+        return cls.to(torch.int32), pen
+    if select_by == "log_prob":
+        if log_prob is None:
+            raise RuntimeError("select_keys: select_by='log_prob' needs the grasps' log_prob")
+        return torch.where(torch.isnan(log_prob), 2, 0).to(torch.int32), -log_prob
+    raise RuntimeError(f"select_keys: select_by must be one of {SELECT_BY} (got {select_by!r})")

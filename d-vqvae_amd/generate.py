@@ -63,7 +63,23 @@ def build_parser(dataset: str) -> argparse.ArgumentParser:
     p.add_argument("--top_k", type=int, default=0, help="draw every grid position from its top_k likeliest codes (0 = all)")
     p.add_argument("--log_prob", type=int, default=0,
                    help="1: every object's JSON gains \"log_prob\", each grasp's log-likelihood under the (untempered) prior")
+    p.add_argument("--candidates", type=int, default=0,
+                   help="best-of-M: generate this many candidates per object, score them on the device and keep the num_grasp best "
+                        "(0 = off; otherwise >= num_grasp); the JSON gains \"candidate\", \"penetration\", \"n_interior\", \"n_contact\"")
+    p.add_argument("--select_by", choices=["penetration", "log_prob"], default="penetration",
+                   help="what ranks the candidates: least penetration among the hands that touch the object, or the prior's log-likelihood")
+    p.add_argument("--min_contact", type=int, default=1,
+                   help="--select_by penetration: hands with fewer object points within 2 cm rank after all others")
     return p
+
+
+def parse_args(dataset: str, argv: Optional[Sequence[str]] = None) -> argparse.Namespace:
+    """build_parser(dataset).parse_args(argv) plus the checks that span two flags."""
+    p = build_parser(dataset)
+    args = p.parse_args(argv)
+    if args.candidates < 0 or 0 < args.candidates < args.num_grasp:
+        p.error(f"--candidates must be 0 or at least --num_grasp (got {args.candidates} for {args.num_grasp} grasps)")
+    return args
 
 
 def _prior_controls(temperature: float, top_k: int, log_prob: bool) -> Dict[str, object]:
@@ -175,11 +191,16 @@ def generate_for_object(net: GenNet, obj4n: torch.Tensor, num_grasp: int, rotate
                      "R_list": Rt.tolist(), "trans_list": [t.reshape(3, 1).tolist()] * G, "r_list": angles.tolist(), **extra_json}}
 
 
-def _hand_topology(net: GenNet, n_verts: int, dev):
-    from . import contact
+def _hand_faces(net: GenNet) -> np.ndarray:
     faces = np.asarray(net.rh_mano.faces)
     if faces.size == 0 or int(faces.max()) == 0:
         raise RuntimeError("proxies: the MANO layer has no face list (synthetic model); load MANO_RIGHT.pkl")
+    return faces
+
+
+def _hand_topology(net: GenNet, n_verts: int, dev):
+    from . import contact
+    faces = _hand_faces(net)
     topo = getattr(net, "_hand_topology", None)
     if topo is None or topo.faces.device != dev:
         topo = contact.HandTopology(faces, n_verts, dev)
@@ -204,12 +225,17 @@ def plan_calls(point_counts: Sequence[int], num_grasp: int, rows_per_call: int) 
 @torch.no_grad()
 def _generate_call(net: GenNet, objs: Sequence[torch.Tensor], num_grasp: int, rotate: bool, seed: int,
                    object_indices: Sequence[int], proxies: bool, temperature: float = 1.0, top_k: int = 0,
-                   log_prob: bool = False) -> List[Dict[str, object]]:
+                   log_prob: bool = False, candidates: int = 0, select_by: str = "penetration",
+                   min_contact: int = 1) -> List[Dict[str, object]]:
     """One batched call: the ``num_grasp`` grasps of each of ``objs`` (all of one point count), row o * num_grasp + g = grasp g
     of object o.  Every step is row-independent and keyed per row, so each object's slice holds the bits of its own
-    ``generate_for_object`` call."""
+    ``generate_for_object`` call.  With ``candidates`` = M the call generates M rows per object (exactly the grasps of a
+    ``num_grasp = M`` call) and keeps each object's ``num_grasp`` best (_select_call)."""
     dev = next(net.parameters()).device
-    G, O = num_grasp, len(objs)
+    keep = num_grasp
+    G, O = (candidates or num_grasp), len(objs)
+    want_logp = log_prob
+    log_prob = log_prob or (bool(candidates) and select_by == "log_prob")
     if rotate:                                                                     # each object's own generator, as the loop draws them
         angles = [np.random.default_rng([seed, int(gi)]).random((G, 3)) * np.pi * 2 for gi in object_indices]
         Rs = [rotation_xyz(a) for a in angles]
@@ -230,6 +256,9 @@ def _generate_call(net: GenNet, objs: Sequence[torch.Tensor], num_grasp: int, ro
     params = ops.assemble61(recon, pos)                                            # obman.py:243-247
     final = net.rh_mano(betas=params[:, :10], global_orient=params[:, 10:13], hand_pose=params[:, 13:58],
                         transl=params[:, 58:61])                                   # obman.py:252-253
+    if candidates:
+        return _select_call(net, batch, params, final.vertices, logp, err, O, G, keep, select_by, min_contact, want_logp, proxies,
+                            np.concatenate(Rs), np.concatenate(angles), t)
     host = params.cpu().numpy()                                                    # ONE device-to-host copy per call
     if int(err.item()) != 0:
         raise RuntimeError("generate_for_objects: object index out of range in transform_clouds")
@@ -259,9 +288,65 @@ def _generate_call(net: GenNet, objs: Sequence[torch.Tensor], num_grasp: int, ro
     return outs
 
 
+def _host_copy(pieces: Sequence[torch.Tensor]) -> List[np.ndarray]:
+    """The given device tensors (4- or 8-byte elements, the 8-byte ones first) on the host through ONE device-to-host copy."""
+    flat = [p.contiguous().reshape(-1).view(torch.uint8) for p in pieces]
+    host = torch.cat(flat).cpu().numpy()
+    out, lo = [], 0
+    for p, f in zip(pieces, flat):
+        dt = {torch.float32: np.float32, torch.int32: np.int32, torch.int64: np.int64}[p.dtype]
+        out.append(host[lo:lo + f.numel()].view(dt).reshape(tuple(p.shape)))
+        lo += f.numel()
+    return out
+
+
+def _select_call(net: GenNet, batch: torch.Tensor, params: torch.Tensor, vertices: torch.Tensor, logp: Optional[torch.Tensor],
+                 err: torch.Tensor, O: int, M: int, keep: int, select_by: str, min_contact: int, want_logp: bool, proxies: bool,
+                 R: np.ndarray, angles: np.ndarray, t: np.ndarray) -> List[Dict[str, object]]:
+    """Best-of-M for all the objects of a call together: the candidates' scores (one fused kernel), their keys, each object's
+    ``keep`` best (one kernel), one ``index_select`` of the kept rows and one device-to-host copy.  Row o * M + c is candidate c of
+    object o; nothing here depends on which objects share the call."""
+    from . import contact
+    dev = params.device
+    topo = _hand_topology(net, vertices.shape[1], dev)
+    scores = contact.grasp_scores(topo, vertices, batch[:, :3].transpose(1, 2))
+    if logp is not None:
+        scores["log_prob"] = logp
+    cls, key = contact.select_keys(scores, select_by, min_contact, log_prob=logp)
+    sel = ops.segment_topk(cls.contiguous(), key.contiguous(), O, M, keep)                # [O,keep] candidate indices, best first
+    rows = (sel + torch.arange(O, device=dev).unsqueeze(1) * M).reshape(-1)                 # rows of the call
+    kept_p, kept_v = params.index_select(0, rows), vertices.index_select(0, rows)
+    kept_s = {k: v.index_select(0, rows) for k, v in scores.items()}
+    names = sorted(kept_s)
+    host = _host_copy([sel] + [kept_p] + [kept_s[k] for k in names] + [err])           # ONE device-to-host copy per call
+    if int(host[-1][0]) != 0:
+        raise RuntimeError("generate_for_objects: object index out of range in transform_clouds")
+    sel_h, p_list = host[0], host[1].tolist()
+    s_list = {k: h.tolist() for k, h in zip(names, host[2:-1])}
+    rows_h = (sel_h + np.arange(O)[:, None] * M).reshape(-1)
+    Rt_list = np.concatenate([R[rows_h], np.broadcast_to(t.reshape(1, 3, 1), (O * keep, 3, 1))], axis=2).tolist()
+    r_list = angles[rows_h].tolist()
+    c_list = sel_h.tolist()
+    trans = t.reshape(3, 1).tolist()
+    json_scores = ["penetration", "n_interior", "n_contact"] + (["log_prob"] if want_logp or select_by == "log_prob" else [])
+    p_dev, v_dev = kept_p.split(keep), kept_v.split(keep)
+    outs = []
+    for o in range(O):
+        lo, hi = o * keep, (o + 1) * keep
+        extra = {"log_prob": kept_s["log_prob"][lo:hi]} if "log_prob" in json_scores else {}
+        if proxies:                                                                # of the kept grasps, as the plain path returns them
+            extra["proxies"] = contact.grasp_proxies(topo, v_dev[o], batch.index_select(0, rows[lo:hi])[:, :3].transpose(1, 2))
+        outs.append({**extra, "params": p_dev[o], "vertices": v_dev[o], "candidate": sel[o],
+                     "scores": {k: v[o * M:(o + 1) * M] for k, v in scores.items()},
+                     "json": {"recon_params": [[p] for p in p_list[lo:hi]], "R_list": Rt_list[lo:hi], "trans_list": [trans] * keep,
+                              "r_list": r_list[lo:hi], "candidate": c_list[o], **{k: s_list[k][lo:hi] for k in json_scores}}})
+    return outs
+
+
 def generate_for_objects(net: GenNet, objs: Sequence[torch.Tensor], num_grasp: int, rotate: bool, seed: int,
                          object_indices: Sequence[int], proxies: bool = False, rows_per_call: int = 16384, temperature: float = 1.0,
-                         top_k: int = 0, log_prob: bool = False) -> List[Dict[str, object]]:
+                         top_k: int = 0, log_prob: bool = False, candidates: int = 0, select_by: str = "penetration",
+                         min_contact: int = 1) -> List[Dict[str, object]]:
     """``num_grasp`` grasps for each of ``objs`` ([4,N] tensors) in batched calls that mix objects (plan_calls): one dict per
     object, in the order given, equal to ``generate_for_object(net, objs[i], num_grasp, rotate,
     np.random.default_rng([seed, object_indices[i]]), seed=seed, object_index=object_indices[i], proxies=proxies)`` (and the same
@@ -269,20 +354,37 @@ def generate_for_objects(net: GenNet, objs: Sequence[torch.Tensor], num_grasp: i
     tensors bit for bit, ``json`` as Python objects.  Per call: the rotations of each object's own generator, one
     ``ops.transform_clouds``, one ``GenNet.gen(row_keys=)`` with stream = object index and row = grasp index, one ``assemble61``,
     one posed-MANO pass, one device-to-host copy.  A call's clouds and intermediates are freed before the next call; the results
-    returned stay on the device, so hand over one call's objects at a time (as ``main`` does) when the list is long."""
+    returned stay on the device, so hand over one call's objects at a time (as ``main`` does) when the list is long.
+
+    Best-of-M (``candidates`` = M >= ``num_grasp``): every call generates M rows per object -- candidate c is exactly grasp c of a
+    ``num_grasp = M`` run -- scores them against their clouds (``contact.grasp_scores``), ranks them (``contact.select_keys`` by
+    ``select_by`` / ``min_contact``, ``ops.segment_topk``) and keeps each object's ``num_grasp`` best, best first: ``params``
+    [num_grasp,61], ``vertices``, ``candidate`` [num_grasp] (indices into the M), ``scores`` (the [M] tensors of ALL candidates:
+    penetration, n_interior, n_contact and, when computed, log_prob) and ``json`` with the four reference fields of the kept grasps
+    plus "candidate", "penetration", "n_interior", "n_contact" (and "log_prob" when asked for or selected by).  Still one
+    device-to-host copy per call and no per-object device work; needs a MANO layer with a face list."""
     if len(object_indices) != len(objs):
         raise RuntimeError("generate_for_objects: one object index per object")
+    if candidates:
+        from . import contact
+        if candidates < num_grasp:
+            raise RuntimeError(f"generate_for_objects: candidates must be 0 or >= num_grasp (got {candidates} for {num_grasp})")
+        if candidates > ops.SEGMENT_TOPK_MAX_M:
+            raise RuntimeError(f"generate_for_objects: at most {ops.SEGMENT_TOPK_MAX_M} candidates per object (got {candidates})")
+        if select_by not in contact.SELECT_BY:
+            raise RuntimeError(f"generate_for_objects: select_by must be one of {contact.SELECT_BY} (got {select_by!r})")
+        _hand_faces(net)                                                           # no face list: raise before any work
     out: List[Optional[Dict[str, object]]] = [None] * len(objs)
-    for call in plan_calls([o.shape[1] for o in objs], num_grasp, rows_per_call):
+    for call in plan_calls([o.shape[1] for o in objs], candidates or num_grasp, rows_per_call):
         res = _generate_call(net, [objs[p] for p in call], num_grasp, rotate, seed, [object_indices[p] for p in call], proxies,
-                             temperature, top_k, log_prob)
+                             temperature, top_k, log_prob, candidates, select_by, min_contact)
         for p, r in zip(call, res):
             out[p] = r
     return out
 
 
 def main(dataset: str, argv: Optional[Sequence[str]] = None) -> List[str]:
-    args = build_parser(dataset).parse_args(argv)
+    args = parse_args(dataset, argv)
     rank, local_rank, world = dist.init()
     if not torch.cuda.is_available():
         raise RuntimeError("the HIP path needs a GPU: there is no CPU fallback (use the reference on CPU)")
@@ -301,22 +403,26 @@ def main(dataset: str, argv: Optional[Sequence[str]] = None) -> List[str]:
     total_t, total_g = 0.0, 0
     wall0 = time.time()
     rotate = DATASETS[dataset]["rotate"]
-    if args.rows_per_call > 0:
+    if args.rows_per_call > 0 or args.candidates:
+        # grouped calls (best-of-M always: --rows_per_call 0 is then one object per call)
+        rows_per_call, per_object = max(1, args.rows_per_call), (args.candidates or args.num_grasp)
+        selection = dict(candidates=args.candidates, select_by=args.select_by, min_contact=args.min_contact) if args.candidates else {}
         # grouped calls: one call's objects at a time, its files written before the next call starts, so the device and the host
         # hold one call's results, not the whole list's
         mine = objs[lo:hi]
         paths: Dict[int, str] = {}
-        for call in plan_calls([o.shape[1] for _, o in mine], args.num_grasp, args.rows_per_call):
+        for call in plan_calls([o.shape[1] for _, o in mine], per_object, rows_per_call):
             torch.cuda.synchronize(device)
             t0 = time.time()
             outs = generate_for_objects(net, [mine[p][1] for p in call], args.num_grasp, rotate, args.seed, [lo + p for p in call],
-                                        rows_per_call=args.rows_per_call, temperature=args.temperature, top_k=args.top_k,
-                                        log_prob=bool(args.log_prob))
+                                        rows_per_call=rows_per_call, temperature=args.temperature, top_k=args.top_k,
+                                        log_prob=bool(args.log_prob), **selection)
             torch.cuda.synchronize(device)
             dt = time.time() - t0
             total_t += dt
             total_g += args.num_grasp * len(call)
-            print(f"gen_time: {dt:.4f} s for {args.num_grasp * len(call)} grasps of {len(call)} objects")
+            best_of = f" (the best of {args.candidates * len(call)} candidates)" if args.candidates else ""
+            print(f"gen_time: {dt:.4f} s for {args.num_grasp * len(call)} grasps of {len(call)} objects{best_of}")
             for p, out in zip(call, outs):
                 paths[p] = os.path.join(args.out_dir, f"obj_id_{mine[p][0]}.json")
                 with open(paths[p], "w") as f:

@@ -697,3 +697,61 @@ def interior(normals: Tensor, hand: Tensor, obj: Tensor, nn_idx: Tensor) -> Tens
         check(lib.dvq_interior(normals.data_ptr(), hand.data_ptr(), V, po, ob, op, oc, nn_idx.data_ptr(), B, N,
                                out.data_ptr(), _stream(dev)), "dvq_interior")
     return out.bool()
+
+
+GRASP_SCORES_MAX_V = 2048          # csrc/contact.hip: GS_MAX_V (the hand and its normals sit in LDS)
+SEGMENT_TOPK_MAX_M = 4096          # csrc/contact.hip: TOPK_MAX_M
+
+
+def grasp_scores(hand: Tensor, faces: Tensor, vf_off: Tensor, vf_face: Tensor, obj: Tensor, contact_threshold: float = 0.02 ** 2):
+    """Per-grasp ``(penetration [B] f32, n_interior [B] i32, n_contact [B] i32)`` in one fused kernel (dvq_grasp_scores): hand
+    [B,V,3] contiguous, the topology of ``contact.face_csr`` on the device, obj [B,N,3] with any strides.  Per point the bits of
+    ``vertex_normals`` / ``nn_points`` / ``interior``; the sums in the fixed order include/dvq.h documents."""
+    for t, n in ((hand, "hand"), (obj, "obj"), (faces, "faces"), (vf_off, "vf_off"), (vf_face, "vf_face")):
+        if not isinstance(t, Tensor):
+            raise RuntimeError(f"grasp_scores: {n} must be a tensor")
+    _f32(hand, "hand")
+    for t, n in ((faces, "faces"), (vf_off, "vf_off"), (vf_face, "vf_face")):
+        if t.dtype != torch.int32 or not t.is_contiguous():
+            raise RuntimeError(f"grasp_scores: {n} must be contiguous int32")
+    if hand.dim() != 3 or hand.shape[2] != 3 or not hand.is_contiguous():
+        raise RuntimeError("grasp_scores: hand must be contiguous [B,V,3]")
+    po, ob, op, oc = _points(obj, "obj")
+    B, V, N = hand.shape[0], hand.shape[1], obj.shape[1]
+    if obj.shape[0] != B:
+        raise RuntimeError("grasp_scores: batch mismatch")
+    if N < 1 or not 1 <= V <= GRASP_SCORES_MAX_V:
+        raise RuntimeError(f"grasp_scores: need N >= 1 and 1 <= V <= {GRASP_SCORES_MAX_V} (got N={N} V={V})")
+    if faces.dim() != 2 or faces.shape[1] != 3 or vf_off.numel() != V + 1 or vf_face.numel() != faces.numel():
+        raise RuntimeError("grasp_scores: CSR does not match the mesh")
+    dev = _require_gpu(hand, obj, faces, vf_off, vf_face)
+    lib = _lib.load()
+    pen = torch.empty(B, dtype=torch.float32, device=dev)
+    n_in = torch.empty(B, dtype=torch.int32, device=dev)
+    n_ct = torch.empty(B, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        check(lib.dvq_grasp_scores(hand.data_ptr(), faces.data_ptr(), vf_off.data_ptr(), vf_face.data_ptr(), V, po, ob, op, oc, B, N,
+                                   float(contact_threshold), pen.data_ptr(), n_in.data_ptr(), n_ct.data_ptr(), _stream(dev)),
+              "dvq_grasp_scores")
+    return pen, n_in, n_ct
+
+
+def segment_topk(cls: Tensor, key: Tensor, n_objects: int, n_candidates: int, keep: int) -> Tensor:
+    """cls int32 [O*M], key f32 [O*M] (candidate c of object o at o * M + c) -> int64 [O,keep]: each object's ``keep`` best
+    candidate indices, best first, by (cls, key, index) with NaN keys last in their class and -0.0 == +0.0 (dvq_segment_topk)."""
+    if not isinstance(cls, Tensor) or not isinstance(key, Tensor):
+        raise RuntimeError("segment_topk: cls and key must be tensors")
+    O, M, keep = int(n_objects), int(n_candidates), int(keep)
+    if cls.dtype != torch.int32:
+        raise RuntimeError(f"segment_topk: cls: expected int32, got {cls.dtype}")
+    _f32(key, "key")
+    if O < 0 or not 1 <= keep <= M <= SEGMENT_TOPK_MAX_M:
+        raise RuntimeError(f"segment_topk: need O >= 0 and 1 <= keep <= M <= {SEGMENT_TOPK_MAX_M} (got O={O} M={M} keep={keep})")
+    if cls.dim() != 1 or key.dim() != 1 or cls.numel() != O * M or key.numel() != O * M or not cls.is_contiguous() or not key.is_contiguous():
+        raise RuntimeError(f"segment_topk: cls and key must be contiguous [O*M] = [{O * M}] (got {tuple(cls.shape)}, {tuple(key.shape)})")
+    dev = _require_gpu(cls, key)
+    lib = _lib.load()
+    sel = torch.empty(O, keep, dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        check(lib.dvq_segment_topk(cls.data_ptr(), key.data_ptr(), O, M, keep, sel.data_ptr(), _stream(dev)), "dvq_segment_topk")
+    return sel

@@ -41,7 +41,7 @@ typedef enum {
  * (struct layouts change between versions). */
 #define DVQ_ABI_VERSION 10
 /* Entry points added since 10 without touching a struct or a signature of it (a compatible extension: bindings of 10 keep
- * working, the version stays): dvq_pixelcnn_sample_ctl. */
+ * working, the version stays): dvq_pixelcnn_sample_ctl, dvq_grasp_scores, dvq_segment_topk. */
 int dvq_abi_version(void);
 const char* dvq_last_error(void);
 /* number of visible HIP devices, or -1; does not create a context */
@@ -361,6 +361,34 @@ int dvq_vertex_normals(const float* verts /* [B,V,3] */, int64_t B, int V, const
 int dvq_interior(const float* normals /* [B,V,3] */, const float* hand /* [B,V,3] */, int V, const float* obj,
                  int64_t obj_batch_stride, int64_t obj_point_stride, int64_t obj_coord_stride,
                  const int64_t* nn_idx /* [B,N] */, int64_t B, int N, uint8_t* interior /* [B,N] */, dvq_stream_t stream);
+
+/* Per-grasp scores for ranking candidates: the three reductions of the proxies above (utils/utils_loss.py:7-45 get_NN /
+ * get_interior, the penetration and contact terms of utils/loss.py:154-160) in ONE kernel, one workgroup of 256 threads per grasp;
+ * no [B,N] or [B,V,3] intermediate is written.  hand [B,V,3] contiguous; faces / vf_off / vf_face as in dvq_vertex_normals; obj
+ * with strides in floats as in dvq_nn_points (a channel-first cloud is read in place).  B >= 0, N >= 1, 1 <= V <= 2048; anything
+ * else is DVQ_EINVAL.
+ * Per object point p of grasp b (the bits dvq_vertex_normals, dvq_nn_points and dvq_interior produce):
+ *   normals : per vertex the sum over its incident faces, ascending, of cross(v1 - v0, v2 - v0) (products rounded, no fma), divided
+ *             by max(|n|, 1e-6) with |n| = sqrt(fma(nz,nz, fma(ny,ny, nx*nx)))
+ *   d, j    : d = fma(dz,dz, fma(dy,dy, dx*dx)) with dx = obj.x - hand[v].x ..., minimum over v = 0 .. V-1, first minimum, NaN first
+ *   inside  : fma(vz, n[j].z, fma(vy, n[j].y, vx * n[j].x)) > 0 with vx = hand[j].x - obj.x ...
+ *   term    : d when inside or d is NaN, else +0.0f
+ * Reduction, in this fixed order (a grasp's result does not depend on B or on its row):
+ *   thread t (0 .. 255) starts from +0.0f and adds the terms of its points p = t, t + 256, ... in ascending p (fp32 additions);
+ *   the 256 partial sums are combined by the tree  for s in 128, 64, ..., 1: part[t] += part[t + s] for every t < s;
+ *   penetration[b] = part[0]  (NaN when any distance of the grasp is NaN);
+ *   n_interior[b] = #inside, n_contact[b] = #(d < contact_threshold): integer sums. */
+int dvq_grasp_scores(const float* hand /* [B,V,3] */, const int32_t* faces, const int32_t* vf_off, const int32_t* vf_face, int V,
+                     const float* obj, int64_t obj_batch_stride, int64_t obj_point_stride, int64_t obj_coord_stride,
+                     int64_t B, int N, float contact_threshold, float* penetration /* [B] */, int32_t* n_interior /* [B] */,
+                     int32_t* n_contact /* [B] */, dvq_stream_t stream);
+/* Per-object selection: cls, key [O*M] (candidate c of object o at o * M + c) -> sel [O,keep]: the candidate indices (0 .. M-1) of
+ * each object's keep best candidates, best first.  Candidate a ranks before b iff (cls, key, index) is smaller: cls as signed
+ * integers; within a class a NaN key sorts after every number and -0.0 == +0.0; the index breaks every tie.  One workgroup per
+ * object; a candidate's rank is the count of candidates before it (O(M^2), deterministic, no workspace).
+ * O >= 0, 1 <= keep <= M <= 4096; anything else is DVQ_EINVAL. */
+int dvq_segment_topk(const int32_t* cls /* [O*M] */, const float* key /* [O*M] */, int64_t O, int M, int keep,
+                     int64_t* sel /* [O,keep] */, dvq_stream_t stream);
 
 /* ------------------------------------------------------------------ all-gather of the generated MANO parameters (multi-GPU)
  * The batch of objects shards contiguously over R ranks (one process per GPU); the only exchange of the path is
