@@ -23,6 +23,8 @@ from .network.gen_net import GenNet
 
 CANONICAL_OFFSET = (-0.0793, 0.0208, -0.6924)       # gen_diverse_grasp_ho3d.py:221
 
+DIVERSE_SPACES = ("params", "verts")                 # --diverse_space: squared distances over [61] or [778 * 3]
+
 DATASETS = {                                         # grasps per object, random rotation per grasp
     "obman": dict(num_grasp=1, rotate=False),        # gen_diverse_grasp_obman.py:233
     "ho3d": dict(num_grasp=100, rotate=True),        # gen_diverse_grasp_ho3d.py:212
@@ -70,6 +72,12 @@ def build_parser(dataset: str) -> argparse.ArgumentParser:
                    help="what ranks the candidates: least penetration among the hands that touch the object, or the prior's log-likelihood")
     p.add_argument("--min_contact", type=int, default=1,
                    help="--select_by penetration: hands with fewer object points within 2 cm rank after all others")
+    p.add_argument("--diverse_pool", type=int, default=0,
+                   help="diverse best-of-M: keep the num_grasp most spread-out of the diverse_pool best-ranked candidates (greedy "
+                        "farthest-point order, the best one first) instead of the num_grasp best; 0 = off, otherwise num_grasp <= "
+                        "diverse_pool <= candidates; the JSON gains \"rank\" and \"novelty\"")
+    p.add_argument("--diverse_space", choices=list(DIVERSE_SPACES), default="params",
+                   help="what --diverse_pool measures distances in: the 61 parameters or the 778 posed vertices")
     return p
 
 
@@ -79,6 +87,11 @@ def parse_args(dataset: str, argv: Optional[Sequence[str]] = None) -> argparse.N
     args = p.parse_args(argv)
     if args.candidates < 0 or 0 < args.candidates < args.num_grasp:
         p.error(f"--candidates must be 0 or at least --num_grasp (got {args.candidates} for {args.num_grasp} grasps)")
+    if args.diverse_pool < 0 or (args.diverse_pool and not args.candidates):
+        p.error(f"--diverse_pool must be 0, or positive together with --candidates (got {args.diverse_pool} with --candidates {args.candidates})")
+    if args.diverse_pool and not args.num_grasp <= args.diverse_pool <= args.candidates:
+        p.error(f"--diverse_pool must lie between --num_grasp and --candidates (got {args.diverse_pool} for {args.num_grasp} grasps of "
+                f"{args.candidates} candidates)")
     return args
 
 
@@ -226,7 +239,7 @@ def plan_calls(point_counts: Sequence[int], num_grasp: int, rows_per_call: int) 
 def _generate_call(net: GenNet, objs: Sequence[torch.Tensor], num_grasp: int, rotate: bool, seed: int,
                    object_indices: Sequence[int], proxies: bool, temperature: float = 1.0, top_k: int = 0,
                    log_prob: bool = False, candidates: int = 0, select_by: str = "penetration",
-                   min_contact: int = 1) -> List[Dict[str, object]]:
+                   min_contact: int = 1, diverse_pool: int = 0, diverse_space: str = "params") -> List[Dict[str, object]]:
     """One batched call: the ``num_grasp`` grasps of each of ``objs`` (all of one point count), row o * num_grasp + g = grasp g
     of object o.  Every step is row-independent and keyed per row, so each object's slice holds the bits of its own
     ``generate_for_object`` call.  With ``candidates`` = M the call generates M rows per object (exactly the grasps of a
@@ -258,7 +271,7 @@ def _generate_call(net: GenNet, objs: Sequence[torch.Tensor], num_grasp: int, ro
                         transl=params[:, 58:61])                                   # obman.py:252-253
     if candidates:
         return _select_call(net, batch, params, final.vertices, logp, err, O, G, keep, select_by, min_contact, want_logp, proxies,
-                            np.concatenate(Rs), np.concatenate(angles), t)
+                            np.concatenate(Rs), np.concatenate(angles), t, diverse_pool, diverse_space)
     host = params.cpu().numpy()                                                    # ONE device-to-host copy per call
     if int(err.item()) != 0:
         raise RuntimeError("generate_for_objects: object index out of range in transform_clouds")
@@ -302,10 +315,13 @@ def _host_copy(pieces: Sequence[torch.Tensor]) -> List[np.ndarray]:
 
 def _select_call(net: GenNet, batch: torch.Tensor, params: torch.Tensor, vertices: torch.Tensor, logp: Optional[torch.Tensor],
                  err: torch.Tensor, O: int, M: int, keep: int, select_by: str, min_contact: int, want_logp: bool, proxies: bool,
-                 R: np.ndarray, angles: np.ndarray, t: np.ndarray) -> List[Dict[str, object]]:
+                 R: np.ndarray, angles: np.ndarray, t: np.ndarray, diverse_pool: int = 0,
+                 diverse_space: str = "params") -> List[Dict[str, object]]:
     """Best-of-M for all the objects of a call together: the candidates' scores (one fused kernel), their keys, each object's
     ``keep`` best (one kernel), one ``index_select`` of the kept rows and one device-to-host copy.  Row o * M + c is candidate c of
-    object o; nothing here depends on which objects share the call."""
+    object o; nothing here depends on which objects share the call.  ``diverse_pool`` = P: each object's P best (the same kernel),
+    then the ``keep`` most spread-out of them in greedy farthest-point order (``ops.segment_diverse`` over the parameters or the
+    posed vertices, read in place); their pool positions and squared gaps ride along in the one copy."""
     from . import contact
     dev = params.device
     topo = _hand_topology(net, vertices.shape[1], dev)
@@ -313,16 +329,29 @@ def _select_call(net: GenNet, batch: torch.Tensor, params: torch.Tensor, vertice
     if logp is not None:
         scores["log_prob"] = logp
     cls, key = contact.select_keys(scores, select_by, min_contact, log_prob=logp)
-    sel = ops.segment_topk(cls.contiguous(), key.contiguous(), O, M, keep)                # [O,keep] candidate indices, best first
+    diverse = []
+    if diverse_pool:
+        pool = ops.segment_topk(cls.contiguous(), key.contiguous(), O, M, diverse_pool)   # [O,P] candidate indices, best first
+        feat = params if diverse_space == "params" else vertices.reshape(vertices.shape[0], -1)
+        pool_err = ops.new_err_flag(dev)                                                  # read with everything else, below
+        sel, rank, gap = ops.segment_diverse(feat, pool, O, M, keep, err=pool_err)        # [O,keep] in pick order
+        diverse = [rank, gap, pool_err]
+    else:
+        sel = ops.segment_topk(cls.contiguous(), key.contiguous(), O, M, keep)            # [O,keep] candidate indices, best first
     rows = (sel + torch.arange(O, device=dev).unsqueeze(1) * M).reshape(-1)                 # rows of the call
     kept_p, kept_v = params.index_select(0, rows), vertices.index_select(0, rows)
     kept_s = {k: v.index_select(0, rows) for k, v in scores.items()}
     names = sorted(kept_s)
-    host = _host_copy([sel] + [kept_p] + [kept_s[k] for k in names] + [err])           # ONE device-to-host copy per call
+    host = _host_copy([sel] + [kept_p] + [kept_s[k] for k in names] + diverse + [err])  # ONE device-to-host copy per call
     if int(host[-1][0]) != 0:
         raise RuntimeError("generate_for_objects: object index out of range in transform_clouds")
     sel_h, p_list = host[0], host[1].tolist()
-    s_list = {k: h.tolist() for k, h in zip(names, host[2:-1])}
+    s_list = {k: h.tolist() for k, h in zip(names, host[2:2 + len(names)])}
+    if diverse_pool:
+        rank_h, gap_h, pool_err_h = host[2 + len(names):-1]
+        if int(pool_err_h[0]) != 0:
+            raise RuntimeError("generate_for_objects: pool entry out of range in segment_diverse")
+        rank_list, gap_list = rank_h.tolist(), gap_h.tolist()
     rows_h = (sel_h + np.arange(O)[:, None] * M).reshape(-1)
     Rt_list = np.concatenate([R[rows_h], np.broadcast_to(t.reshape(1, 3, 1), (O * keep, 3, 1))], axis=2).tolist()
     r_list = angles[rows_h].tolist()
@@ -336,17 +365,22 @@ def _select_call(net: GenNet, batch: torch.Tensor, params: torch.Tensor, vertice
         extra = {"log_prob": kept_s["log_prob"][lo:hi]} if "log_prob" in json_scores else {}
         if proxies:                                                                # of the kept grasps, as the plain path returns them
             extra["proxies"] = contact.grasp_proxies(topo, v_dev[o], batch.index_select(0, rows[lo:hi])[:, :3].transpose(1, 2))
+        extra_json = {}
+        if diverse_pool:
+            extra["rank"], extra["novelty"] = rank[o], gap[o]
+            extra_json = {"rank": rank_list[o], "novelty": gap_list[o]}
         outs.append({**extra, "params": p_dev[o], "vertices": v_dev[o], "candidate": sel[o],
                      "scores": {k: v[o * M:(o + 1) * M] for k, v in scores.items()},
                      "json": {"recon_params": [[p] for p in p_list[lo:hi]], "R_list": Rt_list[lo:hi], "trans_list": [trans] * keep,
-                              "r_list": r_list[lo:hi], "candidate": c_list[o], **{k: s_list[k][lo:hi] for k in json_scores}}})
+                              "r_list": r_list[lo:hi], "candidate": c_list[o], **{k: s_list[k][lo:hi] for k in json_scores},
+                              **extra_json}})
     return outs
 
 
 def generate_for_objects(net: GenNet, objs: Sequence[torch.Tensor], num_grasp: int, rotate: bool, seed: int,
                          object_indices: Sequence[int], proxies: bool = False, rows_per_call: int = 16384, temperature: float = 1.0,
                          top_k: int = 0, log_prob: bool = False, candidates: int = 0, select_by: str = "penetration",
-                         min_contact: int = 1) -> List[Dict[str, object]]:
+                         min_contact: int = 1, diverse_pool: int = 0, diverse_space: str = "params") -> List[Dict[str, object]]:
     """``num_grasp`` grasps for each of ``objs`` ([4,N] tensors) in batched calls that mix objects (plan_calls): one dict per
     object, in the order given, equal to ``generate_for_object(net, objs[i], num_grasp, rotate,
     np.random.default_rng([seed, object_indices[i]]), seed=seed, object_index=object_indices[i], proxies=proxies)`` (and the same
@@ -362,9 +396,25 @@ def generate_for_objects(net: GenNet, objs: Sequence[torch.Tensor], num_grasp: i
     [num_grasp,61], ``vertices``, ``candidate`` [num_grasp] (indices into the M), ``scores`` (the [M] tensors of ALL candidates:
     penetration, n_interior, n_contact and, when computed, log_prob) and ``json`` with the four reference fields of the kept grasps
     plus "candidate", "penetration", "n_interior", "n_contact" (and "log_prob" when asked for or selected by).  Still one
-    device-to-host copy per call and no per-object device work; needs a MANO layer with a face list."""
+    device-to-host copy per call and no per-object device work; needs a MANO layer with a face list.
+
+    Diverse best-of-M (``diverse_pool`` = P, ``num_grasp`` <= P <= ``candidates``): of each object's P best-ranked candidates the
+    call keeps the ``num_grasp`` most spread-out ones, in greedy farthest-point order starting from the best (``ops.segment_diverse``;
+    squared distances over the 61 parameters, or over the posed vertices with ``diverse_space="verts"``).  The kept grasps come in
+    pick order; the dicts gain ``rank`` (int32 [num_grasp], the position in the ranking) and ``novelty`` (fp32 [num_grasp], the
+    squared distance to the nearest earlier pick, -1 for the first), and ``json`` gains "rank" and "novelty" after the scores.
+    ``diverse_pool = 0`` is the call without the keyword."""
     if len(object_indices) != len(objs):
         raise RuntimeError("generate_for_objects: one object index per object")
+    if diverse_pool:
+        if diverse_space not in DIVERSE_SPACES:
+            raise RuntimeError(f"generate_for_objects: diverse_space must be one of {DIVERSE_SPACES} (got {diverse_space!r})")
+        if diverse_pool < 0 or not candidates:
+            raise RuntimeError(f"generate_for_objects: diverse_pool must be 0, or positive together with candidates (got {diverse_pool} "
+                               f"with candidates={candidates})")
+        if not num_grasp <= diverse_pool <= candidates:
+            raise RuntimeError(f"generate_for_objects: diverse_pool must lie between num_grasp and candidates (got {diverse_pool} for "
+                               f"{num_grasp} grasps of {candidates} candidates)")
     if candidates:
         from . import contact
         if candidates < num_grasp:
@@ -377,7 +427,7 @@ def generate_for_objects(net: GenNet, objs: Sequence[torch.Tensor], num_grasp: i
     out: List[Optional[Dict[str, object]]] = [None] * len(objs)
     for call in plan_calls([o.shape[1] for o in objs], candidates or num_grasp, rows_per_call):
         res = _generate_call(net, [objs[p] for p in call], num_grasp, rotate, seed, [object_indices[p] for p in call], proxies,
-                             temperature, top_k, log_prob, candidates, select_by, min_contact)
+                             temperature, top_k, log_prob, candidates, select_by, min_contact, diverse_pool, diverse_space)
         for p, r in zip(call, res):
             out[p] = r
     return out
@@ -407,6 +457,8 @@ def main(dataset: str, argv: Optional[Sequence[str]] = None) -> List[str]:
         # grouped calls (best-of-M always: --rows_per_call 0 is then one object per call)
         rows_per_call, per_object = max(1, args.rows_per_call), (args.candidates or args.num_grasp)
         selection = dict(candidates=args.candidates, select_by=args.select_by, min_contact=args.min_contact) if args.candidates else {}
+        if args.diverse_pool:
+            selection.update(diverse_pool=args.diverse_pool, diverse_space=args.diverse_space)
         # grouped calls: one call's objects at a time, its files written before the next call starts, so the device and the host
         # hold one call's results, not the whole list's
         mine = objs[lo:hi]

@@ -755,3 +755,59 @@ def segment_topk(cls: Tensor, key: Tensor, n_objects: int, n_candidates: int, ke
     with torch.cuda.device(dev):
         check(lib.dvq_segment_topk(cls.data_ptr(), key.data_ptr(), O, M, keep, sel.data_ptr(), _stream(dev)), "dvq_segment_topk")
     return sel
+
+
+SEGMENT_DIVERSE_MAX_D = 4096       # csrc/diverse.hip: DIV_MAX (M, P and D)
+SEGMENT_DIVERSE_LDS_FLOATS = 40960  # csrc/diverse.hip: DIV_LDS_FLOATS, the 160 KiB one workgroup may hold
+
+
+def segment_diverse_lds_resident(pool: int, n_features: int) -> bool:
+    """True when ``segment_diverse`` keeps the pooled rows in LDS (csrc/diverse.hip: 32 floats of header, one float of state per
+    pool position rounded up to four, the rows at the odd stride D | 1), False when it streams them from global memory every step.
+    The two paths give the same bits."""
+    P, D = int(pool), int(n_features)
+    return 32 + ((P + 3) & ~3) + P * (D | 1) <= SEGMENT_DIVERSE_LDS_FLOATS
+
+
+def segment_diverse(feat: Tensor, pool: Tensor, n_objects: int, n_candidates: int, keep: int, err: Optional[Tensor] = None):
+    """Greedy farthest-point order inside each object's quality pool (dvq_segment_diverse; the definition is in include/dvq.h).
+    feat fp32 [O*M, D] with ``stride(1) == 1`` and any ``stride(0) >= D`` (a column slice or ``vertices.view(B, -1)`` is read in
+    place); pool int64 [O,P] contiguous: distinct candidate indices in rank order (``segment_topk(..., keep=P)``) -> ``(sel int64,
+    rank int32, gap f32)``, each [O,keep]: candidate index, pool position and squared distance to the nearest earlier pick (-1 for
+    pick 0 and for rows that are not finite).  A pool entry outside [0, M) raises RuntimeError unless an ``err`` flag tensor is
+    supplied (then the caller checks it; that object's outputs are -1)."""
+    if not isinstance(feat, Tensor) or not isinstance(pool, Tensor):
+        raise RuntimeError("segment_diverse: feat and pool must be tensors")
+    O, M, keep = int(n_objects), int(n_candidates), int(keep)
+    _f32(feat, "segment_diverse: feat"), _i64(pool, "segment_diverse: pool")
+    if pool.dim() != 2 or pool.shape[0] != O or not pool.is_contiguous():
+        raise RuntimeError(f"segment_diverse: pool must be a contiguous int64 [O,P] with O={O} (got {tuple(pool.shape)})")
+    P = int(pool.shape[1])
+    if O < 0 or not 1 <= keep <= P <= M <= SEGMENT_DIVERSE_MAX_D:
+        raise RuntimeError(f"segment_diverse: need O >= 0 and 1 <= keep <= P <= M <= {SEGMENT_DIVERSE_MAX_D} (got O={O} M={M} P={P} keep={keep})")
+    if feat.dim() != 2 or feat.shape[0] != O * M:
+        raise RuntimeError(f"segment_diverse: feat must be [O*M, D] = [{O * M}, D] (got {tuple(feat.shape)})")
+    D = int(feat.shape[1])
+    if not 1 <= D <= SEGMENT_DIVERSE_MAX_D:
+        raise RuntimeError(f"segment_diverse: need 1 <= D <= {SEGMENT_DIVERSE_MAX_D} (got D={D})")
+    if D > 1 and feat.stride(1) != 1:
+        raise RuntimeError(f"segment_diverse: feat rows must be contiguous (stride(1) == 1, got strides {feat.stride()})")
+    ld = int(feat.stride(0)) if feat.shape[0] > 1 else max(int(feat.stride(0)), D)
+    if ld < D:
+        raise RuntimeError(f"segment_diverse: feat rows overlap (stride(0) = {ld} < D = {D})")
+    if err is not None and (not isinstance(err, Tensor) or err.dtype != torch.int32 or err.numel() != 1):
+        raise RuntimeError("segment_diverse: err must be an int32 tensor of one element (ops.new_err_flag)")
+    dev = _require_gpu(feat, pool, err)
+    lib = _lib.load()
+    sel = torch.empty(O, keep, dtype=torch.int64, device=dev)
+    rank = torch.empty(O, keep, dtype=torch.int32, device=dev)
+    gap = torch.empty(O, keep, dtype=torch.float32, device=dev)
+    own_err = err is None
+    if own_err:
+        err = new_err_flag(dev)
+    with torch.cuda.device(dev):
+        check(lib.dvq_segment_diverse(feat.data_ptr(), ld, D, pool.data_ptr(), O, M, P, keep, sel.data_ptr(), rank.data_ptr(),
+                                      gap.data_ptr(), err.data_ptr(), _stream(dev)), "dvq_segment_diverse")
+    if own_err and int(err.item()) != 0:
+        raise RuntimeError(f"segment_diverse: pool entry out of bounds for {M} candidates")
+    return sel, rank, gap

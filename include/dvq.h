@@ -41,7 +41,7 @@ typedef enum {
  * (struct layouts change between versions). */
 #define DVQ_ABI_VERSION 10
 /* Entry points added since 10 without touching a struct or a signature of it (a compatible extension: bindings of 10 keep
- * working, the version stays): dvq_pixelcnn_sample_ctl, dvq_grasp_scores, dvq_segment_topk. */
+ * working, the version stays): dvq_pixelcnn_sample_ctl, dvq_grasp_scores, dvq_segment_topk, dvq_segment_diverse. */
 int dvq_abi_version(void);
 const char* dvq_last_error(void);
 /* number of visible HIP devices, or -1; does not create a context */
@@ -389,6 +389,28 @@ int dvq_grasp_scores(const float* hand /* [B,V,3] */, const int32_t* faces, cons
  * O >= 0, 1 <= keep <= M <= 4096; anything else is DVQ_EINVAL. */
 int dvq_segment_topk(const int32_t* cls /* [O*M] */, const float* key /* [O*M] */, int64_t O, int M, int keep,
                      int64_t* sel /* [O,keep] */, dvq_stream_t stream);
+/* Diverse selection inside a quality pool: greedy farthest-point (k-centre) order of each object's P best-ranked candidates, the
+ * first `keep` picks written.  One workgroup per object, no workspace; nothing depends on O, on which objects share a call or on
+ * scheduling.  New here: the reference only measures diversity (diverse_grasp/diversity.py:7-15), it does not select for it.
+ * Inputs, per object o: feature rows x_c = feat[(o * M + c) * ld .. + D) of candidates c = 0 .. M-1 (fp32, row stride ld >= D floats);
+ * pool[o, 0 .. P): distinct candidate indices in rank order (dvq_segment_topk with keep = P; duplicates are the caller's business).
+ * Distance d(a, b): eight fp32 partial sums acc[0 .. 7] = +0.0f; for j = 0 .. D-1 ascending: t = a[j] - b[j], acc[j mod 8] =
+ *   acc[j mod 8] + t * t, every operation rounded to fp32 on its own (nothing fused);
+ *   d = ((acc0 + acc1) + (acc2 + acc3)) + ((acc4 + acc5) + (acc6 + acc7)).  d(a, b) == d(b, a) bit for bit.
+ * A pool row is invalid when any of its D features is not finite.
+ * Selection: pick 0 is pool position 0; then mind[i] = d(x_i, x_pick0) for every pool position i.  For r = 1 .. keep-1:
+ *   key(i) = mind[i] for valid, unpicked i whose mind[i] is not NaN, else -1.0f; pick r = the unpicked position of the largest key,
+ *   the lowest position among equals; then mind[i] = d < mind[i] ? d : mind[i] with d = d(x_i, x_pick_r) (a NaN lowers nothing).
+ *   So exact duplicates (key 0) follow every distinct row, and invalid rows come last, in rank order.
+ * Outputs [O,keep]: sel = the candidate index pool[o, pick_r]; rank = the pool position pick_r; gap = the key when picked: the
+ *   squared distance to the nearest earlier pick, -1.0f for pick 0 and for picks whose key was -1 (-1 = not a distance).  Over the
+ *   valid picks gap[1:] is non-increasing and its minimum is the kept set's smallest pairwise distance, bit for bit.
+ * A pool entry outside [0, M) sets bit 0 of *err (device int32, zeroed by the caller) and that object's outputs are all -1; no
+ * feature row of the object is read.
+ * O >= 0, 1 <= keep <= P <= M <= 4096, 1 <= D <= 4096, ld >= D, no null pointer; anything else is DVQ_EINVAL, nothing launched. */
+int dvq_segment_diverse(const float* feat, int64_t ld, int D, const int64_t* pool /* [O*P] */, int64_t O, int M, int P, int keep,
+                        int64_t* sel /* [O,keep] */, int32_t* rank /* [O,keep] */, float* gap /* [O,keep] */, int32_t* err,
+                        dvq_stream_t stream);
 
 /* ------------------------------------------------------------------ all-gather of the generated MANO parameters (multi-GPU)
  * The batch of objects shards contiguously over R ranks (one process per GPU); the only exchange of the path is
