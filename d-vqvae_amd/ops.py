@@ -535,6 +535,9 @@ def mano_forward(packed, betas: Tensor, hand_pose: Tensor, global_orient: Option
     pp, ldp = _rows(_f32(hand_pose, "hand_pose"), "hand_pose")
     if betas.shape[1] != 10 or hand_pose.shape[1] != 45 or hand_pose.shape[0] != B:
         raise RuntimeError("mano_forward: expected betas [B,10] and hand_pose [B,45]")
+    for name, t in (("global_orient", global_orient), ("transl", transl)):
+        if t is not None and tuple(t.shape) != (B, 3):
+            raise RuntimeError(f"mano_forward: expected {name} [B,3], got {tuple(t.shape)}")
     pg = ldg = pt = ldt = 0
     if global_orient is not None:
         pg, ldg = _rows(_f32(global_orient, "global_orient"), "global_orient")
@@ -542,6 +545,8 @@ def mano_forward(packed, betas: Tensor, hand_pose: Tensor, global_orient: Option
         pt, ldt = _rows(_f32(transl, "transl"), "transl")
     verts = torch.empty((B, 3, 778) if channel_major else (B, 778, 3), dtype=torch.float32, device=dev)
     joints = torch.empty(B, 16, 3, dtype=torch.float32, device=dev) if want_joints else None
+    if B == 0:                                              # empty tensors have null data pointers, which the ABI refuses
+        return (verts, joints) if want_joints else verts
     nws = lib.dvq_mano_workspace_bytes(B)
     ws = workspace(nws, dev)
     with torch.cuda.device(dev):

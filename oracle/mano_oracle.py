@@ -8,7 +8,9 @@ That package is not installed in the build image and not vendored by the referen
 reference has no test that pins values at this boundary, so nothing can pin this file numerically.
 It restates the published smplx-style linear-blend-skinning algorithm that package implements
 (SURVEY.md Appendix E): PCA pose -> axis-angle, Rodrigues, shape + pose blend shapes, joint
-regression, kinematic chain, skinning.  Self-consistency checks live in tests/test_mano.py.
+regression, kinematic chain, skinning.  tests/test_mano.py pins it, within 1e-6, to tests/mano_ref.py: a float64 numpy
+restatement of the same appendix whose own self-consistency checks (zero pose, rigid motion, bone lengths, rotations) live
+in that file too.
 
 Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may import this module.
 """
