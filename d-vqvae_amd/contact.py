@@ -72,6 +72,23 @@ def grasp_scores(topology, hand_xyz, obj_xyz, contact_threshold=0.02 ** 2):
     return {"penetration": pen, "n_interior": n_in, "n_contact": n_ct}
 
 
+def refine_translation(topology, hand_xyz, obj_xyz, steps, push=1.0, pull=0.25, min_contact=1, contact_threshold=0.02 ** 2):
+    """Translation push-out from ONE fused kernel per call (ops.grasp_refine; the update rule is in include/dvq.h under
+    dvq_grasp_refine): at most ``steps`` steps of descent on the scores of ``grasp_scores`` with respect to the hand's rigid
+    translation -- object points inside the hand push it out by ``push`` times their mean pull vector, points within the contact
+    threshold outside it pull it closer by ``pull`` times theirs -- and of the iterates 0 .. steps the best under the key of
+    ``select_keys("penetration")`` (``min_contact``), the earliest among equals.  Returns ``offset`` [B,3] f32 (add it to the hand's
+    translation: ``params[:, 58:61]``), ``iter`` [B] i32 (the iterate kept; 0 = the hand as given) and that iterate's ``penetration``,
+    ``n_interior``, ``n_contact``.  ``steps = 0`` gives the scores of ``grasp_scores`` and a zero offset.
+
+    The defaults are a numpy prototype's on a sphere against a sphere and are untuned; the effect on real grasps is NOT measured
+    (no real checkpoint).  Known limit: an object lying deep inside the hand is pulled further in (its nearest-vertex distances
+    shrink that way): the kept iterate is only "not worse under the proxy"."""
+    offset, it, pen, n_in, n_ct = ops.grasp_refine(hand_xyz.contiguous(), topology.faces, topology.vf_off, topology.vf_face, obj_xyz,
+                                                   steps, push, pull, min_contact, contact_threshold)
+    return {"offset": offset, "iter": it, "penetration": pen, "n_interior": n_in, "n_contact": n_ct}
+
+
 SELECT_BY = ("penetration", "log_prob")
 
 

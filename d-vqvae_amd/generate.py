@@ -78,6 +78,13 @@ def build_parser(dataset: str) -> argparse.ArgumentParser:
                         "diverse_pool <= candidates; the JSON gains \"rank\" and \"novelty\"")
     p.add_argument("--diverse_space", choices=list(DIVERSE_SPACES), default="params",
                    help="what --diverse_pool measures distances in: the 61 parameters or the 778 posed vertices")
+    p.add_argument("--refine_steps", type=int, default=0,
+                   help="translation push-out: at most this many steps (<= 64) moving every generated hand out of its object along the "
+                        "penetration proxy's gradient, before any scoring or selection (0 = off); the JSON gains \"refine_offset\" and "
+                        "\"refine_iter\" (and the three scores when --candidates is off); untuned, effect on real grasps not measured")
+    p.add_argument("--refine_push", type=float, default=1.0, help="--refine_steps: step factor on the mean pull vector of the interior points")
+    p.add_argument("--refine_pull", type=float, default=0.25,
+                   help="--refine_steps: step factor on the mean pull vector of the points within 2 cm outside the hand")
     return p
 
 
@@ -92,6 +99,10 @@ def parse_args(dataset: str, argv: Optional[Sequence[str]] = None) -> argparse.N
     if args.diverse_pool and not args.num_grasp <= args.diverse_pool <= args.candidates:
         p.error(f"--diverse_pool must lie between --num_grasp and --candidates (got {args.diverse_pool} for {args.num_grasp} grasps of "
                 f"{args.candidates} candidates)")
+    if not 0 <= args.refine_steps <= ops.GRASP_REFINE_MAX_STEPS:
+        p.error(f"--refine_steps must lie between 0 and {ops.GRASP_REFINE_MAX_STEPS} (got {args.refine_steps})")
+    if not (0.0 <= args.refine_push < float("inf") and 0.0 <= args.refine_pull < float("inf")):
+        p.error(f"--refine_push and --refine_pull must be finite and >= 0 (got {args.refine_push}, {args.refine_pull})")
     return args
 
 
@@ -239,11 +250,14 @@ def plan_calls(point_counts: Sequence[int], num_grasp: int, rows_per_call: int) 
 def _generate_call(net: GenNet, objs: Sequence[torch.Tensor], num_grasp: int, rotate: bool, seed: int,
                    object_indices: Sequence[int], proxies: bool, temperature: float = 1.0, top_k: int = 0,
                    log_prob: bool = False, candidates: int = 0, select_by: str = "penetration",
-                   min_contact: int = 1, diverse_pool: int = 0, diverse_space: str = "params") -> List[Dict[str, object]]:
+                   min_contact: int = 1, diverse_pool: int = 0, diverse_space: str = "params", refine_steps: int = 0,
+                   refine_push: float = 1.0, refine_pull: float = 0.25) -> List[Dict[str, object]]:
     """One batched call: the ``num_grasp`` grasps of each of ``objs`` (all of one point count), row o * num_grasp + g = grasp g
     of object o.  Every step is row-independent and keyed per row, so each object's slice holds the bits of its own
     ``generate_for_object`` call.  With ``candidates`` = M the call generates M rows per object (exactly the grasps of a
-    ``num_grasp = M`` call) and keeps each object's ``num_grasp`` best (_select_call)."""
+    ``num_grasp = M`` call) and keeps each object's ``num_grasp`` best (_select_call).  With ``refine_steps`` every row of the call
+    is first pushed out of its cloud (contact.refine_translation: one kernel), the offsets are added to the translations and MANO is
+    posed again, so that everything after it -- scores, selection, the rows returned -- sees the hands of the parameters written."""
     dev = next(net.parameters()).device
     keep = num_grasp
     G, O = (candidates or num_grasp), len(objs)
@@ -269,12 +283,31 @@ def _generate_call(net: GenNet, objs: Sequence[torch.Tensor], num_grasp: int, ro
     params = ops.assemble61(recon, pos)                                            # obman.py:243-247
     final = net.rh_mano(betas=params[:, :10], global_orient=params[:, 10:13], hand_pose=params[:, 13:58],
                         transl=params[:, 58:61])                                   # obman.py:252-253
+    refined = None
+    if refine_steps:
+        from . import contact
+        topo = _hand_topology(net, final.vertices.shape[1], dev)
+        refined = contact.refine_translation(topo, final.vertices, batch[:, :3].transpose(1, 2), refine_steps, refine_push, refine_pull,
+                                             min_contact)
+        params[:, 58:61] += refined["offset"]                                      # fp32; the hands below are those of these parameters
+        final = net.rh_mano(betas=params[:, :10], global_orient=params[:, 10:13], hand_pose=params[:, 13:58],
+                            transl=params[:, 58:61])
     if candidates:
         return _select_call(net, batch, params, final.vertices, logp, err, O, G, keep, select_by, min_contact, want_logp, proxies,
-                            np.concatenate(Rs), np.concatenate(angles), t, diverse_pool, diverse_space)
-    host = params.cpu().numpy()                                                    # ONE device-to-host copy per call
-    if int(err.item()) != 0:
-        raise RuntimeError("generate_for_objects: object index out of range in transform_clouds")
+                            np.concatenate(Rs), np.concatenate(angles), t, diverse_pool, diverse_space, refined)
+    ref_lists = {}
+    if refined is not None:                                                        # the scores of the hands written, and the one copy
+        scores = contact.grasp_scores(topo, final.vertices, batch[:, :3].transpose(1, 2))
+        names = ["refine_offset", "refine_iter", "penetration", "n_interior", "n_contact"]
+        tensors = {"refine_offset": refined["offset"], "refine_iter": refined["iter"], **scores}
+        host, *rest_h, err_h = _host_copy([params] + [tensors[k] for k in names] + [err])   # ONE device-to-host copy per call
+        if int(err_h[0]) != 0:
+            raise RuntimeError("generate_for_objects: object index out of range in transform_clouds")
+        ref_lists = {k: h.tolist() for k, h in zip(names, rest_h)}
+    else:
+        host = params.cpu().numpy()                                                # ONE device-to-host copy per call
+        if int(err.item()) != 0:
+            raise RuntimeError("generate_for_objects: object index out of range in transform_clouds")
     topo = _hand_topology(net, final.vertices.shape[1], dev) if proxies else None
     # the JSON fields of the whole call as Python lists in ONE pass each (a .tolist() per object costs more than the device work at
     # one grasp per object), then the per-object split
@@ -295,6 +328,9 @@ def _generate_call(net: GenNet, objs: Sequence[torch.Tensor], num_grasp: int, ro
         if proxies:                                                                # per object: the reductions see the loop's shapes
             from . import contact
             extra["proxies"] = contact.grasp_proxies(topo, final.vertices[lo:hi], batch[lo:hi, :3].transpose(1, 2))
+        if refined is not None:
+            extra.update({k: tensors[k][lo:hi] for k in names})
+            extra_json.update({k: ref_lists[k][lo:hi] for k in names})
         outs.append({**extra, "params": p_dev[o], "vertices": v_dev[o],
                      "json": {"recon_params": [[p] for p in p_list[lo:hi]],           # [[61 floats]] per grasp, as the reference
                               "R_list": Rt_list[lo:hi], "trans_list": [trans] * G, "r_list": r_list[lo:hi], **extra_json}})
@@ -316,12 +352,14 @@ def _host_copy(pieces: Sequence[torch.Tensor]) -> List[np.ndarray]:
 def _select_call(net: GenNet, batch: torch.Tensor, params: torch.Tensor, vertices: torch.Tensor, logp: Optional[torch.Tensor],
                  err: torch.Tensor, O: int, M: int, keep: int, select_by: str, min_contact: int, want_logp: bool, proxies: bool,
                  R: np.ndarray, angles: np.ndarray, t: np.ndarray, diverse_pool: int = 0,
-                 diverse_space: str = "params") -> List[Dict[str, object]]:
+                 diverse_space: str = "params", refined: Optional[Dict[str, torch.Tensor]] = None) -> List[Dict[str, object]]:
     """Best-of-M for all the objects of a call together: the candidates' scores (one fused kernel), their keys, each object's
     ``keep`` best (one kernel), one ``index_select`` of the kept rows and one device-to-host copy.  Row o * M + c is candidate c of
     object o; nothing here depends on which objects share the call.  ``diverse_pool`` = P: each object's P best (the same kernel),
     then the ``keep`` most spread-out of them in greedy farthest-point order (``ops.segment_diverse`` over the parameters or the
-    posed vertices, read in place); their pool positions and squared gaps ride along in the one copy."""
+    posed vertices, read in place); their pool positions and squared gaps ride along in the one copy.  ``refined``: the call's
+    rows were pushed out before (contact.refine_translation's dict; ``params`` and ``vertices`` are the refined ones): the kept rows'
+    offsets and iterates ride along too."""
     from . import contact
     dev = params.device
     topo = _hand_topology(net, vertices.shape[1], dev)
@@ -342,13 +380,16 @@ def _select_call(net: GenNet, batch: torch.Tensor, params: torch.Tensor, vertice
     kept_p, kept_v = params.index_select(0, rows), vertices.index_select(0, rows)
     kept_s = {k: v.index_select(0, rows) for k, v in scores.items()}
     names = sorted(kept_s)
-    host = _host_copy([sel] + [kept_p] + [kept_s[k] for k in names] + diverse + [err])  # ONE device-to-host copy per call
+    kept_r = [refined["offset"].index_select(0, rows), refined["iter"].index_select(0, rows)] if refined is not None else []
+    host = _host_copy([sel] + [kept_p] + [kept_s[k] for k in names] + kept_r + diverse + [err])  # ONE device-to-host copy per call
     if int(host[-1][0]) != 0:
         raise RuntimeError("generate_for_objects: object index out of range in transform_clouds")
     sel_h, p_list = host[0], host[1].tolist()
     s_list = {k: h.tolist() for k, h in zip(names, host[2:2 + len(names)])}
+    if refined is not None:
+        off_list, it_list = (h.tolist() for h in host[2 + len(names):4 + len(names)])
     if diverse_pool:
-        rank_h, gap_h, pool_err_h = host[2 + len(names):-1]
+        rank_h, gap_h, pool_err_h = host[2 + len(names) + len(kept_r):-1]
         if int(pool_err_h[0]) != 0:
             raise RuntimeError("generate_for_objects: pool entry out of range in segment_diverse")
         rank_list, gap_list = rank_h.tolist(), gap_h.tolist()
@@ -369,6 +410,9 @@ def _select_call(net: GenNet, batch: torch.Tensor, params: torch.Tensor, vertice
         if diverse_pool:
             extra["rank"], extra["novelty"] = rank[o], gap[o]
             extra_json = {"rank": rank_list[o], "novelty": gap_list[o]}
+        if refined is not None:
+            extra["refine_offset"], extra["refine_iter"] = kept_r[0][lo:hi], kept_r[1][lo:hi]
+            extra_json = {**extra_json, "refine_offset": off_list[lo:hi], "refine_iter": it_list[lo:hi]}
         outs.append({**extra, "params": p_dev[o], "vertices": v_dev[o], "candidate": sel[o],
                      "scores": {k: v[o * M:(o + 1) * M] for k, v in scores.items()},
                      "json": {"recon_params": [[p] for p in p_list[lo:hi]], "R_list": Rt_list[lo:hi], "trans_list": [trans] * keep,
@@ -380,7 +424,8 @@ def _select_call(net: GenNet, batch: torch.Tensor, params: torch.Tensor, vertice
 def generate_for_objects(net: GenNet, objs: Sequence[torch.Tensor], num_grasp: int, rotate: bool, seed: int,
                          object_indices: Sequence[int], proxies: bool = False, rows_per_call: int = 16384, temperature: float = 1.0,
                          top_k: int = 0, log_prob: bool = False, candidates: int = 0, select_by: str = "penetration",
-                         min_contact: int = 1, diverse_pool: int = 0, diverse_space: str = "params") -> List[Dict[str, object]]:
+                         min_contact: int = 1, diverse_pool: int = 0, diverse_space: str = "params", refine_steps: int = 0,
+                         refine_push: float = 1.0, refine_pull: float = 0.25) -> List[Dict[str, object]]:
     """``num_grasp`` grasps for each of ``objs`` ([4,N] tensors) in batched calls that mix objects (plan_calls): one dict per
     object, in the order given, equal to ``generate_for_object(net, objs[i], num_grasp, rotate,
     np.random.default_rng([seed, object_indices[i]]), seed=seed, object_index=object_indices[i], proxies=proxies)`` (and the same
@@ -403,7 +448,16 @@ def generate_for_objects(net: GenNet, objs: Sequence[torch.Tensor], num_grasp: i
     squared distances over the 61 parameters, or over the posed vertices with ``diverse_space="verts"``).  The kept grasps come in
     pick order; the dicts gain ``rank`` (int32 [num_grasp], the position in the ranking) and ``novelty`` (fp32 [num_grasp], the
     squared distance to the nearest earlier pick, -1 for the first), and ``json`` gains "rank" and "novelty" after the scores.
-    ``diverse_pool = 0`` is the call without the keyword."""
+    ``diverse_pool = 0`` is the call without the keyword.
+
+    Translation push-out (``refine_steps`` = K > 0, ``refine_push``, ``refine_pull``): after the posed-MANO pass and before any scoring
+    or selection, ALL rows of a call go through ``contact.refine_translation`` against their clouds (one kernel; ``min_contact`` is
+    its contact class too), ``params[:, 58:61] += offset`` in fp32 and MANO is posed again, so ``vertices`` are the vertices of the
+    parameters returned; best-of-M then ranks the refined candidates.  The dicts gain ``refine_offset`` [num_grasp,3] and
+    ``refine_iter`` [num_grasp] (the iterate kept, 0 = untouched), and so does ``json``; without ``candidates`` the dicts and ``json``
+    also gain ``penetration``, ``n_interior``, ``n_contact``: ``contact.grasp_scores`` of the refined hands.  Everything rides in the
+    call's one device-to-host copy; needs a face list like best-of-M.  Parameters 0 .. 57 are those of the call without it.
+    ``refine_steps = 0`` is the call without the keyword.  The constants are untuned and the effect on real grasps is not measured."""
     if len(object_indices) != len(objs):
         raise RuntimeError("generate_for_objects: one object index per object")
     if diverse_pool:
@@ -424,10 +478,17 @@ def generate_for_objects(net: GenNet, objs: Sequence[torch.Tensor], num_grasp: i
         if select_by not in contact.SELECT_BY:
             raise RuntimeError(f"generate_for_objects: select_by must be one of {contact.SELECT_BY} (got {select_by!r})")
         _hand_faces(net)                                                           # no face list: raise before any work
+    if refine_steps:
+        if not 0 < refine_steps <= ops.GRASP_REFINE_MAX_STEPS:
+            raise RuntimeError(f"generate_for_objects: refine_steps must lie between 0 and {ops.GRASP_REFINE_MAX_STEPS} (got {refine_steps})")
+        if not (0.0 <= refine_push < float("inf") and 0.0 <= refine_pull < float("inf")):
+            raise RuntimeError(f"generate_for_objects: refine_push and refine_pull must be finite and >= 0 (got {refine_push}, {refine_pull})")
+        _hand_faces(net)                                                           # no face list: raise before any work
     out: List[Optional[Dict[str, object]]] = [None] * len(objs)
     for call in plan_calls([o.shape[1] for o in objs], candidates or num_grasp, rows_per_call):
         res = _generate_call(net, [objs[p] for p in call], num_grasp, rotate, seed, [object_indices[p] for p in call], proxies,
-                             temperature, top_k, log_prob, candidates, select_by, min_contact, diverse_pool, diverse_space)
+                             temperature, top_k, log_prob, candidates, select_by, min_contact, diverse_pool, diverse_space, refine_steps,
+                             refine_push, refine_pull)
         for p, r in zip(call, res):
             out[p] = r
     return out
@@ -453,12 +514,15 @@ def main(dataset: str, argv: Optional[Sequence[str]] = None) -> List[str]:
     total_t, total_g = 0.0, 0
     wall0 = time.time()
     rotate = DATASETS[dataset]["rotate"]
-    if args.rows_per_call > 0 or args.candidates:
-        # grouped calls (best-of-M always: --rows_per_call 0 is then one object per call)
+    if args.rows_per_call > 0 or args.candidates or args.refine_steps:
+        # grouped calls (best-of-M and push-out always: --rows_per_call 0 is then one object per call)
         rows_per_call, per_object = max(1, args.rows_per_call), (args.candidates or args.num_grasp)
         selection = dict(candidates=args.candidates, select_by=args.select_by, min_contact=args.min_contact) if args.candidates else {}
         if args.diverse_pool:
             selection.update(diverse_pool=args.diverse_pool, diverse_space=args.diverse_space)
+        if args.refine_steps:
+            selection.update(refine_steps=args.refine_steps, refine_push=args.refine_push, refine_pull=args.refine_pull,
+                             min_contact=args.min_contact)
         # grouped calls: one call's objects at a time, its files written before the next call starts, so the device and the host
         # hold one call's results, not the whole list's
         mine = objs[lo:hi]

@@ -741,6 +741,51 @@ def grasp_scores(hand: Tensor, faces: Tensor, vf_off: Tensor, vf_face: Tensor, o
     return pen, n_in, n_ct
 
 
+GRASP_REFINE_MAX_STEPS = 64        # csrc/grasp_refine.hip: GR_MAX_STEPS
+
+
+def grasp_refine(hand: Tensor, faces: Tensor, vf_off: Tensor, vf_face: Tensor, obj: Tensor, steps: int, push: float = 1.0,
+                 pull: float = 0.25, min_contact: int = 1, contact_threshold: float = 0.02 ** 2):
+    """Translation push-out in one fused kernel (dvq_grasp_refine; the definition is in include/dvq.h): at most ``steps`` steps of
+    descent on the scores of ``grasp_scores`` with respect to the hand's translation.  Returns ``(offset [B,3] f32, iter [B] i32,
+    penetration [B] f32, n_interior [B] i32, n_contact [B] i32)`` of each grasp's best iterate -- add ``offset`` to the hand's
+    translation.  Arguments as ``grasp_scores`` (obj [B,N,3] with any strides, read in place)."""
+    for t, n in ((hand, "hand"), (obj, "obj"), (faces, "faces"), (vf_off, "vf_off"), (vf_face, "vf_face")):
+        if not isinstance(t, Tensor):
+            raise RuntimeError(f"grasp_refine: {n} must be a tensor")
+    _f32(hand, "hand")
+    for t, n in ((faces, "faces"), (vf_off, "vf_off"), (vf_face, "vf_face")):
+        if t.dtype != torch.int32 or not t.is_contiguous():
+            raise RuntimeError(f"grasp_refine: {n} must be contiguous int32")
+    if hand.dim() != 3 or hand.shape[2] != 3 or not hand.is_contiguous():
+        raise RuntimeError("grasp_refine: hand must be contiguous [B,V,3]")
+    po, ob, op, oc = _points(obj, "obj")
+    B, V, N = hand.shape[0], hand.shape[1], obj.shape[1]
+    if obj.shape[0] != B:
+        raise RuntimeError("grasp_refine: batch mismatch")
+    if N < 1 or not 1 <= V <= GRASP_SCORES_MAX_V:
+        raise RuntimeError(f"grasp_refine: need N >= 1 and 1 <= V <= {GRASP_SCORES_MAX_V} (got N={N} V={V})")
+    if faces.dim() != 2 or faces.shape[1] != 3 or vf_off.numel() != V + 1 or vf_face.numel() != faces.numel():
+        raise RuntimeError("grasp_refine: CSR does not match the mesh")
+    steps, min_contact, push, pull = int(steps), int(min_contact), float(push), float(pull)
+    if not 0 <= steps <= GRASP_REFINE_MAX_STEPS:
+        raise RuntimeError(f"grasp_refine: need 0 <= steps <= {GRASP_REFINE_MAX_STEPS} (got {steps})")
+    if not (0.0 <= push < float("inf") and 0.0 <= pull < float("inf")):
+        raise RuntimeError(f"grasp_refine: push and pull must be finite and >= 0 (got {push}, {pull})")
+    dev = _require_gpu(hand, obj, faces, vf_off, vf_face)
+    lib = _lib.load()
+    offset = torch.empty(B, 3, dtype=torch.float32, device=dev)
+    it = torch.empty(B, dtype=torch.int32, device=dev)
+    pen = torch.empty(B, dtype=torch.float32, device=dev)
+    n_in = torch.empty(B, dtype=torch.int32, device=dev)
+    n_ct = torch.empty(B, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        check(lib.dvq_grasp_refine(hand.data_ptr(), faces.data_ptr(), vf_off.data_ptr(), vf_face.data_ptr(), V, po, ob, op, oc, B, N,
+                                   float(contact_threshold), steps, push, pull, min_contact, offset.data_ptr(), it.data_ptr(),
+                                   pen.data_ptr(), n_in.data_ptr(), n_ct.data_ptr(), _stream(dev)), "dvq_grasp_refine")
+    return offset, it, pen, n_in, n_ct
+
+
 def segment_topk(cls: Tensor, key: Tensor, n_objects: int, n_candidates: int, keep: int) -> Tensor:
     """cls int32 [O*M], key f32 [O*M] (candidate c of object o at o * M + c) -> int64 [O,keep]: each object's ``keep`` best
     candidate indices, best first, by (cls, key, index) with NaN keys last in their class and -0.0 == +0.0 (dvq_segment_topk)."""

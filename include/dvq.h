@@ -41,7 +41,8 @@ typedef enum {
  * (struct layouts change between versions). */
 #define DVQ_ABI_VERSION 10
 /* Entry points added since 10 without touching a struct or a signature of it (a compatible extension: bindings of 10 keep
- * working, the version stays): dvq_pixelcnn_sample_ctl, dvq_grasp_scores, dvq_segment_topk, dvq_segment_diverse. */
+ * working, the version stays): dvq_pixelcnn_sample_ctl, dvq_grasp_scores, dvq_segment_topk, dvq_segment_diverse,
+ * dvq_grasp_refine. */
 int dvq_abi_version(void);
 const char* dvq_last_error(void);
 /* number of visible HIP devices, or -1; does not create a context */
@@ -381,6 +382,40 @@ int dvq_interior(const float* normals /* [B,V,3] */, const float* hand /* [B,V,3
 int dvq_grasp_scores(const float* hand /* [B,V,3] */, const int32_t* faces, const int32_t* vf_off, const int32_t* vf_face, int V,
                      const float* obj, int64_t obj_batch_stride, int64_t obj_point_stride, int64_t obj_coord_stride,
                      int64_t B, int N, float contact_threshold, float* penetration /* [B] */, int32_t* n_interior /* [B] */,
+                     int32_t* n_contact /* [B] */, dvq_stream_t stream);
+/* Translation push-out of grasps: at most `steps` steps of descent on the scores above with respect to the hand's rigid translation,
+ * in ONE kernel, one workgroup of 256 threads per grasp; the best iterate is reported.  New here: the reference's TTT_loss
+ * (utils/loss.py:144-167) is what the scores mirror, but the reference does not descend on it at generation time.  A translation
+ * changes no vertex normal and is added to every vertex (dvq_mano_forward), so no MANO backward pass is involved: the caller adds
+ * `offset` to the hand's transl.  The effect on real grasps is NOT MEASURED (no real checkpoint was available); the update rule's
+ * constants are a prototype's.  Inputs as dvq_grasp_scores (hand [B,V,3] contiguous, the topology, obj with strides in floats: a
+ * channel-first cloud is read in place) plus steps, push, pull, min_contact.  The hand copy never moves: the translation is taken
+ * from the object points.  Normals are computed once per grasp.
+ * Per grasp, with t = (+0, +0, +0), for k = 0 .. steps:
+ *   1. o'_p = obj_p - t per component (fp32); at k = 0 this is obj_p bit for bit.
+ *   2. normals, d_p, j_p, inside_p, term_p exactly as dvq_grasp_scores defines them, on o'.
+ *   3. g_p = o'_p - hand[j_p] per component; near_p = !inside_p && d_p < contact_threshold.
+ *   4. eight sums, each in the fixed order of dvq_grasp_scores (256 strided partial sums from +0.0f in ascending p, then the tree
+ *      s = 128 .. 1): pen = sum of term_p; S_in[c] = sum of (inside_p ? g_p[c] : +0.0f) and S_nr[c] = sum of (near_p ? g_p[c] : +0.0f)
+ *      for c = 0, 1, 2; the integer counts n_in = #inside, n_ct = #(d < contact_threshold), n_nr = #near.
+ *   5. key (cls, pen): cls = 2 if pen is NaN, else 1 if n_ct < min_contact, else 0 (the order of the host's select_keys by
+ *      penetration).  Iterate 0 starts as the best; iterate k becomes the best iff cls_k < cls_best, or cls_k == cls_best and
+ *      pen_k < pen_best (strictly: among equal keys the earliest iterate is kept; an iterate of class 2 never replaces anything).
+ *   6. if k == steps, stop.  Otherwise step[c] = +0.0f; if n_in > 0: step[c] = step[c] + push * (S_in[c] / (float)n_in); if n_nr > 0:
+ *      step[c] = step[c] + pull * (S_nr[c] / (float)n_nr); t[c] = t[c] + step[c].  Every operation is rounded to fp32 on its own
+ *      (nothing fused), the division is IEEE.  The loop also ends when pen is NaN or all three step[c] == 0 (no later iterate
+ *      could become the best).
+ * Outputs: offset [B,3] = the best iterate's t; iter [B] = its k; penetration / n_interior / n_contact [B] = its pen, n_in, n_ct.
+ * With steps = 0: the three scores are the bits of dvq_grasp_scores, offset = 0, iter = 0.  A grasp's result does not depend on B
+ * or on its row.  Interior points push the hand along the mean of their g (out of the object), near points pull it along theirs
+ * (towards the surface); an object lying deep inside the hand is pulled further in, since its nearest-vertex distances shrink that
+ * way: the kept iterate is only "not worse under the proxy".
+ * B >= 0, N >= 1, 1 <= V <= 2048, 0 <= steps <= 64, push and pull finite and >= 0, no null pointer; anything else is DVQ_EINVAL,
+ * nothing launched. */
+int dvq_grasp_refine(const float* hand /* [B,V,3] */, const int32_t* faces, const int32_t* vf_off, const int32_t* vf_face, int V,
+                     const float* obj, int64_t obj_batch_stride, int64_t obj_point_stride, int64_t obj_coord_stride,
+                     int64_t B, int N, float contact_threshold, int steps, float push, float pull, int min_contact,
+                     float* offset /* [B,3] */, int32_t* iter /* [B] */, float* penetration /* [B] */, int32_t* n_interior /* [B] */,
                      int32_t* n_contact /* [B] */, dvq_stream_t stream);
 /* Per-object selection: cls, key [O*M] (candidate c of object o at o * M + c) -> sel [O,keep]: the candidate indices (0 .. M-1) of
  * each object's keep best candidates, best first.  Candidate a ranks before b iff (cls, key, index) is smaller: cls as signed
