@@ -24,6 +24,7 @@ from .network.gen_net import GenNet
 CANONICAL_OFFSET = (-0.0793, 0.0208, -0.6924)       # gen_diverse_grasp_ho3d.py:221
 
 DIVERSE_SPACES = ("params", "verts")                 # --diverse_space: squared distances over [61] or [778 * 3]
+DIVERSITY_ITERS = 100                                # --diversity: the Lloyd iterations allowed (ops.segment_kmeans)
 
 DATASETS = {                                         # grasps per object, random rotation per grasp
     "obman": dict(num_grasp=1, rotate=False),        # gen_diverse_grasp_obman.py:233
@@ -82,6 +83,11 @@ def build_parser(dataset: str) -> argparse.ArgumentParser:
                    help="translation push-out: at most this many steps (<= 64) moving every generated hand out of its object along the "
                         "penetration proxy's gradient, before any scoring or selection (0 = off); the JSON gains \"refine_offset\" and "
                         "\"refine_iter\" (and the three scores when --candidates is off); untuned, effect on real grasps not measured")
+    p.add_argument("--diversity", type=int, default=0,
+                   help="the reference's diversity statistic of the grasps kept, on the device: k-means with this many clusters (the "
+                        "paper uses 20; <= num_grasp and <= 64) over each object's [num_grasp,61] parameters, one deterministic run "
+                        "from evenly spaced starting rows; 0 = off; every JSON gains \"diversity\" (clusters, entropy, mean_dist, "
+                        "iters, counts) and the run writes the pooled statistic of all its grasps to diversity.json")
     p.add_argument("--refine_push", type=float, default=1.0, help="--refine_steps: step factor on the mean pull vector of the interior points")
     p.add_argument("--refine_pull", type=float, default=0.25,
                    help="--refine_steps: step factor on the mean pull vector of the points within 2 cm outside the hand")
@@ -99,6 +105,9 @@ def parse_args(dataset: str, argv: Optional[Sequence[str]] = None) -> argparse.N
     if args.diverse_pool and not args.num_grasp <= args.diverse_pool <= args.candidates:
         p.error(f"--diverse_pool must lie between --num_grasp and --candidates (got {args.diverse_pool} for {args.num_grasp} grasps of "
                 f"{args.candidates} candidates)")
+    if not 0 <= args.diversity <= min(args.num_grasp, ops.SEGMENT_KMEANS_MAX_K):
+        p.error(f"--diversity must lie between 0 and min(--num_grasp, {ops.SEGMENT_KMEANS_MAX_K}) (got {args.diversity} for "
+                f"{args.num_grasp} grasps)")
     if not 0 <= args.refine_steps <= ops.GRASP_REFINE_MAX_STEPS:
         p.error(f"--refine_steps must lie between 0 and {ops.GRASP_REFINE_MAX_STEPS} (got {args.refine_steps})")
     if not (0.0 <= args.refine_push < float("inf") and 0.0 <= args.refine_pull < float("inf")):
@@ -251,13 +260,15 @@ def _generate_call(net: GenNet, objs: Sequence[torch.Tensor], num_grasp: int, ro
                    object_indices: Sequence[int], proxies: bool, temperature: float = 1.0, top_k: int = 0,
                    log_prob: bool = False, candidates: int = 0, select_by: str = "penetration",
                    min_contact: int = 1, diverse_pool: int = 0, diverse_space: str = "params", refine_steps: int = 0,
-                   refine_push: float = 1.0, refine_pull: float = 0.25) -> List[Dict[str, object]]:
+                   refine_push: float = 1.0, refine_pull: float = 0.25, diversity: int = 0) -> List[Dict[str, object]]:
     """One batched call: the ``num_grasp`` grasps of each of ``objs`` (all of one point count), row o * num_grasp + g = grasp g
     of object o.  Every step is row-independent and keyed per row, so each object's slice holds the bits of its own
     ``generate_for_object`` call.  With ``candidates`` = M the call generates M rows per object (exactly the grasps of a
     ``num_grasp = M`` call) and keeps each object's ``num_grasp`` best (_select_call).  With ``refine_steps`` every row of the call
     is first pushed out of its cloud (contact.refine_translation: one kernel), the offsets are added to the translations and MANO is
-    posed again, so that everything after it -- scores, selection, the rows returned -- sees the hands of the parameters written."""
+    posed again, so that everything after it -- scores, selection, the rows returned -- sees the hands of the parameters written.
+    With ``diversity`` = K the kept parameters of every object go through one ``ops.segment_kmeans`` (one segment per object) and its
+    counts and distances ride in the call's one device-to-host copy (_diversity_launch / _diversity_dicts)."""
     dev = next(net.parameters()).device
     keep = num_grasp
     G, O = (candidates or num_grasp), len(objs)
@@ -294,16 +305,22 @@ def _generate_call(net: GenNet, objs: Sequence[torch.Tensor], num_grasp: int, ro
                             transl=params[:, 58:61])
     if candidates:
         return _select_call(net, batch, params, final.vertices, logp, err, O, G, keep, select_by, min_contact, want_logp, proxies,
-                            np.concatenate(Rs), np.concatenate(angles), t, diverse_pool, diverse_space, refined)
+                            np.concatenate(Rs), np.concatenate(angles), t, diverse_pool, diverse_space, refined, diversity)
     ref_lists = {}
+    div = _diversity_launch(params, O, G, diversity) if diversity else []
     if refined is not None:                                                        # the scores of the hands written, and the one copy
         scores = contact.grasp_scores(topo, final.vertices, batch[:, :3].transpose(1, 2))
         names = ["refine_offset", "refine_iter", "penetration", "n_interior", "n_contact"]
         tensors = {"refine_offset": refined["offset"], "refine_iter": refined["iter"], **scores}
-        host, *rest_h, err_h = _host_copy([params] + [tensors[k] for k in names] + [err])   # ONE device-to-host copy per call
+        host, *rest_h, err_h = _host_copy([params] + [tensors[k] for k in names] + div + [err])   # ONE device-to-host copy per call
         if int(err_h[0]) != 0:
             raise RuntimeError("generate_for_objects: object index out of range in transform_clouds")
         ref_lists = {k: h.tolist() for k, h in zip(names, rest_h)}
+        div_h = rest_h[len(names):]
+    elif div:
+        host, *div_h, err_h = _host_copy([params] + div + [err])                   # ONE device-to-host copy per call
+        if int(err_h[0]) != 0:
+            raise RuntimeError("generate_for_objects: object index out of range in transform_clouds")
     else:
         host = params.cpu().numpy()                                                # ONE device-to-host copy per call
         if int(err.item()) != 0:
@@ -318,6 +335,7 @@ def _generate_call(net: GenNet, objs: Sequence[torch.Tensor], num_grasp: int, ro
     trans = t.reshape(3, 1).tolist()
     p_dev, v_dev = params.split(G), final.vertices.split(G)
     lp_list = logp.cpu().numpy().tolist() if log_prob else None
+    div_dicts = _diversity_dicts(diversity, div_h) if diversity else None
     outs = []
     for o in range(O):
         lo, hi = o * G, (o + 1) * G
@@ -331,6 +349,8 @@ def _generate_call(net: GenNet, objs: Sequence[torch.Tensor], num_grasp: int, ro
         if refined is not None:
             extra.update({k: tensors[k][lo:hi] for k in names})
             extra_json.update({k: ref_lists[k][lo:hi] for k in names})
+        if diversity:
+            extra["diversity"] = extra_json["diversity"] = div_dicts[o]
         outs.append({**extra, "params": p_dev[o], "vertices": v_dev[o],
                      "json": {"recon_params": [[p] for p in p_list[lo:hi]],           # [[61 floats]] per grasp, as the reference
                               "R_list": Rt_list[lo:hi], "trans_list": [trans] * G, "r_list": r_list[lo:hi], **extra_json}})
@@ -349,17 +369,40 @@ def _host_copy(pieces: Sequence[torch.Tensor]) -> List[np.ndarray]:
     return out
 
 
+def _diversity_launch(kept: torch.Tensor, O: int, keep: int, clusters: int) -> List[torch.Tensor]:
+    """``--diversity``: one ``ops.segment_kmeans`` over the call's kept parameters [O*keep,61], one segment per object, from evenly
+    spaced starting rows; the device tensors whose host copies _diversity_dicts reads (counts, dist, iters_used, the error flag)."""
+    from . import diversity as dv
+    bad = ops.new_err_flag(kept.device)
+    _, counts, _, dist, used = ops.segment_kmeans(kept, dv.kmeans_init(O, keep, clusters, "spaced", device=kept.device), O, keep,
+                                                  DIVERSITY_ITERS, err=bad)
+    return [counts, dist, used, bad]
+
+
+def _diversity_dicts(clusters: int, host: Sequence[np.ndarray]) -> List[Dict[str, object]]:
+    """The "diversity" entry of every object of a call from the host copies of _diversity_launch's tensors: float64 on the host, per
+    object, so that an object's entry does not depend on which objects share the call."""
+    from . import diversity as dv
+    counts, dist, used, bad = host
+    if int(bad[0]) != 0:
+        raise RuntimeError("generate_for_objects: diversity: a starting row of the k-means is not finite")
+    return [{k: d[k] for k in ("clusters", "entropy", "mean_dist", "iters", "counts")}
+            for d in dv.segment_statistics(clusters, counts, dist, used)]
+
+
 def _select_call(net: GenNet, batch: torch.Tensor, params: torch.Tensor, vertices: torch.Tensor, logp: Optional[torch.Tensor],
                  err: torch.Tensor, O: int, M: int, keep: int, select_by: str, min_contact: int, want_logp: bool, proxies: bool,
                  R: np.ndarray, angles: np.ndarray, t: np.ndarray, diverse_pool: int = 0,
-                 diverse_space: str = "params", refined: Optional[Dict[str, torch.Tensor]] = None) -> List[Dict[str, object]]:
+                 diverse_space: str = "params", refined: Optional[Dict[str, torch.Tensor]] = None,
+                 diversity: int = 0) -> List[Dict[str, object]]:
     """Best-of-M for all the objects of a call together: the candidates' scores (one fused kernel), their keys, each object's
     ``keep`` best (one kernel), one ``index_select`` of the kept rows and one device-to-host copy.  Row o * M + c is candidate c of
     object o; nothing here depends on which objects share the call.  ``diverse_pool`` = P: each object's P best (the same kernel),
     then the ``keep`` most spread-out of them in greedy farthest-point order (``ops.segment_diverse`` over the parameters or the
     posed vertices, read in place); their pool positions and squared gaps ride along in the one copy.  ``refined``: the call's
     rows were pushed out before (contact.refine_translation's dict; ``params`` and ``vertices`` are the refined ones): the kept rows'
-    offsets and iterates ride along too."""
+    offsets and iterates ride along too.  ``diversity``: the k-means statistic of the kept parameters (_diversity_launch) rides along
+    as well."""
     from . import contact
     dev = params.device
     topo = _hand_topology(net, vertices.shape[1], dev)
@@ -381,7 +424,8 @@ def _select_call(net: GenNet, batch: torch.Tensor, params: torch.Tensor, vertice
     kept_s = {k: v.index_select(0, rows) for k, v in scores.items()}
     names = sorted(kept_s)
     kept_r = [refined["offset"].index_select(0, rows), refined["iter"].index_select(0, rows)] if refined is not None else []
-    host = _host_copy([sel] + [kept_p] + [kept_s[k] for k in names] + kept_r + diverse + [err])  # ONE device-to-host copy per call
+    div = _diversity_launch(kept_p, O, keep, diversity) if diversity else []
+    host = _host_copy([sel] + [kept_p] + [kept_s[k] for k in names] + kept_r + diverse + div + [err])  # ONE device-to-host copy per call
     if int(host[-1][0]) != 0:
         raise RuntimeError("generate_for_objects: object index out of range in transform_clouds")
     sel_h, p_list = host[0], host[1].tolist()
@@ -389,10 +433,12 @@ def _select_call(net: GenNet, batch: torch.Tensor, params: torch.Tensor, vertice
     if refined is not None:
         off_list, it_list = (h.tolist() for h in host[2 + len(names):4 + len(names)])
     if diverse_pool:
-        rank_h, gap_h, pool_err_h = host[2 + len(names) + len(kept_r):-1]
+        at = 2 + len(names) + len(kept_r)
+        rank_h, gap_h, pool_err_h = host[at:at + 3]
         if int(pool_err_h[0]) != 0:
             raise RuntimeError("generate_for_objects: pool entry out of range in segment_diverse")
         rank_list, gap_list = rank_h.tolist(), gap_h.tolist()
+    div_dicts = _diversity_dicts(diversity, host[-5:-1]) if diversity else None
     rows_h = (sel_h + np.arange(O)[:, None] * M).reshape(-1)
     Rt_list = np.concatenate([R[rows_h], np.broadcast_to(t.reshape(1, 3, 1), (O * keep, 3, 1))], axis=2).tolist()
     r_list = angles[rows_h].tolist()
@@ -413,6 +459,9 @@ def _select_call(net: GenNet, batch: torch.Tensor, params: torch.Tensor, vertice
         if refined is not None:
             extra["refine_offset"], extra["refine_iter"] = kept_r[0][lo:hi], kept_r[1][lo:hi]
             extra_json = {**extra_json, "refine_offset": off_list[lo:hi], "refine_iter": it_list[lo:hi]}
+        if diversity:
+            extra["diversity"] = div_dicts[o]
+            extra_json = {**extra_json, "diversity": div_dicts[o]}
         outs.append({**extra, "params": p_dev[o], "vertices": v_dev[o], "candidate": sel[o],
                      "scores": {k: v[o * M:(o + 1) * M] for k, v in scores.items()},
                      "json": {"recon_params": [[p] for p in p_list[lo:hi]], "R_list": Rt_list[lo:hi], "trans_list": [trans] * keep,
@@ -425,7 +474,7 @@ def generate_for_objects(net: GenNet, objs: Sequence[torch.Tensor], num_grasp: i
                          object_indices: Sequence[int], proxies: bool = False, rows_per_call: int = 16384, temperature: float = 1.0,
                          top_k: int = 0, log_prob: bool = False, candidates: int = 0, select_by: str = "penetration",
                          min_contact: int = 1, diverse_pool: int = 0, diverse_space: str = "params", refine_steps: int = 0,
-                         refine_push: float = 1.0, refine_pull: float = 0.25) -> List[Dict[str, object]]:
+                         refine_push: float = 1.0, refine_pull: float = 0.25, diversity: int = 0) -> List[Dict[str, object]]:
     """``num_grasp`` grasps for each of ``objs`` ([4,N] tensors) in batched calls that mix objects (plan_calls): one dict per
     object, in the order given, equal to ``generate_for_object(net, objs[i], num_grasp, rotate,
     np.random.default_rng([seed, object_indices[i]]), seed=seed, object_index=object_indices[i], proxies=proxies)`` (and the same
@@ -457,7 +506,14 @@ def generate_for_objects(net: GenNet, objs: Sequence[torch.Tensor], num_grasp: i
     ``refine_iter`` [num_grasp] (the iterate kept, 0 = untouched), and so does ``json``; without ``candidates`` the dicts and ``json``
     also gain ``penetration``, ``n_interior``, ``n_contact``: ``contact.grasp_scores`` of the refined hands.  Everything rides in the
     call's one device-to-host copy; needs a face list like best-of-M.  Parameters 0 .. 57 are those of the call without it.
-    ``refine_steps = 0`` is the call without the keyword.  The constants are untuned and the effect on real grasps is not measured."""
+    ``refine_steps = 0`` is the call without the keyword.  The constants are untuned and the effect on real grasps is not measured.
+
+    Diversity statistic (``diversity`` = K, 1 <= K <= min(``num_grasp``, 64)): after selection and push-out the kept [num_grasp,61]
+    parameters of every object of a call go through ONE ``ops.segment_kmeans`` (one segment per object, K clusters, evenly spaced
+    starting rows, at most 100 iterations); counts and distances ride in the call's one device-to-host copy and the two floats are
+    computed per object on the host (``diversity.kmeans_statistics``).  Each dict and each ``json`` gains ``"diversity"``: a dict of
+    clusters, entropy, mean_dist, iters and counts -- one deterministic run, not scipy's best of 20 random starts
+    (``diversity.diversity``).  ``diversity = 0`` is the call without the keyword."""
     if len(object_indices) != len(objs):
         raise RuntimeError("generate_for_objects: one object index per object")
     if diverse_pool:
@@ -478,6 +534,9 @@ def generate_for_objects(net: GenNet, objs: Sequence[torch.Tensor], num_grasp: i
         if select_by not in contact.SELECT_BY:
             raise RuntimeError(f"generate_for_objects: select_by must be one of {contact.SELECT_BY} (got {select_by!r})")
         _hand_faces(net)                                                           # no face list: raise before any work
+    if diversity and not 0 < diversity <= min(num_grasp, ops.SEGMENT_KMEANS_MAX_K):
+        raise RuntimeError(f"generate_for_objects: diversity must lie between 0 and min(num_grasp, {ops.SEGMENT_KMEANS_MAX_K}) "
+                           f"(got {diversity} for {num_grasp} grasps)")
     if refine_steps:
         if not 0 < refine_steps <= ops.GRASP_REFINE_MAX_STEPS:
             raise RuntimeError(f"generate_for_objects: refine_steps must lie between 0 and {ops.GRASP_REFINE_MAX_STEPS} (got {refine_steps})")
@@ -488,7 +547,7 @@ def generate_for_objects(net: GenNet, objs: Sequence[torch.Tensor], num_grasp: i
     for call in plan_calls([o.shape[1] for o in objs], candidates or num_grasp, rows_per_call):
         res = _generate_call(net, [objs[p] for p in call], num_grasp, rotate, seed, [object_indices[p] for p in call], proxies,
                              temperature, top_k, log_prob, candidates, select_by, min_contact, diverse_pool, diverse_space, refine_steps,
-                             refine_push, refine_pull)
+                             refine_push, refine_pull, diversity)
         for p, r in zip(call, res):
             out[p] = r
     return out
@@ -514,8 +573,11 @@ def main(dataset: str, argv: Optional[Sequence[str]] = None) -> List[str]:
     total_t, total_g = 0.0, 0
     wall0 = time.time()
     rotate = DATASETS[dataset]["rotate"]
-    if args.rows_per_call > 0 or args.candidates or args.refine_steps:
-        # grouped calls (best-of-M and push-out always: --rows_per_call 0 is then one object per call)
+    if args.diversity and (hi - lo) * args.num_grasp > ops.SEGMENT_KMEANS_MAX_M:
+        raise RuntimeError(f"--diversity: the pooled statistic takes at most {ops.SEGMENT_KMEANS_MAX_M} grasps per rank "
+                           f"(got {(hi - lo) * args.num_grasp})")
+    if args.rows_per_call > 0 or args.candidates or args.refine_steps or args.diversity:
+        # grouped calls (best-of-M, push-out and the diversity statistic always: --rows_per_call 0 is then one object per call)
         rows_per_call, per_object = max(1, args.rows_per_call), (args.candidates or args.num_grasp)
         selection = dict(candidates=args.candidates, select_by=args.select_by, min_contact=args.min_contact) if args.candidates else {}
         if args.diverse_pool:
@@ -523,6 +585,9 @@ def main(dataset: str, argv: Optional[Sequence[str]] = None) -> List[str]:
         if args.refine_steps:
             selection.update(refine_steps=args.refine_steps, refine_push=args.refine_push, refine_pull=args.refine_pull,
                              min_contact=args.min_contact)
+        if args.diversity:
+            selection.update(diversity=args.diversity)
+        kept: Dict[int, np.ndarray] = {}                                           # --diversity: every object's kept parameters, on the host
         # grouped calls: one call's objects at a time, its files written before the next call starts, so the device and the host
         # hold one call's results, not the whole list's
         mine = objs[lo:hi]
@@ -543,8 +608,21 @@ def main(dataset: str, argv: Optional[Sequence[str]] = None) -> List[str]:
                 paths[p] = os.path.join(args.out_dir, f"obj_id_{mine[p][0]}.json")
                 with open(paths[p], "w") as f:
                     json.dump(out["json"], f)
+                if args.diversity:
+                    kept[p] = np.asarray(out["json"]["recon_params"], dtype=np.float32).reshape(args.num_grasp, -1)
             del outs, out
         written = [paths[p] for p in sorted(paths)]                                # object order, whatever the grouping
+        if args.diversity and kept:
+            # the pooled statistic of all of this rank's kept grasps in object order: one segment, uploaded once
+            from . import diversity as dv
+            pooled = torch.from_numpy(np.concatenate([kept[p] for p in sorted(kept)])).to(device)
+            stat = dv.device_diversity(pooled, 1, pooled.shape[0], cls_num=args.diversity, iters=DIVERSITY_ITERS)[0]
+            name = "diversity.json" if world == 1 else f"diversity_rank{rank}.json"
+            with open(os.path.join(args.out_dir, name), "w") as f:
+                json.dump({**{k: stat[k] for k in ("clusters", "entropy", "mean_dist", "iters", "counts")},
+                           "grasps": int(pooled.shape[0])}, f)
+            print(f"rank {rank}: diversity of {pooled.shape[0]} grasps in {stat['clusters']} clusters: entropy {stat['entropy']:.4f}, "
+                  f"mean distance {stat['mean_dist']:.4f} ({stat['iters']} iterations)")
     else:
         for gi, (name, obj) in enumerate(objs[lo:hi], start=lo):                   # --rows_per_call 0: one call per object
             torch.cuda.synchronize(device)

@@ -861,3 +861,57 @@ def segment_diverse(feat: Tensor, pool: Tensor, n_objects: int, n_candidates: in
     if own_err and int(err.item()) != 0:
         raise RuntimeError(f"segment_diverse: pool entry out of bounds for {M} candidates")
     return sel, rank, gap
+
+
+SEGMENT_KMEANS_MAX_M = 262144      # csrc/kmeans.hip: KM_MAX_M
+SEGMENT_KMEANS_MAX_K = 64          # csrc/kmeans.hip: KM_MAX_K
+SEGMENT_KMEANS_MAX_D = 64          # csrc/kmeans.hip: KM_MAX_D
+
+
+def segment_kmeans(feat: Tensor, init: Tensor, n_objects: int, n_rows: int, iters: int, err: Optional[Tensor] = None):
+    """Lloyd's k-means inside each segment of ``n_rows`` rows (dvq_segment_kmeans; the definition is in include/dvq.h): ONE
+    deterministic run from the starting rows ``init``, one workgroup per segment, one launch.  feat fp32 [O*M, D] with
+    ``stride(1) == 1`` and any ``stride(0) >= D`` (a column slice is read in place), D <= 64 (vertex space is out of scope);
+    init int64 [O,k] contiguous: distinct positions of valid rows inside each segment, k <= 64 -> ``(centres f32 [O,k,D], counts
+    int32 [O,k], assign int32 [O*M], dist f32 [O*M], iters_used int32 [O])``; rows that are not finite get assign -1 and dist NaN.
+    A bad ``init`` (out of range, a duplicate, a row that is not finite) raises RuntimeError unless an ``err`` flag tensor is
+    supplied (then the caller checks it; that segment's outputs are -1 / NaN)."""
+    if not isinstance(feat, Tensor) or not isinstance(init, Tensor):
+        raise RuntimeError("segment_kmeans: feat and init must be tensors")
+    O, M, iters = int(n_objects), int(n_rows), int(iters)
+    _f32(feat, "segment_kmeans: feat"), _i64(init, "segment_kmeans: init")
+    if init.dim() != 2 or init.shape[0] != O or not init.is_contiguous():
+        raise RuntimeError(f"segment_kmeans: init must be a contiguous int64 [O,k] with O={O} (got {tuple(init.shape)})")
+    k = int(init.shape[1])
+    if O < 0 or iters < 0 or not 1 <= k <= SEGMENT_KMEANS_MAX_K or not k <= M <= SEGMENT_KMEANS_MAX_M:
+        raise RuntimeError(f"segment_kmeans: need O >= 0, iters >= 0, 1 <= k <= {SEGMENT_KMEANS_MAX_K} and k <= M <= {SEGMENT_KMEANS_MAX_M} "
+                           f"(got O={O} M={M} k={k} iters={iters})")
+    if feat.dim() != 2 or feat.shape[0] != O * M:
+        raise RuntimeError(f"segment_kmeans: feat must be [O*M, D] = [{O * M}, D] (got {tuple(feat.shape)})")
+    D = int(feat.shape[1])
+    if not 1 <= D <= SEGMENT_KMEANS_MAX_D:
+        raise RuntimeError(f"segment_kmeans: need 1 <= D <= {SEGMENT_KMEANS_MAX_D} (got D={D}; vertex space is out of scope)")
+    if D > 1 and feat.stride(1) != 1:
+        raise RuntimeError(f"segment_kmeans: feat rows must be contiguous (stride(1) == 1, got strides {feat.stride()})")
+    ld = int(feat.stride(0)) if feat.shape[0] > 1 else max(int(feat.stride(0)), D)
+    if ld < D:
+        raise RuntimeError(f"segment_kmeans: feat rows overlap (stride(0) = {ld} < D = {D})")
+    if err is not None and (not isinstance(err, Tensor) or err.dtype != torch.int32 or err.numel() != 1):
+        raise RuntimeError("segment_kmeans: err must be an int32 tensor of one element (ops.new_err_flag)")
+    dev = _require_gpu(feat, init, err)
+    lib = _lib.load()
+    centres = torch.empty(O, k, D, dtype=torch.float32, device=dev)
+    counts = torch.empty(O, k, dtype=torch.int32, device=dev)
+    assign = torch.empty(O * M, dtype=torch.int32, device=dev)
+    dist = torch.empty(O * M, dtype=torch.float32, device=dev)
+    used = torch.empty(O, dtype=torch.int32, device=dev)
+    own_err = err is None
+    if own_err:
+        err = new_err_flag(dev)
+    with torch.cuda.device(dev):
+        check(lib.dvq_segment_kmeans(feat.data_ptr(), ld, D, init.data_ptr(), O, M, k, iters, centres.data_ptr(), counts.data_ptr(),
+                                     assign.data_ptr(), dist.data_ptr(), used.data_ptr(), err.data_ptr(), _stream(dev)),
+              "dvq_segment_kmeans")
+    if own_err and int(err.item()) != 0:
+        raise RuntimeError(f"segment_kmeans: init entry out of bounds for {M} rows, repeated, or the position of a row that is not finite")
+    return centres, counts, assign, dist, used

@@ -42,7 +42,7 @@ typedef enum {
 #define DVQ_ABI_VERSION 10
 /* Entry points added since 10 without touching a struct or a signature of it (a compatible extension: bindings of 10 keep
  * working, the version stays): dvq_pixelcnn_sample_ctl, dvq_grasp_scores, dvq_segment_topk, dvq_segment_diverse,
- * dvq_grasp_refine. */
+ * dvq_grasp_refine, dvq_segment_kmeans. */
 int dvq_abi_version(void);
 const char* dvq_last_error(void);
 /* number of visible HIP devices, or -1; does not create a context */
@@ -446,6 +446,32 @@ int dvq_segment_topk(const int32_t* cls /* [O*M] */, const float* key /* [O*M] *
 int dvq_segment_diverse(const float* feat, int64_t ld, int D, const int64_t* pool /* [O*P] */, int64_t O, int M, int P, int keep,
                         int64_t* sel /* [O,keep] */, int32_t* rank /* [O,keep] */, float* gap /* [O,keep] */, int32_t* err,
                         dvq_stream_t stream);
+/* Lloyd's k-means inside each segment: the statistic behind the reference's diversity figure (diverse_grasp/diversity.py:7-15:
+ * 20 clusters over the [n,61] parameter vectors) as ONE deterministic run from given starting rows -- scipy's kmeans keeps the
+ * best of 20 random starts, which no fixed definition can restate.  One workgroup per segment, the whole loop in one launch, no
+ * workspace; nothing depends on O, on which segments share a call or on scheduling.
+ * Inputs: feature rows x_i = feat[(o * M + i) * ld .. + D) of segment o, i = 0 .. M-1 (fp32, row stride ld >= D floats, read in
+ * place); init[o, 0 .. k): row positions inside the segment; iters >= 0.
+ * Valid row: a row is valid iff all D features are finite.  An invalid row gets assign = -1 and dist = NaN and takes part in nothing.
+ * Distance: d(x, c) is the eight-chain squared distance of dvq_segment_diverse: acc[j mod 8] = acc[j mod 8] + (x[j] - c[j])^2 over
+ *   ascending j, every operation rounded to fp32 on its own (nothing fused), d = ((acc0 + acc1) + (acc2 + acc3)) + ((acc4 + acc5)
+ *   + (acc6 + acc7)).
+ * Assign: best = 0; for j = 1 .. k-1 centre j replaces best iff d_j < d_best, or d_best is NaN and d_j is not: the lowest index wins
+ *   ties and a NaN never wins over a number.  assign[i] = best, dist[i] = d_best.
+ * Update: for each centre c and feature j four chains: chain g starts at +0.0f and adds x[i][j] over ascending segment positions
+ *   i = g (mod 4) with assign[i] == c.  S = (ch0 + ch1) + (ch2 + ch3); centre[c][j] = S / (float)count[c] by IEEE division, count[c]
+ *   the number of rows with assign == c.  A centre with count == 0 keeps its value.
+ * Loop: 1. the centres start as the init rows.  2. assign every row.  3. for u = 1 .. iters: update, then assign again; stop when
+ *   no assignment changed, with iters_used = u.  4. iters_used = iters when the limit ends the loop; iters = 0 gives 0.
+ * Outputs: centres [O,k,D]; counts [O,k]; assign, dist [O*M]; iters_used [O].  assign, dist and counts are always those of the
+ *   centres returned.
+ * Bad init: an entry outside [0, M), a duplicate within a segment or an invalid row sets bit 0 of *err (device int32, zeroed by the
+ *   caller); that segment's integer outputs are all -1 and its centres and dist NaN; no row of the segment is read through a bad index.
+ * O >= 0, 1 <= k <= 64, 1 <= D <= 64, k <= M <= 262144, ld >= D, iters >= 0, no null pointer; anything else is DVQ_EINVAL, nothing
+ * launched.  Vertex space (D = 2334) is out of scope: the accumulators of one workgroup would not fit in LDS. */
+int dvq_segment_kmeans(const float* feat, int64_t ld, int D, const int64_t* init /* [O,k] */, int64_t O, int M, int k, int iters,
+                       float* centres /* [O,k,D] */, int32_t* counts /* [O,k] */, int32_t* assign /* [O*M] */, float* dist /* [O*M] */,
+                       int32_t* iters_used /* [O] */, int32_t* err, dvq_stream_t stream);
 
 /* ------------------------------------------------------------------ all-gather of the generated MANO parameters (multi-GPU)
  * The batch of objects shards contiguously over R ranks (one process per GPU); the only exchange of the path is
