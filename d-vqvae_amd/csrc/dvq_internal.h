@@ -227,6 +227,7 @@ struct DvqKnobs {
     int gemm_skinny;      // DVQ_GEMM_SKINNY=0: tiled kernels also for M <= 256 (the two must agree bitwise)
     int pn_filter;        // DVQ_PN_FILTER: 0 six-product trunk, 1 default, 2 filtered trunk whatever the tile fill
     int pn_tail;          // DVQ_PN_TAIL: 1 (default): a cloud's 1 .. 32 points beyond a multiple of 256 as a one-block tail tile; 0: a full tile
+    int pn_recompute;     // DVQ_PN_RECOMPUTE: 1: the trunk kernel does not spill its conv2 rows, the exact stage recomputes the ones it reads; 0: spill + gather (the features are the same bit for bit)
     int pn_exhaustive;    // DVQ_PN_EXHAUSTIVE=1: exact stage evaluates every point (what the filter must reproduce bit for bit)
     int pn_caps[2];       // DVQ_PN_CAPS=a,b: candidate-list capacities (tests shrink them to reach the overflow paths); < 0: default
     long pn_chunk;        // DVQ_PN_CHUNK: samples per PointNet launch (<= 0: at most 4 096, at least four launches per pass)

@@ -2,7 +2,8 @@
 // cost (PointNetEncoder.forward, network/pointnet_encoder.py:147-164; STN3d.forward :30-35):
 //
 //   1. pn_trunk_filter_kernel: conv1 (vector ALU) and conv2 (split-bf16, six matrix-core products, fp32-accurate) as in
-//      pn_trunk_kernel; the fp32 h2 rows [point][128] go to HBM.  conv3 (94 % of the trunk's FLOPs) is then evaluated as ONE
+//      pn_trunk_kernel; the fp32 h2 rows [point][128] go to HBM only with DVQ_PN_RECOMPUTE=0 (default: pn_exact_kernel recomputes
+//      the rows it reads with the same device function, pn_conv12_block).  conv3 (94 % of the trunk's FLOPs) is then evaluated as ONE
 //      fp16 product per term on CENTRED rows: d_p = h2_p - c (c = pn_center_kernel's mean of four rows of the sample; the
 //      argmax over the points does not depend on it), d scaled by a per-wave power of two, W3 by a per-channel power of
 //      two, both rounded to fp16.  Every lane keeps, per 16-channel column block (its 16 points of one channel: four per row block), the TWO largest
@@ -181,6 +182,107 @@ __device__ __forceinline__ float g_wave_sum(float v) {    // uniform result
     v = g_half_sum(v);
     return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 0)) + __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 16));
 }
+// One point of a cloud as conv1 sees it: pc [C][N] of the sample at ``src`` (= its point's first coordinate), xyz @ trans (t: [9] or
+// null) in front (pointnet_encoder.py:146).  The trunk kernel and pn_exact_kernel's recompute both read their points through here.
+template <int C>
+__device__ __forceinline__ void pn_point_in(const float* __restrict__ src, int N, const float* __restrict__ t, float (&x)[4]) {
+    float x0 = src[0], x1 = src[N], x2 = src[2L * N];
+    const float x3 = (C > 3) ? src[3L * N] : 0.f;
+    if (t) {
+        const float n0 = fmaf(x2, t[6], fmaf(x1, t[3], x0 * t[0]));
+        const float n1 = fmaf(x2, t[7], fmaf(x1, t[4], x0 * t[1]));
+        const float n2 = fmaf(x2, t[8], fmaf(x1, t[5], x0 * t[2]));
+        x0 = n0; x1 = n1; x2 = n2;
+    }
+    x[0] = x0; x[1] = x1; x[2] = x2; x[3] = x3;
+}
+
+// THE definition of a conv2 row: conv1 + conv2 of one 32-point block of a wave (lanes l and l + 32 work on point l & 31: lane half
+// h holds rows k = 16 s + 8 h + j of conv1's 64 activations).  conv1: the FMAs in their order; conv2 on the fp16 three-product split
+// of csrc/gemm_f16x2.hip: weights as two fp16 planes of w * 2^t_n (per output row), the activations of a point as two fp16 pieces of
+// h1 * s_p with s_p a power of two that puts the POINT's largest activation in [2^14, 2^15) -- a function of the point alone, so a
+// row's bits do not depend on which points share its wave (tail tile == full tile, batched == single, recomputed == spilled);
+// acc = a1 w2 + a2 w1 + a1 w1 in ONE fp32 accumulator per 32 channels (second pieces unscaled; the eight small products first, the
+// four large ones after), h2 = relu(acc / s_p 2^-t_n + b2).  Parameterised only by where its operands live: w1 [64][4], b1 [64],
+// k2 [128] (2^-t_n), b2 [128] in the LDS (trunk) or in global memory (exact stage); frag(t4, plane, s) = the W2 fragment of channel
+// row 32 t4 + (l & 31), k chunk 2 s + h -- from the trunk's LDS stages or from the filter image.  emit(t4, o): the lane's sixteen
+// channels 32 t4 + (e & 3) + 8 (e >> 2) + 4 h of its point.  The instruction shape and the k-to-lane assignment define the bits.
+// Two halves: pn_conv1_split (conv1 -> the point's two fp16 pieces and 1 / s_p) and pn_conv2_block (32 channels); pn_conv12_block is
+// both for all 128 channels, written out (the trunk kernel); pn_exact_kernel keeps the loop over the channel blocks rolled.
+template <int C>
+__device__ __forceinline__ void pn_conv1_split(const float (&xin)[4], const float* w1s, const float* b1s, int h_op, qf16x8 (&h1a)[4], qf16x8 (&h1b)[4],
+                                               float& r_p_out) {
+    float v[4][8];
+    float amax = 0.f;
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const f32x4 w = *reinterpret_cast<const f32x4*>(w1s + 32 * h_op + 64 * s + 4 * j);   // row k = 16 s + 8 h + j
+            float a = fmaf(xin[0], w[0], (b1s + 8 * h_op)[16 * s + j]);
+            a = fmaf(xin[1], w[1], a);
+            a = fmaf(xin[2], w[2], a);
+            if constexpr (C > 3) a = fmaf(xin[3], w[3], a);
+            v[s][j] = fmaxf(a, 0.f);
+        }
+#pragma unroll
+        for (int j = 0; j < 8; j += 2) amax = fmaxf(fmaxf(amax, v[s][j]), v[s][j + 1]);   // v_max3_f32 (a NaN is dropped here and reaches the products through the pieces)
+    }
+    amax = g_half_max(amax);                          // the lane halves hold the two halves of a point's 64 activations
+    float s_p = 1.f, r_p = 1.f;
+    {
+        const int ex = (int)((__float_as_uint(amax) >> 23) & 255u);              // amax in [2^(ex-127), 2^(ex-126))
+        if (ex > 20 && ex < 235) {
+            s_p = __uint_as_float((unsigned)(127 + 15 - (ex - 126)) << 23);
+            r_p = __uint_as_float((unsigned)(127 - 15 + (ex - 126)) << 23);
+        }
+    }
+#pragma unroll
+    for (int s = 0; s < 4; ++s) q_split2(v[s], s_p, h1a[s], h1b[s]);
+    r_p_out = r_p;
+}
+template <class Frag, class Emit>
+__device__ __forceinline__ void pn_conv2_block(const qf16x8 (&h1a)[4], const qf16x8 (&h1b)[4], float r_p, int t4, const float* k2s, const float* b2s,
+                                               int h_op, Frag frag, Emit emit) {
+    {
+        // ONE fp32 accumulator: the eight small products (a1 w2, a2 w1: 2^-11 of the large ones) first, the four large ones after
+        f32x16 acc;
+#pragma unroll
+        for (int e = 0; e < 16; ++e) acc[e] = 0.f;
+        qf16x8 w1f[4];
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+            w1f[s] = frag(t4, 0, s);
+            const qf16x8 w2f = frag(t4, 1, s);
+            acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(w2f, h1a[s], acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(w1f[s], h1b[s], acc, 0, 0, 0);
+        }
+#pragma unroll
+        for (int s = 0; s < 4; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(w1f[s], h1a[s], acc, 0, 0, 0);
+        float o[16];
+#pragma unroll
+        for (int e = 0; e < 16; ++e) {
+            const int ch = 32 * t4 + (e & 3) + 8 * (e >> 2);       // + 4 h
+            o[e] = fmaxf(fmaf(acc[e] * r_p, (k2s + 4 * h_op)[ch], (b2s + 4 * h_op)[ch]), 0.f);
+        }
+        emit(t4, o);
+    }
+}
+template <int C, class Frag, class Emit>
+__device__ __forceinline__ void pn_conv12_block(const float (&xin)[4], const float* w1s, const float* b1s, const float* k2s, const float* b2s,
+                                                int h_op, Frag frag, Emit emit) {
+    qf16x8 h1a[4], h1b[4];
+    float r_p;
+    pn_conv1_split<C>(xin, w1s, b1s, h_op, h1a, h1b, r_p);
+#pragma unroll
+    for (int t4 = 0; t4 < 4; ++t4) pn_conv2_block(h1a, h1b, r_p, t4, k2s, b2s, h_op, frag, emit);
+}
+// the lane's sixteen channels of block t4 to its row (dst = row + 32 t4 + 4 h): natural channel order, 4 consecutive channels per 16-byte store
+__device__ __forceinline__ void pn_store_row16(float* dst, const float (&o)[16]) {
+#pragma unroll
+    for (int g = 0; g < 4; ++g) *reinterpret_cast<f32x4*>(dst + 8 * g) = f32x4{o[4 * g], o[4 * g + 1], o[4 * g + 2], o[4 * g + 3]};
+}
+
 // TAIL = false: one workgroup per (sample, dealt tile), blockIdx.x = sample * deal + tile (no workgroup for a tail tile: launched
 // and left at once they would all sit on two of the eight XCDs -- blockIdx % 4 == 3 -- and idle a quarter of the chip).  TAIL = true: the tail tiles of FOUR samples per workgroup, one per wave (one 32-point block each;
 // the staged W2 / W3 images are shared, everything per sample is per wave: centre, scales, records).
@@ -242,17 +344,8 @@ __global__ __launch_bounds__(256, 2) void pn_trunk_filter_kernel(const float* __
         pidx[pb] = p;
         if (p >= N) p %= N;                               // padding slots repeat real points cyclically (a max ignores repeats; a point
                                                           // repeated once costs nothing: both copies carry ids that map back to it)
-        const float* src = pc + b * (long)C * N + p;
-        float x0 = src[0], x1 = src[N], x2 = src[2L * N];
-        const float x3 = (C > 3) ? src[3L * N] : 0.f;
-        if (trans) {                                      // xyz @ trans[b]  (pointnet_encoder.py:146)
-            const float* t = trans + b * 9;
-            const float n0 = fmaf(x2, t[6], fmaf(x1, t[3], x0 * t[0]));
-            const float n1 = fmaf(x2, t[7], fmaf(x1, t[4], x0 * t[1]));
-            const float n2 = fmaf(x2, t[8], fmaf(x1, t[5], x0 * t[2]));
-            x0 = n0; x1 = n1; x2 = n2;
-        }
-        xin[pb][0] = x0; xin[pb][1] = x1; xin[pb][2] = x2; xin[pb][3] = x3;
+        pn_point_in<C>(pc + b * (long)C * N + p, N, trans ? trans + b * 9 : nullptr, xin[pb]);
+        const float x0 = xin[pb][0], x1 = xin[pb][1], x2 = xin[pb][2], x3 = xin[pb][3];
         // a non-finite coordinate (after the transform): the reference's features of such a cloud are NaN in every channel -- affine
         // layers and torch.max propagate it.  ReLU as fmaxf(x, 0) squashes it here, and the cloud would go on as a DEGENERATE one
         // (all its points tie: every group flagged, every channel evaluated over all points by one workgroup -- the straggler of its
@@ -273,11 +366,7 @@ __global__ __launch_bounds__(256, 2) void pn_trunk_filter_kernel(const float* __
         cnorm = sqrtf(g_wave_sum(cq)) * 1.0001f;
     }
 
-    // ---- conv1 + conv2, h2 = relu(conv2 + b2) kept in fp32: hv[pb][16 t4 + e].  conv2 runs on the fp16 THREE-product split of
-    // csrc/gemm_f16x2.hip since round 5 (six bf16 products before): weights as two fp16 planes of w * 2^t_n (per output row), the
-    // activations of a point as two fp16 pieces of h1 * s_p with s_p a power of two that puts the POINT's largest activation in
-    // [2^14, 2^15) -- a function of the point alone, so a row's bits do not depend on which points share its wave (tail tile ==
-    // full tile, batched == single); acc = a1 w2 + a2 w1 + a1 w1 in ONE fp32 accumulator (second pieces unscaled), h2 = acc / s_p 2^-t_n + b2.
+    // ---- conv1 + conv2 (pn_conv12_block, W2 from the LDS stages), h2 = relu(conv2 + b2) kept in fp32: hv[pb][16 t4 + e]
     float hv[NPB][64];
     if (abl & PN_ABL_CONSUMER) {                                    // timing only: a "consumer" workgroup -- no conv1 / conv2, rows from thin air
 #pragma unroll
@@ -287,65 +376,15 @@ __global__ __launch_bounds__(256, 2) void pn_trunk_filter_kernel(const float* __
     } else
 #pragma unroll
     for (int pb = 0; pb < NPB; ++pb) {
-        float v[4][8];
-        float amax = 0.f;
+        // (h2buf == nullptr, workgroup-uniform: the rows are not spilled -- pn_exact_kernel recomputes the ones it needs, DVQ_PN_RECOMPUTE)
+        const bool spill = pidx[pb] < N && live && h2buf != nullptr && !(abl & PN_ABL_NO_H2_STORE);
+        pn_conv12_block<C>(xin[pb], w1s, b1s, k2s, b2s, h_op,
+                           [&](int t4, int pl, int s) { return w2_frag(fl + (t4 >> 1) * F_STAGE2, pl, 32 * (t4 & 1) + r, 2 * s + h); },
+                           [&](int t4, const float (&o)[16]) {
 #pragma unroll
-        for (int s = 0; s < 4; ++s) {
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const f32x4 w = *reinterpret_cast<const f32x4*>(w1s + 32 * h_op + 64 * s + 4 * j);   // row k = 16 s + 8 h + j
-                float a = fmaf(xin[pb][0], w[0], (b1s + 8 * h_op)[16 * s + j]);
-                a = fmaf(xin[pb][1], w[1], a);
-                a = fmaf(xin[pb][2], w[2], a);
-                if constexpr (C > 3) a = fmaf(xin[pb][3], w[3], a);
-                v[s][j] = fmaxf(a, 0.f);
-            }
-#pragma unroll
-            for (int j = 0; j < 8; j += 2) amax = fmaxf(fmaxf(amax, v[s][j]), v[s][j + 1]);   // v_max3_f32 (a NaN is dropped here and reaches the products through the pieces)
-        }
-        amax = g_half_max(amax);                          // the lane halves hold the two halves of a point's 64 activations
-        float s_p = 1.f, r_p = 1.f;
-        {
-            const int ex = (int)((__float_as_uint(amax) >> 23) & 255u);              // amax in [2^(ex-127), 2^(ex-126))
-            if (ex > 20 && ex < 235) {
-                s_p = __uint_as_float((unsigned)(127 + 15 - (ex - 126)) << 23);
-                r_p = __uint_as_float((unsigned)(127 - 15 + (ex - 126)) << 23);
-            }
-        }
-        qf16x8 h1a[4], h1b[4];
-#pragma unroll
-        for (int s = 0; s < 4; ++s) q_split2(v[s], s_p, h1a[s], h1b[s]);
-#pragma unroll
-        for (int t4 = 0; t4 < 4; ++t4) {
-            const char* st = fl + (t4 >> 1) * F_STAGE2;
-            const int row = 32 * (t4 & 1) + r;
-            // ONE fp32 accumulator: the eight small products (a1 w2, a2 w1: 2^-11 of the large ones) first, the four large ones after
-            f32x16 acc;
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[e] = 0.f;
-            qf16x8 w1f[4];
-#pragma unroll
-            for (int s = 0; s < 4; ++s) {
-                w1f[s] = w2_frag(st, 0, row, 2 * s + h);
-                const qf16x8 w2f = w2_frag(st, 1, row, 2 * s + h);
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(w2f, h1a[s], acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(w1f[s], h1b[s], acc, 0, 0, 0);
-            }
-#pragma unroll
-            for (int s = 0; s < 4; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(w1f[s], h1a[s], acc, 0, 0, 0);
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                const int ch = 32 * t4 + (e & 3) + 8 * (e >> 2);       // + 4 h
-                hv[pb][16 * t4 + e] = fmaxf(fmaf(acc[e] * r_p, (k2s + 4 * h_op)[ch], (b2s + 4 * h_op)[ch]), 0.f);
-            }
-            if (pidx[pb] < N && live && !(abl & PN_ABL_NO_H2_STORE)) {     // natural channel order: 4 consecutive channels per 16-byte store
-                float* dst = h2buf + ((b * Npad + pidx[pb]) * 128 + 32 * t4 + 4 * h);
-#pragma unroll
-                for (int g = 0; g < 4; ++g)
-                    *reinterpret_cast<f32x4*>(dst + 8 * g) =
-                        f32x4{hv[pb][16 * t4 + 4 * g], hv[pb][16 * t4 + 4 * g + 1], hv[pb][16 * t4 + 4 * g + 2], hv[pb][16 * t4 + 4 * g + 3]};
-            }
-        }
+                               for (int e = 0; e < 16; ++e) hv[pb][16 * t4 + e] = o[e];
+                               if (spill) pn_store_row16(h2buf + ((b * Npad + pidx[pb]) * 128 + 32 * t4 + 4 * h), o);
+                           });
     }
     if (abl & PN_ABL_STAMPS) t_b = __builtin_amdgcn_s_memtime();
     // ---- centre the rows on the sample's centre (pn_center_kernel)
@@ -796,11 +835,25 @@ __device__ unsigned long long g_pn_faults[2];
 //   phase C (one wave per entry, no barrier): the 16 points of a flagged group; then, whole workgroup per channel, every
 //           point for the channels on the "everything" list (DVQ_PN_EXHAUSTIVE / non-finite inputs).
 // stats (optional): channels with one candidate, with another count, wave entries, candidates; phase cycles; distinct rows, clouds.
+//
+// recompute != 0 (DVQ_PN_RECOMPUTE): the trunk kernel has NOT spilled its conv2 rows.  In front of every place that reads rows the
+// workgroup then produces exactly the distinct points named there -- the anchors; the pairs and the 16 points of every flagged group;
+// every point for the "everything" list and the interval check's repair -- with the trunk's own pn_conv12_block (W2 fragments from
+// the filter image in L2, b2 / 2^-t_n from global memory, W1 / b1 staged in the LDS), 32 points per wave and batch, into their natural place h2[p] of
+// the cloud's block of the scratch set: dots(), phase C and eval_all_list read them as they read spilled rows.  A bit per point says
+// which rows exist.  A row's bits do not depend on its wave-mates, so they are the trunk's (DVQ_PN_EXHAUSTIVE=1 keeps the spilled
+// rows and checks that).  Producer -> consumer inside the workgroup: every wave waits for its stores (vmcnt(0)) before the barrier
+// that precedes the reads; the waves of a workgroup share their CU's L1, which the stores write through.
 constexpr int PAIR_CAP = 2048;                            // (channel, point) pairs beyond the anchors; more: their 16-point groups instead
 constexpr int FB_CAP = 512;
 constexpr unsigned short NO_ANCHOR = 0xFFFFu;              // a channel on the "everything" list
+constexpr int TODO_CAP = 2 * PAIR_CAP;                     // points of one recompute round (16-bit entries in pair_list's bytes); more: the whole cloud
+template <int C>
 __global__ __launch_bounds__(256, 4) void pn_exact_kernel(const f32x4* __restrict__ part, const qf32x2* __restrict__ part2, int tiles, int deal,
-                                                       const float* __restrict__ h2buf,
+                                                       float* h2buf /* read; written too under ``recompute`` */, int recompute,
+                                                       const float* __restrict__ pc, const float* __restrict__ trans,
+                                                       const float* __restrict__ W1, const float* __restrict__ b1, const float* __restrict__ b2,
+                                                       const char* __restrict__ w3f,
                                                        int N, int Npad, const float* __restrict__ w3, const float* __restrict__ b3,
                                                        const float* __restrict__ wnorm, const float* __restrict__ rnorm,
                                                        const unsigned* __restrict__ tstat, const float* __restrict__ cbuf, int relu, int exhaustive,
@@ -820,12 +873,18 @@ __global__ __launch_bounds__(256, 4) void pn_exact_kernel(const f32x4* __restric
     __shared__ unsigned sorted[PAIR_CAP];                  // channel | point << 10, grouped by point: the anchors, then the pairs
     __shared__ int wave_tot[4];
     __shared__ unsigned row_mask[32];                      // statistics: points that were somebody's anchor
+    __shared__ unsigned done_mask[PN_MAX_POINTS / 32];     // recompute: bit p = row p of this cloud exists
+    __shared__ int todo_count;                             // recompute: points claimed so far (never reset: a round's list starts at todo_base)
+    __shared__ __attribute__((aligned(16))) float w1s[64 * 4 + 64];   // recompute: conv1's weights [64][4] and bias [64] (from global memory the compiler requests all 32 rows ahead: 128 registers)
     static_assert(PAIR_CAP >= 1024, "sorted[] holds the 1 024 anchors");
+    static_assert(PN_MAX_POINTS <= 65536, "a point fits a 16-bit list entry");
     const int tid = threadIdx.x, g = tid >> 4, j = tid & 15;
     const long b = blockIdx.x;
-    const f32x4 cen_a = *reinterpret_cast<const f32x4*>(cbuf + b * 128 + 4 * j), cen_b = *reinterpret_cast<const f32x4*>(cbuf + b * 128 + 4 * j + 64);
-    if (tid == 0) { pair_count = 0; fb_count = 0; all_count = 0; }
+    if (tid == 0) { pair_count = 0; fb_count = 0; all_count = 0; todo_count = 0; }
     if (tid < 32) row_mask[tid] = 0;
+    done_mask[tid] = 0; done_mask[tid + 256] = 0;
+    w1s[tid] = W1[tid];
+    if (tid < 64) w1s[256 + tid] = b1[tid];
 #pragma unroll
     for (int i = 0; i < 4; ++i) pcnt[tid + 256 * i] = 0;
     int nonfinite_point = 0;
@@ -842,14 +901,14 @@ __global__ __launch_bounds__(256, 4) void pn_exact_kernel(const f32x4* __restric
         for (int n = tid; n < 1024; n += 256) feat[b * ld_feat + n] = __builtin_nanf("");
         return;
     }
-    const float* h2 = h2buf + b * (long)Npad * 128;
+    float* h2 = h2buf + b * (long)Npad * 128;
     const bool wrap_small = Npad <= 2 * N;                  // a padding slot's index is below 2 N: one subtraction instead of a division
     const f32x4* pt = part + b * (long)tiles * 1024;
     const qf32x2* pt2 = part2 + b * (long)tiles * 1024;     // the fourth and fifth id-carrying scores
     const bool stamps = DVQ_DIAG_ON && stats && (abl & PN_ABL_STAMPS);   // diagnostics: cycles per phase (tid 0's clock), summed into stats[4..7]
     unsigned long long tp[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     if (stamps) tp[0] = __builtin_amdgcn_s_memtime();
-    unsigned n_single = 0, n_multi = 0, n_cand = 0, n_wave = 0, n_suspect = 0, n_rows = 0;
+    unsigned n_single = 0, n_multi = 0, n_cand = 0, n_wave = 0, n_suspect = 0;
     // E_t of channel (wn, rn)
     auto bound_of = [&](float wn, float rn, int t) { return fmaf(rn, dm[t], fmaf(wn, rd[t], fmaf(C_ID * wn, dm[t], 2.0f * DELTA * wn * hm[t]))); };
     // The interval the records promise for (max - w.c) of channel n: lb = max_t (c1_t - E_t), ub = max_t (c1_t + E_t); the first tile
@@ -899,6 +958,57 @@ __global__ __launch_bounds__(256, 4) void pn_exact_kernel(const f32x4* __restric
         if (abl & PN_ABL_FEW_ROWS) p &= 63;
         return p;
     };
+    // ---- recompute: claim(p) puts point p on the round's list unless its row exists; fill_rows() ends the round: the listed rows
+    // (all = false), or every row of the cloud that does not exist yet (all = true: a round without claims; a list beyond TODO_CAP:
+    // every row, whatever the bits say), 32 points per wave and batch; a batch with fewer points repeats its last one and stores it once.  The list lives
+    // in pair_list's bytes: free before phase A2 fills it and again once the pairs are sorted.
+    unsigned short* todo = reinterpret_cast<unsigned short*>(pair_list);
+    int todo_base = 0;
+    auto claim = [&](int p) {
+        const unsigned bit = 1u << (p & 31);
+        if (atomicOr(&done_mask[p >> 5], bit) & bit) return;
+        const int slot = atomicAdd(&todo_count, 1) - todo_base;
+        if (slot < TODO_CAP) todo[slot] = (unsigned short)p;
+    };
+    auto fill_rows = [&](bool all) {
+        dvq_lds_barrier();                                  // the round's claims are complete
+        const int end = __builtin_amdgcn_readfirstlane(todo_count), listed = end - todo_base;   // (uniform: scalar registers)
+        todo_base = end;
+        const bool forced = listed > TODO_CAP;
+        const bool whole = all || forced;
+        const int cnt = whole ? N : listed;
+        const int lane = tid & 63, r = lane & 31, h = lane >> 5;
+        const float* k2g = reinterpret_cast<const float*>(w3f + IMG_OFF_K2);
+        const uint16_t* w2pl = reinterpret_cast<const uint16_t*>(w3f + IMG_OFF_W2);
+        for (int i0 = 32 * __builtin_amdgcn_readfirstlane(tid >> 6); i0 < cnt; i0 += 128) {
+            if (whole && !forced && done_mask[i0 >> 5] == ~0u) continue;   // (i0 >> 5: the word of points i0 .. i0 + 31)
+            // the lane half as an opaque value (see the trunk kernel), made opaque again in every batch: the reads of conv1's weights
+            // do not depend on the batch otherwise, and the compiler moves all of them in front of the loop and spills them
+            int h_op = h;
+            asm volatile("" : "+v"(h_op));
+            const int i = min(i0 + r, cnt - 1);
+            const int p = whole ? i : (int)todo[i];
+            float x[4];
+            pn_point_in<C>(pc + b * (long)C * N + p, N, trans ? trans + b * 9 : nullptr, x);
+            float* row = h2 + (long)p * 128 + 4 * h;
+            const bool mine = i0 + r < cnt;
+            qf16x8 h1a[4], h1b[4];
+            float r_p;
+            pn_conv1_split<C>(x, w1s, w1s + 256, h_op, h1a, h1b, r_p);
+#pragma unroll 1
+            for (int t4 = 0; t4 < 4; ++t4)                  // (rolled: 128 registers, and the code is there twice)
+                pn_conv2_block(h1a, h1b, r_p, t4, k2g, b2, h_op,
+                               [&](int t, int pl, int s) { return *reinterpret_cast<const qf16x8*>(w2pl + pl * (128 * 64) + (32 * t + r) * 64 + 8 * (2 * s + h)); },
+                               [&](int t, const float (&o)[16]) { if (mine) pn_store_row16(row + 32 * t, o); });
+            if (whole && lane == 0) done_mask[i0 >> 5] = ~0u;
+            if (stats && lane == 0) {                        // statistics: batches and rows (straight to memory: no counter held across the kernel)
+                atomicAdd(stats + 10, 1ull);
+                atomicAdd(stats + 11, (unsigned long long)min(32, cnt - i0));
+            }
+        }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's rows have left it ...
+        dvq_lds_barrier();                                  // ... before anybody of the workgroup reads one
+    };
     // Counting sort in the LDS of count codes (channel | point << 10; ~0u: none) by point into sorted[]; pcnt is zero on entry.  A
     // cloud's 1 024 channels take their maxima at ~100-200 distinct points: evaluated channel by channel every pair fetched its
     // 512-byte row from HBM again (the kernel ran at the HBM roofline); grouped by point a row is fetched once and found in the
@@ -913,13 +1023,19 @@ __global__ __launch_bounds__(256, 4) void pn_exact_kernel(const f32x4* __restric
         if (stats) {                                        // distinct rows: points with an anchor, then points with pairs only
             const unsigned m = (unsigned)(c0 != 0) | (unsigned)(c1 != 0) << 1 | (unsigned)(c2 != 0) << 2 | (unsigned)(c3 != 0) << 3;
             const int sh = 4 * (tid & 7);
-            if (first) { if (m) atomicOr(&row_mask[tid >> 3], m << sh); n_rows += __popc(m); }
-            else n_rows += __popc(m & ~(row_mask[tid >> 3] >> sh));
+            int rows;                                       // (straight to memory: no counter held across the kernel)
+            if (first) { if (m) atomicOr(&row_mask[tid >> 3], m << sh); rows = __popc(m); }
+            else rows = __popc(m & ~(row_mask[tid >> 3] >> sh));
+            if (rows) atomicAdd(stats + 8, (unsigned long long)rows);
         }
         int incl = c0 + c1 + c2 + c3;
+        // (the lane as an opaque value per sort: the six shuffle addresses are then formed here, not kept -- spilled -- from the first
+        // sort to the second across the recompute; a lane below o reads some lane's value and ignores it)
+        int lane_op = tid & 63;
+        asm volatile("" : "+v"(lane_op));
 #pragma unroll
         for (int o = 1; o < 64; o <<= 1) {
-            const int v = __shfl_up(incl, o);
+            const int v = __builtin_amdgcn_ds_bpermute(4 * (lane_op - o), incl);
             if ((tid & 63) >= o) incl += v;
         }
         if ((tid & 63) == 63) wave_tot[tid >> 6] = incl;
@@ -944,6 +1060,8 @@ __global__ __launch_bounds__(256, 4) void pn_exact_kernel(const f32x4* __restric
     // first: the anchors -- one per channel: plain stores, and the centre term of the channel with them.
     auto dots = [&](int total, bool first) {
         const int per = (total + 15) >> 4, i0 = g * per, i1 = min(total, i0 + per);
+        f32x4 cen_a = {0.f, 0.f, 0.f, 0.f}, cen_b = cen_a;   // the centre's slice: the anchors' pass only (not held across the other phases)
+        if (first) { cen_a = *reinterpret_cast<const f32x4*>(cbuf + b * 128 + 4 * j); cen_b = *reinterpret_cast<const f32x4*>(cbuf + b * 128 + 4 * j + 64); }
         for (int i = i0; i < i1; i += 4) {
             f32x4 w0[4], w1[4], ha[4], hb[4];
             int nn[4];
@@ -1004,6 +1122,13 @@ __global__ __launch_bounds__(256, 4) void pn_exact_kernel(const f32x4* __restric
 #pragma unroll
     for (int i = 0; i < 4; ++i) pcnt[tid + 256 * i] = 0;   // (the next sort's histogram: after the barrier that ends this one)
     if (stamps) tp[2] = __builtin_amdgcn_s_memtime();
+    if (recompute) {                                        // the anchors' rows (sorted[] is grouped by point: one claim per run)
+        for (int i = tid; i < n_anchor; i += 256) {
+            const int p = (int)(sorted[i] >> 10);
+            if (i == 0 || (int)(sorted[i - 1] >> 10) != p) claim(p);
+        }
+        fill_rows(false);
+    }
     if (!(abl & PN_ABL_NO_DOTS)) dots(n_anchor, true);
     dvq_lds_barrier();
     if (stamps) tp[3] = __builtin_amdgcn_s_memtime();
@@ -1127,36 +1252,6 @@ __global__ __launch_bounds__(256, 4) void pn_exact_kernel(const f32x4* __restric
     }
     dvq_lds_barrier();
     if (stamps) tp[4] = __builtin_amdgcn_s_memtime();
-    // ---- phase B: the pairs in point order
-    const int npairs = min(pair_count, pair_cap);
-    const int n_sorted = sort_by_point([&](int i) { return (unsigned)pair_list[i]; }, npairs, false);
-    if (stamps) tp[5] = __builtin_amdgcn_s_memtime();
-    if (!(abl & PN_ABL_NO_DOTS)) dots(n_sorted, false);
-    if (stamps) tp[6] = __builtin_amdgcn_s_memtime();
-    // ---- phase C: flagged 16-point groups, one wave of the workgroup per entry, its four 16-lane groups take 4 points each
-    const int nfb = (abl & PN_ABL_NO_GROUPS) ? 0 : min(fb_count, fb_cap);
-    for (int i = tid >> 6; i < nfb; i += 4) {
-        const int code = fb_list[i];
-        const int n = code & 1023, t = (code >> 10) & 1023, grp = (code >> 20) & 15;
-        const float* wr = reinterpret_cast<const float*>(reinterpret_cast<const char*>(w3) + ((unsigned)n * 512u + 16u * (unsigned)j));
-        const f32x4 w0 = *reinterpret_cast<const f32x4*>(wr), w1 = *reinterpret_cast<const f32x4*>(wr + 64);
-        float best = NEG_BIG;
-        {
-            f32x4 ha[4], hb[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {                   // this lane group's 4 of the group's 16 points: row block g & 3, register u
-                int p = point_of_slot(t, pn_group_slot(grp, 4 * (g & 3) + u), deal);   // tail tile: row blocks 2, 3 repeat 0, 1
-                if (p >= N) p %= N;
-                const float* hr = reinterpret_cast<const float*>(reinterpret_cast<const char*>(h2) + ((unsigned)p * 512u + 16u * (unsigned)j));
-                ha[u] = *reinterpret_cast<const f32x4*>(hr);
-                hb[u] = *reinterpret_cast<const f32x4*>(hr + 64);
-            }
-#pragma unroll
-            for (int u = 0; u < 4; ++u) best = fmaxf(best, exact_dot_regs(w0, w1, ha[u], hb[u]));
-        }
-        if (j == 0) atomicMax(&best_k[n], f2key(best));
-    }
-    dvq_lds_barrier();
     // ---- phase C: everything (NaN-propagating maximum, torch.max semantics): the channels on all_list over ALL points, four channels
     // per sweep of the rows (a row's slice is loaded once for the four)
     auto eval_all_list = [&](int count) {
@@ -1193,32 +1288,92 @@ __global__ __launch_bounds__(256, 4) void pn_exact_kernel(const f32x4* __restric
             dvq_lds_barrier();
         }
     };
-    eval_all_list(all_count);
-    // ---- consistency: the exact maximum of a channel must lie where its tile records said it would.  |approx + w.c - exact| <= E_t
-    // for every point of tile t, so  max_t (top_t - E_t) <= max - w.c <= max_t (top_t + E_t).  A maximum outside that interval means a
-    // record did not describe its tile (a wrong score or id; a missing input that was the tile's best shows up in the trunk kernel's
-    // own tag check instead): such a channel is evaluated over all points, and counted.
-    dvq_lds_barrier();                                       // best_k / wcs complete; all_list free again
-    if (tid == 0) all_count = 0;
-    dvq_lds_barrier();
+    // ---- phases B and C, then the consistency check and its repair, as two trips of ONE rolled loop: the recompute and the sweep of the
+    // "everything" list exist once in the code (the instruction cache: see lo_0 .. hi_3)
     unsigned n_bad = 0;
+    int n_sorted = 0, nfb = 0;
+#pragma unroll 1
+    for (int pass = 0; pass < 2; ++pass) {
+        if (pass == 0) {
+            // ---- phase B: the pairs in point order
+            const int npairs = min(pair_count, pair_cap);
+            n_sorted = sort_by_point([&](int i) { return (unsigned)pair_list[i]; }, npairs, false);
+            if (stamps) tp[5] = __builtin_amdgcn_s_memtime();
+            nfb = (abl & PN_ABL_NO_GROUPS) ? 0 : min(fb_count, fb_cap);
+            // the rows of the pairs (grouped by point: one claim per run) and of the flagged groups -- unless the "everything" list has
+            // entries (complete since phase A2): every row is produced then, and a claim would mark a row that is not there yet
+            if (recompute && all_count == 0) {
+                for (int i = tid; i < n_sorted; i += 256) {
+                    const int p = (int)(sorted[i] >> 10);
+                    if (i == 0 || (int)(sorted[i - 1] >> 10) != p) claim(p);
+                }
+                for (int i = tid; i < 16 * nfb; i += 256) {
+                    const int code = fb_list[i >> 4];
+                    int p = point_of_slot((code >> 10) & 1023, pn_group_slot((code >> 20) & 15, i & 15), deal);
+                    if (p >= N) p %= N;
+                    claim(p);
+                }
+            }
+        } else {
+            // ---- consistency: the exact maximum of a channel must lie where its tile records said it would.  |approx + w.c - exact| <= E_t
+            // for every point of tile t, so  max_t (top_t - E_t) <= max - w.c <= max_t (top_t + E_t).  A maximum outside that interval means a
+            // record did not describe its tile (a wrong score or id; a missing input that was the tile's best shows up in the trunk kernel's
+            // own tag check instead): such a channel is evaluated over all points, and counted.
+            dvq_lds_barrier();                               // best_k / wcs complete; all_list free again
+            if (tid == 0) all_count = 0;
+            dvq_lds_barrier();
 #pragma unroll
-    for (int ci = 0; ci < 4; ++ci) {
-        const int n = tid + 256 * ci;
-        const float lo_c = ci == 0 ? lo_0 : ci == 1 ? lo_1 : ci == 2 ? lo_2 : lo_3, hi_c = ci == 0 ? hi_0 : ci == 1 ? hi_1 : ci == 2 ? hi_2 : hi_3;
-        if (!(lo_c <= hi_c) || (abl & ~PN_ABL_VALID)) continue;   // (the timing ablations -- of either kernel -- leave maxima that are not maxima)
-        const float v = key2f(best_k[n]), wc = wcs[n];
-        const float x = v - wc, slack = 4.0e-7f * (fabsf(v) + fabsf(wc));   // the subtraction's own rounding
-        if (!(x >= lo_c - slack && x <= hi_c + slack)) {
-            all_list[atomicAdd(&all_count, 1)] = (short)n;
-            ++n_bad;
+            for (int ci = 0; ci < 4; ++ci) {
+                const int n = tid + 256 * ci;
+                const float lo_c = ci == 0 ? lo_0 : ci == 1 ? lo_1 : ci == 2 ? lo_2 : lo_3, hi_c = ci == 0 ? hi_0 : ci == 1 ? hi_1 : ci == 2 ? hi_2 : hi_3;
+                if (!(lo_c <= hi_c) || (abl & ~PN_ABL_VALID)) continue;   // (the timing ablations -- of either kernel -- leave maxima that are not maxima)
+                const float v = key2f(best_k[n]), wc = wcs[n];
+                const float x = v - wc, slack = 4.0e-7f * (fabsf(v) + fabsf(wc));   // the subtraction's own rounding
+                if (!(x >= lo_c - slack && x <= hi_c + slack)) {
+                    all_list[atomicAdd(&all_count, 1)] = (short)n;
+                    ++n_bad;
+                }
+            }
+            dvq_lds_barrier();
         }
+        const int n_all = __builtin_amdgcn_readfirstlane(all_count);
+        if (recompute && (pass == 0 || n_all > 0)) fill_rows(n_all > 0);
+        if (pass == 0) {
+            if (!(abl & PN_ABL_NO_DOTS)) dots(n_sorted, false);
+            if (stamps) tp[6] = __builtin_amdgcn_s_memtime();
+            // ---- phase C: flagged 16-point groups, one wave of the workgroup per entry, its four 16-lane groups take 4 points each
+            for (int i = tid >> 6; i < nfb; i += 4) {
+                const int code = fb_list[i];
+                const int n = code & 1023, t = (code >> 10) & 1023, grp = (code >> 20) & 15;
+                const float* wr = reinterpret_cast<const float*>(reinterpret_cast<const char*>(w3) + ((unsigned)n * 512u + 16u * (unsigned)j));
+                const f32x4 w0 = *reinterpret_cast<const f32x4*>(wr), w1 = *reinterpret_cast<const f32x4*>(wr + 64);
+                float best = NEG_BIG;
+                {
+                    f32x4 ha[4], hb[4];
+#pragma unroll
+                    for (int u = 0; u < 4; ++u) {                   // this lane group's 4 of the group's 16 points: row block g & 3, register u
+                        int p = point_of_slot(t, pn_group_slot(grp, 4 * (g & 3) + u), deal);   // tail tile: row blocks 2, 3 repeat 0, 1
+                        if (p >= N) p %= N;
+                        const float* hr = reinterpret_cast<const float*>(reinterpret_cast<const char*>(h2) + ((unsigned)p * 512u + 16u * (unsigned)j));
+                        ha[u] = *reinterpret_cast<const f32x4*>(hr);
+                        hb[u] = *reinterpret_cast<const f32x4*>(hr + 64);
+                    }
+#pragma unroll
+                    for (int u = 0; u < 4; ++u) best = fmaxf(best, exact_dot_regs(w0, w1, ha[u], hb[u]));
+                }
+                if (j == 0) atomicMax(&best_k[n], f2key(best));
+            }
+            dvq_lds_barrier();
+        }
+        eval_all_list(n_all);
     }
-    dvq_lds_barrier();
-    eval_all_list(all_count);
     if (n_suspect) atomicAdd(&g_pn_faults[0], (unsigned long long)n_suspect);
     if (n_bad) atomicAdd(&g_pn_faults[1], (unsigned long long)n_bad);
-    for (int n = tid; n < 1024; n += 256) {
+    int tid_op = tid;                                       // (opaque: the channel offsets are formed again here instead of being kept -- spilled -- since phase A2)
+    asm volatile("" : "+v"(tid_op));
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int n = tid_op + 256 * i;
         const unsigned k = best_k[n];
         const float v = (k == 0xffffffffu ? __builtin_nanf("") : key2f(k)) + b3[n];
         feat[b * ld_feat + n] = relu ? (v != v ? v : fmaxf(v, 0.f)) : v;
@@ -1230,7 +1385,6 @@ __global__ __launch_bounds__(256, 4) void pn_exact_kernel(const f32x4* __restric
         atomicAdd(stats + 9, tp[3] - tp[0]);               // of the above: lower bounds, anchors, their sort and dots (rule 2's extra pass)
     }
     if (stats) {
-        if (n_rows) atomicAdd(stats + 8, (unsigned long long)n_rows);
         if (n_single) atomicAdd(stats + 0, (unsigned long long)n_single);
         if (n_multi) atomicAdd(stats + 1, (unsigned long long)n_multi);
         if (n_wave) atomicAdd(stats + 2, (unsigned long long)n_wave);
@@ -1382,6 +1536,11 @@ static TrunkFilterKernel trunk_filter_kernel(int C, bool tail) {
     return k[C == 4][tail];
 }
 static decltype(&pn_center_kernel<3>) center_kernel(int C) { return C == 4 ? &pn_center_kernel<4> : &pn_center_kernel<3>; }
+static decltype(&pn_exact_kernel<3>) exact_kernel(int C) { return C == 4 ? &pn_exact_kernel<4> : &pn_exact_kernel<3>; }
+// DVQ_PN_RECOMPUTE: the trunk kernel does not spill its conv2 rows, pn_exact_kernel produces the ones it reads.  Front and back of a
+// launch both ask here.  The exhaustive evaluation (DVQ_PN_EXHAUSTIVE=1) always takes spilled rows: it stays an independent check,
+// and "filtered == exhaustive" then also says that recomputed rows have the trunk's bits.
+static bool pn_recompute() { return dvq_knobs().pn_recompute && !dvq_knobs().pn_exhaustive; }
 
 int dvq_launch_pn_filter_front(const PnBatch& in, const PnTrunkWeights& w, const PnSlot& sl, unsigned long long* stats, hipStream_t st) {
     PnGeometry g;
@@ -1405,13 +1564,14 @@ int dvq_launch_pn_filter_front(const PnBatch& in, const PnTrunkWeights& w, const
     DVQ_CHECK_LAUNCH("pn_center");
     const double pts = (double)B * g.slots;
     const int abl = pn_abl();
+    float* h2 = pn_recompute() ? nullptr : sl.h2;          // nullptr: no spill
     // one launch of the trunk kernel: the full-tile grid (a workgroup per sample and dealt tile) or the tail grid (four samples each)
     auto launch = [&](bool tail, int lds, hipStream_t s, int abl_arg) {
         DVQ_LAUNCH(trunk_filter_kernel(in.C, tail), dim3((unsigned)(tail ? (B + 3) / 4 : grid)), dim3(256), lds, s, in.pc, in.trans, in.N, g.Npad,
-                   g.tiles, g.deal, B, w.w1, w.b1, w.b2, (const char*)w.w3f, sl.h2, (f32x4*)sl.part, (qf32x2*)sl.part2, sl.tstat, sl.cbuf, abl_arg);
+                   g.tiles, g.deal, B, w.w1, w.b1, w.b2, (const char*)w.w3f, h2, (f32x4*)sl.part, (qf32x2*)sl.part2, sl.tstat, sl.cbuf, abl_arg);
     };
     {
-        DVQ_PROF("pn_trunk", 2.0 * pts * (4.0 * 64 + 64.0 * 128 + 128.0 * 1024), pts * (16 + 512) + (double)grid * 16384, st);
+        DVQ_PROF("pn_trunk", 2.0 * pts * (4.0 * 64 + 64.0 * 128 + 128.0 * 1024), pts * (16 + (h2 ? 512 : 0)) + (double)grid * 16384, st);
 #ifdef DVQ_DIAG
         if ((abl & PN_ABL_SPLIT) && in.C == 4) {
             // timing only (results INVALID): what splitting the trunk into a producer kernel (conv1 / conv2 / centring / conversion) and a
@@ -1450,10 +1610,12 @@ int dvq_launch_pn_filter_back(const PnBatch& in, const PnTrunkWeights& w, const 
         pair_cap = kn.pn_caps[0] > PAIR_CAP ? PAIR_CAP : kn.pn_caps[0];
         fb_cap = kn.pn_caps[1] > FB_CAP ? FB_CAP : kn.pn_caps[1];
     }
+    const int recompute = pn_recompute();
     {
-        DVQ_PROF("pn_exact", 2.0 * (double)B * 1024 * 128, (double)B * (tiles * 16384.0 + 1024.0 * 512 + 4096), st);
-        DVQ_LAUNCH(pn_exact_kernel, dim3((unsigned)B), dim3(256), 0, st, (const f32x4*)sl.part, (const qf32x2*)sl.part2, tiles, g.deal, sl.h2, N,
-                   g.Npad, w.w3, w.b3, reinterpret_cast<const float*>((const char*)w.w3f + IMG_OFF_WN),
+        // rows: one read per candidate point (about 1 024 of them with repeats); recomputed rows are written first, and their points read
+        DVQ_PROF("pn_exact", 2.0 * (double)B * 1024 * 128, (double)B * (tiles * 16384.0 + 1024.0 * 512 * (recompute ? 2 : 1) + 4096), st);
+        DVQ_LAUNCH(exact_kernel(in.C), dim3((unsigned)B), dim3(256), 0, st, (const f32x4*)sl.part, (const qf32x2*)sl.part2, tiles, g.deal, sl.h2,
+                   recompute, in.pc, in.trans, w.w1, w.b1, w.b2, (const char*)w.w3f, N, g.Npad, w.w3, w.b3, reinterpret_cast<const float*>((const char*)w.w3f + IMG_OFF_WN),
                    reinterpret_cast<const float*>((const char*)w.w3f + IMG_OFF_RN), tstat, sl.cbuf, w.relu3, exhaustive, pair_cap, fb_cap,
                    feat, ld_feat, stats, abl);
     }
@@ -1487,6 +1649,8 @@ int dvq_launch_pn_filter_back(const PnBatch& in, const PnTrunkWeights& w, const 
         // the non-empty slots of the point histograms + 16 per flagged group (an upper bound: a group's points may be candidates too)
         fprintf(stderr, "[dvq pn] B=%ld N=%d: distinct conv2 rows fetched per cloud <= %.1f (%.1f candidate points + 16 per flagged group)\n",
                 B, N, (double)(h[8] + 16 * h[2]) / B, (double)h[8] / B);
+        if (recompute)
+            fprintf(stderr, "[dvq pn] B=%ld N=%d: recomputed per cloud: %.2f batches of 32 points, %.1f conv2 rows\n", B, N, (double)h[10] / B, (double)h[11] / B);
         if (abl & PN_ABL_STAMPS)
             fprintf(stderr, "[dvq pn] exact stage, mean cycles per workgroup: records -> candidates %.0f, sort by point %.0f, candidate dots %.0f, flagged groups + checks + store %.0f; of these the anchor pass %.0f\n",
                     (double)h[4] / B, (double)h[5] / B, (double)h[6] / B, (double)h[7] / B, (double)h[9] / B);
