@@ -14,7 +14,7 @@
 //      |estimate - exact_dot(w_n, h2_p)| <= E_t = |r_n| max_p |d_p| + |w_n| max_p |rd_p| + C_ID |w_n| max_p |d_p|
 //      + 2 DELTA |w_n| max_p |h2_p|, maxima over the tile; r_n = w_n - fp16 image (norm measured by the packer), rd_p =
 //      d_p - fp16 image (norm measured by the trunk kernel), C_ID: id bits + matrix-core accumulation, DELTA: rounding of
-//      one exact_dot.  Every tracked
+//      one exact_dot; pn_exact_kernel adds a floor for the id bits of a score that is zero (E_ID_FLOOR, bound_of).  Every tracked
 //      point whose upper bound reaches the best lower bound is re-evaluated in fp32 (exact_dot: a fixed-order fp32 FMA dot
 //      of W3[n,:] and the stored h2 row) and the maximum of THOSE values + bias is the feature -- bit-identical to the
 //      maximum of exact_dot over ALL points (tests: DVQ_PN_EXHAUSTIVE=1 evaluates exactly that).  The 16 points of a flagged
@@ -44,6 +44,9 @@ constexpr float C_ID = 5.0e-5f;
 // the centre term
 constexpr float DELTA = 1.0e-6f;
 constexpr float NEG_BIG = -3.0e38f;
+// the id and tag bits of a score that is zero or denormal: 2 x 2^-141 in scaled units, doubled for the rounding of a denormal product
+// (bound_of in pn_exact_kernel)
+constexpr float E_ID_FLOOR = 0x1p-139f;
 
 constexpr int F_STAGE2 = 2 * 64 * 128;                    // conv2: one half of W2's two fp16 planes (2 x 64 rows x 128 B)
 // the filter image of a trunk (dvq_pointnet_pack_filter): conv3 [1024][128] fp16 | 1 / scale [1024] | |w_n| [1024] | |w_n - image| [1024]
@@ -866,7 +869,7 @@ __global__ __launch_bounds__(256, 4) void pn_exact_kernel(const f32x4* __restric
     __shared__ short all_list[1024];
     __shared__ int pair_count, fb_count, all_count;
     __shared__ float fb_part[4][16];
-    __shared__ float hm[PN_MAX_TILES], dm[PN_MAX_TILES], rd[PN_MAX_TILES];
+    __shared__ float hm[PN_MAX_TILES], dm[PN_MAX_TILES], rd[PN_MAX_TILES], ef[PN_MAX_TILES];   // ef: the id bits' floor of E_t (bound_of)
     __shared__ unsigned best_k[1024];
     __shared__ float wcs[1024];                            // w_n . c per channel (rule 2, consistency check)
     __shared__ int pcnt[1024];                             // pairs per point -> first slot of the point -> fill cursor
@@ -893,6 +896,7 @@ __global__ __launch_bounds__(256, 4) void pn_exact_kernel(const f32x4* __restric
         hm[tid] = __uint_as_float(ts[0]) * 1.00001f;
         dm[tid] = __uint_as_float(ts[1]) * 1.00001f;
         rd[tid] = __uint_as_float(ts[2]) * 1.00001f;
+        ef[tid] = E_ID_FLOOR * fmaxf(1.0f, 0x1p-13f * (__uint_as_float(ts[1]) * 1.00001f));
         nonfinite_point = ts[3] != 0 && !(abl & PN_ABL_STAMPS);      // (word 3 holds the phase stamps of the diagnostics build otherwise)
     }
     if (__syncthreads_or(nonfinite_point)) {
@@ -909,8 +913,15 @@ __global__ __launch_bounds__(256, 4) void pn_exact_kernel(const f32x4* __restric
     unsigned long long tp[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     if (stamps) tp[0] = __builtin_amdgcn_s_memtime();
     unsigned n_single = 0, n_multi = 0, n_cand = 0, n_wave = 0, n_suspect = 0;
-    // E_t of channel (wn, rn)
-    auto bound_of = [&](float wn, float rn, int t) { return fmaf(rn, dm[t], fmaf(wn, rd[t], fmaf(C_ID * wn, dm[t], 2.0f * DELTA * wn * hm[t]))); };
+    // E_t of channel (wn, rn).  C_ID covers the id bits RELATIVE to a score: 2^-15 of a normal number.  A score that is zero (or
+    // denormal) in the trunk kernel's scaled units carries them as an ABSOLUTE 2^-141, which becomes 2^-141 / (s_w 2^t_n) in real
+    // units, and the group tag replaces bits of the real value once more.  For a conv3 row of zeros (a channel whose BatchNorm gamma is
+    // 0: w_n = r_n = 0, 2^t_n = 1) every other term is 0 and the records' interval was the single value "id bits" -- the exact maximum,
+    // 0, lay outside it, and every such channel was counted and re-evaluated over all points.  1 / s_w <= max(1, 2^-13 max|d_p|)
+    // (the wave's largest row norm times s_w is at least 2^14; s_w = 1 outside the exponent guard), hence the floor; rows with weights
+    // have 2^-t_n <= 2^-14 |w_n| in front of it, far below the C_ID term.
+    // (the floor is the innermost addend: a NaN / Inf term stays one and sends the channel to the "everything" path)
+    auto bound_of = [&](float wn, float rn, int t) { return fmaf(rn, dm[t], fmaf(wn, rd[t], fmaf(C_ID * wn, dm[t], fmaf(2.0f * DELTA * wn, hm[t], ef[t])))); };
     // The interval the records promise for (max - w.c) of channel n: lb = max_t (c1_t - E_t), ub = max_t (c1_t + E_t); the first tile
     // that attains lb and its top score (the anchor); the largest bound.  top0 .. top3: c1 of the first four tiles (N <= 1024: all of
     // them), requested by the caller ahead of time; the tiles beyond are read here, in blocks of four.  A non-finite bound or top score
