@@ -89,14 +89,68 @@ def refine_translation(topology, hand_xyz, obj_xyz, steps, push=1.0, pull=0.25, 
     return {"offset": offset, "iter": it, "penetration": pen, "n_interior": n_in, "n_contact": n_ct}
 
 
-SELECT_BY = ("penetration", "log_prob")
+def grasp_stability(topology, hand_xyz, obj_xyz, length=0.1, contact_threshold=0.02 ** 2):
+    """A force-closure proxy from ONE fused kernel (ops.grasp_wrench; the definition is in include/dvq.h under dvq_grasp_wrench):
+    every object point within the contact threshold of the hand pushes with a unit force along the normal of its nearest hand vertex
+    (frictionless), and its torque is taken about the cloud's centre with the arm divided by ``length``.  Returns the three scores of
+    ``grasp_scores`` (the same bits: the selection path launches this kernel INSTEAD of that one) plus ``centre`` [B,3], ``sums``
+    [B,27] (the summed wrench, then the upper triangle of sum w w^T: ``wrench_stats`` turns them into figures) and ``key`` [B] =
+    |sum of the wrenches|^2 / n_contact^2, +inf without a contact, NaN with a NaN penetration -- smaller means the unit contact
+    forces cancel better.
+
+    ``length`` is in metres; 0.1 is a hand-sized default and is UNTUNED, as is the unit-force model.  This is a proxy: it replaces no
+    physics run, and its effect on real grasps is NOT measured (no real checkpoint)."""
+    length = float(length)
+    if not 0.0 < length < float("inf"):
+        raise RuntimeError(f"grasp_stability: length must be finite and positive (got {length})")
+    pen, n_in, n_ct, centre, sums, key = ops.grasp_wrench(hand_xyz.contiguous(), topology.faces, topology.vf_off, topology.vf_face,
+                                                          obj_xyz, 1.0 / length, contact_threshold)
+    return {"penetration": pen, "n_interior": n_in, "n_contact": n_ct, "centre": centre, "sums": sums, "key": key}
 
 
-def select_keys(scores, select_by, min_contact, log_prob=None):
+def wrench_stats(sums, n_contact):
+    """Host side, float64: per grasp, from ``grasp_stability``'s ``sums`` [B,27] and ``n_contact`` [B] (arrays or tensors),
+    ``force_residual`` = |S[0:3]| / n (in [0,1]: 0 = the unit forces cancel, 1 = they all point one way), ``torque_residual`` =
+    |S[3:6]| / n and ``min_sv`` = sqrt(max(lambda_min(G / n), 0)) with G the symmetric 6x6 matrix of columns 6 .. 26 (the smallest
+    singular value of the grasp matrix over sqrt(n): 0 = some wrench direction no contact resists).  Three lists of floats, ``None``
+    where n == 0 or a sum is not finite (json writes null).  A sphere-like contact patch has near-zero torque rows, so ``min_sv`` is small there by
+    construction."""
+    s = np.asarray(sums.detach().cpu() if torch.is_tensor(sums) else sums, dtype=np.float64).reshape(-1, 27)
+    n = np.asarray(n_contact.detach().cpu() if torch.is_tensor(n_contact) else n_contact, dtype=np.int64).reshape(-1)
+    if n.shape[0] != s.shape[0]:
+        raise RuntimeError("wrench_stats: one n_contact per row of sums")
+    iu = np.triu_indices(6)
+    force, torque, min_sv = [], [], []
+    for row, k in zip(s, n):
+        if k <= 0 or not np.isfinite(row).all():                # no contact, or a grasp with a NaN / inf in it: no figure
+            force.append(None), torque.append(None), min_sv.append(None)
+            continue
+        g = np.zeros((6, 6))
+        g[iu] = row[6:]
+        g = g + np.triu(g, 1).T
+        force.append(float(np.sqrt(np.sum(row[0:3] ** 2)) / k))
+        torque.append(float(np.sqrt(np.sum(row[3:6] ** 2)) / k))
+        min_sv.append(float(np.sqrt(max(float(np.linalg.eigvalsh(g / k)[0]), 0.0))))
+    return {"force_residual": force, "torque_residual": torque, "min_sv": min_sv}
+
+
+SELECT_BY = ("penetration", "log_prob", "stability")
+
+
+def select_keys(scores, select_by, min_contact, log_prob=None, max_penetration=float("inf")):
     """(cls int32 [B], key f32 [B]) for ``ops.segment_topk`` -- smaller is better, row by row:
     ``"penetration"``: cls 2 where the penetration is NaN, else 1 where the hand touches fewer than ``min_contact`` object
     points (a hand far from the object penetrates nothing), else 0; key = penetration.
-    ``"log_prob"``: cls 2 where it is NaN, else 0; key = -log_prob (likeliest first)."""
+    ``"log_prob"``: cls 2 where it is NaN, else 0; key = -log_prob (likeliest first).
+    ``"stability"`` (``scores`` of ``grasp_stability``): cls 2 where the penetration is NaN, else 1 where the hand touches fewer than
+    ``min_contact`` object points or penetrates more than ``max_penetration``, else 0; key = the kernel's ``key``.  Ranking by
+    stability alone rewards hands that wrap the object by sinking into it: ``max_penetration`` (default +inf: no limit) is the
+    caller's guard against that."""
+    if select_by == "stability":
+        pen = scores["penetration"]
+        poor = (scores["n_contact"] < int(min_contact)) | (pen > float(max_penetration))
+        cls = torch.where(torch.isnan(pen), 2, torch.where(poor, 1, 0))
+        return cls.to(torch.int32), scores["key"]
     if select_by == "penetration":
         pen = scores["penetration"]
         cls = torch.where(torch.isnan(pen), 2, torch.where(scores["n_contact"] < int(min_contact), 1, 0))

@@ -69,8 +69,9 @@ def build_parser(dataset: str) -> argparse.ArgumentParser:
     p.add_argument("--candidates", type=int, default=0,
                    help="best-of-M: generate this many candidates per object, score them on the device and keep the num_grasp best "
                         "(0 = off; otherwise >= num_grasp); the JSON gains \"candidate\", \"penetration\", \"n_interior\", \"n_contact\"")
-    p.add_argument("--select_by", choices=["penetration", "log_prob"], default="penetration",
-                   help="what ranks the candidates: least penetration among the hands that touch the object, or the prior's log-likelihood")
+    p.add_argument("--select_by", choices=["penetration", "log_prob", "stability"], default="penetration",
+                   help="what ranks the candidates: least penetration among the hands that touch the object, the prior's log-likelihood, "
+                        "or the contact-wrench stability proxy (smallest net wrench of unit contact forces; untuned, see --stability)")
     p.add_argument("--min_contact", type=int, default=1,
                    help="--select_by penetration: hands with fewer object points within 2 cm rank after all others")
     p.add_argument("--diverse_pool", type=int, default=0,
@@ -88,6 +89,16 @@ def build_parser(dataset: str) -> argparse.ArgumentParser:
                         "paper uses 20; <= num_grasp and <= 64) over each object's [num_grasp,61] parameters, one deterministic run "
                         "from evenly spaced starting rows; 0 = off; every JSON gains \"diversity\" (clusters, entropy, mean_dist, "
                         "iters, counts) and the run writes the pooled statistic of all its grasps to diversity.json")
+    p.add_argument("--stability", type=int, default=0,
+                   help="1: every grasp's JSON gains \"force_residual\", \"torque_residual\", \"min_sv\" and \"stability_key\" (beside the "
+                        "three scores): a frictionless unit-force force-closure proxy over the contact wrenches, without selecting by it "
+                        "(--select_by stability writes them too); null where the hand touches nothing; a proxy with untuned constants that "
+                        "replaces no physics run, effect on real grasps not measured")
+    p.add_argument("--max_penetration", type=float, default=float("inf"),
+                   help="--select_by stability: hands that penetrate more than this (the \"penetration\" score) rank after all others -- "
+                        "the guard against hands that wrap the object by sinking into it (default: no limit)")
+    p.add_argument("--torque_length", type=float, default=0.1,
+                   help="--stability / --select_by stability: the length in metres that scales torques to forces (hand-sized default, untuned)")
     p.add_argument("--refine_push", type=float, default=1.0, help="--refine_steps: step factor on the mean pull vector of the interior points")
     p.add_argument("--refine_pull", type=float, default=0.25,
                    help="--refine_steps: step factor on the mean pull vector of the points within 2 cm outside the hand")
@@ -112,6 +123,10 @@ def parse_args(dataset: str, argv: Optional[Sequence[str]] = None) -> argparse.N
         p.error(f"--refine_steps must lie between 0 and {ops.GRASP_REFINE_MAX_STEPS} (got {args.refine_steps})")
     if not (0.0 <= args.refine_push < float("inf") and 0.0 <= args.refine_pull < float("inf")):
         p.error(f"--refine_push and --refine_pull must be finite and >= 0 (got {args.refine_push}, {args.refine_pull})")
+    if not 0.0 < args.torque_length < float("inf"):
+        p.error(f"--torque_length must be finite and positive (got {args.torque_length})")
+    if not args.max_penetration >= 0.0:
+        p.error(f"--max_penetration must be >= 0 (got {args.max_penetration})")
     return args
 
 
@@ -260,7 +275,8 @@ def _generate_call(net: GenNet, objs: Sequence[torch.Tensor], num_grasp: int, ro
                    object_indices: Sequence[int], proxies: bool, temperature: float = 1.0, top_k: int = 0,
                    log_prob: bool = False, candidates: int = 0, select_by: str = "penetration",
                    min_contact: int = 1, diverse_pool: int = 0, diverse_space: str = "params", refine_steps: int = 0,
-                   refine_push: float = 1.0, refine_pull: float = 0.25, diversity: int = 0) -> List[Dict[str, object]]:
+                   refine_push: float = 1.0, refine_pull: float = 0.25, diversity: int = 0, stability: bool = False,
+                   max_penetration: float = float("inf"), torque_length: float = 0.1) -> List[Dict[str, object]]:
     """One batched call: the ``num_grasp`` grasps of each of ``objs`` (all of one point count), row o * num_grasp + g = grasp g
     of object o.  Every step is row-independent and keyed per row, so each object's slice holds the bits of its own
     ``generate_for_object`` call.  With ``candidates`` = M the call generates M rows per object (exactly the grasps of a
@@ -268,7 +284,9 @@ def _generate_call(net: GenNet, objs: Sequence[torch.Tensor], num_grasp: int, ro
     is first pushed out of its cloud (contact.refine_translation: one kernel), the offsets are added to the translations and MANO is
     posed again, so that everything after it -- scores, selection, the rows returned -- sees the hands of the parameters written.
     With ``diversity`` = K the kept parameters of every object go through one ``ops.segment_kmeans`` (one segment per object) and its
-    counts and distances ride in the call's one device-to-host copy (_diversity_launch / _diversity_dicts)."""
+    counts and distances ride in the call's one device-to-host copy (_diversity_launch / _diversity_dicts).  With ``stability`` the
+    scores come from ``contact.grasp_stability`` (one kernel in the place of ``contact.grasp_scores``) and its sums and key ride
+    in that copy too (_stability_json)."""
     dev = next(net.parameters()).device
     keep = num_grasp
     G, O = (candidates or num_grasp), len(objs)
@@ -305,18 +323,33 @@ def _generate_call(net: GenNet, objs: Sequence[torch.Tensor], num_grasp: int, ro
                             transl=params[:, 58:61])
     if candidates:
         return _select_call(net, batch, params, final.vertices, logp, err, O, G, keep, select_by, min_contact, want_logp, proxies,
-                            np.concatenate(Rs), np.concatenate(angles), t, diverse_pool, diverse_space, refined, diversity)
+                            np.concatenate(Rs), np.concatenate(angles), t, diverse_pool, diverse_space, refined, diversity, stability,
+                            max_penetration, torque_length)
     ref_lists = {}
     div = _diversity_launch(params, O, G, diversity) if diversity else []
-    if refined is not None:                                                        # the scores of the hands written, and the one copy
-        scores = contact.grasp_scores(topo, final.vertices, batch[:, :3].transpose(1, 2))
-        names = ["refine_offset", "refine_iter", "penetration", "n_interior", "n_contact"]
-        tensors = {"refine_offset": refined["offset"], "refine_iter": refined["iter"], **scores}
+    if refined is not None or stability:                                           # the scores of the hands written, and the one copy
+        from . import contact
+        cloud_xyz = batch[:, :3].transpose(1, 2)
+        names = ["penetration", "n_interior", "n_contact"]
+        if stability:
+            topo = _hand_topology(net, final.vertices.shape[1], dev)
+            scores = contact.grasp_stability(topo, final.vertices, cloud_xyz, torque_length)
+            names = names + ["sums", "key"]
+        else:
+            scores = contact.grasp_scores(topo, final.vertices, cloud_xyz)
+        tensors = dict(scores)
+        if refined is not None:
+            names = ["refine_offset", "refine_iter"] + names
+            tensors.update(refine_offset=refined["offset"], refine_iter=refined["iter"])
         host, *rest_h, err_h = _host_copy([params] + [tensors[k] for k in names] + div + [err])   # ONE device-to-host copy per call
         if int(err_h[0]) != 0:
             raise RuntimeError("generate_for_objects: object index out of range in transform_clouds")
-        ref_lists = {k: h.tolist() for k, h in zip(names, rest_h)}
-        div_h = rest_h[len(names):]
+        by_name = dict(zip(names, rest_h))
+        names = [k for k in names if k not in ("sums", "key")]
+        ref_lists = {k: by_name[k].tolist() for k in names}
+        if stability:
+            ref_lists.update(_stability_json(by_name["sums"], by_name["n_contact"], by_name["key"]))
+        div_h = rest_h[len(by_name):]
     elif div:
         host, *div_h, err_h = _host_copy([params] + div + [err])                   # ONE device-to-host copy per call
         if int(err_h[0]) != 0:
@@ -346,9 +379,11 @@ def _generate_call(net: GenNet, objs: Sequence[torch.Tensor], num_grasp: int, ro
         if proxies:                                                                # per object: the reductions see the loop's shapes
             from . import contact
             extra["proxies"] = contact.grasp_proxies(topo, final.vertices[lo:hi], batch[lo:hi, :3].transpose(1, 2))
-        if refined is not None:
+        if ref_lists:
             extra.update({k: tensors[k][lo:hi] for k in names})
-            extra_json.update({k: ref_lists[k][lo:hi] for k in names})
+            if stability:
+                extra.update(wrench_sums=tensors["sums"][lo:hi], stability_key=tensors["key"][lo:hi])
+            extra_json.update({k: v[lo:hi] for k, v in ref_lists.items()})
         if diversity:
             extra["diversity"] = extra_json["diversity"] = div_dicts[o]
         outs.append({**extra, "params": p_dev[o], "vertices": v_dev[o],
@@ -366,6 +401,16 @@ def _host_copy(pieces: Sequence[torch.Tensor]) -> List[np.ndarray]:
         dt = {torch.float32: np.float32, torch.int32: np.int32, torch.int64: np.int64}[p.dtype]
         out.append(host[lo:lo + f.numel()].view(dt).reshape(tuple(p.shape)))
         lo += f.numel()
+    return out
+
+
+def _stability_json(sums: np.ndarray, n_contact: np.ndarray, key: np.ndarray) -> Dict[str, list]:
+    """``--stability`` / ``--select_by stability``: the four JSON lists of a call's rows from the host copies of the kernel's sums,
+    contact counts and keys -- float64 on the host, row by row (contact.wrench_stats), so that a grasp's figures do not depend on which
+    rows share the call.  A hand that touches nothing has no figure: null, and so has a key that is not finite."""
+    from . import contact
+    out = contact.wrench_stats(sums, n_contact)
+    out["stability_key"] = [float(k) if np.isfinite(k) else None for k in key]
     return out
 
 
@@ -394,7 +439,8 @@ def _select_call(net: GenNet, batch: torch.Tensor, params: torch.Tensor, vertice
                  err: torch.Tensor, O: int, M: int, keep: int, select_by: str, min_contact: int, want_logp: bool, proxies: bool,
                  R: np.ndarray, angles: np.ndarray, t: np.ndarray, diverse_pool: int = 0,
                  diverse_space: str = "params", refined: Optional[Dict[str, torch.Tensor]] = None,
-                 diversity: int = 0) -> List[Dict[str, object]]:
+                 diversity: int = 0, stability: bool = False, max_penetration: float = float("inf"),
+                 torque_length: float = 0.1) -> List[Dict[str, object]]:
     """Best-of-M for all the objects of a call together: the candidates' scores (one fused kernel), their keys, each object's
     ``keep`` best (one kernel), one ``index_select`` of the kept rows and one device-to-host copy.  Row o * M + c is candidate c of
     object o; nothing here depends on which objects share the call.  ``diverse_pool`` = P: each object's P best (the same kernel),
@@ -402,14 +448,18 @@ def _select_call(net: GenNet, batch: torch.Tensor, params: torch.Tensor, vertice
     posed vertices, read in place); their pool positions and squared gaps ride along in the one copy.  ``refined``: the call's
     rows were pushed out before (contact.refine_translation's dict; ``params`` and ``vertices`` are the refined ones): the kept rows'
     offsets and iterates ride along too.  ``diversity``: the k-means statistic of the kept parameters (_diversity_launch) rides along
-    as well."""
+    as well.  ``stability``: the candidates' scores come from ``contact.grasp_stability`` (the one kernel in the place of
+    ``contact.grasp_scores``); the kept rows' sums and keys ride along and become the four JSON fields of _stability_json."""
     from . import contact
     dev = params.device
     topo = _hand_topology(net, vertices.shape[1], dev)
-    scores = contact.grasp_scores(topo, vertices, batch[:, :3].transpose(1, 2))
+    if stability:
+        scores = contact.grasp_stability(topo, vertices, batch[:, :3].transpose(1, 2), torque_length)
+    else:
+        scores = contact.grasp_scores(topo, vertices, batch[:, :3].transpose(1, 2))
     if logp is not None:
         scores["log_prob"] = logp
-    cls, key = contact.select_keys(scores, select_by, min_contact, log_prob=logp)
+    cls, key = contact.select_keys(scores, select_by, min_contact, log_prob=logp, max_penetration=max_penetration)
     diverse = []
     if diverse_pool:
         pool = ops.segment_topk(cls.contiguous(), key.contiguous(), O, M, diverse_pool)   # [O,P] candidate indices, best first
@@ -429,7 +479,11 @@ def _select_call(net: GenNet, batch: torch.Tensor, params: torch.Tensor, vertice
     if int(host[-1][0]) != 0:
         raise RuntimeError("generate_for_objects: object index out of range in transform_clouds")
     sel_h, p_list = host[0], host[1].tolist()
-    s_list = {k: h.tolist() for k, h in zip(names, host[2:2 + len(names)])}
+    s_list = {k: h.tolist() for k, h in zip(names, host[2:2 + len(names)]) if k not in ("centre", "sums", "key")}
+    stab_lists = {}
+    if stability:
+        s_host = dict(zip(names, host[2:2 + len(names)]))
+        stab_lists = _stability_json(s_host["sums"], s_host["n_contact"], s_host["key"])
     if refined is not None:
         off_list, it_list = (h.tolist() for h in host[2 + len(names):4 + len(names)])
     if diverse_pool:
@@ -452,10 +506,12 @@ def _select_call(net: GenNet, batch: torch.Tensor, params: torch.Tensor, vertice
         extra = {"log_prob": kept_s["log_prob"][lo:hi]} if "log_prob" in json_scores else {}
         if proxies:                                                                # of the kept grasps, as the plain path returns them
             extra["proxies"] = contact.grasp_proxies(topo, v_dev[o], batch.index_select(0, rows[lo:hi])[:, :3].transpose(1, 2))
-        extra_json = {}
+        extra_json = {k: v[lo:hi] for k, v in stab_lists.items()}
+        if stability:
+            extra["wrench_sums"], extra["stability_key"] = kept_s["sums"][lo:hi], kept_s["key"][lo:hi]
         if diverse_pool:
             extra["rank"], extra["novelty"] = rank[o], gap[o]
-            extra_json = {"rank": rank_list[o], "novelty": gap_list[o]}
+            extra_json = {**extra_json, "rank": rank_list[o], "novelty": gap_list[o]}
         if refined is not None:
             extra["refine_offset"], extra["refine_iter"] = kept_r[0][lo:hi], kept_r[1][lo:hi]
             extra_json = {**extra_json, "refine_offset": off_list[lo:hi], "refine_iter": it_list[lo:hi]}
@@ -474,7 +530,8 @@ def generate_for_objects(net: GenNet, objs: Sequence[torch.Tensor], num_grasp: i
                          object_indices: Sequence[int], proxies: bool = False, rows_per_call: int = 16384, temperature: float = 1.0,
                          top_k: int = 0, log_prob: bool = False, candidates: int = 0, select_by: str = "penetration",
                          min_contact: int = 1, diverse_pool: int = 0, diverse_space: str = "params", refine_steps: int = 0,
-                         refine_push: float = 1.0, refine_pull: float = 0.25, diversity: int = 0) -> List[Dict[str, object]]:
+                         refine_push: float = 1.0, refine_pull: float = 0.25, diversity: int = 0, stability: bool = False,
+                         max_penetration: float = float("inf"), torque_length: float = 0.1) -> List[Dict[str, object]]:
     """``num_grasp`` grasps for each of ``objs`` ([4,N] tensors) in batched calls that mix objects (plan_calls): one dict per
     object, in the order given, equal to ``generate_for_object(net, objs[i], num_grasp, rotate,
     np.random.default_rng([seed, object_indices[i]]), seed=seed, object_index=object_indices[i], proxies=proxies)`` (and the same
@@ -513,7 +570,24 @@ def generate_for_objects(net: GenNet, objs: Sequence[torch.Tensor], num_grasp: i
     starting rows, at most 100 iterations); counts and distances ride in the call's one device-to-host copy and the two floats are
     computed per object on the host (``diversity.kmeans_statistics``).  Each dict and each ``json`` gains ``"diversity"``: a dict of
     clusters, entropy, mean_dist, iters and counts -- one deterministic run, not scipy's best of 20 random starts
-    (``diversity.diversity``).  ``diversity = 0`` is the call without the keyword."""
+    (``diversity.diversity``).  ``diversity = 0`` is the call without the keyword.
+
+    Stability proxy (``stability=True``, or ``select_by="stability"`` together with ``candidates``): the scores of a call come from
+    ``contact.grasp_stability`` -- ONE kernel in the place of ``contact.grasp_scores``, after the push-out has re-posed the hands if
+    there is one -- with ``torque_length`` as its length.  ``select_by="stability"`` ranks the candidates by its key (``min_contact``
+    and ``max_penetration`` set the class, ``contact.select_keys``).  Each dict gains ``wrench_sums`` [num_grasp,27] and
+    ``stability_key`` [num_grasp] (and ``scores`` gains centre, sums and key of all candidates); ``json`` gains "force_residual",
+    "torque_residual", "min_sv" and "stability_key" per grasp (``contact.wrench_stats``, float64 on the host; null where the hand
+    touches nothing) and, without ``candidates``, the three scores as well.  The sums ride in the call's one device-to-host copy.
+    A frictionless unit-force proxy with untuned constants: it replaces no physics run and its effect on real grasps is not
+    measured.  Without either switch nothing of it runs."""
+    stability = bool(stability) or (bool(candidates) and select_by == "stability")
+    if stability:
+        if not 0.0 < float(torque_length) < float("inf"):
+            raise RuntimeError(f"generate_for_objects: torque_length must be finite and positive (got {torque_length})")
+        if not float(max_penetration) >= 0.0:
+            raise RuntimeError(f"generate_for_objects: max_penetration must be >= 0 (got {max_penetration})")
+        _hand_faces(net)                                                           # no face list: raise before any work
     if len(object_indices) != len(objs):
         raise RuntimeError("generate_for_objects: one object index per object")
     if diverse_pool:
@@ -547,7 +621,7 @@ def generate_for_objects(net: GenNet, objs: Sequence[torch.Tensor], num_grasp: i
     for call in plan_calls([o.shape[1] for o in objs], candidates or num_grasp, rows_per_call):
         res = _generate_call(net, [objs[p] for p in call], num_grasp, rotate, seed, [object_indices[p] for p in call], proxies,
                              temperature, top_k, log_prob, candidates, select_by, min_contact, diverse_pool, diverse_space, refine_steps,
-                             refine_push, refine_pull, diversity)
+                             refine_push, refine_pull, diversity, stability, max_penetration, torque_length)
         for p, r in zip(call, res):
             out[p] = r
     return out
@@ -576,8 +650,9 @@ def main(dataset: str, argv: Optional[Sequence[str]] = None) -> List[str]:
     if args.diversity and (hi - lo) * args.num_grasp > ops.SEGMENT_KMEANS_MAX_M:
         raise RuntimeError(f"--diversity: the pooled statistic takes at most {ops.SEGMENT_KMEANS_MAX_M} grasps per rank "
                            f"(got {(hi - lo) * args.num_grasp})")
-    if args.rows_per_call > 0 or args.candidates or args.refine_steps or args.diversity:
-        # grouped calls (best-of-M, push-out and the diversity statistic always: --rows_per_call 0 is then one object per call)
+    if args.rows_per_call > 0 or args.candidates or args.refine_steps or args.diversity or args.stability:
+        # grouped calls (best-of-M, push-out, the diversity statistic and the stability proxy always: --rows_per_call 0 is then one
+        # object per call)
         rows_per_call, per_object = max(1, args.rows_per_call), (args.candidates or args.num_grasp)
         selection = dict(candidates=args.candidates, select_by=args.select_by, min_contact=args.min_contact) if args.candidates else {}
         if args.diverse_pool:
@@ -587,6 +662,8 @@ def main(dataset: str, argv: Optional[Sequence[str]] = None) -> List[str]:
                              min_contact=args.min_contact)
         if args.diversity:
             selection.update(diversity=args.diversity)
+        if args.stability or (args.candidates and args.select_by == "stability"):
+            selection.update(stability=True, max_penetration=args.max_penetration, torque_length=args.torque_length)
         kept: Dict[int, np.ndarray] = {}                                           # --diversity: every object's kept parameters, on the host
         # grouped calls: one call's objects at a time, its files written before the next call starts, so the device and the host
         # hold one call's results, not the whole list's

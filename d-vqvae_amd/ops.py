@@ -741,6 +741,50 @@ def grasp_scores(hand: Tensor, faces: Tensor, vf_off: Tensor, vf_face: Tensor, o
     return pen, n_in, n_ct
 
 
+GRASP_WRENCH_SUMS = 27             # csrc/grasp_wrench.hip: GW_SUMS (the wrench's 6 sums, then the upper triangle of sum w w^T)
+
+
+def grasp_wrench(hand: Tensor, faces: Tensor, vf_off: Tensor, vf_face: Tensor, obj: Tensor, inv_length: float,
+                 contact_threshold: float = 0.02 ** 2):
+    """The contact-wrench sums of every grasp in one fused kernel (dvq_grasp_wrench; the definition is in include/dvq.h):
+    ``(penetration [B] f32, n_interior [B] i32, n_contact [B] i32, centre [B,3] f32, sums [B,27] f32, key [B] f32)``.  The first
+    three are the bits of ``grasp_scores``; ``inv_length`` is the reciprocal of the length that scales torques to forces.
+    Arguments as ``grasp_scores`` (obj [B,N,3] with any strides, read in place)."""
+    for t, n in ((hand, "hand"), (obj, "obj"), (faces, "faces"), (vf_off, "vf_off"), (vf_face, "vf_face")):
+        if not isinstance(t, Tensor):
+            raise RuntimeError(f"grasp_wrench: {n} must be a tensor")
+    _f32(hand, "hand")
+    for t, n in ((faces, "faces"), (vf_off, "vf_off"), (vf_face, "vf_face")):
+        if t.dtype != torch.int32 or not t.is_contiguous():
+            raise RuntimeError(f"grasp_wrench: {n} must be contiguous int32")
+    if hand.dim() != 3 or hand.shape[2] != 3 or not hand.is_contiguous():
+        raise RuntimeError("grasp_wrench: hand must be contiguous [B,V,3]")
+    po, ob, op, oc = _points(obj, "obj")
+    B, V, N = hand.shape[0], hand.shape[1], obj.shape[1]
+    if obj.shape[0] != B:
+        raise RuntimeError("grasp_wrench: batch mismatch")
+    if N < 1 or not 1 <= V <= GRASP_SCORES_MAX_V:
+        raise RuntimeError(f"grasp_wrench: need N >= 1 and 1 <= V <= {GRASP_SCORES_MAX_V} (got N={N} V={V})")
+    if faces.dim() != 2 or faces.shape[1] != 3 or vf_off.numel() != V + 1 or vf_face.numel() != faces.numel():
+        raise RuntimeError("grasp_wrench: CSR does not match the mesh")
+    inv_length = float(inv_length)
+    if not 0.0 < inv_length < float("inf"):
+        raise RuntimeError(f"grasp_wrench: inv_length must be finite and positive (got {inv_length})")
+    dev = _require_gpu(hand, obj, faces, vf_off, vf_face)
+    lib = _lib.load()
+    pen = torch.empty(B, dtype=torch.float32, device=dev)
+    n_in = torch.empty(B, dtype=torch.int32, device=dev)
+    n_ct = torch.empty(B, dtype=torch.int32, device=dev)
+    centre = torch.empty(B, 3, dtype=torch.float32, device=dev)
+    sums = torch.empty(B, GRASP_WRENCH_SUMS, dtype=torch.float32, device=dev)
+    key = torch.empty(B, dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        check(lib.dvq_grasp_wrench(hand.data_ptr(), faces.data_ptr(), vf_off.data_ptr(), vf_face.data_ptr(), V, po, ob, op, oc, B, N,
+                                   float(contact_threshold), inv_length, pen.data_ptr(), n_in.data_ptr(), n_ct.data_ptr(),
+                                   centre.data_ptr(), sums.data_ptr(), key.data_ptr(), _stream(dev)), "dvq_grasp_wrench")
+    return pen, n_in, n_ct, centre, sums, key
+
+
 GRASP_REFINE_MAX_STEPS = 64        # csrc/grasp_refine.hip: GR_MAX_STEPS
 
 

@@ -42,7 +42,7 @@ typedef enum {
 #define DVQ_ABI_VERSION 10
 /* Entry points added since 10 without touching a struct or a signature of it (a compatible extension: bindings of 10 keep
  * working, the version stays): dvq_pixelcnn_sample_ctl, dvq_grasp_scores, dvq_segment_topk, dvq_segment_diverse,
- * dvq_grasp_refine, dvq_segment_kmeans. */
+ * dvq_grasp_refine, dvq_segment_kmeans, dvq_grasp_wrench. */
 int dvq_abi_version(void);
 const char* dvq_last_error(void);
 /* number of visible HIP devices, or -1; does not create a context */
@@ -417,6 +417,39 @@ int dvq_grasp_refine(const float* hand /* [B,V,3] */, const int32_t* faces, cons
                      int64_t B, int N, float contact_threshold, int steps, float push, float pull, int min_contact,
                      float* offset /* [B,3] */, int32_t* iter /* [B] */, float* penetration /* [B] */, int32_t* n_interior /* [B] */,
                      int32_t* n_contact /* [B] */, dvq_stream_t stream);
+/* Grasp stability proxy: the contact-wrench sums of a grasp and a ranking key from them, with the three scores of dvq_grasp_scores,
+ * in ONE kernel, one workgroup of 256 threads per grasp.  New here: the reference judges whether the object stays in the hand by a
+ * physics run (pybullet + V-HACD, out of scope); this is the usual cheap stand-in, a force-closure figure over the contact wrenches:
+ * every object point within the contact threshold of the hand is a contact that pushes with a UNIT force along the normal of its
+ * nearest hand vertex, frictionless.  27 sums per grasp -- the 6-vector sum of the wrenches and the upper triangle of sum w w^T --
+ * give the net wrench of unit contact forces (the force-closure term of differentiable grasp synthesis, |G c|) and, on the host, the
+ * smallest singular value of the grasp matrix (Li & Sastry's Q_MSV).  A PROXY: the force model and the torque length are untuned,
+ * it replaces no physics run, and its effect on real grasps is NOT MEASURED (no real checkpoint was available).
+ * Inputs exactly as dvq_grasp_scores (hand [B,V,3] contiguous, the topology, obj with strides in floats: a channel-first cloud is
+ * read in place) plus inv_length, the reciprocal of the length that makes torques commensurate with forces.
+ * "The canonical sum" below is the reduction of dvq_grasp_scores: thread t (0 .. 255) starts from +0.0f and adds the terms of its
+ * points p = t, t + 256, ... in ascending p (fp32 additions); then the tree  for s in 128, 64, ..., 1: part[t] += part[t + s] for
+ * every t < s.  Per grasp:
+ *   1. centre.x = (the canonical sum of obj.x over all N points) / (float)N, an fp32 IEEE division; .y and .z likewise.
+ *   2. per point p: normals, d, j, inside and term exactly as dvq_grasp_scores defines them; contact = d < contact_threshold, the
+ *      set that n_contact counts.
+ *   3. per point p: force f = n[j]; arm r = ((obj.x - centre.x) * inv_length, (obj.y - centre.y) * inv_length, (obj.z - centre.z) *
+ *      inv_length); torque tau = (r.y*f.z - r.z*f.y, r.z*f.x - r.x*f.z, r.x*f.y - r.y*f.x), every product rounded, no fma; wrench
+ *      w = (f.x, f.y, f.z, tau.x, tau.y, tau.z).
+ *   4. the 27 terms of point p: w[a] for a = 0 .. 5 (columns 0 .. 5), then w[a] * w[b] for a <= b in row-major order of the upper
+ *      triangle (columns 6 .. 26: 00 01 02 03 04 05 11 12 ... 55); each term is its value when contact holds and +0.0f otherwise;
+ *      sums[b][c] = the canonical sum of column c.
+ *   5. with S = sums[b]: q = fma(S5,S5, fma(S4,S4, fma(S3,S3, fma(S2,S2, fma(S1,S1, S0*S0))))), nf = (float)n_contact;
+ *      key = NaN when penetration is NaN, otherwise +inf when n_contact == 0, otherwise q / (nf * nf) (fp32, IEEE division).
+ *      A smaller key means the unit contact forces cancel better.
+ * Outputs: penetration, n_interior, n_contact [B]: the bits of dvq_grasp_scores on the same inputs; centre [B,3]; sums [B,27];
+ * key [B].  A grasp's outputs depend on neither B nor its row.
+ * B >= 0, N >= 1, 1 <= V <= 2048, no null pointer; anything else is DVQ_EINVAL, nothing launched. */
+int dvq_grasp_wrench(const float* hand /* [B,V,3] */, const int32_t* faces, const int32_t* vf_off, const int32_t* vf_face, int V,
+                     const float* obj, int64_t obj_batch_stride, int64_t obj_point_stride, int64_t obj_coord_stride,
+                     int64_t B, int N, float contact_threshold, float inv_length, float* penetration /* [B] */,
+                     int32_t* n_interior /* [B] */, int32_t* n_contact /* [B] */, float* centre /* [B,3] */, float* sums /* [B,27] */,
+                     float* key /* [B] */, dvq_stream_t stream);
 /* Per-object selection: cls, key [O*M] (candidate c of object o at o * M + c) -> sel [O,keep]: the candidate indices (0 .. M-1) of
  * each object's keep best candidates, best first.  Candidate a ranks before b iff (cls, key, index) is smaller: cls as signed
  * integers; within a class a NaN key sorts after every number and -0.0 == +0.0; the index breaks every tie.  One workgroup per
