@@ -485,7 +485,9 @@ def pixelcnn_sample(packed, label: Tensor, noise: Optional[Tensor], return_logit
         if e & 1:
             raise RuntimeError(f"label or given code out of range for the prior's {packed.n_classes} classes / {packed.n_in} tokens"
                                if controlled else f"label out of range for the prior's {packed.n_classes} classes")
-        if (e & 4) and packed.kind == _lib.PLANES_F16X2 and not _retry:
+        # a given code is never -1 and raises no bit 2: NaN logits at its position show in what the call returns for it alone
+        nan_given = given is not None and not _retry and _out_of_range(packed.kind, logp[0] if return_logp else None, logits)
+        if ((e & 4) or nan_given) and packed.kind == _lib.PLANES_F16X2 and not _retry:
             # non-finite logits under the fp16 weight images: an activation left fp16's range (or the input is not finite): once
             # more on the six-product bf16 split, which has fp32's range; the images return to the default kind at the next use
             from . import packing
