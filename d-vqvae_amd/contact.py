@@ -23,8 +23,51 @@ def face_csr(faces, n_verts):
     return f.astype(np.int32), off.astype(np.int32), face[order].astype(np.int32)
 
 
+def seal_faces(faces, n_verts):
+    """faces [F,3] of an orientable mesh with holes -> ``(faces_sealed int32 [F + sum of loop lengths, 3], loop_off int32 [L+1],
+    loop_vert int32)``: the open boundary loops, found from the topology alone (the directed edges whose reverse no face uses), each
+    closed by a fan of triangles to a NEW centre vertex ``n_verts + l`` (``dvq_grasp_volume`` places it at the loop's mean), wound
+    against the boundary edges so that the sealed mesh is closed and consistently oriented.  Loops are ordered by their lowest vertex
+    and start there; a closed mesh gives no loop.  Raises if a directed edge is used twice (an edge used more than twice, or faces of
+    inconsistent orientation) or if the boundary branches at a vertex."""
+    f = np.asarray(faces, dtype=np.int64).reshape(-1, 3)
+    if f.size and (f.min() < 0 or f.max() >= n_verts):
+        raise RuntimeError(f"seal_faces: a face index is outside [0, {n_verts})")
+    directed = {}
+    for a, b in f[:, [0, 1, 1, 2, 2, 0]].reshape(-1, 2).tolist():
+        if a == b or (a, b) in directed:
+            raise RuntimeError(f"seal_faces: the directed edge ({a}, {b}) is degenerate or used twice (non-manifold or inconsistently oriented mesh)")
+        directed[(a, b)] = True
+    nxt = {}
+    for a, b in directed:
+        if (b, a) not in directed:                              # used by one face only: a boundary edge a -> b
+            if a in nxt:
+                raise RuntimeError(f"seal_faces: the boundary branches at vertex {a}")
+            nxt[a] = b
+    loops, seen = [], set()
+    for start in sorted(nxt):
+        if start in seen:
+            continue
+        loop, v = [], start
+        while v not in seen:
+            seen.add(v)
+            loop.append(v)
+            if v not in nxt:
+                raise RuntimeError(f"seal_faces: the boundary does not close at vertex {v}")
+            v = nxt[v]
+        if v != start:
+            raise RuntimeError(f"seal_faces: the boundary branches at vertex {v}")
+        loops.append(loop)
+    fan = [[b, a, n_verts + l] for l, loop in enumerate(loops) for a, b in zip(loop, loop[1:] + loop[:1])]
+    sealed = np.concatenate([f, np.asarray(fan, np.int64).reshape(-1, 3)]).astype(np.int32)
+    off = np.zeros(len(loops) + 1, dtype=np.int32)
+    off[1:] = np.cumsum([len(loop) for loop in loops])
+    return sealed, off, np.asarray([v for loop in loops for v in loop], dtype=np.int32)
+
+
 class HandTopology:
-    """Device copies of a mesh topology (MANO: 778 vertices, 1538 faces) for ``vertex_normals``."""
+    """Device copies of a mesh topology (MANO: 778 vertices, 1538 faces) for ``vertex_normals``; ``sealed()``: the closed face list
+    and boundary loops of ``seal_faces`` for ``grasp_volume``, made on first use."""
 
     def __init__(self, faces, n_verts, device):
         f, off, vf = face_csr(faces, n_verts)
@@ -32,9 +75,16 @@ class HandTopology:
         self.faces = torch.from_numpy(f).to(device)
         self.vf_off = torch.from_numpy(off).to(device)
         self.vf_face = torch.from_numpy(vf).to(device)
+        self._host_faces, self._sealed = f, None
 
     def normals(self, verts):
         return ops.vertex_normals(verts.contiguous(), self.faces, self.vf_off, self.vf_face)
+
+    def sealed(self):
+        """(faces_sealed, loop_off, loop_vert) of ``seal_faces`` on the device."""
+        if self._sealed is None:
+            self._sealed = tuple(torch.from_numpy(a).to(self.faces.device) for a in seal_faces(self._host_faces, self.n_verts))
+        return self._sealed
 
 
 def get_NN(src_xyz, trg_xyz):
@@ -132,6 +182,75 @@ def wrench_stats(sums, n_contact):
         torque.append(float(np.sqrt(np.sum(row[3:6] ** 2)) / k))
         min_sv.append(float(np.sqrt(max(float(np.linalg.eigvalsh(g / k)[0]), 0.0))))
     return {"force_residual": force, "torque_residual": torque, "min_sv": min_sv}
+
+
+def hull_planes(points_xyz):
+    """[N,3] cloud -> fp32 [P,4] rows (n, d), |n| = 1, with n.x <= d for every x inside the cloud's convex hull: the unique rows of
+    ``scipy.spatial.ConvexHull(points).equations`` (float64; qhull lists a plane once per triangle of a facet), normalised, in
+    lexicographic order.  The hull of a sampled cloud lies inside the hull of the mesh it was sampled from."""
+    try:
+        from scipy.spatial import ConvexHull
+    except ImportError as e:
+        raise RuntimeError("hull_planes: scipy is needed to build a convex hull (scipy.spatial.ConvexHull) and is not installed") from e
+    pts = np.asarray(points_xyz, dtype=np.float64).reshape(-1, 3)
+    if pts.shape[0] < 4 or not np.isfinite(pts).all():
+        raise RuntimeError(f"hull_planes: need at least four finite points (got {pts.shape[0]})")
+    eq = ConvexHull(pts).equations                              # [n, off] with n.x + off <= 0 inside
+    eq = eq / np.linalg.norm(eq[:, :3], axis=1, keepdims=True)
+    rows = np.concatenate([eq[:, :3], -eq[:, 3:]], axis=1).astype(np.float32) + np.float32(0.0)      # (no -0.0)
+    return np.unique(rows, axis=0)
+
+
+def pack_planes(planes_per_object):
+    """A list of [P_o,4] arrays -> ``(planes fp32 [sum P_o, 4], plane_off int32 [O+1])`` numpy arrays for ``grasp_volume``."""
+    rows = [np.asarray(p, dtype=np.float32).reshape(-1, 4) for p in planes_per_object]
+    for o, r in enumerate(rows):
+        if r.shape[0] > ops.GRASP_VOLUME_MAX_PLANES:
+            raise RuntimeError(f"pack_planes: object {o} has {r.shape[0]} planes, at most {ops.GRASP_VOLUME_MAX_PLANES} fit")
+    off = np.zeros(len(rows) + 1, dtype=np.int64)
+    off[1:] = np.cumsum([r.shape[0] for r in rows])
+    if off[-1] >= 2 ** 31:
+        raise RuntimeError("pack_planes: too many planes")
+    return (np.concatenate(rows) if rows else np.zeros((0, 4), np.float32)).astype(np.float32).reshape(-1, 4), off.astype(np.int32)
+
+
+def grasp_volume(topology, hand_xyz, planes, plane_off, obj_of_row, R=None, t=None, res=0.001, err=None):
+    """Penetration volume from ONE fused kernel (ops.grasp_volume; the definition is in include/dvq.h under dvq_grasp_volume): the
+    hand mesh of ``topology`` sealed at its open boundary (``seal_faces``) against the convex hull of each row's object, given as
+    half-spaces (``hull_planes`` / ``pack_planes``, on the device), on a lattice of spacing ``res`` metres in the object's own frame
+    (``R`` [B,3,3], ``t`` [3]: what ``ops.transform_clouds`` got, None for objects in place).  Returns ``count`` [B] i32 (voxels in
+    both; -1 = no figure), ``depth`` [B] f32 (the deepest hand vertex inside the hull, metres) and ``status`` [B] i32 (0 fine, 1 the
+    hand's box misses the hull or the object has no plane, 2 the box has more than 1024 cells on an axis, 3 a vertex is not finite).
+    ``volume_stats`` turns them into the figures written.
+
+    Against the reference's intersection_eval this is a LOWER bound when the planes come from a sampled cloud (its hull lies inside
+    the mesh's), the lattice is the object's and not anchored at a box corner, and no igl / trimesh run pins parity."""
+    faces, loop_off, loop_vert = topology.sealed()
+    count, depth, status = ops.grasp_volume(hand_xyz.contiguous(), faces, loop_off, loop_vert, planes, plane_off, obj_of_row, R, t, res,
+                                            err=err)
+    return {"count": count, "depth": depth, "status": status}
+
+
+def volume_stats(count, depth, res):
+    """Host side, float64, row by row: ``penetration_volume`` = count * res^3 * 1e6 in cm^3 and ``penetration_depth`` = depth * 100 in
+    cm from ``grasp_volume``'s ``count`` and ``depth`` (arrays or tensors); two lists of floats, ``None`` where count < 0 (json writes
+    null)."""
+    c = np.asarray(count.detach().cpu() if torch.is_tensor(count) else count, dtype=np.int64).reshape(-1)
+    d = np.asarray(depth.detach().cpu() if torch.is_tensor(depth) else depth, dtype=np.float64).reshape(-1)
+    if c.shape[0] != d.shape[0]:
+        raise RuntimeError("volume_stats: one depth per count")
+    res = float(res)
+    if not 0.0 < res < float("inf"):
+        raise RuntimeError(f"volume_stats: res must be finite and positive (got {res})")
+    cell = res * res * res * 1e6
+    return {"penetration_volume": [float(k) * cell if k >= 0 else None for k in c],
+            "penetration_depth": [float(x) * 100.0 if k >= 0 else None for k, x in zip(c, d)]}
+
+
+def volume_limit(max_volume, res):
+    """``--max_volume`` X cm^3 as the largest voxel count allowed, floor(X / (res^3 * 1e6)) in float64; +inf -> 2^31 - 1 (no limit)."""
+    x = float(max_volume) / (float(res) ** 3 * 1e6)
+    return int(min(np.floor(x), 2 ** 31 - 1))
 
 
 SELECT_BY = ("penetration", "log_prob", "stability")

@@ -1,0 +1,400 @@
+// dvq_grasp_volume: the voxels shared by the sealed hand mesh and the object's convex hull, and the deepest vertex inside the hull,
+// in ONE kernel, one workgroup of 256 threads per grasp.  The definition is the ABI (include/dvq.h); this file only says how the
+// kernel is laid out.  The count is an integer, so nothing below has to keep an order.
+//
+// The hand's V + L vertices sit in LDS in the object's frame as x|y|z planes.  The box of cells is walked in tiles of columns.
+// Per tile:
+//   H  every thread takes columns and intersects them with the object's half-spaces (planes from global memory, the same address
+//      in every lane; a column leaves the loop as soon as its interval is empty or misses the box): the cells of the column inside
+//      the hull are one range [ka, kb), kept in LDS.  A tile without such a column is done -- most of a hand's box is.
+//   R  every thread takes TRIANGLES (not columns: scatter, not gather) and walks the columns of the triangle's xy box inside the
+//      tile; a covered column gets ONE bit toggled (an integer atomicXor in LDS) at the last cell below the crossing.  "An odd
+//      number of crossings above cell k" is then the suffix parity of the column's bits.
+//   C  every thread takes columns again: suffix parity of the bit words from the top, masked by [ka, kb), popcount.
+// The bit words of a tile are laid out word-major (word w of all columns side by side), so phase C reads without bank conflicts.
+// LDS: 12 (V + L) + 16 KB of bit words (the box's and the depth's reduction columns borrow them first) + 8 KB of ranges: 33 KB at
+// MANO's 779 vertices (four workgroups per CU), 49 KB at the largest hand.
+#include "dvq_internal.h"
+
+namespace {
+
+constexpr int GV_THREADS = 256;
+constexpr int GV_MAX_V = 2048;
+constexpr int GV_MAX_L = 64;
+constexpr int GV_MAX_F = 8192;
+constexpr int GV_MAX_P = 8192;
+constexpr int GV_MAX_CELLS = 1024;          // per axis of the box
+constexpr int GV_IDX_LIMIT = 4194302;       // |cell index| up to here: (float)i + 0.5f is exact
+constexpr int GV_MASK_WORDS = 4096;         // bit words of a tile
+constexpr int GV_MAX_COLS = 2048;           // columns of a tile
+constexpr int GV_TILE_X = 64;
+constexpr int GV_SMALL = 16;                // ints: flags and the count
+static_assert(7 * GV_THREADS <= GV_MASK_WORDS, "the box's and the depth's reduction columns borrow the bit words");
+
+__host__ __device__ constexpr int gv_vp(int V, int L) { return (V + L + 3) & ~3; }
+__host__ __device__ constexpr size_t gv_lds_bytes(int V, int L) {
+    return (size_t)(3 * gv_vp(V, L) + GV_MASK_WORDS + GV_MAX_COLS + GV_SMALL) * 4;
+}
+
+__device__ __forceinline__ float gv_c(int i, float h) { return ((float)i + 0.5f) * h; }
+
+// the number of cells kk in [0, nk) with c(lo + kk) < z (STRICT) or <= z: c is non-decreasing in kk, so a guess and two walks
+template <bool STRICT>
+__device__ __forceinline__ int gv_cells(float z, float h, int lo, int nk) {
+    if (z != z) return 0;
+    const float gf = floorf(z / h - 0.5f) - (float)lo + 1.0f;
+    int g = gf < 0.0f ? 0 : (gf > (float)nk ? nk : (int)gf);
+    // (a step or two each; kept scalar: the loop vectoriser would turn them into eight-wide searches with packed-fp32 arithmetic)
+#pragma clang loop vectorize(disable) interleave(disable)
+    while (g < nk && (STRICT ? gv_c(lo + g, h) < z : gv_c(lo + g, h) <= z)) ++g;
+#pragma clang loop vectorize(disable) interleave(disable)
+    while (g > 0 && !(STRICT ? gv_c(lo + g - 1, h) < z : gv_c(lo + g - 1, h) <= z)) --g;
+    return g;
+}
+
+__device__ __forceinline__ bool gv_index_ok(float f) { return fabsf(f) <= (float)GV_IDX_LIMIT; }   // false for a NaN
+
+__global__ __launch_bounds__(GV_THREADS) void grasp_volume_kernel(const float* __restrict__ hand, int V, const int32_t* __restrict__ faces,
+                                                                  int F, const int32_t* __restrict__ loop_off,
+                                                                  const int32_t* __restrict__ loop_vert, int L, int n_loop,
+                                                                  const float* __restrict__ planes, int n_planes,
+                                                                  const int32_t* __restrict__ plane_off, long O, const int64_t* __restrict__ obj_of_row,
+                                                                  const float* __restrict__ R, const float* __restrict__ tr, float h,
+                                                                  int32_t* __restrict__ count, float* __restrict__ depth,
+                                                                  int32_t* __restrict__ status, int32_t* err_flag) {
+    extern __shared__ __align__(16) float gv_lds[];
+    const int VT = V + L, VP = gv_vp(V, L);
+    float* vx = gv_lds;
+    float* vy = vx + VP;
+    float* vz = vy + VP;
+    unsigned* mask = reinterpret_cast<unsigned*>(vz + VP);                 // [GV_MASK_WORDS]
+    int* range = reinterpret_cast<int*>(mask + GV_MASK_WORDS);             // [GV_MAX_COLS]: ka | kb << 16
+    float* red = reinterpret_cast<float*>(mask);                           // [7][256]: box and depth columns, before the first tile
+    int* small = range + GV_MAX_COLS;                                      // 0: not finite, 1: count, 2 .. 4: a tile has a hull column
+    const int t = threadIdx.x;
+    const long b = blockIdx.x;
+    const float nanf_ = __builtin_nanf("");
+
+    const int64_t o = obj_of_row[b];
+    int p0 = 0, P = -1;
+    if (o >= 0 && o < O) {
+        p0 = plane_off[o];
+        P = plane_off[o + 1] - p0;
+    }
+    if (P < 0 || P > GV_MAX_P || p0 < 0 || p0 > n_planes - P) {                                 // uniform over the workgroup
+        if (t == 0) {
+            atomicOr(err_flag, (o >= 0 && o < O) ? 2 : 1);
+            count[b] = -1;
+            depth[b] = nanf_;
+            status[b] = 4;
+        }
+        return;
+    }
+    const f32x4* pl = reinterpret_cast<const f32x4*>(planes) + p0;
+
+    if (t < GV_SMALL) small[t] = 0;
+    dvq_lds_barrier();
+    {                                                                      // the hand as given, and whether it is finite
+        const float* vb = hand + b * V * 3;
+        bool odd = false;
+        for (int i = t; i < V; i += GV_THREADS) {
+            const float x = vb[3 * i], y = vb[3 * i + 1], z = vb[3 * i + 2];
+            vx[i] = x;
+            vy[i] = y;
+            vz[i] = z;
+            odd |= !(fabsf(x) < INFINITY) || !(fabsf(y) < INFINITY) || !(fabsf(z) < INFINITY);
+        }
+        if (odd) small[0] = 1;
+    }
+    dvq_lds_barrier();
+    if (small[0]) {
+        if (t == 0) {
+            count[b] = -1;
+            depth[b] = nanf_;
+            status[b] = 3;
+        }
+        return;
+    }
+    if (t < L) {                                                           // fan centres, in the row's frame
+        int q0 = loop_off[t], q1 = loop_off[t + 1];
+        float sx = 0.0f, sy = 0.0f, sz = 0.0f;
+        if (q0 < 0 || q1 > n_loop) q0 = q1 = 0;                           // offsets outside loop_vert: an empty loop
+        bool bad = q1 <= q0;
+        for (int q = q0; q < q1; ++q) {
+            const int v = loop_vert[q];
+            if ((unsigned)v >= (unsigned)V) {
+                bad = true;
+                continue;
+            }
+            sx += vx[v];
+            sy += vy[v];
+            sz += vz[v];
+        }
+        const float len = (float)(q1 - q0);
+        vx[V + t] = q1 > q0 ? sx / len : 0.0f;
+        vy[V + t] = q1 > q0 ? sy / len : 0.0f;
+        vz[V + t] = q1 > q0 ? sz / len : 0.0f;
+        if (bad) atomicOr(err_flag, 2);
+    }
+    dvq_lds_barrier();
+    float mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
+    {                                                                      // into the object's frame, each vertex by its owner
+        float r[9], tt[3];
+#pragma unroll
+        for (int i = 0; i < 9; ++i) r[i] = R ? R[b * 9 + i] : 0.0f;
+#pragma unroll
+        for (int i = 0; i < 3; ++i) tt[i] = tr ? tr[i] : 0.0f;
+        for (int i = t; i < VT; i += GV_THREADS) {
+            float x = vx[i], y = vy[i], z = vz[i];
+            if (R) {
+                const float u0 = tr ? x - tt[0] : x, u1 = tr ? y - tt[1] : y, u2 = tr ? z - tt[2] : z;
+                x = fmaf(r[6], u2, fmaf(r[3], u1, r[0] * u0));
+                y = fmaf(r[7], u2, fmaf(r[4], u1, r[1] * u0));
+                z = fmaf(r[8], u2, fmaf(r[5], u1, r[2] * u0));
+                vx[i] = x;
+                vy[i] = y;
+                vz[i] = z;
+            }
+            mn[0] = x < mn[0] ? x : mn[0];
+            mn[1] = y < mn[1] ? y : mn[1];
+            mn[2] = z < mn[2] ? z : mn[2];
+            mx[0] = x > mx[0] ? x : mx[0];
+            mx[1] = y > mx[1] ? y : mx[1];
+            mx[2] = z > mx[2] ? z : mx[2];
+            if (x != x || y != y || z != z) mn[0] = nanf_;               // a NaN from R: the box is refused below
+        }
+    }
+    dvq_lds_barrier();                                                     // every vertex is in place
+    float deep = 0.0f;                                                     // depth: thread t's vertices against every plane
+    for (int i = t; i < V; i += GV_THREADS) {
+        const float x = vx[i], y = vy[i], z = vz[i];
+        float g = INFINITY;
+        for (int p = 0; p < P; ++p) {
+            const f32x4 q = pl[p];
+            const float e = q[3] - fmaf(q[2], z, fmaf(q[1], y, q[0] * x));
+            g = e < g ? e : g;
+        }
+        deep = g > deep ? g : deep;
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        red[c * GV_THREADS + t] = mn[c];
+        red[(3 + c) * GV_THREADS + t] = mx[c];
+    }
+    red[6 * GV_THREADS + t] = deep;
+    dvq_lds_barrier();
+    for (int s = GV_THREADS / 2; s >= 1; s >>= 1) {
+        if (t < s) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const float a = red[c * GV_THREADS + t], a2 = red[c * GV_THREADS + t + s];
+                red[c * GV_THREADS + t] = (a2 < a || a2 != a2) ? a2 : a;  // a NaN sticks
+                const float m = red[(3 + c) * GV_THREADS + t], m2 = red[(3 + c) * GV_THREADS + t + s];
+                red[(3 + c) * GV_THREADS + t] = m2 > m ? m2 : m;
+            }
+            const float d = red[6 * GV_THREADS + t], d2 = red[6 * GV_THREADS + t + s];
+            red[6 * GV_THREADS + t] = d2 > d ? d2 : d;
+        }
+        dvq_lds_barrier();
+    }
+    deep = red[6 * GV_THREADS];
+    if (P == 0) {
+        if (t == 0) {
+            count[b] = 0;
+            depth[b] = 0.0f;
+            status[b] = 1;
+        }
+        return;
+    }
+    int lo[3], n[3];
+    bool fits = true;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const float fl = floorf(red[c * GV_THREADS] / h), fh = floorf(red[(3 + c) * GV_THREADS] / h);
+        const bool ok = gv_index_ok(fl) && gv_index_ok(fh);
+        lo[c] = ok ? (int)fl - 1 : 0;
+        n[c] = ok ? ((int)fh + 1) - lo[c] + 1 : GV_MAX_CELLS + 1;
+        fits &= n[c] <= GV_MAX_CELLS;
+    }
+    if (!fits) {
+        if (t == 0) {
+            count[b] = -1;
+            depth[b] = deep;
+            status[b] = 2;
+        }
+        return;
+    }
+    const int nx = n[0], ny = n[1], nk = n[2], ilo = lo[0], jlo = lo[1], klo = lo[2];
+    const int W = (nk + 31) >> 5;                                          // <= 32 bit words per column
+    const int per_tile = GV_MASK_WORDS / W < GV_MAX_COLS ? GV_MASK_WORDS / W : GV_MAX_COLS;   // >= 128
+    const int TX = nx < GV_TILE_X ? nx : GV_TILE_X;
+    const int TY = per_tile / TX < ny ? per_tile / TX : ny;                // >= 1: per_tile >= 128 >= TX
+    const float zbot = gv_c(klo, h), ztop = gv_c(klo + nk - 1, h);
+    int mine = 0, hull_seen = 0, tile = 0;
+    for (int f = t; f < F; f += GV_THREADS) {
+        if ((unsigned)faces[3 * f] >= (unsigned)VT || (unsigned)faces[3 * f + 1] >= (unsigned)VT || (unsigned)faces[3 * f + 2] >= (unsigned)VT)
+            atomicOr(err_flag, 2);
+    }
+    for (int ty0 = 0; ty0 < ny; ty0 += TY) {
+        for (int tx0 = 0; tx0 < nx; tx0 += TX, ++tile) {
+            const int tw = nx - tx0 < TX ? nx - tx0 : TX, th = ny - ty0 < TY ? ny - ty0 : TY;
+            const int ncol = tw * th;
+            int* flag = small + 2 + tile % 3;
+            if (t == 0) small[2 + (tile + 1) % 3] = 0;                    // the next tile's flag: last read two barriers ago
+            // H: the cells of every column inside the hull
+            bool any = false;
+            for (int c = t; c < ncol; c += GV_THREADS) {
+                const float x = gv_c(ilo + tx0 + c % tw, h), y = gv_c(jlo + ty0 + c / tw, h);
+                float zlo = -INFINITY, zhi = INFINITY;
+                bool in = true;
+                for (int p = 0; p < P && in; ++p) {
+                    const f32x4 q = pl[p];
+                    const float s = q[0] * x + q[1] * y;
+                    const float r = q[3] - s;
+                    if (q[2] < 0.0f) {
+                        const float z = r / q[2];
+                        zlo = z > zlo ? z : zlo;
+                    } else if (q[2] > 0.0f) {
+                        const float z = r / q[2];
+                        zhi = z < zhi ? z : zhi;
+                    } else {
+                        in = s <= q[3];
+                    }
+                    in = in && zlo <= zhi && zlo <= ztop && zbot <= zhi;  // (an interval that misses the box holds no cell of it)
+                }
+                int ka = 0, kb = 0;
+                if (in) {
+                    ka = gv_cells<true>(zlo, h, klo, nk);                 // cells below zlo are out
+                    kb = gv_cells<false>(zhi, h, klo, nk);                // cells up to zhi are in
+                    if (kb <= ka) ka = kb = 0;
+                }
+                range[c] = ka | (kb << 16);
+                any |= kb > ka;
+            }
+            if (any) *flag = 1;
+            dvq_lds_barrier();
+            const bool live = *flag != 0;
+            if (!live) continue;                                           // uniform: no column of the tile meets the hull
+            hull_seen = 1;
+            for (int i = t; i < ncol * W; i += GV_THREADS) mask[i] = 0u;
+            dvq_lds_barrier();
+            // R: every triangle toggles one bit in each column it covers
+            const int ia = ilo + tx0, ib = ia + tw - 1, ja = jlo + ty0, jb = ja + th - 1;
+            for (int f = t; f < F; f += GV_THREADS) {
+                const int a = faces[3 * f], bb = faces[3 * f + 1], c = faces[3 * f + 2];
+                if ((unsigned)a >= (unsigned)VT || (unsigned)bb >= (unsigned)VT || (unsigned)c >= (unsigned)VT) {
+                    continue;                                              // (reported once, before the tiles)
+                }
+                const float ax = vx[a], ay = vy[a], az = vz[a], bx = vx[bb], by = vy[bb], bz = vz[bb], cx = vx[c], cy = vy[c], cz = vz[c];
+                const float A = (bx - ax) * (cy - ay) - (by - ay) * (cx - ax);
+                if (!(A > 0.0f) && !(A < 0.0f)) continue;
+                const float xmn = fminf(ax, fminf(bx, cx)), xmx = fmaxf(ax, fmaxf(bx, cx));
+                const float ymn = fminf(ay, fminf(by, cy)), ymx = fmaxf(ay, fmaxf(by, cy));
+                int i0 = (int)floorf(xmn / h) - 1, i1 = (int)floorf(xmx / h) + 1;   // inside the box: the box is made of these values
+                int j0 = (int)floorf(ymn / h) - 1, j1 = (int)floorf(ymx / h) + 1;
+                i0 = i0 < ia ? ia : i0;
+                i1 = i1 > ib ? ib : i1;
+                j0 = j0 < ja ? ja : j0;
+                j1 = j1 > jb ? jb : j1;
+                if (i0 > i1 || j0 > j1) continue;
+                // the three edges in canonical direction: e1 of (a,b), e2 of (b,c), e3 of (c,a); rev: the triangle runs Q -> P
+                const bool r1 = a > bb, r2 = bb > c, r3 = c > a;
+                const float p1x = r1 ? bx : ax, p1y = r1 ? by : ay, d1x = r1 ? ax - bx : bx - ax, d1y = r1 ? ay - by : by - ay;
+                const float p2x = r2 ? cx : bx, p2y = r2 ? cy : by, d2x = r2 ? bx - cx : cx - bx, d2y = r2 ? by - cy : cy - by;
+                const float p3x = r3 ? ax : cx, p3y = r3 ? ay : cy, d3x = r3 ? cx - ax : ax - cx, d3y = r3 ? cy - ay : ay - cy;
+                const bool up = A > 0.0f;
+                // what an edge value of exactly 0 counts as: its sign at the column moved by (eps, eps^2)
+                const bool z1 = d1y < 0.0f || (d1y == 0.0f && d1x > 0.0f), z2 = d2y < 0.0f || (d2y == 0.0f && d2x > 0.0f),
+                           z3 = d3y < 0.0f || (d3y == 0.0f && d3x > 0.0f);
+                for (int j = j0; j <= j1; ++j) {
+                    const float y = gv_c(j, h);
+                    if (!(ymn <= y && y <= ymx)) continue;
+                    for (int i = i0; i <= i1; ++i) {
+                        const float x = gv_c(i, h);
+                        if (!(xmn <= x && x <= xmx)) continue;
+                        const int col = (j - ja) * tw + (i - ia);
+                        const int rg = range[col];
+                        if (rg == 0) continue;                             // no cell of the column is in the hull
+                        const float e1 = d1x * (y - p1y) - d1y * (x - p1x);
+                        const float e2 = d2x * (y - p2y) - d2y * (x - p2x);
+                        const float e3 = d3x * (y - p3y) - d3y * (x - p3x);
+                        // the positive side of an edge belongs to the triangle iff (A > 0) != (it runs Q -> P)
+                        const bool s1 = e1 > 0.0f || (e1 == 0.0f && z1), s2 = e2 > 0.0f || (e2 == 0.0f && z2),
+                                   s3 = e3 > 0.0f || (e3 == 0.0f && z3);
+                        if (s1 != (up != r1) || s2 != (up != r2) || s3 != (up != r3)) continue;
+                        if (e1 != e1 || e2 != e2 || e3 != e3) continue;
+                        const float wc = r1 ? -e1 : e1, wa = r2 ? -e2 : e2, wb = r3 ? -e3 : e3;
+                        const float zc = ((wa * az + wb * bz) + wc * cz) / ((wa + wb) + wc);
+                        const int m = gv_cells<true>(zc, h, klo, nk);     // cells 0 .. m-1 lie below the crossing
+                        if (m > 0) atomicXor(&mask[((m - 1) >> 5) * ncol + col], 1u << ((m - 1) & 31));
+                    }
+                }
+            }
+            dvq_lds_barrier();
+            // C: suffix parity from the top word down, cut to the hull's cells
+            for (int c = t; c < ncol; c += GV_THREADS) {
+                const int rg = range[c];
+                if (rg == 0) continue;
+                const int ka = rg & 0xffff, kb = rg >> 16;
+                unsigned carry = 0u;
+                for (int w = W - 1; w >= (ka >> 5); --w) {
+                    const unsigned v = mask[w * ncol + c];
+                    unsigned s = v;
+                    s ^= s >> 1;
+                    s ^= s >> 2;
+                    s ^= s >> 4;
+                    s ^= s >> 8;
+                    s ^= s >> 16;                                          // bit i = parity of the bits i .. 31
+                    s ^= carry;
+                    carry ^= (__popc(v) & 1) ? 0xffffffffu : 0u;
+                    const int base = w << 5;
+                    if (base >= kb) continue;
+                    unsigned keep = 0xffffffffu;
+                    if (ka > base) keep &= 0xffffffffu << (ka - base);
+                    if (kb < base + 32) keep &= 0xffffffffu >> (base + 32 - kb);
+                    mine += __popc(s & keep);
+                }
+            }
+            dvq_lds_barrier();                                             // the next tile rewrites ranges and bit words
+        }
+    }
+    if (mine) atomicAdd(&small[1], mine);
+    dvq_lds_barrier();
+    if (t == 0) {
+        count[b] = hull_seen ? small[1] : 0;
+        depth[b] = hull_seen ? deep : 0.0f;
+        status[b] = hull_seen ? 0 : 1;
+    }
+}
+
+}  // namespace
+
+extern "C" int dvq_grasp_volume(const float* hand, int V, const int32_t* faces, int F, const int32_t* loop_off, const int32_t* loop_vert,
+                                int L, int n_loop, const float* planes, int n_planes, const int32_t* plane_off, int64_t O, const int64_t* obj_of_row, const float* R,
+                                const float* t, int64_t B, float h, int32_t* count, float* depth, int32_t* status, int32_t* err_flag,
+                                dvq_stream_t stream) {
+    DVQ_REQUIRE(B >= 0 && V >= 1 && V <= GV_MAX_V && F >= 0 && F <= GV_MAX_F && L >= 0 && L <= GV_MAX_L && O >= 0 && n_loop >= 0 && n_planes >= 0,
+                "grasp_volume: need B >= 0, 1 <= V <= %d, 0 <= F <= %d, 0 <= L <= %d, O >= 0 (got B=%ld V=%d F=%d L=%d O=%ld)", GV_MAX_V,
+                GV_MAX_F, GV_MAX_L, (long)B, V, F, L, (long)O);
+    DVQ_REQUIRE(h > 0.0f && h < INFINITY, "grasp_volume: the lattice spacing must be finite and positive (got %g)", (double)h);
+    DVQ_REQUIRE(R || !t, "grasp_volume: t without R");
+    if (B == 0) return DVQ_OK;
+    DVQ_REQUIRE(hand && (faces || F == 0) && loop_off && (loop_vert || n_loop == 0) && (planes || n_planes == 0) && plane_off && obj_of_row && count && depth &&
+                    status && err_flag,
+                "grasp_volume: null pointer");
+    DVQ_REQUIRE((reinterpret_cast<uintptr_t>(planes) & 15) == 0, "grasp_volume: planes must be 16-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    const size_t lds = gv_lds_bytes(V, L);                                 // <= 49 KB: below the default limit, no attribute to set
+    for (int64_t b0 = 0; b0 < B; b0 += 65535) {                            // the grid-dimension limit the neighbouring entry points chunk by
+        const int64_t nb = B - b0 < 65535 ? B - b0 : 65535;
+        // the work depends on the data (the box, the hull's planes, how much of the box the hull meets): only the depth's part is
+        // known here, 8 FLOPs per (vertex, plane) pair with the plane count unknown to the host -- reported as 0 FLOPs.  in: the hand;
+        // out: 12 B per grasp
+        DVQ_PROF("grasp_volume", 0.0, (double)nb * ((double)V * 12 + 12), st);
+        DVQ_LAUNCH(grasp_volume_kernel, dim3((unsigned)nb), dim3(GV_THREADS), lds, st, hand + b0 * V * 3, V, faces, F, loop_off, loop_vert,
+                   L, n_loop, planes, n_planes, plane_off, (long)O, obj_of_row + b0, R ? R + b0 * 9 : nullptr, t, h, count + b0, depth + b0, status + b0,
+                   err_flag);
+    }
+    DVQ_CHECK_LAUNCH("grasp_volume");
+    return DVQ_OK;
+}

@@ -11,6 +11,7 @@ from __future__ import annotations
 
 import argparse
 import json
+import math
 import os
 import time
 from typing import Dict, List, Optional, Sequence
@@ -99,6 +100,16 @@ def build_parser(dataset: str) -> argparse.ArgumentParser:
                         "the guard against hands that wrap the object by sinking into it (default: no limit)")
     p.add_argument("--torque_length", type=float, default=0.1,
                    help="--stability / --select_by stability: the length in metres that scales torques to forces (hand-sized default, untuned)")
+    p.add_argument("--volume", type=int, default=0,
+                   help="1: every grasp's JSON gains \"penetration_volume\" (cm^3), \"penetration_depth\" (cm) and \"volume_voxels\": the "
+                        "voxels shared by the sealed hand mesh and the convex hull of the object's cloud, counted on the device (one "
+                        "kernel per call; the hulls are built on the host with scipy), and the run writes penetration.json with the "
+                        "means and the contact ratio (the share of grasps with at least one voxel).  The hull of a sampled cloud lies "
+                        "inside the mesh's: a lower bound of the reference's figure")
+    p.add_argument("--volume_res", type=float, default=0.001, help="--volume / --max_volume: the voxel size in metres (the reference uses 1 mm)")
+    p.add_argument("--max_volume", type=float, default=float("inf"),
+                   help="best-of-M: candidates whose penetration volume exceeds this many cm^3 rank after all others that touch the object "
+                        "(the class --max_penetration uses), whatever --select_by ranks by; needs --candidates (default: no limit)")
     p.add_argument("--refine_push", type=float, default=1.0, help="--refine_steps: step factor on the mean pull vector of the interior points")
     p.add_argument("--refine_pull", type=float, default=0.25,
                    help="--refine_steps: step factor on the mean pull vector of the points within 2 cm outside the hand")
@@ -127,6 +138,12 @@ def parse_args(dataset: str, argv: Optional[Sequence[str]] = None) -> argparse.N
         p.error(f"--torque_length must be finite and positive (got {args.torque_length})")
     if not args.max_penetration >= 0.0:
         p.error(f"--max_penetration must be >= 0 (got {args.max_penetration})")
+    if not 0.0 < args.volume_res < float("inf"):
+        p.error(f"--volume_res must be finite and positive (got {args.volume_res})")
+    if not args.max_volume >= 0.0:
+        p.error(f"--max_volume must be >= 0 (got {args.max_volume})")
+    if args.max_volume < float("inf") and not args.candidates:
+        p.error("--max_volume needs --candidates (it ranks candidates; --volume 1 alone writes the figure)")
     return args
 
 
@@ -276,7 +293,8 @@ def _generate_call(net: GenNet, objs: Sequence[torch.Tensor], num_grasp: int, ro
                    log_prob: bool = False, candidates: int = 0, select_by: str = "penetration",
                    min_contact: int = 1, diverse_pool: int = 0, diverse_space: str = "params", refine_steps: int = 0,
                    refine_push: float = 1.0, refine_pull: float = 0.25, diversity: int = 0, stability: bool = False,
-                   max_penetration: float = float("inf"), torque_length: float = 0.1) -> List[Dict[str, object]]:
+                   max_penetration: float = float("inf"), torque_length: float = 0.1,
+                   volume: Optional[Dict[str, float]] = None) -> List[Dict[str, object]]:
     """One batched call: the ``num_grasp`` grasps of each of ``objs`` (all of one point count), row o * num_grasp + g = grasp g
     of object o.  Every step is row-independent and keyed per row, so each object's slice holds the bits of its own
     ``generate_for_object`` call.  With ``candidates`` = M the call generates M rows per object (exactly the grasps of a
@@ -286,7 +304,9 @@ def _generate_call(net: GenNet, objs: Sequence[torch.Tensor], num_grasp: int, ro
     With ``diversity`` = K the kept parameters of every object go through one ``ops.segment_kmeans`` (one segment per object) and its
     counts and distances ride in the call's one device-to-host copy (_diversity_launch / _diversity_dicts).  With ``stability`` the
     scores come from ``contact.grasp_stability`` (one kernel in the place of ``contact.grasp_scores``) and its sums and key ride
-    in that copy too (_stability_json)."""
+    in that copy too (_stability_json).  With ``volume`` (``res``, ``max_volume``) every object's hull is built once on the host from
+    its own unrotated cloud and ONE ``contact.grasp_volume`` runs over all rows of the call, after the push-out (_volume_launch); the
+    rows' counts, depths and states ride in that copy as well (_volume_json)."""
     dev = next(net.parameters()).device
     keep = num_grasp
     G, O = (candidates or num_grasp), len(objs)
@@ -305,8 +325,8 @@ def _generate_call(net: GenNet, objs: Sequence[torch.Tensor], num_grasp: int, ro
     stream_ids = torch.as_tensor(np.asarray(object_indices, dtype=np.int64), device=dev).repeat_interleave(G)
     row_ids = torch.arange(G, device=dev).repeat(O)
     err = ops.new_err_flag(dev)                                                    # read after the parameters' copy below: no extra sync
-    batch = ops.transform_clouds(clouds, obj_of_row, torch.as_tensor(np.concatenate(Rs), dtype=torch.float32, device=dev),
-                                 torch.as_tensor(t, dtype=torch.float32, device=dev), err=err)
+    R_dev, t_dev = torch.as_tensor(np.concatenate(Rs), dtype=torch.float32, device=dev), torch.as_tensor(t, dtype=torch.float32, device=dev)
+    batch = ops.transform_clouds(clouds, obj_of_row, R_dev, t_dev, err=err)
     recon, pos, *rest = net.gen(batch, seed=seed, row_keys=(stream_ids, row_ids), **_prior_controls(temperature, top_k, log_prob))
     logp = grasp_log_prob(rest[0]["logp_model"]) if log_prob else None
     params = ops.assemble61(recon, pos)                                            # obman.py:243-247
@@ -321,13 +341,23 @@ def _generate_call(net: GenNet, objs: Sequence[torch.Tensor], num_grasp: int, ro
         params[:, 58:61] += refined["offset"]                                      # fp32; the hands below are those of these parameters
         final = net.rh_mano(betas=params[:, :10], global_orient=params[:, 10:13], hand_pose=params[:, 13:58],
                             transl=params[:, 58:61])
+    vol = None
+    if volume:                                                                     # after the push-out: the hands of the parameters written
+        vol = _volume_launch(net, objs, final.vertices, obj_of_row, R_dev if rotate else None, t_dev if rotate else None, volume["res"])
     if candidates:
         return _select_call(net, batch, params, final.vertices, logp, err, O, G, keep, select_by, min_contact, want_logp, proxies,
                             np.concatenate(Rs), np.concatenate(angles), t, diverse_pool, diverse_space, refined, diversity, stability,
-                            max_penetration, torque_length)
+                            max_penetration, torque_length, vol, volume)
     ref_lists = {}
     div = _diversity_launch(params, O, G, diversity) if diversity else []
-    if refined is not None or stability:                                           # the scores of the hands written, and the one copy
+    if vol is not None and refined is None and not stability:                      # the volume alone: no score is computed
+        host, *vol_h, err_h = _host_copy([params] + [vol[k] for k in VOLUME_PIECES] + div + [err])   # ONE device-to-host copy per call
+        if int(err_h[0]) != 0:
+            raise RuntimeError("generate_for_objects: object index out of range in transform_clouds")
+        div_h = vol_h[len(VOLUME_PIECES):]
+        names, tensors = [], {}
+        ref_lists = _volume_json(vol_h[:len(VOLUME_PIECES)], volume["res"])
+    elif refined is not None or stability:                                         # the scores of the hands written, and the one copy
         from . import contact
         cloud_xyz = batch[:, :3].transpose(1, 2)
         names = ["penetration", "n_interior", "n_contact"]
@@ -341,14 +371,18 @@ def _generate_call(net: GenNet, objs: Sequence[torch.Tensor], num_grasp: int, ro
         if refined is not None:
             names = ["refine_offset", "refine_iter"] + names
             tensors.update(refine_offset=refined["offset"], refine_iter=refined["iter"])
-        host, *rest_h, err_h = _host_copy([params] + [tensors[k] for k in names] + div + [err])   # ONE device-to-host copy per call
+        vol_t = [vol[k] for k in VOLUME_PIECES] if vol is not None else []
+        host, *rest_h, err_h = _host_copy([params] + [tensors[k] for k in names] + vol_t + div + [err])   # ONE device-to-host copy per call
         if int(err_h[0]) != 0:
             raise RuntimeError("generate_for_objects: object index out of range in transform_clouds")
         by_name = dict(zip(names, rest_h))
+        vol_h, rest_h = rest_h[len(names):len(names) + len(vol_t)], rest_h[:len(names)] + rest_h[len(names) + len(vol_t):]
         names = [k for k in names if k not in ("sums", "key")]
         ref_lists = {k: by_name[k].tolist() for k in names}
         if stability:
             ref_lists.update(_stability_json(by_name["sums"], by_name["n_contact"], by_name["key"]))
+        if vol is not None:
+            ref_lists.update(_volume_json(vol_h, volume["res"]))
         div_h = rest_h[len(by_name):]
     elif div:
         host, *div_h, err_h = _host_copy([params] + div + [err])                   # ONE device-to-host copy per call
@@ -384,6 +418,8 @@ def _generate_call(net: GenNet, objs: Sequence[torch.Tensor], num_grasp: int, ro
             if stability:
                 extra.update(wrench_sums=tensors["sums"][lo:hi], stability_key=tensors["key"][lo:hi])
             extra_json.update({k: v[lo:hi] for k, v in ref_lists.items()})
+        if vol is not None:
+            extra["volume"] = {k: vol[k][lo:hi] for k in VOLUME_PIECES[:3]}
         if diversity:
             extra["diversity"] = extra_json["diversity"] = div_dicts[o]
         outs.append({**extra, "params": p_dev[o], "vertices": v_dev[o],
@@ -414,6 +450,37 @@ def _stability_json(sums: np.ndarray, n_contact: np.ndarray, key: np.ndarray) ->
     return out
 
 
+VOLUME_PIECES = ("count", "depth", "status", "err")  # what a call's volume kernel leaves on the device (_volume_launch)
+VOLUME_FIELDS = ("penetration_volume", "penetration_depth", "volume_voxels")
+
+
+def _volume_launch(net: GenNet, objs: Sequence[torch.Tensor], vertices: torch.Tensor, obj_of_row: torch.Tensor,
+                   R: Optional[torch.Tensor], t: Optional[torch.Tensor], res: float) -> Dict[str, torch.Tensor]:
+    """``--volume`` / ``--max_volume``: every object's convex hull once, on the host, from its own unrotated cloud (contact.hull_planes:
+    scipy), and ONE ``contact.grasp_volume`` over all rows of the call with the call's ``obj_of_row``, ``R`` and ``t``.  The device
+    tensors count, depth, status and the kernel's error flag, which _volume_json reads on the host."""
+    from . import contact
+    dev = vertices.device
+    topo = _hand_topology(net, vertices.shape[1], dev)
+    planes, plane_off = contact.pack_planes([contact.hull_planes(o[:3].T.cpu().numpy().astype(np.float64)) for o in objs])
+    bad = ops.new_err_flag(dev)
+    out = contact.grasp_volume(topo, vertices, torch.from_numpy(planes).to(dev), torch.from_numpy(plane_off).to(dev), obj_of_row, R, t,
+                               res, err=bad)
+    return {**out, "err": bad}
+
+
+def _volume_json(host: Sequence[np.ndarray], res: float) -> Dict[str, list]:
+    """The three JSON lists of a call's rows from the host copies of _volume_launch's tensors: float64 on the host, row by row
+    (contact.volume_stats); null where the kernel gives no figure (count < 0)."""
+    from . import contact
+    count, depth, _, bad = host
+    if int(bad[0]) != 0:
+        raise RuntimeError("generate_for_objects: volume: an index of the hand topology or of the hulls is out of range")
+    out = contact.volume_stats(count, depth, res)
+    out["volume_voxels"] = [int(k) if k >= 0 else None for k in count]
+    return out
+
+
 def _diversity_launch(kept: torch.Tensor, O: int, keep: int, clusters: int) -> List[torch.Tensor]:
     """``--diversity``: one ``ops.segment_kmeans`` over the call's kept parameters [O*keep,61], one segment per object, from evenly
     spaced starting rows; the device tensors whose host copies _diversity_dicts reads (counts, dist, iters_used, the error flag)."""
@@ -440,7 +507,8 @@ def _select_call(net: GenNet, batch: torch.Tensor, params: torch.Tensor, vertice
                  R: np.ndarray, angles: np.ndarray, t: np.ndarray, diverse_pool: int = 0,
                  diverse_space: str = "params", refined: Optional[Dict[str, torch.Tensor]] = None,
                  diversity: int = 0, stability: bool = False, max_penetration: float = float("inf"),
-                 torque_length: float = 0.1) -> List[Dict[str, object]]:
+                 torque_length: float = 0.1, vol: Optional[Dict[str, torch.Tensor]] = None,
+                 volume: Optional[Dict[str, float]] = None) -> List[Dict[str, object]]:
     """Best-of-M for all the objects of a call together: the candidates' scores (one fused kernel), their keys, each object's
     ``keep`` best (one kernel), one ``index_select`` of the kept rows and one device-to-host copy.  Row o * M + c is candidate c of
     object o; nothing here depends on which objects share the call.  ``diverse_pool`` = P: each object's P best (the same kernel),
@@ -449,7 +517,10 @@ def _select_call(net: GenNet, batch: torch.Tensor, params: torch.Tensor, vertice
     rows were pushed out before (contact.refine_translation's dict; ``params`` and ``vertices`` are the refined ones): the kept rows'
     offsets and iterates ride along too.  ``diversity``: the k-means statistic of the kept parameters (_diversity_launch) rides along
     as well.  ``stability``: the candidates' scores come from ``contact.grasp_stability`` (the one kernel in the place of
-    ``contact.grasp_scores``); the kept rows' sums and keys ride along and become the four JSON fields of _stability_json."""
+    ``contact.grasp_scores``); the kept rows' sums and keys ride along and become the four JSON fields of _stability_json.
+    ``vol`` (_volume_launch over all candidates) with ``volume`` = its ``res`` and ``max_volume``: candidates whose voxel count exceeds
+    ``contact.volume_limit`` join class 1 and those without a figure class 2 (integer comparisons on the device), whatever ranks the
+    rest; the kept rows' counts, depths and states ride along and become the three JSON fields of _volume_json."""
     from . import contact
     dev = params.device
     topo = _hand_topology(net, vertices.shape[1], dev)
@@ -460,6 +531,10 @@ def _select_call(net: GenNet, batch: torch.Tensor, params: torch.Tensor, vertice
     if logp is not None:
         scores["log_prob"] = logp
     cls, key = contact.select_keys(scores, select_by, min_contact, log_prob=logp, max_penetration=max_penetration)
+    if vol is not None and volume["max_volume"] < float("inf"):
+        cnt = vol["count"]
+        over = (cnt > contact.volume_limit(volume["max_volume"], volume["res"])).to(torch.int32)
+        cls = torch.maximum(cls, torch.where(cnt < 0, torch.full_like(over, 2), over))
     diverse = []
     if diverse_pool:
         pool = ops.segment_topk(cls.contiguous(), key.contiguous(), O, M, diverse_pool)   # [O,P] candidate indices, best first
@@ -475,7 +550,8 @@ def _select_call(net: GenNet, batch: torch.Tensor, params: torch.Tensor, vertice
     names = sorted(kept_s)
     kept_r = [refined["offset"].index_select(0, rows), refined["iter"].index_select(0, rows)] if refined is not None else []
     div = _diversity_launch(kept_p, O, keep, diversity) if diversity else []
-    host = _host_copy([sel] + [kept_p] + [kept_s[k] for k in names] + kept_r + diverse + div + [err])  # ONE device-to-host copy per call
+    kept_vol = [vol[k].index_select(0, rows) for k in VOLUME_PIECES[:3]] + [vol["err"]] if vol is not None else []
+    host = _host_copy([sel] + [kept_p] + [kept_s[k] for k in names] + kept_r + kept_vol + diverse + div + [err])  # ONE device-to-host copy per call
     if int(host[-1][0]) != 0:
         raise RuntimeError("generate_for_objects: object index out of range in transform_clouds")
     sel_h, p_list = host[0], host[1].tolist()
@@ -486,8 +562,12 @@ def _select_call(net: GenNet, batch: torch.Tensor, params: torch.Tensor, vertice
         stab_lists = _stability_json(s_host["sums"], s_host["n_contact"], s_host["key"])
     if refined is not None:
         off_list, it_list = (h.tolist() for h in host[2 + len(names):4 + len(names)])
+    vol_lists = {}
+    if vol is not None:
+        vat = 2 + len(names) + len(kept_r)
+        vol_lists = _volume_json(host[vat:vat + len(kept_vol)], volume["res"])
     if diverse_pool:
-        at = 2 + len(names) + len(kept_r)
+        at = 2 + len(names) + len(kept_r) + len(kept_vol)
         rank_h, gap_h, pool_err_h = host[at:at + 3]
         if int(pool_err_h[0]) != 0:
             raise RuntimeError("generate_for_objects: pool entry out of range in segment_diverse")
@@ -518,6 +598,10 @@ def _select_call(net: GenNet, batch: torch.Tensor, params: torch.Tensor, vertice
         if diversity:
             extra["diversity"] = div_dicts[o]
             extra_json = {**extra_json, "diversity": div_dicts[o]}
+        if vol is not None:
+            extra["volume"] = {k: x[lo:hi] for k, x in zip(VOLUME_PIECES[:3], kept_vol)}
+            extra["volume_scores"] = {k: vol[k][o * M:(o + 1) * M] for k in VOLUME_PIECES[:3]}      # of ALL candidates
+            extra_json = {**extra_json, **{k: v[lo:hi] for k, v in vol_lists.items()}}
         outs.append({**extra, "params": p_dev[o], "vertices": v_dev[o], "candidate": sel[o],
                      "scores": {k: v[o * M:(o + 1) * M] for k, v in scores.items()},
                      "json": {"recon_params": [[p] for p in p_list[lo:hi]], "R_list": Rt_list[lo:hi], "trans_list": [trans] * keep,
@@ -531,7 +615,8 @@ def generate_for_objects(net: GenNet, objs: Sequence[torch.Tensor], num_grasp: i
                          top_k: int = 0, log_prob: bool = False, candidates: int = 0, select_by: str = "penetration",
                          min_contact: int = 1, diverse_pool: int = 0, diverse_space: str = "params", refine_steps: int = 0,
                          refine_push: float = 1.0, refine_pull: float = 0.25, diversity: int = 0, stability: bool = False,
-                         max_penetration: float = float("inf"), torque_length: float = 0.1) -> List[Dict[str, object]]:
+                         max_penetration: float = float("inf"), torque_length: float = 0.1, volume: bool = False,
+                         volume_res: float = 0.001, max_volume: float = float("inf")) -> List[Dict[str, object]]:
     """``num_grasp`` grasps for each of ``objs`` ([4,N] tensors) in batched calls that mix objects (plan_calls): one dict per
     object, in the order given, equal to ``generate_for_object(net, objs[i], num_grasp, rotate,
     np.random.default_rng([seed, object_indices[i]]), seed=seed, object_index=object_indices[i], proxies=proxies)`` (and the same
@@ -580,7 +665,28 @@ def generate_for_objects(net: GenNet, objs: Sequence[torch.Tensor], num_grasp: i
     "torque_residual", "min_sv" and "stability_key" per grasp (``contact.wrench_stats``, float64 on the host; null where the hand
     touches nothing) and, without ``candidates``, the three scores as well.  The sums ride in the call's one device-to-host copy.
     A frictionless unit-force proxy with untuned constants: it replaces no physics run and its effect on real grasps is not
-    measured.  Without either switch nothing of it runs."""
+    measured.  Without either switch nothing of it runs.
+
+    Penetration volume (``volume=True``, or a finite ``max_volume`` together with ``candidates``): every call builds the convex hull
+    of each of its objects once on the host (``contact.hull_planes`` of the object's own unrotated cloud; needs scipy) and launches ONE
+    ``contact.grasp_volume`` over all its rows with the call's ``obj_of_row``, rotations and offset, after the push-out has re-posed
+    the hands if there is one; ``volume_res`` is the voxel size in metres.  ``max_volume`` (cm^3): candidates whose voxel count
+    exceeds ``contact.volume_limit(max_volume, volume_res)`` join class 1 -- the class of ``max_penetration`` -- and candidates without
+    a figure class 2, whatever ``select_by`` ranks by.  Each dict gains ``volume`` (count, depth, status of its grasps; with
+    ``candidates`` also ``volume_scores``, those of ALL candidates) and ``json`` gains "penetration_volume" (cm^3),
+    "penetration_depth" (cm) and "volume_voxels" per grasp (``contact.volume_stats``, float64 on the host; null without a figure).
+    They ride in the call's one device-to-host copy.  A lower bound of the reference's intersection_eval (the cloud's hull lies inside
+    the mesh's) on the object's own lattice; no igl / trimesh run pins parity.  Without either switch nothing of it runs."""
+    vol_args = None
+    if volume or float(max_volume) < float("inf"):
+        if not 0.0 < float(volume_res) < float("inf"):
+            raise RuntimeError(f"generate_for_objects: volume_res must be finite and positive (got {volume_res})")
+        if not float(max_volume) >= 0.0:
+            raise RuntimeError(f"generate_for_objects: max_volume must be >= 0 (got {max_volume})")
+        if float(max_volume) < float("inf") and not candidates:
+            raise RuntimeError("generate_for_objects: max_volume needs candidates")
+        _hand_faces(net)                                                           # no face list: raise before any work
+        vol_args = dict(res=float(volume_res), max_volume=float(max_volume))
     stability = bool(stability) or (bool(candidates) and select_by == "stability")
     if stability:
         if not 0.0 < float(torque_length) < float("inf"):
@@ -621,7 +727,7 @@ def generate_for_objects(net: GenNet, objs: Sequence[torch.Tensor], num_grasp: i
     for call in plan_calls([o.shape[1] for o in objs], candidates or num_grasp, rows_per_call):
         res = _generate_call(net, [objs[p] for p in call], num_grasp, rotate, seed, [object_indices[p] for p in call], proxies,
                              temperature, top_k, log_prob, candidates, select_by, min_contact, diverse_pool, diverse_space, refine_steps,
-                             refine_push, refine_pull, diversity, stability, max_penetration, torque_length)
+                             refine_push, refine_pull, diversity, stability, max_penetration, torque_length, vol_args)
         for p, r in zip(call, res):
             out[p] = r
     return out
@@ -650,7 +756,8 @@ def main(dataset: str, argv: Optional[Sequence[str]] = None) -> List[str]:
     if args.diversity and (hi - lo) * args.num_grasp > ops.SEGMENT_KMEANS_MAX_M:
         raise RuntimeError(f"--diversity: the pooled statistic takes at most {ops.SEGMENT_KMEANS_MAX_M} grasps per rank "
                            f"(got {(hi - lo) * args.num_grasp})")
-    if args.rows_per_call > 0 or args.candidates or args.refine_steps or args.diversity or args.stability:
+    want_volume = bool(args.volume) or args.max_volume < float("inf")
+    if args.rows_per_call > 0 or args.candidates or args.refine_steps or args.diversity or args.stability or want_volume:
         # grouped calls (best-of-M, push-out, the diversity statistic and the stability proxy always: --rows_per_call 0 is then one
         # object per call)
         rows_per_call, per_object = max(1, args.rows_per_call), (args.candidates or args.num_grasp)
@@ -664,6 +771,9 @@ def main(dataset: str, argv: Optional[Sequence[str]] = None) -> List[str]:
             selection.update(diversity=args.diversity)
         if args.stability or (args.candidates and args.select_by == "stability"):
             selection.update(stability=True, max_penetration=args.max_penetration, torque_length=args.torque_length)
+        if want_volume:
+            selection.update(volume=True, volume_res=args.volume_res, max_volume=args.max_volume)
+        vol_rows: Dict[int, list] = {}                                             # --volume: every object's (voxels, cm^3, cm) per grasp
         kept: Dict[int, np.ndarray] = {}                                           # --diversity: every object's kept parameters, on the host
         # grouped calls: one call's objects at a time, its files written before the next call starts, so the device and the host
         # hold one call's results, not the whole list's
@@ -687,6 +797,8 @@ def main(dataset: str, argv: Optional[Sequence[str]] = None) -> List[str]:
                     json.dump(out["json"], f)
                 if args.diversity:
                     kept[p] = np.asarray(out["json"]["recon_params"], dtype=np.float32).reshape(args.num_grasp, -1)
+                if want_volume:
+                    vol_rows[p] = list(zip(*(out["json"][k] for k in ("volume_voxels", "penetration_volume", "penetration_depth"))))
             del outs, out
         written = [paths[p] for p in sorted(paths)]                                # object order, whatever the grouping
         if args.diversity and kept:
@@ -700,6 +812,19 @@ def main(dataset: str, argv: Optional[Sequence[str]] = None) -> List[str]:
                            "grasps": int(pooled.shape[0])}, f)
             print(f"rank {rank}: diversity of {pooled.shape[0]} grasps in {stat['clusters']} clusters: entropy {stat['entropy']:.4f}, "
                   f"mean distance {stat['mean_dist']:.4f} ({stat['iters']} iterations)")
+        if want_volume:
+            # the run's figures over this rank's grasps in object order (float64, exactly rounded sums: no grouping can change a bit);
+            # contact_ratio is the reference's rule, "volume > 0", on the voxel count
+            rows = [r for p in sorted(vol_rows) for r in vol_rows[p] if r[0] is not None]
+            stat = {"res": args.volume_res, "grasps": len(rows),
+                    "mean_volume_cm3": math.fsum(r[1] for r in rows) / len(rows) if rows else None,
+                    "mean_depth_cm": math.fsum(r[2] for r in rows) / len(rows) if rows else None,
+                    "contact_ratio": sum(1 for r in rows if r[0] >= 1) / len(rows) if rows else None}
+            name = "penetration.json" if world == 1 else f"penetration_rank{rank}.json"
+            with open(os.path.join(args.out_dir, name), "w") as f:
+                json.dump(stat, f)
+            print(f"rank {rank}: penetration volume of {len(rows)} grasps at {args.volume_res} m: mean {stat['mean_volume_cm3']} cm^3, "
+                  f"mean depth {stat['mean_depth_cm']} cm, contact ratio {stat['contact_ratio']}")
     else:
         for gi, (name, obj) in enumerate(objs[lo:hi], start=lo):                   # --rows_per_call 0: one call per object
             torch.cuda.synchronize(device)

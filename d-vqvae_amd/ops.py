@@ -787,6 +787,78 @@ def grasp_wrench(hand: Tensor, faces: Tensor, vf_off: Tensor, vf_face: Tensor, o
     return pen, n_in, n_ct, centre, sums, key
 
 
+GRASP_VOLUME_MAX_F = 8192          # csrc/grasp_volume.hip: GV_MAX_F
+GRASP_VOLUME_MAX_LOOPS = 64        # GV_MAX_L
+GRASP_VOLUME_MAX_PLANES = 8192     # GV_MAX_P: per object
+GRASP_VOLUME_MAX_CELLS = 1024      # GV_MAX_CELLS: per axis of a hand's box; beyond it the grasp reports status 2
+
+
+def grasp_volume(hand: Tensor, faces: Tensor, loop_off: Tensor, loop_vert: Tensor, planes: Tensor, plane_off: Tensor,
+                 obj_of_row: Tensor, R: Optional[Tensor] = None, t: Optional[Tensor] = None, res: float = 0.001,
+                 err: Optional[Tensor] = None):
+    """The voxels shared by the sealed hand mesh and the object's convex hull, and the deepest hand vertex inside the hull, in one
+    fused kernel (dvq_grasp_volume; the definition is in include/dvq.h): ``(count [B] i32, depth [B] f32, status [B] i32)``.
+    hand [B,V,3] contiguous; faces [F,3] int32 with indices below V + L, loop_off [L+1] and loop_vert int32 (``contact.seal_faces``);
+    planes [P,4] f32 rows (n, d) with n.x <= d inside, plane_off int32 [O+1] (``contact.pack_planes``); obj_of_row int64 [B]; R [B,3,3]
+    and t [3] as ``transform_clouds`` got them, or None for objects in place; ``res``: the lattice spacing.  An object index outside
+    [0, O) raises RuntimeError unless an ``err`` flag tensor is supplied (then the caller checks it: bit 0; bit 1 = an index of the
+    topology or a plane range out of bounds)."""
+    named = (("hand", hand), ("faces", faces), ("loop_off", loop_off), ("loop_vert", loop_vert), ("planes", planes),
+             ("plane_off", plane_off), ("obj_of_row", obj_of_row))
+    for n, x in named:
+        if not isinstance(x, Tensor):
+            raise RuntimeError(f"grasp_volume: {n} must be a tensor")
+    _f32(hand, "hand"), _f32(planes, "planes"), _i64(obj_of_row, "obj_of_row")
+    for n, x in named[1:4] + named[5:6]:
+        if x.dtype != torch.int32 or not x.is_contiguous():
+            raise RuntimeError(f"grasp_volume: {n} must be contiguous int32")
+    if hand.dim() != 3 or hand.shape[2] != 3 or not hand.is_contiguous():
+        raise RuntimeError("grasp_volume: hand must be contiguous [B,V,3]")
+    B, V = hand.shape[0], hand.shape[1]
+    if not 1 <= V <= GRASP_SCORES_MAX_V:
+        raise RuntimeError(f"grasp_volume: need 1 <= V <= {GRASP_SCORES_MAX_V} (got V={V})")
+    if faces.dim() != 2 or faces.shape[1] != 3 or faces.shape[0] > GRASP_VOLUME_MAX_F:
+        raise RuntimeError(f"grasp_volume: faces must be [F,3] with F <= {GRASP_VOLUME_MAX_F} (got {tuple(faces.shape)})")
+    if loop_off.dim() != 1 or not 1 <= loop_off.numel() <= GRASP_VOLUME_MAX_LOOPS + 1 or loop_vert.dim() != 1:
+        raise RuntimeError(f"grasp_volume: loop_off must be [L+1] with L <= {GRASP_VOLUME_MAX_LOOPS} and loop_vert 1-D")
+    if planes.dim() != 2 or planes.shape[1] != 4 or not planes.is_contiguous() or planes.shape[0] >= 2 ** 31:
+        raise RuntimeError("grasp_volume: planes must be contiguous [P,4]")
+    if plane_off.dim() != 1 or plane_off.numel() < 1:
+        raise RuntimeError("grasp_volume: plane_off must be [O+1]")
+    if obj_of_row.dim() != 1 or obj_of_row.shape[0] != B or not obj_of_row.is_contiguous():
+        raise RuntimeError("grasp_volume: `obj_of_row` must be a contiguous int64 [B] tensor")
+    if R is None and t is not None:
+        raise RuntimeError("grasp_volume: t without R")
+    if R is not None and (not isinstance(R, Tensor) or _f32(R, "R").dim() != 3 or tuple(R.shape) != (B, 3, 3) or not R.is_contiguous()):
+        raise RuntimeError("grasp_volume: expected contiguous R [B,3,3]")
+    if t is not None and (not isinstance(t, Tensor) or _f32(t, "t").numel() != 3 or not t.is_contiguous()):
+        raise RuntimeError("grasp_volume: expected contiguous t [3]")
+    res = float(res)
+    if not 0.0 < res < float("inf"):
+        raise RuntimeError(f"grasp_volume: res must be finite and positive (got {res})")
+    dev = _require_gpu(hand, faces, loop_off, loop_vert, planes, plane_off, obj_of_row, R, t, err)
+    lib = _lib.load()
+    count = torch.empty(B, dtype=torch.int32, device=dev)
+    depth = torch.empty(B, dtype=torch.float32, device=dev)
+    status = torch.empty(B, dtype=torch.int32, device=dev)
+    own_err = err is None
+    if own_err:
+        err = new_err_flag(dev)
+    with torch.cuda.device(dev):
+        check(lib.dvq_grasp_volume(hand.data_ptr(), V, faces.data_ptr(), faces.shape[0], loop_off.data_ptr(), loop_vert.data_ptr(),
+                                   loop_off.numel() - 1, loop_vert.numel(), planes.data_ptr(), planes.shape[0], plane_off.data_ptr(),
+                                   plane_off.numel() - 1, obj_of_row.data_ptr(), R.data_ptr() if R is not None else None,
+                                   t.data_ptr() if t is not None else None, B, res, count.data_ptr(), depth.data_ptr(),
+                                   status.data_ptr(), err.data_ptr(), _stream(dev)), "dvq_grasp_volume")
+    if own_err:
+        bad = int(err.item())
+        if bad & 1:
+            raise RuntimeError(f"grasp_volume: object index out of bounds for {plane_off.numel() - 1} objects")
+        if bad:
+            raise RuntimeError("grasp_volume: an index of the topology or a plane range is out of bounds")
+    return count, depth, status
+
+
 GRASP_REFINE_MAX_STEPS = 64        # csrc/grasp_refine.hip: GR_MAX_STEPS
 
 

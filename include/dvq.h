@@ -42,7 +42,7 @@ typedef enum {
 #define DVQ_ABI_VERSION 10
 /* Entry points added since 10 without touching a struct or a signature of it (a compatible extension: bindings of 10 keep
  * working, the version stays): dvq_pixelcnn_sample_ctl, dvq_grasp_scores, dvq_segment_topk, dvq_segment_diverse,
- * dvq_grasp_refine, dvq_segment_kmeans, dvq_grasp_wrench. */
+ * dvq_grasp_refine, dvq_segment_kmeans, dvq_grasp_wrench, dvq_grasp_volume. */
 int dvq_abi_version(void);
 const char* dvq_last_error(void);
 /* number of visible HIP devices, or -1; does not create a context */
@@ -450,6 +450,63 @@ int dvq_grasp_wrench(const float* hand /* [B,V,3] */, const int32_t* faces, cons
                      int64_t B, int N, float contact_threshold, float inv_length, float* penetration /* [B] */,
                      int32_t* n_interior /* [B] */, int32_t* n_contact /* [B] */, float* centre /* [B,3] */, float* sums /* [B,27] */,
                      float* key /* [B] */, dvq_stream_t stream);
+/* Penetration volume of grasps: the voxels, on a lattice of spacing h, whose centres lie both inside the (sealed) hand mesh and
+ * inside the convex hull of the object -- an INTEGER per grasp, defined to the bit -- and the depth of the deepest hand vertex inside
+ * the hull, in ONE kernel, one workgroup of 256 threads per grasp.  The counterpart of the reference's intersection_eval
+ * (gen_diverse_grasp_obman.py:75-145, 265-279: igl + trimesh on the host, one grasp at a time, 1 mm voxels); it differs from it in
+ * three stated ways: the hull is given as half-spaces (the caller builds it, e.g. from the sampled cloud: a lower bound of the mesh's
+ * hull), the lattice is the object's own and not anchored at a bounding-box corner, and no igl / trimesh output pins parity.
+ * Inputs: hand [B,V,3] contiguous fp32, posed, in the frame of its row; faces [F,3] int32, the closed ("sealed") triangle list with
+ * indices in [0, V+L): vertex V+l is the fan centre of boundary loop l; loop_off [L+1], loop_vert [n_loop] int32: the loops'
+ * vertices (CSR, indices in [0, V)), L >= 0; planes [n_planes,4] fp32 rows (nx, ny, nz, d): x is inside the hull of object o iff
+ * n.x <= d for every plane of rows plane_off[o] .. plane_off[o+1] of the n_planes (plane_off int32 [O+1], CSR); obj_of_row int64 [B]; R [B,3,3] and
+ * t [3]: the arguments dvq_transform_clouds got for these rows (the object was moved by x -> R x + t), or R = NULL (then t = NULL
+ * too) for objects in place; h: the lattice spacing.
+ * Everything is fp32; every operation is rounded on its own and "fma(a,b,c)" marks the only fused ones; "/" is the IEEE division;
+ * comparisons with a NaN are false.  Per grasp b, with o = obj_of_row[b] and the planes of o:
+ *   1. Fan centres (row frame): s = +0.0f; s = s + hand[loop_vert[q]] for q = loop_off[l] .. loop_off[l+1]-1 ascending, per component;
+ *      vertex V+l = s / (float)len.
+ *   2. Object frame, for all V+L vertices: with R, u = v - t per component (u = v when t is NULL) and v_o[i] = fma(R[2][i], u[2],
+ *      fma(R[1][i], u[1], R[0][i] * u[0])) (that is R^T u); without R, v_o = v bit for bit.  The lattice below is therefore the
+ *      object's own: a grasp's result depends on neither B, nor its row, nor which objects share the call.
+ *   3. Lattice and box: c(i) = ((float)i + 0.5f) * h.  Per axis, with mn / mx the smallest / largest v_o component over the V+L
+ *      vertices: lo = (int)floorf(mn / h) - 1, hi = (int)floorf(mx / h) + 1; the box is the cells lo .. hi of the three axes.
+ *   4. Projected area of triangle (a,b,c) (indices as listed in `faces`): A = (bx-ax)*(cy-ay) - (by-ay)*(cx-ax).
+ *   5. Edge value at column (x,y) = (c(i), c(j)): every edge is evaluated in its canonical direction, the lower vertex index P first,
+ *      e = (Qx-Px)*(y-Py) - (Qy-Py)*(x-Px), so the two triangles on an edge see the same bits.  A triangle that traverses the edge
+ *      P -> Q uses w = e, one that traverses it Q -> P uses w = -e.
+ *   6. Cover: the triangle covers the column iff A != 0 (and is no NaN), min(ax,bx,cx) <= x <= max(ax,bx,cx), the same for y, and
+ *      every one of its three edges lies on A's side: for A > 0, w > 0, for A < 0, w < 0, where a value e of exactly 0 counts as
+ *      positive iff Qy-Py < 0, or Qy-Py == 0 and Qx-Px > 0, and as negative otherwise (the differences as rounded in e).  That is the
+ *      sign e takes at the column moved by (eps, eps^2): the tie is broken by the edge's SIDE, the same for every triangle at the
+ *      edge whatever its traversal and the sign of its A, so the parity of a closed mesh survives a column through an edge --
+ *      silhouette edges included -- or through a vertex.
+ *   7. Crossing height of a covering triangle, with wa, wb, wc the values w of the edges b->c, c->a, a->b (opposite a, b, c):
+ *      zc = ((wa * az + wb * bz) + wc * cz) / ((wa + wb) + wc).
+ *   8. Voxel (i,j,k) is in the hand iff the number of covering triangles of its column with zc > c(k) is odd.
+ *   9. Hull, per column: q = nx * x + ny * y, r = d - q; planes with nz < 0: z = r / nz, zlo = z where z > zlo (from -inf); planes
+ *      with nz > 0: zhi = z where z < zhi (from +inf); every other plane rejects the whole column unless q <= d.  Voxel (i,j,k) of
+ *      a column not rejected is in the hull iff zlo <= c(k) and c(k) <= zhi.
+ *  10. count = the number of voxels of the box that are in both: an integer, free of any summation order.
+ *  11. depth: per vertex v < V, g = the smallest over the planes of d - fma(nz, v_o.z, fma(ny, v_o.y, nx * v_o.x)) (from +inf, g' < g
+ *      replaces); depth = the largest g over the vertices that exceeds +0.0f, else +0.0f: the exact deepest vertex inside a convex
+ *      body, in the units of the input.
+ *  12. status, the first that applies: 3 = a component of hand[b] is not finite (count = -1, depth = NaN); 1 = the object has no
+ *      plane (count = 0, depth = 0); 2 = an axis of the box has more than 1024 cells, or a floorf of step 3 is beyond +-4194302 (NaN
+ *      included), where (float)i + 0.5f stops being exact (count = -1, depth as in 11); 1 = no voxel of the box is in the hull
+ *      (count = 0, depth = 0); else 0.
+ * obj_of_row[b] outside [0, O) sets bit 0 of *err_flag (device int32, zeroed by the caller), as dvq_transform_clouds does; that row
+ * reports count = -1, depth = NaN, status = 4.  Bit 1: a face index outside [0, V+L), a loop entry outside [0, V), an empty loop or one
+ * whose offsets leave [0, n_loop] -- such a face or entry is skipped, such a loop's centre is +0 -- and an object with more than 8192
+ * planes or a range that leaves [0, n_planes], whose rows report status 4 as well (plane_off lives on the device, so the launcher
+ * cannot refuse it; the host's contact.pack_planes does).
+ * B >= 0, 1 <= V <= 2048, 0 <= F <= 8192, 0 <= L <= 64, O >= 0, n_loop >= 0, n_planes >= 0, h finite and > 0, t only with R, no null
+ * pointer otherwise; anything else is DVQ_EINVAL, nothing launched. */
+int dvq_grasp_volume(const float* hand /* [B,V,3] */, int V, const int32_t* faces /* [F,3] */, int F, const int32_t* loop_off /* [L+1] */,
+                     const int32_t* loop_vert, int L, int n_loop, const float* planes /* [n_planes,4] */, int n_planes,
+                     const int32_t* plane_off /* [O+1] */, int64_t O, const int64_t* obj_of_row /* [B] */, const float* R /* [B,3,3] or NULL */,
+                     const float* t /* [3] or NULL */, int64_t B, float h, int32_t* count /* [B] */, float* depth /* [B] */,
+                     int32_t* status /* [B] */, int32_t* err_flag, dvq_stream_t stream);
 /* Per-object selection: cls, key [O*M] (candidate c of object o at o * M + c) -> sel [O,keep]: the candidate indices (0 .. M-1) of
  * each object's keep best candidates, best first.  Candidate a ranks before b iff (cls, key, index) is smaller: cls as signed
  * integers; within a class a NaN key sorts after every number and -0.0 == +0.0; the index breaks every tie.  One workgroup per
