@@ -429,7 +429,9 @@ def _generate_call(net: GenNet, objs: Sequence[torch.Tensor], num_grasp: int, ro
 
 
 def _host_copy(pieces: Sequence[torch.Tensor]) -> List[np.ndarray]:
-    """The given device tensors (4- or 8-byte elements, the 8-byte ones first) on the host through ONE device-to-host copy."""
+    """The given tensors (float32, int32 or int64, in any order and of any length) on the host through ONE device-to-host copy: the
+    pieces travel as bytes, and a piece that starts at an odd multiple of 4 bytes comes back as an unaligned view, which numpy reads
+    correctly (tests/test_generate_combined.py)."""
     flat = [p.contiguous().reshape(-1).view(torch.uint8) for p in pieces]
     host = torch.cat(flat).cpu().numpy()
     out, lo = [], 0
