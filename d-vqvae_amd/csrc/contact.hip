@@ -16,6 +16,7 @@
 // read by broadcast (all lanes the same address), so the loop is pure vector work: HBM traffic is the algorithmic
 // (N1 + N2) * 12 B in, N1 * 12 B out per element.
 #include "dvq_internal.h"
+#include "grasp_scan.h"
 
 namespace {
 
@@ -95,134 +96,52 @@ __global__ void interior_kernel(const float* __restrict__ normals, const float* 
 // LDS: the hand's vertices and normals as x|y|z planes of VP = V rounded up to 4 floats (16-byte broadcast reads of four
 // vertices), then the reduction arrays.  Per-point results are the bits of the three kernels above (same expressions, same
 // order); the reduction order is fixed (include/dvq.h), so a grasp's result does not depend on B or on its row.
-constexpr int GS_MAX_V = 2048;              // 6 planes * 2048 * 4 B = 48 KB, + 3 KB of reduction arrays
-constexpr int GS_THREADS = 256;
-constexpr int GS_P = 4;                     // object points per thread and pass: every LDS read serves four points
-
-// Nearest vertex of one point, every case (NaN distances included): nn_points_kernel's loop.
-__device__ __forceinline__ void gs_scan_exact(const float* hx, const float* hy, const float* hz, int V, float sx, float sy, float sz,
-                                              float& best, int& bi) {
-    best = INFINITY;
-    bi = 0x7fffffff;
-    for (int j = 0; j < V; ++j) {
-        const float dx = sx - hx[j], dy = sy - hy[j], dz = sz - hz[j];
-        const float d = fmaf(dz, dz, fmaf(dy, dy, dx * dx));
-        if (dvq_argmin_better(d, j, best, bi)) { best = d; bi = j; }
-    }
-}
-
-__global__ __launch_bounds__(GS_THREADS) void grasp_scores_kernel(const float* __restrict__ hand, const int* __restrict__ faces,
-                                                                  const int* __restrict__ vf_off, const int* __restrict__ vf_face, int V,
-                                                                  const float* __restrict__ obj, long osb, long osp, long osc, int N,
-                                                                  float thr, float* __restrict__ penetration,
-                                                                  int* __restrict__ n_interior, int* __restrict__ n_contact) {
+// Everything up to the per-point results is grasp_scan.h's, shared with grasp_refine_kernel and grasp_wrench_kernel; this kernel's
+// own part is the three accumulators and their tree.
+__global__ __launch_bounds__(GRASP_THREADS) void grasp_scores_kernel(const float* __restrict__ hand, const int* __restrict__ faces,
+                                                                     const int* __restrict__ vf_off, const int* __restrict__ vf_face, int V,
+                                                                     const float* __restrict__ obj, long osb, long osp, long osc, int N,
+                                                                     float thr, float* __restrict__ penetration,
+                                                                     int* __restrict__ n_interior, int* __restrict__ n_contact) {
     extern __shared__ __align__(16) float gs_lds[];
-    const int VP = (V + 3) & ~3;
-    float* hx = gs_lds;                                          // hand vertices, planes
-    float* hy = hx + VP;
-    float* hz = hy + VP;
-    float* nx = hz + VP;                                         // vertex normals, planes
-    float* ny = nx + VP;
-    float* nz = ny + VP;
-    float* part = nz + VP;                                       // [256] partial sums
-    int* cnt_in = reinterpret_cast<int*>(part + GS_THREADS);     // [256]
-    int* cnt_ct = cnt_in + GS_THREADS;                           // [256]
-    int* flag = cnt_ct + GS_THREADS;                             // [1]: a vertex coordinate is not finite
+    float *hx, *hy, *hz, *nx, *ny, *nz;
+    grasp_planes(gs_lds, V, hx, hy, hz, nx, ny, nz);
+    float* part = gs_lds + grasp_hand_floats(V);                 // [256] partial sums
+    int* cnt_in = reinterpret_cast<int*>(part + GRASP_THREADS);  // [256]
+    int* cnt_ct = cnt_in + GRASP_THREADS;                        // [256]
+    int* flag = cnt_ct + GRASP_THREADS;                          // [1]: a vertex coordinate is not finite
     const int t = threadIdx.x;
     const long b = blockIdx.x;
-    const float* vb = hand + b * V * 3;
     if (t == 0) *flag = 0;
-    __syncthreads();
-    bool odd = false;
-    for (int i = t; i < V; i += GS_THREADS) {
-        const float x = vb[3 * i], y = vb[3 * i + 1], z = vb[3 * i + 2];
-        hx[i] = x;
-        hy[i] = y;
-        hz[i] = z;
-        odd |= !(fabsf(x) < INFINITY) || !(fabsf(y) < INFINITY) || !(fabsf(z) < INFINITY);
-    }
-    if (odd) *flag = 1;
-    __syncthreads();
-    for (int v = t; v < V; v += GS_THREADS) {                    // vertex_normals_kernel's expression on the LDS copy
-        float mx = 0.f, my = 0.f, mz = 0.f;
-        for (int q = vf_off[v]; q < vf_off[v + 1]; ++q) {
-            const int f = vf_face[q];
-            const int i0 = faces[3 * f], i1 = faces[3 * f + 1], i2 = faces[3 * f + 2];
-            const float ax = hx[i1] - hx[i0], ay = hy[i1] - hy[i0], az = hz[i1] - hz[i0];
-            const float bx = hx[i2] - hx[i0], by = hy[i2] - hy[i0], bz = hz[i2] - hz[i0];
-            mx += ay * bz - az * by;                            // (no contraction: -ffp-contract=off)
-            my += az * bx - ax * bz;
-            mz += ax * by - ay * bx;
-        }
-        const float len = sqrtf(fmaf(mz, mz, fmaf(my, my, mx * mx)));
-        const float inv = 1.0f / fmaxf(len, 1e-6f);
-        nx[v] = mx * inv;
-        ny[v] = my * inv;
-        nz[v] = mz * inv;
-    }
-    __syncthreads();
+    dvq_lds_barrier();
+    if (grasp_load_hand(hand + b * V * 3, V, t, hx, hy, hz)) *flag = 1;
+    dvq_lds_barrier();
+    grasp_normals(faces, vf_off, vf_face, V, t, hx, hy, hz, nx, ny, nz);
+    dvq_lds_barrier();
     const bool hand_odd = *flag != 0;
     const float* ob = obj + b * osb;
-    const int V4 = V & ~3;
     float sum = 0.0f;
     int n_in = 0, n_ct = 0;
-    for (long p0 = t; p0 < N; p0 += GS_THREADS * GS_P) {         // points p0 + k * 256: thread t's points, ascending
-        float sx[GS_P], sy[GS_P], sz[GS_P], best[GS_P];
-        int bi[GS_P];
+    for (long p0 = t; p0 < N; p0 += GRASP_THREADS * GRASP_P) {   // points p0 + k * 256: thread t's points, ascending
+        float sx[GRASP_P], sy[GRASP_P], sz[GRASP_P], best[GRASP_P];
+        int bi[GRASP_P];
         bool slow = hand_odd;
 #pragma unroll
-        for (int k = 0; k < GS_P; ++k) {
-            const long p = p0 + k * GS_THREADS;
+        for (int k = 0; k < GRASP_P; ++k) {
+            const long p = p0 + k * GRASP_THREADS;
             const bool in = p < N;
             sx[k] = in ? ob[p * osp] : 0.f;
             sy[k] = in ? ob[p * osp + osc] : 0.f;
             sz[k] = in ? ob[p * osp + 2 * osc] : 0.f;
-            slow |= !(fabsf(sx[k]) < INFINITY) || !(fabsf(sy[k]) < INFINITY) || !(fabsf(sz[k]) < INFINITY);
-            best[k] = INFINITY;
-            bi[k] = 0;
+            slow |= !grasp_finite(sx[k], sy[k], sz[k]);
         }
-        if (!slow) {
-            // Every coordinate finite: no distance is NaN, and over ascending j dvq_argmin_better(d, j, best, bi) from
-            // (INFINITY, 0x7fffffff) takes j = 0 and afterwards exactly the j with d < best -- the loop below.
-            for (int j = 0; j < V4; j += 4) {
-                const f32x4 X = *reinterpret_cast<const f32x4*>(hx + j);
-                const f32x4 Y = *reinterpret_cast<const f32x4*>(hy + j);
-                const f32x4 Z = *reinterpret_cast<const f32x4*>(hz + j);
+        grasp_scan4(hx, hy, hz, V, slow, sx, sy, sz, best, bi);
 #pragma unroll
-                for (int u = 0; u < 4; ++u) {
-#pragma unroll
-                    for (int k = 0; k < GS_P; ++k) {
-                        const float dx = sx[k] - X[u], dy = sy[k] - Y[u], dz = sz[k] - Z[u];
-                        const float d = fmaf(dz, dz, fmaf(dy, dy, dx * dx));
-                        const bool better = d < best[k];
-                        best[k] = better ? d : best[k];
-                        bi[k] = better ? j + u : bi[k];
-                    }
-                }
-            }
-            for (int j = V4; j < V; ++j) {
-#pragma unroll
-                for (int k = 0; k < GS_P; ++k) {
-                    const float dx = sx[k] - hx[j], dy = sy[k] - hy[j], dz = sz[k] - hz[j];
-                    const float d = fmaf(dz, dz, fmaf(dy, dy, dx * dx));
-                    const bool better = d < best[k];
-                    best[k] = better ? d : best[k];
-                    bi[k] = better ? j : bi[k];
-                }
-            }
-        } else {
-#pragma unroll
-            for (int k = 0; k < GS_P; ++k) gs_scan_exact(hx, hy, hz, V, sx[k], sy[k], sz[k], best[k], bi[k]);
-        }
-#pragma unroll
-        for (int k = 0; k < GS_P; ++k) {
-            if (p0 + k * GS_THREADS < N) {
-                const int j = bi[k];                             // 0 <= j < V: the scan always takes j = 0
+        for (int k = 0; k < GRASP_P; ++k) {
+            if (p0 + k * GRASP_THREADS < N) {
                 const float d = best[k];
-                const float vx = hx[j] - sx[k], vy = hy[j] - sy[k], vz = hz[j] - sz[k];
-                const float dot = fmaf(vz, nz[j], fmaf(vy, ny[j], vx * nx[j]));   // interior_kernel
-                const bool inside = dot > 0.f;
-                sum += (inside || d != d) ? d : 0.0f;
+                const bool inside = grasp_inside(hx, hy, hz, nx, ny, nz, bi[k], sx[k], sy[k], sz[k]);
+                sum += grasp_pen_term(inside, d);
                 n_in += inside ? 1 : 0;
                 n_ct += d < thr ? 1 : 0;
             }
@@ -231,14 +150,14 @@ __global__ __launch_bounds__(GS_THREADS) void grasp_scores_kernel(const float* _
     part[t] = sum;
     cnt_in[t] = n_in;
     cnt_ct[t] = n_ct;
-    __syncthreads();
-    for (int s = GS_THREADS / 2; s >= 1; s >>= 1) {              // the canonical tree: part[t] += part[t + s] for t < s
+    dvq_lds_barrier();
+    for (int s = GRASP_THREADS / 2; s >= 1; s >>= 1) {           // the canonical tree: part[t] += part[t + s] for t < s
         if (t < s) {
             part[t] += part[t + s];
             cnt_in[t] += cnt_in[t + s];
             cnt_ct[t] += cnt_ct[t + s];
         }
-        __syncthreads();
+        dvq_lds_barrier();
     }
     if (t == 0) {
         penetration[b] = part[0];
@@ -351,21 +270,22 @@ extern "C" int dvq_grasp_scores(const float* hand, const int32_t* faces, const i
                                 const float* obj, int64_t obj_batch_stride, int64_t obj_point_stride, int64_t obj_coord_stride,
                                 int64_t B, int N, float contact_threshold, float* penetration, int32_t* n_interior,
                                 int32_t* n_contact, dvq_stream_t stream) {
-    DVQ_REQUIRE(B >= 0 && N >= 1 && V >= 1 && V <= GS_MAX_V, "grasp_scores: need B >= 0, N >= 1, 1 <= V <= %d (got B=%ld N=%d V=%d)",
-                GS_MAX_V, (long)B, N, V);
+    DVQ_REQUIRE(B >= 0 && N >= 1 && V >= 1 && V <= GRASP_MAX_V, "grasp_scores: need B >= 0, N >= 1, 1 <= V <= %d (got B=%ld N=%d V=%d)",
+                GRASP_MAX_V, (long)B, N, V);
     if (B == 0) return DVQ_OK;
     DVQ_REQUIRE(hand && faces && vf_off && vf_face && obj && penetration && n_interior && n_contact, "grasp_scores: null pointer");
     hipStream_t st = (hipStream_t)stream;
-    const size_t lds = (size_t)(6 * ((V + 3) & ~3) + 3 * GS_THREADS + 4) * 4;
+    constexpr int more = 3 * GRASP_THREADS + 4;                  // floats after the planes: the reduction arrays and the flag
+    const size_t lds = grasp_lds_bytes(V, more);
     static DvqOncePerDevice attr_once;
-    DVQ_PROPAGATE(dvq_lds_limit(attr_once, reinterpret_cast<const void*>(&grasp_scores_kernel), (size_t)(6 * GS_MAX_V + 3 * GS_THREADS + 4) * 4,
+    DVQ_PROPAGATE(dvq_lds_limit(attr_once, reinterpret_cast<const void*>(&grasp_scores_kernel), grasp_lds_bytes(GRASP_MAX_V, more),
                                 "grasp_scores"));
     for (int64_t b0 = 0; b0 < B; b0 += 65535) {                  // the grid-dimension limit the neighbouring entry points chunk by
         const int64_t nb = B - b0 < 65535 ? B - b0 : 65535;
         // per (point, vertex) pair 3 subtractions, 1 product, 2 fmas = 8 FLOPs; in: the hand, the cloud and the topology once per
         // grasp; out: 12 B per grasp
         DVQ_PROF("grasp_scores", 8.0 * nb * N * V, (double)nb * ((double)(V + N) * 12 + 12), st);
-        DVQ_LAUNCH(grasp_scores_kernel, dim3((unsigned)nb), dim3(GS_THREADS), lds, st, hand + b0 * V * 3, faces, vf_off, vf_face, V,
+        DVQ_LAUNCH(grasp_scores_kernel, dim3((unsigned)nb), dim3(GRASP_THREADS), lds, st, hand + b0 * V * 3, faces, vf_off, vf_face, V,
                    obj + b0 * obj_batch_stride, (long)obj_batch_stride, (long)obj_point_stride, (long)obj_coord_stride, N,
                    contact_threshold, penetration + b0, n_interior + b0, n_contact + b0);
     }

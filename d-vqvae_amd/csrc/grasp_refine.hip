@@ -4,156 +4,77 @@
 //
 // The hand never moves: the translation t is subtracted from every object point instead (o' = obj - t), so the hand's vertices
 // and its normals -- which a translation does not change -- are loaded and computed ONCE per grasp and stay in LDS as x|y|z
-// planes for all steps, as in grasp_scores_kernel.  The object points are re-read from global memory every step (a grasp's
+// planes for all steps (grasp_scan.h).  The object points are re-read from global memory every step (a grasp's
 // cloud is 12 KB at N = 1024 and stays in L2; keeping them in registers would tie the register count to N).  Every step is the
-// pair scan of grasp_scores_kernel plus, per point, the pull vector g = o' - hand[j] added to one of two accumulators; seven fp32
+// pair scan of grasp_scan.h plus, per point, the pull vector g = o' - hand[j] added to one of two accumulators; seven fp32
 // sums and three counts go through the canonical tree together.  After the tree every thread reads the ten totals and takes the
 // same decision (key, step, early end): nothing but LDS carries state between threads, and nothing leaves the grasp's workgroup.
 //
-// The pair scan is a copy of grasp_scores_kernel's, not shared code: contact.hip compiles to what it compiled to before.
+// The planes, the hand load, the normals, the pair scan and the interior test are grasp_scan.h's, shared with grasp_scores_kernel and
+// grasp_wrench_kernel: steps = 0 gives the bits of dvq_grasp_scores because it runs the same text.  This kernel's own part is
+// o' = obj - t, the pull vectors and the step rule.
 #include "dvq_internal.h"
+#include "grasp_scan.h"
 
 namespace {
 
-constexpr int GR_MAX_V = 2048;              // 6 planes * 2048 * 4 B = 48 KB, + 10 KB of reduction arrays
 constexpr int GR_MAX_STEPS = 64;
-constexpr int GR_THREADS = 256;
-constexpr int GR_P = 4;                     // object points per thread and pass: every LDS read serves four points
 constexpr int GR_SUMS = 7;                  // penetration, S_in[3], S_nr[3]
 constexpr int GR_CNTS = 3;                  // n_in, n_ct, n_nr
-constexpr int GR_RED = (GR_SUMS + GR_CNTS) * GR_THREADS + 4;    // floats of LDS after the planes: the arrays and the flag
+constexpr int GR_RED = (GR_SUMS + GR_CNTS) * GRASP_THREADS + 4; // floats of LDS after the planes: the arrays and the flag (10 KB)
 
-// Nearest vertex of one point, every case (NaN distances included): nn_points_kernel's loop.
-__device__ __forceinline__ void gr_scan_exact(const float* hx, const float* hy, const float* hz, int V, float sx, float sy, float sz,
-                                              float& best, int& bi) {
-    best = INFINITY;
-    bi = 0x7fffffff;
-    for (int j = 0; j < V; ++j) {
-        const float dx = sx - hx[j], dy = sy - hy[j], dz = sz - hz[j];
-        const float d = fmaf(dz, dz, fmaf(dy, dy, dx * dx));
-        if (dvq_argmin_better(d, j, best, bi)) { best = d; bi = j; }
-    }
-}
-
-__global__ __launch_bounds__(GR_THREADS) void grasp_refine_kernel(const float* __restrict__ hand, const int* __restrict__ faces,
-                                                                  const int* __restrict__ vf_off, const int* __restrict__ vf_face, int V,
-                                                                  const float* __restrict__ obj, long osb, long osp, long osc, int N,
-                                                                  float thr, int steps, float push, float pull, int min_contact,
-                                                                  float* __restrict__ offset, int* __restrict__ iter,
-                                                                  float* __restrict__ penetration, int* __restrict__ n_interior,
-                                                                  int* __restrict__ n_contact) {
+__global__ __launch_bounds__(GRASP_THREADS) void grasp_refine_kernel(const float* __restrict__ hand, const int* __restrict__ faces,
+                                                                     const int* __restrict__ vf_off, const int* __restrict__ vf_face, int V,
+                                                                     const float* __restrict__ obj, long osb, long osp, long osc, int N,
+                                                                     float thr, int steps, float push, float pull, int min_contact,
+                                                                     float* __restrict__ offset, int* __restrict__ iter,
+                                                                     float* __restrict__ penetration, int* __restrict__ n_interior,
+                                                                     int* __restrict__ n_contact) {
     extern __shared__ __align__(16) float gr_lds[];
-    const int VP = (V + 3) & ~3;
-    float* hx = gr_lds;                                          // hand vertices, planes
-    float* hy = hx + VP;
-    float* hz = hy + VP;
-    float* nx = hz + VP;                                         // vertex normals, planes
-    float* ny = nx + VP;
-    float* nz = ny + VP;
-    float* part = nz + VP;                                       // [GR_SUMS][256] partial sums
-    int* cnt = reinterpret_cast<int*>(part + GR_SUMS * GR_THREADS);   // [GR_CNTS][256]
-    int* flag = cnt + GR_CNTS * GR_THREADS;                      // [1]: a vertex coordinate is not finite
+    float *hx, *hy, *hz, *nx, *ny, *nz;
+    grasp_planes(gr_lds, V, hx, hy, hz, nx, ny, nz);
+    float* part = gr_lds + grasp_hand_floats(V);                 // [GR_SUMS][256] partial sums
+    int* cnt = reinterpret_cast<int*>(part + GR_SUMS * GRASP_THREADS);   // [GR_CNTS][256]
+    int* flag = cnt + GR_CNTS * GRASP_THREADS;                   // [1]: a vertex coordinate is not finite
     const int t = threadIdx.x;
     const long b = blockIdx.x;
-    const float* vb = hand + b * V * 3;
     if (t == 0) *flag = 0;
     dvq_lds_barrier();
-    bool odd = false;
-    for (int i = t; i < V; i += GR_THREADS) {
-        const float x = vb[3 * i], y = vb[3 * i + 1], z = vb[3 * i + 2];
-        hx[i] = x;
-        hy[i] = y;
-        hz[i] = z;
-        odd |= !(fabsf(x) < INFINITY) || !(fabsf(y) < INFINITY) || !(fabsf(z) < INFINITY);
-    }
-    if (odd) *flag = 1;
+    if (grasp_load_hand(hand + b * V * 3, V, t, hx, hy, hz)) *flag = 1;
     dvq_lds_barrier();
-    for (int v = t; v < V; v += GR_THREADS) {                    // vertex_normals_kernel's expression on the LDS copy, once per grasp
-        float mx = 0.f, my = 0.f, mz = 0.f;
-        for (int q = vf_off[v]; q < vf_off[v + 1]; ++q) {
-            const int f = vf_face[q];
-            const int i0 = faces[3 * f], i1 = faces[3 * f + 1], i2 = faces[3 * f + 2];
-            const float ax = hx[i1] - hx[i0], ay = hy[i1] - hy[i0], az = hz[i1] - hz[i0];
-            const float bx = hx[i2] - hx[i0], by = hy[i2] - hy[i0], bz = hz[i2] - hz[i0];
-            mx += ay * bz - az * by;                            // (no contraction: -ffp-contract=off)
-            my += az * bx - ax * bz;
-            mz += ax * by - ay * bx;
-        }
-        const float len = sqrtf(fmaf(mz, mz, fmaf(my, my, mx * mx)));
-        const float inv = 1.0f / fmaxf(len, 1e-6f);
-        nx[v] = mx * inv;
-        ny[v] = my * inv;
-        nz[v] = mz * inv;
-    }
+    grasp_normals(faces, vf_off, vf_face, V, t, hx, hy, hz, nx, ny, nz);   // once per grasp
     dvq_lds_barrier();
     const bool hand_odd = *flag != 0;
     const float* ob = obj + b * osb;
-    const int V4 = V & ~3;
     float tx = 0.0f, ty = 0.0f, tz = 0.0f;                       // the translation of iterate k
     float best_tx = 0.0f, best_ty = 0.0f, best_tz = 0.0f, best_pen = 0.0f;
     int best_k = 0, best_cls = 0, best_in = 0, best_ct = 0;
     for (int k = 0;; ++k) {
         float sum = 0.0f, ix = 0.0f, iy = 0.0f, iz = 0.0f, rx = 0.0f, ry = 0.0f, rz = 0.0f;
         int n_in = 0, n_ct = 0, n_nr = 0;
-        for (long p0 = t; p0 < N; p0 += GR_THREADS * GR_P) {     // points p0 + u * 256: thread t's points, ascending
-            float sx[GR_P], sy[GR_P], sz[GR_P], best[GR_P];
-            int bi[GR_P];
+        for (long p0 = t; p0 < N; p0 += GRASP_THREADS * GRASP_P) {   // points p0 + u * 256: thread t's points, ascending
+            float sx[GRASP_P], sy[GRASP_P], sz[GRASP_P], best[GRASP_P];
+            int bi[GRASP_P];
             bool slow = hand_odd;
 #pragma unroll
-            for (int u = 0; u < GR_P; ++u) {
-                const long p = p0 + u * GR_THREADS;
+            for (int u = 0; u < GRASP_P; ++u) {
+                const long p = p0 + u * GRASP_THREADS;
                 const bool in = p < N;
                 sx[u] = (in ? ob[p * osp] : 0.f) - tx;           // o' = obj - t; obj itself at k = 0 (t = +0)
                 sy[u] = (in ? ob[p * osp + osc] : 0.f) - ty;
                 sz[u] = (in ? ob[p * osp + 2 * osc] : 0.f) - tz;
-                slow |= !(fabsf(sx[u]) < INFINITY) || !(fabsf(sy[u]) < INFINITY) || !(fabsf(sz[u]) < INFINITY);
-                best[u] = INFINITY;
-                bi[u] = 0;
+                slow |= !grasp_finite(sx[u], sy[u], sz[u]);
             }
-            if (!slow) {
-                // Every coordinate finite: no distance is NaN, and over ascending j dvq_argmin_better(d, j, best, bi) from
-                // (INFINITY, 0x7fffffff) takes j = 0 and afterwards exactly the j with d < best -- the loop below.
-                for (int j = 0; j < V4; j += 4) {
-                    const f32x4 X = *reinterpret_cast<const f32x4*>(hx + j);
-                    const f32x4 Y = *reinterpret_cast<const f32x4*>(hy + j);
-                    const f32x4 Z = *reinterpret_cast<const f32x4*>(hz + j);
+            grasp_scan4(hx, hy, hz, V, slow, sx, sy, sz, best, bi);
 #pragma unroll
-                    for (int w = 0; w < 4; ++w) {
-#pragma unroll
-                        for (int u = 0; u < GR_P; ++u) {
-                            const float dx = sx[u] - X[w], dy = sy[u] - Y[w], dz = sz[u] - Z[w];
-                            const float d = fmaf(dz, dz, fmaf(dy, dy, dx * dx));
-                            const bool better = d < best[u];
-                            best[u] = better ? d : best[u];
-                            bi[u] = better ? j + w : bi[u];
-                        }
-                    }
-                }
-                for (int j = V4; j < V; ++j) {
-#pragma unroll
-                    for (int u = 0; u < GR_P; ++u) {
-                        const float dx = sx[u] - hx[j], dy = sy[u] - hy[j], dz = sz[u] - hz[j];
-                        const float d = fmaf(dz, dz, fmaf(dy, dy, dx * dx));
-                        const bool better = d < best[u];
-                        best[u] = better ? d : best[u];
-                        bi[u] = better ? j : bi[u];
-                    }
-                }
-            } else {
-#pragma unroll
-                for (int u = 0; u < GR_P; ++u) gr_scan_exact(hx, hy, hz, V, sx[u], sy[u], sz[u], best[u], bi[u]);
-            }
-#pragma unroll
-            for (int u = 0; u < GR_P; ++u) {
-                if (p0 + u * GR_THREADS < N) {
+            for (int u = 0; u < GRASP_P; ++u) {
+                if (p0 + u * GRASP_THREADS < N) {
                     const int j = bi[u];                         // 0 <= j < V: the scan always takes j = 0
                     const float d = best[u];
-                    const float vx = hx[j] - sx[u], vy = hy[j] - sy[u], vz = hz[j] - sz[u];
-                    const float dot = fmaf(vz, nz[j], fmaf(vy, ny[j], vx * nx[j]));   // interior_kernel
-                    const bool inside = dot > 0.f;
+                    const bool inside = grasp_inside(hx, hy, hz, nx, ny, nz, j, sx[u], sy[u], sz[u]);
                     const bool near = !inside && d < thr;
                     const float gx = sx[u] - hx[j], gy = sy[u] - hy[j], gz = sz[u] - hz[j];   // the pull vector
-                    sum += (inside || d != d) ? d : 0.0f;
+                    sum += grasp_pen_term(inside, d);
                     ix += inside ? gx : 0.0f;
                     iy += inside ? gy : 0.0f;
                     iz += inside ? gz : 0.0f;
@@ -167,29 +88,29 @@ __global__ __launch_bounds__(GR_THREADS) void grasp_refine_kernel(const float* _
             }
         }
         part[t] = sum;
-        part[GR_THREADS + t] = ix;
-        part[2 * GR_THREADS + t] = iy;
-        part[3 * GR_THREADS + t] = iz;
-        part[4 * GR_THREADS + t] = rx;
-        part[5 * GR_THREADS + t] = ry;
-        part[6 * GR_THREADS + t] = rz;
+        part[GRASP_THREADS + t] = ix;
+        part[2 * GRASP_THREADS + t] = iy;
+        part[3 * GRASP_THREADS + t] = iz;
+        part[4 * GRASP_THREADS + t] = rx;
+        part[5 * GRASP_THREADS + t] = ry;
+        part[6 * GRASP_THREADS + t] = rz;
         cnt[t] = n_in;
-        cnt[GR_THREADS + t] = n_ct;
-        cnt[2 * GR_THREADS + t] = n_nr;
+        cnt[GRASP_THREADS + t] = n_ct;
+        cnt[2 * GRASP_THREADS + t] = n_nr;
         dvq_lds_barrier();
-        for (int s = GR_THREADS / 2; s >= 1; s >>= 1) {          // the canonical tree, each sum on its own: part[t] += part[t + s] for t < s
+        for (int s = GRASP_THREADS / 2; s >= 1; s >>= 1) {       // the canonical tree, each sum on its own: part[t] += part[t + s] for t < s
             if (t < s) {
 #pragma unroll
-                for (int c = 0; c < GR_SUMS; ++c) part[c * GR_THREADS + t] += part[c * GR_THREADS + t + s];
+                for (int c = 0; c < GR_SUMS; ++c) part[c * GRASP_THREADS + t] += part[c * GRASP_THREADS + t + s];
 #pragma unroll
-                for (int c = 0; c < GR_CNTS; ++c) cnt[c * GR_THREADS + t] += cnt[c * GR_THREADS + t + s];
+                for (int c = 0; c < GR_CNTS; ++c) cnt[c * GRASP_THREADS + t] += cnt[c * GRASP_THREADS + t + s];
             }
             dvq_lds_barrier();
         }
         const float pen = part[0];
-        const float s_in[3] = {part[GR_THREADS], part[2 * GR_THREADS], part[3 * GR_THREADS]};
-        const float s_nr[3] = {part[4 * GR_THREADS], part[5 * GR_THREADS], part[6 * GR_THREADS]};
-        const int c_in = cnt[0], c_ct = cnt[GR_THREADS], c_nr = cnt[2 * GR_THREADS];
+        const float s_in[3] = {part[GRASP_THREADS], part[2 * GRASP_THREADS], part[3 * GRASP_THREADS]};
+        const float s_nr[3] = {part[4 * GRASP_THREADS], part[5 * GRASP_THREADS], part[6 * GRASP_THREADS]};
+        const int c_in = cnt[0], c_ct = cnt[GRASP_THREADS], c_nr = cnt[2 * GRASP_THREADS];
         dvq_lds_barrier();                                       // every thread has the totals before the next step's partial sums land
         // from here on every thread holds the same values: the decisions below are uniform over the workgroup
         const int cls = pen != pen ? 2 : (c_ct < min_contact ? 1 : 0);
@@ -232,8 +153,8 @@ extern "C" int dvq_grasp_refine(const float* hand, const int32_t* faces, const i
                                 int64_t B, int N, float contact_threshold, int steps, float push, float pull, int min_contact,
                                 float* offset, int32_t* iter, float* penetration, int32_t* n_interior, int32_t* n_contact,
                                 dvq_stream_t stream) {
-    DVQ_REQUIRE(B >= 0 && N >= 1 && V >= 1 && V <= GR_MAX_V, "grasp_refine: need B >= 0, N >= 1, 1 <= V <= %d (got B=%ld N=%d V=%d)",
-                GR_MAX_V, (long)B, N, V);
+    DVQ_REQUIRE(B >= 0 && N >= 1 && V >= 1 && V <= GRASP_MAX_V, "grasp_refine: need B >= 0, N >= 1, 1 <= V <= %d (got B=%ld N=%d V=%d)",
+                GRASP_MAX_V, (long)B, N, V);
     DVQ_REQUIRE(steps >= 0 && steps <= GR_MAX_STEPS, "grasp_refine: need 0 <= steps <= %d (got %d)", GR_MAX_STEPS, steps);
     DVQ_REQUIRE(push >= 0.0f && push < INFINITY && pull >= 0.0f && pull < INFINITY,
                 "grasp_refine: push and pull must be finite and >= 0 (got %g, %g)", (double)push, (double)pull);
@@ -241,16 +162,16 @@ extern "C" int dvq_grasp_refine(const float* hand, const int32_t* faces, const i
     DVQ_REQUIRE(hand && faces && vf_off && vf_face && obj && offset && iter && penetration && n_interior && n_contact,
                 "grasp_refine: null pointer");
     hipStream_t st = (hipStream_t)stream;
-    const size_t lds = (size_t)(6 * ((V + 3) & ~3) + GR_RED) * 4;
+    const size_t lds = grasp_lds_bytes(V, GR_RED);
     static DvqOncePerDevice attr_once;
-    DVQ_PROPAGATE(dvq_lds_limit(attr_once, reinterpret_cast<const void*>(&grasp_refine_kernel), (size_t)(6 * GR_MAX_V + GR_RED) * 4,
+    DVQ_PROPAGATE(dvq_lds_limit(attr_once, reinterpret_cast<const void*>(&grasp_refine_kernel), grasp_lds_bytes(GRASP_MAX_V, GR_RED),
                                 "grasp_refine"));
     for (int64_t b0 = 0; b0 < B; b0 += 65535) {                  // the grid-dimension limit the neighbouring entry points chunk by
         const int64_t nb = B - b0 < 65535 ? B - b0 : 65535;
         // at most steps + 1 scans of 8 FLOPs per (point, vertex) pair (a grasp may end early); in: the hand and the topology once,
         // the cloud once per scan; out: 28 B per grasp
         DVQ_PROF("grasp_refine", 8.0 * nb * N * V * (steps + 1), (double)nb * ((double)V * 12 + (double)N * 12 * (steps + 1) + 28), st);
-        DVQ_LAUNCH(grasp_refine_kernel, dim3((unsigned)nb), dim3(GR_THREADS), lds, st, hand + b0 * V * 3, faces, vf_off, vf_face, V,
+        DVQ_LAUNCH(grasp_refine_kernel, dim3((unsigned)nb), dim3(GRASP_THREADS), lds, st, hand + b0 * V * 3, faces, vf_off, vf_face, V,
                    obj + b0 * obj_batch_stride, (long)obj_batch_stride, (long)obj_point_stride, (long)obj_coord_stride, N,
                    contact_threshold, steps, push, pull, min_contact, offset + 3 * b0, iter + b0, penetration + b0, n_interior + b0,
                    n_contact + b0);

@@ -15,11 +15,12 @@
 // LDS: 12 (V + L) + 16 KB of bit words (the box's and the depth's reduction columns borrow them first) + 8 KB of ranges: 33 KB at
 // MANO's 779 vertices (four workgroups per CU), 49 KB at the largest hand.
 #include "dvq_internal.h"
+#include "grasp_scan.h"
 
 namespace {
 
-constexpr int GV_THREADS = 256;
-constexpr int GV_MAX_V = 2048;
+constexpr int GV_THREADS = GRASP_THREADS;   // (the hand load is grasp_scan.h's)
+constexpr int GV_MAX_V = GRASP_MAX_V;
 constexpr int GV_MAX_L = 64;
 constexpr int GV_MAX_F = 8192;
 constexpr int GV_MAX_P = 8192;
@@ -94,18 +95,7 @@ __global__ __launch_bounds__(GV_THREADS) void grasp_volume_kernel(const float* _
 
     if (t < GV_SMALL) small[t] = 0;
     dvq_lds_barrier();
-    {                                                                      // the hand as given, and whether it is finite
-        const float* vb = hand + b * V * 3;
-        bool odd = false;
-        for (int i = t; i < V; i += GV_THREADS) {
-            const float x = vb[3 * i], y = vb[3 * i + 1], z = vb[3 * i + 2];
-            vx[i] = x;
-            vy[i] = y;
-            vz[i] = z;
-            odd |= !(fabsf(x) < INFINITY) || !(fabsf(y) < INFINITY) || !(fabsf(z) < INFINITY);
-        }
-        if (odd) small[0] = 1;
-    }
+    if (grasp_load_hand(hand + b * V * 3, V, t, vx, vy, vz)) small[0] = 1;    // the hand as given, and whether it is finite
     dvq_lds_barrier();
     if (small[0]) {
         if (t == 0) {

@@ -706,31 +706,39 @@ def interior(normals: Tensor, hand: Tensor, obj: Tensor, nn_idx: Tensor) -> Tens
     return out.bool()
 
 
-GRASP_SCORES_MAX_V = 2048          # csrc/contact.hip: GS_MAX_V (the hand and its normals sit in LDS)
+GRASP_SCORES_MAX_V = 2048          # csrc/grasp_scan.h: GRASP_MAX_V (the hand and its normals sit in LDS)
 SEGMENT_TOPK_MAX_M = 4096          # csrc/contact.hip: TOPK_MAX_M
+
+
+def _hand_cloud_args(what: str, hand: Tensor, faces: Tensor, vf_off: Tensor, vf_face: Tensor, obj: Tensor):
+    """The arguments ``grasp_scores``, ``grasp_wrench`` and ``grasp_refine`` share -- hand [B,V,3] contiguous, the topology of
+    ``contact.face_csr``, obj [B,N,3] with any strides -- checked before any device use -> (obj's pointer and its three strides,
+    B, V, N)."""
+    for t, n in ((hand, "hand"), (obj, "obj"), (faces, "faces"), (vf_off, "vf_off"), (vf_face, "vf_face")):
+        if not isinstance(t, Tensor):
+            raise RuntimeError(f"{what}: {n} must be a tensor")
+    _f32(hand, "hand")
+    for t, n in ((faces, "faces"), (vf_off, "vf_off"), (vf_face, "vf_face")):
+        if t.dtype != torch.int32 or not t.is_contiguous():
+            raise RuntimeError(f"{what}: {n} must be contiguous int32")
+    if hand.dim() != 3 or hand.shape[2] != 3 or not hand.is_contiguous():
+        raise RuntimeError(f"{what}: hand must be contiguous [B,V,3]")
+    po, ob, op, oc = _points(obj, "obj")
+    B, V, N = hand.shape[0], hand.shape[1], obj.shape[1]
+    if obj.shape[0] != B:
+        raise RuntimeError(f"{what}: batch mismatch")
+    if N < 1 or not 1 <= V <= GRASP_SCORES_MAX_V:
+        raise RuntimeError(f"{what}: need N >= 1 and 1 <= V <= {GRASP_SCORES_MAX_V} (got N={N} V={V})")
+    if faces.dim() != 2 or faces.shape[1] != 3 or vf_off.numel() != V + 1 or vf_face.numel() != faces.numel():
+        raise RuntimeError(f"{what}: CSR does not match the mesh")
+    return po, ob, op, oc, B, V, N
 
 
 def grasp_scores(hand: Tensor, faces: Tensor, vf_off: Tensor, vf_face: Tensor, obj: Tensor, contact_threshold: float = 0.02 ** 2):
     """Per-grasp ``(penetration [B] f32, n_interior [B] i32, n_contact [B] i32)`` in one fused kernel (dvq_grasp_scores): hand
     [B,V,3] contiguous, the topology of ``contact.face_csr`` on the device, obj [B,N,3] with any strides.  Per point the bits of
     ``vertex_normals`` / ``nn_points`` / ``interior``; the sums in the fixed order include/dvq.h documents."""
-    for t, n in ((hand, "hand"), (obj, "obj"), (faces, "faces"), (vf_off, "vf_off"), (vf_face, "vf_face")):
-        if not isinstance(t, Tensor):
-            raise RuntimeError(f"grasp_scores: {n} must be a tensor")
-    _f32(hand, "hand")
-    for t, n in ((faces, "faces"), (vf_off, "vf_off"), (vf_face, "vf_face")):
-        if t.dtype != torch.int32 or not t.is_contiguous():
-            raise RuntimeError(f"grasp_scores: {n} must be contiguous int32")
-    if hand.dim() != 3 or hand.shape[2] != 3 or not hand.is_contiguous():
-        raise RuntimeError("grasp_scores: hand must be contiguous [B,V,3]")
-    po, ob, op, oc = _points(obj, "obj")
-    B, V, N = hand.shape[0], hand.shape[1], obj.shape[1]
-    if obj.shape[0] != B:
-        raise RuntimeError("grasp_scores: batch mismatch")
-    if N < 1 or not 1 <= V <= GRASP_SCORES_MAX_V:
-        raise RuntimeError(f"grasp_scores: need N >= 1 and 1 <= V <= {GRASP_SCORES_MAX_V} (got N={N} V={V})")
-    if faces.dim() != 2 or faces.shape[1] != 3 or vf_off.numel() != V + 1 or vf_face.numel() != faces.numel():
-        raise RuntimeError("grasp_scores: CSR does not match the mesh")
+    po, ob, op, oc, B, V, N = _hand_cloud_args("grasp_scores", hand, faces, vf_off, vf_face, obj)
     dev = _require_gpu(hand, obj, faces, vf_off, vf_face)
     lib = _lib.load()
     pen = torch.empty(B, dtype=torch.float32, device=dev)
@@ -752,23 +760,7 @@ def grasp_wrench(hand: Tensor, faces: Tensor, vf_off: Tensor, vf_face: Tensor, o
     ``(penetration [B] f32, n_interior [B] i32, n_contact [B] i32, centre [B,3] f32, sums [B,27] f32, key [B] f32)``.  The first
     three are the bits of ``grasp_scores``; ``inv_length`` is the reciprocal of the length that scales torques to forces.
     Arguments as ``grasp_scores`` (obj [B,N,3] with any strides, read in place)."""
-    for t, n in ((hand, "hand"), (obj, "obj"), (faces, "faces"), (vf_off, "vf_off"), (vf_face, "vf_face")):
-        if not isinstance(t, Tensor):
-            raise RuntimeError(f"grasp_wrench: {n} must be a tensor")
-    _f32(hand, "hand")
-    for t, n in ((faces, "faces"), (vf_off, "vf_off"), (vf_face, "vf_face")):
-        if t.dtype != torch.int32 or not t.is_contiguous():
-            raise RuntimeError(f"grasp_wrench: {n} must be contiguous int32")
-    if hand.dim() != 3 or hand.shape[2] != 3 or not hand.is_contiguous():
-        raise RuntimeError("grasp_wrench: hand must be contiguous [B,V,3]")
-    po, ob, op, oc = _points(obj, "obj")
-    B, V, N = hand.shape[0], hand.shape[1], obj.shape[1]
-    if obj.shape[0] != B:
-        raise RuntimeError("grasp_wrench: batch mismatch")
-    if N < 1 or not 1 <= V <= GRASP_SCORES_MAX_V:
-        raise RuntimeError(f"grasp_wrench: need N >= 1 and 1 <= V <= {GRASP_SCORES_MAX_V} (got N={N} V={V})")
-    if faces.dim() != 2 or faces.shape[1] != 3 or vf_off.numel() != V + 1 or vf_face.numel() != faces.numel():
-        raise RuntimeError("grasp_wrench: CSR does not match the mesh")
+    po, ob, op, oc, B, V, N = _hand_cloud_args("grasp_wrench", hand, faces, vf_off, vf_face, obj)
     inv_length = float(inv_length)
     if not 0.0 < inv_length < float("inf"):
         raise RuntimeError(f"grasp_wrench: inv_length must be finite and positive (got {inv_length})")
@@ -868,23 +860,7 @@ def grasp_refine(hand: Tensor, faces: Tensor, vf_off: Tensor, vf_face: Tensor, o
     descent on the scores of ``grasp_scores`` with respect to the hand's translation.  Returns ``(offset [B,3] f32, iter [B] i32,
     penetration [B] f32, n_interior [B] i32, n_contact [B] i32)`` of each grasp's best iterate -- add ``offset`` to the hand's
     translation.  Arguments as ``grasp_scores`` (obj [B,N,3] with any strides, read in place)."""
-    for t, n in ((hand, "hand"), (obj, "obj"), (faces, "faces"), (vf_off, "vf_off"), (vf_face, "vf_face")):
-        if not isinstance(t, Tensor):
-            raise RuntimeError(f"grasp_refine: {n} must be a tensor")
-    _f32(hand, "hand")
-    for t, n in ((faces, "faces"), (vf_off, "vf_off"), (vf_face, "vf_face")):
-        if t.dtype != torch.int32 or not t.is_contiguous():
-            raise RuntimeError(f"grasp_refine: {n} must be contiguous int32")
-    if hand.dim() != 3 or hand.shape[2] != 3 or not hand.is_contiguous():
-        raise RuntimeError("grasp_refine: hand must be contiguous [B,V,3]")
-    po, ob, op, oc = _points(obj, "obj")
-    B, V, N = hand.shape[0], hand.shape[1], obj.shape[1]
-    if obj.shape[0] != B:
-        raise RuntimeError("grasp_refine: batch mismatch")
-    if N < 1 or not 1 <= V <= GRASP_SCORES_MAX_V:
-        raise RuntimeError(f"grasp_refine: need N >= 1 and 1 <= V <= {GRASP_SCORES_MAX_V} (got N={N} V={V})")
-    if faces.dim() != 2 or faces.shape[1] != 3 or vf_off.numel() != V + 1 or vf_face.numel() != faces.numel():
-        raise RuntimeError("grasp_refine: CSR does not match the mesh")
+    po, ob, op, oc, B, V, N = _hand_cloud_args("grasp_refine", hand, faces, vf_off, vf_face, obj)
     steps, min_contact, push, pull = int(steps), int(min_contact), float(push), float(pull)
     if not 0 <= steps <= GRASP_REFINE_MAX_STEPS:
         raise RuntimeError(f"grasp_refine: need 0 <= steps <= {GRASP_REFINE_MAX_STEPS} (got {steps})")

@@ -1,0 +1,123 @@
+"""The seams of csrc/grasp_scan.h -- the hand in LDS and the nearest-vertex scan that dvq_grasp_scores, dvq_grasp_refine and
+dvq_grasp_wrench share -- at sizes the MANO-sized cases of the other grasp tests do not reach: hands of 3, 5 and 7 vertices (no
+four-vertex block at all; one block and a tail of one; one block and a tail of three) against clouds of 1, 257 and 1025 points (one
+point; a second thread block of points; a second 4 x 256 pass with a single live point).  Every batch has a finite row, a row whose
+hand holds a NaN (the whole row takes the exact scan) and a row whose last point holds an inf (only that thread's pass takes it).
+The references are tests/grasp_score_ref.py, grasp_refine_ref.py and grasp_wrench_ref.py; everything is compared bit for bit."""
+import functools
+import hashlib
+
+import numpy as np
+import pytest
+import torch
+
+import dvqvae_amd  # noqa: F401
+from dvqvae_amd import contact, ops, synth
+
+import grasp_refine_ref as refine_ref
+import grasp_score_ref as score_ref
+import grasp_wrench_ref as wrench_ref
+
+DEV = "cuda:0"
+THR, INV_LENGTH, STEPS = 0.02 ** 2, 10.0, 2
+SIZES = [(V, N) for V in (3, 5, 7) for N in (1, 257, 1025)]
+SCORES = ("penetration", "n_interior", "n_contact")
+REFINE = ("offset", "iter") + SCORES
+WRENCH = SCORES + ("centre", "sums", "key")
+
+
+def fan(V):
+    """A triangle fan about vertex 0: open for V = 3 (one face) and V = 5 (three faces), closed for V = 7 (six faces)."""
+    rim = list(range(1, V))
+    pairs = list(zip(rim, rim[1:])) + ([(rim[-1], rim[0])] if V == 7 else [])
+    return np.asarray([(0, a, b) for a, b in pairs], np.int64)
+
+
+@functools.lru_cache(maxsize=None)
+def case(V, N):
+    """(hand [3,V,3], faces, obj [3,N,3], the three references' outputs as dicts): computed once per size, never written to."""
+    hand = synth.synthetic_normal((3, V, 3), 61, f"scan/{V}x{N}/h", 0.03).numpy()
+    obj = synth.synthetic_normal((3, N, 3), 61, f"scan/{V}x{N}/o", 0.03).numpy()
+    hand[1, V - 1, 1] = np.nan
+    obj[2, N - 1, 0] = np.inf
+    faces = fan(V)
+    with np.errstate(all="ignore"):
+        want = {"scores": dict(zip(SCORES, score_ref.grasp_scores(hand, faces, obj, THR))),
+                "refine": dict(zip(REFINE, refine_ref.grasp_refine(hand, faces, obj, STEPS, contact_threshold=THR))),
+                "wrench": wrench_ref.grasp_wrench(hand, faces, obj, INV_LENGTH, THR)}
+    for a in [hand, faces, obj] + [x for d in want.values() for x in d.values()]:
+        a.setflags(write=False)
+    return hand, faces, obj, want
+
+
+def assert_same_bits(got, want, names, what):
+    """Every number bit for bit; a NaN is a NaN (its payload is nobody's contract)."""
+    for k in names:
+        g, w = np.asarray(got[k]), np.asarray(want[k])
+        assert g.shape == w.shape and g.dtype == w.dtype, (what, k, g.dtype, w.dtype)
+        if w.dtype != np.float32:
+            assert np.array_equal(g, w), (what, k, g, w)
+            continue
+        nan = np.isnan(w)
+        assert np.array_equal(np.isnan(g), nan), (what, k, g, w)
+        assert np.array_equal(g.view(np.uint32)[~nan], w.view(np.uint32)[~nan]), (what, k, g, w)
+
+
+def digest(want):
+    """sha256 over the three references' outputs in their documented order, every NaN as the one quiet NaN."""
+    h = hashlib.sha256()
+    for part, names in (("scores", SCORES), ("refine", REFINE), ("wrench", WRENCH)):
+        for k in names:
+            a = np.array(want[part][k])
+            if a.dtype == np.float32:
+                a[np.isnan(a)] = np.float32(np.nan)
+            h.update(np.ascontiguousarray(a).astype(a.dtype.newbyteorder("<")).tobytes())
+    return h.hexdigest()
+
+
+# the references on two of the sizes, as they stood when the kernels came to share grasp_scan.h: a reference cannot drift together
+# with the kernels
+PINNED = {
+    (5, 257): dict(n_interior=[88, 0, 150], n_contact=[40, 0, 47], iter=[2, 0, 2],
+                   sha256="dce96c68039614fbe8940f1f30b24f4fe51d0c6ba50b653289f3b4bab8b93297"),
+    (7, 1025): dict(n_interior=[559, 0, 346], n_contact=[97, 0, 181], iter=[2, 0, 2],
+                    sha256="ccdbdb3e3d9b0b3e58369adf12582d771462b8e8d8604ce8e20c70cd33fc9e60"),
+}
+
+
+@pytest.mark.parametrize("V,N", sorted(PINNED))
+def test_the_references_give_what_they_gave(V, N):
+    hand, faces, obj, want = case(V, N)
+    assert len(faces) == {3: 1, 5: 3, 7: 6}[V] and np.isnan(hand[1]).sum() == 1 and np.isinf(obj[2]).sum() == 1
+    assert np.isfinite(hand[[0, 2]]).all() and np.isfinite(obj[:2]).all()
+    got = dict(n_interior=want["scores"]["n_interior"].tolist(), n_contact=want["scores"]["n_contact"].tolist(),
+               iter=want["refine"]["iter"].tolist(), sha256=digest(want))
+    assert got == PINNED[(V, N)]
+    # what the kernels owe each other holds between the references too
+    zero = dict(zip(REFINE, refine_ref.grasp_refine(hand, faces, obj, 0, contact_threshold=THR)))
+    assert_same_bits(zero, want["scores"], SCORES, "reference: steps = 0")
+    assert_same_bits(want["wrench"], want["scores"], SCORES, "reference: the wrench's scores")
+    assert np.isnan(want["scores"]["penetration"][1]) and not np.isnan(want["scores"]["penetration"][0])
+
+
+def gpu(a):
+    return torch.from_numpy(np.array(a)).to(DEV)                          # (a copy: the cached arrays are read-only)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("V,N", SIZES)
+def test_the_three_kernels_agree_with_their_references_and_each_other(V, N):
+    hand, faces, obj, want = case(V, N)
+    topo = contact.HandTopology(faces, V, DEV)
+    args = (gpu(hand), topo.faces, topo.vf_off, topo.vf_face, gpu(obj))
+    host = lambda names, out: dict(zip(names, (x.cpu().numpy() for x in out)))
+    scores = host(SCORES, ops.grasp_scores(*args, contact_threshold=THR))
+    zero = host(REFINE, ops.grasp_refine(*args, steps=0, contact_threshold=THR))
+    refined = host(REFINE, ops.grasp_refine(*args, steps=STEPS, contact_threshold=THR))
+    wrench = host(WRENCH, ops.grasp_wrench(*args, inv_length=INV_LENGTH, contact_threshold=THR))
+    assert_same_bits(scores, want["scores"], SCORES, "grasp_scores")
+    assert_same_bits(zero, scores, SCORES, "grasp_refine(steps=0) against grasp_scores")
+    assert not zero["offset"].any() and not zero["iter"].any()
+    assert_same_bits(wrench, scores, SCORES, "grasp_wrench's scores against grasp_scores")
+    assert_same_bits(refined, want["refine"], REFINE, "grasp_refine")
+    assert_same_bits(wrench, want["wrench"], WRENCH, "grasp_wrench")
