@@ -4,6 +4,9 @@
 (``knn_points``, ``Meshes.verts_normals_packed``), which is not available here: parity is pinned against
 ``oracle/contact_oracle.py`` (a numpy restatement of the published algorithms), not against pytorch3d output.
 """
+import json
+import os
+
 import numpy as np
 import torch
 
@@ -251,6 +254,136 @@ def volume_limit(max_volume, res):
     """``--max_volume`` X cm^3 as the largest voxel count allowed, floor(X / (res^3 * 1e6)) in float64; +inf -> 2^31 - 1 (no limit)."""
     x = float(max_volume) / (float(res) ** 3 * 1e6)
     return int(min(np.floor(x), 2 ** 31 - 1))
+
+
+HAND_PARTS_JSON = os.path.join(os.path.dirname(os.path.abspath(__file__)), "network", "hand_parts.json")
+PART_THRESHOLD = 0.005             # metres: the reference's hard-contact tolerance (penetration_tol, CMap_consistency_loss); untuned
+
+
+class HandParts:
+    """A partition of the hand's vertices into parts for ``grasp_parts``: ``labels`` [V] (the part of every vertex, -1 = no part),
+    ``names`` (one per part, at most 32; by convention the fingers come first, the thumb as part 0) and the device the int32 label
+    vector lives on (None: it follows the first hand it is used with)."""
+
+    def __init__(self, labels, names, device=None):
+        lab = np.asarray(labels.detach().cpu() if torch.is_tensor(labels) else labels)
+        if lab.ndim != 1 or lab.size < 1 or lab.dtype.kind not in "iu":
+            raise RuntimeError("HandParts: labels must be a non-empty 1-D integer array, one label per vertex")
+        self.names = [str(n) for n in names]
+        if not 1 <= len(self.names) <= ops.GRASP_PARTS_MAX_P:
+            raise RuntimeError(f"HandParts: between 1 and {ops.GRASP_PARTS_MAX_P} parts (got {len(self.names)})")
+        lab = lab.astype(np.int64)
+        self.labels = np.where((lab >= 0) & (lab < len(self.names)), lab, -1).astype(np.int32)
+        self.n_verts, self.n_parts = int(lab.size), len(self.names)
+        self.sizes = np.bincount(self.labels[self.labels >= 0], minlength=self.n_parts).astype(np.int64)
+        self._dev = {}
+        if device is not None:
+            self.on(torch.device(device))
+
+    def on(self, device):
+        """The int32 label vector on ``device`` (uploaded once per device)."""
+        key = str(device)
+        if key not in self._dev:
+            self._dev[key] = torch.from_numpy(self.labels).to(device)
+        return self._dev[key]
+
+    @classmethod
+    def from_json(cls, path=None, device=None):
+        """A label table ``{"order": [names], "parts": [[vertex indices], ...]}``, the packaged ``network/hand_parts.json`` (MANO's 778
+        vertices: thumb, four fingers, palm) by default, in the file's own order.  A vertex listed by two parts takes the first; the
+        vertex count is the file's ``"n_verts"``, or one more than the largest index listed."""
+        with open(path or HAND_PARTS_JSON) as f:
+            table = json.load(f)
+        names, parts = table["order"], table["parts"]
+        if len(names) != len(parts):
+            raise RuntimeError(f"HandParts.from_json: {len(names)} names for {len(parts)} parts")
+        flat = [int(v) for p in parts for v in p]
+        if not flat or min(flat) < 0:
+            raise RuntimeError("HandParts.from_json: the parts list no vertex, or a negative one")
+        n_verts = int(table.get("n_verts", max(flat) + 1))
+        if max(flat) >= n_verts:
+            raise RuntimeError(f"HandParts.from_json: vertex {max(flat)} of a table of {n_verts} vertices")
+        labels = np.full(n_verts, -1, np.int64)
+        for q in reversed(range(len(parts))):                   # the first part that lists a vertex is written last
+            labels[np.asarray(parts[q], np.int64)] = q
+        return cls(labels, names, device)
+
+
+def grasp_parts(parts, hand_xyz, obj_xyz, threshold=PART_THRESHOLD, want_verts=False):
+    """Which parts of the hand touch the object, from ONE fused kernel (ops.grasp_parts; the definition is in include/dvq.h under
+    dvq_grasp_parts): every hand vertex finds its nearest object point, and a vertex closer than ``threshold`` METRES (squared once,
+    here) touches.  Returns ``part_min`` [B,P] f32 (per part the smallest squared distance, +inf for a part without a vertex),
+    ``part_count`` [B,P] i32 (its touching vertices), ``mask`` [B,W] i32 (bit v & 31 of word v >> 5: vertex v touches) and
+    ``status`` [B] i32 (1: a coordinate of the row is not finite, and the row has no figure: NaN, -1, 0); with ``want_verts`` also
+    ``vert_dist`` [B,V] f32 and ``vert_idx`` [B,V] i32, the bits of ``get_NN(hand_xyz, obj_xyz)``.  ``part_stats`` /
+    ``contact_map`` / ``parts_class`` turn them into the figures written and into a selection guard.
+
+    A proximity figure from the hand's side: no contact-force model.  The default threshold is the reference's 5 mm hard-contact
+    tolerance and is UNTUNED; its effect on real grasps is NOT measured (no real checkpoint)."""
+    threshold = float(threshold)
+    if not 0.0 < threshold < float("inf"):
+        raise RuntimeError(f"grasp_parts: threshold must be finite and positive (got {threshold})")
+    if not torch.is_tensor(hand_xyz) or hand_xyz.dim() != 3 or hand_xyz.shape[1] != parts.n_verts:
+        raise RuntimeError(f"grasp_parts: the label table has {parts.n_verts} vertices, the hand "
+                           f"{tuple(hand_xyz.shape) if torch.is_tensor(hand_xyz) else type(hand_xyz)}")
+    part_min, part_count, mask, status, vert_dist, vert_idx = ops.grasp_parts(hand_xyz.contiguous(), parts.on(hand_xyz.device),
+                                                                              parts.n_parts, obj_xyz, threshold * threshold, want_verts)
+    out = {"part_min": part_min, "part_count": part_count, "mask": mask, "status": status}
+    if want_verts:
+        out.update(vert_dist=vert_dist, vert_idx=vert_idx)
+    return out
+
+
+def _host(x, dtype):
+    return np.asarray(x.detach().cpu() if torch.is_tensor(x) else x, dtype=dtype)
+
+
+def part_stats(part_min, part_count, status, min_verts=1, n_fingers=5):
+    """Host side, float64, row by row, from ``grasp_parts``' ``part_min`` [B,P], ``part_count`` [B,P] and ``status`` [B] (arrays or
+    tensors): ``fingers_in_contact`` = how many of the first ``n_fingers`` parts have at least ``min_verts`` touching vertices,
+    ``part_contact`` = the P counts, ``part_dist`` = sqrt(part_min) * 100, each part's smallest distance to the cloud in cm.  Three
+    lists; ``None`` where the row has no figure (status != 0) and, in ``part_dist``, where the part has no vertex (json writes
+    null)."""
+    pm = _host(part_min, np.float64)
+    pc = _host(part_count, np.int64)
+    st = _host(status, np.int64).reshape(-1)
+    if pm.ndim != 2 or pm.shape != pc.shape or st.shape[0] != pm.shape[0]:
+        raise RuntimeError("part_stats: part_min and part_count [B,P], one status per row")
+    min_verts, n_fingers = int(min_verts), int(n_fingers)
+    if min_verts < 1 or not 0 <= n_fingers <= pm.shape[1]:
+        raise RuntimeError(f"part_stats: min_verts >= 1 and 0 <= n_fingers <= {pm.shape[1]} (got {min_verts}, {n_fingers})")
+    fingers, counts, dists = [], [], []
+    for m, c, s in zip(pm, pc, st):
+        if s != 0:
+            fingers.append(None), counts.append(None), dists.append(None)
+            continue
+        fingers.append(int(np.sum(c[:n_fingers] >= min_verts)))
+        counts.append([int(k) for k in c])
+        dists.append([float(np.sqrt(x)) * 100.0 if np.isfinite(x) else None for x in m])
+    return {"fingers_in_contact": fingers, "part_contact": counts, "part_dist": dists}
+
+
+def contact_map(mask, n_verts):
+    """int64 [V] (numpy): at every vertex, how many of the given rows of ``grasp_parts``' ``mask`` [B,W] touch there."""
+    m = np.ascontiguousarray(_host(mask, np.int32)).view(np.uint32)
+    n_verts = int(n_verts)
+    if m.ndim != 2 or m.shape[1] != (n_verts + 31) // 32:
+        raise RuntimeError(f"contact_map: mask must be [B,{(n_verts + 31) // 32}] for {n_verts} vertices (got {m.shape})")
+    v = np.arange(n_verts)
+    return ((m[:, v >> 5] >> (v & 31).astype(np.uint32)) & np.uint32(1)).astype(np.int64).sum(axis=0)
+
+
+def parts_class(out, min_fingers, need_thumb, min_verts=1, n_fingers=5):
+    """int32 [B] on the device, integer operations only, for ``torch.maximum`` with the class of ``select_keys``: 2 where the row of
+    ``grasp_parts``' output has no figure (status != 0), else 1 where fewer than ``min_fingers`` of the first ``n_fingers`` parts have
+    at least ``min_verts`` touching vertices, or where ``need_thumb`` is set and part 0 has not, else 0."""
+    cnt, status = out["part_count"], out["status"]
+    on = cnt[:, :int(n_fingers)] >= int(min_verts)
+    poor = on.sum(dim=1) < int(min_fingers)
+    if need_thumb:
+        poor = poor | ~on[:, 0]
+    one, two = torch.ones_like(status), torch.full_like(status, 2)
+    return torch.where(status != 0, two, torch.where(poor, one, torch.zeros_like(status))).to(torch.int32)
 
 
 SELECT_BY = ("penetration", "log_prob", "stability")

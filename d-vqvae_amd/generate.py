@@ -110,6 +110,24 @@ def build_parser(dataset: str) -> argparse.ArgumentParser:
     p.add_argument("--max_volume", type=float, default=float("inf"),
                    help="best-of-M: candidates whose penetration volume exceeds this many cm^3 rank after all others that touch the object "
                         "(the class --max_penetration uses), whatever --select_by ranks by; needs --candidates (default: no limit)")
+    p.add_argument("--parts", type=int, default=0,
+                   help="1: every grasp's JSON gains \"fingers_in_contact\", \"part_contact\" and \"part_dist\" (cm) and every object's "
+                        "\"hand_contact_map\": which parts of the hand -- thumb, four fingers, palm -- have vertices within "
+                        "--part_threshold of the object's cloud, from the hand's side (one kernel per call), and the run writes "
+                        "hand_contact.json; a proximity figure with an untuned threshold, no contact-force model, effect on real grasps "
+                        "not measured")
+    p.add_argument("--part_threshold", type=float, default=0.005,
+                   help="--parts / --min_fingers / --need_thumb: a hand vertex closer than this many metres to the cloud touches (the "
+                        "reference's 5 mm hard-contact tolerance; untuned)")
+    p.add_argument("--part_min_verts", type=int, default=1, help="touching vertices a part needs to count as in contact")
+    p.add_argument("--min_fingers", type=int, default=0,
+                   help="best-of-M: candidates with fewer than this many of the five fingers in contact rank after all others that touch "
+                        "the object (the class --max_penetration uses), whatever --select_by ranks by; 0..5, above 0 needs --candidates")
+    p.add_argument("--need_thumb", type=int, default=0,
+                   help="best-of-M: 1 = candidates whose thumb is not in contact join that class too; needs --candidates")
+    p.add_argument("--hand_parts", default=None,
+                   help="a label table {\"order\": [names], \"parts\": [[vertex indices], ...]} to use instead of the packaged one "
+                        "(the fingers first, the thumb as part 0)")
     p.add_argument("--refine_push", type=float, default=1.0, help="--refine_steps: step factor on the mean pull vector of the interior points")
     p.add_argument("--refine_pull", type=float, default=0.25,
                    help="--refine_steps: step factor on the mean pull vector of the points within 2 cm outside the hand")
@@ -144,6 +162,16 @@ def parse_args(dataset: str, argv: Optional[Sequence[str]] = None) -> argparse.N
         p.error(f"--max_volume must be >= 0 (got {args.max_volume})")
     if args.max_volume < float("inf") and not args.candidates:
         p.error("--max_volume needs --candidates (it ranks candidates; --volume 1 alone writes the figure)")
+    if not 0.0 < args.part_threshold < float("inf"):
+        p.error(f"--part_threshold must be finite and positive (got {args.part_threshold})")
+    if args.part_min_verts < 1:
+        p.error(f"--part_min_verts must be at least 1 (got {args.part_min_verts})")
+    if not 0 <= args.min_fingers <= 5:
+        p.error(f"--min_fingers must lie between 0 and 5 (got {args.min_fingers})")
+    if args.need_thumb not in (0, 1) or args.parts not in (0, 1):
+        p.error(f"--need_thumb and --parts are 0 or 1 (got {args.need_thumb}, {args.parts})")
+    if (args.min_fingers or args.need_thumb) and not args.candidates:
+        p.error("--min_fingers and --need_thumb need --candidates (they rank candidates; --parts 1 alone writes the figures)")
     return args
 
 
@@ -273,6 +301,19 @@ def _hand_topology(net: GenNet, n_verts: int, dev):
     return topo
 
 
+def _hand_parts(net: GenNet, table):
+    """The label table of ``generate_for_objects``' ``hand_parts``: a ``contact.HandParts`` as given, else the one read from the JSON
+    path (None: the packaged table), kept on the model so that a run reads and uploads it once."""
+    from . import contact
+    if isinstance(table, contact.HandParts):
+        return table
+    cached = getattr(net, "_hand_parts", None)
+    if cached is None or cached[0] != table:
+        cached = (table, contact.HandParts.from_json(table))
+        object.__setattr__(net, "_hand_parts", cached)
+    return cached[1]
+
+
 def plan_calls(point_counts: Sequence[int], num_grasp: int, rows_per_call: int) -> List[List[int]]:
     """Positions of the objects of each batched call.  A call needs one point count: positions are grouped by it (groups in
     the order their first object appears, the given order inside a group) and every group is cut into calls of whole objects,
@@ -294,7 +335,7 @@ def _generate_call(net: GenNet, objs: Sequence[torch.Tensor], num_grasp: int, ro
                    min_contact: int = 1, diverse_pool: int = 0, diverse_space: str = "params", refine_steps: int = 0,
                    refine_push: float = 1.0, refine_pull: float = 0.25, diversity: int = 0, stability: bool = False,
                    max_penetration: float = float("inf"), torque_length: float = 0.1,
-                   volume: Optional[Dict[str, float]] = None) -> List[Dict[str, object]]:
+                   volume: Optional[Dict[str, float]] = None, parts: Optional[Dict[str, object]] = None) -> List[Dict[str, object]]:
     """One batched call: the ``num_grasp`` grasps of each of ``objs`` (all of one point count), row o * num_grasp + g = grasp g
     of object o.  Every step is row-independent and keyed per row, so each object's slice holds the bits of its own
     ``generate_for_object`` call.  With ``candidates`` = M the call generates M rows per object (exactly the grasps of a
@@ -306,7 +347,9 @@ def _generate_call(net: GenNet, objs: Sequence[torch.Tensor], num_grasp: int, ro
     scores come from ``contact.grasp_stability`` (one kernel in the place of ``contact.grasp_scores``) and its sums and key ride
     in that copy too (_stability_json).  With ``volume`` (``res``, ``max_volume``) every object's hull is built once on the host from
     its own unrotated cloud and ONE ``contact.grasp_volume`` runs over all rows of the call, after the push-out (_volume_launch); the
-    rows' counts, depths and states ride in that copy as well (_volume_json)."""
+    rows' counts, depths and states ride in that copy as well (_volume_json).  With ``parts`` (``table``, ``threshold``, ``min_verts``,
+    ``min_fingers``, ``need_thumb``) ONE ``contact.grasp_parts`` runs over all rows of the call, after the push-out too; its four
+    tensors ride in that copy and become the fields of _parts_json."""
     dev = next(net.parameters()).device
     keep = num_grasp
     G, O = (candidates or num_grasp), len(objs)
@@ -344,16 +387,24 @@ def _generate_call(net: GenNet, objs: Sequence[torch.Tensor], num_grasp: int, ro
     vol = None
     if volume:                                                                     # after the push-out: the hands of the parameters written
         vol = _volume_launch(net, objs, final.vertices, obj_of_row, R_dev if rotate else None, t_dev if rotate else None, volume["res"])
+    prt = None
+    if parts:                                                                      # after the push-out: the hands of the parameters written
+        from . import contact
+        prt = contact.grasp_parts(parts["table"], final.vertices, batch[:, :3].transpose(1, 2), parts["threshold"])
     if candidates:
         return _select_call(net, batch, params, final.vertices, logp, err, O, G, keep, select_by, min_contact, want_logp, proxies,
                             np.concatenate(Rs), np.concatenate(angles), t, diverse_pool, diverse_space, refined, diversity, stability,
-                            max_penetration, torque_length, vol, volume)
+                            max_penetration, torque_length, vol, volume, prt, parts)
     ref_lists = {}
     div = _diversity_launch(params, O, G, diversity) if diversity else []
+    prt_t = [prt[k] for k in PARTS_PIECES] if prt is not None else []             # last before the flag in the call's one copy
+    prt_h = None
     if vol is not None and refined is None and not stability:                      # the volume alone: no score is computed
-        host, *vol_h, err_h = _host_copy([params] + [vol[k] for k in VOLUME_PIECES] + div + [err])   # ONE device-to-host copy per call
+        host, *vol_h, err_h = _host_copy([params] + [vol[k] for k in VOLUME_PIECES] + div + prt_t + [err])   # ONE device-to-host copy per call
         if int(err_h[0]) != 0:
             raise RuntimeError("generate_for_objects: object index out of range in transform_clouds")
+        if prt_t:
+            vol_h, prt_h = vol_h[:-len(prt_t)], vol_h[-len(prt_t):]
         div_h = vol_h[len(VOLUME_PIECES):]
         names, tensors = [], {}
         ref_lists = _volume_json(vol_h[:len(VOLUME_PIECES)], volume["res"])
@@ -372,9 +423,11 @@ def _generate_call(net: GenNet, objs: Sequence[torch.Tensor], num_grasp: int, ro
             names = ["refine_offset", "refine_iter"] + names
             tensors.update(refine_offset=refined["offset"], refine_iter=refined["iter"])
         vol_t = [vol[k] for k in VOLUME_PIECES] if vol is not None else []
-        host, *rest_h, err_h = _host_copy([params] + [tensors[k] for k in names] + vol_t + div + [err])   # ONE device-to-host copy per call
+        host, *rest_h, err_h = _host_copy([params] + [tensors[k] for k in names] + vol_t + div + prt_t + [err])   # ONE device-to-host copy per call
         if int(err_h[0]) != 0:
             raise RuntimeError("generate_for_objects: object index out of range in transform_clouds")
+        if prt_t:
+            rest_h, prt_h = rest_h[:-len(prt_t)], rest_h[-len(prt_t):]
         by_name = dict(zip(names, rest_h))
         vol_h, rest_h = rest_h[len(names):len(names) + len(vol_t)], rest_h[:len(names)] + rest_h[len(names) + len(vol_t):]
         names = [k for k in names if k not in ("sums", "key")]
@@ -384,10 +437,12 @@ def _generate_call(net: GenNet, objs: Sequence[torch.Tensor], num_grasp: int, ro
         if vol is not None:
             ref_lists.update(_volume_json(vol_h, volume["res"]))
         div_h = rest_h[len(by_name):]
-    elif div:
-        host, *div_h, err_h = _host_copy([params] + div + [err])                   # ONE device-to-host copy per call
+    elif div or prt_t:
+        host, *div_h, err_h = _host_copy([params] + div + prt_t + [err])           # ONE device-to-host copy per call
         if int(err_h[0]) != 0:
             raise RuntimeError("generate_for_objects: object index out of range in transform_clouds")
+        if prt_t:
+            div_h, prt_h = div_h[:-len(prt_t)], div_h[-len(prt_t):]
     else:
         host = params.cpu().numpy()                                                # ONE device-to-host copy per call
         if int(err.item()) != 0:
@@ -403,6 +458,7 @@ def _generate_call(net: GenNet, objs: Sequence[torch.Tensor], num_grasp: int, ro
     p_dev, v_dev = params.split(G), final.vertices.split(G)
     lp_list = logp.cpu().numpy().tolist() if log_prob else None
     div_dicts = _diversity_dicts(diversity, div_h) if diversity else None
+    prt_lists = _parts_json(prt_h, parts) if prt is not None else None
     outs = []
     for o in range(O):
         lo, hi = o * G, (o + 1) * G
@@ -422,6 +478,9 @@ def _generate_call(net: GenNet, objs: Sequence[torch.Tensor], num_grasp: int, ro
             extra["volume"] = {k: vol[k][lo:hi] for k in VOLUME_PIECES[:3]}
         if diversity:
             extra["diversity"] = extra_json["diversity"] = div_dicts[o]
+        if prt is not None:
+            extra["parts"] = {k: prt[k][lo:hi] for k in PARTS_PIECES}
+            extra_json.update(_parts_slice(prt_lists, prt_h, lo, hi, parts))
         outs.append({**extra, "params": p_dev[o], "vertices": v_dev[o],
                      "json": {"recon_params": [[p] for p in p_list[lo:hi]],           # [[61 floats]] per grasp, as the reference
                               "R_list": Rt_list[lo:hi], "trans_list": [trans] * G, "r_list": r_list[lo:hi], **extra_json}})
@@ -483,6 +542,27 @@ def _volume_json(host: Sequence[np.ndarray], res: float) -> Dict[str, list]:
     return out
 
 
+PARTS_PIECES = ("part_min", "part_count", "mask", "status")     # what a call's parts kernel leaves on the device (contact.grasp_parts)
+PARTS_FIELDS = ("fingers_in_contact", "part_contact", "part_dist")
+
+
+def _parts_json(host: Sequence[np.ndarray], parts: Dict[str, object]) -> Dict[str, list]:
+    """The three per-grasp JSON lists of a call's rows from the host copies of the parts kernel's tensors: float64 on the host, row by
+    row (contact.part_stats); null where a row has no figure."""
+    from . import contact
+    part_min, part_count, _, status = host
+    return contact.part_stats(part_min, part_count, status, parts["min_verts"], min(5, parts["table"].n_parts))
+
+
+def _parts_slice(lists: Dict[str, list], host: Sequence[np.ndarray], lo: int, hi: int, parts: Dict[str, object]) -> Dict[str, list]:
+    """An object's share of _parts_json's lists (its grasps are the rows lo .. hi of the copies) and its "hand_contact_map": at every
+    vertex, how many of those grasps touch there (contact.contact_map)."""
+    from . import contact
+    out = {k: lists[k][lo:hi] for k in PARTS_FIELDS}
+    out["hand_contact_map"] = contact.contact_map(host[2][lo:hi], parts["table"].n_verts).tolist()
+    return out
+
+
 def _diversity_launch(kept: torch.Tensor, O: int, keep: int, clusters: int) -> List[torch.Tensor]:
     """``--diversity``: one ``ops.segment_kmeans`` over the call's kept parameters [O*keep,61], one segment per object, from evenly
     spaced starting rows; the device tensors whose host copies _diversity_dicts reads (counts, dist, iters_used, the error flag)."""
@@ -510,7 +590,8 @@ def _select_call(net: GenNet, batch: torch.Tensor, params: torch.Tensor, vertice
                  diverse_space: str = "params", refined: Optional[Dict[str, torch.Tensor]] = None,
                  diversity: int = 0, stability: bool = False, max_penetration: float = float("inf"),
                  torque_length: float = 0.1, vol: Optional[Dict[str, torch.Tensor]] = None,
-                 volume: Optional[Dict[str, float]] = None) -> List[Dict[str, object]]:
+                 volume: Optional[Dict[str, float]] = None, prt: Optional[Dict[str, torch.Tensor]] = None,
+                 parts: Optional[Dict[str, object]] = None) -> List[Dict[str, object]]:
     """Best-of-M for all the objects of a call together: the candidates' scores (one fused kernel), their keys, each object's
     ``keep`` best (one kernel), one ``index_select`` of the kept rows and one device-to-host copy.  Row o * M + c is candidate c of
     object o; nothing here depends on which objects share the call.  ``diverse_pool`` = P: each object's P best (the same kernel),
@@ -522,7 +603,10 @@ def _select_call(net: GenNet, batch: torch.Tensor, params: torch.Tensor, vertice
     ``contact.grasp_scores``); the kept rows' sums and keys ride along and become the four JSON fields of _stability_json.
     ``vol`` (_volume_launch over all candidates) with ``volume`` = its ``res`` and ``max_volume``: candidates whose voxel count exceeds
     ``contact.volume_limit`` join class 1 and those without a figure class 2 (integer comparisons on the device), whatever ranks the
-    rest; the kept rows' counts, depths and states ride along and become the three JSON fields of _volume_json."""
+    rest; the kept rows' counts, depths and states ride along and become the three JSON fields of _volume_json.
+    ``prt`` (contact.grasp_parts over all candidates) with ``parts`` = its settings: with ``min_fingers`` or ``need_thumb`` the class
+    becomes ``maximum(cls, contact.parts_class(...))`` -- too few fingers on the object joins class 1, a row without a figure class 2 --
+    whatever ranks the rest; the kept rows' four tensors ride along and become the fields of _parts_json."""
     from . import contact
     dev = params.device
     topo = _hand_topology(net, vertices.shape[1], dev)
@@ -537,6 +621,8 @@ def _select_call(net: GenNet, batch: torch.Tensor, params: torch.Tensor, vertice
         cnt = vol["count"]
         over = (cnt > contact.volume_limit(volume["max_volume"], volume["res"])).to(torch.int32)
         cls = torch.maximum(cls, torch.where(cnt < 0, torch.full_like(over, 2), over))
+    if prt is not None and (parts["min_fingers"] or parts["need_thumb"]):
+        cls = torch.maximum(cls, contact.parts_class(prt, parts["min_fingers"], parts["need_thumb"], parts["min_verts"]))
     diverse = []
     if diverse_pool:
         pool = ops.segment_topk(cls.contiguous(), key.contiguous(), O, M, diverse_pool)   # [O,P] candidate indices, best first
@@ -553,7 +639,8 @@ def _select_call(net: GenNet, batch: torch.Tensor, params: torch.Tensor, vertice
     kept_r = [refined["offset"].index_select(0, rows), refined["iter"].index_select(0, rows)] if refined is not None else []
     div = _diversity_launch(kept_p, O, keep, diversity) if diversity else []
     kept_vol = [vol[k].index_select(0, rows) for k in VOLUME_PIECES[:3]] + [vol["err"]] if vol is not None else []
-    host = _host_copy([sel] + [kept_p] + [kept_s[k] for k in names] + kept_r + kept_vol + diverse + div + [err])  # ONE device-to-host copy per call
+    kept_prt = [prt[k].index_select(0, rows) for k in PARTS_PIECES] if prt is not None else []
+    host = _host_copy([sel] + [kept_p] + [kept_s[k] for k in names] + kept_r + kept_vol + kept_prt + diverse + div + [err])  # ONE device-to-host copy per call
     if int(host[-1][0]) != 0:
         raise RuntimeError("generate_for_objects: object index out of range in transform_clouds")
     sel_h, p_list = host[0], host[1].tolist()
@@ -568,8 +655,13 @@ def _select_call(net: GenNet, batch: torch.Tensor, params: torch.Tensor, vertice
     if vol is not None:
         vat = 2 + len(names) + len(kept_r)
         vol_lists = _volume_json(host[vat:vat + len(kept_vol)], volume["res"])
+    prt_lists = None
+    if prt is not None:
+        pat = 2 + len(names) + len(kept_r) + len(kept_vol)
+        prt_h = host[pat:pat + len(kept_prt)]
+        prt_lists = _parts_json(prt_h, parts)
     if diverse_pool:
-        at = 2 + len(names) + len(kept_r) + len(kept_vol)
+        at = 2 + len(names) + len(kept_r) + len(kept_vol) + len(kept_prt)
         rank_h, gap_h, pool_err_h = host[at:at + 3]
         if int(pool_err_h[0]) != 0:
             raise RuntimeError("generate_for_objects: pool entry out of range in segment_diverse")
@@ -604,6 +696,10 @@ def _select_call(net: GenNet, batch: torch.Tensor, params: torch.Tensor, vertice
             extra["volume"] = {k: x[lo:hi] for k, x in zip(VOLUME_PIECES[:3], kept_vol)}
             extra["volume_scores"] = {k: vol[k][o * M:(o + 1) * M] for k in VOLUME_PIECES[:3]}      # of ALL candidates
             extra_json = {**extra_json, **{k: v[lo:hi] for k, v in vol_lists.items()}}
+        if prt is not None:
+            extra["parts"] = {k: x[lo:hi] for k, x in zip(PARTS_PIECES, kept_prt)}
+            extra["part_scores"] = {k: prt[k][o * M:(o + 1) * M] for k in PARTS_PIECES}                 # of ALL candidates
+            extra_json = {**extra_json, **_parts_slice(prt_lists, prt_h, lo, hi, parts)}
         outs.append({**extra, "params": p_dev[o], "vertices": v_dev[o], "candidate": sel[o],
                      "scores": {k: v[o * M:(o + 1) * M] for k, v in scores.items()},
                      "json": {"recon_params": [[p] for p in p_list[lo:hi]], "R_list": Rt_list[lo:hi], "trans_list": [trans] * keep,
@@ -618,7 +714,9 @@ def generate_for_objects(net: GenNet, objs: Sequence[torch.Tensor], num_grasp: i
                          min_contact: int = 1, diverse_pool: int = 0, diverse_space: str = "params", refine_steps: int = 0,
                          refine_push: float = 1.0, refine_pull: float = 0.25, diversity: int = 0, stability: bool = False,
                          max_penetration: float = float("inf"), torque_length: float = 0.1, volume: bool = False,
-                         volume_res: float = 0.001, max_volume: float = float("inf")) -> List[Dict[str, object]]:
+                         volume_res: float = 0.001, max_volume: float = float("inf"), parts: bool = False,
+                         part_threshold: float = 0.005, part_min_verts: int = 1, min_fingers: int = 0, need_thumb: bool = False,
+                         hand_parts=None) -> List[Dict[str, object]]:
     """``num_grasp`` grasps for each of ``objs`` ([4,N] tensors) in batched calls that mix objects (plan_calls): one dict per
     object, in the order given, equal to ``generate_for_object(net, objs[i], num_grasp, rotate,
     np.random.default_rng([seed, object_indices[i]]), seed=seed, object_index=object_indices[i], proxies=proxies)`` (and the same
@@ -678,7 +776,31 @@ def generate_for_objects(net: GenNet, objs: Sequence[torch.Tensor], num_grasp: i
     ``candidates`` also ``volume_scores``, those of ALL candidates) and ``json`` gains "penetration_volume" (cm^3),
     "penetration_depth" (cm) and "volume_voxels" per grasp (``contact.volume_stats``, float64 on the host; null without a figure).
     They ride in the call's one device-to-host copy.  A lower bound of the reference's intersection_eval (the cloud's hull lies inside
-    the mesh's) on the object's own lattice; no igl / trimesh run pins parity.  Without either switch nothing of it runs."""
+    the mesh's) on the object's own lattice; no igl / trimesh run pins parity.  Without either switch nothing of it runs.
+
+    Hand-side contact (``parts=True``, or ``min_fingers`` > 0 / ``need_thumb`` together with ``candidates``): every call launches ONE
+    ``contact.grasp_parts`` over all its rows -- every hand vertex against its row's cloud, a vertex closer than ``part_threshold``
+    metres touches -- after the push-out has re-posed the hands if there is one.  ``hand_parts``: the label table, a
+    ``contact.HandParts``, a JSON path, or None for the packaged MANO table (thumb, four fingers, palm).  ``min_fingers`` = K:
+    candidates with fewer than K of the five fingers in contact (a part counts with ``part_min_verts`` touching vertices) join class
+    1, and so do candidates whose thumb does not touch under ``need_thumb``; rows without a figure join class 2
+    (``contact.parts_class``), whatever ``select_by`` ranks by: a guard only, nothing is ranked by it.  Each dict gains ``parts``
+    (part_min, part_count, mask, status of its grasps; with ``candidates`` also ``part_scores``, those of ALL candidates) and ``json``
+    gains "fingers_in_contact", "part_contact" and "part_dist" (cm) per grasp (``contact.part_stats``, float64 on the host; null
+    without a figure) and "hand_contact_map", per vertex the number of the object's grasps that touch there.  They ride in the
+    call's one device-to-host copy.  A proximity figure with an untuned threshold: no contact-force model, effect on real grasps not
+    measured.  Without these switches nothing of it runs."""
+    parts_args = None
+    if parts or min_fingers or need_thumb:
+        from . import contact
+        if not 0.0 < float(part_threshold) < float("inf"):
+            raise RuntimeError(f"generate_for_objects: part_threshold must be finite and positive (got {part_threshold})")
+        if int(part_min_verts) < 1 or not 0 <= int(min_fingers) <= 5:
+            raise RuntimeError(f"generate_for_objects: part_min_verts >= 1 and 0 <= min_fingers <= 5 (got {part_min_verts}, {min_fingers})")
+        if (min_fingers or need_thumb) and not candidates:
+            raise RuntimeError("generate_for_objects: min_fingers and need_thumb need candidates")
+        parts_args = dict(table=_hand_parts(net, hand_parts), threshold=float(part_threshold), min_verts=int(part_min_verts),
+                          min_fingers=int(min_fingers), need_thumb=bool(need_thumb))
     vol_args = None
     if volume or float(max_volume) < float("inf"):
         if not 0.0 < float(volume_res) < float("inf"):
@@ -729,7 +851,7 @@ def generate_for_objects(net: GenNet, objs: Sequence[torch.Tensor], num_grasp: i
     for call in plan_calls([o.shape[1] for o in objs], candidates or num_grasp, rows_per_call):
         res = _generate_call(net, [objs[p] for p in call], num_grasp, rotate, seed, [object_indices[p] for p in call], proxies,
                              temperature, top_k, log_prob, candidates, select_by, min_contact, diverse_pool, diverse_space, refine_steps,
-                             refine_push, refine_pull, diversity, stability, max_penetration, torque_length, vol_args)
+                             refine_push, refine_pull, diversity, stability, max_penetration, torque_length, vol_args, parts_args)
         for p, r in zip(call, res):
             out[p] = r
     return out
@@ -759,7 +881,8 @@ def main(dataset: str, argv: Optional[Sequence[str]] = None) -> List[str]:
         raise RuntimeError(f"--diversity: the pooled statistic takes at most {ops.SEGMENT_KMEANS_MAX_M} grasps per rank "
                            f"(got {(hi - lo) * args.num_grasp})")
     want_volume = bool(args.volume) or args.max_volume < float("inf")
-    if args.rows_per_call > 0 or args.candidates or args.refine_steps or args.diversity or args.stability or want_volume:
+    want_parts = bool(args.parts) or args.min_fingers > 0 or bool(args.need_thumb)
+    if args.rows_per_call > 0 or args.candidates or args.refine_steps or args.diversity or args.stability or want_volume or want_parts:
         # grouped calls (best-of-M, push-out, the diversity statistic and the stability proxy always: --rows_per_call 0 is then one
         # object per call)
         rows_per_call, per_object = max(1, args.rows_per_call), (args.candidates or args.num_grasp)
@@ -775,6 +898,10 @@ def main(dataset: str, argv: Optional[Sequence[str]] = None) -> List[str]:
             selection.update(stability=True, max_penetration=args.max_penetration, torque_length=args.torque_length)
         if want_volume:
             selection.update(volume=True, volume_res=args.volume_res, max_volume=args.max_volume)
+        if want_parts:
+            selection.update(parts=True, part_threshold=args.part_threshold, part_min_verts=args.part_min_verts,
+                             min_fingers=args.min_fingers, need_thumb=bool(args.need_thumb), hand_parts=args.hand_parts)
+        part_rows: Dict[int, tuple] = {}                                           # --parts: every object's (fingers per grasp, contact map)
         vol_rows: Dict[int, list] = {}                                             # --volume: every object's (voxels, cm^3, cm) per grasp
         kept: Dict[int, np.ndarray] = {}                                           # --diversity: every object's kept parameters, on the host
         # grouped calls: one call's objects at a time, its files written before the next call starts, so the device and the host
@@ -801,6 +928,8 @@ def main(dataset: str, argv: Optional[Sequence[str]] = None) -> List[str]:
                     kept[p] = np.asarray(out["json"]["recon_params"], dtype=np.float32).reshape(args.num_grasp, -1)
                 if want_volume:
                     vol_rows[p] = list(zip(*(out["json"][k] for k in ("volume_voxels", "penetration_volume", "penetration_depth"))))
+                if want_parts:
+                    part_rows[p] = (out["json"]["fingers_in_contact"], out["json"]["hand_contact_map"])
             del outs, out
         written = [paths[p] for p in sorted(paths)]                                # object order, whatever the grouping
         if args.diversity and kept:
@@ -827,6 +956,19 @@ def main(dataset: str, argv: Optional[Sequence[str]] = None) -> List[str]:
                 json.dump(stat, f)
             print(f"rank {rank}: penetration volume of {len(rows)} grasps at {args.volume_res} m: mean {stat['mean_volume_cm3']} cm^3, "
                   f"mean depth {stat['mean_depth_cm']} cm, contact ratio {stat['contact_ratio']}")
+        if want_parts:
+            # the run's figures over this rank's grasps in object order: integers, but for the mean (an exactly rounded sum)
+            fingers = [f for p in sorted(part_rows) for f in part_rows[p][0] if f is not None]
+            maps = [part_rows[p][1] for p in sorted(part_rows)]
+            stat = {"parts": _hand_parts(net, args.hand_parts).names, "threshold": args.part_threshold, "min_verts": args.part_min_verts,
+                    "grasps": len(fingers), "hand_contact_map": [int(sum(col)) for col in zip(*maps)],
+                    "mean_fingers_in_contact": math.fsum(fingers) / len(fingers) if fingers else None,
+                    "fingers_histogram": [sum(1 for f in fingers if f == k) for k in range(6)]}
+            name = "hand_contact.json" if world == 1 else f"hand_contact_rank{rank}.json"
+            with open(os.path.join(args.out_dir, name), "w") as f:
+                json.dump(stat, f)
+            print(f"rank {rank}: hand-side contact of {len(fingers)} grasps at {args.part_threshold} m: mean fingers in contact "
+                  f"{stat['mean_fingers_in_contact']}, histogram 0..5 {stat['fingers_histogram']}")
     else:
         for gi, (name, obj) in enumerate(objs[lo:hi], start=lo):                   # --rows_per_call 0: one call per object
             torch.cuda.synchronize(device)

@@ -779,6 +779,56 @@ def grasp_wrench(hand: Tensor, faces: Tensor, vf_off: Tensor, vf_face: Tensor, o
     return pen, n_in, n_ct, centre, sums, key
 
 
+GRASP_PARTS_TILE = 2048            # csrc/grasp_parts.hip: GP_TILE (the cloud's points per LDS tile)
+GRASP_PARTS_MAX_P = 32             # GP_MAX_P
+
+
+def grasp_parts(hand: Tensor, part_of_vertex: Tensor, n_parts: int, obj: Tensor, contact_threshold: float, want_verts: bool = False):
+    """Contact from the hand's side in one fused kernel (dvq_grasp_parts; the definition is in include/dvq.h): hand [B,V,3]
+    contiguous, ``part_of_vertex`` int32 [V] on the device (a label outside [0, n_parts) is "no part"), obj [B,N,3] with any strides
+    (read in place), ``contact_threshold`` a squared distance.  Returns ``(part_min [B,P] f32, part_count [B,P] i32, mask [B,W] i32,
+    status [B] i32, vert_dist, vert_idx)``: per part the smallest squared distance from one of its vertices to the cloud and the
+    number of its vertices closer than the threshold, a bit per vertex (W = (V + 31) // 32), status 1 for a row with a non-finite
+    coordinate (NaN / -1 / 0 there), and with ``want_verts`` the bits of ``nn_points(hand, obj)`` as f32 [B,V] and int32 [B,V]
+    (None otherwise)."""
+    for t, n in ((hand, "hand"), (part_of_vertex, "part_of_vertex"), (obj, "obj")):
+        if not isinstance(t, Tensor):
+            raise RuntimeError(f"grasp_parts: {n} must be a tensor")
+    _f32(hand, "hand")
+    if hand.dim() != 3 or hand.shape[2] != 3 or not hand.is_contiguous():
+        raise RuntimeError("grasp_parts: hand must be contiguous [B,V,3]")
+    po, ob, op, oc = _points(obj, "obj")
+    B, V, N = hand.shape[0], hand.shape[1], obj.shape[1]
+    if obj.shape[0] != B:
+        raise RuntimeError("grasp_parts: batch mismatch")
+    if N < 1 or not 1 <= V <= GRASP_SCORES_MAX_V:
+        raise RuntimeError(f"grasp_parts: need N >= 1 and 1 <= V <= {GRASP_SCORES_MAX_V} (got N={N} V={V})")
+    n_parts = int(n_parts)
+    if not 1 <= n_parts <= GRASP_PARTS_MAX_P:
+        raise RuntimeError(f"grasp_parts: need 1 <= n_parts <= {GRASP_PARTS_MAX_P} (got {n_parts})")
+    if part_of_vertex.dtype != torch.int32 or not part_of_vertex.is_contiguous() or tuple(part_of_vertex.shape) != (V,):
+        raise RuntimeError(f"grasp_parts: part_of_vertex must be contiguous int32 [{V}] (got {part_of_vertex.dtype} "
+                           f"{tuple(part_of_vertex.shape)})")
+    contact_threshold = float(contact_threshold)
+    if math.isnan(contact_threshold):
+        raise RuntimeError("grasp_parts: contact_threshold is NaN")
+    dev = _require_gpu(hand, obj, part_of_vertex)
+    lib = _lib.load()
+    W = (V + 31) // 32
+    part_min = torch.empty(B, n_parts, dtype=torch.float32, device=dev)
+    part_count = torch.empty(B, n_parts, dtype=torch.int32, device=dev)
+    mask = torch.empty(B, W, dtype=torch.int32, device=dev)
+    status = torch.empty(B, dtype=torch.int32, device=dev)
+    vert_dist = torch.empty(B, V, dtype=torch.float32, device=dev) if want_verts else None
+    vert_idx = torch.empty(B, V, dtype=torch.int32, device=dev) if want_verts else None
+    with torch.cuda.device(dev):
+        check(lib.dvq_grasp_parts(hand.data_ptr(), part_of_vertex.data_ptr(), V, n_parts, po, ob, op, oc, B, N, contact_threshold,
+                                  part_min.data_ptr(), part_count.data_ptr(), mask.data_ptr(), status.data_ptr(),
+                                  vert_dist.data_ptr() if want_verts else None, vert_idx.data_ptr() if want_verts else None,
+                                  _stream(dev)), "dvq_grasp_parts")
+    return part_min, part_count, mask, status, vert_dist, vert_idx
+
+
 GRASP_VOLUME_MAX_F = 8192          # csrc/grasp_volume.hip: GV_MAX_F
 GRASP_VOLUME_MAX_LOOPS = 64        # GV_MAX_L
 GRASP_VOLUME_MAX_PLANES = 8192     # GV_MAX_P: per object

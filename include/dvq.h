@@ -42,7 +42,7 @@ typedef enum {
 #define DVQ_ABI_VERSION 10
 /* Entry points added since 10 without touching a struct or a signature of it (a compatible extension: bindings of 10 keep
  * working, the version stays): dvq_pixelcnn_sample_ctl, dvq_grasp_scores, dvq_segment_topk, dvq_segment_diverse,
- * dvq_grasp_refine, dvq_segment_kmeans, dvq_grasp_wrench, dvq_grasp_volume. */
+ * dvq_grasp_refine, dvq_segment_kmeans, dvq_grasp_wrench, dvq_grasp_volume, dvq_grasp_parts. */
 int dvq_abi_version(void);
 const char* dvq_last_error(void);
 /* number of visible HIP devices, or -1; does not create a context */
@@ -450,6 +450,37 @@ int dvq_grasp_wrench(const float* hand /* [B,V,3] */, const int32_t* faces, cons
                      int64_t B, int N, float contact_threshold, float inv_length, float* penetration /* [B] */,
                      int32_t* n_interior /* [B] */, int32_t* n_contact /* [B] */, float* centre /* [B,3] */, float* sums /* [B,27] */,
                      float* key /* [B] */, dvq_stream_t stream);
+/* Hand-side contact of grasps: for every hand vertex its nearest object point, and from those which PARTS of the hand touch the
+ * object -- per part the smallest squared distance and the number of touching vertices, and a bit per vertex -- in ONE kernel, one
+ * workgroup of 256 threads per grasp.  The scores above look from the object's side (how many cloud points lie near the hand); this
+ * looks from the hand's, as the reference's finger-restricted contact terms do (utils/loss.py: Contact_loss, CMap_loss_hand and
+ * CMap_loss4 take get_NN(hand, obj); CMap_consistency_loss thresholds hard contact at 5 mm).  A PROXIMITY figure: no contact-force
+ * model, the threshold is the caller's and untuned, and its effect on real grasps is NOT MEASURED (no real checkpoint was available).
+ * Inputs: hand [B,V,3] contiguous fp32; part_of_vertex int32 [V]: the part of every vertex, a value outside [0, P) means "no part"
+ * (not an error); P, the number of parts; obj with strides in floats as dvq_grasp_scores takes it (a channel-first cloud is read in
+ * place); contact_threshold, a squared distance.
+ * Per grasp, when all 3 V hand coordinates and all 3 N cloud coordinates are finite (fp32, fma = the only fused operations):
+ *   1. per vertex v and point p: dx = hand.x - obj.x, dy, dz likewise; d(v,p) = fma(dz, dz, fma(dy, dy, dx * dx)).
+ *   2. d[v] = the minimum of d(v,p) over p; idx[v] = the lowest p that attains it: the bits of dvq_nn_points with the hand as source.
+ *   3. touch[v] = d[v] < contact_threshold.
+ *   4. part_min[q] = the minimum of d[v] over the vertices labelled q, +inf if there are none; part_count[q] = the number of
+ *      vertices labelled q with touch[v].
+ *   5. mask: bit (v & 31) of word (v >> 5) is touch[v], for every vertex, labelled or not; the unused high bits of the last word
+ *      are 0.  W = (V + 31) / 32 words per grasp.
+ *   6. status = 0; vert_dist[v] = d[v], vert_idx[v] = idx[v].
+ * A grasp with a non-finite coordinate (hand or cloud) has no figure: status = 1, part_min and vert_dist NaN, part_count and
+ * vert_idx -1, mask 0; other grasps are unaffected.
+ * Only minima, integer counts and bits are produced -- no float sum -- so nothing depends on a reduction order, and a grasp's outputs
+ * depend on neither B nor its row.
+ * Outputs: part_min fp32 [B,P]; part_count int32 [B,P]; mask int32 [B,W]; status int32 [B]; vert_dist fp32 [B,V] and vert_idx int32
+ * [B,V], each of which may be NULL (not written).
+ * B >= 0, N >= 1, 1 <= V <= 2048, 1 <= P <= 32, no null pointer but the two optional ones; anything else is DVQ_EINVAL, nothing
+ * launched. */
+int dvq_grasp_parts(const float* hand /* [B,V,3] */, const int32_t* part_of_vertex /* [V] */, int V, int P, const float* obj,
+                    int64_t obj_batch_stride, int64_t obj_point_stride, int64_t obj_coord_stride, int64_t B, int N,
+                    float contact_threshold, float* part_min /* [B,P] */, int32_t* part_count /* [B,P] */, int32_t* mask /* [B,W] */,
+                    int32_t* status /* [B] */, float* vert_dist /* [B,V] or NULL */, int32_t* vert_idx /* [B,V] or NULL */,
+                    dvq_stream_t stream);
 /* Penetration volume of grasps: the voxels, on a lattice of spacing h, whose centres lie both inside the (sealed) hand mesh and
  * inside the convex hull of the object -- an INTEGER per grasp, defined to the bit -- and the depth of the deepest hand vertex inside
  * the hull, in ONE kernel, one workgroup of 256 threads per grasp.  The counterpart of the reference's intersection_eval
