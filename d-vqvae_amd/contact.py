@@ -142,6 +142,85 @@ def refine_translation(topology, hand_xyz, obj_xyz, steps, push=1.0, pull=0.25, 
     return {"offset": offset, "iter": it, "penetration": pen, "n_interior": n_in, "n_contact": n_ct}
 
 
+def refine_rigid(topology, hand_xyz, obj_xyz, pivot, steps, push=1.0, pull=0.25, spin=1.0, min_contact=1, contact_threshold=0.02 ** 2):
+    """Rigid push-out from ONE fused kernel per call (ops.grasp_refine_rigid; the update rule is in include/dvq.h under
+    dvq_grasp_refine_rigid): ``refine_translation`` whose hand may also TURN about ``pivot`` [B,3] (the wrist: the root joint's world
+    position) -- a hand that sinks into the object with its fingertips while its palm stands off cannot be repaired by a shift.  Per
+    step the turn is ``spin`` times the least-squares small rotation (isotropic inertia about the pivot) towards the pull field left
+    after its mean, which the shift takes, is removed.  Returns ``refine_translation``'s dict plus ``quat`` [B,4] f32 (w, x, y, z):
+    the refined hand is ``apply_rigid(hand_xyz, pivot, offset, quat)``, and for a MANO hand the parameters are ``transl + offset``
+    and ``compose_orient(global_orient, quat)``.  ``spin = 0`` gives ``refine_translation``'s bits and the identity quaternion.
+
+    The defaults are a numpy prototype's and are untuned; the effect on real grasps is NOT measured (no real checkpoint).  Known
+    limits: the turn under-estimates when the contacts cluster far from the wrist; the pull term may turn the hand into the object;
+    the kept iterate is only "not worse under the proxy"."""
+    offset, quat, it, pen, n_in, n_ct = ops.grasp_refine_rigid(hand_xyz.contiguous(), topology.faces, topology.vf_off, topology.vf_face,
+                                                               obj_xyz, pivot.contiguous(), steps, push, pull, spin, min_contact,
+                                                               contact_threshold)
+    return {"offset": offset, "quat": quat, "iter": it, "penetration": pen, "n_interior": n_in, "n_contact": n_ct}
+
+
+def _quat_mul(a, b):
+    """Hamilton product of (w, x, y, z) tuples of tensors, elementwise."""
+    aw, ax, ay, az = a
+    bw, bx, by, bz = b
+    return (aw * bw - ax * bx - ay * by - az * bz, aw * bx + ax * bw + ay * bz - az * by,
+            aw * by - ax * bz + ay * bw + az * bx, aw * bz + ax * by - ay * bx + az * bw)
+
+
+def axis_angle_quat(axis_angle):
+    """Axis-angle [B,3] -> the unit quaternion [B,4] (w, x, y, z) of the same rotation, float64, elementwise per row; safe at 0."""
+    a = axis_angle.to(torch.float64)
+    x, y, z = a.unbind(-1)
+    th2 = x * x + y * y + z * z
+    th = torch.sqrt(th2)
+    small = th < 1e-6
+    k = torch.where(small, 0.5 - th2 / 48.0, torch.sin(0.5 * th) / torch.where(small, torch.ones_like(th), th))   # sin(th/2) / th
+    return torch.stack([torch.cos(0.5 * th), k * x, k * y, k * z], -1)
+
+
+def quat_axis_angle(quat):
+    """Quaternion [B,4] (w, x, y, z; any positive norm) -> the axis-angle [B,3] of its rotation, float64, elementwise per row: the sign
+    is chosen so that w >= 0, the angle is ``2 atan2(|v|, w)`` (at most pi), and the identity gives exact zeros."""
+    q = quat.to(torch.float64)
+    w, x, y, z = q.unbind(-1)
+    flip = w < 0
+    w, x, y, z = (torch.where(flip, -c, c) for c in (w, x, y, z))
+    n = torch.sqrt(x * x + y * y + z * z)
+    small = n < 1e-9 * w                                        # angle / |v| -> 2 / w as |v| -> 0
+    k = torch.where(small, 2.0 / torch.where(small, w, torch.ones_like(w)),
+                    2.0 * torch.atan2(n, w) / torch.where(small, torch.ones_like(n), n))
+    return torch.stack([k * x, k * y, k * z], -1)
+
+
+def compose_orient(global_orient, quat):
+    """The axis-angle [B,3] of ``Q * exp(global_orient)`` for ``quat`` [B,4] (w, x, y, z): the ``global_orient`` of a MANO hand turned by
+    ``Q`` about its root joint (``refine_rigid``'s ``quat`` with the root joint's world position as pivot).  Through quaternions, in
+    float64, elementwise per row (a row's result does not depend on the batch), returned in ``global_orient``'s dtype; a row whose
+    ``quat`` is exactly (1, 0, 0, 0) returns its ``global_orient`` untouched."""
+    qw, qx, qy, qz = quat.to(torch.float64).unbind(-1)
+    out = quat_axis_angle(torch.stack(_quat_mul((qw, qx, qy, qz), axis_angle_quat(global_orient).unbind(-1)), -1)).to(global_orient.dtype)
+    same = ((qw == 1) & (qx == 0) & (qy == 0) & (qz == 0)).unsqueeze(-1)
+    return torch.where(same, global_orient, out)
+
+
+def apply_rigid(hand_xyz, pivot, offset, quat):
+    """``R (v - c) + c + t`` for hand_xyz [B,V,3], pivot c [B,3], offset t [B,3] and quat [B,4] (w, x, y, z; normalised here): the hand
+    ``refine_rigid`` reports, in float64 inside and in ``hand_xyz``'s dtype outside, elementwise per row."""
+    q = quat.to(torch.float64)
+    w, x, y, z = q.unbind(-1)
+    n = torch.sqrt(w * w + x * x + y * y + z * z)
+    w, x, y, z = w / n, x / n, y / n, z / n
+    R = [[1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y)],
+         [2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x)],
+         [2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)]]
+    c, t = pivot.to(torch.float64).unsqueeze(1), offset.to(torch.float64).unsqueeze(1)
+    d = hand_xyz.to(torch.float64) - c
+    dx, dy, dz = d.unbind(-1)
+    rows = [R[i][0].unsqueeze(1) * dx + R[i][1].unsqueeze(1) * dy + R[i][2].unsqueeze(1) * dz for i in range(3)]
+    return (torch.stack(rows, -1) + c + t).to(hand_xyz.dtype)
+
+
 def grasp_stability(topology, hand_xyz, obj_xyz, length=0.1, contact_threshold=0.02 ** 2):
     """A force-closure proxy from ONE fused kernel (ops.grasp_wrench; the definition is in include/dvq.h under dvq_grasp_wrench):
     every object point within the contact threshold of the hand pushes with a unit force along the normal of its nearest hand vertex

@@ -131,6 +131,10 @@ def build_parser(dataset: str) -> argparse.ArgumentParser:
     p.add_argument("--refine_push", type=float, default=1.0, help="--refine_steps: step factor on the mean pull vector of the interior points")
     p.add_argument("--refine_pull", type=float, default=0.25,
                    help="--refine_steps: step factor on the mean pull vector of the points within 2 cm outside the hand")
+    p.add_argument("--refine_spin", type=float, default=0.0,
+                   help="--refine_steps: rigid push-out -- above 0 the hand may also turn about its wrist (the root joint), by this factor "
+                        "times the least-squares small rotation towards the pull field per step; global_orient is updated and the JSON "
+                        "gains \"refine_rotation\" (axis-angle); 0 = translation only; untuned, effect on real grasps not measured")
     return p
 
 
@@ -152,6 +156,10 @@ def parse_args(dataset: str, argv: Optional[Sequence[str]] = None) -> argparse.N
         p.error(f"--refine_steps must lie between 0 and {ops.GRASP_REFINE_MAX_STEPS} (got {args.refine_steps})")
     if not (0.0 <= args.refine_push < float("inf") and 0.0 <= args.refine_pull < float("inf")):
         p.error(f"--refine_push and --refine_pull must be finite and >= 0 (got {args.refine_push}, {args.refine_pull})")
+    if not 0.0 <= args.refine_spin < float("inf"):
+        p.error(f"--refine_spin must be finite and >= 0 (got {args.refine_spin})")
+    if args.refine_spin and not args.refine_steps:
+        p.error("--refine_spin needs --refine_steps (it turns the hand during the push-out)")
     if not 0.0 < args.torque_length < float("inf"):
         p.error(f"--torque_length must be finite and positive (got {args.torque_length})")
     if not args.max_penetration >= 0.0:
@@ -335,13 +343,16 @@ def _generate_call(net: GenNet, objs: Sequence[torch.Tensor], num_grasp: int, ro
                    min_contact: int = 1, diverse_pool: int = 0, diverse_space: str = "params", refine_steps: int = 0,
                    refine_push: float = 1.0, refine_pull: float = 0.25, diversity: int = 0, stability: bool = False,
                    max_penetration: float = float("inf"), torque_length: float = 0.1,
-                   volume: Optional[Dict[str, float]] = None, parts: Optional[Dict[str, object]] = None) -> List[Dict[str, object]]:
+                   volume: Optional[Dict[str, float]] = None, parts: Optional[Dict[str, object]] = None,
+                   refine_spin: float = 0.0) -> List[Dict[str, object]]:
     """One batched call: the ``num_grasp`` grasps of each of ``objs`` (all of one point count), row o * num_grasp + g = grasp g
     of object o.  Every step is row-independent and keyed per row, so each object's slice holds the bits of its own
     ``generate_for_object`` call.  With ``candidates`` = M the call generates M rows per object (exactly the grasps of a
     ``num_grasp = M`` call) and keeps each object's ``num_grasp`` best (_select_call).  With ``refine_steps`` every row of the call
     is first pushed out of its cloud (contact.refine_translation: one kernel), the offsets are added to the translations and MANO is
     posed again, so that everything after it -- scores, selection, the rows returned -- sees the hands of the parameters written.
+    With ``refine_spin`` > 0 the push-out is the rigid one (contact.refine_rigid about the root joint of the first posed pass): its
+    quaternion goes into ``global_orient`` (contact.compose_orient) and its axis-angle rides along as ``refine_rotation``.
     With ``diversity`` = K the kept parameters of every object go through one ``ops.segment_kmeans`` (one segment per object) and its
     counts and distances ride in the call's one device-to-host copy (_diversity_launch / _diversity_dicts).  With ``stability`` the
     scores come from ``contact.grasp_stability`` (one kernel in the place of ``contact.grasp_scores``) and its sums and key ride
@@ -379,8 +390,14 @@ def _generate_call(net: GenNet, objs: Sequence[torch.Tensor], num_grasp: int, ro
     if refine_steps:
         from . import contact
         topo = _hand_topology(net, final.vertices.shape[1], dev)
-        refined = contact.refine_translation(topo, final.vertices, batch[:, :3].transpose(1, 2), refine_steps, refine_push, refine_pull,
-                                             min_contact)
+        if refine_spin:                                                            # about the wrist: the root joint's world position
+            refined = contact.refine_rigid(topo, final.vertices, batch[:, :3].transpose(1, 2), final.joints[:, 0].contiguous(),
+                                           refine_steps, refine_push, refine_pull, refine_spin, min_contact)
+            params[:, 10:13] = contact.compose_orient(params[:, 10:13], refined["quat"])
+            refined["rotation"] = contact.quat_axis_angle(refined["quat"])         # float64 [B,3]
+        else:
+            refined = contact.refine_translation(topo, final.vertices, batch[:, :3].transpose(1, 2), refine_steps, refine_push,
+                                                 refine_pull, min_contact)
         params[:, 58:61] += refined["offset"]                                      # fp32; the hands below are those of these parameters
         final = net.rh_mano(betas=params[:, :10], global_orient=params[:, 10:13], hand_pose=params[:, 13:58],
                             transl=params[:, 58:61])
@@ -420,8 +437,8 @@ def _generate_call(net: GenNet, objs: Sequence[torch.Tensor], num_grasp: int, ro
             scores = contact.grasp_scores(topo, final.vertices, cloud_xyz)
         tensors = dict(scores)
         if refined is not None:
-            names = ["refine_offset", "refine_iter"] + names
-            tensors.update(refine_offset=refined["offset"], refine_iter=refined["iter"])
+            names = ["refine_offset", "refine_iter"] + (["refine_rotation"] if "rotation" in refined else []) + names
+            tensors.update({"refine_" + k: refined[k] for k in ("offset", "iter", "rotation") if k in refined})
         vol_t = [vol[k] for k in VOLUME_PIECES] if vol is not None else []
         host, *rest_h, err_h = _host_copy([params] + [tensors[k] for k in names] + vol_t + div + prt_t + [err])   # ONE device-to-host copy per call
         if int(err_h[0]) != 0:
@@ -488,14 +505,14 @@ def _generate_call(net: GenNet, objs: Sequence[torch.Tensor], num_grasp: int, ro
 
 
 def _host_copy(pieces: Sequence[torch.Tensor]) -> List[np.ndarray]:
-    """The given tensors (float32, int32 or int64, in any order and of any length) on the host through ONE device-to-host copy: the
+    """The given tensors (float32, float64, int32 or int64, in any order and of any length) on the host through ONE device-to-host copy: the
     pieces travel as bytes, and a piece that starts at an odd multiple of 4 bytes comes back as an unaligned view, which numpy reads
     correctly (tests/test_generate_combined.py)."""
     flat = [p.contiguous().reshape(-1).view(torch.uint8) for p in pieces]
     host = torch.cat(flat).cpu().numpy()
     out, lo = [], 0
     for p, f in zip(pieces, flat):
-        dt = {torch.float32: np.float32, torch.int32: np.int32, torch.int64: np.int64}[p.dtype]
+        dt = {torch.float32: np.float32, torch.float64: np.float64, torch.int32: np.int32, torch.int64: np.int64}[p.dtype]
         out.append(host[lo:lo + f.numel()].view(dt).reshape(tuple(p.shape)))
         lo += f.numel()
     return out
@@ -598,8 +615,8 @@ def _select_call(net: GenNet, batch: torch.Tensor, params: torch.Tensor, vertice
     then the ``keep`` most spread-out of them in greedy farthest-point order (``ops.segment_diverse`` over the parameters or the
     posed vertices, read in place); their pool positions and squared gaps ride along in the one copy.  ``refined``: the call's
     rows were pushed out before (contact.refine_translation's dict; ``params`` and ``vertices`` are the refined ones): the kept rows'
-    offsets and iterates ride along too.  ``diversity``: the k-means statistic of the kept parameters (_diversity_launch) rides along
-    as well.  ``stability``: the candidates' scores come from ``contact.grasp_stability`` (the one kernel in the place of
+    offsets and iterates (and, after contact.refine_rigid, the axis-angles under ``rotation``) ride along too.  ``diversity``: the
+    k-means statistic of the kept parameters (_diversity_launch) rides along as well.  ``stability``: the candidates' scores come from ``contact.grasp_stability`` (the one kernel in the place of
     ``contact.grasp_scores``); the kept rows' sums and keys ride along and become the four JSON fields of _stability_json.
     ``vol`` (_volume_launch over all candidates) with ``volume`` = its ``res`` and ``max_volume``: candidates whose voxel count exceeds
     ``contact.volume_limit`` join class 1 and those without a figure class 2 (integer comparisons on the device), whatever ranks the
@@ -636,7 +653,7 @@ def _select_call(net: GenNet, batch: torch.Tensor, params: torch.Tensor, vertice
     kept_p, kept_v = params.index_select(0, rows), vertices.index_select(0, rows)
     kept_s = {k: v.index_select(0, rows) for k, v in scores.items()}
     names = sorted(kept_s)
-    kept_r = [refined["offset"].index_select(0, rows), refined["iter"].index_select(0, rows)] if refined is not None else []
+    kept_r = [refined[k].index_select(0, rows) for k in ("offset", "iter", "rotation") if k in refined] if refined is not None else []
     div = _diversity_launch(kept_p, O, keep, diversity) if diversity else []
     kept_vol = [vol[k].index_select(0, rows) for k in VOLUME_PIECES[:3]] + [vol["err"]] if vol is not None else []
     kept_prt = [prt[k].index_select(0, rows) for k in PARTS_PIECES] if prt is not None else []
@@ -650,7 +667,7 @@ def _select_call(net: GenNet, batch: torch.Tensor, params: torch.Tensor, vertice
         s_host = dict(zip(names, host[2:2 + len(names)]))
         stab_lists = _stability_json(s_host["sums"], s_host["n_contact"], s_host["key"])
     if refined is not None:
-        off_list, it_list = (h.tolist() for h in host[2 + len(names):4 + len(names)])
+        off_list, it_list, *rot_list = (h.tolist() for h in host[2 + len(names):2 + len(names) + len(kept_r)])
     vol_lists = {}
     if vol is not None:
         vat = 2 + len(names) + len(kept_r)
@@ -689,6 +706,9 @@ def _select_call(net: GenNet, batch: torch.Tensor, params: torch.Tensor, vertice
         if refined is not None:
             extra["refine_offset"], extra["refine_iter"] = kept_r[0][lo:hi], kept_r[1][lo:hi]
             extra_json = {**extra_json, "refine_offset": off_list[lo:hi], "refine_iter": it_list[lo:hi]}
+            if rot_list:
+                extra["refine_rotation"] = kept_r[2][lo:hi]
+                extra_json["refine_rotation"] = rot_list[0][lo:hi]
         if diversity:
             extra["diversity"] = div_dicts[o]
             extra_json = {**extra_json, "diversity": div_dicts[o]}
@@ -716,7 +736,7 @@ def generate_for_objects(net: GenNet, objs: Sequence[torch.Tensor], num_grasp: i
                          max_penetration: float = float("inf"), torque_length: float = 0.1, volume: bool = False,
                          volume_res: float = 0.001, max_volume: float = float("inf"), parts: bool = False,
                          part_threshold: float = 0.005, part_min_verts: int = 1, min_fingers: int = 0, need_thumb: bool = False,
-                         hand_parts=None) -> List[Dict[str, object]]:
+                         hand_parts=None, refine_spin: float = 0.0) -> List[Dict[str, object]]:
     """``num_grasp`` grasps for each of ``objs`` ([4,N] tensors) in batched calls that mix objects (plan_calls): one dict per
     object, in the order given, equal to ``generate_for_object(net, objs[i], num_grasp, rotate,
     np.random.default_rng([seed, object_indices[i]]), seed=seed, object_index=object_indices[i], proxies=proxies)`` (and the same
@@ -749,6 +769,12 @@ def generate_for_objects(net: GenNet, objs: Sequence[torch.Tensor], num_grasp: i
     also gain ``penetration``, ``n_interior``, ``n_contact``: ``contact.grasp_scores`` of the refined hands.  Everything rides in the
     call's one device-to-host copy; needs a face list like best-of-M.  Parameters 0 .. 57 are those of the call without it.
     ``refine_steps = 0`` is the call without the keyword.  The constants are untuned and the effect on real grasps is not measured.
+
+    Rigid push-out (``refine_spin`` = S > 0 together with ``refine_steps``): the rows go through ``contact.refine_rigid`` instead, with
+    the root joint's world position of the first posed pass (``joints[:, 0]``) as the pivot, so the hand may also turn about its wrist:
+    besides the offset, ``params[:, 10:13]`` becomes ``contact.compose_orient(params[:, 10:13], quat)`` before MANO is posed again
+    (parameters 0 .. 9 and 13 .. 57 stay).  The dicts gain ``refine_rotation`` [num_grasp,3] (float64: the axis-angle of the turn) next
+    to ``refine_offset`` / ``refine_iter``, and so does ``json``.  ``refine_spin = 0`` is the call without the keyword.
 
     Diversity statistic (``diversity`` = K, 1 <= K <= min(``num_grasp``, 64)): after selection and push-out the kept [num_grasp,61]
     parameters of every object of a call go through ONE ``ops.segment_kmeans`` (one segment per object, K clusters, evenly spaced
@@ -841,6 +867,10 @@ def generate_for_objects(net: GenNet, objs: Sequence[torch.Tensor], num_grasp: i
     if diversity and not 0 < diversity <= min(num_grasp, ops.SEGMENT_KMEANS_MAX_K):
         raise RuntimeError(f"generate_for_objects: diversity must lie between 0 and min(num_grasp, {ops.SEGMENT_KMEANS_MAX_K}) "
                            f"(got {diversity} for {num_grasp} grasps)")
+    if not 0.0 <= float(refine_spin) < float("inf"):
+        raise RuntimeError(f"generate_for_objects: refine_spin must be finite and >= 0 (got {refine_spin})")
+    if refine_spin and not refine_steps:
+        raise RuntimeError("generate_for_objects: refine_spin needs refine_steps")
     if refine_steps:
         if not 0 < refine_steps <= ops.GRASP_REFINE_MAX_STEPS:
             raise RuntimeError(f"generate_for_objects: refine_steps must lie between 0 and {ops.GRASP_REFINE_MAX_STEPS} (got {refine_steps})")
@@ -851,7 +881,8 @@ def generate_for_objects(net: GenNet, objs: Sequence[torch.Tensor], num_grasp: i
     for call in plan_calls([o.shape[1] for o in objs], candidates or num_grasp, rows_per_call):
         res = _generate_call(net, [objs[p] for p in call], num_grasp, rotate, seed, [object_indices[p] for p in call], proxies,
                              temperature, top_k, log_prob, candidates, select_by, min_contact, diverse_pool, diverse_space, refine_steps,
-                             refine_push, refine_pull, diversity, stability, max_penetration, torque_length, vol_args, parts_args)
+                             refine_push, refine_pull, diversity, stability, max_penetration, torque_length, vol_args, parts_args,
+                             float(refine_spin))
         for p, r in zip(call, res):
             out[p] = r
     return out
@@ -892,6 +923,8 @@ def main(dataset: str, argv: Optional[Sequence[str]] = None) -> List[str]:
         if args.refine_steps:
             selection.update(refine_steps=args.refine_steps, refine_push=args.refine_push, refine_pull=args.refine_pull,
                              min_contact=args.min_contact)
+            if args.refine_spin:
+                selection.update(refine_spin=args.refine_spin)
         if args.diversity:
             selection.update(diversity=args.diversity)
         if args.stability or (args.candidates and args.select_by == "stability"):

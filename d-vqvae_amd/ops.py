@@ -930,6 +930,41 @@ def grasp_refine(hand: Tensor, faces: Tensor, vf_off: Tensor, vf_face: Tensor, o
     return offset, it, pen, n_in, n_ct
 
 
+def grasp_refine_rigid(hand: Tensor, faces: Tensor, vf_off: Tensor, vf_face: Tensor, obj: Tensor, pivot: Tensor, steps: int,
+                       push: float = 1.0, pull: float = 0.25, spin: float = 1.0, min_contact: int = 1,
+                       contact_threshold: float = 0.02 ** 2):
+    """Rigid push-out in one fused kernel (dvq_grasp_refine_rigid; the definition is in include/dvq.h): ``grasp_refine`` whose state
+    is a translation and a unit quaternion about ``pivot`` [B,3] (fp32, contiguous: the wrist of every hand).  Returns ``(offset
+    [B,3] f32, quat [B,4] f32 (w, x, y, z), iter [B] i32, penetration [B] f32, n_interior [B] i32, n_contact [B] i32)`` of each
+    grasp's best iterate: the refined hand is ``R(quat) (v - pivot) + pivot + offset``.  ``spin = 0`` gives ``grasp_refine``'s bits
+    and the identity quaternion.  Other arguments as ``grasp_refine``."""
+    po, ob, op, oc, B, V, N = _hand_cloud_args("grasp_refine_rigid", hand, faces, vf_off, vf_face, obj)
+    if not isinstance(pivot, Tensor):
+        raise RuntimeError("grasp_refine_rigid: pivot must be a tensor")
+    _f32(pivot, "pivot")
+    if tuple(pivot.shape) != (B, 3) or not pivot.is_contiguous():
+        raise RuntimeError(f"grasp_refine_rigid: pivot must be contiguous [B,3] = [{B},3] (got {tuple(pivot.shape)})")
+    steps, min_contact, push, pull, spin = int(steps), int(min_contact), float(push), float(pull), float(spin)
+    if not 0 <= steps <= GRASP_REFINE_MAX_STEPS:
+        raise RuntimeError(f"grasp_refine_rigid: need 0 <= steps <= {GRASP_REFINE_MAX_STEPS} (got {steps})")
+    if not (0.0 <= push < float("inf") and 0.0 <= pull < float("inf") and 0.0 <= spin < float("inf")):
+        raise RuntimeError(f"grasp_refine_rigid: push, pull and spin must be finite and >= 0 (got {push}, {pull}, {spin})")
+    dev = _require_gpu(hand, obj, faces, vf_off, vf_face, pivot)
+    lib = _lib.load()
+    offset = torch.empty(B, 3, dtype=torch.float32, device=dev)
+    quat = torch.empty(B, 4, dtype=torch.float32, device=dev)
+    it = torch.empty(B, dtype=torch.int32, device=dev)
+    pen = torch.empty(B, dtype=torch.float32, device=dev)
+    n_in = torch.empty(B, dtype=torch.int32, device=dev)
+    n_ct = torch.empty(B, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        check(lib.dvq_grasp_refine_rigid(hand.data_ptr(), faces.data_ptr(), vf_off.data_ptr(), vf_face.data_ptr(), V, po, ob, op, oc, B,
+                                         N, pivot.data_ptr(), float(contact_threshold), steps, push, pull, spin, min_contact,
+                                         offset.data_ptr(), quat.data_ptr(), it.data_ptr(), pen.data_ptr(), n_in.data_ptr(),
+                                         n_ct.data_ptr(), _stream(dev)), "dvq_grasp_refine_rigid")
+    return offset, quat, it, pen, n_in, n_ct
+
+
 def segment_topk(cls: Tensor, key: Tensor, n_objects: int, n_candidates: int, keep: int) -> Tensor:
     """cls int32 [O*M], key f32 [O*M] (candidate c of object o at o * M + c) -> int64 [O,keep]: each object's ``keep`` best
     candidate indices, best first, by (cls, key, index) with NaN keys last in their class and -0.0 == +0.0 (dvq_segment_topk)."""

@@ -42,7 +42,7 @@ typedef enum {
 #define DVQ_ABI_VERSION 10
 /* Entry points added since 10 without touching a struct or a signature of it (a compatible extension: bindings of 10 keep
  * working, the version stays): dvq_pixelcnn_sample_ctl, dvq_grasp_scores, dvq_segment_topk, dvq_segment_diverse,
- * dvq_grasp_refine, dvq_segment_kmeans, dvq_grasp_wrench, dvq_grasp_volume, dvq_grasp_parts. */
+ * dvq_grasp_refine, dvq_segment_kmeans, dvq_grasp_wrench, dvq_grasp_volume, dvq_grasp_parts, dvq_grasp_refine_rigid. */
 int dvq_abi_version(void);
 const char* dvq_last_error(void);
 /* number of visible HIP devices, or -1; does not create a context */
@@ -417,6 +417,66 @@ int dvq_grasp_refine(const float* hand /* [B,V,3] */, const int32_t* faces, cons
                      int64_t B, int N, float contact_threshold, int steps, float push, float pull, int min_contact,
                      float* offset /* [B,3] */, int32_t* iter /* [B] */, float* penetration /* [B] */, int32_t* n_interior /* [B] */,
                      int32_t* n_contact /* [B] */, dvq_stream_t stream);
+/* Rigid push-out of grasps: dvq_grasp_refine with the other half of a rigid motion -- at most `steps` steps of descent on the same
+ * scores with respect to the hand's rigid translation AND a rotation about a pivot (the wrist), in ONE kernel, one workgroup of 256
+ * threads per grasp; the best iterate is reported.  A hand whose fingertips sink into the object while its palm stands off cannot be
+ * repaired by a shift; it needs a small turn.  No MANO backward pass is involved: a rotation of the hand about a pivot turns its
+ * vertex normals with it, so in the hand's own frame neither the hand nor its normals change, only the object points move; and the
+ * MANO layer applies global_orient about the root joint and adds transl afterwards, so a turn Q about the root joint's world position
+ * is exactly global_orient <- log(Q * exp(global_orient)), and the shift still goes to transl.  The effect on real grasps is NOT
+ * MEASURED (no real checkpoint was available); the update rule's constants are a prototype's, untuned.
+ * Inputs as dvq_grasp_refine plus pivot [B,3] fp32 contiguous, the pivot c of every grasp (the wrist's world position), and spin.
+ * Everything this entry point adds to dvq_grasp_refine is single fp32 operations, each rounded on its own (no fma), IEEE division and
+ * square root, no library function; expressions below are evaluated left to right as parenthesised.  The shared per-point part
+ * (step 2) keeps the fmas dvq_grasp_scores documents.  "The canonical sum" is that of dvq_grasp_scores: 256 strided partial sums from
+ * +0.0f in ascending p, then the tree s = 128 .. 1.
+ * State per grasp: t = (+0, +0, +0), q = (w, x, y, z) = (1, 0, 0, 0), turned = false.  R = R(q), row-major R[i][j], from the products
+ *   xx = x*x, yy = y*y, zz = z*z, xy = x*y, xz = x*z, yz = y*z, wx = w*x, wy = w*y, wz = w*z:
+ *   R[0] = (1 - 2*(yy + zz),  2*(xy - wz),      2*(xz + wy)    )
+ *   R[1] = (2*(xy + wz),      1 - 2*(xx + zz),  2*(yz - wx)    )
+ *   R[2] = (2*(xz - wy),      2*(yz + wx),      1 - 2*(xx + yy))
+ * The world hand of the state is R (v - c) + c + t.  For k = 0 .. steps:
+ *   1. u_p = obj_p - t per component.  If !turned: o'_p = u_p (at k = 0, and always with spin = 0: dvq_grasp_refine's step 1 bit for
+ *      bit).  Otherwise w = u_p - c per component and o'_p[i] = ((R[0][i]*w.x + R[1][i]*w.y) + R[2][i]*w.z) + c[i]: R^T w + c.
+ *   2. normals (once, of the hand as given), d_p, j_p, inside_p, term_p and near_p exactly as dvq_grasp_refine defines them, on o';
+ *      g_p = o'_p - hand[j_p] and r_p = hand[j_p] - c per component.
+ *   3. 21 canonical sums and three integer counts: pen = sum of term_p; and for each of the two sets (S = inside_p, S = near_p), every
+ *      term masked as (S ? x : +0.0f):  G[c] = sum of g[c];  A[c] = sum of r[c];  X = sum of cross(r, g) with components
+ *      (r.y*g.z - r.z*g.y, r.z*g.x - r.x*g.z, r.x*g.y - r.y*g.x);  Q = sum of ((r.x*r.x + r.y*r.y) + r.z*r.z);
+ *      n_in = #inside, n_ct = #(d < contact_threshold), n_nr = #near.
+ *   4. the key (cls, pen) and the rule for the best iterate are dvq_grasp_refine's step 5: the earliest iterate among equal keys.
+ *   5. if k == steps or pen is NaN, stop.  Otherwise
+ *      st[c] : dvq_grasp_refine's step 6 on G_in, G_nr (the step of the translation, in the hand's frame);
+ *      om[c] = +0.0f.  If spin > 0 (with spin = 0 nothing of the turn is evaluated and om stays +0):
+ *        if n_in > 0 and Q_in > 0:  m[c] = G_in[c] / (float)n_in (the quotients of st);  tau = X_in - cross(A_in, m), i.e.
+ *          tau.x = X_in.x - (A_in.y*m.z - A_in.z*m.y) and cyclic;  om[c] = om[c] + push * (tau[c] / Q_in);
+ *        if n_nr > 0 and Q_nr > 0:  the same on the near set with pull;
+ *        om[c] = spin * om[c].
+ *      If all six of st[c] and om[c] are == 0, stop (no later iterate could become the best).
+ *      t[i] = t[i] + (turned ? ((R[i][0]*st.x + R[i][1]*st.y) + R[i][2]*st.z) : st[i]), with R and turned as they stand.
+ *      If some om[c] != 0:  h = 0.5f * om;  p = q (x) (1, h), the Hamilton product with the increment on the right (the turn is
+ *        expressed in the hand's frame):
+ *          p.w = ((q.w - q.x*h.x) - q.y*h.y) - q.z*h.z        p.x = ((q.x + q.w*h.x) + q.y*h.z) - q.z*h.y
+ *          p.y = ((q.y + q.w*h.y) - q.x*h.z) + q.z*h.x        p.z = ((q.z + q.w*h.z) + q.x*h.y) - q.y*h.x
+ *        n2 = ((p.w*p.w + p.x*p.x) + p.y*p.y) + p.z*p.z;  q = p * (1.0f / sqrtf(n2)) per component;  turned = true;  R = R(q).
+ * tau is the torque of the pull field about the pivot after its mean is removed (a field that a shift alone satisfies turns nothing);
+ * tau / Q is the least-squares small rotation under an isotropic inertia, which under-turns when the contacts cluster far from the
+ * wrist; the normalised (1, h) bounds a step's angle below pi without trigonometry.  The pull term may turn the hand INTO the object,
+ * as it may shift it: the kept iterate is only "not worse under the proxy".
+ * Outputs: offset [B,3] = the best iterate's t; quat [B,4] = its q (w, x, y, z); iter [B] = its k; penetration / n_interior /
+ * n_contact [B] = its pen, n_in, n_ct.  The refined hand is R(quat) (v - c) + c + offset.  With spin = 0 every output but quat is the
+ * bits of dvq_grasp_refine and quat = (1, 0, 0, 0); with steps = 0 the three scores are the bits of dvq_grasp_scores.  A grasp's
+ * result does not depend on B or on its row.  Coordinates that are not finite behave as in dvq_grasp_refine: a NaN in the hand or the
+ * cloud makes iterate 0 of class 2 (NaN pen), the only iterate; an Inf in the cloud, or a pivot that is not finite, where it enters a
+ * sum makes the step not finite, the next iterate is of class 2, ends the loop and never replaces the iterate kept.
+ * B >= 0, N >= 1, 1 <= V <= 2048, 0 <= steps <= 64, push, pull and spin finite and >= 0, no null pointer; anything else is
+ * DVQ_EINVAL, nothing launched. */
+int dvq_grasp_refine_rigid(const float* hand /* [B,V,3] */, const int32_t* faces, const int32_t* vf_off, const int32_t* vf_face, int V,
+                           const float* obj, int64_t obj_batch_stride, int64_t obj_point_stride, int64_t obj_coord_stride,
+                           int64_t B, int N, const float* pivot /* [B,3] */, float contact_threshold, int steps, float push, float pull,
+                           float spin, int min_contact, float* offset /* [B,3] */, float* quat /* [B,4] */, int32_t* iter /* [B] */,
+                           float* penetration /* [B] */, int32_t* n_interior /* [B] */, int32_t* n_contact /* [B] */,
+                           dvq_stream_t stream);
 /* Grasp stability proxy: the contact-wrench sums of a grasp and a ranking key from them, with the three scores of dvq_grasp_scores,
  * in ONE kernel, one workgroup of 256 threads per grasp.  New here: the reference judges whether the object stays in the hand by a
  * physics run (pybullet + V-HACD, out of scope); this is the usual cheap stand-in, a force-closure figure over the contact wrenches:
