@@ -179,9 +179,24 @@ def axis_angle_quat(axis_angle):
     return torch.stack([torch.cos(0.5 * th), k * x, k * y, k * z], -1)
 
 
+def _atan2_rowwise(y, x):
+    """``torch.atan2`` whose result for an element does not depend on the tensor around it.  On the device every element is one
+    thread's.  On the host torch's vectorised loop and its scalar tail round differently (seen: the last bit of 2 rows in 24), so host
+    tensors go through numpy, whose loop treats every element alike."""
+    if y.is_cuda:
+        return torch.atan2(y, x)
+    return torch.from_numpy(np.arctan2(y.detach().numpy(), x.detach().numpy()))
+
+
 def quat_axis_angle(quat):
     """Quaternion [B,4] (w, x, y, z; any positive norm) -> the axis-angle [B,3] of its rotation, float64, elementwise per row: the sign
     is chosen so that w >= 0, the angle is ``2 atan2(|v|, w)`` (at most pi), and the identity gives exact zeros."""
+    return _quat_axis_angle(quat, torch.atan2)
+
+
+def _quat_axis_angle(quat, _atan2):
+    """``quat_axis_angle`` with the arc tangent given: ``torch.atan2``, or ``_atan2_rowwise`` where a row's bits must not depend on its
+    batch on the host either (``compose_finger_pose``)."""
     q = quat.to(torch.float64)
     w, x, y, z = q.unbind(-1)
     flip = w < 0
@@ -189,7 +204,7 @@ def quat_axis_angle(quat):
     n = torch.sqrt(x * x + y * y + z * z)
     small = n < 1e-9 * w                                        # angle / |v| -> 2 / w as |v| -> 0
     k = torch.where(small, 2.0 / torch.where(small, w, torch.ones_like(w)),
-                    2.0 * torch.atan2(n, w) / torch.where(small, torch.ones_like(n), n))
+                    2.0 * _atan2(n, w) / torch.where(small, torch.ones_like(n), n))
     return torch.stack([k * x, k * y, k * z], -1)
 
 
@@ -219,6 +234,158 @@ def apply_rigid(hand_xyz, pivot, offset, quat):
     dx, dy, dz = d.unbind(-1)
     rows = [R[i][0].unsqueeze(1) * dx + R[i][1].unsqueeze(1) * dy + R[i][2].unsqueeze(1) * dz for i in range(3)]
     return (torch.stack(rows, -1) + c + t).to(hand_xyz.dtype)
+
+
+class FingerRig:
+    """What the articulated push-out knows of the hand's fingers: ``vert_part`` int32 [V] (the finger of every vertex, -1 = none),
+    ``vert_w`` float32 [V] (how far the vertex follows its finger's turn, in [0, 1]) and ``joints`` (per finger the index of its
+    knuckle among the layer's joints: the pivot of the finger's turn).  Device copies are made once per device (``on``)."""
+
+    def __init__(self, vert_part, vert_w, joints, device=None):
+        part = np.asarray(vert_part.detach().cpu() if torch.is_tensor(vert_part) else vert_part)
+        w = np.asarray(vert_w.detach().cpu() if torch.is_tensor(vert_w) else vert_w, dtype=np.float64)
+        self.joints = [int(j) for j in joints]
+        if not 1 <= len(self.joints) <= ops.GRASP_FINGERS_MAX_P:
+            raise RuntimeError(f"FingerRig: between 1 and {ops.GRASP_FINGERS_MAX_P} fingers (got {len(self.joints)})")
+        if part.ndim != 1 or part.size < 1 or part.dtype.kind not in "iu" or w.shape != part.shape:
+            raise RuntimeError("FingerRig: vert_part must be a non-empty 1-D integer array and vert_w one weight per vertex")
+        part = part.astype(np.int64)
+        if part.min() < -1 or part.max() >= len(self.joints):
+            raise RuntimeError(f"FingerRig: vert_part must lie in [-1, {len(self.joints)}) (got {int(part.min())} .. {int(part.max())})")
+        if not np.all((w >= 0.0) & (w <= 1.0)):
+            raise RuntimeError("FingerRig: vert_w must lie in [0, 1]")
+        self.vert_part, self.vert_w = part.astype(np.int32), w.astype(np.float32)
+        self.n_verts, self.n_fingers = int(part.size), len(self.joints)
+        self._dev = {}
+        if device is not None:
+            self.on(torch.device(device))
+
+    def on(self, device):
+        """(vert_part int32 [V], vert_w f32 [V]) on ``device`` (uploaded once per device)."""
+        key = str(device)
+        if key not in self._dev:
+            self._dev[key] = (torch.from_numpy(self.vert_part).to(device), torch.from_numpy(self.vert_w).to(device))
+        return self._dev[key]
+
+    @classmethod
+    def from_mano(cls, layer, device=None):
+        """The rig of a MANO layer (``mano.ManoLayer``), from its kinematic tree and skinning weights: a finger is a child of the root
+        joint with all its descendants, in joint order; a vertex belongs to the chain with the largest sum of skinning weights (the
+        lowest chain on ties), that sum (float64 over the weights as loaded, rounded once to fp32 and clipped to [0, 1]) is its
+        weight, and a vertex whose sum is 0 belongs to no finger."""
+        packed = layer._packed
+        parents = [int(p) for p in packed.parents]
+        weights = np.asarray(packed.skin_weights, np.float64)                                   # [V,J], as loaded (not the fp32 copy)
+        knuckles = [j for j, p in enumerate(parents) if p == 0]
+        chain_of = [-1] * len(parents)
+        for j in range(1, len(parents)):                          # parents precede their children in the tree
+            chain_of[j] = knuckles.index(j) if parents[j] == 0 else chain_of[parents[j]]
+        sums = np.stack([weights[:, [j for j, c in enumerate(chain_of) if c == f]].sum(axis=1) for f in range(len(knuckles))], 1)
+        part = np.argmax(sums, axis=1)                            # the first of equal sums
+        w = np.clip(sums[np.arange(len(part)), part].astype(np.float32), 0.0, 1.0)
+        return cls(np.where(w > 0, part, -1), w, knuckles, device)
+
+
+def refine_fingers(topology, rig, hand_xyz, obj_xyz, pivot, knuckles, steps, push=1.0, pull=0.25, spin=1.0, curl=1.0, max_curl=0.35,
+                   min_contact=1, contact_threshold=0.02 ** 2):
+    """Articulated push-out from ONE fused kernel per call (ops.grasp_refine_fingers; the update rule is in include/dvq.h under
+    dvq_grasp_refine_fingers): ``refine_rigid`` whose fingers may also CURL, each by one rotation about its knuckle (``knuckles``
+    [B,P,3]: the world positions of ``rig.joints`` in the hand as given) -- one fingertip buried in the object while the others sit
+    well cannot be repaired by a rigid motion.  The kernel searches with a blend model of the hand (``apply_fingers``), not with MANO;
+    per step a finger's turn is ``curl`` times the least-squares small rotation about its knuckle towards the pulls at its own
+    vertices, and no finger turns further than ``max_curl`` radians from the hand as given.  Returns ``refine_rigid``'s dict plus
+    ``finger_quat`` [B,P,4] f32 (w, x, y, z, in the frame of the hand as given) and ``penetration0`` / ``n_interior0`` /
+    ``n_contact0`` [B], the scores of the hand as given (the bits of ``grasp_scores``).  The hand the kernel believed in is
+    ``apply_rigid(apply_fingers(hand_xyz, rig, knuckles, finger_quat), pivot, offset, quat)``; for a MANO hand the pose parameters are
+    ``compose_finger_pose(...)``.  ``curl = 0`` gives ``refine_rigid``'s bits and identity finger quaternions.
+
+    The defaults are untuned; the effect on real grasps is NOT measured (no real checkpoint).  Known limits: the blend model differs
+    from the re-posed MANO hand by up to 3.2 mm at 0.35 rad, so the kept iterate is the best only under that model --
+    compare the re-posed hand's scores with ``penetration0`` / ``n_contact0`` before keeping it; no joint limits beyond ``max_curl``;
+    no finger-to-finger collision test; shift, turn and curl answer the same contacts, so a step may overshoot."""
+    if not torch.is_tensor(hand_xyz) or hand_xyz.dim() != 3 or hand_xyz.shape[1] != rig.n_verts:
+        raise RuntimeError(f"refine_fingers: the rig has {rig.n_verts} vertices, the hand "
+                           f"{tuple(hand_xyz.shape) if torch.is_tensor(hand_xyz) else type(hand_xyz)}")
+    part, w = rig.on(hand_xyz.device)
+    names = ("offset", "quat", "finger_quat", "iter", "penetration", "n_interior", "n_contact", "penetration0", "n_interior0", "n_contact0")
+    out = ops.grasp_refine_fingers(hand_xyz.contiguous(), topology.faces, topology.vf_off, topology.vf_face, part, w, rig.n_fingers,
+                                   obj_xyz, pivot.contiguous(), knuckles.contiguous(), steps, push, pull, spin, curl, max_curl,
+                                   min_contact, contact_threshold)
+    return dict(zip(names, out))
+
+
+def _quat_rows(quat):
+    """(w, x, y, z) of quaternions [..., 4], float64, normalised."""
+    w, x, y, z = quat.to(torch.float64).unbind(-1)
+    n = torch.sqrt(w * w + x * x + y * y + z * z)
+    return w / n, x / n, y / n, z / n
+
+
+def apply_fingers(hand_xyz, rig, knuckles, finger_quat):
+    """The blend model of ``refine_fingers``: a vertex v of finger f with weight w becomes ``v + w (R_f (v - c_f) + c_f - v)`` for
+    hand_xyz [B,V,3], knuckles c [B,P,3] and finger_quat [B,P,4] (w, x, y, z; normalised here); a vertex of no finger, or of a finger
+    whose quaternion is exactly (1, 0, 0, 0), keeps its bits.  Float64 inside, ``hand_xyz``'s dtype outside, elementwise per row.  It
+    states what the kernel believed, NOT the MANO hand of the composed pose (DESIGN.md 3 has the difference); ``apply_rigid`` on top
+    gives the world hand."""
+    part, wv = rig.on(hand_xyz.device)
+    part = part.to(torch.int64)
+    v = hand_xyz.to(torch.float64)
+    qw, qx, qy, qz = finger_quat.to(torch.float64).unbind(-1)                       # [B,P]
+    same = (qw == 1) & (qx == 0) & (qy == 0) & (qz == 0)
+    w, x, y, z = _quat_rows(finger_quat)
+    R = [[1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y)],
+         [2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x)],
+         [2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)]]
+    idx = part.clamp(min=0)                                                         # [V]: finger per vertex (0 where none; masked below)
+    c = knuckles.to(torch.float64).index_select(1, idx)                             # [B,V,3]
+    d = v - c
+    dx, dy, dz = d.unbind(-1)
+    rows = [R[i][0].index_select(1, idx) * dx + R[i][1].index_select(1, idx) * dy + R[i][2].index_select(1, idx) * dz for i in range(3)]
+    rot = torch.stack(rows, -1) + c
+    out = v + wv.to(torch.float64).view(1, -1, 1) * (rot - v)
+    keep = (part < 0).view(1, -1) | same.index_select(1, idx)                       # [B,V]
+    return torch.where(keep.unsqueeze(-1), hand_xyz, out.to(hand_xyz.dtype))
+
+
+def compose_finger_pose(layer, global_orient, hand_pose, finger_quat, rig):
+    """The ``hand_pose`` [B,45] (PCA coefficients) of a MANO hand whose finger f has been turned by ``finger_quat[:, f]`` (w, x, y, z;
+    expressed in the frame of the hand as generated) about its knuckle.  The knuckles are children of the root joint, so the turn D_f
+    is exactly ``R_loc' = R0^T D_f R0 R_loc`` on the knuckle's local rotation, with ``R0 = exp(global_orient)`` -- ``global_orient``
+    [B,3] is the one AS GENERATED, before ``compose_orient``.  Through quaternions, in float64: the full pose is ``hand_pose @ comps +
+    mean``, the knuckles' axis-angles are replaced, the mean is subtracted and the result is multiplied by the inverse of ``comps``
+    (taken once, in float64, on the host: the components are invertible but not orthonormal).  Both 45-term products are summed term
+    by term in a fixed elementwise order, so a row's result does not depend on its batch.  Returned in ``hand_pose``'s dtype; a row
+    whose finger quaternions are all exactly (1, 0, 0, 0) returns its ``hand_pose`` untouched.  No MANO backward pass is involved."""
+    packed = layer._packed
+    cache = getattr(packed, "_finger_pose_cache", None)
+    if cache is None:
+        comps = packed.tensors["comps"].detach().cpu().numpy().astype(np.float64)
+        mean = packed.tensors["pose_mean"].detach().cpu().numpy().astype(np.float64)[3:]
+        cache = {"host": (comps, np.linalg.inv(comps), mean)}
+        packed._finger_pose_cache = cache
+    key = str(hand_pose.device)
+    if key not in cache:
+        cache[key] = tuple(torch.from_numpy(a).to(hand_pose.device) for a in cache["host"])
+    comps, inv, mean = cache[key]
+    hp = hand_pose.to(torch.float64)
+    acc = hp[:, 0:1] * comps[0]
+    for k in range(1, 45):
+        acc = acc + hp[:, k:k + 1] * comps[k]
+    full = (acc + mean).clone()
+    q0 = axis_angle_quat(global_orient).unbind(-1)
+    q0c = (q0[0], -q0[1], -q0[2], -q0[3])
+    fq = finger_quat.to(torch.float64)
+    for f, j in enumerate(rig.joints):
+        lo = 3 * (j - 1)
+        loc = axis_angle_quat(full[:, lo:lo + 3]).unbind(-1)
+        new = _quat_mul(_quat_mul(_quat_mul(q0c, _quat_rows(fq[:, f])), q0), loc)
+        full[:, lo:lo + 3] = _quat_axis_angle(torch.stack(new, -1), _atan2_rowwise)
+    z = full - mean
+    acc = z[:, 0:1] * inv[0]
+    for k in range(1, 45):
+        acc = acc + z[:, k:k + 1] * inv[k]
+    same = ((fq[..., 0] == 1) & (fq[..., 1] == 0) & (fq[..., 2] == 0) & (fq[..., 3] == 0)).all(dim=1, keepdim=True)
+    return torch.where(same, hand_pose, acc.to(hand_pose.dtype))
 
 
 def grasp_stability(topology, hand_xyz, obj_xyz, length=0.1, contact_threshold=0.02 ** 2):

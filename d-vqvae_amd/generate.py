@@ -14,6 +14,7 @@ import json
 import math
 import os
 import time
+import types
 from typing import Dict, List, Optional, Sequence
 
 import numpy as np
@@ -135,6 +136,14 @@ def build_parser(dataset: str) -> argparse.ArgumentParser:
                    help="--refine_steps: rigid push-out -- above 0 the hand may also turn about its wrist (the root joint), by this factor "
                         "times the least-squares small rotation towards the pull field per step; global_orient is updated and the JSON "
                         "gains \"refine_rotation\" (axis-angle); 0 = translation only; untuned, effect on real grasps not measured")
+    p.add_argument("--refine_curl", type=float, default=0.0,
+                   help="--refine_steps: articulated push-out -- above 0 every finger may also curl about its knuckle, by this factor times "
+                        "the least-squares small rotation towards the pulls at its own vertices per step; hand_pose is updated, a row "
+                        "whose re-posed hand scores worse than the hand as generated is reverted, and the JSON gains \"refine_curl\" "
+                        "(axis-angles per finger) and \"refine_reverted\"; works with or without --refine_spin; 0 = no curl; untuned, "
+                        "effect on real grasps not measured")
+    p.add_argument("--refine_max_curl", type=float, default=0.35,
+                   help="--refine_curl: the largest angle (radians) a finger may turn from the hand as generated; untuned")
     return p
 
 
@@ -160,6 +169,12 @@ def parse_args(dataset: str, argv: Optional[Sequence[str]] = None) -> argparse.N
         p.error(f"--refine_spin must be finite and >= 0 (got {args.refine_spin})")
     if args.refine_spin and not args.refine_steps:
         p.error("--refine_spin needs --refine_steps (it turns the hand during the push-out)")
+    if not 0.0 <= args.refine_curl < float("inf"):
+        p.error(f"--refine_curl must be finite and >= 0 (got {args.refine_curl})")
+    if args.refine_curl and not args.refine_steps:
+        p.error("--refine_curl needs --refine_steps (it curls the fingers during the push-out)")
+    if not 0.0 < args.refine_max_curl <= math.pi:
+        p.error(f"--refine_max_curl must lie in (0, pi] (got {args.refine_max_curl})")
     if not 0.0 < args.torque_length < float("inf"):
         p.error(f"--torque_length must be finite and positive (got {args.torque_length})")
     if not args.max_penetration >= 0.0:
@@ -309,6 +324,61 @@ def _hand_topology(net: GenNet, n_verts: int, dev):
     return topo
 
 
+def _finger_rig(net: GenNet):
+    """The ``contact.FingerRig`` of the net's MANO layer, built once and kept on the model."""
+    from . import contact
+    rig = getattr(net, "_finger_rig", None)
+    if rig is None:
+        rig = contact.FingerRig.from_mano(net.rh_mano)
+        object.__setattr__(net, "_finger_rig", rig)
+    return rig
+
+
+REFINE_PIECES = ("offset", "iter", "rotation", "curl", "reverted")   # of a push-out's dict: what rides to the host, in this order
+
+
+def _refine_fingers_call(net: GenNet, topo, params: torch.Tensor, first, cloud_xyz: torch.Tensor, steps: int, push: float, pull: float,
+                         spin: float, curl: float, max_curl: float, min_contact: int):
+    """The articulated push-out of one call's rows: contact.refine_fingers about the root joint and the knuckles of the first posed
+    pass ``first``; the offset goes to ``transl``, the turn to ``global_orient``, the curls to ``hand_pose``
+    (contact.compose_finger_pose), MANO is posed again -- and, because the kept iterate was the best only under the kernel's blend
+    model, the hands that would be written are scored once (contact.grasp_scores) and a row whose key (class, penetration) came out
+    worse than that of the hand as generated takes back its generated parameters, its first-pass vertices and joints, a zero offset,
+    identity turns and iterate 0.  ``torch.where`` only: no host sync, no third MANO pass.  Returns (params, the hands written,
+    refined); ``refined["scores"]`` holds ``contact.grasp_scores`` of the hands written, merged from the two score sets at hand."""
+    from . import contact
+    rig = _finger_rig(net)
+    knuckles = first.joints[:, rig.joints].contiguous()                            # [B,P,3]
+    out = contact.refine_fingers(topo, rig, first.vertices, cloud_xyz, first.joints[:, 0].contiguous(), knuckles, steps, push, pull,
+                                 spin, curl, max_curl, min_contact)
+    new = params.clone()
+    new[:, 10:13] = contact.compose_orient(params[:, 10:13], out["quat"])
+    new[:, 13:58] = contact.compose_finger_pose(net.rh_mano, params[:, 10:13], params[:, 13:58], out["finger_quat"], rig)
+    new[:, 58:61] = params[:, 58:61] + out["offset"]
+    posed = net.rh_mano(betas=new[:, :10], global_orient=new[:, 10:13], hand_pose=new[:, 13:58], transl=new[:, 58:61])
+    scores1 = contact.grasp_scores(topo, posed.vertices, cloud_xyz)
+    cls1, key1 = contact.select_keys(scores1, "penetration", min_contact)
+    cls0, key0 = contact.select_keys({"penetration": out["penetration0"], "n_contact": out["n_contact0"]}, "penetration", min_contact)
+    worse = (cls1 > cls0) | ((cls1 == cls0) & (key1 > key0))                       # [B]; a NaN key compares false: such a row never moved
+    w1, w2 = worse.unsqueeze(-1), worse.view(-1, 1, 1)
+    ident = torch.zeros_like(out["quat"])
+    ident[:, 0] = 1.0
+    quat = torch.where(w1, ident, out["quat"])
+    fquat = torch.where(w2, ident.unsqueeze(1), out["finger_quat"])
+    refined = {"offset": torch.where(w1, torch.zeros_like(out["offset"]), out["offset"]),
+               "iter": torch.where(worse, torch.zeros_like(out["iter"]), out["iter"]), "quat": quat, "finger_quat": fquat,
+               "curl": contact.quat_axis_angle(fquat.reshape(-1, 4)).reshape(fquat.shape[0], fquat.shape[1], 3),   # float64 [B,P,3]
+               "reverted": worse.to(torch.int32),
+               # the scores of the hands written: the guard's on the re-posed hands, iterate 0's (the bits of grasp_scores on the hand
+               # as generated) on the reverted rows -- a caller that wants exactly these three needs no further launch
+               "scores": {k: torch.where(worse, out[k + "0"], scores1[k]) for k in ("penetration", "n_interior", "n_contact")}}
+    if spin:
+        refined["rotation"] = contact.quat_axis_angle(quat)                        # float64 [B,3]
+    final = types.SimpleNamespace(vertices=torch.where(w2, first.vertices, posed.vertices),
+                                  joints=torch.where(w2, first.joints, posed.joints))
+    return torch.where(w1, params, new), final, refined
+
+
 def _hand_parts(net: GenNet, table):
     """The label table of ``generate_for_objects``' ``hand_parts``: a ``contact.HandParts`` as given, else the one read from the JSON
     path (None: the packaged table), kept on the model so that a run reads and uploads it once."""
@@ -344,7 +414,7 @@ def _generate_call(net: GenNet, objs: Sequence[torch.Tensor], num_grasp: int, ro
                    refine_push: float = 1.0, refine_pull: float = 0.25, diversity: int = 0, stability: bool = False,
                    max_penetration: float = float("inf"), torque_length: float = 0.1,
                    volume: Optional[Dict[str, float]] = None, parts: Optional[Dict[str, object]] = None,
-                   refine_spin: float = 0.0) -> List[Dict[str, object]]:
+                   refine_spin: float = 0.0, refine_curl: float = 0.0, refine_max_curl: float = 0.35) -> List[Dict[str, object]]:
     """One batched call: the ``num_grasp`` grasps of each of ``objs`` (all of one point count), row o * num_grasp + g = grasp g
     of object o.  Every step is row-independent and keyed per row, so each object's slice holds the bits of its own
     ``generate_for_object`` call.  With ``candidates`` = M the call generates M rows per object (exactly the grasps of a
@@ -353,6 +423,8 @@ def _generate_call(net: GenNet, objs: Sequence[torch.Tensor], num_grasp: int, ro
     posed again, so that everything after it -- scores, selection, the rows returned -- sees the hands of the parameters written.
     With ``refine_spin`` > 0 the push-out is the rigid one (contact.refine_rigid about the root joint of the first posed pass): its
     quaternion goes into ``global_orient`` (contact.compose_orient) and its axis-angle rides along as ``refine_rotation``.
+    With ``refine_curl`` > 0 it is the articulated one (_refine_fingers_call): the curls go into ``hand_pose``, rows that came out
+    worse are reverted, and ``refine_curl`` / ``refine_reverted`` ride along.
     With ``diversity`` = K the kept parameters of every object go through one ``ops.segment_kmeans`` (one segment per object) and its
     counts and distances ride in the call's one device-to-host copy (_diversity_launch / _diversity_dicts).  With ``stability`` the
     scores come from ``contact.grasp_stability`` (one kernel in the place of ``contact.grasp_scores``) and its sums and key ride
@@ -390,7 +462,10 @@ def _generate_call(net: GenNet, objs: Sequence[torch.Tensor], num_grasp: int, ro
     if refine_steps:
         from . import contact
         topo = _hand_topology(net, final.vertices.shape[1], dev)
-        if refine_spin:                                                            # about the wrist: the root joint's world position
+        if refine_curl:                                                            # fingers too: parameters, hands and the guard in one place
+            params, final, refined = _refine_fingers_call(net, topo, params, final, batch[:, :3].transpose(1, 2), refine_steps,
+                                                          refine_push, refine_pull, refine_spin, refine_curl, refine_max_curl, min_contact)
+        elif refine_spin:                                                          # about the wrist: the root joint's world position
             refined = contact.refine_rigid(topo, final.vertices, batch[:, :3].transpose(1, 2), final.joints[:, 0].contiguous(),
                                            refine_steps, refine_push, refine_pull, refine_spin, min_contact)
             params[:, 10:13] = contact.compose_orient(params[:, 10:13], refined["quat"])
@@ -398,9 +473,10 @@ def _generate_call(net: GenNet, objs: Sequence[torch.Tensor], num_grasp: int, ro
         else:
             refined = contact.refine_translation(topo, final.vertices, batch[:, :3].transpose(1, 2), refine_steps, refine_push,
                                                  refine_pull, min_contact)
-        params[:, 58:61] += refined["offset"]                                      # fp32; the hands below are those of these parameters
-        final = net.rh_mano(betas=params[:, :10], global_orient=params[:, 10:13], hand_pose=params[:, 13:58],
-                            transl=params[:, 58:61])
+        if not refine_curl:
+            params[:, 58:61] += refined["offset"]                                  # fp32; the hands below are those of these parameters
+            final = net.rh_mano(betas=params[:, :10], global_orient=params[:, 10:13], hand_pose=params[:, 13:58],
+                                transl=params[:, 58:61])
     vol = None
     if volume:                                                                     # after the push-out: the hands of the parameters written
         vol = _volume_launch(net, objs, final.vertices, obj_of_row, R_dev if rotate else None, t_dev if rotate else None, volume["res"])
@@ -433,12 +509,14 @@ def _generate_call(net: GenNet, objs: Sequence[torch.Tensor], num_grasp: int, ro
             topo = _hand_topology(net, final.vertices.shape[1], dev)
             scores = contact.grasp_stability(topo, final.vertices, cloud_xyz, torque_length)
             names = names + ["sums", "key"]
+        elif refined is not None and "scores" in refined:                          # the articulated push-out's guard has scored them
+            scores = refined["scores"]
         else:
             scores = contact.grasp_scores(topo, final.vertices, cloud_xyz)
         tensors = dict(scores)
         if refined is not None:
-            names = ["refine_offset", "refine_iter"] + (["refine_rotation"] if "rotation" in refined else []) + names
-            tensors.update({"refine_" + k: refined[k] for k in ("offset", "iter", "rotation") if k in refined})
+            names = ["refine_" + k for k in REFINE_PIECES if k in refined] + names
+            tensors.update({"refine_" + k: refined[k] for k in REFINE_PIECES if k in refined})
         vol_t = [vol[k] for k in VOLUME_PIECES] if vol is not None else []
         host, *rest_h, err_h = _host_copy([params] + [tensors[k] for k in names] + vol_t + div + prt_t + [err])   # ONE device-to-host copy per call
         if int(err_h[0]) != 0:
@@ -615,7 +693,7 @@ def _select_call(net: GenNet, batch: torch.Tensor, params: torch.Tensor, vertice
     then the ``keep`` most spread-out of them in greedy farthest-point order (``ops.segment_diverse`` over the parameters or the
     posed vertices, read in place); their pool positions and squared gaps ride along in the one copy.  ``refined``: the call's
     rows were pushed out before (contact.refine_translation's dict; ``params`` and ``vertices`` are the refined ones): the kept rows'
-    offsets and iterates (and, after contact.refine_rigid, the axis-angles under ``rotation``) ride along too.  ``diversity``: the
+    offsets and iterates (and, where present, ``rotation``, ``curl`` and ``reverted``: REFINE_PIECES) ride along too.  ``diversity``: the
     k-means statistic of the kept parameters (_diversity_launch) rides along as well.  ``stability``: the candidates' scores come from ``contact.grasp_stability`` (the one kernel in the place of
     ``contact.grasp_scores``); the kept rows' sums and keys ride along and become the four JSON fields of _stability_json.
     ``vol`` (_volume_launch over all candidates) with ``volume`` = its ``res`` and ``max_volume``: candidates whose voxel count exceeds
@@ -630,7 +708,8 @@ def _select_call(net: GenNet, batch: torch.Tensor, params: torch.Tensor, vertice
     if stability:
         scores = contact.grasp_stability(topo, vertices, batch[:, :3].transpose(1, 2), torque_length)
     else:
-        scores = contact.grasp_scores(topo, vertices, batch[:, :3].transpose(1, 2))
+        scores = (dict(refined["scores"]) if refined is not None and "scores" in refined     # the articulated push-out's guard has scored them
+                  else contact.grasp_scores(topo, vertices, batch[:, :3].transpose(1, 2)))
     if logp is not None:
         scores["log_prob"] = logp
     cls, key = contact.select_keys(scores, select_by, min_contact, log_prob=logp, max_penetration=max_penetration)
@@ -653,7 +732,8 @@ def _select_call(net: GenNet, batch: torch.Tensor, params: torch.Tensor, vertice
     kept_p, kept_v = params.index_select(0, rows), vertices.index_select(0, rows)
     kept_s = {k: v.index_select(0, rows) for k, v in scores.items()}
     names = sorted(kept_s)
-    kept_r = [refined[k].index_select(0, rows) for k in ("offset", "iter", "rotation") if k in refined] if refined is not None else []
+    r_names = [k for k in REFINE_PIECES if k in refined] if refined is not None else []
+    kept_r = [refined[k].index_select(0, rows) for k in r_names]
     div = _diversity_launch(kept_p, O, keep, diversity) if diversity else []
     kept_vol = [vol[k].index_select(0, rows) for k in VOLUME_PIECES[:3]] + [vol["err"]] if vol is not None else []
     kept_prt = [prt[k].index_select(0, rows) for k in PARTS_PIECES] if prt is not None else []
@@ -667,7 +747,7 @@ def _select_call(net: GenNet, batch: torch.Tensor, params: torch.Tensor, vertice
         s_host = dict(zip(names, host[2:2 + len(names)]))
         stab_lists = _stability_json(s_host["sums"], s_host["n_contact"], s_host["key"])
     if refined is not None:
-        off_list, it_list, *rot_list = (h.tolist() for h in host[2 + len(names):2 + len(names) + len(kept_r)])
+        r_lists = [h.tolist() for h in host[2 + len(names):2 + len(names) + len(kept_r)]]
     vol_lists = {}
     if vol is not None:
         vat = 2 + len(names) + len(kept_r)
@@ -704,11 +784,8 @@ def _select_call(net: GenNet, batch: torch.Tensor, params: torch.Tensor, vertice
             extra["rank"], extra["novelty"] = rank[o], gap[o]
             extra_json = {**extra_json, "rank": rank_list[o], "novelty": gap_list[o]}
         if refined is not None:
-            extra["refine_offset"], extra["refine_iter"] = kept_r[0][lo:hi], kept_r[1][lo:hi]
-            extra_json = {**extra_json, "refine_offset": off_list[lo:hi], "refine_iter": it_list[lo:hi]}
-            if rot_list:
-                extra["refine_rotation"] = kept_r[2][lo:hi]
-                extra_json["refine_rotation"] = rot_list[0][lo:hi]
+            extra.update({"refine_" + k: x[lo:hi] for k, x in zip(r_names, kept_r)})
+            extra_json = {**extra_json, **{"refine_" + k: x[lo:hi] for k, x in zip(r_names, r_lists)}}
         if diversity:
             extra["diversity"] = div_dicts[o]
             extra_json = {**extra_json, "diversity": div_dicts[o]}
@@ -736,7 +813,8 @@ def generate_for_objects(net: GenNet, objs: Sequence[torch.Tensor], num_grasp: i
                          max_penetration: float = float("inf"), torque_length: float = 0.1, volume: bool = False,
                          volume_res: float = 0.001, max_volume: float = float("inf"), parts: bool = False,
                          part_threshold: float = 0.005, part_min_verts: int = 1, min_fingers: int = 0, need_thumb: bool = False,
-                         hand_parts=None, refine_spin: float = 0.0) -> List[Dict[str, object]]:
+                         hand_parts=None, refine_spin: float = 0.0, refine_curl: float = 0.0,
+                         refine_max_curl: float = 0.35) -> List[Dict[str, object]]:
     """``num_grasp`` grasps for each of ``objs`` ([4,N] tensors) in batched calls that mix objects (plan_calls): one dict per
     object, in the order given, equal to ``generate_for_object(net, objs[i], num_grasp, rotate,
     np.random.default_rng([seed, object_indices[i]]), seed=seed, object_index=object_indices[i], proxies=proxies)`` (and the same
@@ -775,6 +853,16 @@ def generate_for_objects(net: GenNet, objs: Sequence[torch.Tensor], num_grasp: i
     besides the offset, ``params[:, 10:13]`` becomes ``contact.compose_orient(params[:, 10:13], quat)`` before MANO is posed again
     (parameters 0 .. 9 and 13 .. 57 stay).  The dicts gain ``refine_rotation`` [num_grasp,3] (float64: the axis-angle of the turn) next
     to ``refine_offset`` / ``refine_iter``, and so does ``json``.  ``refine_spin = 0`` is the call without the keyword.
+
+    Articulated push-out (``refine_curl`` = C > 0 together with ``refine_steps``, with or without ``refine_spin``): the rows go through
+    ``contact.refine_fingers`` instead, with the knuckles of the first posed pass (``joints[:, rig.joints]``, the rig built once from
+    the layer: ``contact.FingerRig.from_mano``) as the fingers' pivots and ``refine_max_curl`` radians as the largest turn of a
+    finger.  Besides the offset and the turn, ``params[:, 13:58]`` becomes ``contact.compose_finger_pose(...)`` before MANO is posed
+    again (parameters 0 .. 9 stay).  The kernel searches with a blend model of the hand, so the re-posed hands are scored once and a
+    row whose key (class, penetration) came out worse than that of the hand as generated is REVERTED: it keeps its generated
+    parameters and hand, a zero offset, identity turns and ``refine_iter`` = 0.  The dicts gain ``refine_curl`` [num_grasp,P,3]
+    (float64: the axis-angle of every finger's turn, in the rig's order) and ``refine_reverted`` [num_grasp] (int32), and so does
+    ``json``.  ``refine_curl = 0`` is the call without the keyword.  Untuned; the effect on real grasps is not measured.
 
     Diversity statistic (``diversity`` = K, 1 <= K <= min(``num_grasp``, 64)): after selection and push-out the kept [num_grasp,61]
     parameters of every object of a call go through ONE ``ops.segment_kmeans`` (one segment per object, K clusters, evenly spaced
@@ -871,6 +959,12 @@ def generate_for_objects(net: GenNet, objs: Sequence[torch.Tensor], num_grasp: i
         raise RuntimeError(f"generate_for_objects: refine_spin must be finite and >= 0 (got {refine_spin})")
     if refine_spin and not refine_steps:
         raise RuntimeError("generate_for_objects: refine_spin needs refine_steps")
+    if not 0.0 <= float(refine_curl) < float("inf"):
+        raise RuntimeError(f"generate_for_objects: refine_curl must be finite and >= 0 (got {refine_curl})")
+    if refine_curl and not refine_steps:
+        raise RuntimeError("generate_for_objects: refine_curl needs refine_steps")
+    if not 0.0 < float(refine_max_curl) <= math.pi:
+        raise RuntimeError(f"generate_for_objects: refine_max_curl must lie in (0, pi] (got {refine_max_curl})")
     if refine_steps:
         if not 0 < refine_steps <= ops.GRASP_REFINE_MAX_STEPS:
             raise RuntimeError(f"generate_for_objects: refine_steps must lie between 0 and {ops.GRASP_REFINE_MAX_STEPS} (got {refine_steps})")
@@ -882,7 +976,7 @@ def generate_for_objects(net: GenNet, objs: Sequence[torch.Tensor], num_grasp: i
         res = _generate_call(net, [objs[p] for p in call], num_grasp, rotate, seed, [object_indices[p] for p in call], proxies,
                              temperature, top_k, log_prob, candidates, select_by, min_contact, diverse_pool, diverse_space, refine_steps,
                              refine_push, refine_pull, diversity, stability, max_penetration, torque_length, vol_args, parts_args,
-                             float(refine_spin))
+                             float(refine_spin), float(refine_curl), float(refine_max_curl))
         for p, r in zip(call, res):
             out[p] = r
     return out
@@ -925,6 +1019,8 @@ def main(dataset: str, argv: Optional[Sequence[str]] = None) -> List[str]:
                              min_contact=args.min_contact)
             if args.refine_spin:
                 selection.update(refine_spin=args.refine_spin)
+            if args.refine_curl:
+                selection.update(refine_curl=args.refine_curl, refine_max_curl=args.refine_max_curl)
         if args.diversity:
             selection.update(diversity=args.diversity)
         if args.stability or (args.candidates and args.select_by == "stability"):
@@ -934,6 +1030,7 @@ def main(dataset: str, argv: Optional[Sequence[str]] = None) -> List[str]:
         if want_parts:
             selection.update(parts=True, part_threshold=args.part_threshold, part_min_verts=args.part_min_verts,
                              min_fingers=args.min_fingers, need_thumb=bool(args.need_thumb), hand_parts=args.hand_parts)
+        curl_rows: Dict[int, tuple] = {}                                           # --refine_curl: every object's (curled, reverted) counts
         part_rows: Dict[int, tuple] = {}                                           # --parts: every object's (fingers per grasp, contact map)
         vol_rows: Dict[int, list] = {}                                             # --volume: every object's (voxels, cm^3, cm) per grasp
         kept: Dict[int, np.ndarray] = {}                                           # --diversity: every object's kept parameters, on the host
@@ -959,6 +1056,9 @@ def main(dataset: str, argv: Optional[Sequence[str]] = None) -> List[str]:
                     json.dump(out["json"], f)
                 if args.diversity:
                     kept[p] = np.asarray(out["json"]["recon_params"], dtype=np.float32).reshape(args.num_grasp, -1)
+                if args.refine_curl:
+                    curl_rows[p] = (sum(1 for g in out["json"]["refine_curl"] if any(x != 0 for a in g for x in a)),
+                                    sum(out["json"]["refine_reverted"]))
                 if want_volume:
                     vol_rows[p] = list(zip(*(out["json"][k] for k in ("volume_voxels", "penetration_volume", "penetration_depth"))))
                 if want_parts:
@@ -976,6 +1076,16 @@ def main(dataset: str, argv: Optional[Sequence[str]] = None) -> List[str]:
                            "grasps": int(pooled.shape[0])}, f)
             print(f"rank {rank}: diversity of {pooled.shape[0]} grasps in {stat['clusters']} clusters: entropy {stat['entropy']:.4f}, "
                   f"mean distance {stat['mean_dist']:.4f} ({stat['iters']} iterations)")
+        if args.refine_curl:
+            # the run's metadata of the articulated push-out: the rig's joints (the order of "refine_curl") and two integer counts
+            stat = {"joints": _finger_rig(net).joints, "refine_curl": args.refine_curl, "refine_max_curl": args.refine_max_curl,
+                    "grasps": args.num_grasp * len(curl_rows), "curled": sum(c for c, _ in curl_rows.values()),
+                    "reverted": sum(r for _, r in curl_rows.values())}
+            name = "refine_curl.json" if world == 1 else f"refine_curl_rank{rank}.json"
+            with open(os.path.join(args.out_dir, name), "w") as f:
+                json.dump(stat, f)
+            print(f"rank {rank}: articulated push-out of {stat['grasps']} grasps: {stat['curled']} with a curled finger, "
+                  f"{stat['reverted']} reverted")
         if want_volume:
             # the run's figures over this rank's grasps in object order (float64, exactly rounded sums: no grouping can change a bit);
             # contact_ratio is the reference's rule, "volume > 0", on the voxel count

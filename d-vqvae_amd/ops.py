@@ -965,6 +965,64 @@ def grasp_refine_rigid(hand: Tensor, faces: Tensor, vf_off: Tensor, vf_face: Ten
     return offset, quat, it, pen, n_in, n_ct
 
 
+GRASP_FINGERS_MAX_P = 5            # csrc/grasp_refine_fingers.hip: GRF_MAX_P
+
+
+def grasp_refine_fingers(hand: Tensor, faces: Tensor, vf_off: Tensor, vf_face: Tensor, vert_part: Tensor, vert_w: Tensor, n_fingers: int,
+                         obj: Tensor, pivot: Tensor, knuckle: Tensor, steps: int, push: float = 1.0, pull: float = 0.25,
+                         spin: float = 1.0, curl: float = 1.0, max_curl: float = 0.35, min_contact: int = 1,
+                         contact_threshold: float = 0.02 ** 2):
+    """Articulated push-out in one fused kernel (dvq_grasp_refine_fingers; the definition is in include/dvq.h): ``grasp_refine_rigid``
+    whose state also holds one unit quaternion per finger, a turn of the finger about its knuckle.  ``vert_part`` int32 [V] (-1, or the
+    vertex's finger in [0, n_fingers); checked here, on the host, when it lives there -- a device tensor is the caller's word, and the
+    kernel treats a label outside the range as -1), ``vert_w`` f32 [V] (the blend weight in [0, 1]), ``knuckle`` [B,P,3] (fp32,
+    contiguous: every finger's pivot), ``max_curl`` (radians, 0 < max_curl <= pi: no finger turns further from the hand as given).
+    Returns ``(offset [B,3], quat [B,4], finger_quat [B,P,4], iter [B], penetration [B], n_interior [B], n_contact [B],
+    penetration0 [B], n_interior0 [B], n_contact0 [B])``: the best iterate as ``grasp_refine_rigid`` reports it, its finger
+    quaternions (w, x, y, z) and the three scores of iterate 0, which are ``grasp_scores`` of the input.  ``curl = 0`` gives
+    ``grasp_refine_rigid``'s bits and identity finger quaternions."""
+    po, ob, op, oc, B, V, N = _hand_cloud_args("grasp_refine_fingers", hand, faces, vf_off, vf_face, obj)
+    P = int(n_fingers)
+    if not 1 <= P <= GRASP_FINGERS_MAX_P:
+        raise RuntimeError(f"grasp_refine_fingers: need 1 <= n_fingers <= {GRASP_FINGERS_MAX_P} (got {P})")
+    for name, x, dt in (("vert_part", vert_part, torch.int32), ("vert_w", vert_w, torch.float32)):
+        if not isinstance(x, Tensor) or x.dtype != dt or tuple(x.shape) != (V,) or not x.is_contiguous():
+            raise RuntimeError(f"grasp_refine_fingers: {name} must be a contiguous {dt} tensor [V] = [{V}]")
+    if vert_part.device.type == "cpu" and V and (int(vert_part.min()) < -1 or int(vert_part.max()) >= P):
+        raise RuntimeError(f"grasp_refine_fingers: vert_part must lie in [-1, {P}) (got {int(vert_part.min())} .. {int(vert_part.max())})")
+    if vert_w.device.type == "cpu" and V and not bool(((vert_w >= 0) & (vert_w <= 1)).all()):
+        raise RuntimeError("grasp_refine_fingers: vert_w must lie in [0, 1]")
+    for name, x, shape in (("pivot", pivot, (B, 3)), ("knuckle", knuckle, (B, P, 3))):
+        if not isinstance(x, Tensor):
+            raise RuntimeError(f"grasp_refine_fingers: {name} must be a tensor")
+        _f32(x, name)
+        if tuple(x.shape) != shape or not x.is_contiguous():
+            raise RuntimeError(f"grasp_refine_fingers: {name} must be contiguous {list(shape)} (got {tuple(x.shape)})")
+    steps, min_contact = int(steps), int(min_contact)
+    push, pull, spin, curl, max_curl = float(push), float(pull), float(spin), float(curl), float(max_curl)
+    if not 0 <= steps <= GRASP_REFINE_MAX_STEPS:
+        raise RuntimeError(f"grasp_refine_fingers: need 0 <= steps <= {GRASP_REFINE_MAX_STEPS} (got {steps})")
+    if not all(0.0 <= x < float("inf") for x in (push, pull, spin, curl)):
+        raise RuntimeError(f"grasp_refine_fingers: push, pull, spin and curl must be finite and >= 0 (got {push}, {pull}, {spin}, {curl})")
+    if not 0.0 < max_curl <= math.pi:
+        raise RuntimeError(f"grasp_refine_fingers: need 0 < max_curl <= pi (got {max_curl})")
+    min_w = math.cos(0.5 * max_curl)                                                   # float64; rounded once, to fp32, by the call
+    dev = _require_gpu(hand, obj, faces, vf_off, vf_face, vert_part, vert_w, pivot, knuckle)
+    lib = _lib.load()
+    f32 = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)
+    i32 = lambda *shape: torch.empty(*shape, dtype=torch.int32, device=dev)
+    offset, quat, fquat, it, pen, n_in, n_ct, pen0, n_in0, n_ct0 = (f32(B, 3), f32(B, 4), f32(B, P, 4), i32(B), f32(B), i32(B), i32(B),
+                                                                    f32(B), i32(B), i32(B))
+    with torch.cuda.device(dev):
+        check(lib.dvq_grasp_refine_fingers(hand.data_ptr(), faces.data_ptr(), vf_off.data_ptr(), vf_face.data_ptr(), V, vert_part.data_ptr(),
+                                           vert_w.data_ptr(), P, po, ob, op, oc, B, N, pivot.data_ptr(), knuckle.data_ptr(),
+                                           float(contact_threshold), steps, push, pull, spin, curl, min_w, min_contact, offset.data_ptr(),
+                                           quat.data_ptr(), fquat.data_ptr(), it.data_ptr(), pen.data_ptr(), n_in.data_ptr(),
+                                           n_ct.data_ptr(), pen0.data_ptr(), n_in0.data_ptr(), n_ct0.data_ptr(), _stream(dev)),
+              "dvq_grasp_refine_fingers")
+    return offset, quat, fquat, it, pen, n_in, n_ct, pen0, n_in0, n_ct0
+
+
 def segment_topk(cls: Tensor, key: Tensor, n_objects: int, n_candidates: int, keep: int) -> Tensor:
     """cls int32 [O*M], key f32 [O*M] (candidate c of object o at o * M + c) -> int64 [O,keep]: each object's ``keep`` best
     candidate indices, best first, by (cls, key, index) with NaN keys last in their class and -0.0 == +0.0 (dvq_segment_topk)."""

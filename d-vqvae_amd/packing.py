@@ -365,6 +365,7 @@ class PackedMano(_Packed):
         t["j_template"] = tt(jr @ vt)
         t["j_shapedirs"] = tt(np.einsum("jv,vkl->ljk", jr, sh).reshape(10, 48))
         t["weights"] = tt(f64("weights"))
+        self.skin_weights = f64("weights")                # [778,16] float64 as loaded: contact.FingerRig.from_mano sums chains of them
         t["comps"] = tt(f64("hands_components")[:45])
         mean = np.zeros(45) if flat_hand_mean else f64("hands_mean")
         t["pose_mean"] = tt(np.concatenate([np.zeros(3), mean]))

@@ -42,7 +42,8 @@ typedef enum {
 #define DVQ_ABI_VERSION 10
 /* Entry points added since 10 without touching a struct or a signature of it (a compatible extension: bindings of 10 keep
  * working, the version stays): dvq_pixelcnn_sample_ctl, dvq_grasp_scores, dvq_segment_topk, dvq_segment_diverse,
- * dvq_grasp_refine, dvq_segment_kmeans, dvq_grasp_wrench, dvq_grasp_volume, dvq_grasp_parts, dvq_grasp_refine_rigid. */
+ * dvq_grasp_refine, dvq_segment_kmeans, dvq_grasp_wrench, dvq_grasp_volume, dvq_grasp_parts, dvq_grasp_refine_rigid,
+ * dvq_grasp_refine_fingers. */
 int dvq_abi_version(void);
 const char* dvq_last_error(void);
 /* number of visible HIP devices, or -1; does not create a context */
@@ -477,6 +478,61 @@ int dvq_grasp_refine_rigid(const float* hand /* [B,V,3] */, const int32_t* faces
                            float spin, int min_contact, float* offset /* [B,3] */, float* quat /* [B,4] */, int32_t* iter /* [B] */,
                            float* penetration /* [B] */, int32_t* n_interior /* [B] */, int32_t* n_contact /* [B] */,
                            dvq_stream_t stream);
+/* Articulated push-out of grasps: dvq_grasp_refine_rigid whose fingers may also curl -- the state gains one unit quaternion q_f per
+ * finger, a turn of the finger about its knuckle c_f, in ONE kernel, one workgroup of 256 threads per grasp; the best iterate is
+ * reported.  One fingertip buried in the object while the other four sit well cannot be repaired by a rigid motion.  No MANO backward
+ * pass is involved: the kernel searches with a BLEND MODEL of the hand (below), the host writes the turns into the pose parameters (the
+ * knuckles are children of the root joint, so a turn D_f about a knuckle is R_loc' = R0^T D_f R0 R_loc on its local rotation), MANO is
+ * posed again, and the caller compares the re-posed hand's scores with those of iterate 0, which this entry point reports for that
+ * purpose.  The blend model differs from the re-posed hand (measured on the real model: up to 0.44 / 1.81 / 3.24 mm at 0.05 / 0.2 /
+ * 0.35 rad), so the kept iterate is the best only under the model.  The effect on real grasps is NOT MEASURED; the constants are untuned.
+ * Inputs as dvq_grasp_refine_rigid plus: vert_part [V] int32 (-1, or the vertex's finger in [0, P); a label outside [0, P) is read as
+ * -1), vert_w [V] fp32 (a weight in [0, 1]), P (1 <= P <= 5), knuckle [B,P,3] fp32 contiguous (c_f, in the frame of the hand as
+ * given), curl >= 0, and min_w = cos(max_curl / 2), computed in float64 by the caller and rounded once to fp32.
+ * Everything this entry point adds to dvq_grasp_refine_rigid is single fp32 operations, each rounded on its own (no fma), IEEE division
+ * and square root; expressions are evaluated left to right as parenthesised.  With curl = 0 nothing of it is evaluated.
+ * State per grasp: dvq_grasp_refine_rigid's (t, q, turned) plus, per finger f, q_f = (1, 0, 0, 0) and turned_f = false; base = the hand
+ * as given; hand = base; normals = those of hand.  For k = 0 .. steps:
+ *   1-3. dvq_grasp_refine_rigid's steps 1 to 3 on `hand` and `normals` as they stand: o', d_p, j_p, inside_p, near_p, g_p, r_p, the 21
+ *      canonical sums and the three counts.  If k == 0: penetration0, n_interior0, n_contact0 = pen, n_in, n_ct.
+ *      If curl > 0, with f = vert_part[j_p] (if 0 <= f < P) and w = vert_w[j_p]:  a = hand[j_p] - c_f per component;
+ *        e = (w * (a.y*g.z - a.z*g.y), w * (a.z*g.x - a.x*g.z), w * (a.x*g.y - a.y*g.x));  s = (w * w) * ((a.x*a.x + a.y*a.y) + a.z*a.z);
+ *        for each set S (inside, near) and each finger f, four more canonical sums over all points, a point's term being
+ *        ((S_p and vert_part[j_p] == f) ? x : +0.0f):  X_S,f[c] = sum of e[c];  Q_S,f = sum of s.
+ *   4. the key and the rule for the best iterate are dvq_grasp_refine's; the best iterate keeps its q_f too.
+ *   5. if k == steps or pen is NaN, stop.  st and om as dvq_grasp_refine_rigid's step 5.
+ *      If curl > 0, for every finger f:  of[c] = +0.0f;  if Q_in,f > 0: of[c] = of[c] + push * (X_in,f[c] / Q_in,f);  if Q_nr,f > 0:
+ *        of[c] = of[c] + pull * (X_nr,f[c] / Q_nr,f);  of[c] = curl * of[c].  (The least-squares small rotation of the finger about its
+ *        knuckle; no mean is removed: a finger has no shift of its own.)  If some of[c] != 0:  h = 0.5f * of;  p = (1, h) (x) q_f, the
+ *        increment on the LEFT (it is expressed in the hand's fixed frame):
+ *          p.w = ((q.w - h.x*q.x) - h.y*q.y) - h.z*q.z        p.x = ((q.x + h.x*q.w) + h.y*q.z) - h.z*q.y
+ *          p.y = ((q.y + h.y*q.w) - h.x*q.z) + h.z*q.x        p.z = ((q.z + h.z*q.w) + h.x*q.y) - h.y*q.x
+ *        n2 = ((p.w*p.w + p.x*p.x) + p.y*p.y) + p.z*p.z;  cand = p * (1.0f / sqrtf(n2)) per component.  The candidate is accepted iff
+ *        cand.w >= min_w (a NaN refuses): then q_f = cand, turned_f = true.  Otherwise q_f stays for this step.
+ *      If all six of st[c] and om[c] are == 0 and no finger was accepted in this step, stop.
+ *      t and q are updated as in dvq_grasp_refine_rigid.  If a finger was accepted in this step, the hand of the next iterate is, for
+ *      every vertex v with f = vert_part[v] in [0, P) and turned_f, with R = R(q_f) and d = base[v] - c_f per component:
+ *        rot[i] = ((R[i][0]*d.x + R[i][1]*d.y) + R[i][2]*d.z) + c_f[i];   hand[v][i] = base[v][i] + vert_w[v] * (rot[i] - base[v][i]);
+ *      every other vertex is base[v] bit for bit; and normals = the vertex normals of this hand (recomputed, not rotated).
+ * Outputs: dvq_grasp_refine_rigid's six, finger_quat [B,P,4] = the best iterate's q_f (w, x, y, z), and penetration0 / n_interior0 /
+ * n_contact0 [B], which are the bits of dvq_grasp_scores on the input.  The hand the kernel believed in is R(quat) (hand* - c) + c +
+ * offset with hand* the blend above under finger_quat.  With curl = 0 the six are the bits of dvq_grasp_refine_rigid and every q_f is
+ * (1, 0, 0, 0); with spin = 0 as well they are those of dvq_grasp_refine; with steps = 0 the scores are those of dvq_grasp_scores.  A
+ * grasp's result does not depend on B or on its row.  Coordinates that are not finite behave as in dvq_grasp_refine_rigid; a knuckle
+ * that is NaN makes its finger's Q NaN (no turn), one that is Inf makes the candidate NaN (refused): such a finger never turns.
+ * Known limits: no joint limits beyond max_curl; no finger-to-finger collision test; the shift, the turn and the curl all answer the
+ * same contacts, so a step may overshoot.
+ * B >= 0, N >= 1, 1 <= V <= 2048, 1 <= P <= 5, 0 <= steps <= 64, push, pull, spin and curl finite and >= 0, 0 <= min_w <= 1, no null
+ * pointer; anything else is DVQ_EINVAL, nothing launched. */
+int dvq_grasp_refine_fingers(const float* hand /* [B,V,3] */, const int32_t* faces, const int32_t* vf_off, const int32_t* vf_face, int V,
+                             const int32_t* vert_part /* [V] */, const float* vert_w /* [V] */, int P, const float* obj,
+                             int64_t obj_batch_stride, int64_t obj_point_stride, int64_t obj_coord_stride, int64_t B, int N,
+                             const float* pivot /* [B,3] */, const float* knuckle /* [B,P,3] */, float contact_threshold, int steps,
+                             float push, float pull, float spin, float curl, float min_w, int min_contact, float* offset /* [B,3] */,
+                             float* quat /* [B,4] */, float* finger_quat /* [B,P,4] */, int32_t* iter /* [B] */,
+                             float* penetration /* [B] */, int32_t* n_interior /* [B] */, int32_t* n_contact /* [B] */,
+                             float* penetration0 /* [B] */, int32_t* n_interior0 /* [B] */, int32_t* n_contact0 /* [B] */,
+                             dvq_stream_t stream);
 /* Grasp stability proxy: the contact-wrench sums of a grasp and a ranking key from them, with the three scores of dvq_grasp_scores,
  * in ONE kernel, one workgroup of 256 threads per grasp.  New here: the reference judges whether the object stays in the hand by a
  * physics run (pybullet + V-HACD, out of scope); this is the usual cheap stand-in, a force-closure figure over the contact wrenches:
