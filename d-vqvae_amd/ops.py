@@ -902,6 +902,39 @@ def grasp_volume(hand: Tensor, faces: Tensor, loop_off: Tensor, loop_vert: Tenso
 
 
 GRASP_REFINE_MAX_STEPS = 64        # csrc/grasp_refine.hip: GR_MAX_STEPS
+GRASP_FINGERS_MAX_P = 5            # csrc/grasp_refine.hip: GR_MAX_P
+
+
+def _refine_steps(what: str, steps) -> int:
+    steps = int(steps)
+    if not 0 <= steps <= GRASP_REFINE_MAX_STEPS:
+        raise RuntimeError(f"{what}: need 0 <= steps <= {GRASP_REFINE_MAX_STEPS} (got {steps})")
+    return steps
+
+
+def _refine_factors(what: str, **factors):
+    """The step factors as floats, in the order given; each must be finite and >= 0 (a NaN compares false)."""
+    names, vals = list(factors), [float(v) for v in factors.values()]
+    if not all(0.0 <= v < float("inf") for v in vals):
+        raise RuntimeError(f"{what}: {', '.join(names[:-1])} and {names[-1]} must be finite and >= 0 (got {', '.join(map(str, vals))})")
+    return vals
+
+
+def _refine_rows(what: str, name: str, x, shape, shown=None) -> None:
+    """``pivot`` / ``knuckle``: an fp32 tensor of exactly ``shape`` = [B,...], contiguous."""
+    if not isinstance(x, Tensor):
+        raise RuntimeError(f"{what}: {name} must be a tensor")
+    _f32(x, name)
+    if tuple(x.shape) != shape or not x.is_contiguous():
+        raise RuntimeError(f"{what}: {name} must be contiguous {shown or list(shape)} (got {tuple(x.shape)})")
+
+
+def _refine_outputs(B: int, dev: torch.device, *state, iterate0: bool = False):
+    """A level's outputs: one fp32 [B,*s] per ``s`` of ``state`` (offset, quat, ...), then iter i32, penetration f32, n_interior i32,
+    n_contact i32, all [B]; with ``iterate0`` the three scores once more, for iterate 0."""
+    f32 = lambda *shape: torch.empty(B, *shape, dtype=torch.float32, device=dev)
+    i32 = lambda: torch.empty(B, dtype=torch.int32, device=dev)
+    return tuple(f32(*s) for s in state) + (i32(), f32(), i32(), i32()) + ((f32(), i32(), i32()) if iterate0 else ())
 
 
 def grasp_refine(hand: Tensor, faces: Tensor, vf_off: Tensor, vf_face: Tensor, obj: Tensor, steps: int, push: float = 1.0,
@@ -910,24 +943,18 @@ def grasp_refine(hand: Tensor, faces: Tensor, vf_off: Tensor, vf_face: Tensor, o
     descent on the scores of ``grasp_scores`` with respect to the hand's translation.  Returns ``(offset [B,3] f32, iter [B] i32,
     penetration [B] f32, n_interior [B] i32, n_contact [B] i32)`` of each grasp's best iterate -- add ``offset`` to the hand's
     translation.  Arguments as ``grasp_scores`` (obj [B,N,3] with any strides, read in place)."""
-    po, ob, op, oc, B, V, N = _hand_cloud_args("grasp_refine", hand, faces, vf_off, vf_face, obj)
-    steps, min_contact, push, pull = int(steps), int(min_contact), float(push), float(pull)
-    if not 0 <= steps <= GRASP_REFINE_MAX_STEPS:
-        raise RuntimeError(f"grasp_refine: need 0 <= steps <= {GRASP_REFINE_MAX_STEPS} (got {steps})")
-    if not (0.0 <= push < float("inf") and 0.0 <= pull < float("inf")):
-        raise RuntimeError(f"grasp_refine: push and pull must be finite and >= 0 (got {push}, {pull})")
+    what = "grasp_refine"
+    po, ob, op, oc, B, V, N = _hand_cloud_args(what, hand, faces, vf_off, vf_face, obj)
+    steps, min_contact = _refine_steps(what, steps), int(min_contact)
+    push, pull = _refine_factors(what, push=push, pull=pull)
     dev = _require_gpu(hand, obj, faces, vf_off, vf_face)
     lib = _lib.load()
-    offset = torch.empty(B, 3, dtype=torch.float32, device=dev)
-    it = torch.empty(B, dtype=torch.int32, device=dev)
-    pen = torch.empty(B, dtype=torch.float32, device=dev)
-    n_in = torch.empty(B, dtype=torch.int32, device=dev)
-    n_ct = torch.empty(B, dtype=torch.int32, device=dev)
+    outs = _refine_outputs(B, dev, (3,))                                               # offset, iter, penetration, n_interior, n_contact
     with torch.cuda.device(dev):
         check(lib.dvq_grasp_refine(hand.data_ptr(), faces.data_ptr(), vf_off.data_ptr(), vf_face.data_ptr(), V, po, ob, op, oc, B, N,
-                                   float(contact_threshold), steps, push, pull, min_contact, offset.data_ptr(), it.data_ptr(),
-                                   pen.data_ptr(), n_in.data_ptr(), n_ct.data_ptr(), _stream(dev)), "dvq_grasp_refine")
-    return offset, it, pen, n_in, n_ct
+                                   float(contact_threshold), steps, push, pull, min_contact, *(t.data_ptr() for t in outs),
+                                   _stream(dev)), "dvq_grasp_refine")
+    return outs
 
 
 def grasp_refine_rigid(hand: Tensor, faces: Tensor, vf_off: Tensor, vf_face: Tensor, obj: Tensor, pivot: Tensor, steps: int,
@@ -938,34 +965,19 @@ def grasp_refine_rigid(hand: Tensor, faces: Tensor, vf_off: Tensor, vf_face: Ten
     [B,3] f32, quat [B,4] f32 (w, x, y, z), iter [B] i32, penetration [B] f32, n_interior [B] i32, n_contact [B] i32)`` of each
     grasp's best iterate: the refined hand is ``R(quat) (v - pivot) + pivot + offset``.  ``spin = 0`` gives ``grasp_refine``'s bits
     and the identity quaternion.  Other arguments as ``grasp_refine``."""
-    po, ob, op, oc, B, V, N = _hand_cloud_args("grasp_refine_rigid", hand, faces, vf_off, vf_face, obj)
-    if not isinstance(pivot, Tensor):
-        raise RuntimeError("grasp_refine_rigid: pivot must be a tensor")
-    _f32(pivot, "pivot")
-    if tuple(pivot.shape) != (B, 3) or not pivot.is_contiguous():
-        raise RuntimeError(f"grasp_refine_rigid: pivot must be contiguous [B,3] = [{B},3] (got {tuple(pivot.shape)})")
-    steps, min_contact, push, pull, spin = int(steps), int(min_contact), float(push), float(pull), float(spin)
-    if not 0 <= steps <= GRASP_REFINE_MAX_STEPS:
-        raise RuntimeError(f"grasp_refine_rigid: need 0 <= steps <= {GRASP_REFINE_MAX_STEPS} (got {steps})")
-    if not (0.0 <= push < float("inf") and 0.0 <= pull < float("inf") and 0.0 <= spin < float("inf")):
-        raise RuntimeError(f"grasp_refine_rigid: push, pull and spin must be finite and >= 0 (got {push}, {pull}, {spin})")
+    what = "grasp_refine_rigid"
+    po, ob, op, oc, B, V, N = _hand_cloud_args(what, hand, faces, vf_off, vf_face, obj)
+    _refine_rows(what, "pivot", pivot, (B, 3), f"[B,3] = [{B},3]")
+    steps, min_contact = _refine_steps(what, steps), int(min_contact)
+    push, pull, spin = _refine_factors(what, push=push, pull=pull, spin=spin)
     dev = _require_gpu(hand, obj, faces, vf_off, vf_face, pivot)
     lib = _lib.load()
-    offset = torch.empty(B, 3, dtype=torch.float32, device=dev)
-    quat = torch.empty(B, 4, dtype=torch.float32, device=dev)
-    it = torch.empty(B, dtype=torch.int32, device=dev)
-    pen = torch.empty(B, dtype=torch.float32, device=dev)
-    n_in = torch.empty(B, dtype=torch.int32, device=dev)
-    n_ct = torch.empty(B, dtype=torch.int32, device=dev)
+    outs = _refine_outputs(B, dev, (3,), (4,))                                         # offset, quat, iter, penetration, n_interior, n_contact
     with torch.cuda.device(dev):
         check(lib.dvq_grasp_refine_rigid(hand.data_ptr(), faces.data_ptr(), vf_off.data_ptr(), vf_face.data_ptr(), V, po, ob, op, oc, B,
                                          N, pivot.data_ptr(), float(contact_threshold), steps, push, pull, spin, min_contact,
-                                         offset.data_ptr(), quat.data_ptr(), it.data_ptr(), pen.data_ptr(), n_in.data_ptr(),
-                                         n_ct.data_ptr(), _stream(dev)), "dvq_grasp_refine_rigid")
-    return offset, quat, it, pen, n_in, n_ct
-
-
-GRASP_FINGERS_MAX_P = 5            # csrc/grasp_refine_fingers.hip: GRF_MAX_P
+                                         *(t.data_ptr() for t in outs), _stream(dev)), "dvq_grasp_refine_rigid")
+    return outs
 
 
 def grasp_refine_fingers(hand: Tensor, faces: Tensor, vf_off: Tensor, vf_face: Tensor, vert_part: Tensor, vert_w: Tensor, n_fingers: int,
@@ -981,7 +993,8 @@ def grasp_refine_fingers(hand: Tensor, faces: Tensor, vf_off: Tensor, vf_face: T
     penetration0 [B], n_interior0 [B], n_contact0 [B])``: the best iterate as ``grasp_refine_rigid`` reports it, its finger
     quaternions (w, x, y, z) and the three scores of iterate 0, which are ``grasp_scores`` of the input.  ``curl = 0`` gives
     ``grasp_refine_rigid``'s bits and identity finger quaternions."""
-    po, ob, op, oc, B, V, N = _hand_cloud_args("grasp_refine_fingers", hand, faces, vf_off, vf_face, obj)
+    what = "grasp_refine_fingers"
+    po, ob, op, oc, B, V, N = _hand_cloud_args(what, hand, faces, vf_off, vf_face, obj)
     P = int(n_fingers)
     if not 1 <= P <= GRASP_FINGERS_MAX_P:
         raise RuntimeError(f"grasp_refine_fingers: need 1 <= n_fingers <= {GRASP_FINGERS_MAX_P} (got {P})")
@@ -992,35 +1005,23 @@ def grasp_refine_fingers(hand: Tensor, faces: Tensor, vf_off: Tensor, vf_face: T
         raise RuntimeError(f"grasp_refine_fingers: vert_part must lie in [-1, {P}) (got {int(vert_part.min())} .. {int(vert_part.max())})")
     if vert_w.device.type == "cpu" and V and not bool(((vert_w >= 0) & (vert_w <= 1)).all()):
         raise RuntimeError("grasp_refine_fingers: vert_w must lie in [0, 1]")
-    for name, x, shape in (("pivot", pivot, (B, 3)), ("knuckle", knuckle, (B, P, 3))):
-        if not isinstance(x, Tensor):
-            raise RuntimeError(f"grasp_refine_fingers: {name} must be a tensor")
-        _f32(x, name)
-        if tuple(x.shape) != shape or not x.is_contiguous():
-            raise RuntimeError(f"grasp_refine_fingers: {name} must be contiguous {list(shape)} (got {tuple(x.shape)})")
-    steps, min_contact = int(steps), int(min_contact)
-    push, pull, spin, curl, max_curl = float(push), float(pull), float(spin), float(curl), float(max_curl)
-    if not 0 <= steps <= GRASP_REFINE_MAX_STEPS:
-        raise RuntimeError(f"grasp_refine_fingers: need 0 <= steps <= {GRASP_REFINE_MAX_STEPS} (got {steps})")
-    if not all(0.0 <= x < float("inf") for x in (push, pull, spin, curl)):
-        raise RuntimeError(f"grasp_refine_fingers: push, pull, spin and curl must be finite and >= 0 (got {push}, {pull}, {spin}, {curl})")
+    _refine_rows(what, "pivot", pivot, (B, 3))
+    _refine_rows(what, "knuckle", knuckle, (B, P, 3))
+    steps, min_contact, max_curl = _refine_steps(what, steps), int(min_contact), float(max_curl)
+    push, pull, spin, curl = _refine_factors(what, push=push, pull=pull, spin=spin, curl=curl)
     if not 0.0 < max_curl <= math.pi:
         raise RuntimeError(f"grasp_refine_fingers: need 0 < max_curl <= pi (got {max_curl})")
     min_w = math.cos(0.5 * max_curl)                                                   # float64; rounded once, to fp32, by the call
     dev = _require_gpu(hand, obj, faces, vf_off, vf_face, vert_part, vert_w, pivot, knuckle)
     lib = _lib.load()
-    f32 = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)
-    i32 = lambda *shape: torch.empty(*shape, dtype=torch.int32, device=dev)
-    offset, quat, fquat, it, pen, n_in, n_ct, pen0, n_in0, n_ct0 = (f32(B, 3), f32(B, 4), f32(B, P, 4), i32(B), f32(B), i32(B), i32(B),
-                                                                    f32(B), i32(B), i32(B))
+    # offset, quat, finger_quat, iter, penetration, n_interior, n_contact, then iterate 0's penetration0, n_interior0, n_contact0
+    outs = _refine_outputs(B, dev, (3,), (4,), (P, 4), iterate0=True)
     with torch.cuda.device(dev):
         check(lib.dvq_grasp_refine_fingers(hand.data_ptr(), faces.data_ptr(), vf_off.data_ptr(), vf_face.data_ptr(), V, vert_part.data_ptr(),
                                            vert_w.data_ptr(), P, po, ob, op, oc, B, N, pivot.data_ptr(), knuckle.data_ptr(),
-                                           float(contact_threshold), steps, push, pull, spin, curl, min_w, min_contact, offset.data_ptr(),
-                                           quat.data_ptr(), fquat.data_ptr(), it.data_ptr(), pen.data_ptr(), n_in.data_ptr(),
-                                           n_ct.data_ptr(), pen0.data_ptr(), n_in0.data_ptr(), n_ct0.data_ptr(), _stream(dev)),
-              "dvq_grasp_refine_fingers")
-    return offset, quat, fquat, it, pen, n_in, n_ct, pen0, n_in0, n_ct0
+                                           float(contact_threshold), steps, push, pull, spin, curl, min_w, min_contact,
+                                           *(t.data_ptr() for t in outs), _stream(dev)), "dvq_grasp_refine_fingers")
+    return outs
 
 
 def segment_topk(cls: Tensor, key: Tensor, n_objects: int, n_candidates: int, keep: int) -> Tensor:

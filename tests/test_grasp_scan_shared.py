@@ -3,7 +3,11 @@ dvq_grasp_wrench share -- at sizes the MANO-sized cases of the other grasp tests
 four-vertex block at all; one block and a tail of one; one block and a tail of three) against clouds of 1, 257 and 1025 points (one
 point; a second thread block of points; a second 4 x 256 pass with a single live point).  Every batch has a finite row, a row whose
 hand holds a NaN (the whole row takes the exact scan) and a row whose last point holds an inf (only that thread's pass takes it).
-The references are tests/grasp_score_ref.py, grasp_refine_ref.py and grasp_wrench_ref.py; everything is compared bit for bit."""
+The references are tests/grasp_score_ref.py, grasp_refine_ref.py and grasp_wrench_ref.py; everything is compared bit for bit.
+
+The three levels of the push-out (csrc/grasp_refine.hip: translation, rigid, fingers) are one kernel text, so the two upper levels go
+to the same sizes (``ladder``): the pivot at vertex 0, two fingers that share the rim vertices alternately with weights 1 and 0.5, their
+knuckles at vertices 1 and 2, against tests/grasp_refine_rigid_ref.py and grasp_refine_fingers_ref.py."""
 import functools
 import hashlib
 
@@ -14,7 +18,9 @@ import torch
 import dvqvae_amd  # noqa: F401
 from dvqvae_amd import contact, ops, synth
 
+import grasp_refine_fingers_ref as fingers_ref
 import grasp_refine_ref as refine_ref
+import grasp_refine_rigid_ref as rigid_ref
 import grasp_score_ref as score_ref
 import grasp_wrench_ref as wrench_ref
 
@@ -24,6 +30,10 @@ SIZES = [(V, N) for V in (3, 5, 7) for N in (1, 257, 1025)]
 SCORES = ("penetration", "n_interior", "n_contact")
 REFINE = ("offset", "iter") + SCORES
 WRENCH = SCORES + ("centre", "sums", "key")
+RIGID = ("offset", "quat", "iter") + SCORES
+FINGERS = fingers_ref.NAMES
+N_FINGERS, MAX_CURL = 2, 0.35
+IDENTITY = np.asarray([1, 0, 0, 0], np.float32)
 
 
 def fan(V):
@@ -48,6 +58,27 @@ def case(V, N):
     for a in [hand, faces, obj] + [x for d in want.values() for x in d.values()]:
         a.setflags(write=False)
     return hand, faces, obj, want
+
+
+@functools.lru_cache(maxsize=None)
+def ladder(V, N):
+    """``case(V, N)``'s hand and cloud for the two upper levels: (pivot [3,3], vert_part [V], vert_w [V], knuckle [3,2,3], the rigid and
+    the fingers reference's outputs with the turn on and off as dicts): computed once per size, never written to.  Steps, push, pull
+    and min_contact are the translation case's; spin = curl = 1."""
+    hand, faces, obj, _ = case(V, N)
+    finite = lambda a: np.where(np.isfinite(a), a, np.float32(0.0)).astype(np.float32)
+    pivot = finite(hand[:, 0])
+    knuckle = finite(np.stack([hand[:, 1], hand[:, 2]], 1))
+    vert_part = np.asarray([-1] + [i % 2 for i in range(V - 1)], np.int32)
+    vert_w = np.asarray([0.0] + [1.0 if i % 2 == 0 else 0.5 for i in range(V - 1)], np.float32)
+    rigid = lambda spin: dict(zip(RIGID, rigid_ref.grasp_refine_rigid(hand, faces, obj, pivot, STEPS, spin=spin, contact_threshold=THR)))
+    fingers = lambda curl: dict(zip(FINGERS, fingers_ref.grasp_refine_fingers(hand, faces, obj, pivot, vert_part, vert_w, knuckle, STEPS, spin=1.0,
+                                                                              curl=curl, max_curl=MAX_CURL, contact_threshold=THR)))
+    with np.errstate(all="ignore"):
+        want = {"rigid": rigid(1.0), "rigid_spin0": rigid(0.0), "fingers": fingers(1.0), "fingers_curl0": fingers(0.0)}
+    for a in [pivot, vert_part, vert_w, knuckle] + [x for d in want.values() for x in d.values()]:
+        a.setflags(write=False)
+    return pivot, vert_part, vert_w, knuckle, want
 
 
 def assert_same_bits(got, want, names, what):
@@ -83,6 +114,11 @@ PINNED = {
     (7, 1025): dict(n_interior=[559, 0, 346], n_contact=[97, 0, 181], iter=[2, 0, 2],
                     sha256="ccdbdb3e3d9b0b3e58369adf12582d771462b8e8d8604ce8e20c70cd33fc9e60"),
 }
+# the iterates the two upper levels' references kept on those sizes, as they stood when the three kernels became one text
+PINNED_LADDER = {
+    (5, 257): dict(rigid=[2, 0, 1], fingers=[2, 0, 1]),
+    (7, 1025): dict(rigid=[2, 0, 2], fingers=[2, 0, 2]),
+}
 
 
 @pytest.mark.parametrize("V,N", sorted(PINNED))
@@ -98,6 +134,28 @@ def test_the_references_give_what_they_gave(V, N):
     assert_same_bits(zero, want["scores"], SCORES, "reference: steps = 0")
     assert_same_bits(want["wrench"], want["scores"], SCORES, "reference: the wrench's scores")
     assert np.isnan(want["scores"]["penetration"][1]) and not np.isnan(want["scores"]["penetration"][0])
+
+
+@pytest.mark.parametrize("V,N", SIZES)
+def test_the_upper_levels_references_reduce_to_the_level_below(V, N):
+    hand, faces, obj, want = case(V, N)
+    pivot, vert_part, vert_w, knuckle, up = ladder(V, N)
+    assert np.isfinite(pivot).all() and np.isfinite(knuckle).all()
+    assert_same_bits(up["rigid_spin0"], want["refine"], REFINE, "reference: rigid at spin = 0 against the translation")
+    assert np.array_equal(up["rigid_spin0"]["quat"], np.tile(IDENTITY, (3, 1)))
+    assert_same_bits(up["fingers_curl0"], up["rigid"], RIGID, "reference: fingers at curl = 0 against rigid")
+    assert np.array_equal(up["fingers_curl0"]["finger_quat"], np.tile(IDENTITY, (3, N_FINGERS, 1)))
+    # the inputs exercise what they are for: the finite row turns, and one of its fingers curls (at V = 3 the knuckles are the
+    # fingers' only vertices: no arm, no curl)
+    if N >= 257:
+        assert not np.array_equal(up["rigid"]["quat"][0], IDENTITY), up["rigid"]["quat"][0]
+    curled = (up["fingers"]["finger_quat"][0] != IDENTITY).any(axis=1)
+    if V == 3:
+        assert not curled.any(), up["fingers"]["finger_quat"][0]
+    elif N >= 257:
+        assert curled.any(), up["fingers"]["finger_quat"][0]
+    if (V, N) in PINNED_LADDER:
+        assert dict(rigid=up["rigid"]["iter"].tolist(), fingers=up["fingers"]["iter"].tolist()) == PINNED_LADDER[(V, N)]
 
 
 def gpu(a):
@@ -121,3 +179,25 @@ def test_the_three_kernels_agree_with_their_references_and_each_other(V, N):
     assert_same_bits(wrench, scores, SCORES, "grasp_wrench's scores against grasp_scores")
     assert_same_bits(refined, want["refine"], REFINE, "grasp_refine")
     assert_same_bits(wrench, want["wrench"], WRENCH, "grasp_wrench")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("V,N", SIZES)
+def test_the_upper_levels_agree_with_their_references_and_the_level_below(V, N):
+    hand, faces, obj, _ = case(V, N)
+    pivot, vert_part, vert_w, knuckle, want = ladder(V, N)
+    topo = contact.HandTopology(faces, V, DEV)
+    mesh, cloud, piv = (gpu(hand), topo.faces, topo.vf_off, topo.vf_face), gpu(obj), gpu(pivot)
+    host = lambda names, out: dict(zip(names, (x.cpu().numpy() for x in out)))
+    rigid = lambda spin: host(RIGID, ops.grasp_refine_rigid(*mesh, cloud, piv, steps=STEPS, spin=spin, contact_threshold=THR))
+    fingers = lambda curl: host(FINGERS, ops.grasp_refine_fingers(*mesh, gpu(vert_part), gpu(vert_w), N_FINGERS, cloud, piv, gpu(knuckle),
+                                                                  steps=STEPS, spin=1.0, curl=curl, max_curl=MAX_CURL,
+                                                                  contact_threshold=THR))
+    turned, curled = rigid(1.0), fingers(1.0)
+    assert_same_bits(turned, want["rigid"], RIGID, "grasp_refine_rigid")
+    assert_same_bits(curled, want["fingers"], FINGERS, "grasp_refine_fingers")
+    shifted = host(REFINE, ops.grasp_refine(*mesh, cloud, steps=STEPS, contact_threshold=THR))
+    assert_same_bits(rigid(0.0), shifted, REFINE, "grasp_refine_rigid(spin=0) against grasp_refine")
+    assert_same_bits(fingers(0.0), turned, RIGID, "grasp_refine_fingers(curl=0) against grasp_refine_rigid")
+    scores = host(SCORES, ops.grasp_scores(*mesh, cloud, contact_threshold=THR))
+    assert_same_bits({k: curled[k + "0"] for k in SCORES}, scores, SCORES, "grasp_refine_fingers' iterate 0 against grasp_scores")
