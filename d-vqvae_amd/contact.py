@@ -632,6 +632,142 @@ def parts_class(out, min_fingers, need_thumb, min_verts=1, n_fingers=5):
     return torch.where(status != 0, two, torch.where(poor, one, torch.zeros_like(status))).to(torch.int32)
 
 
+SELF_REACH, SELF_MARGIN, SELF_SEAM = 0.01, 0.001, 2    # metres, metres, edge rings: calibrated against false alarms only; untuned
+
+
+class SelfTable:
+    """What ``grasp_self`` tests a hand of ``parts`` (a ``HandParts``) against itself with: ``source`` int32 [V], 0 at the SEAM
+    vertices -- parts of one hand are joined surfaces, and next to a join the vector to the nearest vertex of the other part is
+    tangent to the surface, so the sign of the interior test is noise there: a vertex that an edge of ``faces`` joins to a vertex of
+    a different label, or that lies within ``seam`` - 1 further edge rings of such a vertex, never counts as a source (it remains a
+    target; ``seam`` = 0: no seam) -- and ``pairs``, P words: bit b of ``pairs[a]`` = part a's vertices are tested against part
+    b's.  The first ``n_fingers`` parts are tested against one another and, with ``palm``, against every remaining part as well
+    (the remaining parts are sources of nothing).  ``pairs=`` / ``source=`` replace the derived ones outright."""
+
+    def __init__(self, parts, faces, seam=SELF_SEAM, palm=True, n_fingers=5, pairs=None, source=None, device=None):
+        if not isinstance(parts, HandParts):
+            raise RuntimeError("SelfTable: parts must be a HandParts")
+        V, P = parts.n_verts, parts.n_parts
+        seam, n_fingers = int(seam), int(n_fingers)
+        if seam < 0 or n_fingers < 0:
+            raise RuntimeError(f"SelfTable: seam >= 0 and n_fingers >= 0 (got {seam}, {n_fingers})")
+        n_fingers = min(n_fingers, P)                           # a table of fewer parts: all of them are fingers
+        self.parts, self.seam, self.palm, self.n_fingers = parts, seam, bool(palm), n_fingers
+        if source is None:
+            f = np.asarray(faces.detach().cpu() if torch.is_tensor(faces) else faces, dtype=np.int64).reshape(-1, 3)
+            if f.size and (f.min() < 0 or f.max() >= V):
+                raise RuntimeError(f"SelfTable: a face index is outside [0, {V})")
+            edges = np.concatenate([f[:, [0, 1]], f[:, [1, 2]], f[:, [2, 0]]])
+            near = np.zeros(V, bool)
+            if seam >= 1:
+                cut = edges[parts.labels[edges[:, 0]] != parts.labels[edges[:, 1]]]
+                near[cut.reshape(-1)] = True
+                for _ in range(seam - 1):                       # one more edge ring
+                    grow = near.copy()
+                    grow[edges[near[edges[:, 1]], 0]] = True
+                    grow[edges[near[edges[:, 0]], 1]] = True
+                    near = grow
+            src = (~near).astype(np.int32)
+        else:
+            src = np.asarray(source.detach().cpu() if torch.is_tensor(source) else source)
+            if src.shape != (V,) or src.dtype.kind not in "iub":
+                raise RuntimeError(f"SelfTable: source must be an integer array [{V}] (got {src.dtype} {src.shape})")
+            src = (src != 0).astype(np.int32)
+        self.source = src
+        self.n_seam = int(V - src.sum())
+        if pairs is None:
+            fingers = (1 << n_fingers) - 1
+            rest = ((1 << P) - 1) & ~fingers if palm else 0
+            words = [(fingers & ~(1 << a)) | rest if a < n_fingers else 0 for a in range(P)]
+        else:
+            words = [int(w) for w in (pairs.tolist() if hasattr(pairs, "tolist") else pairs)]
+            if len(words) != P:
+                raise RuntimeError(f"SelfTable: pairs must hold {P} words, one per part (got {len(words)})")
+            for a, w in enumerate(words):
+                if not 0 <= w < 1 << P or (w >> a) & 1:
+                    raise RuntimeError(f"SelfTable: pairs[{a}] = {w:#x} names a part at or above {P}, or part {a} itself")
+        self.pairs = np.asarray(words, dtype=np.uint32)
+        self._dev = {}
+        if device is not None:
+            self.on(torch.device(device))
+
+    def on(self, device):
+        """(labels, source) int32 [V] on ``device`` (uploaded once per device)."""
+        key = str(device)
+        if key not in self._dev:
+            self._dev[key] = (self.parts.on(device), torch.from_numpy(self.source).to(device))
+        return self._dev[key]
+
+
+def grasp_self(topology, table, hand_xyz, reach=SELF_REACH, margin=SELF_MARGIN):
+    """Finger-to-finger (and finger-to-palm) collision of hands, from ONE fused kernel (ops.grasp_self; the definition is in
+    include/dvq.h under dvq_grasp_self): every source vertex of ``table`` (a ``SelfTable``) finds its nearest vertex among the parts
+    its own part is tested against, and PENETRATES when that vertex lies within ``reach`` METRES (squared once, here) and the source
+    is more than ``margin`` metres behind its tangent plane.  Returns ``pen_count`` [B,P] i32, ``pen_depth`` [B,P] f32 (metres, +0.0
+    without a penetrating vertex), ``gap_min`` [B,P] f32 (squared metres, +inf for a part without a source), ``pair_bits`` [B,P] i32
+    (bit b: part b was hit), ``mask`` [B,W] i32 (bit v & 31 of word v >> 5: vertex v penetrates) and ``status`` [B] i32 (1: a
+    coordinate of the row is not finite, and the row has no figure: -1, NaN, NaN, 0, 0).  ``self_stats`` / ``self_class`` turn them
+    into the figures written and into a selection guard.
+
+    A proximity figure in the style of ``get_interior``, not a mesh-mesh intersection: vertices only, so a thin crossing between
+    vertices is missed.  The defaults are calibrated only against false alarms on 48 posed hands of the real hand model and are
+    UNTUNED otherwise; the effect on real grasps is NOT measured (no real checkpoint)."""
+    reach, margin = float(reach), float(margin)
+    if not 0.0 < reach < float("inf"):
+        raise RuntimeError(f"grasp_self: reach must be finite and positive (got {reach})")
+    if not 0.0 <= margin < float("inf"):
+        raise RuntimeError(f"grasp_self: margin must be finite and >= 0 (got {margin})")
+    if not isinstance(table, SelfTable):
+        raise RuntimeError("grasp_self: table must be a SelfTable")
+    V = table.parts.n_verts
+    if not torch.is_tensor(hand_xyz) or hand_xyz.dim() != 3 or hand_xyz.shape[1] != V or topology.n_verts != V:
+        raise RuntimeError(f"grasp_self: the table has {V} vertices, the topology {topology.n_verts}, the hand "
+                           f"{tuple(hand_xyz.shape) if torch.is_tensor(hand_xyz) else type(hand_xyz)}")
+    labels, source = table.on(hand_xyz.device)
+    out = ops.grasp_self(hand_xyz.contiguous(), topology.faces, topology.vf_off, topology.vf_face, labels, source, table.parts.n_parts,
+                         table.pairs, reach * reach, margin)
+    return dict(zip(SELF_OUTPUTS, out))
+
+
+SELF_OUTPUTS = ("pen_count", "pen_depth", "gap_min", "pair_bits", "mask", "status")
+SELF_FIELDS = ("self_penetrating", "self_part_penetrating", "self_depth", "self_pairs", "self_clearance")
+
+
+def self_stats(out):
+    """Host side, float64, row by row, from ``grasp_self``'s dict (tensors or arrays): ``self_penetrating`` = the row's penetrating
+    vertices, ``self_part_penetrating`` = the P counts, ``self_depth`` = the largest depth over the parts in cm, ``self_pairs`` = the
+    sorted [a, b] pairs "a vertex of part a penetrates part b", ``self_clearance`` = sqrt of the smallest ``gap_min`` in cm (None
+    when no part has a source with a target).  Five lists; ``None`` where the row has no figure (status != 0)."""
+    cnt, dep, gap = _host(out["pen_count"], np.int64), _host(out["pen_depth"], np.float64), _host(out["gap_min"], np.float64)
+    bits = _host(out["pair_bits"], np.int64) & 0xffffffff
+    st = _host(out["status"], np.int64).reshape(-1)
+    if cnt.ndim != 2 or not (cnt.shape == dep.shape == gap.shape == bits.shape) or st.shape[0] != cnt.shape[0]:
+        raise RuntimeError("self_stats: pen_count, pen_depth, gap_min and pair_bits [B,P], one status per row")
+    P = cnt.shape[1]
+    res = {k: [] for k in SELF_FIELDS}
+    for c, d, g, w, s in zip(cnt, dep, gap, bits, st):
+        if s != 0:
+            for k in SELF_FIELDS:
+                res[k].append(None)
+            continue
+        res["self_penetrating"].append(int(c.sum()))
+        res["self_part_penetrating"].append([int(k) for k in c])
+        res["self_depth"].append(float(d.max()) * 100.0)
+        res["self_pairs"].append([[a, b] for a in range(P) for b in range(P) if (int(w[a]) >> b) & 1])
+        low = float(g.min())
+        res["self_clearance"].append(float(np.sqrt(low)) * 100.0 if np.isfinite(low) else None)
+    return res
+
+
+def self_class(out, max_verts):
+    """int32 [B] on the device, integer operations only, for ``torch.maximum`` with the class of ``select_keys``: 2 where the row of
+    ``grasp_self``'s output has no figure (status != 0), else 1 where more than ``max_verts`` vertices penetrate, else 0."""
+    cnt, status = out["pen_count"], out["status"]
+    over = cnt.sum(dim=1) > int(max_verts)
+    one, two = torch.ones_like(status), torch.full_like(status, 2)
+    return torch.where(status != 0, two, torch.where(over, one, torch.zeros_like(status))).to(torch.int32)
+
+
 SELECT_BY = ("penetration", "log_prob", "stability")
 
 

@@ -129,6 +129,26 @@ def build_parser(dataset: str) -> argparse.ArgumentParser:
     p.add_argument("--hand_parts", default=None,
                    help="a label table {\"order\": [names], \"parts\": [[vertex indices], ...]} to use instead of the packaged one "
                         "(the fingers first, the thumb as part 0)")
+    p.add_argument("--self_collision", type=int, default=0,
+                   help="1: every grasp's JSON gains \"self_penetrating\", \"self_part_penetrating\", \"self_depth\" (cm), \"self_pairs\" "
+                        "and \"self_clearance\" (cm): the vertices of a finger that lie behind the surface of another finger or of the palm "
+                        "-- the hand against itself, after any push-out (one kernel per call) -- and the run writes self_collision.json; a "
+                        "proximity figure on vertices only (a thin crossing between vertices is missed), calibrated against false alarms "
+                        "only and untuned otherwise, effect on real grasps not measured")
+    p.add_argument("--self_reach", type=float, default=0.01,
+                   help="--self_collision / --max_self_verts: a vertex is tested against its nearest vertex of another part when that lies "
+                        "within this many metres (untuned)")
+    p.add_argument("--self_margin", type=float, default=0.001,
+                   help="--self_collision / --max_self_verts: a vertex penetrates when it lies more than this many metres behind that "
+                        "vertex's tangent plane (untuned)")
+    p.add_argument("--self_seam", type=int, default=2,
+                   help="--self_collision / --max_self_verts: vertices within this many edge rings of a join of two parts never count "
+                        "(next to a join the test's sign is noise); 0 = every vertex counts")
+    p.add_argument("--self_palm", type=int, default=1,
+                   help="--self_collision / --max_self_verts: 1 = the fingers are tested against the palm too, 0 = against one another only")
+    p.add_argument("--max_self_verts", type=int, default=None,
+                   help="best-of-M: candidates with more than this many self-penetrating vertices rank after all others that touch the "
+                        "object (the class --max_penetration uses), whatever --select_by ranks by; needs --candidates (default: no guard)")
     p.add_argument("--refine_push", type=float, default=1.0, help="--refine_steps: step factor on the mean pull vector of the interior points")
     p.add_argument("--refine_pull", type=float, default=0.25,
                    help="--refine_steps: step factor on the mean pull vector of the points within 2 cm outside the hand")
@@ -195,6 +215,18 @@ def parse_args(dataset: str, argv: Optional[Sequence[str]] = None) -> argparse.N
         p.error(f"--need_thumb and --parts are 0 or 1 (got {args.need_thumb}, {args.parts})")
     if (args.min_fingers or args.need_thumb) and not args.candidates:
         p.error("--min_fingers and --need_thumb need --candidates (they rank candidates; --parts 1 alone writes the figures)")
+    if args.self_collision not in (0, 1) or args.self_palm not in (0, 1):
+        p.error(f"--self_collision and --self_palm are 0 or 1 (got {args.self_collision}, {args.self_palm})")
+    if not 0.0 < args.self_reach < float("inf"):
+        p.error(f"--self_reach must be finite and positive (got {args.self_reach})")
+    if not 0.0 <= args.self_margin < float("inf"):
+        p.error(f"--self_margin must be finite and >= 0 (got {args.self_margin})")
+    if args.self_seam < 0:
+        p.error(f"--self_seam must be >= 0 (got {args.self_seam})")
+    if args.max_self_verts is not None and args.max_self_verts < 0:
+        p.error(f"--max_self_verts must be >= 0 (got {args.max_self_verts})")
+    if args.max_self_verts is not None and not args.candidates:
+        p.error("--max_self_verts needs --candidates (it ranks candidates; --self_collision 1 alone writes the figures)")
     return args
 
 
@@ -392,6 +424,18 @@ def _hand_parts(net: GenNet, table):
     return cached[1]
 
 
+def _self_table(net: GenNet, hand_parts, seam: int, palm: bool):
+    """The ``contact.SelfTable`` of ``generate_for_objects``' self-collision switches: the label table of _hand_parts with the hand
+    model's faces, kept on the model so that a run derives the seam and uploads it once."""
+    from . import contact
+    parts = _hand_parts(net, hand_parts)
+    cached = getattr(net, "_self_table", None)
+    if cached is None or cached[0] is not parts or cached[1:3] != (int(seam), bool(palm)):
+        cached = (parts, int(seam), bool(palm), contact.SelfTable(parts, _hand_faces(net), seam=seam, palm=palm, n_fingers=min(5, parts.n_parts)))
+        object.__setattr__(net, "_self_table", cached)
+    return cached[3]
+
+
 def plan_calls(point_counts: Sequence[int], num_grasp: int, rows_per_call: int) -> List[List[int]]:
     """Positions of the objects of each batched call.  A call needs one point count: positions are grouped by it (groups in
     the order their first object appears, the given order inside a group) and every group is cut into calls of whole objects,
@@ -414,7 +458,8 @@ def _generate_call(net: GenNet, objs: Sequence[torch.Tensor], num_grasp: int, ro
                    refine_push: float = 1.0, refine_pull: float = 0.25, diversity: int = 0, stability: bool = False,
                    max_penetration: float = float("inf"), torque_length: float = 0.1,
                    volume: Optional[Dict[str, float]] = None, parts: Optional[Dict[str, object]] = None,
-                   refine_spin: float = 0.0, refine_curl: float = 0.0, refine_max_curl: float = 0.35) -> List[Dict[str, object]]:
+                   refine_spin: float = 0.0, refine_curl: float = 0.0, refine_max_curl: float = 0.35,
+                   slf: Optional[Dict[str, object]] = None) -> List[Dict[str, object]]:
     """One batched call: the ``num_grasp`` grasps of each of ``objs`` (all of one point count), row o * num_grasp + g = grasp g
     of object o.  Every step is row-independent and keyed per row, so each object's slice holds the bits of its own
     ``generate_for_object`` call.  With ``candidates`` = M the call generates M rows per object (exactly the grasps of a
@@ -432,7 +477,9 @@ def _generate_call(net: GenNet, objs: Sequence[torch.Tensor], num_grasp: int, ro
     its own unrotated cloud and ONE ``contact.grasp_volume`` runs over all rows of the call, after the push-out (_volume_launch); the
     rows' counts, depths and states ride in that copy as well (_volume_json).  With ``parts`` (``table``, ``threshold``, ``min_verts``,
     ``min_fingers``, ``need_thumb``) ONE ``contact.grasp_parts`` runs over all rows of the call, after the push-out too; its four
-    tensors ride in that copy and become the fields of _parts_json."""
+    tensors ride in that copy and become the fields of _parts_json.  With ``slf`` (``table``, ``reach``, ``margin``, ``max_verts``)
+    ONE ``contact.grasp_self`` runs over all rows of the call, after the push-out too -- the hands against themselves; its six
+    tensors ride in that copy and become the fields of _self_json."""
     dev = next(net.parameters()).device
     keep = num_grasp
     G, O = (candidates or num_grasp), len(objs)
@@ -484,18 +531,25 @@ def _generate_call(net: GenNet, objs: Sequence[torch.Tensor], num_grasp: int, ro
     if parts:                                                                      # after the push-out: the hands of the parameters written
         from . import contact
         prt = contact.grasp_parts(parts["table"], final.vertices, batch[:, :3].transpose(1, 2), parts["threshold"])
+    sco = None
+    if slf:                                                                        # after the push-out: the hands of the parameters written
+        from . import contact
+        sco = contact.grasp_self(_hand_topology(net, final.vertices.shape[1], dev), slf["table"], final.vertices, slf["reach"], slf["margin"])
     if candidates:
         return _select_call(net, batch, params, final.vertices, logp, err, O, G, keep, select_by, min_contact, want_logp, proxies,
                             np.concatenate(Rs), np.concatenate(angles), t, diverse_pool, diverse_space, refined, diversity, stability,
-                            max_penetration, torque_length, vol, volume, prt, parts)
+                            max_penetration, torque_length, vol, volume, prt, parts, sco, slf)
     ref_lists = {}
     div = _diversity_launch(params, O, G, diversity) if diversity else []
     prt_t = [prt[k] for k in PARTS_PIECES] if prt is not None else []             # last before the flag in the call's one copy
-    prt_h = None
+    slf_t = [sco[k] for k in SELF_PIECES] if sco is not None else []             # after the parts' pieces, before the flag
+    prt_h = slf_h = None
     if vol is not None and refined is None and not stability:                      # the volume alone: no score is computed
-        host, *vol_h, err_h = _host_copy([params] + [vol[k] for k in VOLUME_PIECES] + div + prt_t + [err])   # ONE device-to-host copy per call
+        host, *vol_h, err_h = _host_copy([params] + [vol[k] for k in VOLUME_PIECES] + div + prt_t + slf_t + [err])   # ONE device-to-host copy per call
         if int(err_h[0]) != 0:
             raise RuntimeError("generate_for_objects: object index out of range in transform_clouds")
+        if slf_t:
+            vol_h, slf_h = vol_h[:-len(slf_t)], vol_h[-len(slf_t):]
         if prt_t:
             vol_h, prt_h = vol_h[:-len(prt_t)], vol_h[-len(prt_t):]
         div_h = vol_h[len(VOLUME_PIECES):]
@@ -518,9 +572,11 @@ def _generate_call(net: GenNet, objs: Sequence[torch.Tensor], num_grasp: int, ro
             names = ["refine_" + k for k in REFINE_PIECES if k in refined] + names
             tensors.update({"refine_" + k: refined[k] for k in REFINE_PIECES if k in refined})
         vol_t = [vol[k] for k in VOLUME_PIECES] if vol is not None else []
-        host, *rest_h, err_h = _host_copy([params] + [tensors[k] for k in names] + vol_t + div + prt_t + [err])   # ONE device-to-host copy per call
+        host, *rest_h, err_h = _host_copy([params] + [tensors[k] for k in names] + vol_t + div + prt_t + slf_t + [err])   # ONE device-to-host copy per call
         if int(err_h[0]) != 0:
             raise RuntimeError("generate_for_objects: object index out of range in transform_clouds")
+        if slf_t:
+            rest_h, slf_h = rest_h[:-len(slf_t)], rest_h[-len(slf_t):]
         if prt_t:
             rest_h, prt_h = rest_h[:-len(prt_t)], rest_h[-len(prt_t):]
         by_name = dict(zip(names, rest_h))
@@ -532,10 +588,12 @@ def _generate_call(net: GenNet, objs: Sequence[torch.Tensor], num_grasp: int, ro
         if vol is not None:
             ref_lists.update(_volume_json(vol_h, volume["res"]))
         div_h = rest_h[len(by_name):]
-    elif div or prt_t:
-        host, *div_h, err_h = _host_copy([params] + div + prt_t + [err])           # ONE device-to-host copy per call
+    elif div or prt_t or slf_t:
+        host, *div_h, err_h = _host_copy([params] + div + prt_t + slf_t + [err])   # ONE device-to-host copy per call
         if int(err_h[0]) != 0:
             raise RuntimeError("generate_for_objects: object index out of range in transform_clouds")
+        if slf_t:
+            div_h, slf_h = div_h[:-len(slf_t)], div_h[-len(slf_t):]
         if prt_t:
             div_h, prt_h = div_h[:-len(prt_t)], div_h[-len(prt_t):]
     else:
@@ -554,6 +612,7 @@ def _generate_call(net: GenNet, objs: Sequence[torch.Tensor], num_grasp: int, ro
     lp_list = logp.cpu().numpy().tolist() if log_prob else None
     div_dicts = _diversity_dicts(diversity, div_h) if diversity else None
     prt_lists = _parts_json(prt_h, parts) if prt is not None else None
+    slf_lists = _self_json(slf_h) if sco is not None else None
     outs = []
     for o in range(O):
         lo, hi = o * G, (o + 1) * G
@@ -576,6 +635,9 @@ def _generate_call(net: GenNet, objs: Sequence[torch.Tensor], num_grasp: int, ro
         if prt is not None:
             extra["parts"] = {k: prt[k][lo:hi] for k in PARTS_PIECES}
             extra_json.update(_parts_slice(prt_lists, prt_h, lo, hi, parts))
+        if sco is not None:
+            extra["self"] = {k: sco[k][lo:hi] for k in SELF_PIECES}
+            extra_json.update({k: v[lo:hi] for k, v in slf_lists.items()})
         outs.append({**extra, "params": p_dev[o], "vertices": v_dev[o],
                      "json": {"recon_params": [[p] for p in p_list[lo:hi]],           # [[61 floats]] per grasp, as the reference
                               "R_list": Rt_list[lo:hi], "trans_list": [trans] * G, "r_list": r_list[lo:hi], **extra_json}})
@@ -658,6 +720,16 @@ def _parts_slice(lists: Dict[str, list], host: Sequence[np.ndarray], lo: int, hi
     return out
 
 
+SELF_PIECES = ("pen_count", "pen_depth", "gap_min", "pair_bits", "mask", "status")   # what a call's self-collision kernel leaves on the device
+
+
+def _self_json(host: Sequence[np.ndarray]) -> Dict[str, list]:
+    """The five per-grasp JSON lists of a call's rows from the host copies of the self-collision kernel's tensors: float64 on the
+    host, row by row (contact.self_stats); null where a row has no figure."""
+    from . import contact
+    return contact.self_stats(dict(zip(SELF_PIECES, host)))
+
+
 def _diversity_launch(kept: torch.Tensor, O: int, keep: int, clusters: int) -> List[torch.Tensor]:
     """``--diversity``: one ``ops.segment_kmeans`` over the call's kept parameters [O*keep,61], one segment per object, from evenly
     spaced starting rows; the device tensors whose host copies _diversity_dicts reads (counts, dist, iters_used, the error flag)."""
@@ -686,7 +758,8 @@ def _select_call(net: GenNet, batch: torch.Tensor, params: torch.Tensor, vertice
                  diversity: int = 0, stability: bool = False, max_penetration: float = float("inf"),
                  torque_length: float = 0.1, vol: Optional[Dict[str, torch.Tensor]] = None,
                  volume: Optional[Dict[str, float]] = None, prt: Optional[Dict[str, torch.Tensor]] = None,
-                 parts: Optional[Dict[str, object]] = None) -> List[Dict[str, object]]:
+                 parts: Optional[Dict[str, object]] = None, sco: Optional[Dict[str, torch.Tensor]] = None,
+                 slf: Optional[Dict[str, object]] = None) -> List[Dict[str, object]]:
     """Best-of-M for all the objects of a call together: the candidates' scores (one fused kernel), their keys, each object's
     ``keep`` best (one kernel), one ``index_select`` of the kept rows and one device-to-host copy.  Row o * M + c is candidate c of
     object o; nothing here depends on which objects share the call.  ``diverse_pool`` = P: each object's P best (the same kernel),
@@ -701,7 +774,10 @@ def _select_call(net: GenNet, batch: torch.Tensor, params: torch.Tensor, vertice
     rest; the kept rows' counts, depths and states ride along and become the three JSON fields of _volume_json.
     ``prt`` (contact.grasp_parts over all candidates) with ``parts`` = its settings: with ``min_fingers`` or ``need_thumb`` the class
     becomes ``maximum(cls, contact.parts_class(...))`` -- too few fingers on the object joins class 1, a row without a figure class 2 --
-    whatever ranks the rest; the kept rows' four tensors ride along and become the fields of _parts_json."""
+    whatever ranks the rest; the kept rows' four tensors ride along and become the fields of _parts_json.
+    ``sco`` (contact.grasp_self over all candidates) with ``slf`` = its settings: with ``max_verts`` = K the class becomes
+    ``maximum(cls, contact.self_class(sco, K))`` -- more than K self-penetrating vertices joins class 1, a row without a figure class
+    2 -- whatever ranks the rest; the kept rows' six tensors ride along and become the fields of _self_json."""
     from . import contact
     dev = params.device
     topo = _hand_topology(net, vertices.shape[1], dev)
@@ -719,6 +795,8 @@ def _select_call(net: GenNet, batch: torch.Tensor, params: torch.Tensor, vertice
         cls = torch.maximum(cls, torch.where(cnt < 0, torch.full_like(over, 2), over))
     if prt is not None and (parts["min_fingers"] or parts["need_thumb"]):
         cls = torch.maximum(cls, contact.parts_class(prt, parts["min_fingers"], parts["need_thumb"], parts["min_verts"]))
+    if sco is not None and slf["max_verts"] is not None:
+        cls = torch.maximum(cls, contact.self_class(sco, slf["max_verts"]))
     diverse = []
     if diverse_pool:
         pool = ops.segment_topk(cls.contiguous(), key.contiguous(), O, M, diverse_pool)   # [O,P] candidate indices, best first
@@ -737,7 +815,8 @@ def _select_call(net: GenNet, batch: torch.Tensor, params: torch.Tensor, vertice
     div = _diversity_launch(kept_p, O, keep, diversity) if diversity else []
     kept_vol = [vol[k].index_select(0, rows) for k in VOLUME_PIECES[:3]] + [vol["err"]] if vol is not None else []
     kept_prt = [prt[k].index_select(0, rows) for k in PARTS_PIECES] if prt is not None else []
-    host = _host_copy([sel] + [kept_p] + [kept_s[k] for k in names] + kept_r + kept_vol + kept_prt + diverse + div + [err])  # ONE device-to-host copy per call
+    kept_slf = [sco[k].index_select(0, rows) for k in SELF_PIECES] if sco is not None else []
+    host = _host_copy([sel] + [kept_p] + [kept_s[k] for k in names] + kept_r + kept_vol + kept_prt + kept_slf + diverse + div + [err])  # ONE device-to-host copy per call
     if int(host[-1][0]) != 0:
         raise RuntimeError("generate_for_objects: object index out of range in transform_clouds")
     sel_h, p_list = host[0], host[1].tolist()
@@ -757,8 +836,12 @@ def _select_call(net: GenNet, batch: torch.Tensor, params: torch.Tensor, vertice
         pat = 2 + len(names) + len(kept_r) + len(kept_vol)
         prt_h = host[pat:pat + len(kept_prt)]
         prt_lists = _parts_json(prt_h, parts)
+    slf_lists = None
+    if sco is not None:
+        sat = 2 + len(names) + len(kept_r) + len(kept_vol) + len(kept_prt)
+        slf_lists = _self_json(host[sat:sat + len(kept_slf)])
     if diverse_pool:
-        at = 2 + len(names) + len(kept_r) + len(kept_vol) + len(kept_prt)
+        at = 2 + len(names) + len(kept_r) + len(kept_vol) + len(kept_prt) + len(kept_slf)
         rank_h, gap_h, pool_err_h = host[at:at + 3]
         if int(pool_err_h[0]) != 0:
             raise RuntimeError("generate_for_objects: pool entry out of range in segment_diverse")
@@ -797,6 +880,10 @@ def _select_call(net: GenNet, batch: torch.Tensor, params: torch.Tensor, vertice
             extra["parts"] = {k: x[lo:hi] for k, x in zip(PARTS_PIECES, kept_prt)}
             extra["part_scores"] = {k: prt[k][o * M:(o + 1) * M] for k in PARTS_PIECES}                 # of ALL candidates
             extra_json = {**extra_json, **_parts_slice(prt_lists, prt_h, lo, hi, parts)}
+        if sco is not None:
+            extra["self"] = {k: x[lo:hi] for k, x in zip(SELF_PIECES, kept_slf)}
+            extra["self_scores"] = {k: sco[k][o * M:(o + 1) * M] for k in SELF_PIECES}                  # of ALL candidates
+            extra_json = {**extra_json, **{k: v[lo:hi] for k, v in slf_lists.items()}}
         outs.append({**extra, "params": p_dev[o], "vertices": v_dev[o], "candidate": sel[o],
                      "scores": {k: v[o * M:(o + 1) * M] for k, v in scores.items()},
                      "json": {"recon_params": [[p] for p in p_list[lo:hi]], "R_list": Rt_list[lo:hi], "trans_list": [trans] * keep,
@@ -814,7 +901,9 @@ def generate_for_objects(net: GenNet, objs: Sequence[torch.Tensor], num_grasp: i
                          volume_res: float = 0.001, max_volume: float = float("inf"), parts: bool = False,
                          part_threshold: float = 0.005, part_min_verts: int = 1, min_fingers: int = 0, need_thumb: bool = False,
                          hand_parts=None, refine_spin: float = 0.0, refine_curl: float = 0.0,
-                         refine_max_curl: float = 0.35) -> List[Dict[str, object]]:
+                         refine_max_curl: float = 0.35, self_collision: bool = False, self_reach: float = 0.01,
+                         self_margin: float = 0.001, self_seam: int = 2, self_palm: bool = True,
+                         max_self_verts: Optional[int] = None) -> List[Dict[str, object]]:
     """``num_grasp`` grasps for each of ``objs`` ([4,N] tensors) in batched calls that mix objects (plan_calls): one dict per
     object, in the order given, equal to ``generate_for_object(net, objs[i], num_grasp, rotate,
     np.random.default_rng([seed, object_indices[i]]), seed=seed, object_index=object_indices[i], proxies=proxies)`` (and the same
@@ -903,7 +992,28 @@ def generate_for_objects(net: GenNet, objs: Sequence[torch.Tensor], num_grasp: i
     gains "fingers_in_contact", "part_contact" and "part_dist" (cm) per grasp (``contact.part_stats``, float64 on the host; null
     without a figure) and "hand_contact_map", per vertex the number of the object's grasps that touch there.  They ride in the
     call's one device-to-host copy.  A proximity figure with an untuned threshold: no contact-force model, effect on real grasps not
-    measured.  Without these switches nothing of it runs."""
+    measured.  Without these switches nothing of it runs.
+    Self-collision (``self_collision=True``, or ``max_self_verts`` = K together with ``candidates``): every call launches ONE
+    ``contact.grasp_self`` over all its rows -- the hands against themselves, the fingers of ``hand_parts`` against one another and,
+    with ``self_palm``, against the remaining parts; ``self_reach`` / ``self_margin`` in metres, ``self_seam`` in edge rings
+    (``contact.SelfTable``) -- after the push-out has re-posed the hands if there is one.  Candidates with more than K penetrating
+    vertices join class 1, rows without a figure class 2 (``contact.self_class``), whatever ``select_by`` ranks by: a guard only,
+    nothing is ranked by it.  Each dict gains ``self`` (the kernel's six tensors of its grasps; with ``candidates`` also
+    ``self_scores``, those of ALL candidates) and ``json`` gains "self_penetrating", "self_part_penetrating", "self_depth" (cm),
+    "self_pairs" and "self_clearance" (cm) per grasp (``contact.self_stats``, float64 on the host; null without a figure).  A
+    proximity figure on vertices only, calibrated against false alarms only: untuned, effect on real grasps not measured.  Without
+    these switches nothing of it runs."""
+    self_args = None
+    if self_collision or max_self_verts is not None:
+        if not 0.0 < float(self_reach) < float("inf") or not 0.0 <= float(self_margin) < float("inf"):
+            raise RuntimeError(f"generate_for_objects: self_reach must be finite and positive, self_margin finite and >= 0 "
+                               f"(got {self_reach}, {self_margin})")
+        if int(self_seam) < 0:
+            raise RuntimeError(f"generate_for_objects: self_seam must be >= 0 (got {self_seam})")
+        if max_self_verts is not None and (int(max_self_verts) < 0 or not candidates):
+            raise RuntimeError(f"generate_for_objects: max_self_verts must be >= 0 and needs candidates (got {max_self_verts})")
+        self_args = dict(table=_self_table(net, hand_parts, int(self_seam), bool(self_palm)), reach=float(self_reach),
+                         margin=float(self_margin), max_verts=None if max_self_verts is None else int(max_self_verts))
     parts_args = None
     if parts or min_fingers or need_thumb:
         from . import contact
@@ -976,7 +1086,7 @@ def generate_for_objects(net: GenNet, objs: Sequence[torch.Tensor], num_grasp: i
         res = _generate_call(net, [objs[p] for p in call], num_grasp, rotate, seed, [object_indices[p] for p in call], proxies,
                              temperature, top_k, log_prob, candidates, select_by, min_contact, diverse_pool, diverse_space, refine_steps,
                              refine_push, refine_pull, diversity, stability, max_penetration, torque_length, vol_args, parts_args,
-                             float(refine_spin), float(refine_curl), float(refine_max_curl))
+                             float(refine_spin), float(refine_curl), float(refine_max_curl), self_args)
         for p, r in zip(call, res):
             out[p] = r
     return out
@@ -1007,7 +1117,9 @@ def main(dataset: str, argv: Optional[Sequence[str]] = None) -> List[str]:
                            f"(got {(hi - lo) * args.num_grasp})")
     want_volume = bool(args.volume) or args.max_volume < float("inf")
     want_parts = bool(args.parts) or args.min_fingers > 0 or bool(args.need_thumb)
-    if args.rows_per_call > 0 or args.candidates or args.refine_steps or args.diversity or args.stability or want_volume or want_parts:
+    want_self = bool(args.self_collision) or args.max_self_verts is not None
+    if (args.rows_per_call > 0 or args.candidates or args.refine_steps or args.diversity or args.stability or want_volume or want_parts
+            or want_self):
         # grouped calls (best-of-M, push-out, the diversity statistic and the stability proxy always: --rows_per_call 0 is then one
         # object per call)
         rows_per_call, per_object = max(1, args.rows_per_call), (args.candidates or args.num_grasp)
@@ -1030,6 +1142,10 @@ def main(dataset: str, argv: Optional[Sequence[str]] = None) -> List[str]:
         if want_parts:
             selection.update(parts=True, part_threshold=args.part_threshold, part_min_verts=args.part_min_verts,
                              min_fingers=args.min_fingers, need_thumb=bool(args.need_thumb), hand_parts=args.hand_parts)
+        if want_self:
+            selection.update(self_collision=True, self_reach=args.self_reach, self_margin=args.self_margin, self_seam=args.self_seam,
+                             self_palm=bool(args.self_palm), max_self_verts=args.max_self_verts, hand_parts=args.hand_parts)
+        self_rows: Dict[int, tuple] = {}                                           # --self_collision: every object's (counts, pairs) per grasp
         curl_rows: Dict[int, tuple] = {}                                           # --refine_curl: every object's (curled, reverted) counts
         part_rows: Dict[int, tuple] = {}                                           # --parts: every object's (fingers per grasp, contact map)
         vol_rows: Dict[int, list] = {}                                             # --volume: every object's (voxels, cm^3, cm) per grasp
@@ -1063,6 +1179,8 @@ def main(dataset: str, argv: Optional[Sequence[str]] = None) -> List[str]:
                     vol_rows[p] = list(zip(*(out["json"][k] for k in ("volume_voxels", "penetration_volume", "penetration_depth"))))
                 if want_parts:
                     part_rows[p] = (out["json"]["fingers_in_contact"], out["json"]["hand_contact_map"])
+                if want_self:
+                    self_rows[p] = (out["json"]["self_penetrating"], out["json"]["self_pairs"])
             del outs, out
         written = [paths[p] for p in sorted(paths)]                                # object order, whatever the grouping
         if args.diversity and kept:
@@ -1112,6 +1230,22 @@ def main(dataset: str, argv: Optional[Sequence[str]] = None) -> List[str]:
                 json.dump(stat, f)
             print(f"rank {rank}: hand-side contact of {len(fingers)} grasps at {args.part_threshold} m: mean fingers in contact "
                   f"{stat['mean_fingers_in_contact']}, histogram 0..5 {stat['fingers_histogram']}")
+        if want_self:
+            # the run's figures over this rank's grasps in object order: integers, but for the mean (an exactly rounded sum)
+            table = _self_table(net, args.hand_parts, args.self_seam, bool(args.self_palm))
+            counts = [c for p in sorted(self_rows) for c in self_rows[p][0] if c is not None]
+            pairs = [tuple(ab) for p in sorted(self_rows) for g in self_rows[p][1] if g is not None for ab in g]
+            names = table.parts.names
+            stat = {"parts": names, "reach": args.self_reach, "margin": args.self_margin, "seam": args.self_seam,
+                    "palm": int(args.self_palm), "seam_vertices": table.n_seam, "grasps": len(counts),
+                    "share_penetrating": sum(1 for c in counts if c > 0) / len(counts) if counts else None,
+                    "mean_penetrating": math.fsum(counts) / len(counts) if counts else None,
+                    "pair_histogram": [[pairs.count((a, b)) for b in range(len(names))] for a in range(len(names))]}
+            name = "self_collision.json" if world == 1 else f"self_collision_rank{rank}.json"
+            with open(os.path.join(args.out_dir, name), "w") as f:
+                json.dump(stat, f)
+            print(f"rank {rank}: self-collision of {len(counts)} grasps at reach {args.self_reach} m, margin {args.self_margin} m: share "
+                  f"with a penetrating vertex {stat['share_penetrating']}, mean count {stat['mean_penetrating']}")
     else:
         for gi, (name, obj) in enumerate(objs[lo:hi], start=lo):                   # --rows_per_call 0: one call per object
             torch.cuda.synchronize(device)

@@ -829,6 +829,71 @@ def grasp_parts(hand: Tensor, part_of_vertex: Tensor, n_parts: int, obj: Tensor,
     return part_min, part_count, mask, status, vert_dist, vert_idx
 
 
+GRASP_SELF_MAX_P = 32               # csrc/grasp_self.hip: GSELF_MAX_P (one bit per part)
+
+
+def grasp_self(hand: Tensor, faces: Tensor, vf_off: Tensor, vf_face: Tensor, part_of_vertex: Tensor, source_of_vertex: Tensor,
+               n_parts: int, pairs, reach2: float, margin: float):
+    """Self-collision of hands in one fused kernel (dvq_grasp_self; the definition is in include/dvq.h): hand [B,V,3] contiguous,
+    the topology of ``contact.face_csr`` on the device, ``part_of_vertex`` and ``source_of_vertex`` int32 [V] on the device (a label
+    outside [0, n_parts) is "no part"; a vertex with source 0 never counts, it remains a target), ``pairs``: ``n_parts`` words on
+    the HOST (a sequence of ints or an integer array), bit b of ``pairs[a]`` = part a's vertices are tested against part b's;
+    ``reach2`` a squared distance, ``margin`` a distance.  Returns ``(pen_count [B,P] i32, pen_depth [B,P] f32, gap_min [B,P] f32,
+    pair_bits [B,P] i32, mask [B,W] i32, status [B] i32)``: per part the number of penetrating vertices, the largest depth (+0.0
+    without one), the smallest squared distance of a source vertex to its targets (+inf without one) and the parts hit, a bit per
+    vertex (W = (V + 31) // 32), status 1 for a row with a non-finite coordinate (-1 / NaN / NaN / 0 / 0 there)."""
+    for t, n in ((hand, "hand"), (faces, "faces"), (vf_off, "vf_off"), (vf_face, "vf_face"), (part_of_vertex, "part_of_vertex"),
+                 (source_of_vertex, "source_of_vertex")):
+        if not isinstance(t, Tensor):
+            raise RuntimeError(f"grasp_self: {n} must be a tensor")
+    _f32(hand, "hand")
+    for t, n in ((faces, "faces"), (vf_off, "vf_off"), (vf_face, "vf_face")):
+        if t.dtype != torch.int32 or not t.is_contiguous():
+            raise RuntimeError(f"grasp_self: {n} must be contiguous int32")
+    if hand.dim() != 3 or hand.shape[2] != 3 or not hand.is_contiguous():
+        raise RuntimeError("grasp_self: hand must be contiguous [B,V,3]")
+    B, V = hand.shape[0], hand.shape[1]
+    if not 1 <= V <= GRASP_SCORES_MAX_V:
+        raise RuntimeError(f"grasp_self: need 1 <= V <= {GRASP_SCORES_MAX_V} (got V={V})")
+    if faces.dim() != 2 or faces.shape[1] != 3 or vf_off.numel() != V + 1 or vf_face.numel() != faces.numel():
+        raise RuntimeError("grasp_self: CSR does not match the mesh")
+    n_parts = int(n_parts)
+    if not 1 <= n_parts <= GRASP_SELF_MAX_P:
+        raise RuntimeError(f"grasp_self: need 1 <= n_parts <= {GRASP_SELF_MAX_P} (got {n_parts})")
+    for t, n in ((part_of_vertex, "part_of_vertex"), (source_of_vertex, "source_of_vertex")):
+        if t.dtype != torch.int32 or not t.is_contiguous() or tuple(t.shape) != (V,):
+            raise RuntimeError(f"grasp_self: {n} must be contiguous int32 [{V}] (got {t.dtype} {tuple(t.shape)})")
+    words = [int(w) for w in (pairs.tolist() if hasattr(pairs, "tolist") else pairs)]
+    if len(words) != n_parts:
+        raise RuntimeError(f"grasp_self: pairs must hold {n_parts} words, one per part (got {len(words)})")
+    for a, w in enumerate(words):
+        if not 0 <= w < 1 << n_parts:
+            raise RuntimeError(f"grasp_self: pairs[{a}] = {w:#x} names a part at or above n_parts = {n_parts} (or is negative)")
+        if (w >> a) & 1:
+            raise RuntimeError(f"grasp_self: pairs[{a}] tests part {a} against itself")
+    reach2, margin = float(reach2), float(margin)
+    if not 0.0 < reach2 < float("inf"):
+        raise RuntimeError(f"grasp_self: reach2 must be finite and positive (got {reach2})")
+    if not 0.0 <= margin < float("inf"):
+        raise RuntimeError(f"grasp_self: margin must be finite and >= 0 (got {margin})")
+    dev = _require_gpu(hand, faces, vf_off, vf_face, part_of_vertex, source_of_vertex)
+    lib = _lib.load()
+    W = (V + 31) // 32
+    pen_count = torch.empty(B, n_parts, dtype=torch.int32, device=dev)
+    pen_depth = torch.empty(B, n_parts, dtype=torch.float32, device=dev)
+    gap_min = torch.empty(B, n_parts, dtype=torch.float32, device=dev)
+    pair_bits = torch.empty(B, n_parts, dtype=torch.int32, device=dev)
+    mask = torch.empty(B, W, dtype=torch.int32, device=dev)
+    status = torch.empty(B, dtype=torch.int32, device=dev)
+    host_pairs = (C.c_uint32 * n_parts)(*words)                # read by the library before the call returns
+    with torch.cuda.device(dev):
+        check(lib.dvq_grasp_self(hand.data_ptr(), faces.data_ptr(), vf_off.data_ptr(), vf_face.data_ptr(), V, part_of_vertex.data_ptr(),
+                                 source_of_vertex.data_ptr(), n_parts, C.addressof(host_pairs), B, reach2, margin,
+                                 pen_count.data_ptr(), pen_depth.data_ptr(), gap_min.data_ptr(), pair_bits.data_ptr(), mask.data_ptr(),
+                                 status.data_ptr(), _stream(dev)), "dvq_grasp_self")
+    return pen_count, pen_depth, gap_min, pair_bits, mask, status
+
+
 GRASP_VOLUME_MAX_F = 8192          # csrc/grasp_volume.hip: GV_MAX_F
 GRASP_VOLUME_MAX_LOOPS = 64        # GV_MAX_L
 GRASP_VOLUME_MAX_PLANES = 8192     # GV_MAX_P: per object

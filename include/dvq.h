@@ -43,7 +43,7 @@ typedef enum {
 /* Entry points added since 10 without touching a struct or a signature of it (a compatible extension: bindings of 10 keep
  * working, the version stays): dvq_pixelcnn_sample_ctl, dvq_grasp_scores, dvq_segment_topk, dvq_segment_diverse,
  * dvq_grasp_refine, dvq_segment_kmeans, dvq_grasp_wrench, dvq_grasp_volume, dvq_grasp_parts, dvq_grasp_refine_rigid,
- * dvq_grasp_refine_fingers. */
+ * dvq_grasp_refine_fingers, dvq_grasp_self. */
 int dvq_abi_version(void);
 const char* dvq_last_error(void);
 /* number of visible HIP devices, or -1; does not create a context */
@@ -597,6 +597,48 @@ int dvq_grasp_parts(const float* hand /* [B,V,3] */, const int32_t* part_of_vert
                     float contact_threshold, float* part_min /* [B,P] */, int32_t* part_count /* [B,P] */, int32_t* mask /* [B,W] */,
                     int32_t* status /* [B] */, float* vert_dist /* [B,V] or NULL */, int32_t* vert_idx /* [B,V] or NULL */,
                     dvq_stream_t stream);
+/* Self-collision of grasps: the hand against ITSELF -- for every vertex of a part its nearest vertex among the parts it is tested
+ * against, the interior test of dvq_grasp_scores against that vertex's tangent plane, and from those, per part, the number of
+ * penetrating vertices, the largest depth, the smallest clearance and which parts were hit, and a bit per vertex -- in ONE kernel, one
+ * workgroup of 256 threads per grasp.  The decoder builds a hand from separately sampled codes (thumb, four fingers, palm) and the
+ * scores above look at hand against object only: two fingers passing through each other show in none of them.  A PROXIMITY figure in
+ * the style of the reference's get_interior (utils/utils_loss.py), NOT a mesh-mesh intersection: vertices only, so a thin crossing
+ * between vertices is missed; reach, margin and the seam are the caller's, calibrated only against false alarms on 48 posed hands of
+ * the real hand model and untuned otherwise; the effect on real grasps is NOT MEASURED (no real checkpoint was available).
+ * Inputs: hand [B,V,3] contiguous fp32; faces / vf_off / vf_face: the topology as dvq_grasp_scores takes it; part_of_vertex int32 [V]
+ * on the device: the part of every vertex, a value outside [0, P) means "no part" (not an error); source_of_vertex int32 [V] on the
+ * device: != 0 where the vertex may count as a SOURCE (the caller clears the vertices next to a join of two parts, where v - u is
+ * tangent to the surface and the sign of the test is noise; they remain targets); P, the number of parts; pairs uint32 [P] on the
+ * HOST (read before the call returns): bit b of pairs[a] = part a's vertices are tested against part b's; reach2, a squared distance;
+ * margin, a distance.
+ * Per grasp, when all 3 V coordinates are finite (fp32, fma = the only fused operations):
+ *   1. n[u]: the vertex normals exactly as dvq_grasp_scores defines them.
+ *   2. a = part_of_vertex[v]; a vertex whose label is outside [0, P) is neither source nor target.  Vertex u is a target of v iff its
+ *      label b is in [0, P) and bit b of pairs[a] is set.  dx = hand[v].x - hand[u].x, dy, dz likewise; d(v,u) = fma(dz, dz, fma(dy, dy,
+ *      dx * dx)).  d[v] = the minimum of d(v,u) over the targets; idx[v] = the lowest u that attains it.  With no target: d[v] = +inf,
+ *      idx[v] = -1.
+ *   3. depth[v] = fma(wz, n[idx].z, fma(wy, n[idx].y, wx * n[idx].x)) with w = hand[idx] - hand[v] per component: the expression of
+ *      the interior test.
+ *   4. pen[v] = source_of_vertex[v] != 0 && idx[v] >= 0 && d[v] < reach2 && depth[v] > margin.
+ *   5. per part a, over the vertices labelled a: pen_count[a] = the number with pen[v]; pen_depth[a] = the largest depth[v] over those,
+ *      +0.0f if there are none; gap_min[a] = the smallest d[v] over the vertices with source_of_vertex != 0, +inf if there are none;
+ *      pair_bits[a] = the OR of 1 << part_of_vertex[idx[v]] over the vertices with pen[v].
+ *   6. mask: bit (v & 31) of word (v >> 5) is pen[v]; the unused high bits of the last word are 0.  W = (V + 31) / 32 words per
+ *      grasp.  status = 0.
+ * A grasp with a non-finite coordinate has no figure: status = 1, pen_depth and gap_min NaN, pen_count -1, pair_bits and mask 0;
+ * other grasps are unaffected.
+ * Only minima, maxima, integer counts and bits are produced -- no float sum -- so nothing depends on a reduction order, and a grasp's
+ * outputs depend on neither B nor its row.
+ * Outputs: pen_count int32 [B,P]; pen_depth fp32 [B,P]; gap_min fp32 [B,P]; pair_bits int32 [B,P]; mask int32 [B,W]; status int32 [B].
+ * B >= 0, 1 <= V <= 2048, 1 <= P <= 32, no null pointer, reach2 finite and > 0, margin finite and >= 0, no bit a in pairs[a] (a part
+ * against itself) and no bit at or above P; anything else is DVQ_EINVAL, nothing launched.  (B = 0 returns DVQ_OK before any pointer
+ * is looked at, as in dvq_grasp_parts.) */
+int dvq_grasp_self(const float* hand /* [B,V,3] */, const int32_t* faces, const int32_t* vf_off, const int32_t* vf_face, int V,
+                   const int32_t* part_of_vertex /* [V] device */, const int32_t* source_of_vertex /* [V] device, != 0: may count */,
+                   int P, const uint32_t* pairs /* [P] HOST: bit b of pairs[a] = test part a's vertices against part b */,
+                   int64_t B, float reach2, float margin,
+                   int32_t* pen_count /* [B,P] */, float* pen_depth /* [B,P] */, float* gap_min /* [B,P] */,
+                   int32_t* pair_bits /* [B,P] */, int32_t* mask /* [B,W] */, int32_t* status /* [B] */, dvq_stream_t stream);
 /* Penetration volume of grasps: the voxels, on a lattice of spacing h, whose centres lie both inside the (sealed) hand mesh and
  * inside the convex hull of the object -- an INTEGER per grasp, defined to the bit -- and the depth of the deepest hand vertex inside
  * the hull, in ONE kernel, one workgroup of 256 threads per grasp.  The counterpart of the reference's intersection_eval
