@@ -146,6 +146,12 @@ struct GemmSrc {
     const int64_t* arow;
 };
 
+// No-overlap rule: what a launch writes (out, pre, partial, part_val, part_idx) overlaps nothing it reads -- no source's A / W / Wp /
+// arow, not bias, wscale, cls, label, acc_hi, acc_lo, acc_row -- with ONE exception: resid may be out element for element (same
+// pointer, ldr == ldo; a lane reads only the residual elements it writes itself).  The fp16-plane kernels load every epilogue
+// operand of a wave's block before the block's first store and rely on it.  Callers (pixelcnn.hip, pointnet.hip, mano.hip,
+// misc.hip / gemm_f32.hip's dvq_linear and dvq_mlp3): outputs are workspace or caller buffers of their own, operands are weights,
+// labels, class tables and state buffers written by EARLIER launches; the PixelCNN's residual is the level below its output.
 struct GemmParams {
     GemmSrc src[DVQ_MAX_SRC];
     int nsrc;

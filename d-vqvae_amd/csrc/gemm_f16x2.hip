@@ -124,6 +124,84 @@ __device__ __forceinline__ void f16x2_store_gate(const GemmParams& p, long m, in
     *reinterpret_cast<f32x4*>(p.out + m * p.ldo + c) = o;
 }
 
+__device__ __forceinline__ f32x4 ld4(const float* q) { return *reinterpret_cast<const f32x4*>(q); }
+__device__ __forceinline__ void st4(float* q, const f32x4& v) { *reinterpret_cast<f32x4*>(q) = v; }
+
+// Epilogue of a wave whose 64 x (16 NJ) block lies wholly inside the output, on the 16-byte path: every operand is loaded before
+// the first store, in at most two round trips where the block-by-block code below takes one per operand and block (a store through
+// out / pre may alias any operand for all the compiler knows, so no load moves above a store on its own, and vmcnt counts loads
+// and stores alike: each of those waits also drained the block before).  Trip 1: the wave's scale and bias quads -- they depend on
+// the column only -- and the four labels; hi + lo * 2^-11 of all blocks is formed under it, which halves the live accumulators.
+// Trip 2: the class rows' quads, which need the labels (the residual quads need nothing and join trip 1 where the registers allow).
+// Then arithmetic and stores, no wait that drains a store between them.  The arithmetic per
+// element and its order are f16x2_store_block's / f16x2_store_gate's.  No-overlap rule: at GemmParams.
+template <int EPI, int NJ>
+__device__ __forceinline__ void f16x2_epilogue_inside(const GemmParams& p, f32x4 (&hi)[NJ][4], f32x4 (&lo)[NJ][4], long m0w, int n0w, int c0w,
+                                                      int lane) {
+    static_assert(EPI == EPI_BIAS || EPI == EPI_RESID || (EPI == EPI_GATE && NJ == 4), "store epilogues with operands");
+    const long m = m0w + (lane & 15);                       // row of block i: m + 16 i
+    const int l4 = 4 * (lane >> 4), nl = n0w + l4;          // column of block jn: nl + 16 jn
+    f32x4 ws[NJ], bq[NJ], aq[NJ][4];
+    const float* crow[4];
+#pragma unroll
+    for (int jn = 0; jn < NJ; ++jn) ws[jn] = ld4(p.wscale + nl + 16 * jn);
+    if (p.bias) {
+#pragma unroll
+        for (int jn = 0; jn < NJ; ++jn) bq[jn] = ld4(p.bias + nl + 16 * jn);
+    }
+    if constexpr (EPI == EPI_GATE) {
+        if (p.cls) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) crow[i] = p.cls + (long)p.label[m + 16 * i] * p.N + nl;
+        }
+    }
+#pragma unroll
+    for (int jn = 0; jn < NJ; ++jn)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) hi[jn][i] = hi[jn][i] + lo[jn][i] * LO_SCALE;
+    if constexpr (EPI == EPI_RESID) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int jn = 0; jn < NJ; ++jn) aq[jn][i] = ld4(p.resid + (m + 16 * i) * p.ldr + nl + 16 * jn);
+    } else if constexpr (EPI == EPI_GATE) {
+        if (p.cls) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+#pragma unroll
+                for (int jn = 0; jn < NJ; ++jn) aq[jn][i] = ld4(crow[i] + 16 * jn);
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        if constexpr (EPI == EPI_GATE) {
+#pragma unroll
+            for (int jn = 0; jn < 2; ++jn) {                // tanh columns jn, their sigmoid partners 32 further: jn + 2
+                f32x4 a = hi[jn][i] * ws[jn], g = hi[jn + 2][i] * ws[jn + 2];
+                if (p.bias) { a += bq[jn]; g += bq[jn + 2]; }
+                if (p.pre) {
+                    st4(p.pre + (m + 16 * i) * p.ldpre + nl + 16 * jn, a);
+                    st4(p.pre + (m + 16 * i) * p.ldpre + nl + 16 * jn + 32, g);
+                }
+                if (p.cls) { a += aq[jn][i]; g += aq[jn + 2][i]; }
+                f32x4 o;
+#pragma unroll
+                for (int q = 0; q < 4; ++q) o[q] = gate_act(a[q], g[q]);
+                st4(p.out + (m + 16 * i) * p.ldo + c0w + l4 + 16 * jn, o);
+            }
+        } else {
+#pragma unroll
+            for (int jn = 0; jn < NJ; ++jn) {
+                f32x4 v = hi[jn][i] * ws[jn];
+                if (p.bias) v += bq[jn];
+                if constexpr (EPI == EPI_RESID) v += aq[jn][i];
+                if (p.relu) { v[0] = relu_nan(v[0]); v[1] = relu_nan(v[1]); v[2] = relu_nan(v[2]); v[3] = relu_nan(v[3]); }
+                st4(p.out + (m + 16 * i) * p.ldo + nl + 16 * jn, v);
+            }
+        }
+    }
+}
+
 // accumulators of a wave's 64 x (16 NJ) block from a stored state (GemmParams::acc_*), or zero
 template <int NJ, bool INIT>
 __device__ __forceinline__ void f16x2_init_acc(const GemmParams& p, f32x4 (&hi)[NJ][4], f32x4 (&lo)[NJ][4], long m0w, int n0w, int lane) {
@@ -135,6 +213,23 @@ __device__ __forceinline__ void f16x2_init_acc(const GemmParams& p, f32x4 (&hi)[
         return;
     }
     const int lr = lane & 15, lc = lane >> 4;
+    if (p.acc_hi && m0w + 64 <= p.M && n0w + 16 * NJ <= p.N) {   // the block wholly inside (wave-uniform): the four row indices, then
+        long r[4];                                               // every quad of the state in flight at once -- one wait, not twenty
+#pragma unroll
+        for (int i = 0; i < 4; ++i) r[i] = m0w + i * 16 + lr;
+        if (p.acc_row) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) r[i] = p.acc_row[r[i]];
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int jn = 0; jn < NJ; ++jn) {
+                hi[jn][i] = ld4(p.acc_hi + r[i] * p.ldacc + n0w + jn * 16 + 4 * lc);
+                lo[jn][i] = ld4(p.acc_lo + r[i] * p.ldacc + n0w + jn * 16 + 4 * lc);
+            }
+        return;
+    }
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         const long m = m0w + i * 16 + lr;
@@ -158,6 +253,13 @@ template <int EPI, int NJ = 4>
 __device__ __forceinline__ void f16x2_epilogue(const GemmParams& p, f32x4 (&hi)[NJ][4], f32x4 (&lo)[NJ][4], long m0w, int n0w, int c0w,
                                                int lane) {
     static_assert(NJ == 4 || EPI != EPI_GATE, "the gate pairs a wave's tanh columns with their partners 32 columns further");
+    if constexpr (EPI == EPI_BIAS || EPI == EPI_RESID || (EPI == EPI_GATE && NJ == 4)) {
+        const bool vec_ok = EPI == EPI_GATE || ((p.N % 4 == 0) && (p.ldo % 4 == 0) && (EPI != EPI_RESID || p.ldr % 4 == 0));
+        if (vec_ok && m0w + 64 <= p.M && n0w + 16 * NJ <= p.N) {      // wave-uniform; the rest: ragged rows / columns, 4-byte rows
+            f16x2_epilogue_inside<EPI, NJ>(p, hi, lo, m0w, n0w, c0w, lane);
+            return;
+        }
+    }
     const int lr = lane & 15, lc = lane >> 4;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
@@ -296,33 +398,36 @@ __global__ __launch_bounds__(512, 1) void gemm_f16x2_pp_kernel(const GemmParams 
 
     PpCursorA ca;
     PpCursorW<NJ> cw;
-    ca.open(p, 0, m0, tid);
     cw.open(p, 0, n0, wave, lane);
     const int a_dst = (tid >> 2) * 64 + 16 * ((tid & 3) ^ swz16(tid >> 2));
     f32x4 alo, ahi;
-    auto load_a = [&]() {
-        alo = *reinterpret_cast<const f32x4*>(ca.a_ptr);
-        ahi = *reinterpret_cast<const f32x4*>(ca.a_ptr + 4);
+    auto load_a = [&](f32x4& qlo, f32x4& qhi) {
+        qlo = *reinterpret_cast<const f32x4*>(ca.a_ptr);
+        qhi = *reinterpret_cast<const f32x4*>(ca.a_ptr + 4);
         ca.advance(p, m0, tid);
     };
-    auto store_a = [&](char* stage) {
+    auto store_a = [&](char* stage, const f32x4& qlo, const f32x4& qhi) {
         h8 p1, p2;
-        split2(alo, ahi, p1, p2);
+        split2(qlo, qhi, p1, p2);
         *reinterpret_cast<h8*>(stage + a_dst) = p1;
         *reinterpret_cast<h8*>(stage + A_PL + a_dst) = p2;
     };
-    // prologue: tiles 0 and 1 staged, tile 2's activations in registers
-    load_a();
+    // prologue: tiles 0 and 1 staged, tile 2's activations in registers.  Everything is issued before the one wait: both weight DMAs
+    // first (they wait for nothing, not even for a source's arow entry), then the activations of all three tiles -- the accumulators
+    // do not exist yet, the registers are free.  What still costs a round trip of its own is the arow entry of each source opened.
     cw.issue(smem_c, wave);
     cw.advance(p, n0, wave, lane);
-    store_a(smem_c);
     if (T > 1) {
-        load_a();
         cw.issue(smem_c + STAGE, wave);
         cw.advance(p, n0, wave, lane);
-        store_a(smem_c + STAGE);
     }
-    if (T > 2) load_a();
+    ca.open(p, 0, m0, tid);
+    f32x4 a0lo, a0hi, a1lo, a1hi;
+    load_a(a0lo, a0hi);
+    if (T > 1) load_a(a1lo, a1hi);
+    if (T > 2) load_a(alo, ahi);
+    store_a(smem_c, a0lo, a0hi);
+    if (T > 1) store_a(smem_c + STAGE, a1lo, a1hi);
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
 
@@ -361,10 +466,10 @@ __global__ __launch_bounds__(512, 1) void gemm_f16x2_pp_kernel(const GemmParams 
             // (timing-only ablations of the diagnostics build, DVQ_GEMM_ABL: 2 no MFMAs, 8 no weight DMA, 16 no split + plane store, 32 no
             // activation loads, 64 half the fragment reads, 128 none, 256 no epilogue, 512 one barrier per K-tile; results are garbage;
             // tools/gemm_skeleton.py turns them into nanoseconds per K-tile)
-            if (!(DVQ_DIAG_ON && (p.dbg_abl & 16))) store_a(nx);   // tile t + 2
+            if (!(DVQ_DIAG_ON && (p.dbg_abl & 16))) store_a(nx, alo, ahi);   // tile t + 2
             if (!(DVQ_DIAG_ON && (p.dbg_abl & 8))) cw.issue(nx, wave);
             cw.advance(p, n0, wave, lane);
-            if (t + 3 < T && !(DVQ_DIAG_ON && (p.dbg_abl & 32))) load_a();   // tile t + 3
+            if (t + 3 < T && !(DVQ_DIAG_ON && (p.dbg_abl & 32))) load_a(alo, ahi);   // tile t + 3
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // fragments in registers (and the plane writes retired) before the phase ends
         __builtin_amdgcn_s_barrier();
@@ -404,8 +509,11 @@ __global__ __launch_bounds__(512, 1) void gemm_f16x2_pp_kernel(const GemmParams 
 // launches (the PixelCNN's 1x1 residual conv and head, K = 512: 46 us per launch = 187 TFLOP/s; 100 MB of HBM traffic for 8.6 GFLOP).
 // Bit-identical, and no faster: residual GEMMs 22.6 -> 23.3 ms per step, gated GEMMs 192 -> 212 ms when forced on everything.  A
 // workgroup of those launches moves ~1 MB (activations 256 KB, weight planes 512 KB from L2, residual in, tile out) in 46 us =
-// 22 GB/s per CU, the rate one CU sustains from beyond L2 (MI355X_MICROARCH.md: 23-33 GB/s): they are bound by the per-CU memory
-// path, not by the overlap of prologue and epilogue, and the smaller tile reads every activation row twice as often.
+// 22 GB/s per CU, the rate one CU sustains from beyond L2 (MI355X_MICROARCH.md: 23-33 GB/s), and the smaller tile reads every
+// activation row twice as often.  (That read them as bound by the per-CU memory path.  Part of it was latency, not rate: their
+// epilogue waited for every operand of every 16 x 16 block on its own, ~50 dependent round trips per wave, and workgroups that start
+// together reach their epilogues together whatever the tile.  With the operands loaded before the first store -- f16x2_epilogue_inside
+// -- the residual GEMMs went 20.5 -> 17.8 ms per step on the tile they have.)
 template <int EPI, int NJ, bool INIT>
 int launch_pp(const GemmParams& p, hipStream_t stream) {
     constexpr size_t smem = NJ == 4 ? PP_SMEM : PP_SMEM_N128;
