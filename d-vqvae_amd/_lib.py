@@ -118,6 +118,10 @@ SIGNATURES = {
     "dvq_mano_workspace_bytes": (C.c_size_t, [C.c_int64]),
     "dvq_mano_forward": (C.c_int, [C.POINTER(ManoModel), c_f32p, C.c_int64, c_f32p, C.c_int64, c_f32p, C.c_int64, c_f32p,
                                    C.c_int64, C.c_int64, c_f32p, C.c_int, c_f32p, C.c_void_p, C.c_size_t, c_stream]),
+    "dvq_mano_backward_workspace_bytes": (C.c_size_t, [C.c_int64]),
+    "dvq_mano_backward": (C.c_int, [C.POINTER(ManoModel), c_f32p, c_f32p, C.c_int64, c_f32p, C.c_int64, c_f32p, C.c_int64, c_f32p,
+                                    C.c_int64, C.c_int64, c_f32p, C.c_int, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, C.c_void_p,
+                                    C.c_size_t, c_stream]),
     "dvq_copy_cols": (C.c_int, [c_f32p, C.c_int64, C.c_int64, C.c_int, c_f32p, C.c_int64, c_stream]),
     "dvq_assemble61": (C.c_int, [c_f32p, c_f32p, C.c_int64, c_f32p, c_stream]),
     "dvq_prof_enable": (C.c_int, [C.c_int]),

@@ -244,6 +244,10 @@ struct DvqKnobs {
     int pixelcnn_tables;  // DVQ_PIXELCNN_TABLES: 1 (default): what depends on the class label only is evaluated once per class; 0: per row
 };
 const DvqKnobs& dvq_knobs();
+// mano.hip: the pose kernel and the blendshape GEMM of one chunk of nb <= 16 384 samples (pointers at the chunk's first row):
+// X [nb,160], V [nb,2336], A [nb,16,3,4], optional joints [nb,16,3].  The forward skins them, the backward (mano_grad.hip) rebuilds them.
+int dvq_mano_chunk_state(const dvq_mano_model* m, const float* betas, long ldb, const float* pose, long ldp, const float* global_orient,
+                         long ldg, const float* transl, long ldt, long nb, float* X, float* V, float* A, float* joints, hipStream_t st);
 // simple helpers implemented in misc.hip
 int dvq_launch_gather_rows(const float* table, const int64_t* idx, long idx_stride, long M, int K, int D,
                            float* out, long ldo, int32_t* err_flag, hipStream_t stream);

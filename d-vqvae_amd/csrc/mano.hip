@@ -141,6 +141,29 @@ __global__ __launch_bounds__(256) void mano_skin_kernel(const float* __restrict_
 
 }  // namespace
 
+// The first two launches of one chunk (nb <= CHUNK samples, pointers at the chunk's first row): X [nb,160], A [nb,16,3,4], optional
+// joints, and V [nb,2336] = X . blend_w^T + v_template.  dvq_mano_forward skins them; dvq_mano_backward (mano_grad.hip) rebuilds
+// the forward state with the same two launches instead of keeping it alive.
+int dvq_mano_chunk_state(const dvq_mano_model* m, const float* betas, long ldb, const float* pose, long ldp, const float* global_orient,
+                         long ldg, const float* transl, long ldt, long nb, float* X, float* V, float* A, float* joints, hipStream_t st) {
+    {
+        DVQ_PROF("mano_pose", (double)nb * 2.0e4, (double)nb * (55 + XK + NJ * 12) * 4, st);
+        DVQ_LAUNCH(mano_pose_kernel, dim3((unsigned)((nb + WPB - 1) / WPB)), dim3(64 * WPB), 0, st, *m, betas, ldb, pose, ldp, global_orient, ldg,
+                   transl, ldt, nb, X, A, joints);
+    }
+    DVQ_CHECK_LAUNCH("mano_pose");
+    GemmParams g = {};
+    g.src[0] = GemmSrc{X, m->blend_w, XK, XK, XK, m->planes_kind, m->blend_w_planes, (long)NV * 3 * XK};
+    g.wscale = m->blend_w_scale;
+    g.nsrc = 1;
+    g.M = nb;
+    g.N = NV * 3;
+    g.bias = m->v_template;
+    g.out = V;
+    g.ldo = VLD;
+    return dvq_launch_gemm(g, EPI_BIAS, st);
+}
+
 extern "C" size_t dvq_mano_workspace_bytes(int64_t B) {
     const long c = B < CHUNK ? (B > 0 ? B : 1) : CHUNK;
     return dvq_round_up((size_t)c * XK * 4, 256) + dvq_round_up((size_t)c * VLD * 4, 256) + dvq_round_up((size_t)c * NJ * 12 * 4, 256);
@@ -172,23 +195,8 @@ extern "C" int dvq_mano_forward(const dvq_mano_model* m, const float* betas, int
     float* A = (float*)p;
     for (long b0 = 0; b0 < B; b0 += CHUNK) {
         const long nb = B - b0 < CHUNK ? B - b0 : CHUNK;
-        {
-            DVQ_PROF("mano_pose", (double)nb * 2.0e4, (double)nb * (55 + XK + NJ * 12) * 4, st);
-            DVQ_LAUNCH(mano_pose_kernel, dim3((unsigned)((nb + WPB - 1) / WPB)), dim3(64 * WPB), 0, st, *m, betas + b0 * ldb, (long)ldb,
-                       pose + b0 * ldp, (long)ldp, global_orient ? global_orient + b0 * ldg : nullptr, (long)ldg,
-                       transl ? transl + b0 * ldt : nullptr, (long)ldt, nb, X, A, joints ? joints + b0 * 48 : nullptr);
-        }
-        DVQ_CHECK_LAUNCH("mano_pose");
-        GemmParams g = {};
-        g.src[0] = GemmSrc{X, m->blend_w, XK, XK, XK, m->planes_kind, m->blend_w_planes, (long)NV * 3 * XK};
-        g.wscale = m->blend_w_scale;
-        g.nsrc = 1;
-        g.M = nb;
-        g.N = NV * 3;
-        g.bias = m->v_template;
-        g.out = V;
-        g.ldo = VLD;
-        DVQ_PROPAGATE(dvq_launch_gemm(g, EPI_BIAS, st));
+        DVQ_PROPAGATE(dvq_mano_chunk_state(m, betas + b0 * ldb, ldb, pose + b0 * ldp, ldp, global_orient ? global_orient + b0 * ldg : nullptr, ldg,
+                                           transl ? transl + b0 * ldt : nullptr, ldt, nb, X, V, A, joints ? joints + b0 * 48 : nullptr, st));
         {
             DVQ_PROF("mano_skin", (double)nb * NV * (NJ * 24 + 18), (double)nb * NV * 3 * 8, st);
             DVQ_LAUNCH(mano_skin_kernel, dim3((NV + 255) / 256, (unsigned)nb), dim3(256), 0, st, m->weights, V, A,

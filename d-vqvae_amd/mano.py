@@ -1,7 +1,9 @@
 """Host mirror of the third-party ``mano`` layer the reference calls (``mano.load(model_path=..., model_type='mano',
 use_pca=True, num_pca_comps=45, flat_hand_mean=True)``, gen_diverse_grasp_obman.py:355-360): same call
 signature (``layer(betas=, global_orient=, hand_pose=, transl=).vertices``), arithmetic in dvq_mano_forward.
-"parity unpinned": that package is not installed/vendored; the algorithm is the published smplx-style LBS."""
+"parity unpinned": that package is not installed/vendored; the algorithm is the published smplx-style LBS.
+Like that layer it is differentiable: when grad is enabled and an input requires it, the outputs carry a ``grad_fn`` whose backward is
+dvq_mano_backward (no double backward); every other call runs dvq_mano_forward alone."""
 from __future__ import annotations
 
 import pickle
@@ -73,6 +75,37 @@ def synthetic_mano_arrays(seed: int = 7) -> Dict[str, np.ndarray]:
     return out
 
 
+class _ManoFunction(torch.autograd.Function):
+    """``ops.mano_forward`` as autograd sees it: the backward is ``ops.mano_backward`` (dvq_mano_backward), which recomputes the
+    forward state from the four inputs -- they are all that is saved.  No double backward."""
+
+    @staticmethod
+    def forward(ctx, packed, channel_major, want_joints, betas, hand_pose, global_orient, transl):
+        ctx.packed, ctx.channel_major = packed, channel_major
+        ctx.present = (global_orient is not None, transl is not None)
+        ctx.set_materialize_grads(False)                    # an output the loss does not use arrives as None, not as zeros
+        ctx.save_for_backward(*[t for t in (betas, hand_pose, global_orient, transl) if t is not None])
+        return ops.mano_forward(packed, betas, hand_pose, global_orient, transl, channel_major=channel_major, want_joints=want_joints)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_verts, grad_joints=None):
+        saved = list(ctx.saved_tensors)
+        betas, hand_pose = saved[0], saved[1]
+        global_orient = saved[2] if ctx.present[0] else None
+        transl = saved[-1] if ctx.present[1] else None
+        needs = tuple(ctx.needs_input_grad[3:7])
+        if grad_verts is None and grad_joints is None:
+            return (None,) * 7
+        grads = ops.mano_backward(ctx.packed, betas, hand_pose, global_orient, transl, grad_verts, grad_joints,
+                                  channel_major=ctx.channel_major, needs=needs)
+        return (None, None, None) + tuple(grads)
+
+
+def _wants_grad(*ts) -> bool:
+    return torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in ts)
+
+
 class ManoLayer(nn.Module):
     def __init__(self, arrays: Dict[str, np.ndarray], use_pca: bool = True, num_pca_comps: int = 45,
                  flat_hand_mean: bool = True):
@@ -95,6 +128,10 @@ class ManoLayer(nn.Module):
         return cls(arrays, flat_hand_mean=False)
 
     def forward(self, betas, global_orient=None, hand_pose=None, transl=None, **_):
+        if _wants_grad(betas, hand_pose, global_orient, transl):        # differentiable: gradients through dvq_mano_backward
+            verts, joints = _ManoFunction.apply(self._packed, False, True, betas, hand_pose, global_orient, transl)
+            return types.SimpleNamespace(vertices=verts, joints=joints, betas=betas, global_orient=global_orient,
+                                         hand_pose=hand_pose)
         verts, joints = ops.mano_forward(self._packed, betas.contiguous(), hand_pose.contiguous(),
                                          None if global_orient is None else global_orient.contiguous(),
                                          None if transl is None else transl.contiguous(), want_joints=True)
@@ -103,6 +140,8 @@ class ManoLayer(nn.Module):
 
     def vertices_channel_major(self, betas, hand_pose):
         """[B,3,778] vertices for zero global pose: the layout the hand PointNet consumes (gen_net.py:116-120)."""
+        if _wants_grad(betas, hand_pose):
+            return _ManoFunction.apply(self._packed, True, False, betas, hand_pose, None, None)
         return ops.mano_forward(self._packed, betas, hand_pose, channel_major=True)
 
 

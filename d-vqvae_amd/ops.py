@@ -563,6 +563,55 @@ def mano_forward(packed, betas: Tensor, hand_pose: Tensor, global_orient: Option
     return (verts, joints) if want_joints else verts
 
 
+def mano_backward(packed, betas: Tensor, hand_pose: Tensor, global_orient: Optional[Tensor] = None,
+                  transl: Optional[Tensor] = None, grad_verts: Optional[Tensor] = None, grad_joints: Optional[Tensor] = None,
+                  channel_major: bool = False, needs: Sequence[bool] = (True, True, True, True)):
+    """Vector-Jacobian product of ``mano_forward`` (dvq_mano_backward): the forward call's inputs, ``grad_verts`` [B,778,3] (or
+    [B,3,778] when channel_major) and / or ``grad_joints`` [B,16,3] -> (grad_betas [B,10], grad_hand_pose [B,45], grad_global_orient
+    [B,3], grad_transl [B,3]); an entry of ``needs`` that is false gives ``None`` in its place.  The forward state is recomputed."""
+    lib = _lib.load()
+    dev = _require_gpu(betas, hand_pose, global_orient, transl, grad_verts, grad_joints)
+    packed.to(dev)
+    B = betas.shape[0]
+    pb, ldb = _rows(_f32(betas, "betas"), "betas")
+    pp, ldp = _rows(_f32(hand_pose, "hand_pose"), "hand_pose")
+    if betas.shape[1] != 10 or hand_pose.shape[1] != 45 or hand_pose.shape[0] != B:
+        raise RuntimeError("mano_backward: expected betas [B,10] and hand_pose [B,45]")
+    for name, t in (("global_orient", global_orient), ("transl", transl)):
+        if t is not None and tuple(t.shape) != (B, 3):
+            raise RuntimeError(f"mano_backward: expected {name} [B,3], got {tuple(t.shape)}")
+    pg = ldg = pt = ldt = 0
+    if global_orient is not None:
+        pg, ldg = _rows(_f32(global_orient, "global_orient"), "global_orient")
+    if transl is not None:
+        pt, ldt = _rows(_f32(transl, "transl"), "transl")
+    if grad_verts is None and grad_joints is None:
+        raise RuntimeError("mano_backward: grad_verts and grad_joints are both None")
+    vshape = (B, 3, 778) if channel_major else (B, 778, 3)
+    for name, t, shape in (("grad_verts", grad_verts, vshape), ("grad_joints", grad_joints, (B, 16, 3))):
+        if t is not None and tuple(_f32(t, name).shape) != shape:
+            raise RuntimeError(f"mano_backward: expected {name} {list(shape)}, got {tuple(t.shape)}")
+    if len(needs) != 4:
+        raise RuntimeError("mano_backward: needs = (betas, hand_pose, global_orient, transl)")
+    grad_verts = None if grad_verts is None else grad_verts.contiguous()
+    grad_joints = None if grad_joints is None else grad_joints.contiguous()
+    outs = [torch.empty(B, n, dtype=torch.float32, device=dev) if need else None for n, need in zip((10, 45, 3, 3), needs)]
+    if B == 0:                                              # empty tensors have null data pointers, which the ABI refuses
+        return tuple(outs)
+    ptr = lambda t: None if t is None else t.data_ptr()
+    nws = lib.dvq_mano_backward_workspace_bytes(B)
+    ws = workspace(nws, dev)
+    with torch.cuda.device(dev):
+        check(lib.dvq_mano_backward(C.byref(packed.cstruct), packed.tensors["blend_wt"].data_ptr(), pb, ldb, pp, ldp, pg or None, ldg,
+                                    pt or None, ldt, B, ptr(grad_verts), 1 if channel_major else 0, ptr(grad_joints),
+                                    *[ptr(o) for o in outs], ws.data_ptr(), ws.numel(), _stream(dev)), "dvq_mano_backward")
+    if _out_of_range(getattr(packed, "kind", None), *outs):
+        from . import packing
+        with no_range_check(), packing.gemm_kind_as(_lib.PLANES_BF16X3):     # the recomputed blendshapes once more on the six-product images
+            return mano_backward(packed, betas, hand_pose, global_orient, transl, grad_verts, grad_joints, channel_major, needs)
+    return tuple(outs)
+
+
 # ------------------------------------------------------------------------------------------ data movement
 def copy_cols(src: Tensor, out: Tensor) -> Tensor:
     lib = _lib.load()

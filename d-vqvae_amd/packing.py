@@ -362,6 +362,9 @@ class PackedMano(_Packed):
         blend[:, :10] = sh.reshape(778 * 3, 10)
         blend[:, 10:145] = po.reshape(778 * 3, 135)
         t["blend_w"] = tt(blend)
+        blend_t = np.zeros((160, 2336))                   # the backward's operand (dvq_mano_backward): dX = dV @ blend_wt^T, K = 2336 = 73 * 32
+        blend_t[:, :2334] = blend.T
+        t["blend_wt"] = tt(blend_t)
         t["j_template"] = tt(jr @ vt)
         t["j_shapedirs"] = tt(np.einsum("jv,vkl->ljk", jr, sh).reshape(10, 48))
         t["weights"] = tt(f64("weights"))

@@ -43,7 +43,7 @@ typedef enum {
 /* Entry points added since 10 without touching a struct or a signature of it (a compatible extension: bindings of 10 keep
  * working, the version stays): dvq_pixelcnn_sample_ctl, dvq_grasp_scores, dvq_segment_topk, dvq_segment_diverse,
  * dvq_grasp_refine, dvq_segment_kmeans, dvq_grasp_wrench, dvq_grasp_volume, dvq_grasp_parts, dvq_grasp_refine_rigid,
- * dvq_grasp_refine_fingers, dvq_grasp_self. */
+ * dvq_grasp_refine_fingers, dvq_grasp_self, dvq_mano_backward_workspace_bytes, dvq_mano_backward. */
 int dvq_abi_version(void);
 const char* dvq_last_error(void);
 /* number of visible HIP devices, or -1; does not create a context */
@@ -297,6 +297,32 @@ int dvq_mano_forward(const dvq_mano_model* m_host, const float* betas, int64_t l
                      int64_t ldp, const float* global_orient, int64_t ldg, const float* transl,
                      int64_t ldt, int64_t B, float* verts, int layout, float* joints /* optional [B,16,3] */,
                      void* workspace, size_t workspace_bytes, dvq_stream_t stream);
+
+/* Backward pass of the layer: the vector-Jacobian product of dvq_mano_forward.  The forward call's inputs (same row strides), the
+ * upstream gradients grad_verts ([B,778,3], or [B,3,778] with layout 1) and / or grad_joints [B,16,3] (at least one non-null) ->
+ * grad_betas [B,10], grad_pose [B,45], grad_global_orient [B,3], grad_transl [B,3], dense; each is optional (null: not wanted).
+ * blend_wt [160][2336]: blend_w transposed, rows 145..159 and columns 2334, 2335 zero (16-byte aligned; the model struct is unchanged).
+ * Nothing of the forward call is kept: per 16 384 samples the forward's pose kernel and blendshape GEMM run again (X, A, V), then
+ *   skin backward   one workgroup per sample: dV[v] = T_r^T g[v] with T = sum_j w[v][j] A[j] as in the forward -> dV [B,2336], pad
+ *                   columns zero; dA[j][i][c] = sum_v w[v][j] g[v][i] [V[v];1][c] and sum_v g[v]: every sum by one thread over
+ *                   v = 0, 1, .. 777 in this order, term (w g) x, with a compensated (Kahan) accumulator;
+ *   GEMM            dX [B,160] = dV . blend_wt^T on the matrix cores (operands split exactly into bf16 pieces on the fly, fp32
+ *                   accumulation; the fp32 kernel with DVQ_GEMM=fp32), the forward's row tiling;
+ *   pose backward   one wave per sample: A = [Gr | Gt - Gr J] and the chain Gr_j = Gr_p R_j, Gt_j = Gr_p (J_j - J_p) + Gt_p backwards
+ *                   (j = 15 .. 0), grad_joints entering at Gt; dR_j += dX[10 + 9 (j - 1) ..] for j >= 1; Rodrigues backwards with
+ *                   angle = ||r + 1e-8|| and 1 - cos a taken as 2 sin^2(a/2), forwards and backwards (the literal form loses the K^2
+ *                   term's coefficient at angles near 1e-4); grad_global_orient = d full_pose[0:3], grad_pose = comps . d full_pose[3:48],
+ *                   grad_betas = dX[0:10] + j_shapedirs . dJ, grad_transl = sum_v g[v] + sum_j grad_joints[j].
+ * With grad_verts null only the pose backward runs.  No atomics, every sum in a fixed order: a row's gradient does not depend on the
+ * batch it is in.  transl is accepted for symmetry with the forward (no gradient depends on its value).
+ * Refused without a launch: null / unaligned workspace or blend_wt, bad strides, layout or parents, both upstream gradients null
+ * (DVQ_EINVAL); a short workspace (DVQ_EWORKSPACE).  B == 0: DVQ_OK.  workspace: dvq_mano_backward_workspace_bytes(B). */
+size_t dvq_mano_backward_workspace_bytes(int64_t B);
+int dvq_mano_backward(const dvq_mano_model* m_host, const float* blend_wt, const float* betas, int64_t ldb, const float* pose,
+                      int64_t ldp, const float* global_orient, int64_t ldg, const float* transl, int64_t ldt, int64_t B,
+                      const float* grad_verts, int layout, const float* grad_joints /* optional [B,16,3] */,
+                      float* grad_betas, float* grad_pose, float* grad_global_orient, float* grad_transl,
+                      void* workspace, size_t workspace_bytes, dvq_stream_t stream);
 
 /* ------------------------------------------------------------------ small data movement
  * out[m, col0:col0+W] = src[m, 0:W]  (concatenations of gen_net.py:109,121) */
