@@ -794,3 +794,199 @@ def select_keys(scores, select_by, min_contact, log_prob=None, max_penetration=f
             raise RuntimeError("select_keys: select_by='log_prob' needs the grasps' log_prob")
         return torch.where(torch.isnan(log_prob), 2, 0).to(torch.int32), -log_prob
     raise RuntimeError(f"select_keys: select_by must be one of {SELECT_BY} (got {select_by!r})")
+
+
+# ------------------------------------------------------------------------------------------ gradient refinement (the reference's TTT loop)
+TTT_W_PEN = 840.0                  # utils/loss.py TTT_loss and gen_diverse_grasp_obman.py:69-94: 7 * (120 * penetration)
+TTT_W_CON = 7500.0                 # 1 * (2.5 * 3000 * contact); both are the reference's constants, untuned here
+TTT_LR = 6.25e-6                   # SGD(lr=6.25e-6, momentum=0.8), 300 steps in the reference
+TTT_MOMENTUM = 0.8
+TTT_MAX_STEPS = 1000
+
+
+class ContactTargets:
+    """The hand vertices the contact term of ``ttt_terms`` measures distances to (the reference's ``prior_idx`` subset of
+    ``Contact_loss``): built from a list of vertex indices or from a boolean mask of ``n_verts`` entries; ``from_json`` reads a JSON
+    file that holds a list of indices.  ``on(device)`` is the int32 flag vector [n_verts] the kernel takes (uploaded once per device).
+    An empty set is refused; "every vertex" is ``targets=None`` at the call, not an object of this class."""
+
+    def __init__(self, spec, n_verts=778, device=None):
+        a = np.asarray(spec.detach().cpu() if torch.is_tensor(spec) else spec)
+        n_verts = int(n_verts)
+        if a.dtype == np.bool_:
+            if a.ndim != 1 or a.size != n_verts:
+                raise RuntimeError(f"ContactTargets: a mask must have {n_verts} entries (got shape {a.shape})")
+            idx = np.flatnonzero(a)
+        else:
+            if a.ndim != 1 or (a.size and a.dtype.kind not in "iu"):
+                raise RuntimeError("ContactTargets: expected a 1-D list of vertex indices or a boolean mask")
+            idx = np.unique(a.astype(np.int64))
+        if idx.size == 0:
+            raise RuntimeError("ContactTargets: the set is empty (every vertex is targets=None)")
+        if idx.min() < 0 or idx.max() >= n_verts:
+            raise RuntimeError(f"ContactTargets: a vertex index lies outside [0, {n_verts})")
+        self.n_verts = n_verts
+        self.indices = idx.astype(np.int64)
+        self.flags = np.zeros(n_verts, np.int32)
+        self.flags[idx] = 1
+        self._dev = {}
+        if device is not None:
+            self.on(torch.device(device))
+
+    def on(self, device):
+        """The int32 flag vector on ``device`` (uploaded once per device)."""
+        key = str(device)
+        if key not in self._dev:
+            self._dev[key] = torch.from_numpy(self.flags).to(device)
+        return self._dev[key]
+
+    @classmethod
+    def from_json(cls, path, n_verts=778, device=None):
+        """A JSON file holding a list of vertex indices."""
+        with open(path) as f:
+            table = json.load(f)
+        if not isinstance(table, list) or not all(isinstance(v, int) and not isinstance(v, bool) for v in table):
+            raise RuntimeError(f"ContactTargets.from_json: {path} must hold a list of vertex indices")
+        return cls(np.asarray(table, np.int64), n_verts, device)
+
+
+def _ttt_flags(what, targets, topology, hand_xyz):
+    if targets is None:
+        return None
+    if not isinstance(targets, ContactTargets):
+        raise RuntimeError(f"{what}: targets must be a ContactTargets or None")
+    if targets.n_verts != topology.n_verts or hand_xyz.shape[1] != targets.n_verts:
+        raise RuntimeError(f"{what}: the targets name {targets.n_verts} vertices, the topology {topology.n_verts}, the hand "
+                           f"{hand_xyz.shape[1]}")
+    return targets.on(hand_xyz.device)
+
+
+class _TttFunction(torch.autograd.Function):
+    """``ops.grasp_ttt`` as autograd sees it: the forward launch computes no gradient; the backward is a second launch with the
+    upstream gradients as the two weights, which recomputes the forward from the hand and the cloud -- they are all that is saved.
+    The masks and indices are constants (the reference indexes with booleans); no gradient for the cloud; no double backward."""
+
+    @staticmethod
+    def forward(ctx, topology, flags, threshold, hand_xyz, obj_xyz):
+        ctx.topology, ctx.flags, ctx.threshold = topology, flags, threshold
+        ctx.set_materialize_grads(False)                    # an output the loss does not use arrives as None: weight 0
+        ctx.save_for_backward(hand_xyz, obj_xyz)
+        pen, con, n_in, n_ct, _ = ops.grasp_ttt(hand_xyz, topology.faces, topology.vf_off, topology.vf_face, obj_xyz, flags,
+                                                contact_threshold=threshold)
+        ctx.mark_non_differentiable(n_in, n_ct)
+        return pen, con, n_in, n_ct
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_pen, g_con, _g_in=None, _g_ct=None):
+        if (g_pen is None and g_con is None) or not ctx.needs_input_grad[3]:
+            return (None,) * 5
+        hand_xyz, obj_xyz = ctx.saved_tensors
+        B = hand_xyz.shape[0]
+        weight = lambda g: (torch.zeros(B, dtype=torch.float32, device=hand_xyz.device) if g is None
+                            else g.to(torch.float32).contiguous())
+        topo = ctx.topology
+        grad = ops.grasp_ttt(hand_xyz, topo.faces, topo.vf_off, topo.vf_face, obj_xyz, ctx.flags, weight(g_pen), weight(g_con),
+                             want_grad=True, contact_threshold=ctx.threshold)[4]
+        return None, None, None, grad, None
+
+
+def ttt_terms(topology, hand_xyz, obj_xyz, targets=None, contact_threshold=0.02 ** 2):
+    """The two terms of the reference's test-time loss (utils/loss.py: TTT_loss), unweighted and per grasp, from ONE fused kernel
+    (ops.grasp_ttt; the definition is in include/dvq.h under dvq_grasp_ttt): ``penetration`` [B] f32, ``n_interior`` [B] i32 and
+    ``n_contact`` [B] i32 are the bits of ``grasp_scores``; ``contact_sum`` [B] f32 is the sum, over the object points within the
+    threshold of the hand, of the squared distance to the nearest vertex of ``targets`` (a ``ContactTargets``; None = every vertex) --
+    the hand-centric ``Contact_loss`` before its mean.  When grad is enabled and ``hand_xyz`` requires it, ``penetration`` and
+    ``contact_sum`` are differentiable with respect to the hand (once; the masks and nearest-vertex indices are constants, nothing
+    flows to the cloud): the backward is a second launch of the kernel.  Otherwise only the forward launch runs."""
+    flags = _ttt_flags("ttt_terms", targets, topology, hand_xyz)
+    hand = hand_xyz.contiguous()
+    if torch.is_grad_enabled() and hand.requires_grad:
+        pen, con, n_in, n_ct = _TttFunction.apply(topology, flags, float(contact_threshold), hand, obj_xyz.detach())
+    else:
+        pen, con, n_in, n_ct, _ = ops.grasp_ttt(hand, topology.faces, topology.vf_off, topology.vf_face, obj_xyz, flags,
+                                                contact_threshold=contact_threshold)
+    return {"penetration": pen, "contact_sum": con, "n_interior": n_in, "n_contact": n_ct}
+
+
+def _ttt_combine(pen, con, n_ct, w_pen, w_con):
+    scale = torch.full_like(pen, float(w_con)) / n_ct.clamp(min=1).to(pen.dtype)       # fp32 division, row by row
+    return pen * float(w_pen) + con * scale
+
+
+def ttt_loss(topology, hand_xyz, obj_xyz, targets=None, w_pen=TTT_W_PEN, w_con=TTT_W_CON, contact_threshold=0.02 ** 2):
+    """[B]: ``w_pen * penetration + w_con * contact_sum / max(n_contact, 1)`` of ``ttt_terms`` -- with the defaults (the reference's
+    7 * 120 and 1 * 2.5 * 3000) and B = 1, the way the reference calls it, this is utils/loss.py's TTT_loss without the ContactNet
+    term.  DEVIATION for B > 1: every row is normalised by its OWN contact count (the reference's mean runs over the batch's contact
+    points and its penetration term divides by B), which keeps a grasp's loss and gradient independent of the batch it is in.  A row
+    without a contact point has contact term 0 (the reference divides 0 by 0 there).  Differentiable through ``ttt_terms``."""
+    t = ttt_terms(topology, hand_xyz, obj_xyz, targets, contact_threshold)
+    return _ttt_combine(t["penetration"], t["contact_sum"], t["n_contact"], w_pen, w_con)
+
+
+def ttt_value_and_grad(topology, hand_xyz, obj_xyz, targets=None, w_pen=TTT_W_PEN, w_con=TTT_W_CON, contact_threshold=0.02 ** 2,
+                       want_grad=True):
+    """``(ttt_loss [B], d sum(ttt_loss) / d hand_xyz [B,V,3])`` from ONE launch (the kernel divides the contact weight by the row's
+    contact count itself): what ``refine_ttt`` calls per step.  The bits of ``ttt_loss`` and of its autograd gradient.  No graph is
+    recorded.  ``want_grad=False`` skips the gradient phase and returns None for it."""
+    flags = _ttt_flags("ttt_value_and_grad", targets, topology, hand_xyz)
+    hand = hand_xyz.detach().contiguous()
+    B = hand.shape[0]
+    wp = torch.full((B,), float(w_pen), dtype=torch.float32, device=hand.device)
+    wc = torch.full((B,), float(w_con), dtype=torch.float32, device=hand.device)
+    pen, con, _, n_ct, grad = ops.grasp_ttt(hand, topology.faces, topology.vf_off, topology.vf_face, obj_xyz.detach(), flags, wp, wc,
+                                            mean_contact=True, want_grad=want_grad, contact_threshold=contact_threshold)
+    return _ttt_combine(pen, con, n_ct, w_pen, w_con), grad
+
+
+def refine_ttt(layer, topology, params61, obj_xyz, steps, lr=TTT_LR, momentum=TTT_MOMENTUM, targets=None, w_pen=TTT_W_PEN,
+               w_con=TTT_W_CON, keep_best=True):
+    """Gradient refinement of grasps, the reference's test-time loop (gen_diverse_grasp_obman.py:69-94): ``steps`` steps of
+    ``SGD(lr, momentum)`` on the [B,61] MANO parameters (betas 10 | global_orient 3 | hand_pose 45 | transl 3) down ``ttt_loss``.
+    Per step: ``layer`` poses the hands, ``ttt_value_and_grad`` gives the loss and its gradient at the vertices in one launch,
+    ``ops.mano_backward`` carries it to the 61 columns, and the update is torch.optim.SGD's (buf = g on the first step,
+    buf = momentum * buf + g after it, p -= lr * buf).  Returns ``params`` [B,61], ``loss0`` [B] (iterate 0), ``loss`` [B] and
+    ``iter`` [B] i32 (of the iterate returned).  With ``keep_best`` every row keeps its iterate of lowest loss among 0 .. steps, the
+    earliest among equals; without it the last iterate is returned, as the reference does.  A row whose loss is NaN at iterate 0,
+    or whose parameters become non-finite, comes back as given with ``iter = 0``.  ``steps = 0`` returns the input's bits.  Every
+    row is refined on its own (``ttt_loss``'s per-row normalisation): the result does not depend on the batch.  The constants are
+    the reference's and untuned here."""
+    steps = int(steps)
+    if not 0 <= steps <= TTT_MAX_STEPS:
+        raise RuntimeError(f"refine_ttt: steps must lie between 0 and {TTT_MAX_STEPS} (got {steps})")
+    lr, momentum = float(lr), float(momentum)
+    if not (0.0 <= lr < float("inf") and 0.0 <= momentum < 1.0):
+        raise RuntimeError(f"refine_ttt: lr must be finite and >= 0, momentum in [0, 1) (got {lr}, {momentum})")
+    if params61.dim() != 2 or params61.shape[1] != 61 or params61.dtype != torch.float32:
+        raise RuntimeError(f"refine_ttt: params61 must be float32 [B,61] (got {params61.dtype} {tuple(params61.shape)})")
+    pose = lambda q: layer(betas=q[:, :10], global_orient=q[:, 10:13], hand_pose=q[:, 13:58], transl=q[:, 58:61]).vertices
+    with torch.no_grad():
+        given = params61.detach()
+        p = given.clone()
+        loss0, grad = ttt_value_and_grad(topology, pose(p), obj_xyz, targets, w_pen, w_con, want_grad=steps > 0)
+        loss = loss0
+        best_p, best_loss = p.clone(), loss0.clone()
+        best_iter = torch.zeros(p.shape[0], dtype=torch.int32, device=p.device)
+        buf = None
+        for k in range(1, steps + 1):
+            g_betas, g_pose, g_orient, g_transl = ops.mano_backward(layer._packed, p[:, :10], p[:, 13:58], p[:, 10:13], p[:, 58:61], grad)
+            g = torch.cat((g_betas, g_orient, g_pose, g_transl), dim=1)          # the 61 columns' order
+            if buf is None:
+                buf = g.clone()
+            else:
+                buf.mul_(momentum).add_(g)
+            p.add_(buf, alpha=-lr)
+            loss, grad = ttt_value_and_grad(topology, pose(p), obj_xyz, targets, w_pen, w_con, want_grad=k < steps)
+            if keep_best:
+                better = loss < best_loss                   # strictly: the earliest among equals; never true against a NaN
+                best_p = torch.where(better[:, None], p, best_p)
+                best_loss = torch.where(better, loss, best_loss)
+                best_iter = torch.where(better, torch.full_like(best_iter, k), best_iter)
+        if not keep_best:
+            best_p, best_loss, best_iter = p, loss, torch.full_like(best_iter, steps)
+        lost = ~torch.isfinite(p).all(dim=1) | torch.isnan(loss0)
+        best_p = torch.where(lost[:, None], given, best_p)
+        best_loss = torch.where(lost, loss0, best_loss)
+        best_iter = torch.where(lost, torch.zeros_like(best_iter), best_iter)
+    return {"params": best_p, "loss0": loss0, "loss": best_loss, "iter": best_iter}
+

@@ -164,6 +164,23 @@ def build_parser(dataset: str) -> argparse.ArgumentParser:
                         "effect on real grasps not measured")
     p.add_argument("--refine_max_curl", type=float, default=0.35,
                    help="--refine_curl: the largest angle (radians) a finger may turn from the hand as generated; untuned")
+    p.add_argument("--ttt_steps", type=int, default=0,
+                   help="gradient refinement, the reference's test-time loop: this many steps (<= 1000; the reference runs 300) of SGD "
+                        "with momentum on the 61 MANO parameters of every generated hand, down 7 * penetration + 1 * contact of the "
+                        "reference's TTT_loss (one fused loss-and-gradient kernel and the MANO backward pass per step), after any "
+                        "push-out and before any scoring or selection (0 = off); the JSON gains \"ttt_loss0\", \"ttt_loss\" and "
+                        "\"ttt_iter\"; the constants are the reference's and untuned here, effect on real grasps not measured")
+    p.add_argument("--ttt_lr", type=float, default=6.25e-6, help="--ttt_steps: the learning rate (the reference's)")
+    p.add_argument("--ttt_momentum", type=float, default=0.8, help="--ttt_steps: the momentum (the reference's)")
+    p.add_argument("--ttt_w_pen", type=float, default=840.0, help="--ttt_steps: the weight of the penetration term (the reference's 7 * 120)")
+    p.add_argument("--ttt_w_con", type=float, default=7500.0,
+                   help="--ttt_steps: the weight of the contact term, the mean squared distance of the object points within 2 cm to "
+                        "the nearest contact vertex (the reference's 1 * 2.5 * 3000)")
+    p.add_argument("--ttt_prior", default=None,
+                   help="--ttt_steps: a JSON file holding the list of hand vertices the contact term measures distances to (the "
+                        "reference uses 204 finger-pad and palm vertices); default: every vertex")
+    p.add_argument("--ttt_keep_best", type=int, default=1,
+                   help="--ttt_steps: 1 = every hand keeps its iterate of lowest loss, 0 = the last iterate, as the reference does")
     return p
 
 
@@ -195,6 +212,16 @@ def parse_args(dataset: str, argv: Optional[Sequence[str]] = None) -> argparse.N
         p.error("--refine_curl needs --refine_steps (it curls the fingers during the push-out)")
     if not 0.0 < args.refine_max_curl <= math.pi:
         p.error(f"--refine_max_curl must lie in (0, pi] (got {args.refine_max_curl})")
+    if not 0 <= args.ttt_steps <= TTT_MAX_STEPS:
+        p.error(f"--ttt_steps must lie between 0 and {TTT_MAX_STEPS} (got {args.ttt_steps})")
+    if not (0.0 <= args.ttt_lr < float("inf") and 0.0 <= args.ttt_momentum < 1.0):
+        p.error(f"--ttt_lr must be finite and >= 0 and --ttt_momentum in [0, 1) (got {args.ttt_lr}, {args.ttt_momentum})")
+    if not (0.0 <= args.ttt_w_pen < float("inf") and 0.0 <= args.ttt_w_con < float("inf")):
+        p.error(f"--ttt_w_pen and --ttt_w_con must be finite and >= 0 (got {args.ttt_w_pen}, {args.ttt_w_con})")
+    if args.ttt_keep_best not in (0, 1):
+        p.error(f"--ttt_keep_best is 0 or 1 (got {args.ttt_keep_best})")
+    if args.ttt_prior is not None and not args.ttt_steps:
+        p.error("--ttt_prior needs --ttt_steps (it names the contact vertices of the gradient refinement)")
     if not 0.0 < args.torque_length < float("inf"):
         p.error(f"--torque_length must be finite and positive (got {args.torque_length})")
     if not args.max_penetration >= 0.0:
@@ -459,7 +486,7 @@ def _generate_call(net: GenNet, objs: Sequence[torch.Tensor], num_grasp: int, ro
                    max_penetration: float = float("inf"), torque_length: float = 0.1,
                    volume: Optional[Dict[str, float]] = None, parts: Optional[Dict[str, object]] = None,
                    refine_spin: float = 0.0, refine_curl: float = 0.0, refine_max_curl: float = 0.35,
-                   slf: Optional[Dict[str, object]] = None) -> List[Dict[str, object]]:
+                   slf: Optional[Dict[str, object]] = None, ttt: Optional[Dict[str, object]] = None) -> List[Dict[str, object]]:
     """One batched call: the ``num_grasp`` grasps of each of ``objs`` (all of one point count), row o * num_grasp + g = grasp g
     of object o.  Every step is row-independent and keyed per row, so each object's slice holds the bits of its own
     ``generate_for_object`` call.  With ``candidates`` = M the call generates M rows per object (exactly the grasps of a
@@ -479,7 +506,9 @@ def _generate_call(net: GenNet, objs: Sequence[torch.Tensor], num_grasp: int, ro
     ``min_fingers``, ``need_thumb``) ONE ``contact.grasp_parts`` runs over all rows of the call, after the push-out too; its four
     tensors ride in that copy and become the fields of _parts_json.  With ``slf`` (``table``, ``reach``, ``margin``, ``max_verts``)
     ONE ``contact.grasp_self`` runs over all rows of the call, after the push-out too -- the hands against themselves; its six
-    tensors ride in that copy and become the fields of _self_json."""
+    tensors ride in that copy and become the fields of _self_json.  With ``ttt`` (``steps``, ``lr``, ``momentum``, ``w_pen``, ``w_con``,
+    ``targets``, ``keep_best``) every row goes through ``contact.refine_ttt`` after any push-out and MANO is posed again, so that
+    everything after it sees the refined hands; the rows' three figures travel in a small copy of their own (_ttt_attach)."""
     dev = next(net.parameters()).device
     keep = num_grasp
     G, O = (candidates or num_grasp), len(objs)
@@ -524,6 +553,15 @@ def _generate_call(net: GenNet, objs: Sequence[torch.Tensor], num_grasp: int, ro
             params[:, 58:61] += refined["offset"]                                  # fp32; the hands below are those of these parameters
             final = net.rh_mano(betas=params[:, :10], global_orient=params[:, 10:13], hand_pose=params[:, 13:58],
                                 transl=params[:, 58:61])
+    tuned = None
+    if ttt:                                                                        # gradient refinement: after any push-out, before any score
+        from . import contact
+        tuned = contact.refine_ttt(net.rh_mano, _hand_topology(net, final.vertices.shape[1], dev), params, batch[:, :3].transpose(1, 2),
+                                   ttt["steps"], ttt["lr"], ttt["momentum"], ttt["targets"], ttt["w_pen"], ttt["w_con"], ttt["keep_best"])
+        params = tuned["params"]
+        final = net.rh_mano(betas=params[:, :10], global_orient=params[:, 10:13], hand_pose=params[:, 13:58], transl=params[:, 58:61])
+        if refined is not None and "scores" in refined:                            # the push-out's guard scored the hands before this
+            refined = {k: v for k, v in refined.items() if k != "scores"}
     vol = None
     if volume:                                                                     # after the push-out: the hands of the parameters written
         vol = _volume_launch(net, objs, final.vertices, obj_of_row, R_dev if rotate else None, t_dev if rotate else None, volume["res"])
@@ -536,9 +574,9 @@ def _generate_call(net: GenNet, objs: Sequence[torch.Tensor], num_grasp: int, ro
         from . import contact
         sco = contact.grasp_self(_hand_topology(net, final.vertices.shape[1], dev), slf["table"], final.vertices, slf["reach"], slf["margin"])
     if candidates:
-        return _select_call(net, batch, params, final.vertices, logp, err, O, G, keep, select_by, min_contact, want_logp, proxies,
-                            np.concatenate(Rs), np.concatenate(angles), t, diverse_pool, diverse_space, refined, diversity, stability,
-                            max_penetration, torque_length, vol, volume, prt, parts, sco, slf)
+        return _ttt_attach(_select_call(net, batch, params, final.vertices, logp, err, O, G, keep, select_by, min_contact, want_logp, proxies,
+                                        np.concatenate(Rs), np.concatenate(angles), t, diverse_pool, diverse_space, refined, diversity,
+                                        stability, max_penetration, torque_length, vol, volume, prt, parts, sco, slf), tuned, G)
     ref_lists = {}
     div = _diversity_launch(params, O, G, diversity) if diversity else []
     prt_t = [prt[k] for k in PARTS_PIECES] if prt is not None else []             # last before the flag in the call's one copy
@@ -641,6 +679,31 @@ def _generate_call(net: GenNet, objs: Sequence[torch.Tensor], num_grasp: int, ro
         outs.append({**extra, "params": p_dev[o], "vertices": v_dev[o],
                      "json": {"recon_params": [[p] for p in p_list[lo:hi]],           # [[61 floats]] per grasp, as the reference
                               "R_list": Rt_list[lo:hi], "trans_list": [trans] * G, "r_list": r_list[lo:hi], **extra_json}})
+    return _ttt_attach(outs, tuned, G)
+
+
+TTT_PIECES = ("loss0", "loss", "iter")   # of contact.refine_ttt's dict: what rides to the host, in this order
+TTT_MAX_STEPS = 1000                     # contact.TTT_MAX_STEPS
+
+
+def _ttt_attach(outs: List[Dict[str, object]], tuned: Optional[Dict[str, torch.Tensor]], M: int) -> List[Dict[str, object]]:
+    """``--ttt_steps``: the three figures of ``contact.refine_ttt`` for the grasps of a call's dicts -- all M rows of every object, or
+    with best-of-M the rows ``candidate`` names -- as ``ttt_loss0`` / ``ttt_loss`` / ``ttt_iter`` tensors and JSON lists (a loss that
+    is not finite becomes null), through one small device-to-host copy of their own.  ``tuned`` = None: the dicts as they are."""
+    if tuned is None:
+        return outs
+    pieces = [tuned[k] for k in TTT_PIECES]
+    if "candidate" in outs[0]:
+        rows = torch.cat([out["candidate"] + o * M for o, out in enumerate(outs)])
+        pieces = [x.index_select(0, rows) for x in pieces]
+    n = pieces[0].shape[0] // len(outs)
+    host = _host_copy(pieces)
+    lists = [[float(x) if np.isfinite(x) else None for x in host[0]], [float(x) if np.isfinite(x) else None for x in host[1]],
+             host[2].tolist()]
+    for o, out in enumerate(outs):
+        lo, hi = o * n, (o + 1) * n
+        out.update({"ttt_" + k: x[lo:hi] for k, x in zip(TTT_PIECES, pieces)})
+        out["json"].update({"ttt_" + k: v[lo:hi] for k, v in zip(TTT_PIECES, lists)})
     return outs
 
 
@@ -903,7 +966,9 @@ def generate_for_objects(net: GenNet, objs: Sequence[torch.Tensor], num_grasp: i
                          hand_parts=None, refine_spin: float = 0.0, refine_curl: float = 0.0,
                          refine_max_curl: float = 0.35, self_collision: bool = False, self_reach: float = 0.01,
                          self_margin: float = 0.001, self_seam: int = 2, self_palm: bool = True,
-                         max_self_verts: Optional[int] = None) -> List[Dict[str, object]]:
+                         max_self_verts: Optional[int] = None, ttt_steps: int = 0, ttt_lr: float = 6.25e-6,
+                         ttt_momentum: float = 0.8, ttt_w_pen: float = 840.0, ttt_w_con: float = 7500.0, ttt_prior=None,
+                         ttt_keep_best: bool = True) -> List[Dict[str, object]]:
     """``num_grasp`` grasps for each of ``objs`` ([4,N] tensors) in batched calls that mix objects (plan_calls): one dict per
     object, in the order given, equal to ``generate_for_object(net, objs[i], num_grasp, rotate,
     np.random.default_rng([seed, object_indices[i]]), seed=seed, object_index=object_indices[i], proxies=proxies)`` (and the same
@@ -1002,7 +1067,17 @@ def generate_for_objects(net: GenNet, objs: Sequence[torch.Tensor], num_grasp: i
     ``self_scores``, those of ALL candidates) and ``json`` gains "self_penetrating", "self_part_penetrating", "self_depth" (cm),
     "self_pairs" and "self_clearance" (cm) per grasp (``contact.self_stats``, float64 on the host; null without a figure).  A
     proximity figure on vertices only, calibrated against false alarms only: untuned, effect on real grasps not measured.  Without
-    these switches nothing of it runs."""
+    these switches nothing of it runs.
+
+    Gradient refinement (``ttt_steps`` = K > 0 with ``ttt_lr``, ``ttt_momentum``, ``ttt_w_pen``, ``ttt_w_con``, ``ttt_prior``,
+    ``ttt_keep_best``): every row of a call goes through ``contact.refine_ttt`` -- K steps of SGD with momentum on the 61 parameters
+    down the reference's test-time loss (one fused loss-and-gradient kernel and the MANO backward pass per step) -- after any push-out
+    and before any scoring or selection, and MANO is posed again, so ``params`` / ``vertices`` are the refined ones and best-of-M ranks
+    the refined candidates.  ``ttt_prior``: None (every vertex is a contact target), a ``contact.ContactTargets``, or the path of a
+    JSON list of vertex indices (the reference's 204).  The dicts gain ``ttt_loss0``, ``ttt_loss`` [num_grasp] f32 and ``ttt_iter``
+    [num_grasp] i32, and the JSON the same three lists (a loss that is not finite: null), through a small copy of their own.  Rows are
+    refined independently: the results do not depend on ``rows_per_call``; ``ttt_steps = 0`` is the call without the keyword.  The
+    constants are the reference's and untuned here; the effect on real grasps is not measured."""
     self_args = None
     if self_collision or max_self_verts is not None:
         if not 0.0 < float(self_reach) < float("inf") or not 0.0 <= float(self_margin) < float("inf"):
@@ -1081,15 +1156,44 @@ def generate_for_objects(net: GenNet, objs: Sequence[torch.Tensor], num_grasp: i
         if not (0.0 <= refine_push < float("inf") and 0.0 <= refine_pull < float("inf")):
             raise RuntimeError(f"generate_for_objects: refine_push and refine_pull must be finite and >= 0 (got {refine_push}, {refine_pull})")
         _hand_faces(net)                                                           # no face list: raise before any work
+    ttt_args = None
+    if ttt_steps:
+        from . import contact
+        if not 0 < int(ttt_steps) <= TTT_MAX_STEPS:
+            raise RuntimeError(f"generate_for_objects: ttt_steps must lie between 0 and {TTT_MAX_STEPS} (got {ttt_steps})")
+        if not (0.0 <= float(ttt_lr) < float("inf") and 0.0 <= float(ttt_momentum) < 1.0):
+            raise RuntimeError(f"generate_for_objects: ttt_lr must be finite and >= 0, ttt_momentum in [0, 1) (got {ttt_lr}, {ttt_momentum})")
+        if not (0.0 <= float(ttt_w_pen) < float("inf") and 0.0 <= float(ttt_w_con) < float("inf")):
+            raise RuntimeError(f"generate_for_objects: ttt_w_pen and ttt_w_con must be finite and >= 0 (got {ttt_w_pen}, {ttt_w_con})")
+        _hand_faces(net)                                                           # no face list: raise before any work
+        ttt_args = dict(steps=int(ttt_steps), lr=float(ttt_lr), momentum=float(ttt_momentum), w_pen=float(ttt_w_pen),
+                        w_con=float(ttt_w_con), targets=_ttt_targets(ttt_prior), keep_best=bool(ttt_keep_best))
+    elif ttt_prior is not None:
+        raise RuntimeError("generate_for_objects: ttt_prior needs ttt_steps")
     out: List[Optional[Dict[str, object]]] = [None] * len(objs)
     for call in plan_calls([o.shape[1] for o in objs], candidates or num_grasp, rows_per_call):
         res = _generate_call(net, [objs[p] for p in call], num_grasp, rotate, seed, [object_indices[p] for p in call], proxies,
                              temperature, top_k, log_prob, candidates, select_by, min_contact, diverse_pool, diverse_space, refine_steps,
                              refine_push, refine_pull, diversity, stability, max_penetration, torque_length, vol_args, parts_args,
-                             float(refine_spin), float(refine_curl), float(refine_max_curl), self_args)
+                             float(refine_spin), float(refine_curl), float(refine_max_curl), self_args, ttt_args)
         for p, r in zip(call, res):
             out[p] = r
     return out
+
+
+def _ttt_targets(prior):
+    """``ttt_prior`` -> what contact.refine_ttt takes: None (every vertex), a ``contact.ContactTargets`` as given, or the path of a
+    JSON list of vertex indices (read once per path)."""
+    from . import contact
+    if prior is None or isinstance(prior, contact.ContactTargets):
+        return prior
+    key = os.path.abspath(str(prior))
+    if key not in _TTT_TARGETS:
+        _TTT_TARGETS[key] = contact.ContactTargets.from_json(key)
+    return _TTT_TARGETS[key]
+
+
+_TTT_TARGETS: Dict[str, object] = {}
 
 
 def main(dataset: str, argv: Optional[Sequence[str]] = None) -> List[str]:
@@ -1119,7 +1223,7 @@ def main(dataset: str, argv: Optional[Sequence[str]] = None) -> List[str]:
     want_parts = bool(args.parts) or args.min_fingers > 0 or bool(args.need_thumb)
     want_self = bool(args.self_collision) or args.max_self_verts is not None
     if (args.rows_per_call > 0 or args.candidates or args.refine_steps or args.diversity or args.stability or want_volume or want_parts
-            or want_self):
+            or want_self or args.ttt_steps):
         # grouped calls (best-of-M, push-out, the diversity statistic and the stability proxy always: --rows_per_call 0 is then one
         # object per call)
         rows_per_call, per_object = max(1, args.rows_per_call), (args.candidates or args.num_grasp)
@@ -1133,6 +1237,9 @@ def main(dataset: str, argv: Optional[Sequence[str]] = None) -> List[str]:
                 selection.update(refine_spin=args.refine_spin)
             if args.refine_curl:
                 selection.update(refine_curl=args.refine_curl, refine_max_curl=args.refine_max_curl)
+        if args.ttt_steps:
+            selection.update(ttt_steps=args.ttt_steps, ttt_lr=args.ttt_lr, ttt_momentum=args.ttt_momentum, ttt_w_pen=args.ttt_w_pen,
+                             ttt_w_con=args.ttt_w_con, ttt_prior=args.ttt_prior, ttt_keep_best=bool(args.ttt_keep_best))
         if args.diversity:
             selection.update(diversity=args.diversity)
         if args.stability or (args.candidates and args.select_by == "stability"):

@@ -943,7 +943,44 @@ def grasp_self(hand: Tensor, faces: Tensor, vf_off: Tensor, vf_face: Tensor, par
     return pen_count, pen_depth, gap_min, pair_bits, mask, status
 
 
-GRASP_VOLUME_MAX_F = 8192          # csrc/grasp_volume.hip: GV_MAX_F
+GRASP_TTT_MAX_N = 16384             # include/dvq.h: DVQ_GRASP_TTT_MAX_N (one word per object point sits in LDS)
+
+
+def grasp_ttt(hand: Tensor, faces: Tensor, vf_off: Tensor, vf_face: Tensor, obj: Tensor, targets: Optional[Tensor] = None,
+              w_pen: Optional[Tensor] = None, w_con: Optional[Tensor] = None, mean_contact: bool = False, want_grad: bool = False,
+              contact_threshold: float = 0.02 ** 2):
+    """The two terms of the reference's test-time loss and their gradient with respect to the hand in one fused kernel
+    (dvq_grasp_ttt; the definition is in include/dvq.h): arguments as ``grasp_scores``; ``targets`` int32 [V] on the device (nonzero =
+    the vertex is a contact target) or None for every vertex; ``w_pen`` / ``w_con`` fp32 [B] on the device or None (= 1): the
+    weights of the two terms in the gradient; ``mean_contact``: the contact weight is divided by max(n_contact, 1).  Returns
+    ``(penetration [B] f32, contact_sum [B] f32, n_interior [B] i32, n_contact [B] i32, grad_hand [B,V,3] f32 or None)``; without
+    ``want_grad`` the gradient phase does not run.  A row with a non-finite coordinate has a NaN contact sum and a NaN gradient."""
+    po, ob, op, oc, B, V, N = _hand_cloud_args("grasp_ttt", hand, faces, vf_off, vf_face, obj)
+    if N > GRASP_TTT_MAX_N:
+        raise RuntimeError(f"grasp_ttt: need N <= {GRASP_TTT_MAX_N} (got N={N})")
+    if targets is not None and (not isinstance(targets, Tensor) or targets.dtype != torch.int32 or not targets.is_contiguous()
+                                or tuple(targets.shape) != (V,)):
+        raise RuntimeError(f"grasp_ttt: targets must be a contiguous int32 tensor [{V}] or None")
+    for t, n in ((w_pen, "w_pen"), (w_con, "w_con")):
+        if t is not None and (not isinstance(t, Tensor) or t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != (B,)):
+            raise RuntimeError(f"grasp_ttt: {n} must be a contiguous float32 tensor [{B}] or None")
+    dev = _require_gpu(hand, obj, faces, vf_off, vf_face, targets, w_pen, w_con)
+    lib = _lib.load()
+    pen = torch.empty(B, dtype=torch.float32, device=dev)
+    con = torch.empty(B, dtype=torch.float32, device=dev)
+    n_in = torch.empty(B, dtype=torch.int32, device=dev)
+    n_ct = torch.empty(B, dtype=torch.int32, device=dev)
+    grad = torch.empty(B, V, 3, dtype=torch.float32, device=dev) if want_grad else None
+    ptr = lambda t: None if t is None else t.data_ptr()
+    with torch.cuda.device(dev):
+        check(lib.dvq_grasp_ttt(hand.data_ptr(), faces.data_ptr(), vf_off.data_ptr(), vf_face.data_ptr(), V, po, ob, op, oc, B, N,
+                                float(contact_threshold), ptr(targets), ptr(w_pen), ptr(w_con), 1 if mean_contact else 0,
+                                pen.data_ptr(), con.data_ptr(), n_in.data_ptr(), n_ct.data_ptr(), ptr(grad), _stream(dev)),
+              "dvq_grasp_ttt")
+    return pen, con, n_in, n_ct, grad
+
+
+GRASP_VOLUME_MAX_F = 8192         # csrc/grasp_volume.hip: GV_MAX_F
 GRASP_VOLUME_MAX_LOOPS = 64        # GV_MAX_L
 GRASP_VOLUME_MAX_PLANES = 8192     # GV_MAX_P: per object
 GRASP_VOLUME_MAX_CELLS = 1024      # GV_MAX_CELLS: per axis of a hand's box; beyond it the grasp reports status 2

@@ -43,7 +43,7 @@ typedef enum {
 /* Entry points added since 10 without touching a struct or a signature of it (a compatible extension: bindings of 10 keep
  * working, the version stays): dvq_pixelcnn_sample_ctl, dvq_grasp_scores, dvq_segment_topk, dvq_segment_diverse,
  * dvq_grasp_refine, dvq_segment_kmeans, dvq_grasp_wrench, dvq_grasp_volume, dvq_grasp_parts, dvq_grasp_refine_rigid,
- * dvq_grasp_refine_fingers, dvq_grasp_self, dvq_mano_backward_workspace_bytes, dvq_mano_backward. */
+ * dvq_grasp_refine_fingers, dvq_grasp_self, dvq_mano_backward_workspace_bytes, dvq_mano_backward, dvq_grasp_ttt. */
 int dvq_abi_version(void);
 const char* dvq_last_error(void);
 /* number of visible HIP devices, or -1; does not create a context */
@@ -665,6 +665,39 @@ int dvq_grasp_self(const float* hand /* [B,V,3] */, const int32_t* faces, const 
                    int64_t B, float reach2, float margin,
                    int32_t* pen_count /* [B,P] */, float* pen_depth /* [B,P] */, float* gap_min /* [B,P] */,
                    int32_t* pair_bits /* [B,P] */, int32_t* mask /* [B,W] */, int32_t* status /* [B] */, dvq_stream_t stream);
+/* The test-time loss of grasps and its gradient: the two terms of the reference's TTT_loss (utils/loss.py: the penetration term and
+ * the hand-centric Contact_loss) AND their gradient with respect to the hand's vertices, in ONE kernel, one workgroup of 256 threads
+ * per grasp; no [B,N] or [B,N,V] intermediate is written.  What dvq_mano_backward is fed with for gradient refinement
+ * (gen_diverse_grasp_obman.py:69-94).
+ * Inputs: everything dvq_grasp_scores takes (hand [B,V,3] contiguous, the topology, obj with strides in floats: a channel-first cloud
+ * is read in place; contact_threshold, a squared distance); target_of_vertex int32 [V] on the device or NULL: != 0 where the vertex is
+ * a CONTACT TARGET (the reference's prior_idx subset), NULL = every vertex; w_pen, w_con fp32 [B] on the device or NULL (= 1 for every
+ * row): the weights of the two terms in the gradient; mean_contact 0 or 1; grad_hand fp32 [B,V,3] or NULL (no gradient phase).
+ * Per grasp b, when every coordinate of its hand and of its cloud is finite (fp32, fma = the only fused operations):
+ *   1. normals, d_p, j_p, inside_p, term_p exactly as dvq_grasp_scores defines them; penetration, n_interior, n_contact are its bits.
+ *   2. dc_p = the minimum over the target vertices of the same distance expression, jc_p = the lowest target index that attains it
+ *      (with no target vertex: dc_p = +inf and the point names no vertex); contact_p = d_p < contact_threshold -- the mask is taken
+ *      from the all-vertex distance, the value from the target distance, as the reference does.
+ *   3. contact_sum = the canonical sum of dvq_grasp_scores (256 strided partial sums from +0.0f in ascending p, then the tree
+ *      128 .. 1) of  contact_p ? dc_p : +0.0f.
+ *   4. with grad_hand: Gp[v][c] = the fp32 sum from +0.0f, in ascending p, of hand[v][c] - obj[p][c] over the points with inside_p and
+ *      j_p == v; Gc[v][c] the same sum over the points with contact_p and jc_p == v; a = 2.0f * w_pen[b]; c = 2.0f * w_con[b], with
+ *      mean_contact c = (2.0f * w_con[b]) / (float)max(n_contact, 1) (an IEEE fp32 division);
+ *      grad_hand[b][v][c] = fma(c, Gc[v][c], a * Gp[v][c]).  This is the gradient of w_pen * penetration + w_con * contact_sum
+ *      (/ max(n_contact, 1)) with the masks and the indices held constant: nothing flows through the normals or the threshold.
+ * A grasp with a non-finite coordinate of its hand or of its cloud: the three scores are what dvq_grasp_scores reports, contact_sum is
+ * NaN and every element of its grad_hand is NaN; other grasps are unaffected.
+ * No atomics: every sum has one owner and one order, so the outputs are the same bits on every run and depend on neither B nor the row.
+ * Outputs: penetration, contact_sum fp32 [B]; n_interior, n_contact int32 [B]; grad_hand fp32 [B,V,3] if given.
+ * B >= 0, 1 <= N <= DVQ_GRASP_TTT_MAX_N (one word per point sits in LDS), 1 <= V <= 2048, mean_contact 0 or 1, no null pointer but
+ * the four that may be; anything else is DVQ_EINVAL, nothing launched.  (B = 0 returns DVQ_OK before any pointer is looked at.) */
+#define DVQ_GRASP_TTT_MAX_N 16384
+int dvq_grasp_ttt(const float* hand /* [B,V,3] */, const int32_t* faces, const int32_t* vf_off, const int32_t* vf_face, int V,
+                  const float* obj, int64_t obj_batch_stride, int64_t obj_point_stride, int64_t obj_coord_stride, int64_t B, int N,
+                  float contact_threshold, const int32_t* target_of_vertex /* [V] or NULL */, const float* w_pen /* [B] or NULL */,
+                  const float* w_con /* [B] or NULL */, int mean_contact, float* penetration /* [B] */, float* contact_sum /* [B] */,
+                  int32_t* n_interior /* [B] */, int32_t* n_contact /* [B] */, float* grad_hand /* [B,V,3] or NULL */,
+                  dvq_stream_t stream);
 /* Penetration volume of grasps: the voxels, on a lattice of spacing h, whose centres lie both inside the (sealed) hand mesh and
  * inside the convex hull of the object -- an INTEGER per grasp, defined to the bit -- and the depth of the deepest hand vertex inside
  * the hull, in ONE kernel, one workgroup of 256 threads per grasp.  The counterpart of the reference's intersection_eval
