@@ -67,6 +67,10 @@ class PixelcnnCtl(C.Structure):
                 ("logp_draw_out", C.c_void_p)]
 
 
+class PixelcnnBeamTrace(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("parent", "token", "score", "live", "logits")]
+
+
 class ManoModel(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("v_template", "blend_w", "blend_w_planes", "j_template", "j_shapedirs",
                                           "weights", "comps", "pose_mean")] + [
@@ -115,6 +119,9 @@ SIGNATURES = {
                                           c_i32p, C.c_void_p, C.c_size_t, c_stream]),
     "dvq_pixelcnn_forward": (C.c_int, [C.POINTER(PixelcnnWeights), c_i64p, c_i64p, C.c_int64, c_f32p, c_i32p, C.c_void_p,
                                        C.c_size_t, c_stream]),
+    "dvq_pixelcnn_beam_workspace_bytes": (C.c_size_t, [C.POINTER(PixelcnnWeights), C.c_int64, C.c_int32]),
+    "dvq_pixelcnn_beam": (C.c_int, [C.POINTER(PixelcnnWeights), c_i64p, C.c_int64, C.c_int32, c_i64p, c_f32p, c_i32p,
+                                    C.POINTER(PixelcnnBeamTrace), c_i32p, C.c_void_p, C.c_size_t, c_stream]),
     "dvq_mano_workspace_bytes": (C.c_size_t, [C.c_int64]),
     "dvq_mano_forward": (C.c_int, [C.POINTER(ManoModel), c_f32p, C.c_int64, c_f32p, C.c_int64, c_f32p, C.c_int64, c_f32p,
                                    C.c_int64, C.c_int64, c_f32p, C.c_int, c_f32p, C.c_void_p, C.c_size_t, c_stream]),

@@ -5,6 +5,8 @@
 // horizontal stack + head position by position.  Every conv tap is one K=dim source of a multi-source
 // fp32-MFMA GEMM whose epilogue applies bias + class-conditional bias + tanh*sigmoid gate (gate-packed
 // channels) or the residual add; taps that fall into the zero padding are simply skipped.
+// dvq_pixelcnn_beam walks the same plan with a selection in the draw's place (beam_score_kernel, beam_expand_kernel) and reads the
+// cached activations of a beam's prefix through its ancestry (GemmSrc::arow) instead of copying them.
 //
 // Geometry (models.py:41-55): layer 0 has k=5 and mask 'A' (last kernel row of the vertical stack and
 // last kernel column of the horizontal stack are zero: applied by skipping those taps), layers >= 1
@@ -111,6 +113,20 @@ __device__ __forceinline__ uint32_t order_key(float v) {
     if (v == 0.f) v = 0.f;
     const uint32_t u = __float_as_uint(v);
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
+// max_k l[k] and sum_k expf(l[k] - max) of one logits row as one wave: lane ``lane`` owns tokens k = lane + 64 j in ascending j, then
+// the xor butterfly 32 .. 1 -- sample_kernel's orders.  logp_model = (l[c] - mx) - logf(sum) of the controlled draw and the beam
+// search's candidate scores are both made from these two numbers, which is why a beam's score replays bit for bit.
+__device__ __forceinline__ void row_softmax_stats(const float* __restrict__ lg, int n_in, int lane, float& mx, float& sum) {
+    mx = -INFINITY;
+    for (int k = lane; k < n_in; k += 64) mx = fmaxf(mx, lg[k]);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
+    sum = 0.f;
+    for (int k = lane; k < n_in; k += 64) sum += expf(lg[k] - mx);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
 }
 
 // One wave per sample, lane ``lane`` owns tokens k = lane + 64 j (sample_kernel's striding, so the per-lane and the butterfly
@@ -264,14 +280,8 @@ __global__ void sample_ctl_kernel(const float* __restrict__ logits, const float*
         if (T == 1.0f && !sel) {
             lm = ld;                                        // s = l and the kept set is everything
         } else {
-            float mxl = -INFINITY;
-            for (int k = lane; k < n_in; k += 64) mxl = fmaxf(mxl, lg[k]);
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) mxl = fmaxf(mxl, __shfl_xor(mxl, o));
-            float suml = 0.f;
-            for (int k = lane; k < n_in; k += 64) suml += expf(lg[k] - mxl);
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) suml += __shfl_xor(suml, o);
+            float mxl, suml;
+            row_softmax_stats(lg, n_in, lane, mxl, suml);
             lm = (lc - mxl) - logf(suml);
         }
         if (nan_row || nan_draw) lm = ld = __builtin_nanf("");
@@ -289,7 +299,221 @@ __global__ void iota_kernel(int64_t* __restrict__ out, int n) {
     if (i < n) out[i] = i;
 }
 
+// order_key of the float whose bits are ``u``, in integer arithmetic alone (no NaN reaches it: a segment with one is dead)
+__device__ __forceinline__ uint32_t order_key_bits(uint32_t u) {
+    if ((u << 1) == 0u) u = 0u;                            // -0 counts as +0
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
+// ---- beam search (dvq_pixelcnn_beam).  A segment = one label = W consecutive rows of the plan; row base + r holds the beam of rank r.
+constexpr int BEAM_MAX_W = 1024, BEAM_THREADS = 1024, BEAM_WAVES = BEAM_THREADS / 64;
+
+// labels of the chunk's rows (row -> its segment's label, range-checked as sanitize_labels_kernel does), score +0.0f, one live beam
+__global__ void beam_init_kernel(const int64_t* __restrict__ label /* at the chunk's first segment */, long segs, int W, int n_classes,
+                                 int64_t* __restrict__ lab, float* __restrict__ score, int32_t* __restrict__ live,
+                                 int32_t* __restrict__ nanflag, int32_t* err_flag) {
+    const long b = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= segs * W) return;
+    const long s = b / W;
+    int64_t l = label[s];
+    if (l < 0 || l >= n_classes) {
+        if (err_flag) atomicOr(err_flag, 1);
+        l = 0;
+    }
+    lab[b] = l;
+    score[b] = 0.0f;
+    if (b == s * W) {
+        live[s] = 1;
+        nanflag[s] = 0;
+    }
+}
+
+// One wave per row: the logits of a live row become its candidates' scores in place, score_b + ((l[k] - mx) - logf(sum)) -- the
+// logp_model of sample_ctl_kernel at T = 1 without top-k (row_softmax_stats), one float32 addition on top.  A NaN among them marks
+// the segment (an integer OR).  Rows beyond the segment's live count are left alone: beam_expand_kernel never looks at them.
+// ``table`` / ``lrow`` (position (0, 0) under class tables): row b's logits are row lrow[b] of ``table``; the scores still go to lg.
+__global__ void beam_score_kernel(float* lg /* [Bc,n_in]; no __restrict__: the logits read may be these rows */, int n_in, long Bc, int W, const float* __restrict__ score,
+                                  const int32_t* __restrict__ live, int32_t* __restrict__ nanflag,
+                                  float* __restrict__ trace_logits /* [Bc,n_in] of this position, or null */,
+                                  const float* table, const int64_t* __restrict__ lrow) {
+    const int lane = threadIdx.x & 63;
+    const long b = (long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    if (b >= Bc) return;
+    float* row = lg + b * n_in;
+    const float* src = table ? table + lrow[b] * n_in : row;
+    if (trace_logits)
+        for (int k = lane; k < n_in; k += 64) trace_logits[b * n_in + k] = src[k];
+    const long s = b / W;
+    if ((int)(b - s * W) >= live[s]) return;
+    float mx, sum;
+    row_softmax_stats(src, n_in, lane, mx, sum);
+    const float sc = score[b], ls = logf(sum);
+    bool nan = false;
+    for (int k = lane; k < n_in; k += 64) {
+        const float lm = (src[k] - mx) - ls;
+        const float v = sc + lm;
+        nan = nan || v != v;
+        row[k] = v;
+    }
+    if (__ballot(nan) != 0 && lane == 0) atomicOr(nanflag + s, 1);
+}
+
+// One workgroup per segment.  Of its N = live * n_in candidates (flat index b * n_in + k, b = the parent's rank) the Wn = min(W, N)
+// largest survive, compared on order_key(score), ties to the lower flat index:
+//   1. the Wn-th largest key bit by bit from the top (sample_ctl_kernel's method; counts are integers, summed wave by wave);
+//   2. the survivors -- keys above it, and of the keys equal to it the first ``need`` in flat-index order -- are compacted in flat-index
+//      order into LDS (ballots within a wave, the waves' counts through LDS);
+//   3. each survivor's rank = the survivors that sort before it on (key descending, flat index ascending): all distinct;
+//   4. rank r writes its token, parent, score, its ancestor rows anc_new[q][r] = anc_old[q][parent] (q < pos; anc_new[pos][r] = r) and
+//      its token's embedding as level 0 of this position at its own row.  Ranks beyond Wn: token -1, score -inf, token 0's embedding.
+// Nothing depends on the launch geometry or on the order in which waves arrive.
+__global__ __launch_bounds__(BEAM_THREADS) void beam_expand_kernel(
+    const float* __restrict__ cand /* [Bc,n_in]: beam_score_kernel's */, int n_in, int W, int pos, int dim, long chunk,
+    int32_t* __restrict__ live, const int32_t* __restrict__ nanflag, float* __restrict__ score /* [Bc] */,
+    int32_t* __restrict__ tok /* [Bc]: this position's */, const int64_t* __restrict__ anc_old /* [9][chunk] */,
+    int64_t* __restrict__ anc_new, const float* __restrict__ tok_emb, float* __restrict__ x0 /* [Bc,dim] */, int32_t* err_flag,
+    int32_t* __restrict__ t_parent, int32_t* __restrict__ t_tok, float* __restrict__ t_score /* [Bc] of this position, or null */,
+    int32_t* __restrict__ t_live /* [segs] of this position, or null */) {
+    __shared__ unsigned long long s_comp[BEAM_MAX_W];
+    __shared__ uint32_t s_flat[BEAM_MAX_W];
+    __shared__ int s_tok[BEAM_MAX_W];
+    __shared__ int s_cnt[2][BEAM_WAVES][2];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const long seg = blockIdx.x, base = seg * W;
+    const int live_in = live[seg];
+    const bool dead = live_in <= 0 || nanflag[seg] != 0;
+    const int N = dead ? 0 : live_in * n_in;
+    const int Wn = N < W ? N : W;
+    const float* c = cand + base * n_in;
+    const uint32_t* cu = reinterpret_cast<const uint32_t*>(c);         // the scores' bits: the keys are integer work from the load on
+    int buf = 0;
+    // every thread's count summed over the workgroup (one barrier: the partials alternate between two buffers)
+    auto block_sum = [&](int v) -> int {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+        if (lane == 0) s_cnt[buf][wave][0] = v;
+        dvq_lds_barrier();
+        int t = 0;
+#pragma unroll
+        for (int i = 0; i < BEAM_WAVES; ++i) t += s_cnt[buf][i][0];
+        buf ^= 1;
+        return t;
+    };
+    uint32_t thr = 0;
+    if (N > Wn) {
+        for (int bit = 31; bit >= 0; --bit) {
+            const uint32_t ct = thr | (1u << bit);
+            int cnt = 0;
+            for (int i = tid; i < N; i += BEAM_THREADS) cnt += order_key_bits(cu[i]) >= ct ? 1 : 0;
+            if (block_sum(cnt) >= Wn) thr = ct;
+        }
+    }
+    int need = 0;
+    {
+        int gt = 0;
+        for (int i = tid; i < N; i += BEAM_THREADS) gt += order_key_bits(cu[i]) > thr ? 1 : 0;
+        need = Wn - block_sum(gt);
+    }
+    const unsigned long long below = (1ull << lane) - 1ull;
+    int eq_base = 0, kept_base = 0;                        // equal keys / survivors in the flat indices before this round (uniform)
+    for (int i0 = 0; i0 < N && kept_base < Wn; i0 += BEAM_THREADS) {
+        const int i = i0 + tid;
+        const bool valid = i < N;
+        const uint32_t key = valid ? order_key_bits(cu[i]) : 0u;
+        const bool g = valid && key > thr, e = valid && key == thr;
+        const unsigned long long gm = __ballot(g), em = __ballot(e);
+        if (lane == 0) {
+            s_cnt[buf][wave][0] = __popcll(gm);
+            s_cnt[buf][wave][1] = __popcll(em);
+        }
+        dvq_lds_barrier();
+        int eq_run = eq_base, kept_run = kept_base, eq_mine = 0, kept_mine = 0;
+#pragma unroll
+        for (int wv = 0; wv < BEAM_WAVES; ++wv) {
+            if (wv == wave) { eq_mine = eq_run; kept_mine = kept_run; }
+            const int ng = s_cnt[buf][wv][0], ne = s_cnt[buf][wv][1];
+            int room = need - eq_run;
+            room = room < 0 ? 0 : (room > ne ? ne : room);
+            eq_run += ne;
+            kept_run += ng + room;
+        }
+        buf ^= 1;
+        const int eq_lane = __popcll(em & below);
+        int room = need - eq_mine;
+        room = room < 0 ? 0 : room;
+        const bool kept = g || (e && eq_lane < room);
+        const int at = kept_mine + __popcll(gm & below) + (eq_lane < room ? eq_lane : room);
+        if (kept && at < BEAM_MAX_W) s_comp[at] = ((unsigned long long)(~key) << 32) | (uint32_t)i;
+        eq_base = eq_run;
+        kept_base = kept_run;
+    }
+    dvq_lds_barrier();
+    if (tid < Wn) {
+        const unsigned long long mine = s_comp[tid];
+        int r = 0;
+        for (int j = 0; j < Wn; ++j) r += s_comp[j] < mine ? 1 : 0;
+        s_flat[r] = (uint32_t)mine;
+    }
+    dvq_lds_barrier();
+    if (tid < W) {
+        int parent = tid, t = -1;
+        float sc = -INFINITY;
+        if (tid < Wn) {
+            const uint32_t flat = s_flat[tid];
+            parent = (int)(flat / (uint32_t)n_in);
+            t = (int)(flat - (uint32_t)parent * (uint32_t)n_in);
+            sc = c[flat];
+        }
+        s_tok[tid] = t < 0 ? 0 : t;
+        const long row = base + tid;
+        score[row] = sc;
+        tok[row] = t;
+        for (int q = 0; q < pos; ++q) anc_new[(long)q * chunk + row] = anc_old[(long)q * chunk + base + parent];
+        anc_new[(long)pos * chunk + row] = row;
+        if (t_parent) t_parent[row] = tid < Wn ? parent : -1;
+        if (t_tok) t_tok[row] = t;
+        if (t_score) t_score[row] = sc;
+    }
+    if (tid == 0) {
+        live[seg] = Wn;                                    // 0 from here on for a segment with a NaN
+        if (t_live) t_live[seg] = Wn;
+        if (live_in > 0 && nanflag[seg] != 0 && err_flag) atomicOr(err_flag, 4);
+    }
+    dvq_lds_barrier();
+    const int d4 = dim / 4;
+    for (int idx = tid; idx < W * d4; idx += BEAM_THREADS) {
+        const int r = idx / d4, c4 = (idx - r * d4) * 4;
+        *reinterpret_cast<f32x4*>(x0 + (base + r) * dim + c4) = *reinterpret_cast<const f32x4*>(tok_emb + (long)s_tok[r] * dim + c4);
+    }
+}
+
+// codes [segs,W,9] read back along the ancestry (anc[8] is the identity), the final scores and live counts
+__global__ void beam_finish_kernel(const int32_t* __restrict__ tok /* [9][chunk] */, const int64_t* __restrict__ anc /* [9][chunk] */,
+                                   long chunk, long Bc, int W, const float* __restrict__ score, const int32_t* __restrict__ live,
+                                   int64_t* __restrict__ codes, float* __restrict__ score_out, int32_t* __restrict__ n_live) {
+    const long b = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= Bc) return;
+    const long s = b / W;
+    const int r = (int)(b - s * W), lv = live[s];
+    for (int q = 0; q < NPOS; ++q) codes[b * NPOS + q] = r < lv ? (int64_t)tok[(long)q * chunk + anc[(long)q * chunk + b]] : (int64_t)-1;
+    score_out[b] = r < lv ? score[b] : -INFINITY;
+    if (r == 0) n_live[s] = lv;
+}
+
+struct BeamCall {
+    int64_t S;
+    int W;
+    int64_t* codes;
+    float* score;
+    int32_t* n_live;
+    const dvq_pixelcnn_beam_trace* trace;
+};
+
 struct Plan {
+    int beam_w;                                            // > 0: a beam search's plan (dvq_pixelcnn_beam): chunks of whole segments, no class tables
+    int64_t* anc[2];                                       // [9][chunk] each: row -> its ancestor's row after position q; expand reads one, writes the other
+    int32_t *btok, *blive, *bnan;                          // [9][chunk] tokens per position; [chunk / beam_w] live counts, NaN marks
+    float* bscore;                                         // [chunk]
     long chunk;
     int L, dim;
     float *xv, *xh, *hv, *g, *hid, *lg;
@@ -342,12 +566,15 @@ size_t carve_tables(Plan& p, const dvq_pixelcnn_weights* w, char* base) {
     return (size_t)(c - base);
 }
 
-Plan make_plan(const dvq_pixelcnn_weights* w, int64_t B, void* ws) {
+// ``beam_w`` > 0: the plan of a beam search over B = segments * beam_w rows (a chunk holds whole segments, at least one)
+Plan make_plan(const dvq_pixelcnn_weights* w, int64_t B, void* ws, int beam_w = 0) {
     Plan p;
     p.L = w->n_layers;
     p.dim = w->dim;
+    p.beam_w = beam_w;
     long chunk = 16384;
     if (dvq_knobs().pixelcnn_chunk > 0) chunk = dvq_knobs().pixelcnn_chunk;
+    if (beam_w > 0) chunk = chunk / beam_w >= 1 ? chunk / beam_w * beam_w : beam_w;
     if (chunk > B) chunk = B;
     if (chunk < 1) chunk = 1;
     p.chunk = chunk;
@@ -360,9 +587,22 @@ Plan make_plan(const dvq_pixelcnn_weights* w, int64_t B, void* ws) {
     p.hid = (float*)take((size_t)chunk * w->n_hidden * 4);
     p.lg = (float*)take((size_t)chunk * w->n_in * 4);
     p.lab = (int64_t*)take((size_t)chunk * 8);
+    p.anc[0] = p.anc[1] = nullptr;
+    p.btok = p.blive = p.bnan = nullptr;
+    p.bscore = nullptr;
+    if (beam_w > 0) {
+        p.anc[0] = (int64_t*)take((size_t)NPOS * chunk * 8);
+        p.anc[1] = (int64_t*)take((size_t)NPOS * chunk * 8);
+        p.btok = (int32_t*)take((size_t)NPOS * chunk * 4);
+        p.bscore = (float*)take((size_t)chunk * 4);
+        p.blive = (int32_t*)take((size_t)(chunk / beam_w) * 4);
+        p.bnan = (int32_t*)take((size_t)(chunk / beam_w) * 4);
+    }
     // class tables: fp16-plane kernels only (they read activation rows through an index).  The weights' own when they carry them
     // (any batch size); else built per call in the workspace by batches that are at least twice the table
     p.nc = w->n_classes;
+    // (a beam search reads the tables' activations like any call -- a segment's rows share its label -- but not their accumulator
+    // states: run() never asks for mode 2 there, see "leading sources")
     const bool can = tables_possible(w);
     p.prebuilt = can && w->class_tables != nullptr;
     p.tab = can && (p.prebuilt || B >= 2L * w->n_classes);
@@ -392,7 +632,8 @@ int check_weights(const dvq_pixelcnn_weights* w) {
 // ``ctl`` non-null: the draws of dvq_pixelcnn_sample_ctl (sample_ctl_kernel in sample_kernel's place; ``forced`` is null then)
 int run(const dvq_pixelcnn_weights* w, const int64_t* label, const float* noise, const int64_t* forced, int64_t B,
         int64_t* codes, float* logits_out, int32_t* err_flag, void* ws, size_t ws_bytes, hipStream_t st, void* build = nullptr,
-        const dvq_pixelcnn_ctl* ctl = nullptr) {
+        const dvq_pixelcnn_ctl* ctl = nullptr, const BeamCall* beam = nullptr) {
+    // ``beam`` non-null: dvq_pixelcnn_beam -- ``label`` is [beam->S], B = S * W rows, the draw is beam_score_kernel + beam_expand_kernel
     DVQ_PROPAGATE(check_weights(w));
     Plan pl;
     if (build) {
@@ -404,9 +645,9 @@ int run(const dvq_pixelcnn_weights* w, const int64_t* label, const float* noise,
     } else {
         DVQ_REQUIRE(B >= 0, "pixelcnn: negative batch");
         if (B == 0) return DVQ_OK;
-        DVQ_REQUIRE(label && (forced || (codes && (noise || (ctl && ctl->given)))), "pixelcnn: null input");
+        DVQ_REQUIRE(label && (beam || forced || (codes && (noise || (ctl && ctl->given)))), "pixelcnn: null input");
         DVQ_REQUIRE(ws && dvq_aligned16(ws), "pixelcnn: null/unaligned workspace");
-        pl = make_plan(w, B, ws);
+        pl = make_plan(w, B, ws, beam ? beam->W : 0);
         if (ws_bytes < pl.bytes) {
             dvq_set_error("pixelcnn: workspace %zu < %zu bytes", ws_bytes, pl.bytes);
             return DVQ_EWORKSPACE;
@@ -622,9 +863,27 @@ int run(const dvq_pixelcnn_weights* w, const int64_t* label, const float* noise,
     if (build) return DVQ_OK;
     for (int64_t b0 = 0; b0 < B; b0 += pl.chunk) {
         const long Bc = (long)((B - b0 < pl.chunk) ? (B - b0) : pl.chunk);
-        DVQ_LAUNCH(sanitize_labels_kernel, dim3((unsigned)((Bc + 255) / 256)), dim3(256), 0, st, label + b0, Bc,
-                           w->n_classes, pl.lab, err_flag);
-        DVQ_CHECK_LAUNCH("sanitize_labels");
+        // beam search: the position and grid row being evaluated and which of the two ancestry buffers is current.  ANC(q)[row] = the
+        // row that held ``row``'s ancestor after position q's selection, kept current by every beam_expand_kernel.  What was cached
+        //   at level 0 of position q (the chosen token's embedding) belongs to the survivor:            read through ANC(q);
+        //   at levels >= 1 of position q / of grid row ir (computed from the prefix, before the selection) to the parent:
+        //                                                                                 read through ANC(q - 1) / ANC(3 ir - 1);
+        //   before position 0 depends on the label alone, the same bits in every row of a segment:      read at the own row --
+        //   or, when the plan has class tables, in the tables through the labels as every call does (row 0 and position (0, 0) are
+        //   then not evaluated at all).  The tables' accumulator states are NOT used: their "leading sources" are told apart by
+        //   "has a row index", which here the ancestry has too, so a beam search runs every product whole (mode 0) -- the same bits.
+        int cur_r = 0, cur_pos = 0, acur = 0;
+        auto ANC = [&](int q) -> const int64_t* { return pl.anc[acur] + (size_t)q * pl.chunk; };
+        const long segs = beam ? Bc / beam->W : 0, s0 = beam ? (long)(b0 / beam->W) : 0;
+        if (beam) {
+            DVQ_LAUNCH(beam_init_kernel, dim3((unsigned)((Bc + 255) / 256)), dim3(256), 0, st, label + s0, segs, beam->W, w->n_classes,
+                       pl.lab, pl.bscore, pl.blive, pl.bnan, err_flag);
+            DVQ_CHECK_LAUNCH("beam_init");
+        } else {
+            DVQ_LAUNCH(sanitize_labels_kernel, dim3((unsigned)((Bc + 255) / 256)), dim3(256), 0, st, label + b0, Bc,
+                       w->n_classes, pl.lab, err_flag);
+            DVQ_CHECK_LAUNCH("sanitize_labels");
+        }
         if (forced)   // teacher forcing: level-0 activations of all nine positions are known up front
             for (int pos = 0; pos < NPOS; ++pos)
                 DVQ_PROPAGATE(dvq_launch_gather_rows(w->tok_emb, forced + b0 * NPOS + pos, NPOS, Bc, w->n_in, dim,
@@ -633,33 +892,63 @@ int run(const dvq_pixelcnn_weights* w, const int64_t* label, const float* noise,
         // and position (0, 0)'s horizontal levels >= 1 in the class tables, through the labels
         auto xv_b = [&](int level, int pos) {
             if (pl.tab && level >= 1 && pos < GRID) return Act{pl.XVC(level, pos), pl.lab};
+            if (beam) {
+                const int ir = pos / GRID;
+                if (level == 0) return Act{pl.XV(0, pos), ANC(pos)};
+                if (ir != cur_r && ir > 0) return Act{pl.XV(level, pos), ANC(GRID * ir - 1)};
+            }
             return Act{pl.XV(level, pos), nullptr};
         };
         auto hv_b = [&](int layer, int col, int r) {
             if (pl.tab && r == 0) return Act{pl.HVC(layer, col), pl.lab};
+            if (beam && r > 0 && cur_pos > GRID * r) return Act{pl.HV(layer, col), ANC(GRID * r - 1)};
             return Act{pl.HV(layer, col), nullptr};
         };
         auto xh_b = [&](int level, int pos) {
             if (pl.tab && level >= 1 && pos == 0) return Act{pl.XHC(level), pl.lab};
+            if (beam) {
+                if (level == 0) return Act{pl.XH(0, pos), ANC(pos)};
+                if (pos != cur_pos && pos > 0) return Act{pl.XH(level, pos), ANC(pos - 1)};
+            }
             return Act{pl.XH(level, pos), nullptr};
         };
         for (int r = 0; r < GRID; ++r) {
+            cur_r = r;
+            cur_pos = r * GRID;
             // ---- vertical stack of row r, all layers (depends on rows < r only)
             if (!(pl.tab && r == 0))
                 for (int l = 0; l < L; ++l)
                     DVQ_PROPAGATE(vertical_layer(r, l, Bc, pl.lab, xv_b, [&](int c) { return pl.XV(l + 1, r * GRID + c); },
-                                                 [&](int c) { return pl.HV(l, c); }, (pl.tab && r == 1) ? 2 : 0,
+                                                 [&](int c) { return pl.HV(l, c); }, (pl.tab && r == 1 && !beam) ? 2 : 0,
                                                  [&](int c, int which) { return pl.SV(l, c, which); }));
             // ---- horizontal stack + head + draw, position by position
             for (int c = 0; c < GRID; ++c) {
                 const int pos = r * GRID + c;
+                cur_pos = pos;
                 const bool from_table = pl.tab && pos == 0;     // its logits are the class table's rows
                 if (!from_table)
                     DVQ_PROPAGATE(horizontal_position(r, c, Bc, pl.lab, [&](int layer, int col) { return hv_b(layer, col, r); }, xh_b,
                                                       [&](int level) { return pl.XH(level, pos); }, pl.g, pl.hid, pl.lg,
-                                                      (pl.tab && r == 0) ? 2 : 0,
+                                                      (pl.tab && r == 0 && !beam) ? 2 : 0,
                                                       [&](int layer, int which) { return pl.SH(layer, c, which); }));
-                if (ctl) {
+                if (beam) {
+                    const dvq_pixelcnn_beam_trace* tr = beam->trace;
+                    const size_t toff = ((size_t)pos * beam->S + s0) * beam->W;      // this position, this chunk in a [9,S,W] trace array
+                    {
+                        DVQ_PROF("pixelcnn_beam_score", 0, (double)Bc * 2.0 * w->n_in * 4, st);
+                        DVQ_LAUNCH(beam_score_kernel, dim3((unsigned)((Bc + 3) / 4)), dim3(256), 0, st, pl.lg, w->n_in, Bc, beam->W, pl.bscore,
+                                   pl.blive, pl.bnan, tr && tr->logits ? tr->logits + toff * w->n_in : nullptr,
+                                   from_table ? pl.lgc : nullptr, pl.lab);
+                        DVQ_CHECK_LAUNCH("pixelcnn_beam_score");
+                    }
+                    DVQ_PROF("pixelcnn_beam_expand", 0, (double)Bc * (w->n_in + dim) * 4, st);
+                    DVQ_LAUNCH(beam_expand_kernel, dim3((unsigned)segs), dim3(BEAM_THREADS), 0, st, pl.lg, w->n_in, beam->W, pos, dim, pl.chunk,
+                               pl.blive, pl.bnan, pl.bscore, pl.btok + (size_t)pos * pl.chunk, pl.anc[acur], pl.anc[acur ^ 1], w->tok_emb,
+                               pl.XV(0, pos), err_flag, tr && tr->parent ? tr->parent + toff : nullptr,
+                               tr && tr->token ? tr->token + toff : nullptr, tr && tr->score ? tr->score + toff : nullptr,
+                               tr && tr->live ? tr->live + (size_t)pos * beam->S + s0 : nullptr);
+                    acur ^= 1;
+                } else if (ctl) {
                     DVQ_PROF("pixelcnn_draw", 0, (double)Bc * (2.0 * w->n_in + dim) * 4, st);
                     const dim3 grid((unsigned)((Bc + 3) / 4)), block(256);
                     const float* lgp = from_table ? pl.lgc : pl.lg;
@@ -685,6 +974,11 @@ int run(const dvq_pixelcnn_weights* w, const int64_t* label, const float* noise,
                 }
                 DVQ_CHECK_LAUNCH("pixelcnn_sample_step");
             }
+        }
+        if (beam) {
+            DVQ_LAUNCH(beam_finish_kernel, dim3((unsigned)((Bc + 255) / 256)), dim3(256), 0, st, pl.btok, pl.anc[acur], pl.chunk, Bc, beam->W,
+                       pl.bscore, pl.blive, beam->codes + b0 * NPOS, beam->score + b0, beam->n_live + s0);
+            DVQ_CHECK_LAUNCH("pixelcnn_beam_finish");
         }
     }
     return DVQ_OK;
@@ -726,6 +1020,26 @@ extern "C" int dvq_pixelcnn_sample_ctl(const dvq_pixelcnn_weights* w, const int6
     DVQ_REQUIRE(ctl->top_k >= 0, "pixelcnn_sample_ctl: top_k must be >= 0 (0: off)");
     DVQ_REQUIRE(codes, "pixelcnn_sample_ctl: null codes");
     return run(w, label, noise, nullptr, B, codes, logits_out, err_flag, workspace, workspace_bytes, (hipStream_t)stream, nullptr, ctl);
+}
+
+extern "C" size_t dvq_pixelcnn_beam_workspace_bytes(const dvq_pixelcnn_weights* w, int64_t S, int32_t width) {
+    if (!w || S <= 0 || width < 1 || width > BEAM_MAX_W) return 256;
+    return make_plan(w, S * width, nullptr, width).bytes;
+}
+
+extern "C" int dvq_pixelcnn_beam(const dvq_pixelcnn_weights* w, const int64_t* label, int64_t S, int32_t width, int64_t* codes,
+                                 float* score, int32_t* n_live, const dvq_pixelcnn_beam_trace* trace, int32_t* err_flag,
+                                 void* workspace, size_t workspace_bytes, dvq_stream_t stream) {
+    DVQ_REQUIRE(width >= 1 && width <= BEAM_MAX_W, "pixelcnn_beam: width %d outside 1 .. %d", (int)width, BEAM_MAX_W);
+    DVQ_REQUIRE(S >= 0 && S <= (int64_t)1 << 40, "pixelcnn_beam: bad segment count");
+    DVQ_REQUIRE(w, "pixelcnn_beam: null weights");
+    // the search follows a beam's ancestry through GemmSrc::arow, which only the fp16-plane kernels read
+    DVQ_REQUIRE(w->planes_kind == DVQ_PLANES_F16X2 && w->w0_p && dvq_gemm_mode() == 1,
+                "pixelcnn_beam: fp16 weight images only (DVQ_PLANES_F16X2): the bf16x3 and fp32 GEMMs cannot read activation rows through an index");
+    DVQ_REQUIRE(S == 0 || (codes && score && n_live), "pixelcnn_beam: null output");
+    const BeamCall bc = {S, (int)width, codes, score, n_live, trace};
+    return run(w, label, nullptr, nullptr, S * width, nullptr, nullptr, err_flag, workspace, workspace_bytes, (hipStream_t)stream, nullptr,
+               nullptr, &bc);
 }
 
 extern "C" int dvq_pixelcnn_forward(const dvq_pixelcnn_weights* w, const int64_t* x, const int64_t* label, int64_t B,

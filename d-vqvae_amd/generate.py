@@ -68,6 +68,13 @@ def build_parser(dataset: str) -> argparse.ArgumentParser:
     p.add_argument("--top_k", type=int, default=0, help="draw every grid position from its top_k likeliest codes (0 = all)")
     p.add_argument("--log_prob", type=int, default=0,
                    help="1: every object's JSON gains \"log_prob\", each grasp's log-likelihood under the (untempered) prior")
+    p.add_argument("--beam_width", type=int, default=0,
+                   help="beam search instead of sampling: every pose of an object gets the beam_width likeliest distinct code grids of the "
+                        "prior, in rank order, with no noise (0 = off); num_grasp (or --candidates) must equal beam_poses * beam_width; "
+                        "the JSON gains \"log_prob\", \"beam_pose\", \"beam_rank\", \"beam_duplicate_of\"")
+    p.add_argument("--beam_poses", type=int, default=1,
+                   help="--beam_width: poses per object, drawn as the rotations of its first beam_poses grasps are drawn without the "
+                        "flag; row p * beam_width + r is rank r of pose p (datasets that do not rotate take 1)")
     p.add_argument("--candidates", type=int, default=0,
                    help="best-of-M: generate this many candidates per object, score them on the device and keep the num_grasp best "
                         "(0 = off; otherwise >= num_grasp); the JSON gains \"candidate\", \"penetration\", \"n_interior\", \"n_contact\"")
@@ -252,6 +259,20 @@ def parse_args(dataset: str, argv: Optional[Sequence[str]] = None) -> argparse.N
         p.error(f"--self_seam must be >= 0 (got {args.self_seam})")
     if args.max_self_verts is not None and args.max_self_verts < 0:
         p.error(f"--max_self_verts must be >= 0 (got {args.max_self_verts})")
+    if not 0 <= args.beam_width <= ops.PIXELCNN_BEAM_MAX_W or args.beam_poses < 1:
+        p.error(f"--beam_width must lie between 0 and {ops.PIXELCNN_BEAM_MAX_W} and --beam_poses be at least 1 "
+                f"(got {args.beam_width}, {args.beam_poses})")
+    if not args.beam_width and args.beam_poses != 1:
+        p.error("--beam_poses needs --beam_width (it counts the poses a beam search runs for)")
+    if args.beam_width:
+        if args.beam_poses != 1 and not DATASETS[dataset]["rotate"]:
+            p.error(f"--beam_poses must be 1 for {dataset}: its objects are not rotated, every pose would be the same search")
+        rows = args.beam_poses * args.beam_width
+        if (args.candidates or args.num_grasp) != rows:
+            p.error(f"--beam_width: {'--candidates' if args.candidates else '--num_grasp'} must equal --beam_poses * --beam_width = {rows} "
+                    f"(got {args.candidates or args.num_grasp})")
+        if args.temperature != 1.0 or args.top_k != 0:
+            p.error("--beam_width excludes --temperature and --top_k: a beam search draws nothing")
     if args.max_self_verts is not None and not args.candidates:
         p.error("--max_self_verts needs --candidates (it ranks candidates; --self_collision 1 alone writes the figures)")
     return args
@@ -486,7 +507,8 @@ def _generate_call(net: GenNet, objs: Sequence[torch.Tensor], num_grasp: int, ro
                    max_penetration: float = float("inf"), torque_length: float = 0.1,
                    volume: Optional[Dict[str, float]] = None, parts: Optional[Dict[str, object]] = None,
                    refine_spin: float = 0.0, refine_curl: float = 0.0, refine_max_curl: float = 0.35,
-                   slf: Optional[Dict[str, object]] = None, ttt: Optional[Dict[str, object]] = None) -> List[Dict[str, object]]:
+                   slf: Optional[Dict[str, object]] = None, ttt: Optional[Dict[str, object]] = None,
+                   beam: Optional[Sequence[int]] = None) -> List[Dict[str, object]]:
     """One batched call: the ``num_grasp`` grasps of each of ``objs`` (all of one point count), row o * num_grasp + g = grasp g
     of object o.  Every step is row-independent and keyed per row, so each object's slice holds the bits of its own
     ``generate_for_object`` call.  With ``candidates`` = M the call generates M rows per object (exactly the grasps of a
@@ -508,13 +530,26 @@ def _generate_call(net: GenNet, objs: Sequence[torch.Tensor], num_grasp: int, ro
     ONE ``contact.grasp_self`` runs over all rows of the call, after the push-out too -- the hands against themselves; its six
     tensors ride in that copy and become the fields of _self_json.  With ``ttt`` (``steps``, ``lr``, ``momentum``, ``w_pen``, ``w_con``,
     ``targets``, ``keep_best``) every row goes through ``contact.refine_ttt`` after any push-out and MANO is posed again, so that
-    everything after it sees the refined hands; the rows' three figures travel in a small copy of their own (_ttt_attach)."""
+    everything after it sees the refined hands; the rows' three figures travel in a small copy of their own (_ttt_attach).
+    With ``beam`` = (P, W), P * W = the rows per object, nothing is drawn: every object gets P poses (the rotations of its first P rows),
+    every pose ONE beam search of width W (GenNet.gen_beam on the call's O * P posed clouds); row p * W + r holds rank r of pose p, and
+    everything after the parameters sees ordinary rows.  The rows' log-likelihoods are the beams' scores (``log_prob`` is on), and the
+    dicts and JSON gain ``beam_pose``, ``beam_rank``, ``beam_duplicate_of`` per grasp kept (_beam_attach)."""
     dev = next(net.parameters()).device
     keep = num_grasp
     G, O = (candidates or num_grasp), len(objs)
+    if beam:
+        if beam[0] * beam[1] != G or (beam[0] != 1 and not rotate) or float(temperature) != 1.0 or int(top_k) != 0:
+            raise RuntimeError(f"_generate_call: beam = {tuple(beam)} needs {G} = poses * width rows per object, one pose without rotation, "
+                               "and no temperature / top_k")
+        log_prob = True                                                            # the beams' scores: always there, always written
     want_logp = log_prob
     log_prob = log_prob or (bool(candidates) and select_by == "log_prob")
-    if rotate:                                                                     # each object's own generator, as the loop draws them
+    if rotate and beam:                                                            # the first P draws of each object's generator, W rows each
+        angles = [np.repeat(np.random.default_rng([seed, int(gi)]).random((beam[0], 3)) * np.pi * 2, beam[1], axis=0) for gi in object_indices]
+        Rs = [rotation_xyz(a) for a in angles]
+        t = np.asarray(CANONICAL_OFFSET)
+    elif rotate:                                                                   # each object's own generator, as the loop draws them
         angles = [np.random.default_rng([seed, int(gi)]).random((G, 3)) * np.pi * 2 for gi in object_indices]
         Rs = [rotation_xyz(a) for a in angles]
         t = np.asarray(CANONICAL_OFFSET)
@@ -529,8 +564,13 @@ def _generate_call(net: GenNet, objs: Sequence[torch.Tensor], num_grasp: int, ro
     err = ops.new_err_flag(dev)                                                    # read after the parameters' copy below: no extra sync
     R_dev, t_dev = torch.as_tensor(np.concatenate(Rs), dtype=torch.float32, device=dev), torch.as_tensor(t, dtype=torch.float32, device=dev)
     batch = ops.transform_clouds(clouds, obj_of_row, R_dev, t_dev, err=err)
-    recon, pos, *rest = net.gen(batch, seed=seed, row_keys=(stream_ids, row_ids), **_prior_controls(temperature, top_k, log_prob))
-    logp = grasp_log_prob(rest[0]["logp_model"]) if log_prob else None
+    baux = None
+    if beam:                                                                       # one search per posed cloud: rows 0, W, 2 W, ... of the batch
+        recon, pos, baux = net.gen_beam(batch[::beam[1]].contiguous(), int(beam[1]), return_aux=True)
+        logp = baux["log_prob"]
+    else:
+        recon, pos, *rest = net.gen(batch, seed=seed, row_keys=(stream_ids, row_ids), **_prior_controls(temperature, top_k, log_prob))
+        logp = grasp_log_prob(rest[0]["logp_model"]) if log_prob else None
     params = ops.assemble61(recon, pos)                                            # obman.py:243-247
     final = net.rh_mano(betas=params[:, :10], global_orient=params[:, 10:13], hand_pose=params[:, 13:58],
                         transl=params[:, 58:61])                                   # obman.py:252-253
@@ -574,9 +614,10 @@ def _generate_call(net: GenNet, objs: Sequence[torch.Tensor], num_grasp: int, ro
         from . import contact
         sco = contact.grasp_self(_hand_topology(net, final.vertices.shape[1], dev), slf["table"], final.vertices, slf["reach"], slf["margin"])
     if candidates:
-        return _ttt_attach(_select_call(net, batch, params, final.vertices, logp, err, O, G, keep, select_by, min_contact, want_logp, proxies,
-                                        np.concatenate(Rs), np.concatenate(angles), t, diverse_pool, diverse_space, refined, diversity,
-                                        stability, max_penetration, torque_length, vol, volume, prt, parts, sco, slf), tuned, G)
+        return _beam_attach(_ttt_attach(_select_call(net, batch, params, final.vertices, logp, err, O, G, keep, select_by, min_contact, want_logp,
+                                                     proxies, np.concatenate(Rs), np.concatenate(angles), t, diverse_pool, diverse_space, refined,
+                                                     diversity, stability, max_penetration, torque_length, vol, volume, prt, parts, sco, slf),
+                                        tuned, G), baux, beam)
     ref_lists = {}
     div = _diversity_launch(params, O, G, diversity) if diversity else []
     prt_t = [prt[k] for k in PARTS_PIECES] if prt is not None else []             # last before the flag in the call's one copy
@@ -679,7 +720,25 @@ def _generate_call(net: GenNet, objs: Sequence[torch.Tensor], num_grasp: int, ro
         outs.append({**extra, "params": p_dev[o], "vertices": v_dev[o],
                      "json": {"recon_params": [[p] for p in p_list[lo:hi]],           # [[61 floats]] per grasp, as the reference
                               "R_list": Rt_list[lo:hi], "trans_list": [trans] * G, "r_list": r_list[lo:hi], **extra_json}})
-    return _ttt_attach(outs, tuned, G)
+    return _beam_attach(_ttt_attach(outs, tuned, G), baux, beam)
+
+
+def _beam_attach(outs: List[Dict[str, object]], baux: Optional[Dict[str, torch.Tensor]], beam: Optional[Sequence[int]]) -> List[Dict[str, object]]:
+    """``--beam_width``: where each grasp of a call's dicts came from -- all P * W rows of every object, or with best-of-M the rows
+    ``candidate`` names -- as ``beam_pose``, ``beam_rank`` and ``beam_duplicate_of`` (the rank, within the same pose, of the first
+    better beam with the same six hand codes, or -1: GenNet.beam_duplicates) int64 tensors and JSON lists.  The duplicates table of the
+    call's O * P searches travels in a small copy of its own."""
+    if baux is None:
+        return outs
+    P, W = int(beam[0]), int(beam[1])
+    dup = baux["duplicate_of"].view(len(outs), P * W)
+    dup_h = dup.cpu().numpy()
+    for o, out in enumerate(outs):
+        cand = np.asarray(out["json"]["candidate"], dtype=np.int64) if "candidate" in out["json"] else np.arange(P * W)
+        out["beam_pose"], out["beam_rank"] = torch.from_numpy(cand // W), torch.from_numpy(cand % W)
+        out["beam_duplicate_of"] = dup[o] if "candidate" not in out else dup[o].index_select(0, out["candidate"].reshape(-1))
+        out["json"].update(beam_pose=(cand // W).tolist(), beam_rank=(cand % W).tolist(), beam_duplicate_of=dup_h[o][cand].tolist())
+    return outs
 
 
 TTT_PIECES = ("loss0", "loss", "iter")   # of contact.refine_ttt's dict: what rides to the host, in this order
@@ -968,7 +1027,7 @@ def generate_for_objects(net: GenNet, objs: Sequence[torch.Tensor], num_grasp: i
                          self_margin: float = 0.001, self_seam: int = 2, self_palm: bool = True,
                          max_self_verts: Optional[int] = None, ttt_steps: int = 0, ttt_lr: float = 6.25e-6,
                          ttt_momentum: float = 0.8, ttt_w_pen: float = 840.0, ttt_w_con: float = 7500.0, ttt_prior=None,
-                         ttt_keep_best: bool = True) -> List[Dict[str, object]]:
+                         ttt_keep_best: bool = True, beam_width: int = 0, beam_poses: int = 1) -> List[Dict[str, object]]:
     """``num_grasp`` grasps for each of ``objs`` ([4,N] tensors) in batched calls that mix objects (plan_calls): one dict per
     object, in the order given, equal to ``generate_for_object(net, objs[i], num_grasp, rotate,
     np.random.default_rng([seed, object_indices[i]]), seed=seed, object_index=object_indices[i], proxies=proxies)`` (and the same
@@ -1077,7 +1136,29 @@ def generate_for_objects(net: GenNet, objs: Sequence[torch.Tensor], num_grasp: i
     JSON list of vertex indices (the reference's 204).  The dicts gain ``ttt_loss0``, ``ttt_loss`` [num_grasp] f32 and ``ttt_iter``
     [num_grasp] i32, and the JSON the same three lists (a loss that is not finite: null), through a small copy of their own.  Rows are
     refined independently: the results do not depend on ``rows_per_call``; ``ttt_steps = 0`` is the call without the keyword.  The
-    constants are the reference's and untuned here; the effect on real grasps is not measured."""
+    constants are the reference's and untuned here; the effect on real grasps is not measured.
+
+    Beam search (``beam_width`` = W > 0, ``beam_poses`` = P, P * W = ``candidates`` or ``num_grasp``): nothing is drawn.  Every object
+    gets P poses -- the rotations of its first P grasp rows of the call without the keyword; P = 1 without ``rotate`` -- and every pose
+    ONE ``GenNet.gen_beam`` search: row p * W + r is the r-th likeliest distinct code grid of pose p under the prior, decoded as
+    ``gen`` decodes it.  Push-out, refinement, scores, selection and diversity see ordinary rows.  The dicts and ``json`` gain
+    ``log_prob`` (the beam's score), ``beam_pose``, ``beam_rank`` and ``beam_duplicate_of`` (the rank within the pose of the first
+    better beam with the same six hand codes, or -1).  Excludes ``temperature`` / ``top_k``; the searches of a call do not depend on
+    one another, so the results do not depend on ``rows_per_call``.  fp16 weight images only, no bf16 fallback inside the search;
+    whether likelier grids are better grasps is not measured.  ``beam_width = 0`` is the call without the keyword."""
+    beam = None
+    if beam_width:
+        rows = candidates or num_grasp
+        if not 1 <= int(beam_width) <= ops.PIXELCNN_BEAM_MAX_W or int(beam_poses) < 1 or int(beam_width) * int(beam_poses) != rows:
+            raise RuntimeError(f"generate_for_objects: beam_width in 1 .. {ops.PIXELCNN_BEAM_MAX_W} and beam_poses * beam_width = "
+                               f"{'candidates' if candidates else 'num_grasp'} (got {beam_width}, {beam_poses} for {rows} rows)")
+        if int(beam_poses) != 1 and not rotate:
+            raise RuntimeError("generate_for_objects: beam_poses must be 1 without rotation")
+        if float(temperature) != 1.0 or int(top_k) != 0:
+            raise RuntimeError("generate_for_objects: beam_width excludes temperature and top_k")
+        beam = (int(beam_poses), int(beam_width))
+    elif int(beam_poses) != 1:
+        raise RuntimeError("generate_for_objects: beam_poses needs beam_width")
     self_args = None
     if self_collision or max_self_verts is not None:
         if not 0.0 < float(self_reach) < float("inf") or not 0.0 <= float(self_margin) < float("inf"):
@@ -1175,7 +1256,7 @@ def generate_for_objects(net: GenNet, objs: Sequence[torch.Tensor], num_grasp: i
         res = _generate_call(net, [objs[p] for p in call], num_grasp, rotate, seed, [object_indices[p] for p in call], proxies,
                              temperature, top_k, log_prob, candidates, select_by, min_contact, diverse_pool, diverse_space, refine_steps,
                              refine_push, refine_pull, diversity, stability, max_penetration, torque_length, vol_args, parts_args,
-                             float(refine_spin), float(refine_curl), float(refine_max_curl), self_args, ttt_args)
+                             float(refine_spin), float(refine_curl), float(refine_max_curl), self_args, ttt_args, beam)
         for p, r in zip(call, res):
             out[p] = r
     return out
@@ -1223,7 +1304,7 @@ def main(dataset: str, argv: Optional[Sequence[str]] = None) -> List[str]:
     want_parts = bool(args.parts) or args.min_fingers > 0 or bool(args.need_thumb)
     want_self = bool(args.self_collision) or args.max_self_verts is not None
     if (args.rows_per_call > 0 or args.candidates or args.refine_steps or args.diversity or args.stability or want_volume or want_parts
-            or want_self or args.ttt_steps):
+            or want_self or args.ttt_steps or args.beam_width):
         # grouped calls (best-of-M, push-out, the diversity statistic and the stability proxy always: --rows_per_call 0 is then one
         # object per call)
         rows_per_call, per_object = max(1, args.rows_per_call), (args.candidates or args.num_grasp)
@@ -1242,6 +1323,8 @@ def main(dataset: str, argv: Optional[Sequence[str]] = None) -> List[str]:
                              ttt_w_con=args.ttt_w_con, ttt_prior=args.ttt_prior, ttt_keep_best=bool(args.ttt_keep_best))
         if args.diversity:
             selection.update(diversity=args.diversity)
+        if args.beam_width:
+            selection.update(beam_width=args.beam_width, beam_poses=args.beam_poses)
         if args.stability or (args.candidates and args.select_by == "stability"):
             selection.update(stability=True, max_penetration=args.max_penetration, torque_length=args.torque_length)
         if want_volume:

@@ -259,6 +259,77 @@ class GenNet(nn.Module):
             aux["fallback_rows"] = rows
         return (recon, recon_pos, aux) if return_aux else (recon, recon_pos)
 
+    @staticmethod
+    def beam_duplicates(codes, n_live):
+        """codes [S,W,3,3] / [S,W,9] int64, n_live [S] -> int64 [S,W]: the rank of the first better beam of the same cloud with the
+        same six CODE_SLOTS codes (the hand decodes from those alone: such a beam is the same grasp), or -1."""
+        S, W = codes.shape[:2]
+        six = codes.reshape(S, W, 9)[:, :, [i * 3 + j for i, j in CODE_SLOTS]]
+        rank = torch.arange(W, device=codes.device)
+        live = rank[None, :] < n_live[:, None].to(torch.int64)
+        same = (six[:, :, None, :] == six[:, None, :, :]).all(dim=-1) & (rank[None, :] < rank[:, None])[None] & live[:, None, :] & live[:, :, None]
+        first = torch.where(same, rank[None, None, :], torch.full_like(rank, W)[None, None, :]).min(dim=2).values
+        return torch.where(first < W, first, torch.full_like(first, -1))
+
+    @torch.no_grad()
+    def gen_beam(self, obj, width, return_aux=False):
+        """obj [S,4,N] f32 on the GPU -> (recon [S*W,55], recon_pos [S*W,6]): row s * W + r is the grasp decoded from the r-th
+        likeliest code grid of cloud s under the prior (ops.pixelcnn_beam) -- no noise, nothing drawn.  Both object
+        encoders and the object codebook run once per cloud; their features are repeated into the W rows, and the decode, MANO,
+        recon_encoder and pos_decoder are gen()'s launches on S * W rows: the result equals
+        ``gen(obj.repeat_interleave(W, 0), codes=aux["codes"])`` bit for bit.
+        ``aux``: ``codes`` [S*W,3,3], ``log_prob`` [S*W] (the beam's score: its nine log-probabilities summed in float32),
+        ``n_live`` [S] int32, ``duplicate_of`` [S,W] (beam_duplicates; beams are distinct on nine tokens, the hand uses six),
+        ``idx6`` [S,1], ``verts`` [S*W,3,778].  Rows beyond a cloud's n_live (fewer than W grids exist) come out NaN.
+        Rows whose parameters are not finite (fp16 range in the decoders) are generated again by ``gen(codes=...)``, which has the
+        bf16 fallback; the SEARCH has none: a cloud whose logits held a NaN raises."""
+        if obj.dim() != 3:
+            raise RuntimeError(f"gen_beam: expected obj [S,4,N], got {tuple(obj.shape)}")
+        if isinstance(width, bool) or not isinstance(width, int) or not 1 <= width <= ops.PIXELCNN_BEAM_MAX_W:
+            raise RuntimeError(f"gen_beam: width must be an integer in 1 .. {ops.PIXELCNN_BEAM_MAX_W}, got {width!r}")
+        S, W, dev = obj.shape[0], width, obj.device
+        B = S * W
+        obj = obj.contiguous()
+        with ops.no_range_check():
+            z1 = torch.empty(S, 2560, device=dev, dtype=torch.float32)
+            p1 = torch.empty(S, 2048, device=dev, dtype=torch.float32)
+            self.obj_encoder_type(obj, out=z1[:, 1536:])
+            self.obj_encoder_pos(obj, out=p1[:, 1024:])
+            idx6, _ = self.vqvae6.inference(z1[:, 1536:])
+            label = idx6[:, 0].contiguous()
+            err = ops.new_err_flag(dev)
+            codes, score, n_live = ops.pixelcnn_beam(self.GatedPixelCNN.packed(), label, W, err=err)
+            z_out = torch.empty(B, 2560, device=dev, dtype=torch.float32)
+            z_pos = torch.empty(B, 2048, device=dev, dtype=torch.float32)
+            z_out.view(S, W, 2560)[:, :, 1536:] = z1[:, None, 1536:]
+            z_pos.view(S, W, 2048)[:, :, 1024:] = p1[:, None, 1024:]
+            codes = codes.view(B, 3, 3)
+            recon = self._decode(codes.clamp_min(0), {"z_out": z_out}, None, err)
+            verts = self._hand_vertices(recon)
+            self.recon_encoder(verts, out=z_pos[:, :1024])
+            recon_pos = self.pos_decoder(z_pos).view(B, 6)
+        status = int(err.item())
+        if status & 1:
+            raise RuntimeError(self._RANGE_ERROR)
+        if status & 4:
+            raise RuntimeError(f"GenNet.gen_beam: NaN logits in the search of clouds {(n_live == 0).nonzero().reshape(-1).tolist()} "
+                               "(an activation beyond fp16's range); the beam search has no bf16 fallback")
+        live = (torch.arange(W, device=dev)[None, :] < n_live[:, None]).reshape(B)
+        bad = live & ~(torch.isfinite(recon).all(dim=1) & torch.isfinite(recon_pos).all(dim=1))
+        rows = bad.nonzero().reshape(-1)
+        if rows.numel():
+            self.range_fallbacks += 1
+            self.range_fallback_rows += int(rows.numel())
+            r2, p2, aux2 = self.gen(obj.index_select(0, rows // W), codes=codes.index_select(0, rows), return_aux=True)
+            recon[rows], recon_pos[rows], verts[rows] = r2, p2, aux2["verts"]
+        dead = ~live
+        recon[dead], recon_pos[dead], verts[dead] = float("nan"), float("nan"), float("nan")
+        if not return_aux:
+            return recon, recon_pos
+        aux = dict(codes=codes, log_prob=score.view(B), n_live=n_live, duplicate_of=self.beam_duplicates(codes.view(S, W, 9), n_live),
+                   idx6=idx6, verts=verts, err=err)
+        return recon, recon_pos, aux
+
     @torch.no_grad()
     def gen_byid(self, idx6, noise=None):
         """Debug variant (gen_net.py:41-75): samples codes for a given object code, then decodes an all-zero

@@ -72,6 +72,11 @@ class GatedPixelCNN(PackedModule):
         return ops.pixelcnn_sample(pk, label, noise.contiguous(), return_logits=return_logits, temperature=temperature, top_k=top_k,
                                    given=given, return_logp=return_logp)
 
+    def beam_search(self, label, width, trace=False):
+        """The ``width`` likeliest distinct code grids of every label under the prior, in rank order (ops.pixelcnn_beam):
+        (codes [S,W,3,3] int64, log_prob [S,W] f32, n_live [S] int32); rows beyond n_live hold -1 / -inf.  Deterministic: no noise."""
+        return ops.pixelcnn_beam(self.packed(), label.reshape(-1).contiguous(), width, trace=trace)
+
     def log_prob(self, x, label):
         """log p(x[b, position] | earlier positions, label[b]) under the prior, [B,9] fp32 in raster order, for code grids
         x [B,3,3] / [B,9] int64: every position given to the controlled sampler, read as logp_model (no noise is drawn)."""

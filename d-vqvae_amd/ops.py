@@ -498,6 +498,61 @@ def pixelcnn_sample(packed, label: Tensor, noise: Optional[Tensor], return_logit
     return out if len(out) > 1 else codes
 
 
+PIXELCNN_BEAM_MAX_W = 1024          # csrc/pixelcnn.hip: BEAM_MAX_W (a segment's survivors are ordered in LDS)
+
+
+def pixelcnn_beam(packed, label: Tensor, width: int, trace: bool = False, err: Optional[Tensor] = None):
+    """Beam search over the prior (include/dvq.h: dvq_pixelcnn_beam): label [S] int64 -> (codes [S,W,3,3] int64, score [S,W] f32,
+    n_live [S] int32), the ``width`` likeliest distinct code grids of every label in rank order; rows beyond n_live hold -1 / -inf.
+    ``trace=True`` appends a dict of the per-position selections: parent, token [9,S,W] int32, score [9,S,W] f32, live [9,S] int32,
+    logits [9,S,W,n_in] f32.  No noise, no temperature: the result is a function of the weights and the labels.
+    fp16 weight images only: the search has no bf16 fallback.  With a caller-supplied ``err`` flag nothing synchronises here;
+    otherwise a label out of range and a segment whose logits held a NaN (n_live = 0) raise."""
+    if isinstance(width, bool) or not isinstance(width, int) or not 1 <= width <= PIXELCNN_BEAM_MAX_W:
+        raise RuntimeError(f"pixelcnn_beam: width must be an integer in 1 .. {PIXELCNN_BEAM_MAX_W}, got {width!r}")
+    if not torch.is_tensor(label):
+        raise RuntimeError("pixelcnn_beam: label must be a tensor")
+    _i64(label, "label")
+    if label.dim() != 1 or not label.is_contiguous():
+        raise RuntimeError("pixelcnn_beam: label must be a contiguous [S] tensor")
+    dev = _require_gpu(label, err)
+    from . import packing
+    if packing.gemm_kind() != _lib.PLANES_F16X2:
+        raise RuntimeError("pixelcnn_beam: the search runs on the fp16 weight images only (it follows a beam's ancestry through the "
+                           "row index of the fp16-plane GEMMs); there is no bf16 beam")
+    lib = _lib.load()
+    packed.to(dev)
+    S, W, n_in = label.shape[0], width, packed.n_in
+    codes = torch.empty(S, W, 3, 3, dtype=torch.int64, device=dev)
+    score = torch.empty(S, W, dtype=torch.float32, device=dev)
+    n_live = torch.empty(S, dtype=torch.int32, device=dev)
+    tr, ctr = None, None
+    if trace:
+        tr = dict(parent=torch.empty(9, S, W, dtype=torch.int32, device=dev), token=torch.empty(9, S, W, dtype=torch.int32, device=dev),
+                  score=torch.empty(9, S, W, dtype=torch.float32, device=dev), live=torch.empty(9, S, dtype=torch.int32, device=dev),
+                  logits=torch.empty(9, S, W, n_in, dtype=torch.float32, device=dev))
+        ctr = _lib.PixelcnnBeamTrace(*(tr[k].data_ptr() for k in ("parent", "token", "score", "live", "logits")))
+    own_err = err is None
+    if own_err:
+        err = new_err_flag(dev)
+    if S > 0:
+        nws = lib.dvq_pixelcnn_beam_workspace_bytes(C.byref(packed.cstruct), S, W)
+        ws = workspace(nws, dev)
+        with torch.cuda.device(dev):
+            check(lib.dvq_pixelcnn_beam(C.byref(packed.cstruct), label.data_ptr(), S, W, codes.data_ptr(), score.data_ptr(),
+                                        n_live.data_ptr(), C.byref(ctr) if ctr is not None else None, err.data_ptr(), ws.data_ptr(),
+                                        ws.numel(), _stream(dev)), "dvq_pixelcnn_beam")
+    if own_err:
+        e = int(err.item())
+        if e & 1:
+            raise RuntimeError(f"label out of range for the prior's {packed.n_classes} classes")
+        if e & 4:
+            bad = (n_live == 0).nonzero().reshape(-1).tolist()
+            raise RuntimeError(f"pixelcnn_beam: NaN logits in the search of segments {bad} (an activation beyond fp16's range); "
+                               "there is no bf16 beam")
+    return (codes, score, n_live) + ((tr,) if trace else ())
+
+
 def pixelcnn_forward(packed, x: Tensor, label: Tensor) -> Tensor:
     """x [B,3,3] int64 tokens, label [B] -> logits [B,n_in,3,3] (GatedPixelCNN.forward)."""
     lib = _lib.load()

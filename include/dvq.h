@@ -43,7 +43,8 @@ typedef enum {
 /* Entry points added since 10 without touching a struct or a signature of it (a compatible extension: bindings of 10 keep
  * working, the version stays): dvq_pixelcnn_sample_ctl, dvq_grasp_scores, dvq_segment_topk, dvq_segment_diverse,
  * dvq_grasp_refine, dvq_segment_kmeans, dvq_grasp_wrench, dvq_grasp_volume, dvq_grasp_parts, dvq_grasp_refine_rigid,
- * dvq_grasp_refine_fingers, dvq_grasp_self, dvq_mano_backward_workspace_bytes, dvq_mano_backward, dvq_grasp_ttt. */
+ * dvq_grasp_refine_fingers, dvq_grasp_self, dvq_mano_backward_workspace_bytes, dvq_mano_backward, dvq_grasp_ttt,
+ * dvq_pixelcnn_beam_workspace_bytes, dvq_pixelcnn_beam. */
 int dvq_abi_version(void);
 const char* dvq_last_error(void);
 /* number of visible HIP devices, or -1; does not create a context */
@@ -269,6 +270,35 @@ int dvq_pixelcnn_sample_ctl(const dvq_pixelcnn_weights* w_host, const int64_t* l
 int dvq_pixelcnn_forward(const dvq_pixelcnn_weights* w_host, const int64_t* x, const int64_t* label,
                          int64_t B, float* logits /* [B,9,n_in] */, int32_t* err_flag,
                          void* workspace, size_t workspace_bytes, dvq_stream_t stream);
+/* Beam search over the prior: for each of S labels (segments) the `width` most probable distinct code grids, in rank order, with
+ * no noise.  Positions 0 .. 8 are visited in the sampler's (raster) order; before position 0 a segment has one live beam of score
+ * +0.0f.  At position p every live beam b (b = its rank) has logits l_b: the bits dvq_pixelcnn_forward returns at position p for
+ * any grid that starts with b's prefix.  Candidate (b, k), flat index b * n_in + k, has score
+ *     score_b + lm,   lm = (l_b[k] - mx) - logf(sum)
+ * with mx and sum as dvq_pixelcnn_sample_ctl computes them for logp_model at temperature 1 without top-k (same per-lane stride,
+ * same butterfly order), and one float32 addition.  The min(width, live * n_in) candidates with the largest scores survive; the
+ * comparison is on the integer order key of the float32 score (-0 counts as +0), ties go to the lower flat index.  Survivors are
+ * stored in rank order: score descending, then flat index ascending.
+ *   codes [S,W,9] int64 (raster order), score [S,W] f32 = the sum of the nine lm in position order, n_live [S] int32; rows beyond
+ *   n_live hold code -1 and score -INFINITY.
+ * *err_flag: a NaN candidate score (a NaN logit) in any live row of a segment sets bit 2; that segment comes out with n_live = 0
+ * and every code -1, the others are unaffected.  A label out of range sets bit 0 and the segment proceeds from label 0.
+ * 1 <= width <= 1024, fp16 weight images (DVQ_PLANES_F16X2) only: anything else is DVQ_EINVAL before any launch.
+ * trace (optional, each array optional): what every position selected -- parent [9,S,W] int32 (the parent's rank; -1 beyond the
+ * live count), token [9,S,W] int32, score [9,S,W] f32, live [9,S] int32 (after the position), logits [9,S,W,n_in] f32 (the rows'
+ * logits BEFORE the position's selection: meaningful for the ranks below the previous live count, 1 at position 0). */
+typedef struct {
+    int32_t* parent;
+    int32_t* token;
+    float* score;
+    int32_t* live;
+    float* logits;
+} dvq_pixelcnn_beam_trace;
+size_t dvq_pixelcnn_beam_workspace_bytes(const dvq_pixelcnn_weights* w_host, int64_t S, int32_t width);
+int dvq_pixelcnn_beam(const dvq_pixelcnn_weights* w_host, const int64_t* label /* [S] */, int64_t S, int32_t width,
+                      int64_t* codes /* [S,W,9] */, float* score /* [S,W] */, int32_t* n_live /* [S] */,
+                      const dvq_pixelcnn_beam_trace* trace /* or null */, int32_t* err_flag,
+                      void* workspace, size_t workspace_bytes, dvq_stream_t stream);
 
 /* ------------------------------------------------------------------ MANO layer (third-party `mano`
  * package at network/gen_net.py:116-118 and gen_diverse_grasp_obman.py:252-253; restated, unpinned)
