@@ -5,6 +5,7 @@
 ``oracle/contact_oracle.py`` (a numpy restatement of the published algorithms), not against pytorch3d output.
 """
 import json
+import math
 import os
 
 import numpy as np
@@ -500,6 +501,157 @@ def volume_limit(max_volume, res):
     """``--max_volume`` X cm^3 as the largest voxel count allowed, floor(X / (res^3 * 1e6)) in float64; +inf -> 2^31 - 1 (no limit)."""
     x = float(max_volume) / (float(res) ** 3 * 1e6)
     return int(min(np.floor(x), 2 ** 31 - 1))
+
+
+class ObjectMeshes:
+    """The triangle meshes of a call's objects, packed for ``grasp_mesh``: a list of ``(verts [n,3], faces [m,3])`` -> ``verts`` fp32
+    [sum n, 3], ``vert_off`` int32 [O+1], ``faces`` int32 [sum m, 3] (indices local to each object's vertices) and ``face_off`` int32
+    [O+1] as numpy arrays, uploaded once per device by ``on``.  ``closed[o]``: every edge of object o is used by exactly two faces,
+    once in each direction (computed here, on the host) -- only then is "inside" defined; an open mesh is NOT refused, as the
+    reference does not refuse it either.  Refused: a face index outside the object's vertices, an object without a face, and more
+    than ``ops.GRASP_MESH_MAX_FACES`` faces per object (decimate the mesh first)."""
+
+    def __init__(self, meshes, device=None):
+        vs, fs, self.closed = [], [], []
+        for o, (v, f) in enumerate(meshes):
+            v = np.asarray(v.detach().cpu() if torch.is_tensor(v) else v)
+            f = np.asarray(f.detach().cpu() if torch.is_tensor(f) else f)
+            if v.ndim != 2 or v.shape[1] != 3 or f.ndim != 2 or f.shape[1] != 3 or f.dtype.kind not in "iu":
+                raise RuntimeError(f"ObjectMeshes: object {o}: verts must be [n,3] and faces an integer [m,3] (got {v.shape}, {f.dtype} {f.shape})")
+            if f.shape[0] < 1:
+                raise RuntimeError(f"ObjectMeshes: object {o} has no face")
+            if f.shape[0] > ops.GRASP_MESH_MAX_FACES:
+                raise RuntimeError(f"ObjectMeshes: object {o} has {f.shape[0]} faces, at most {ops.GRASP_MESH_MAX_FACES} fit: "
+                                   "decimate the mesh first")
+            f = f.astype(np.int64)
+            if f.min() < 0 or f.max() >= v.shape[0]:
+                raise RuntimeError(f"ObjectMeshes: object {o}: a face index is outside [0, {v.shape[0]})")
+            vs.append(v.astype(np.float32))
+            fs.append(f.astype(np.int32))
+            self.closed.append(self._closed(f, v.shape[0]))
+        self.n_objects = len(vs)
+        self.vert_off, self.face_off = np.zeros(len(vs) + 1, np.int64), np.zeros(len(fs) + 1, np.int64)
+        self.vert_off[1:], self.face_off[1:] = np.cumsum([len(v) for v in vs]), np.cumsum([len(f) for f in fs])
+        if self.vert_off[-1] >= 2 ** 31 or self.face_off[-1] >= 2 ** 31:
+            raise RuntimeError("ObjectMeshes: too many vertices or faces")
+        self.vert_off, self.face_off = self.vert_off.astype(np.int32), self.face_off.astype(np.int32)
+        self.verts = np.concatenate(vs).reshape(-1, 3) if vs else np.zeros((0, 3), np.float32)
+        self.faces = np.concatenate(fs).reshape(-1, 3) if fs else np.zeros((0, 3), np.int32)
+        self._dev = {}
+        if device is not None:
+            self.on(torch.device(device))
+
+    @staticmethod
+    def _closed(f, n):
+        """Every directed edge at most once, and its reverse exactly as often."""
+        d = np.concatenate([f[:, [0, 1]], f[:, [1, 2]], f[:, [2, 0]]])
+        if (d[:, 0] == d[:, 1]).any():
+            return False
+        fwd, rev = np.sort(d[:, 0] * n + d[:, 1]), np.sort(d[:, 1] * n + d[:, 0])
+        return bool((np.diff(fwd) != 0).all() and np.array_equal(fwd, rev))
+
+    def on(self, device):
+        """(verts, vert_off, faces, face_off) on ``device`` (uploaded once per device)."""
+        key = str(device)
+        if key not in self._dev:
+            self._dev[key] = tuple(torch.from_numpy(np.ascontiguousarray(x)).to(device)
+                                   for x in (self.verts, self.vert_off, self.faces, self.face_off))
+        return self._dev[key]
+
+
+def load_mesh(path):
+    """``(verts float64 [n,3], faces int64 [m,3])`` from a ``.npz`` with ``verts`` and ``faces``, or from a Wavefront ``.obj`` of
+    ``v`` and ``f`` lines (other lines are skipped): polygons are fan-triangulated, the ``v/vt/vn`` index forms are accepted, indices
+    are 1-based and negative ones count from the end, as the format says.  Nothing else is read (no trimesh)."""
+    ext = os.path.splitext(str(path))[1].lower()
+    if ext == ".npz":
+        with np.load(path) as z:
+            if "verts" not in z.files or "faces" not in z.files:
+                raise RuntimeError(f"load_mesh: {path}: an .npz needs the arrays 'verts' and 'faces' (has {sorted(z.files)})")
+            verts, faces = np.asarray(z["verts"], np.float64), np.asarray(z["faces"])
+        if faces.dtype.kind not in "iu":
+            raise RuntimeError(f"load_mesh: {path}: 'faces' must be integers (got {faces.dtype})")
+        faces = faces.astype(np.int64)
+    elif ext == ".obj":
+        vs, fs = [], []
+        with open(path) as f:
+            for no, line in enumerate(f, 1):
+                w = line.split("#", 1)[0].split()
+                if not w:
+                    continue
+                try:
+                    if w[0] == "v":
+                        if len(w) < 4:
+                            raise ValueError("a vertex needs three coordinates")
+                        vs.append([float(w[1]), float(w[2]), float(w[3])])
+                    elif w[0] == "f":
+                        idx = [int(tok.split("/")[0]) for tok in w[1:]]
+                        if len(idx) < 3 or 0 in idx:
+                            raise ValueError("a face needs three or more non-zero indices")
+                        idx = [i - 1 if i > 0 else len(vs) + i for i in idx]
+                        fs.extend([idx[0], idx[k], idx[k + 1]] for k in range(1, len(idx) - 1))
+                except ValueError as e:
+                    raise RuntimeError(f"load_mesh: {path}:{no}: {e}") from e
+        verts, faces = np.asarray(vs, np.float64).reshape(-1, 3), np.asarray(fs, np.int64).reshape(-1, 3)
+    else:
+        raise RuntimeError(f"load_mesh: {path}: only .npz (verts, faces) and Wavefront .obj are read")
+    if verts.ndim != 2 or verts.shape[1] != 3 or faces.ndim != 2 or faces.shape[1] != 3 or faces.shape[0] < 1:
+        raise RuntimeError(f"load_mesh: {path}: need verts [n,3] and at least one face [m,3] (got {verts.shape}, {faces.shape})")
+    if faces.min() < 0 or faces.max() >= verts.shape[0]:
+        raise RuntimeError(f"load_mesh: {path}: a face index is outside the file's {verts.shape[0]} vertices")
+    return verts, faces
+
+
+MESH_OUTPUTS = ("n_inside", "depth", "deep_vertex", "deep_face", "mask", "status")
+
+
+def grasp_mesh(meshes, hand_xyz, obj_of_row, R=None, t=None, want_verts=False, err=None):
+    """Penetration depth against the object's MESH from ONE fused kernel (ops.grasp_mesh; the definition is in include/dvq.h under
+    dvq_grasp_mesh): ``meshes`` an ``ObjectMeshes`` in the clouds' own frame, ``R`` [B,3,3] / ``t`` [3] what ``ops.transform_clouds``
+    got (None for objects in place).  Returns ``n_inside`` [B] i32 (hand vertices inside the mesh; -1 = no figure), ``depth`` [B] f32
+    (the largest distance of one of them to the surface, metres), ``deep_vertex`` / ``deep_face`` [B] i32 (that vertex and its nearest
+    face, -1 without one), ``mask`` [B,W] i32 (bit v & 31 of word v >> 5: vertex v is inside) and ``status`` [B] i32 (0 fine, 1 the
+    object has no face, 3 a hand coordinate is not finite, 4 the object index or its ranges are out of bounds); with ``want_verts``
+    also ``vert_d2`` [B,V] f32 and ``vert_face`` [B,V] i32.  ``mesh_stats`` / ``mesh_class`` turn them into the figures written and
+    into a selection guard.
+
+    This is the reference's metric/penetration.py figure with a +z ray and a watertight tie rule in place of its oblique ray with
+    strict inequalities.  On an open mesh (``meshes.closed[o]`` False) the parity, and with it every figure, is undefined."""
+    if not isinstance(meshes, ObjectMeshes):
+        raise RuntimeError("grasp_mesh: meshes must be an ObjectMeshes")
+    if not torch.is_tensor(hand_xyz) or hand_xyz.dim() != 3:
+        raise RuntimeError("grasp_mesh: hand_xyz must be a [B,V,3] tensor")
+    verts, vert_off, faces, face_off = meshes.on(hand_xyz.device)
+    out = ops.grasp_mesh(hand_xyz.contiguous(), verts, vert_off, faces, face_off, obj_of_row, R, t, want_verts, err=err)
+    res = dict(zip(MESH_OUTPUTS, out[:6]))
+    if want_verts:
+        res.update(vert_d2=out[6], vert_face=out[7])
+    return res
+
+
+def mesh_stats(out):
+    """Host side, float64, row by row, from ``grasp_mesh``'s dict (tensors or arrays): ``mesh_depth`` = depth * 100 in cm and
+    ``mesh_interior`` = n_inside; two lists, ``None`` where n_inside < 0 (json writes null)."""
+    n = _host(out["n_inside"], np.int64).reshape(-1)
+    d = _host(out["depth"], np.float64).reshape(-1)
+    if n.shape[0] != d.shape[0]:
+        raise RuntimeError("mesh_stats: one depth per count")
+    return {"mesh_depth": [float(x) * 100.0 if k >= 0 else None for k, x in zip(n, d)],
+            "mesh_interior": [int(k) if k >= 0 else None for k in n]}
+
+
+def mesh_class(out, max_depth_cm):
+    """int32 [B] on the device for ``torch.maximum`` with the class of ``select_keys``: 2 where the row of ``grasp_mesh``'s output has
+    no figure (n_inside < 0), else 1 where the depth exceeds ``max_depth_cm`` centimetres, else 0.  One fp32 comparison per row,
+    ``depth > fp32(max_depth_cm / 100)``: no sum, so nothing depends on which rows share the call."""
+    n, depth = out["n_inside"], out["depth"]
+    limit = float(max_depth_cm) / 100.0
+    if math.isnan(limit) or limit < 0.0:
+        raise RuntimeError(f"mesh_class: max_depth_cm must be >= 0 (got {max_depth_cm})")
+    over = depth > torch.tensor(limit, dtype=torch.float64, device=depth.device).to(torch.float32) if limit < float("inf") \
+        else torch.zeros_like(n, dtype=torch.bool)
+    one, two = torch.ones_like(n), torch.full_like(n, 2)
+    return torch.where(n < 0, two, torch.where(over, one, torch.zeros_like(n))).to(torch.int32)
 
 
 HAND_PARTS_JSON = os.path.join(os.path.dirname(os.path.abspath(__file__)), "network", "hand_parts.json")

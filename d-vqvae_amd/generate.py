@@ -156,6 +156,21 @@ def build_parser(dataset: str) -> argparse.ArgumentParser:
     p.add_argument("--max_self_verts", type=int, default=None,
                    help="best-of-M: candidates with more than this many self-penetrating vertices rank after all others that touch the "
                         "object (the class --max_penetration uses), whatever --select_by ranks by; needs --candidates (default: no guard)")
+    p.add_argument("--object_meshes", nargs="*", default=[],
+                   help="the objects' triangle meshes, one per --objects file in the same order and in the cloud's own frame: .npz "
+                        "(verts [n,3], faces [m,3]) or a Wavefront .obj of v / f lines; at most "
+                        f"{ops.GRASP_MESH_MAX_FACES} faces each (decimate larger ones); what --mesh_depth and --max_mesh_depth test against")
+    p.add_argument("--mesh_depth", type=int, default=0,
+                   help="1: every grasp's JSON gains \"mesh_depth\" (cm) and \"mesh_interior\": the hand vertices inside the object's MESH "
+                        "(a +z ray, watertight at edges and vertices) and the largest distance of one of them to its surface -- the "
+                        "reference's metric/penetration.py figure, of the hands written (one kernel per call); every object's JSON gains "
+                        "\"mesh_closed\" and \"mesh_penetration_map\", and the run writes mesh_penetration.json; needs --object_meshes; "
+                        "on an open mesh the figures are undefined; work is rows x 1024 x faces pair tests: lower --rows_per_call for "
+                        "big meshes")
+    p.add_argument("--max_mesh_depth", type=float, default=float("inf"),
+                   help="best-of-M: candidates whose mesh depth exceeds this many cm rank after all others that touch the object (the "
+                        "class --max_penetration uses), whatever --select_by ranks by; needs --candidates and --object_meshes "
+                        "(default: no guard)")
     p.add_argument("--refine_push", type=float, default=1.0, help="--refine_steps: step factor on the mean pull vector of the interior points")
     p.add_argument("--refine_pull", type=float, default=0.25,
                    help="--refine_steps: step factor on the mean pull vector of the points within 2 cm outside the hand")
@@ -275,6 +290,17 @@ def parse_args(dataset: str, argv: Optional[Sequence[str]] = None) -> argparse.N
             p.error("--beam_width excludes --temperature and --top_k: a beam search draws nothing")
     if args.max_self_verts is not None and not args.candidates:
         p.error("--max_self_verts needs --candidates (it ranks candidates; --self_collision 1 alone writes the figures)")
+    if args.mesh_depth not in (0, 1):
+        p.error(f"--mesh_depth is 0 or 1 (got {args.mesh_depth})")
+    if args.object_meshes and len(args.object_meshes) != len(args.objects):
+        p.error(f"--object_meshes needs one mesh per --objects file, in the same order (got {len(args.object_meshes)} for "
+                f"{len(args.objects)} objects)")
+    if not args.max_mesh_depth >= 0.0:
+        p.error(f"--max_mesh_depth must be >= 0 (got {args.max_mesh_depth})")
+    if (args.mesh_depth or args.max_mesh_depth < float("inf")) and not args.object_meshes:
+        p.error("--mesh_depth and --max_mesh_depth need --object_meshes (the surfaces they test against)")
+    if args.max_mesh_depth < float("inf") and not args.candidates:
+        p.error("--max_mesh_depth needs --candidates (it ranks candidates; --mesh_depth 1 alone writes the figures)")
     return args
 
 
@@ -508,7 +534,7 @@ def _generate_call(net: GenNet, objs: Sequence[torch.Tensor], num_grasp: int, ro
                    volume: Optional[Dict[str, float]] = None, parts: Optional[Dict[str, object]] = None,
                    refine_spin: float = 0.0, refine_curl: float = 0.0, refine_max_curl: float = 0.35,
                    slf: Optional[Dict[str, object]] = None, ttt: Optional[Dict[str, object]] = None,
-                   beam: Optional[Sequence[int]] = None) -> List[Dict[str, object]]:
+                   beam: Optional[Sequence[int]] = None, msh: Optional[Dict[str, object]] = None) -> List[Dict[str, object]]:
     """One batched call: the ``num_grasp`` grasps of each of ``objs`` (all of one point count), row o * num_grasp + g = grasp g
     of object o.  Every step is row-independent and keyed per row, so each object's slice holds the bits of its own
     ``generate_for_object`` call.  With ``candidates`` = M the call generates M rows per object (exactly the grasps of a
@@ -534,7 +560,10 @@ def _generate_call(net: GenNet, objs: Sequence[torch.Tensor], num_grasp: int, ro
     With ``beam`` = (P, W), P * W = the rows per object, nothing is drawn: every object gets P poses (the rotations of its first P rows),
     every pose ONE beam search of width W (GenNet.gen_beam on the call's O * P posed clouds); row p * W + r holds rank r of pose p, and
     everything after the parameters sees ordinary rows.  The rows' log-likelihoods are the beams' scores (``log_prob`` is on), and the
-    dicts and JSON gain ``beam_pose``, ``beam_rank``, ``beam_duplicate_of`` per grasp kept (_beam_attach)."""
+    dicts and JSON gain ``beam_pose``, ``beam_rank``, ``beam_duplicate_of`` per grasp kept (_beam_attach).
+    With ``msh`` (``meshes``: the ``contact.ObjectMeshes`` of the call's objects, ``max_depth`` in cm) ONE ``contact.grasp_mesh`` runs
+    over all rows of the call, after the push-out and the gradient refinement, with the call's ``obj_of_row``, ``R`` and ``t``
+    (_mesh_launch); its tensors ride in the call's one copy and become the fields of _mesh_json."""
     dev = next(net.parameters()).device
     keep = num_grasp
     G, O = (candidates or num_grasp), len(objs)
@@ -613,20 +642,27 @@ def _generate_call(net: GenNet, objs: Sequence[torch.Tensor], num_grasp: int, ro
     if slf:                                                                        # after the push-out: the hands of the parameters written
         from . import contact
         sco = contact.grasp_self(_hand_topology(net, final.vertices.shape[1], dev), slf["table"], final.vertices, slf["reach"], slf["margin"])
+    msc = None
+    if msh:                                                                        # after the push-out: the hands of the parameters written
+        msc = _mesh_launch(msh["meshes"], final.vertices, obj_of_row, R_dev if rotate else None, t_dev if rotate else None)
     if candidates:
         return _beam_attach(_ttt_attach(_select_call(net, batch, params, final.vertices, logp, err, O, G, keep, select_by, min_contact, want_logp,
                                                      proxies, np.concatenate(Rs), np.concatenate(angles), t, diverse_pool, diverse_space, refined,
-                                                     diversity, stability, max_penetration, torque_length, vol, volume, prt, parts, sco, slf),
+                                                     diversity, stability, max_penetration, torque_length, vol, volume, prt, parts, sco, slf,
+                                                     msc, msh),
                                         tuned, G), baux, beam)
     ref_lists = {}
     div = _diversity_launch(params, O, G, diversity) if diversity else []
     prt_t = [prt[k] for k in PARTS_PIECES] if prt is not None else []             # last before the flag in the call's one copy
     slf_t = [sco[k] for k in SELF_PIECES] if sco is not None else []             # after the parts' pieces, before the flag
-    prt_h = slf_h = None
+    msh_t = [msc[k] for k in MESH_PIECES] if msc is not None else []            # after the self-collision pieces, before the flag
+    prt_h = slf_h = msh_h = None
     if vol is not None and refined is None and not stability:                      # the volume alone: no score is computed
-        host, *vol_h, err_h = _host_copy([params] + [vol[k] for k in VOLUME_PIECES] + div + prt_t + slf_t + [err])   # ONE device-to-host copy per call
+        host, *vol_h, err_h = _host_copy([params] + [vol[k] for k in VOLUME_PIECES] + div + prt_t + slf_t + msh_t + [err])   # ONE device-to-host copy per call
         if int(err_h[0]) != 0:
             raise RuntimeError("generate_for_objects: object index out of range in transform_clouds")
+        if msh_t:
+            vol_h, msh_h = vol_h[:-len(msh_t)], vol_h[-len(msh_t):]
         if slf_t:
             vol_h, slf_h = vol_h[:-len(slf_t)], vol_h[-len(slf_t):]
         if prt_t:
@@ -651,9 +687,11 @@ def _generate_call(net: GenNet, objs: Sequence[torch.Tensor], num_grasp: int, ro
             names = ["refine_" + k for k in REFINE_PIECES if k in refined] + names
             tensors.update({"refine_" + k: refined[k] for k in REFINE_PIECES if k in refined})
         vol_t = [vol[k] for k in VOLUME_PIECES] if vol is not None else []
-        host, *rest_h, err_h = _host_copy([params] + [tensors[k] for k in names] + vol_t + div + prt_t + slf_t + [err])   # ONE device-to-host copy per call
+        host, *rest_h, err_h = _host_copy([params] + [tensors[k] for k in names] + vol_t + div + prt_t + slf_t + msh_t + [err])   # ONE device-to-host copy per call
         if int(err_h[0]) != 0:
             raise RuntimeError("generate_for_objects: object index out of range in transform_clouds")
+        if msh_t:
+            rest_h, msh_h = rest_h[:-len(msh_t)], rest_h[-len(msh_t):]
         if slf_t:
             rest_h, slf_h = rest_h[:-len(slf_t)], rest_h[-len(slf_t):]
         if prt_t:
@@ -667,10 +705,12 @@ def _generate_call(net: GenNet, objs: Sequence[torch.Tensor], num_grasp: int, ro
         if vol is not None:
             ref_lists.update(_volume_json(vol_h, volume["res"]))
         div_h = rest_h[len(by_name):]
-    elif div or prt_t or slf_t:
-        host, *div_h, err_h = _host_copy([params] + div + prt_t + slf_t + [err])   # ONE device-to-host copy per call
+    elif div or prt_t or slf_t or msh_t:
+        host, *div_h, err_h = _host_copy([params] + div + prt_t + slf_t + msh_t + [err])   # ONE device-to-host copy per call
         if int(err_h[0]) != 0:
             raise RuntimeError("generate_for_objects: object index out of range in transform_clouds")
+        if msh_t:
+            div_h, msh_h = div_h[:-len(msh_t)], div_h[-len(msh_t):]
         if slf_t:
             div_h, slf_h = div_h[:-len(slf_t)], div_h[-len(slf_t):]
         if prt_t:
@@ -692,6 +732,7 @@ def _generate_call(net: GenNet, objs: Sequence[torch.Tensor], num_grasp: int, ro
     div_dicts = _diversity_dicts(diversity, div_h) if diversity else None
     prt_lists = _parts_json(prt_h, parts) if prt is not None else None
     slf_lists = _self_json(slf_h) if sco is not None else None
+    msh_lists = _mesh_json(msh_h) if msc is not None else None
     outs = []
     for o in range(O):
         lo, hi = o * G, (o + 1) * G
@@ -717,6 +758,9 @@ def _generate_call(net: GenNet, objs: Sequence[torch.Tensor], num_grasp: int, ro
         if sco is not None:
             extra["self"] = {k: sco[k][lo:hi] for k in SELF_PIECES}
             extra_json.update({k: v[lo:hi] for k, v in slf_lists.items()})
+        if msc is not None:
+            extra["mesh"] = {k: msc[k][lo:hi] for k in MESH_PIECES[:3]}
+            extra_json.update(_mesh_slice(msh_lists, msh_h, lo, hi, msh["meshes"], o, final.vertices.shape[1]))
         outs.append({**extra, "params": p_dev[o], "vertices": v_dev[o],
                      "json": {"recon_params": [[p] for p in p_list[lo:hi]],           # [[61 floats]] per grasp, as the reference
                               "R_list": Rt_list[lo:hi], "trans_list": [trans] * G, "r_list": r_list[lo:hi], **extra_json}})
@@ -852,6 +896,41 @@ def _self_json(host: Sequence[np.ndarray]) -> Dict[str, list]:
     return contact.self_stats(dict(zip(SELF_PIECES, host)))
 
 
+MESH_PIECES = ("n_inside", "depth", "mask", "err")   # what a call's mesh kernel leaves on the device (_mesh_launch)
+MESH_FIELDS = ("mesh_depth", "mesh_interior")
+
+
+def _mesh_launch(meshes, vertices: torch.Tensor, obj_of_row: torch.Tensor, R: Optional[torch.Tensor],
+                 t: Optional[torch.Tensor]) -> Dict[str, torch.Tensor]:
+    """``--mesh_depth`` / ``--max_mesh_depth``: ONE ``contact.grasp_mesh`` over all rows of the call against the call's packed object
+    meshes (``contact.ObjectMeshes``, uploaded once), with the call's ``obj_of_row``, ``R`` and ``t``.  The device tensors n_inside,
+    depth, mask and the kernel's error flag, which _mesh_json reads on the host."""
+    from . import contact
+    bad = ops.new_err_flag(vertices.device)
+    out = contact.grasp_mesh(meshes, vertices, obj_of_row, R, t, err=bad)
+    return {**{k: out[k] for k in MESH_PIECES[:3]}, "err": bad}
+
+
+def _mesh_json(host: Sequence[np.ndarray]) -> Dict[str, list]:
+    """The two per-grasp JSON lists of a call's rows from the host copies of _mesh_launch's tensors: float64 on the host, row by row
+    (contact.mesh_stats); null where the kernel gives no figure (n_inside < 0)."""
+    from . import contact
+    n_inside, depth, _, bad = host
+    if int(bad[0]) != 0:
+        raise RuntimeError("generate_for_objects: mesh depth: an object index, an object's range or a face index is out of range")
+    return contact.mesh_stats({"n_inside": n_inside, "depth": depth})
+
+
+def _mesh_slice(lists: Dict[str, list], host: Sequence[np.ndarray], lo: int, hi: int, meshes, o: int, n_verts: int) -> Dict[str, object]:
+    """An object's share of _mesh_json's lists (its grasps are the rows lo .. hi of the copies), whether its mesh is closed, and its
+    "mesh_penetration_map": at every hand vertex, how many of those grasps have it inside the mesh (contact.contact_map)."""
+    from . import contact
+    out = {k: lists[k][lo:hi] for k in MESH_FIELDS}
+    out["mesh_closed"] = bool(meshes.closed[o])
+    out["mesh_penetration_map"] = contact.contact_map(host[2][lo:hi], n_verts).tolist()
+    return out
+
+
 def _diversity_launch(kept: torch.Tensor, O: int, keep: int, clusters: int) -> List[torch.Tensor]:
     """``--diversity``: one ``ops.segment_kmeans`` over the call's kept parameters [O*keep,61], one segment per object, from evenly
     spaced starting rows; the device tensors whose host copies _diversity_dicts reads (counts, dist, iters_used, the error flag)."""
@@ -881,7 +960,8 @@ def _select_call(net: GenNet, batch: torch.Tensor, params: torch.Tensor, vertice
                  torque_length: float = 0.1, vol: Optional[Dict[str, torch.Tensor]] = None,
                  volume: Optional[Dict[str, float]] = None, prt: Optional[Dict[str, torch.Tensor]] = None,
                  parts: Optional[Dict[str, object]] = None, sco: Optional[Dict[str, torch.Tensor]] = None,
-                 slf: Optional[Dict[str, object]] = None) -> List[Dict[str, object]]:
+                 slf: Optional[Dict[str, object]] = None, msc: Optional[Dict[str, torch.Tensor]] = None,
+                 msh: Optional[Dict[str, object]] = None) -> List[Dict[str, object]]:
     """Best-of-M for all the objects of a call together: the candidates' scores (one fused kernel), their keys, each object's
     ``keep`` best (one kernel), one ``index_select`` of the kept rows and one device-to-host copy.  Row o * M + c is candidate c of
     object o; nothing here depends on which objects share the call.  ``diverse_pool`` = P: each object's P best (the same kernel),
@@ -899,7 +979,10 @@ def _select_call(net: GenNet, batch: torch.Tensor, params: torch.Tensor, vertice
     whatever ranks the rest; the kept rows' four tensors ride along and become the fields of _parts_json.
     ``sco`` (contact.grasp_self over all candidates) with ``slf`` = its settings: with ``max_verts`` = K the class becomes
     ``maximum(cls, contact.self_class(sco, K))`` -- more than K self-penetrating vertices joins class 1, a row without a figure class
-    2 -- whatever ranks the rest; the kept rows' six tensors ride along and become the fields of _self_json."""
+    2 -- whatever ranks the rest; the kept rows' six tensors ride along and become the fields of _self_json.
+    ``msc`` (_mesh_launch over all candidates) with ``msh`` = its settings: with a finite ``max_depth`` (cm) the class becomes
+    ``maximum(cls, contact.mesh_class(msc, max_depth))`` -- deeper inside the object's mesh joins class 1, a row without a figure class
+    2 -- whatever ranks the rest; the kept rows' tensors ride along and become the fields of _mesh_json."""
     from . import contact
     dev = params.device
     topo = _hand_topology(net, vertices.shape[1], dev)
@@ -919,6 +1002,8 @@ def _select_call(net: GenNet, batch: torch.Tensor, params: torch.Tensor, vertice
         cls = torch.maximum(cls, contact.parts_class(prt, parts["min_fingers"], parts["need_thumb"], parts["min_verts"]))
     if sco is not None and slf["max_verts"] is not None:
         cls = torch.maximum(cls, contact.self_class(sco, slf["max_verts"]))
+    if msc is not None and msh["max_depth"] < float("inf"):
+        cls = torch.maximum(cls, contact.mesh_class(msc, msh["max_depth"]))
     diverse = []
     if diverse_pool:
         pool = ops.segment_topk(cls.contiguous(), key.contiguous(), O, M, diverse_pool)   # [O,P] candidate indices, best first
@@ -938,7 +1023,8 @@ def _select_call(net: GenNet, batch: torch.Tensor, params: torch.Tensor, vertice
     kept_vol = [vol[k].index_select(0, rows) for k in VOLUME_PIECES[:3]] + [vol["err"]] if vol is not None else []
     kept_prt = [prt[k].index_select(0, rows) for k in PARTS_PIECES] if prt is not None else []
     kept_slf = [sco[k].index_select(0, rows) for k in SELF_PIECES] if sco is not None else []
-    host = _host_copy([sel] + [kept_p] + [kept_s[k] for k in names] + kept_r + kept_vol + kept_prt + kept_slf + diverse + div + [err])  # ONE device-to-host copy per call
+    kept_msh = [msc[k].index_select(0, rows) for k in MESH_PIECES[:3]] + [msc["err"]] if msc is not None else []
+    host = _host_copy([sel] + [kept_p] + [kept_s[k] for k in names] + kept_r + kept_vol + kept_prt + kept_slf + kept_msh + diverse + div + [err])  # ONE device-to-host copy per call
     if int(host[-1][0]) != 0:
         raise RuntimeError("generate_for_objects: object index out of range in transform_clouds")
     sel_h, p_list = host[0], host[1].tolist()
@@ -962,8 +1048,13 @@ def _select_call(net: GenNet, batch: torch.Tensor, params: torch.Tensor, vertice
     if sco is not None:
         sat = 2 + len(names) + len(kept_r) + len(kept_vol) + len(kept_prt)
         slf_lists = _self_json(host[sat:sat + len(kept_slf)])
+    msh_lists = None
+    if msc is not None:
+        mat = 2 + len(names) + len(kept_r) + len(kept_vol) + len(kept_prt) + len(kept_slf)
+        msh_h = host[mat:mat + len(kept_msh)]
+        msh_lists = _mesh_json(msh_h)
     if diverse_pool:
-        at = 2 + len(names) + len(kept_r) + len(kept_vol) + len(kept_prt) + len(kept_slf)
+        at = 2 + len(names) + len(kept_r) + len(kept_vol) + len(kept_prt) + len(kept_slf) + len(kept_msh)
         rank_h, gap_h, pool_err_h = host[at:at + 3]
         if int(pool_err_h[0]) != 0:
             raise RuntimeError("generate_for_objects: pool entry out of range in segment_diverse")
@@ -1006,6 +1097,10 @@ def _select_call(net: GenNet, batch: torch.Tensor, params: torch.Tensor, vertice
             extra["self"] = {k: x[lo:hi] for k, x in zip(SELF_PIECES, kept_slf)}
             extra["self_scores"] = {k: sco[k][o * M:(o + 1) * M] for k in SELF_PIECES}                  # of ALL candidates
             extra_json = {**extra_json, **{k: v[lo:hi] for k, v in slf_lists.items()}}
+        if msc is not None:
+            extra["mesh"] = {k: x[lo:hi] for k, x in zip(MESH_PIECES[:3], kept_msh)}
+            extra["mesh_scores"] = {k: msc[k][o * M:(o + 1) * M] for k in MESH_PIECES[:3]}              # of ALL candidates
+            extra_json = {**extra_json, **_mesh_slice(msh_lists, msh_h, lo, hi, msh["meshes"], o, vertices.shape[1])}
         outs.append({**extra, "params": p_dev[o], "vertices": v_dev[o], "candidate": sel[o],
                      "scores": {k: v[o * M:(o + 1) * M] for k, v in scores.items()},
                      "json": {"recon_params": [[p] for p in p_list[lo:hi]], "R_list": Rt_list[lo:hi], "trans_list": [trans] * keep,
@@ -1025,7 +1120,8 @@ def generate_for_objects(net: GenNet, objs: Sequence[torch.Tensor], num_grasp: i
                          hand_parts=None, refine_spin: float = 0.0, refine_curl: float = 0.0,
                          refine_max_curl: float = 0.35, self_collision: bool = False, self_reach: float = 0.01,
                          self_margin: float = 0.001, self_seam: int = 2, self_palm: bool = True,
-                         max_self_verts: Optional[int] = None, ttt_steps: int = 0, ttt_lr: float = 6.25e-6,
+                         max_self_verts: Optional[int] = None, object_meshes=None, mesh_depth: bool = False,
+                         max_mesh_depth: float = float("inf"), ttt_steps: int = 0, ttt_lr: float = 6.25e-6,
                          ttt_momentum: float = 0.8, ttt_w_pen: float = 840.0, ttt_w_con: float = 7500.0, ttt_prior=None,
                          ttt_keep_best: bool = True, beam_width: int = 0, beam_poses: int = 1) -> List[Dict[str, object]]:
     """``num_grasp`` grasps for each of ``objs`` ([4,N] tensors) in batched calls that mix objects (plan_calls): one dict per
@@ -1138,6 +1234,15 @@ def generate_for_objects(net: GenNet, objs: Sequence[torch.Tensor], num_grasp: i
     refined independently: the results do not depend on ``rows_per_call``; ``ttt_steps = 0`` is the call without the keyword.  The
     constants are the reference's and untuned here; the effect on real grasps is not measured.
 
+    Mesh depth (``mesh_depth=True``, or a finite ``max_mesh_depth`` together with ``candidates``; both need ``object_meshes``, one
+    ``(verts, faces)`` per object in the cloud's own frame): every call packs its objects' meshes (``contact.ObjectMeshes``) and launches
+    ONE ``contact.grasp_mesh`` over all its rows with the call's ``obj_of_row``, rotations and offset, after the push-out and the
+    gradient refinement.  ``max_mesh_depth`` (cm): candidates whose deepest inside vertex lies farther than that from the mesh's surface
+    join class 1 and candidates without a figure class 2 (``contact.mesh_class``), whatever ``select_by`` ranks by.  Each dict gains
+    ``mesh`` (n_inside, depth, mask of its grasps; with ``candidates`` also ``mesh_scores``, those of ALL candidates) and ``json`` gains
+    "mesh_depth" (cm) and "mesh_interior" per grasp (``contact.mesh_stats``, float64 on the host; null without a figure), "mesh_closed" and
+    "mesh_penetration_map" per object.  On an open mesh the figures are undefined; it is not refused.
+
     Beam search (``beam_width`` = W > 0, ``beam_poses`` = P, P * W = ``candidates`` or ``num_grasp``): nothing is drawn.  Every object
     gets P poses -- the rotations of its first P grasp rows of the call without the keyword; P = 1 without ``rotate`` -- and every pose
     ONE ``GenNet.gen_beam`` search: row p * W + r is the r-th likeliest distinct code grid of pose p under the prior, decoded as
@@ -1170,6 +1275,14 @@ def generate_for_objects(net: GenNet, objs: Sequence[torch.Tensor], num_grasp: i
             raise RuntimeError(f"generate_for_objects: max_self_verts must be >= 0 and needs candidates (got {max_self_verts})")
         self_args = dict(table=_self_table(net, hand_parts, int(self_seam), bool(self_palm)), reach=float(self_reach),
                          margin=float(self_margin), max_verts=None if max_self_verts is None else int(max_self_verts))
+    want_mesh = bool(mesh_depth) or float(max_mesh_depth) < float("inf")
+    if want_mesh:
+        if object_meshes is None or len(object_meshes) != len(objs):
+            raise RuntimeError("generate_for_objects: mesh_depth and max_mesh_depth need object_meshes, one (verts, faces) per object")
+        if not float(max_mesh_depth) >= 0.0:
+            raise RuntimeError(f"generate_for_objects: max_mesh_depth must be >= 0 (got {max_mesh_depth})")
+        if float(max_mesh_depth) < float("inf") and not candidates:
+            raise RuntimeError("generate_for_objects: max_mesh_depth needs candidates")
     parts_args = None
     if parts or min_fingers or need_thumb:
         from . import contact
@@ -1253,10 +1366,15 @@ def generate_for_objects(net: GenNet, objs: Sequence[torch.Tensor], num_grasp: i
         raise RuntimeError("generate_for_objects: ttt_prior needs ttt_steps")
     out: List[Optional[Dict[str, object]]] = [None] * len(objs)
     for call in plan_calls([o.shape[1] for o in objs], candidates or num_grasp, rows_per_call):
+        mesh_args = None
+        if want_mesh:                                                              # the call's objects, packed and uploaded once per call
+            from . import contact
+            mesh_args = dict(meshes=contact.ObjectMeshes([object_meshes[p] for p in call]), max_depth=float(max_mesh_depth))
         res = _generate_call(net, [objs[p] for p in call], num_grasp, rotate, seed, [object_indices[p] for p in call], proxies,
                              temperature, top_k, log_prob, candidates, select_by, min_contact, diverse_pool, diverse_space, refine_steps,
                              refine_push, refine_pull, diversity, stability, max_penetration, torque_length, vol_args, parts_args,
-                             float(refine_spin), float(refine_curl), float(refine_max_curl), self_args, ttt_args, beam)
+                             float(refine_spin), float(refine_curl), float(refine_max_curl), self_args, ttt_args, beam,
+                             mesh_args)
         for p, r in zip(call, res):
             out[p] = r
     return out
@@ -1303,8 +1421,9 @@ def main(dataset: str, argv: Optional[Sequence[str]] = None) -> List[str]:
     want_volume = bool(args.volume) or args.max_volume < float("inf")
     want_parts = bool(args.parts) or args.min_fingers > 0 or bool(args.need_thumb)
     want_self = bool(args.self_collision) or args.max_self_verts is not None
+    want_mesh = bool(args.mesh_depth) or args.max_mesh_depth < float("inf")
     if (args.rows_per_call > 0 or args.candidates or args.refine_steps or args.diversity or args.stability or want_volume or want_parts
-            or want_self or args.ttt_steps or args.beam_width):
+            or want_self or want_mesh or args.ttt_steps or args.beam_width):
         # grouped calls (best-of-M, push-out, the diversity statistic and the stability proxy always: --rows_per_call 0 is then one
         # object per call)
         rows_per_call, per_object = max(1, args.rows_per_call), (args.candidates or args.num_grasp)
@@ -1335,6 +1454,11 @@ def main(dataset: str, argv: Optional[Sequence[str]] = None) -> List[str]:
         if want_self:
             selection.update(self_collision=True, self_reach=args.self_reach, self_margin=args.self_margin, self_seam=args.self_seam,
                              self_palm=bool(args.self_palm), max_self_verts=args.max_self_verts, hand_parts=args.hand_parts)
+        meshes = []
+        if want_mesh:                                                              # this rank's objects' meshes, read once
+            from . import contact
+            meshes = [contact.load_mesh(p) for p in args.object_meshes[lo:hi]]
+        mesh_rows: Dict[int, tuple] = {}                                           # --mesh_depth: every object's (depths, counts, map)
         self_rows: Dict[int, tuple] = {}                                           # --self_collision: every object's (counts, pairs) per grasp
         curl_rows: Dict[int, tuple] = {}                                           # --refine_curl: every object's (curled, reverted) counts
         part_rows: Dict[int, tuple] = {}                                           # --parts: every object's (fingers per grasp, contact map)
@@ -1349,7 +1473,9 @@ def main(dataset: str, argv: Optional[Sequence[str]] = None) -> List[str]:
             t0 = time.time()
             outs = generate_for_objects(net, [mine[p][1] for p in call], args.num_grasp, rotate, args.seed, [lo + p for p in call],
                                         rows_per_call=rows_per_call, temperature=args.temperature, top_k=args.top_k,
-                                        log_prob=bool(args.log_prob), **selection)
+                                        log_prob=bool(args.log_prob), **selection,
+                                        **(dict(object_meshes=[meshes[p] for p in call], mesh_depth=True,
+                                                max_mesh_depth=args.max_mesh_depth) if want_mesh else {}))
             torch.cuda.synchronize(device)
             dt = time.time() - t0
             total_t += dt
@@ -1371,6 +1497,8 @@ def main(dataset: str, argv: Optional[Sequence[str]] = None) -> List[str]:
                     part_rows[p] = (out["json"]["fingers_in_contact"], out["json"]["hand_contact_map"])
                 if want_self:
                     self_rows[p] = (out["json"]["self_penetrating"], out["json"]["self_pairs"])
+                if want_mesh:
+                    mesh_rows[p] = (out["json"]["mesh_depth"], out["json"]["mesh_interior"], out["json"]["mesh_penetration_map"])
             del outs, out
         written = [paths[p] for p in sorted(paths)]                                # object order, whatever the grouping
         if args.diversity and kept:
@@ -1436,6 +1564,20 @@ def main(dataset: str, argv: Optional[Sequence[str]] = None) -> List[str]:
                 json.dump(stat, f)
             print(f"rank {rank}: self-collision of {len(counts)} grasps at reach {args.self_reach} m, margin {args.self_margin} m: share "
                   f"with a penetrating vertex {stat['share_penetrating']}, mean count {stat['mean_penetrating']}")
+        if want_mesh:
+            # the run's figures over this rank's grasps in object order: integers, but for the means (exactly rounded sums)
+            depths = [d for p in sorted(mesh_rows) for d in mesh_rows[p][0] if d is not None]
+            counts = [c for p in sorted(mesh_rows) for c in mesh_rows[p][1] if c is not None]
+            maps = [mesh_rows[p][2] for p in sorted(mesh_rows)]
+            stat = {"grasps": len(counts), "mean_depth_cm": math.fsum(depths) / len(depths) if depths else None,
+                    "mean_interior": math.fsum(counts) / len(counts) if counts else None,
+                    "share_penetrating": sum(1 for c in counts if c > 0) / len(counts) if counts else None,
+                    "mesh_penetration_map": [int(sum(col)) for col in zip(*maps)]}
+            name = "mesh_penetration.json" if world == 1 else f"mesh_penetration_rank{rank}.json"
+            with open(os.path.join(args.out_dir, name), "w") as f:
+                json.dump(stat, f)
+            print(f"rank {rank}: penetration depth against the meshes of {len(counts)} grasps: mean depth {stat['mean_depth_cm']} cm, "
+                  f"mean inside count {stat['mean_interior']}, share with a vertex inside {stat['share_penetrating']}")
     else:
         for gi, (name, obj) in enumerate(objs[lo:hi], start=lo):                   # --rows_per_call 0: one call per object
             torch.cuda.synchronize(device)

@@ -1107,6 +1107,79 @@ def grasp_volume(hand: Tensor, faces: Tensor, loop_off: Tensor, loop_vert: Tenso
     return count, depth, status
 
 
+GRASP_MESH_MAX_FACES = 262144      # include/dvq.h: DVQ_GRASP_MESH_MAX_FACES, per object
+GRASP_MESH_TILE = 256              # csrc/grasp_mesh.hip: GM_TILE (the faces per LDS tile)
+
+
+def grasp_mesh(hand: Tensor, mesh_verts: Tensor, vert_off: Tensor, mesh_faces: Tensor, face_off: Tensor, obj_of_row: Tensor,
+               R: Optional[Tensor] = None, t: Optional[Tensor] = None, want_verts: bool = False, err: Optional[Tensor] = None):
+    """The hand vertices inside each row's object MESH (parity along +z, watertight at edges and vertices) and the largest distance
+    of one of them to the surface, in one fused kernel (dvq_grasp_mesh; the definition is in include/dvq.h): ``(n_inside [B] i32,
+    depth [B] f32, deep_vertex [B] i32, deep_face [B] i32, inside_mask [B,W] i32, status [B] i32, vert_d2, vert_face)``.
+    hand [B,V,3] contiguous; mesh_verts [n,3] f32 and vert_off int32 [O+1], mesh_faces [m,3] int32 (indices local to the object's
+    vertices) and face_off int32 [O+1] (``contact.ObjectMeshes``); obj_of_row int64 [B]; R [B,3,3] and t [3] as ``transform_clouds``
+    got them, or None for objects in place.  With ``want_verts`` every inside vertex's squared distance and nearest face as f32 /
+    int32 [B,V] (+inf / -1 outside; None otherwise).  An object index outside [0, O) raises RuntimeError unless an ``err`` flag tensor
+    is supplied (then the caller checks it: bit 0; bit 1 = a face index or an object's range out of bounds)."""
+    named = (("hand", hand), ("mesh_verts", mesh_verts), ("vert_off", vert_off), ("mesh_faces", mesh_faces), ("face_off", face_off),
+             ("obj_of_row", obj_of_row))
+    for n, x in named:
+        if not isinstance(x, Tensor):
+            raise RuntimeError(f"grasp_mesh: {n} must be a tensor")
+    _f32(hand, "hand"), _f32(mesh_verts, "mesh_verts"), _i64(obj_of_row, "obj_of_row")
+    for n, x in (named[2], named[3], named[4]):
+        if x.dtype != torch.int32 or not x.is_contiguous():
+            raise RuntimeError(f"grasp_mesh: {n} must be contiguous int32")
+    if hand.dim() != 3 or hand.shape[2] != 3 or not hand.is_contiguous():
+        raise RuntimeError("grasp_mesh: hand must be contiguous [B,V,3]")
+    B, V = hand.shape[0], hand.shape[1]
+    if not 1 <= V <= GRASP_SCORES_MAX_V:
+        raise RuntimeError(f"grasp_mesh: need 1 <= V <= {GRASP_SCORES_MAX_V} (got V={V})")
+    if mesh_verts.dim() != 2 or mesh_verts.shape[1] != 3 or not mesh_verts.is_contiguous() or mesh_verts.shape[0] >= 2 ** 31:
+        raise RuntimeError("grasp_mesh: mesh_verts must be contiguous [n,3]")
+    if mesh_faces.dim() != 2 or mesh_faces.shape[1] != 3 or mesh_faces.shape[0] >= 2 ** 31:
+        raise RuntimeError("grasp_mesh: mesh_faces must be contiguous [m,3]")
+    if vert_off.dim() != 1 or vert_off.numel() < 1 or face_off.dim() != 1 or face_off.numel() != vert_off.numel():
+        raise RuntimeError("grasp_mesh: vert_off and face_off must both be [O+1]")
+    if obj_of_row.dim() != 1 or obj_of_row.shape[0] != B or not obj_of_row.is_contiguous():
+        raise RuntimeError("grasp_mesh: `obj_of_row` must be a contiguous int64 [B] tensor")
+    if R is None and t is not None:
+        raise RuntimeError("grasp_mesh: t without R")
+    if R is not None and (not isinstance(R, Tensor) or _f32(R, "R").dim() != 3 or tuple(R.shape) != (B, 3, 3) or not R.is_contiguous()):
+        raise RuntimeError("grasp_mesh: expected contiguous R [B,3,3]")
+    if t is not None and (not isinstance(t, Tensor) or _f32(t, "t").numel() != 3 or not t.is_contiguous()):
+        raise RuntimeError("grasp_mesh: expected contiguous t [3]")
+    dev = _require_gpu(hand, mesh_verts, vert_off, mesh_faces, face_off, obj_of_row, R, t, err)
+    lib = _lib.load()
+    W = (V + 31) // 32
+    n_inside = torch.empty(B, dtype=torch.int32, device=dev)
+    depth = torch.empty(B, dtype=torch.float32, device=dev)
+    deep_vertex = torch.empty(B, dtype=torch.int32, device=dev)
+    deep_face = torch.empty(B, dtype=torch.int32, device=dev)
+    mask = torch.empty(B, W, dtype=torch.int32, device=dev)
+    status = torch.empty(B, dtype=torch.int32, device=dev)
+    vert_d2 = torch.empty(B, V, dtype=torch.float32, device=dev) if want_verts else None
+    vert_face = torch.empty(B, V, dtype=torch.int32, device=dev) if want_verts else None
+    own_err = err is None
+    if own_err:
+        err = new_err_flag(dev)
+    with torch.cuda.device(dev):
+        check(lib.dvq_grasp_mesh(hand.data_ptr(), V, mesh_verts.data_ptr(), mesh_verts.shape[0], vert_off.data_ptr(),
+                                 mesh_faces.data_ptr(), mesh_faces.shape[0], face_off.data_ptr(), vert_off.numel() - 1,
+                                 obj_of_row.data_ptr(), R.data_ptr() if R is not None else None,
+                                 t.data_ptr() if t is not None else None, B, n_inside.data_ptr(), depth.data_ptr(),
+                                 deep_vertex.data_ptr(), deep_face.data_ptr(), mask.data_ptr(), status.data_ptr(),
+                                 vert_d2.data_ptr() if want_verts else None, vert_face.data_ptr() if want_verts else None,
+                                 err.data_ptr(), _stream(dev)), "dvq_grasp_mesh")
+    if own_err:
+        bad = int(err.item())
+        if bad & 1:
+            raise RuntimeError(f"grasp_mesh: object index out of bounds for {vert_off.numel() - 1} objects")
+        if bad:
+            raise RuntimeError("grasp_mesh: a face index or an object's vertex / face range is out of bounds")
+    return n_inside, depth, deep_vertex, deep_face, mask, status, vert_d2, vert_face
+
+
 GRASP_REFINE_MAX_STEPS = 64        # csrc/grasp_refine.hip: GR_MAX_STEPS
 GRASP_FINGERS_MAX_P = 5            # csrc/grasp_refine.hip: GR_MAX_P
 

@@ -44,7 +44,7 @@ typedef enum {
  * working, the version stays): dvq_pixelcnn_sample_ctl, dvq_grasp_scores, dvq_segment_topk, dvq_segment_diverse,
  * dvq_grasp_refine, dvq_segment_kmeans, dvq_grasp_wrench, dvq_grasp_volume, dvq_grasp_parts, dvq_grasp_refine_rigid,
  * dvq_grasp_refine_fingers, dvq_grasp_self, dvq_mano_backward_workspace_bytes, dvq_mano_backward, dvq_grasp_ttt,
- * dvq_pixelcnn_beam_workspace_bytes, dvq_pixelcnn_beam. */
+ * dvq_pixelcnn_beam_workspace_bytes, dvq_pixelcnn_beam, dvq_grasp_mesh. */
 int dvq_abi_version(void);
 const char* dvq_last_error(void);
 /* number of visible HIP devices, or -1; does not create a context */
@@ -785,6 +785,63 @@ int dvq_grasp_volume(const float* hand /* [B,V,3] */, int V, const int32_t* face
                      const int32_t* plane_off /* [O+1] */, int64_t O, const int64_t* obj_of_row /* [B] */, const float* R /* [B,3,3] or NULL */,
                      const float* t /* [3] or NULL */, int64_t B, float h, int32_t* count /* [B] */, float* depth /* [B] */,
                      int32_t* status /* [B] */, int32_t* err_flag, dvq_stream_t stream);
+/* Penetration depth of grasps against the object's MESH: the hand vertices that lie inside the closed triangle mesh of the row's
+ * object (a parity test along +z) and, of those, the largest distance to the mesh's surface -- in ONE kernel, one workgroup of 256
+ * threads per grasp.  The counterpart of the reference's metric/penetration.py (metric/contactutils.py: batch_mesh_contains_points,
+ * then the largest distance of an inside vertex to the surface); it differs from it in one stated way: the ray runs along +z and a
+ * column through a mesh edge or a mesh vertex is decided by the tie rule of dvq_grasp_volume (the reference casts an oblique ray with
+ * strict inequalities and loses exactly those columns).  The depth of dvq_grasp_volume is against the convex HULL; this one sees holes
+ * and handles.  An open mesh is not refused: its parity is then undefined.
+ * Inputs: hand [B,V,3] contiguous fp32, posed, in the frame of its row; mesh_verts [n_mv,3] fp32 and vert_off int32 [O+1] (CSR: the
+ * vertices of object o are rows vert_off[o] .. vert_off[o+1]-1); mesh_faces [n_mf,3] int32 and face_off int32 [O+1] (CSR likewise), the
+ * indices LOCAL to the object's vertex range; obj_of_row int64 [B]; R [B,3,3] and t [3]: the arguments dvq_transform_clouds got for
+ * these rows, or R = NULL (then t = NULL too) for objects in place, exactly as dvq_grasp_volume takes them.
+ * Everything is fp32; every operation is rounded on its own and "fma(a,b,c)" marks the only fused ones; "/" is the IEEE division;
+ * comparisons with a NaN are false; dot(u,w) = fma(u.z, w.z, fma(u.y, w.y, u.x * w.x)).  Per grasp b, with o = obj_of_row[b]:
+ *   1. Object frame: step 2 of dvq_grasp_volume for the V hand vertices, bit for bit (p = R^T (v - t), or p = v without R).
+ *   2. Inside: a face (a,b,c) of object o covers the column (x,y) = (p.x, p.y) by rules 4 - 6 of dvq_grasp_volume (the projected
+ *      area, the edges in their canonical direction -- the lower LOCAL vertex index first -- with a value of exactly 0 decided by the
+ *      edge's side, and the xy bounds), and its crossing height zc is rule 7's.  The vertex is inside iff the number of covering faces
+ *      with zc > p.z is odd.
+ *   3. Distance, for inside vertices only: per face the squared distance to its closest point q, by the regions of Ericson, Real-Time
+ *      Collision Detection 5.1.5, in his order, the first that applies: ab = b - a, ac = c - a, ap = p - a, bp = p - b, cp = p - c,
+ *      cb = c - b per component; d1 = dot(ab,ap), d2 = dot(ac,ap), d3 = dot(ab,bp), d4 = dot(ac,bp), d5 = dot(ab,cp), d6 = dot(ac,cp);
+ *      vc = d1 * d4 - d3 * d2, vb = d5 * d2 - d1 * d6, va = d3 * d6 - d5 * d4; u = d4 - d3, w = d5 - d6;
+ *        d1 <= 0 and d2 <= 0:              q = a;
+ *        d3 >= 0 and d4 <= d3:             q = b;
+ *        vc <= 0, d1 >= 0 and d3 <= 0:     s = d1 / (d1 - d3), q = fma(s, ab, a) per component;
+ *        d6 >= 0 and d5 <= d6:             q = c;
+ *        vb <= 0, d2 >= 0 and d6 <= 0:     s = d2 / (d2 - d6), q = fma(s, ac, a);
+ *        va <= 0, u >= 0 and w >= 0:       s = u / (u + w), q = fma(s, cb, b);
+ *        otherwise:                        n = (va + vb) + vc, s = vb / n, r = vc / n, q = fma(r, ac, fma(s, ab, a));
+ *      e = p - q per component, dist2 = dot(e,e).  The vertex's dist2 is the smallest over the faces in ascending order (from +inf,
+ *      d' < d replaces: a NaN never does) and its face the lowest LOCAL face index that attains it, -1 if none replaced.
+ *   4. Per row: n_inside = the number of inside vertices; over them in ascending order the first and then every one with a larger
+ *      dist2 replaces: depth = sqrtf of that dist2, deep_vertex its index, deep_face its face; with none +0.0f, -1, -1.
+ *   5. inside_mask: bit (v & 31) of word (v >> 5) is "v is inside"; the unused high bits of the last word are 0; W = (V + 31) / 32 words
+ *      per grasp, as dvq_grasp_parts lays out its mask.  vert_d2 / vert_face: step 3's two figures per vertex, +inf / -1 for a vertex
+ *      outside.
+ *   6. status, the first that applies: 4 = obj_of_row[b] is outside [0, O) (bit 0 of *err_flag, a device int32 zeroed by the caller),
+ *      or the object's vertex or face range leaves [0, n_mv] / [0, n_mf] or holds more than DVQ_GRASP_MESH_MAX_FACES faces (bit 1; the
+ *      offsets live on the device, so the launcher cannot refuse them); 3 = a component of hand[b] is not finite; both report
+ *      n_inside = -1, depth = NaN, deep_vertex = deep_face = -1, mask 0, vert_d2 NaN, vert_face -1.  1 = the object has no face:
+ *      n_inside = 0, depth = +0.0f, mask 0 and what "no vertex inside" gives the rest (-1, -1, +inf, -1).  0 otherwise.
+ * A face with an index outside the object's vertex range sets bit 1 of *err_flag and is skipped in steps 2 and 3.  A face with a NaN
+ * coordinate covers nothing and is never nearest: that follows from the comparisons and needs no rule of its own.
+ * Only a parity, minima, a maximum and bits are produced -- no float sum -- so nothing depends on a reduction order or a schedule,
+ * and a grasp's outputs depend on neither B, nor its row, nor which objects share the call.
+ * Outputs: n_inside int32 [B]; depth fp32 [B]; deep_vertex, deep_face int32 [B]; inside_mask int32 [B,W]; status int32 [B]; vert_d2
+ * fp32 [B,V] and vert_face int32 [B,V], each of which may be NULL (not written).
+ * B >= 0, 1 <= V <= 2048, O >= 0, n_mv >= 0, n_mf >= 0, t only with R, no null pointer but R, t, the two optional outputs and the
+ * arrays of an empty pool; anything else is DVQ_EINVAL, nothing launched.  (B = 0 returns DVQ_OK before any pointer is looked at.) */
+#define DVQ_GRASP_MESH_MAX_FACES 262144
+int dvq_grasp_mesh(const float* hand /* [B,V,3] */, int V, const float* mesh_verts /* [n_mv,3] */, int n_mv,
+                   const int32_t* vert_off /* [O+1] */, const int32_t* mesh_faces /* [n_mf,3] local indices */, int n_mf,
+                   const int32_t* face_off /* [O+1] */, int64_t O, const int64_t* obj_of_row /* [B] */,
+                   const float* R /* [B,3,3] or NULL */, const float* t /* [3] or NULL */, int64_t B, int32_t* n_inside /* [B] */,
+                   float* depth /* [B] */, int32_t* deep_vertex /* [B] */, int32_t* deep_face /* [B] */,
+                   int32_t* inside_mask /* [B,W] */, int32_t* status /* [B] */, float* vert_d2 /* [B,V] or NULL */,
+                   int32_t* vert_face /* [B,V] or NULL */, int32_t* err_flag, dvq_stream_t stream);
 /* Per-object selection: cls, key [O*M] (candidate c of object o at o * M + c) -> sel [O,keep]: the candidate indices (0 .. M-1) of
  * each object's keep best candidates, best first.  Candidate a ranks before b iff (cls, key, index) is smaller: cls as signed
  * integers; within a class a NaN key sorts after every number and -0.0 == +0.0; the index breaks every tie.  One workgroup per
