@@ -319,24 +319,70 @@ constexpr int PP_STAGES = 3;
 constexpr size_t PP_SMEM = PP_STAGES * STAGE;               // 147 456 B: one workgroup per CU (eight waves, <= 256 registers)
 constexpr size_t PP_SMEM_N128 = PP_STAGES * (2 * A_PL + 2 * 128 * 64);   // 98 304 B (128 x 128 tile)
 
+typedef __attribute__((address_space(3))) char lds_char;
+typedef __attribute__((address_space(3))) h8 lds_h8;
+
+template <int V>
+struct PpConst { static constexpr int value = V; };
+
+// The two cursors walk the launch's sources one K-tile at a time: the weight cursor two tiles ahead of the tile being multiplied,
+// the activation cursor three.  A cursor keeps what it needs of the source AFTER its current one in registers, fetched long before
+// the switch (fetch(): scalar loads of the descriptor, issued from the compute phase behind the switch that used the last set up;
+// the activation cursor also the row index of a source read through arow, loaded by the switch BEFORE -- at least one K-tile
+// ahead, K >= 32 -- and complete at the next load phase's vmcnt(0)).  The load phase that switches sources then waits for nothing
+// it started itself.  Source indices past the launch's last source are clamped to it: an exhausted cursor re-opens the last source
+// and is not read again (the loop never loads a tile the launch does not have).
 struct PpCursorA {
-    int s, k_left;
+    int s, tiles;                                           // current source; its K-tiles from the cursor's on
     const float* a_ptr;
-    __device__ __forceinline__ void open(const GemmParams& p, int src_i, long m0, int tid) {
-        s = src_i;
-        if (s >= p.nsrc) { k_left = 0; return; }
-        const GemmSrc& src = p.src[s];
-        k_left = src.K;
-        long m = m0 + (tid >> 2);
-        if (m >= p.M) m = p.M - 1;                         // clamped rows / columns only feed outputs the epilogue masks
-        if (src.arow) m = src.arow[m];
-        a_ptr = src.A + m * src.lda + 8 * (tid & 3);
+    const float* n_a;                                       // source s + 1: A, lda, K-tiles; its row index (the row itself without arow)
+    long n_lda;
+    int n_k;
+    long n_row;
+    const int64_t* nn_arow;                                 // source s + 2: arow
+    __device__ __forceinline__ long row(const GemmParams& p, long m0, int tid) const {
+        const long m = m0 + (tid >> 2);
+        return m < p.M ? m : p.M - 1;                       // clamped rows / columns only feed outputs the epilogue masks
     }
-    __device__ __forceinline__ bool valid() const { return k_left > 0; }
-    __device__ __forceinline__ void advance(const GemmParams& p, long m0, int tid) {
+    __device__ __forceinline__ void fetch(const GemmParams& p) {
+        const int i1 = min(s + 1, p.nsrc - 1), i2 = min(s + 2, p.nsrc - 1);
+        n_a = p.src[i1].A;                                  // as loaded: nothing here waits for a scalar load it has just issued
+        n_lda = p.src[i1].lda;
+        n_k = p.src[i1].K;
+        nn_arow = p.src[i2].arow;
+    }
+    // prologue only: waits for the descriptors and for up to two row indices
+    __device__ __forceinline__ void open(const GemmParams& p, long m0, int tid) {
+        s = 0;
+        const GemmSrc& src = p.src[0];
+        const long m = row(p, m0, tid);
+        const int64_t* arow1 = p.src[min(1, p.nsrc - 1)].arow;
+        const long r0 = src.arow ? src.arow[m] : m;
+        n_row = arow1 ? arow1[m] : m;
+        tiles = (int)((unsigned)src.K / BK);
+        a_ptr = src.A + r0 * src.lda + 8 * (tid & 3);
+        fetch(p);
+    }
+    // load phase: everything it reads is in registers
+    __device__ __forceinline__ void next_source(const GemmParams& p, long m0, int tid) {
+        asm volatile("" : "+v"(tid));                       // the row and the column offset are formed HERE, not kept in registers all loop long
+        a_ptr = n_a + n_row * n_lda + 8 * (tid & 3);
+        tiles = (int)((unsigned)n_k / BK);
+        ++s;
+        // the row index of the source after: issued BEHIND the last use of the one it replaces (the asm orders them), so that it
+        // loads into that register and the phase does not wait for it -- the next load phase's vmcnt(0) does
+        int q = tid >> 2;
+        asm volatile("" : "+v"(q) : "v"(a_ptr));
+        long m = m0 + q;
+        if (m >= p.M) m = p.M - 1;
+        n_row = nn_arow ? nn_arow[m] : m;
+    }
+    // true: the source changed -- the caller fetches the next descriptor behind the phase barrier
+    __device__ __forceinline__ bool advance(const GemmParams& p, long m0, int tid) {
         a_ptr += BK;
-        k_left -= BK;
-        if (k_left <= 0) open(p, s + 1, m0, tid);
+        if (__builtin_expect(--tiles != 0, 1)) return false;
+        next_source(p, m0, tid);
+        return true;
     }
 };
 
@@ -344,37 +390,60 @@ struct PpCursorA {
 // the CUs idle: the short-N GEMMs of an 8 192-row batch -- one rank's share of the benchmark batch on eight GPUs)
 template <int NJ>
 struct PpCursorW {
-    int s, k_left;
+    int s, tiles;
+    lds_char* dma_dst[NJ];
     const uint16_t* w_ptr[NJ];
-    __device__ __forceinline__ void open(const GemmParams& p, int src_i, int n0, int wave, int lane) {
-        s = src_i;
-        if (s >= p.nsrc) { k_left = 0; return; }
-        const GemmSrc& src = p.src[s];
-        k_left = src.K;
-#pragma unroll
-        for (int i = 0; i < NJ; ++i) {                     // 8 NJ pieces of 16 rows x 64 B (two planes x 64 NJ rows), NJ per wave
-            const int id = wave * NJ + i;
-            const int pl = id / (4 * NJ), rb = id % (4 * NJ);
-            const int row = rb * 16 + (lane >> 2);
-            int n = n0 + row;
-            if (n >= p.N) n = p.N - 1;
-            w_ptr[i] = src.Wp + pl * src.wp_plane + (long)n * src.ldw + 8 * ((lane & 3) ^ swz16(row));
-        }
+    const uint16_t* n_wp;                                   // source s + 1
+    long n_plane, n_ldw;
+    int n_k;
+    __device__ __forceinline__ void fetch(const GemmParams& p) {
+        const int i1 = min(s + 1, p.nsrc - 1);
+        n_wp = p.src[i1].Wp;
+        n_plane = p.src[i1].wp_plane;
+        n_ldw = p.src[i1].ldw;
+        n_k = p.src[i1].K;
     }
-    __device__ __forceinline__ void issue(char* stage, int wave) const {
+    // The wave's NJ pieces of 16 rows x 64 B (8 NJ pieces: two planes x 64 NJ rows) are piece ids wave NJ .. wave NJ + NJ - 1: plane
+    // wave >> 2, row blocks (wave & 3) NJ + i.  The swizzle of a row depends on (row >> 2) & 3 = (lane >> 4) & 3 alone.
+    __device__ __forceinline__ void place(const GemmParams& p, const uint16_t* wp, long plane, long ldw, int n0, int wave, int lane) {
+        const uint16_t* base = wp + (wave >> 2) * plane + 8 * ((lane & 3) ^ swz16(lane >> 2));
+        const int nr = n0 + (wave & 3) * (16 * NJ) + (lane >> 2);
+#pragma unroll
+        for (int i = 0; i < NJ; ++i) w_ptr[i] = base + (long)min(nr + 16 * i, p.N - 1) * ldw;
+    }
+    __device__ __forceinline__ void open(const GemmParams& p, int n0, int wave, int lane) {
+        s = 0;
+        const GemmSrc& src = p.src[0];
+        tiles = (int)((unsigned)src.K / BK);
+        place(p, src.Wp, src.wp_plane, src.ldw, n0, wave, lane);
+        fetch(p);
+    }
+    // LDS address of the wave's piece i in stage 0: wave-uniform, formed once (the asm keeps it ONE scalar register that the
+    // compiler does not take apart again: per K-tile m0 is this register plus the stage's offset)
+    __device__ __forceinline__ void set_wave(const char* smem, int wave) {
 #pragma unroll
         for (int i = 0; i < NJ; ++i) {
             const int id = wave * NJ + i;
             const int pl = id / (4 * NJ), rb = id % (4 * NJ);
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)w_ptr[i],
-                                             (__attribute__((address_space(3))) void*)(stage + 2 * A_PL + pl * (64 * NJ * 64) + rb * 1024), 16, 0, 0);
+            dma_dst[i] = (lds_char*)smem + (2 * A_PL + pl * (64 * NJ * 64) + rb * 1024);
+            asm volatile("" : "+s"(dma_dst[i]));
         }
     }
-    __device__ __forceinline__ void advance(const GemmParams& p, int n0, int wave, int lane) {
+    __device__ __forceinline__ void issue(int stage_off) const {
+#pragma unroll
+        for (int i = 0; i < NJ; ++i)
+            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)w_ptr[i],
+                                             (__attribute__((address_space(3))) void*)(dma_dst[i] + stage_off), 16, 0, 0);
+    }
+    __device__ __forceinline__ bool advance(const GemmParams& p, int n0, int wave, int lane) {
 #pragma unroll
         for (int i = 0; i < NJ; ++i) w_ptr[i] += BK;
-        k_left -= BK;
-        if (k_left <= 0) open(p, s + 1, n0, wave, lane);
+        if (__builtin_expect(--tiles != 0, 1)) return false;
+        asm volatile("" : "+v"(lane));                      // the rows and the swizzle are formed HERE, not kept in registers all loop long
+        place(p, n_wp, n_plane, n_ldw, n0, wave, lane);
+        tiles = (int)((unsigned)n_k / BK);
+        ++s;
+        return true;
     }
 };
 
@@ -396,50 +465,96 @@ __global__ __launch_bounds__(512, 1) void gemm_f16x2_pp_kernel(const GemmParams 
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave >> 2, wn = wave & 3;
 
+    // The K loop: a steady state that ALWAYS stores tile t + 2, DMAs tile t + 2 and loads tile t + 3 (tiles 0 .. T - 4; the back edge
+    // is its only branch on the common path), then the last three tiles peeled: T - 3 stores and DMAs, T - 2 and T - 1 only multiply.
     PpCursorA ca;
     PpCursorW<NJ> cw;
-    cw.open(p, 0, n0, wave, lane);
+    int refetch = 0;                                        // 1: the weight cursor switched sources, 2: the activation cursor
+    auto fetch_next = [&]() {                               // the descriptors behind a switch; in the loop from the compute phase
+        if (refetch & 1) cw.fetch(p);
+        if (refetch & 2) ca.fetch(p);
+        refetch = 0;
+    };
+    cw.open(p, n0, wave, lane);
+    cw.set_wave(smem_c, wave);
     const int a_dst = (tid >> 2) * 64 + 16 * ((tid & 3) ^ swz16(tid >> 2));
     f32x4 alo, ahi;
     auto load_a = [&](f32x4& qlo, f32x4& qhi) {
         qlo = *reinterpret_cast<const f32x4*>(ca.a_ptr);
         qhi = *reinterpret_cast<const f32x4*>(ca.a_ptr + 4);
-        ca.advance(p, m0, tid);
+        if (ca.advance(p, m0, tid)) refetch |= 2;
     };
-    auto store_a = [&](char* stage, const f32x4& qlo, const f32x4& qhi) {
+    auto step_w = [&]() {
+        if (cw.advance(p, n0, wave, lane)) refetch |= 1;
+    };
+    auto store_a = [&](lds_char* dst, const f32x4& qlo, const f32x4& qhi) {   // dst: the stage + a_dst
         h8 p1, p2;
         split2(qlo, qhi, p1, p2);
-        *reinterpret_cast<h8*>(stage + a_dst) = p1;
-        *reinterpret_cast<h8*>(stage + A_PL + a_dst) = p2;
+        *reinterpret_cast<lds_h8*>(dst) = p1;
+        *reinterpret_cast<lds_h8*>(dst + A_PL) = p2;
     };
     // prologue: tiles 0 and 1 staged, tile 2's activations in registers.  Everything is issued before the one wait: both weight DMAs
     // first (they wait for nothing, not even for a source's arow entry), then the activations of all three tiles -- the accumulators
-    // do not exist yet, the registers are free.  What still costs a round trip of its own is the arow entry of each source opened.
-    cw.issue(smem_c, wave);
-    cw.advance(p, n0, wave, lane);
+    // do not exist yet, the registers are free.  What still costs a round trip of its own is the arow entry of the first two sources
+    // (one trip for both) and the descriptor behind every source opened here.
+    char* const st0 = smem_c;
+    char* const st1 = smem_c + STAGE;
+    cw.issue(0);
+    step_w();
+    if (refetch) fetch_next();
     if (T > 1) {
-        cw.issue(smem_c + STAGE, wave);
-        cw.advance(p, n0, wave, lane);
+        cw.issue(STAGE);
+        step_w();
+        if (refetch) fetch_next();
     }
-    ca.open(p, 0, m0, tid);
+    ca.open(p, m0, tid);
     f32x4 a0lo, a0hi, a1lo, a1hi;
     load_a(a0lo, a0hi);
-    if (T > 1) load_a(a1lo, a1hi);
-    if (T > 2) load_a(alo, ahi);
-    store_a(smem_c, a0lo, a0hi);
-    if (T > 1) store_a(smem_c + STAGE, a1lo, a1hi);
+    if (refetch) fetch_next();
+    if (T > 1) {
+        load_a(a1lo, a1hi);
+        if (refetch) fetch_next();
+    }
+    if (T > 2) {
+        load_a(alo, ahi);
+        if (refetch) fetch_next();
+    }
+    store_a((lds_char*)st0 + a_dst, a0lo, a0hi);
+    if (T > 1) store_a((lds_char*)st1 + a_dst, a1lo, a1hi);
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
 
     f32x4 hi[NJ][4], lo[NJ][4];                             // [jn][i]
     f16x2_init_acc<NJ, INIT>(p, hi, lo, m0 + wm * 64, n0 + wn * 16 * NJ, lane);
 
-    const int rd = (lane & 15) * 64 + 16 * ((lane >> 4) ^ swz16(lane & 15));       // fragment read: row lane & 15, chunk lane >> 4
+    // fragment read: row lane & 15, chunk lane >> 4, of the wave's first activation / weight block
+    const int rd = (lane & 15) * 64 + 16 * ((lane >> 4) ^ swz16(lane & 15));
+    // The stages rotate as three byte offsets in scalar registers (tile t, t + 1, t + 2; renamed behind the MFMAs, no multiply, no
+    // compare): an LDS address of the loop is one thread-constant register plus one of them, m0 of a DMA piece the piece's
+    // wave-constant register plus one of them.
+    lds_char* fr_a = (lds_char*)smem_c + (wm * 64 * 64 + rd);
+    lds_char* fr_w = (lds_char*)smem_c + (2 * A_PL + wn * 16 * NJ * 64 + rd);
+    lds_char* wr_a = (lds_char*)smem_c + a_dst;
+    asm volatile("" : "+v"(fr_a), "+v"(fr_w), "+v"(wr_a));
+    int st_cur = 0, st_n1 = STAGE, st_nx = 2 * STAGE;
     if (wave >= 4) __builtin_amdgcn_s_barrier();           // the second half runs half a period behind
-    int cur_st = 0, nx_st = 2;                              // stage of tile t, of tile t + 2
-    for (int t = 0; t < T; ++t) {
+    // The peeled K-tiles follow each other as straight-line code: without the fence the scheduler moves one phase's arithmetic
+    // across the barrier into the phase before.
+    auto phase_barrier = [&]() __attribute__((always_inline)) {
+        __builtin_amdgcn_sched_barrier(0);
+        __builtin_amdgcn_s_barrier();
+        __builtin_amdgcn_sched_barrier(0);
+    };
+    // One K-tile.  FEED 2: the steady state -- store tile t + 2, DMA tile t + 2, load tile t + 3; 1: the third tile from the end
+    // (nothing left to load); 0: the last two.  FEED is a constant: no bounds test at run time.
+    auto ktile = [&](auto feed_c) __attribute__((always_inline)) {
+        constexpr int FEED = decltype(feed_c)::value;
+        // The barrier that ends the tile before (the stage it multiplied may be written again) stands at the head of this one: what
+        // the loop carries round -- the stage offsets renamed, its counter -- is then settled in the compute phase, beside the MFMAs.
+        if (!(DVQ_DIAG_ON && (p.dbg_abl & 512))) phase_barrier();   // (512: timing only, the loop with ONE barrier per K-tile)
         // ---- load phase
-        const char* st = smem_c + cur_st * STAGE;
+        const lds_char* const st_a = fr_a + st_cur;
+        const lds_char* const st_w = fr_w + st_cur;
         h8 af[4][2], wf[NJ][2];
 #pragma unroll
         for (int i = 0; i < 4; ++i)
@@ -455,24 +570,27 @@ __global__ __launch_bounds__(512, 1) void gemm_f16x2_pp_kernel(const GemmParams 
                     if (i < NJ) wf[i][1] = wf[i][0];
                     continue;
                 }
-                af[i][pl] = *reinterpret_cast<const h8*>(st + pl * A_PL + (wm * 64 + i * 16) * 64 + rd);
-                if (i < NJ) wf[i][pl] = *reinterpret_cast<const h8*>(st + 2 * A_PL + pl * W_PL + (wn * 16 * NJ + i * 16) * 64 + rd);
+                af[i][pl] = *reinterpret_cast<const lds_h8*>(st_a + pl * A_PL + i * 16 * 64);
+                if (i < NJ) wf[i][pl] = *reinterpret_cast<const lds_h8*>(st_w + pl * W_PL + i * 16 * 64);
             }
         // Everything this wave issued in its previous load phase (a period ago) has landed before it passes this phase's barrier:
         // the DMA pieces of tile t + 1 -- read by everybody from the next load phase on -- and the activations converted below.
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        if (t + 2 < T) {
-            char* nx = smem_c + nx_st * STAGE;
+        // (the registers the wait releases are its operands: the split below is scheduled behind it, after the fragment reads)
+        if constexpr (FEED >= 1) asm volatile("s_waitcnt vmcnt(0)" : "+v"(alo), "+v"(ahi) : : "memory");
+        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        if constexpr (FEED >= 1) {
             // (timing-only ablations of the diagnostics build, DVQ_GEMM_ABL: 2 no MFMAs, 8 no weight DMA, 16 no split + plane store, 32 no
             // activation loads, 64 half the fragment reads, 128 none, 256 no epilogue, 512 one barrier per K-tile; results are garbage;
             // tools/gemm_skeleton.py turns them into nanoseconds per K-tile)
-            if (!(DVQ_DIAG_ON && (p.dbg_abl & 16))) store_a(nx, alo, ahi);   // tile t + 2
-            if (!(DVQ_DIAG_ON && (p.dbg_abl & 8))) cw.issue(nx, wave);
-            cw.advance(p, n0, wave, lane);
-            if (t + 3 < T && !(DVQ_DIAG_ON && (p.dbg_abl & 32))) load_a(alo, ahi);   // tile t + 3
+            if (!(DVQ_DIAG_ON && (p.dbg_abl & 16))) store_a(wr_a + st_nx, alo, ahi);   // tile t + 2
+            if (!(DVQ_DIAG_ON && (p.dbg_abl & 8))) cw.issue(st_nx);
+            if constexpr (FEED == 2) {
+                step_w();
+                if (!(DVQ_DIAG_ON && (p.dbg_abl & 32))) load_a(alo, ahi);    // tile t + 3
+            }
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // fragments in registers (and the plane writes retired) before the phase ends
-        __builtin_amdgcn_s_barrier();
+        phase_barrier();
         // ---- compute phase: hi: (a1 w1); lo: (a1 w2) then (a2 w1) -- per output the order the file header gives
         __builtin_amdgcn_s_setprio(1);
         if (DVQ_DIAG_ON && (p.dbg_abl & 2)) {               // timing only: no matrix work (the operands still have to arrive)
@@ -492,11 +610,19 @@ __global__ __launch_bounds__(512, 1) void gemm_f16x2_pp_kernel(const GemmParams 
 #pragma unroll
             for (int i = 0; i < 4; ++i) lo[jn][i] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wf[jn][0], af[i][1], lo[jn][i], 0, 0, 0);
         }
+        if constexpr (FEED == 2) {                          // behind the MFMAs: their operand wait does not cover these scalar loads
+            if (__builtin_expect(refetch != 0, 0)) fetch_next();
+        }
+        const int st_free = st_cur;                         // the stage just multiplied is the one tile t + 3 goes to
+        st_cur = st_n1;
+        st_n1 = st_nx;
+        st_nx = st_free;
         __builtin_amdgcn_s_setprio(0);
-        if (!(DVQ_DIAG_ON && (p.dbg_abl & 512))) __builtin_amdgcn_s_barrier();   // (512: timing only, the loop with ONE barrier per K-tile)
-        cur_st = cur_st == PP_STAGES - 1 ? 0 : cur_st + 1;
-        nx_st = nx_st == PP_STAGES - 1 ? 0 : nx_st + 1;
-    }
+    };
+    for (int t = 3; t < T; ++t) ktile(PpConst<2>{});
+    if (T > 2) ktile(PpConst<1>{});
+    if (T > 1) ktile(PpConst<0>{});
+    ktile(PpConst<0>{});
     if (wave < 4) __builtin_amdgcn_s_barrier();            // pairs with the late half's extra barrier
     if (DVQ_DIAG_ON && (p.dbg_abl & 256)) {                // timing only: no epilogue (one store so that the accumulators stay alive)
         if (hi[0][0][0] + lo[0][0][0] == 12345.678f) p.out[0] = 1.f;

@@ -1,6 +1,9 @@
 """Timing-only ablations of gemm_f16x2_pp_kernel (diagnostics build, DVQ_DIAG_LIB=1 DVQ_GEMM_ABL=<bits>) on one weight source:
 time per launch against K -> cost per 32-wide K-tile (slope) and per tile outside the loop (intercept).  Bits: 2 no MFMA, 8 no weight
-DMA, 16 no split + plane store, 32 no activation loads, 64 half the fragment reads, 128 no fragment reads, 256 no epilogue."""
+DMA, 16 no split + plane store, 32 no activation loads, 64 half the fragment reads, 128 no fragment reads, 256 no epilogue, 512 one
+barrier per K-tile (since the loop carries each K-tile's closing barrier at the head of the next one, 512 drops THAT barrier -- the
+one in front of the load phase -- and the peeled last tile ends without one: figures taken with 512 on the loop before that, the
+376 ns of DESIGN.md 3.1 among them, are not comparable)."""
 import os, sys, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import dvqvae_amd
