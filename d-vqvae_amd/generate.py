@@ -10,6 +10,7 @@ readers for /data/ObMan, /data/GRAB_unzip, HO3D models -- objects come from ``--
 from __future__ import annotations
 
 import argparse
+import dataclasses
 import json
 import math
 import os
@@ -391,8 +392,7 @@ def generate_for_object(net: GenNet, obj4n: torch.Tensor, num_grasp: int, rotate
     recon, pos, *rest = net.gen(batch, noise=noise, seed=seed, row0=row0, stream_id=object_index,
                                 **_prior_controls(temperature, top_k, log_prob))
     params = ops.assemble61(recon, pos)                                            # obman.py:243-247
-    final = net.rh_mano(betas=params[:, :10], global_orient=params[:, 10:13], hand_pose=params[:, 13:58],
-                        transl=params[:, 58:61])                                   # obman.py:252-253
+    final = _pose(net, params)
     Rt = np.concatenate([R, np.broadcast_to(t.reshape(1, 3, 1), (G, 3, 1))], axis=2)
     extra, extra_json = {}, {}
     if log_prob:
@@ -400,17 +400,15 @@ def generate_for_object(net: GenNet, obj4n: torch.Tensor, num_grasp: int, rotate
         extra_json["log_prob"] = extra["log_prob"].cpu().numpy().tolist()
     if proxies:
         from . import contact
-        faces = np.asarray(net.rh_mano.faces)
-        if faces.size == 0 or int(faces.max()) == 0:
-            raise RuntimeError("proxies: the MANO layer has no face list (synthetic model); load MANO_RIGHT.pkl")
-        topo = getattr(net, "_hand_topology", None)
-        if topo is None or topo.faces.device != dev:
-            topo = contact.HandTopology(faces, final.vertices.shape[1], dev)
-            object.__setattr__(net, "_hand_topology", topo)
-        extra["proxies"] = contact.grasp_proxies(topo, final.vertices, batch[:, :3].transpose(1, 2))
+        extra["proxies"] = contact.grasp_proxies(_hand_topology(net, final.vertices.shape[1], dev), final.vertices, batch[:, :3].transpose(1, 2))
     return {**extra, "params": params, "vertices": final.vertices,
             "json": {"recon_params": [[p] for p in params.cpu().numpy().tolist()],   # [[61 floats]] per grasp, as the reference
                      "R_list": Rt.tolist(), "trans_list": [t.reshape(3, 1).tolist()] * G, "r_list": angles.tolist(), **extra_json}}
+
+
+def _pose(net: GenNet, params: torch.Tensor):
+    """The posed-MANO pass of [B,61] parameters: betas, global_orient, hand_pose, transl (obman.py:252-253)."""
+    return net.rh_mano(betas=params[:, :10], global_orient=params[:, 10:13], hand_pose=params[:, 13:58], transl=params[:, 58:61])
 
 
 def _hand_faces(net: GenNet) -> np.ndarray:
@@ -461,7 +459,7 @@ def _refine_fingers_call(net: GenNet, topo, params: torch.Tensor, first, cloud_x
     new[:, 10:13] = contact.compose_orient(params[:, 10:13], out["quat"])
     new[:, 13:58] = contact.compose_finger_pose(net.rh_mano, params[:, 10:13], params[:, 13:58], out["finger_quat"], rig)
     new[:, 58:61] = params[:, 58:61] + out["offset"]
-    posed = net.rh_mano(betas=new[:, :10], global_orient=new[:, 10:13], hand_pose=new[:, 13:58], transl=new[:, 58:61])
+    posed = _pose(net, new)
     scores1 = contact.grasp_scores(topo, posed.vertices, cloud_xyz)
     cls1, key1 = contact.select_keys(scores1, "penetration", min_contact)
     cls0, key0 = contact.select_keys({"penetration": out["penetration0"], "n_contact": out["n_contact0"]}, "penetration", min_contact)
@@ -524,247 +522,210 @@ def plan_calls(point_counts: Sequence[int], num_grasp: int, rows_per_call: int) 
     return [g[i:i + per_call] for g in groups.values() for i in range(0, len(g), per_call)]
 
 
+@dataclasses.dataclass(frozen=True)
+class _Options:
+    """What generate_for_objects has validated, the same for every call of it: its keywords under their own names, but ``stability``
+    is also on with ``select_by="stability"``, ``figures`` holds the active per-row figures with their settings -- (_Figure, dict)
+    pairs in the order of FIGURES -- and ``ttt`` the settings of contact.refine_ttt, or None."""
+    num_grasp: int
+    rotate: bool
+    seed: int
+    proxies: bool
+    temperature: float
+    top_k: int
+    log_prob: bool
+    candidates: int
+    select_by: str
+    min_contact: int
+    diverse_pool: int
+    diverse_space: str
+    refine_steps: int
+    refine_push: float
+    refine_pull: float
+    refine_spin: float
+    refine_curl: float
+    refine_max_curl: float
+    diversity: int
+    stability: bool
+    max_penetration: float
+    torque_length: float
+    figures: tuple
+    ttt: Optional[Dict[str, object]]
+
+
+@dataclasses.dataclass
+class _Call:
+    """The state of one batched call once its hands are final, for the figures' launches and _select_call: row o * G + g is grasp (or
+    candidate) g of object o."""
+    net: GenNet
+    objs: Sequence[torch.Tensor]
+    G: int                                      # rows per object
+    batch: torch.Tensor                         # [O*G,4,N] the posed clouds
+    err: torch.Tensor                           # the flag of ops.transform_clouds: read with the call's one copy
+    obj_of_row: torch.Tensor
+    frame: tuple                                # (R, t) on the device as the figures' kernels take them: (None, None) without rotation
+    R: np.ndarray                               # [O*G,3,3], angles [O*G,3] and t [3] on the host
+    angles: np.ndarray
+    t: np.ndarray
+    params: torch.Tensor
+    vertices: torch.Tensor
+    logp: Optional[torch.Tensor]                # [O*G] where the log-likelihood is written or ranked by
+    refined: Optional[Dict[str, torch.Tensor]]  # the push-out's dict
+    meshes: object                              # the contact.ObjectMeshes of the call's objects, or None
+    figs: Sequence = ()                         # (figure, settings, its launch's device tensors) of the active figures
+
+    @property
+    def cloud_xyz(self) -> torch.Tensor:
+        return self.batch[:, :3].transpose(1, 2)
+
+
 @torch.no_grad()
-def _generate_call(net: GenNet, objs: Sequence[torch.Tensor], num_grasp: int, rotate: bool, seed: int,
-                   object_indices: Sequence[int], proxies: bool, temperature: float = 1.0, top_k: int = 0,
-                   log_prob: bool = False, candidates: int = 0, select_by: str = "penetration",
-                   min_contact: int = 1, diverse_pool: int = 0, diverse_space: str = "params", refine_steps: int = 0,
-                   refine_push: float = 1.0, refine_pull: float = 0.25, diversity: int = 0, stability: bool = False,
-                   max_penetration: float = float("inf"), torque_length: float = 0.1,
-                   volume: Optional[Dict[str, float]] = None, parts: Optional[Dict[str, object]] = None,
-                   refine_spin: float = 0.0, refine_curl: float = 0.0, refine_max_curl: float = 0.35,
-                   slf: Optional[Dict[str, object]] = None, ttt: Optional[Dict[str, object]] = None,
-                   beam: Optional[Sequence[int]] = None, msh: Optional[Dict[str, object]] = None) -> List[Dict[str, object]]:
-    """One batched call: the ``num_grasp`` grasps of each of ``objs`` (all of one point count), row o * num_grasp + g = grasp g
-    of object o.  Every step is row-independent and keyed per row, so each object's slice holds the bits of its own
-    ``generate_for_object`` call.  With ``candidates`` = M the call generates M rows per object (exactly the grasps of a
-    ``num_grasp = M`` call) and keeps each object's ``num_grasp`` best (_select_call).  With ``refine_steps`` every row of the call
-    is first pushed out of its cloud (contact.refine_translation: one kernel), the offsets are added to the translations and MANO is
-    posed again, so that everything after it -- scores, selection, the rows returned -- sees the hands of the parameters written.
-    With ``refine_spin`` > 0 the push-out is the rigid one (contact.refine_rigid about the root joint of the first posed pass): its
-    quaternion goes into ``global_orient`` (contact.compose_orient) and its axis-angle rides along as ``refine_rotation``.
-    With ``refine_curl`` > 0 it is the articulated one (_refine_fingers_call): the curls go into ``hand_pose``, rows that came out
-    worse are reverted, and ``refine_curl`` / ``refine_reverted`` ride along.
-    With ``diversity`` = K the kept parameters of every object go through one ``ops.segment_kmeans`` (one segment per object) and its
-    counts and distances ride in the call's one device-to-host copy (_diversity_launch / _diversity_dicts).  With ``stability`` the
-    scores come from ``contact.grasp_stability`` (one kernel in the place of ``contact.grasp_scores``) and its sums and key ride
-    in that copy too (_stability_json).  With ``volume`` (``res``, ``max_volume``) every object's hull is built once on the host from
-    its own unrotated cloud and ONE ``contact.grasp_volume`` runs over all rows of the call, after the push-out (_volume_launch); the
-    rows' counts, depths and states ride in that copy as well (_volume_json).  With ``parts`` (``table``, ``threshold``, ``min_verts``,
-    ``min_fingers``, ``need_thumb``) ONE ``contact.grasp_parts`` runs over all rows of the call, after the push-out too; its four
-    tensors ride in that copy and become the fields of _parts_json.  With ``slf`` (``table``, ``reach``, ``margin``, ``max_verts``)
-    ONE ``contact.grasp_self`` runs over all rows of the call, after the push-out too -- the hands against themselves; its six
-    tensors ride in that copy and become the fields of _self_json.  With ``ttt`` (``steps``, ``lr``, ``momentum``, ``w_pen``, ``w_con``,
-    ``targets``, ``keep_best``) every row goes through ``contact.refine_ttt`` after any push-out and MANO is posed again, so that
-    everything after it sees the refined hands; the rows' three figures travel in a small copy of their own (_ttt_attach).
-    With ``beam`` = (P, W), P * W = the rows per object, nothing is drawn: every object gets P poses (the rotations of its first P rows),
-    every pose ONE beam search of width W (GenNet.gen_beam on the call's O * P posed clouds); row p * W + r holds rank r of pose p, and
-    everything after the parameters sees ordinary rows.  The rows' log-likelihoods are the beams' scores (``log_prob`` is on), and the
-    dicts and JSON gain ``beam_pose``, ``beam_rank``, ``beam_duplicate_of`` per grasp kept (_beam_attach).
-    With ``msh`` (``meshes``: the ``contact.ObjectMeshes`` of the call's objects, ``max_depth`` in cm) ONE ``contact.grasp_mesh`` runs
-    over all rows of the call, after the push-out and the gradient refinement, with the call's ``obj_of_row``, ``R`` and ``t``
-    (_mesh_launch); its tensors ride in the call's one copy and become the fields of _mesh_json."""
+def _generate_call(net: GenNet, opt: _Options, objs: Sequence[torch.Tensor], object_indices: Sequence[int],
+                   beam: Optional[Sequence[int]] = None, meshes=None) -> List[Dict[str, object]]:
+    """One batched call: the ``num_grasp`` grasps (with ``candidates`` = M: the M candidates) of each of ``objs`` (all of one point
+    count), row o * G + g = grasp g of object o.  Every step is row-independent and keyed per row, so each object's slice holds the bits
+    of its own ``generate_for_object`` call.  The stages, in order:
+    1. the rotations of each object's own generator (``beam`` = (P, W): of its first P rows, W times each), ONE ``ops.transform_clouds``;
+    2. ``GenNet.gen`` keyed per row -- or, with ``beam``, ONE ``GenNet.gen_beam`` search of width W per posed cloud, row p * W + r = rank r
+       of pose p, the beams' scores as the rows' log-likelihoods -- then ``ops.assemble61`` and the posed-MANO pass;
+    3. ``refine_steps``: the push-out of every row (contact.refine_translation; with ``refine_spin`` contact.refine_rigid about the root
+       joint of the first pass; with ``refine_curl`` _refine_fingers_call) into the parameters, and MANO posed again;
+    4. ``ttt``: contact.refine_ttt on every row, and MANO posed again -- everything below sees the hands of the parameters written;
+    5. every active figure's ONE launch over all rows (_Figure.launch, in the order of FIGURES);
+    6. with ``candidates``: _select_call.  Otherwise the scores where a push-out or ``stability`` asks for them (contact.grasp_stability
+       in the place of contact.grasp_scores; neither where the articulated push-out's guard has scored the rows), the k-means of
+       ``diversity`` (_diversity_launch), the call's ONE device-to-host copy (_host_groups), the JSON lists of the whole call and the
+       per-object split;
+    7. _ttt_attach and _beam_attach."""
     dev = next(net.parameters()).device
-    keep = num_grasp
-    G, O = (candidates or num_grasp), len(objs)
-    if beam:
-        if beam[0] * beam[1] != G or (beam[0] != 1 and not rotate) or float(temperature) != 1.0 or int(top_k) != 0:
-            raise RuntimeError(f"_generate_call: beam = {tuple(beam)} needs {G} = poses * width rows per object, one pose without rotation, "
-                               "and no temperature / top_k")
-        log_prob = True                                                            # the beams' scores: always there, always written
-    want_logp = log_prob
-    log_prob = log_prob or (bool(candidates) and select_by == "log_prob")
-    if rotate and beam:                                                            # the first P draws of each object's generator, W rows each
-        angles = [np.repeat(np.random.default_rng([seed, int(gi)]).random((beam[0], 3)) * np.pi * 2, beam[1], axis=0) for gi in object_indices]
-        Rs = [rotation_xyz(a) for a in angles]
-        t = np.asarray(CANONICAL_OFFSET)
-    elif rotate:                                                                   # each object's own generator, as the loop draws them
-        angles = [np.random.default_rng([seed, int(gi)]).random((G, 3)) * np.pi * 2 for gi in object_indices]
-        Rs = [rotation_xyz(a) for a in angles]
-        t = np.asarray(CANONICAL_OFFSET)
+    rotate, seed = opt.rotate, opt.seed
+    G, O = (opt.candidates or opt.num_grasp), len(objs)
+    log_prob = bool(opt.log_prob) or bool(beam) or (bool(opt.candidates) and opt.select_by == "log_prob")   # the beams' scores: always written
+    if rotate:                                  # each object's own generator, as the loop draws them; beam: its first P draws, W rows each
+        P, W = beam if beam else (G, 1)
+        angles = [np.repeat(np.random.default_rng([seed, int(gi)]).random((P, 3)) * np.pi * 2, W, axis=0) for gi in object_indices]
+        R, angles, t = np.concatenate([rotation_xyz(a) for a in angles]), np.concatenate(angles), np.asarray(CANONICAL_OFFSET)
     else:
-        angles = [np.zeros((G, 3))] * O
-        Rs = [np.tile(np.eye(3), (G, 1, 1))] * O
-        t = np.zeros(3)
+        R, angles, t = np.tile(np.eye(3), (O * G, 1, 1)), np.zeros((O * G, 3)), np.zeros(3)
     clouds = torch.stack([o.contiguous() for o in objs]).to(dev)                 # [O,4,N]: one copy per object, none per grasp
     obj_of_row = torch.arange(O, device=dev).repeat_interleave(G)
     stream_ids = torch.as_tensor(np.asarray(object_indices, dtype=np.int64), device=dev).repeat_interleave(G)
     row_ids = torch.arange(G, device=dev).repeat(O)
-    err = ops.new_err_flag(dev)                                                    # read after the parameters' copy below: no extra sync
-    R_dev, t_dev = torch.as_tensor(np.concatenate(Rs), dtype=torch.float32, device=dev), torch.as_tensor(t, dtype=torch.float32, device=dev)
+    err = ops.new_err_flag(dev)                                                    # read with the call's one copy below: no extra sync
+    R_dev, t_dev = torch.as_tensor(R, dtype=torch.float32, device=dev), torch.as_tensor(t, dtype=torch.float32, device=dev)
     batch = ops.transform_clouds(clouds, obj_of_row, R_dev, t_dev, err=err)
+    cloud_xyz = batch[:, :3].transpose(1, 2)
     baux = None
     if beam:                                                                       # one search per posed cloud: rows 0, W, 2 W, ... of the batch
         recon, pos, baux = net.gen_beam(batch[::beam[1]].contiguous(), int(beam[1]), return_aux=True)
         logp = baux["log_prob"]
     else:
-        recon, pos, *rest = net.gen(batch, seed=seed, row_keys=(stream_ids, row_ids), **_prior_controls(temperature, top_k, log_prob))
+        recon, pos, *rest = net.gen(batch, seed=seed, row_keys=(stream_ids, row_ids), **_prior_controls(opt.temperature, opt.top_k, log_prob))
         logp = grasp_log_prob(rest[0]["logp_model"]) if log_prob else None
     params = ops.assemble61(recon, pos)                                            # obman.py:243-247
-    final = net.rh_mano(betas=params[:, :10], global_orient=params[:, 10:13], hand_pose=params[:, 13:58],
-                        transl=params[:, 58:61])                                   # obman.py:252-253
+    final = _pose(net, params)
     refined = None
-    if refine_steps:
+    if opt.refine_steps:
         from . import contact
         topo = _hand_topology(net, final.vertices.shape[1], dev)
-        if refine_curl:                                                            # fingers too: parameters, hands and the guard in one place
-            params, final, refined = _refine_fingers_call(net, topo, params, final, batch[:, :3].transpose(1, 2), refine_steps,
-                                                          refine_push, refine_pull, refine_spin, refine_curl, refine_max_curl, min_contact)
-        elif refine_spin:                                                          # about the wrist: the root joint's world position
-            refined = contact.refine_rigid(topo, final.vertices, batch[:, :3].transpose(1, 2), final.joints[:, 0].contiguous(),
-                                           refine_steps, refine_push, refine_pull, refine_spin, min_contact)
+        if opt.refine_curl:                                                        # fingers too: parameters, hands and the guard in one place
+            params, final, refined = _refine_fingers_call(net, topo, params, final, cloud_xyz, opt.refine_steps, opt.refine_push,
+                                                          opt.refine_pull, opt.refine_spin, opt.refine_curl, opt.refine_max_curl, opt.min_contact)
+        elif opt.refine_spin:                                                      # about the wrist: the root joint's world position
+            refined = contact.refine_rigid(topo, final.vertices, cloud_xyz, final.joints[:, 0].contiguous(), opt.refine_steps,
+                                           opt.refine_push, opt.refine_pull, opt.refine_spin, opt.min_contact)
             params[:, 10:13] = contact.compose_orient(params[:, 10:13], refined["quat"])
             refined["rotation"] = contact.quat_axis_angle(refined["quat"])         # float64 [B,3]
         else:
-            refined = contact.refine_translation(topo, final.vertices, batch[:, :3].transpose(1, 2), refine_steps, refine_push,
-                                                 refine_pull, min_contact)
-        if not refine_curl:
+            refined = contact.refine_translation(topo, final.vertices, cloud_xyz, opt.refine_steps, opt.refine_push, opt.refine_pull,
+                                                 opt.min_contact)
+        if not opt.refine_curl:
             params[:, 58:61] += refined["offset"]                                  # fp32; the hands below are those of these parameters
-            final = net.rh_mano(betas=params[:, :10], global_orient=params[:, 10:13], hand_pose=params[:, 13:58],
-                                transl=params[:, 58:61])
+            final = _pose(net, params)
     tuned = None
-    if ttt:                                                                        # gradient refinement: after any push-out, before any score
+    if opt.ttt:                                                                    # gradient refinement: after any push-out, before any score
         from . import contact
-        tuned = contact.refine_ttt(net.rh_mano, _hand_topology(net, final.vertices.shape[1], dev), params, batch[:, :3].transpose(1, 2),
-                                   ttt["steps"], ttt["lr"], ttt["momentum"], ttt["targets"], ttt["w_pen"], ttt["w_con"], ttt["keep_best"])
+        ttt = opt.ttt
+        tuned = contact.refine_ttt(net.rh_mano, _hand_topology(net, final.vertices.shape[1], dev), params, cloud_xyz, ttt["steps"], ttt["lr"],
+                                   ttt["momentum"], ttt["targets"], ttt["w_pen"], ttt["w_con"], ttt["keep_best"])
         params = tuned["params"]
-        final = net.rh_mano(betas=params[:, :10], global_orient=params[:, 10:13], hand_pose=params[:, 13:58], transl=params[:, 58:61])
+        final = _pose(net, params)
         if refined is not None and "scores" in refined:                            # the push-out's guard scored the hands before this
             refined = {k: v for k, v in refined.items() if k != "scores"}
-    vol = None
-    if volume:                                                                     # after the push-out: the hands of the parameters written
-        vol = _volume_launch(net, objs, final.vertices, obj_of_row, R_dev if rotate else None, t_dev if rotate else None, volume["res"])
-    prt = None
-    if parts:                                                                      # after the push-out: the hands of the parameters written
-        from . import contact
-        prt = contact.grasp_parts(parts["table"], final.vertices, batch[:, :3].transpose(1, 2), parts["threshold"])
-    sco = None
-    if slf:                                                                        # after the push-out: the hands of the parameters written
-        from . import contact
-        sco = contact.grasp_self(_hand_topology(net, final.vertices.shape[1], dev), slf["table"], final.vertices, slf["reach"], slf["margin"])
-    msc = None
-    if msh:                                                                        # after the push-out: the hands of the parameters written
-        msc = _mesh_launch(msh["meshes"], final.vertices, obj_of_row, R_dev if rotate else None, t_dev if rotate else None)
-    if candidates:
-        return _beam_attach(_ttt_attach(_select_call(net, batch, params, final.vertices, logp, err, O, G, keep, select_by, min_contact, want_logp,
-                                                     proxies, np.concatenate(Rs), np.concatenate(angles), t, diverse_pool, diverse_space, refined,
-                                                     diversity, stability, max_penetration, torque_length, vol, volume, prt, parts, sco, slf,
-                                                     msc, msh),
-                                        tuned, G), baux, beam)
-    ref_lists = {}
-    div = _diversity_launch(params, O, G, diversity) if diversity else []
-    prt_t = [prt[k] for k in PARTS_PIECES] if prt is not None else []             # last before the flag in the call's one copy
-    slf_t = [sco[k] for k in SELF_PIECES] if sco is not None else []             # after the parts' pieces, before the flag
-    msh_t = [msc[k] for k in MESH_PIECES] if msc is not None else []            # after the self-collision pieces, before the flag
-    prt_h = slf_h = msh_h = None
-    if vol is not None and refined is None and not stability:                      # the volume alone: no score is computed
-        host, *vol_h, err_h = _host_copy([params] + [vol[k] for k in VOLUME_PIECES] + div + prt_t + slf_t + msh_t + [err])   # ONE device-to-host copy per call
-        if int(err_h[0]) != 0:
-            raise RuntimeError("generate_for_objects: object index out of range in transform_clouds")
-        if msh_t:
-            vol_h, msh_h = vol_h[:-len(msh_t)], vol_h[-len(msh_t):]
-        if slf_t:
-            vol_h, slf_h = vol_h[:-len(slf_t)], vol_h[-len(slf_t):]
-        if prt_t:
-            vol_h, prt_h = vol_h[:-len(prt_t)], vol_h[-len(prt_t):]
-        div_h = vol_h[len(VOLUME_PIECES):]
-        names, tensors = [], {}
-        ref_lists = _volume_json(vol_h[:len(VOLUME_PIECES)], volume["res"])
-    elif refined is not None or stability:                                         # the scores of the hands written, and the one copy
-        from . import contact
-        cloud_xyz = batch[:, :3].transpose(1, 2)
-        names = ["penetration", "n_interior", "n_contact"]
-        if stability:
-            topo = _hand_topology(net, final.vertices.shape[1], dev)
-            scores = contact.grasp_stability(topo, final.vertices, cloud_xyz, torque_length)
-            names = names + ["sums", "key"]
-        elif refined is not None and "scores" in refined:                          # the articulated push-out's guard has scored them
-            scores = refined["scores"]
-        else:
-            scores = contact.grasp_scores(topo, final.vertices, cloud_xyz)
-        tensors = dict(scores)
-        if refined is not None:
-            names = ["refine_" + k for k in REFINE_PIECES if k in refined] + names
-            tensors.update({"refine_" + k: refined[k] for k in REFINE_PIECES if k in refined})
-        vol_t = [vol[k] for k in VOLUME_PIECES] if vol is not None else []
-        host, *rest_h, err_h = _host_copy([params] + [tensors[k] for k in names] + vol_t + div + prt_t + slf_t + msh_t + [err])   # ONE device-to-host copy per call
-        if int(err_h[0]) != 0:
-            raise RuntimeError("generate_for_objects: object index out of range in transform_clouds")
-        if msh_t:
-            rest_h, msh_h = rest_h[:-len(msh_t)], rest_h[-len(msh_t):]
-        if slf_t:
-            rest_h, slf_h = rest_h[:-len(slf_t)], rest_h[-len(slf_t):]
-        if prt_t:
-            rest_h, prt_h = rest_h[:-len(prt_t)], rest_h[-len(prt_t):]
-        by_name = dict(zip(names, rest_h))
-        vol_h, rest_h = rest_h[len(names):len(names) + len(vol_t)], rest_h[:len(names)] + rest_h[len(names) + len(vol_t):]
-        names = [k for k in names if k not in ("sums", "key")]
-        ref_lists = {k: by_name[k].tolist() for k in names}
-        if stability:
-            ref_lists.update(_stability_json(by_name["sums"], by_name["n_contact"], by_name["key"]))
-        if vol is not None:
-            ref_lists.update(_volume_json(vol_h, volume["res"]))
-        div_h = rest_h[len(by_name):]
-    elif div or prt_t or slf_t or msh_t:
-        host, *div_h, err_h = _host_copy([params] + div + prt_t + slf_t + msh_t + [err])   # ONE device-to-host copy per call
-        if int(err_h[0]) != 0:
-            raise RuntimeError("generate_for_objects: object index out of range in transform_clouds")
-        if msh_t:
-            div_h, msh_h = div_h[:-len(msh_t)], div_h[-len(msh_t):]
-        if slf_t:
-            div_h, slf_h = div_h[:-len(slf_t)], div_h[-len(slf_t):]
-        if prt_t:
-            div_h, prt_h = div_h[:-len(prt_t)], div_h[-len(prt_t):]
-    else:
-        host = params.cpu().numpy()                                                # ONE device-to-host copy per call
-        if int(err.item()) != 0:
-            raise RuntimeError("generate_for_objects: object index out of range in transform_clouds")
-    topo = _hand_topology(net, final.vertices.shape[1], dev) if proxies else None
+    call = _Call(net=net, objs=objs, G=G, batch=batch, err=err, obj_of_row=obj_of_row, frame=(R_dev, t_dev) if rotate else (None, None),
+                 R=R, angles=angles, t=t, params=params, vertices=final.vertices, logp=logp, refined=refined,
+                 meshes=meshes)
+    call.figs = [(fig, s, fig.launch(s, call)) for fig, s in opt.figures]          # after the push-out: the hands of the parameters written
+    if opt.candidates:
+        return _beam_attach(_ttt_attach(_select_call(opt, call), tuned, G), baux, beam)
+    div = _diversity_launch(params, O, G, opt.diversity) if opt.diversity else []
+    scores, s_names = {}, []
+    if refined is not None or opt.stability:                                       # the scores of the hands written
+        scores = _call_scores(opt, call)
+        s_names = ["penetration", "n_interior", "n_contact"] + (["sums", "key"] if opt.stability else [])
+    r_names = [k for k in REFINE_PIECES if k in refined] if refined is not None else []
+    host = _host_groups({"params": [params], "refine": [refined[k] for k in r_names], "scores": [scores[k] for k in s_names],
+                         **{fig.key: [d[k] for k in fig.pieces] for fig, _, d in call.figs}, "diversity": div, "err": [err]})
+    if int(host["err"][0][0]) != 0:
+        raise RuntimeError("generate_for_objects: object index out of range in transform_clouds")
+    # what every row shows beside its parameters, on the device and as JSON lists, in the order of the fields: the push-out's pieces,
+    # the three scores, the stability figures
+    s_host = dict(zip(s_names, host["scores"]))
+    row_dev = {**{"refine_" + k: refined[k] for k in r_names}, **{k: scores[k] for k in s_names[:3]}}
+    row_lists = {**{"refine_" + k: h.tolist() for k, h in zip(r_names, host["refine"])}, **{k: s_host[k].tolist() for k in s_names[:3]}}
+    if opt.stability:
+        row_dev.update(wrench_sums=scores["sums"], stability_key=scores["key"])
+        row_lists.update(_stability_json(s_host["sums"], s_host["n_contact"], s_host["key"]))
+    shown = [(fig, s, d, host[fig.key], fig.lists(s, host[fig.key])) for fig, s, d in call.figs]
+    n_vol = sum(fig is _Volume for fig, _ in opt.figures)
+    shown = shown[:n_vol] + ([None] if opt.diversity else []) + shown[n_vol:]    # here the diversity stands after the volume, before the rest
+    div_dicts = _diversity_dicts(opt.diversity, host["diversity"]) if opt.diversity else None
+    topo = _hand_topology(net, final.vertices.shape[1], dev) if opt.proxies else None
     # the JSON fields of the whole call as Python lists in ONE pass each (a .tolist() per object costs more than the device work at
     # one grasp per object), then the per-object split
     B = O * G
-    p_list = host.tolist()
-    Rt_list = np.concatenate([np.concatenate(Rs), np.broadcast_to(t.reshape(1, 3, 1), (B, 3, 1))], axis=2).tolist()
-    r_list = np.concatenate(angles).tolist()
+    p_list = host["params"][0].tolist()
+    Rt_list = np.concatenate([call.R, np.broadcast_to(t.reshape(1, 3, 1), (B, 3, 1))], axis=2).tolist()
+    r_list = call.angles.tolist()
     trans = t.reshape(3, 1).tolist()
     p_dev, v_dev = params.split(G), final.vertices.split(G)
-    lp_list = logp.cpu().numpy().tolist() if log_prob else None
-    div_dicts = _diversity_dicts(diversity, div_h) if diversity else None
-    prt_lists = _parts_json(prt_h, parts) if prt is not None else None
-    slf_lists = _self_json(slf_h) if sco is not None else None
-    msh_lists = _mesh_json(msh_h) if msc is not None else None
+    lp_list = logp.cpu().numpy().tolist() if logp is not None else None
     outs = []
     for o in range(O):
         lo, hi = o * G, (o + 1) * G
         extra, extra_json = {}, {}
-        if log_prob:
+        if logp is not None:
             extra["log_prob"] = logp[lo:hi]
             extra_json["log_prob"] = lp_list[lo:hi]
-        if proxies:                                                                # per object: the reductions see the loop's shapes
+        if opt.proxies:                                                            # per object: the reductions see the loop's shapes
             from . import contact
             extra["proxies"] = contact.grasp_proxies(topo, final.vertices[lo:hi], batch[lo:hi, :3].transpose(1, 2))
-        if ref_lists:
-            extra.update({k: tensors[k][lo:hi] for k in names})
-            if stability:
-                extra.update(wrench_sums=tensors["sums"][lo:hi], stability_key=tensors["key"][lo:hi])
-            extra_json.update({k: v[lo:hi] for k, v in ref_lists.items()})
-        if vol is not None:
-            extra["volume"] = {k: vol[k][lo:hi] for k in VOLUME_PIECES[:3]}
-        if diversity:
-            extra["diversity"] = extra_json["diversity"] = div_dicts[o]
-        if prt is not None:
-            extra["parts"] = {k: prt[k][lo:hi] for k in PARTS_PIECES}
-            extra_json.update(_parts_slice(prt_lists, prt_h, lo, hi, parts))
-        if sco is not None:
-            extra["self"] = {k: sco[k][lo:hi] for k in SELF_PIECES}
-            extra_json.update({k: v[lo:hi] for k, v in slf_lists.items()})
-        if msc is not None:
-            extra["mesh"] = {k: msc[k][lo:hi] for k in MESH_PIECES[:3]}
-            extra_json.update(_mesh_slice(msh_lists, msh_h, lo, hi, msh["meshes"], o, final.vertices.shape[1]))
+        if row_dev:                                                                # (one test: this loop is the cost of a call at one grasp per object)
+            extra.update({k: x[lo:hi] for k, x in row_dev.items()})
+            extra_json.update({k: v[lo:hi] for k, v in row_lists.items()})
+        for entry in shown:
+            if entry is None:
+                extra["diversity"] = extra_json["diversity"] = div_dicts[o]
+                continue
+            fig, s, d, fig_h, lists = entry
+            extra[fig.key] = {k: d[k][lo:hi] for k in fig.pieces[:fig.shown]}
+            extra_json.update(fig.slice(s, lists, fig_h, lo, hi, call, o))
         outs.append({**extra, "params": p_dev[o], "vertices": v_dev[o],
                      "json": {"recon_params": [[p] for p in p_list[lo:hi]],           # [[61 floats]] per grasp, as the reference
                               "R_list": Rt_list[lo:hi], "trans_list": [trans] * G, "r_list": r_list[lo:hi], **extra_json}})
     return _beam_attach(_ttt_attach(outs, tuned, G), baux, beam)
+
+
+def _call_scores(opt: _Options, call: _Call) -> Dict[str, torch.Tensor]:
+    """The scores of a call's hands against their clouds: ONE fused kernel -- contact.grasp_stability with ``stability``, else
+    contact.grasp_scores -- or none where the articulated push-out's guard has scored these very hands (_refine_fingers_call)."""
+    from . import contact
+    if not opt.stability and call.refined is not None and "scores" in call.refined:
+        return dict(call.refined["scores"])
+    topo = _hand_topology(call.net, call.vertices.shape[1], call.vertices.device)
+    if opt.stability:
+        return contact.grasp_stability(topo, call.vertices, call.cloud_xyz, opt.torque_length)
+    return contact.grasp_scores(topo, call.vertices, call.cloud_xyz)
 
 
 def _beam_attach(outs: List[Dict[str, object]], baux: Optional[Dict[str, torch.Tensor]], beam: Optional[Sequence[int]]) -> List[Dict[str, object]]:
@@ -834,101 +795,239 @@ def _stability_json(sums: np.ndarray, n_contact: np.ndarray, key: np.ndarray) ->
     return out
 
 
-VOLUME_PIECES = ("count", "depth", "status", "err")  # what a call's volume kernel leaves on the device (_volume_launch)
-VOLUME_FIELDS = ("penetration_volume", "penetration_depth", "volume_voxels")
+def _host_groups(groups: Dict[str, Sequence[torch.Tensor]]) -> Dict[str, List[np.ndarray]]:
+    """_host_copy by name: the device tensors of every group (a list, possibly empty) on the host under the group's own name, all of
+    them through ONE device-to-host copy.  A call's paths build their groups by name and read them back by name, so no piece is found
+    by its position in the packed copy."""
+    host = iter(_host_copy([p for pieces in groups.values() for p in pieces]))
+    return {name: [next(host) for _ in pieces] for name, pieces in groups.items()}
 
 
-def _volume_launch(net: GenNet, objs: Sequence[torch.Tensor], vertices: torch.Tensor, obj_of_row: torch.Tensor,
-                   R: Optional[torch.Tensor], t: Optional[torch.Tensor], res: float) -> Dict[str, torch.Tensor]:
-    """``--volume`` / ``--max_volume``: every object's convex hull once, on the host, from its own unrotated cloud (contact.hull_planes:
-    scipy), and ONE ``contact.grasp_volume`` over all rows of the call with the call's ``obj_of_row``, ``R`` and ``t``.  The device
-    tensors count, depth, status and the kernel's error flag, which _volume_json reads on the host."""
-    from . import contact
-    dev = vertices.device
-    topo = _hand_topology(net, vertices.shape[1], dev)
-    planes, plane_off = contact.pack_planes([contact.hull_planes(o[:3].T.cpu().numpy().astype(np.float64)) for o in objs])
-    bad = ops.new_err_flag(dev)
-    out = contact.grasp_volume(topo, vertices, torch.from_numpy(planes).to(dev), torch.from_numpy(plane_off).to(dev), obj_of_row, R, t,
-                               res, err=bad)
-    return {**out, "err": bad}
+class _Figure:
+    """One per-row figure of a call, described once: the two paths of a call (_generate_call, _select_call) and ``main`` loop over the
+    active ones in the order of FIGURES.  ``s`` is the figure's settings, the dict generate_for_objects validated; ``call`` the _Call.
+    ``key`` / ``scores_key``: where a dict shows the first ``shown`` of ``pieces`` -- of the grasps written and, with candidates, of ALL
+    candidates.  ``pieces``: the device tensors of ``launch`` that ride in the call's one device-to-host copy, in this order; a piece
+    named "err" is the kernel's error flag, every other one is per row.  ``launch(s, call)``: ONE kernel over all rows of the call,
+    after the push-out and the gradient refinement have re-posed the hands.  ``guard(s, dev)``: with candidates, the class the figure
+    raises -- the ranking's becomes the maximum of the two, whatever ``select_by`` ranks by: a guard only -- or None without a limit.
+    ``lists(s, host)``: the per-row JSON lists from the host copies of the pieces, float64 on the host, row by row, so that a grasp's
+    figures do not depend on which rows share the call; raises on the figure's own error flag.  ``slice(s, lists, host, lo, hi, call,
+    o)``: the JSON fields of object o, whose grasps are the rows lo .. hi of the copies.  ``stem``, ``rows(json)`` and ``summary(args,
+    net, rows)``: the run summary ``main`` writes to <stem>.json -- what it keeps of every object's JSON, and from those (in object
+    order) the summary and the line printed; integers and exactly rounded sums, so that no grouping can change a bit."""
+    shown = None                                                                   # every piece
+
+    @staticmethod
+    def guard(s, dev):
+        return None
+
+    @staticmethod
+    def slice(s, lists, host, lo, hi, call, o):
+        return {k: v[lo:hi] for k, v in lists.items()}
 
 
-def _volume_json(host: Sequence[np.ndarray], res: float) -> Dict[str, list]:
-    """The three JSON lists of a call's rows from the host copies of _volume_launch's tensors: float64 on the host, row by row
-    (contact.volume_stats); null where the kernel gives no figure (count < 0)."""
-    from . import contact
-    count, depth, _, bad = host
-    if int(bad[0]) != 0:
-        raise RuntimeError("generate_for_objects: volume: an index of the hand topology or of the hulls is out of range")
-    out = contact.volume_stats(count, depth, res)
-    out["volume_voxels"] = [int(k) if k >= 0 else None for k in count]
-    return out
+def _mean(values: Sequence[float]) -> Optional[float]:
+    return math.fsum(values) / len(values) if values else None
 
 
+def _share(flags: Sequence[bool]) -> Optional[float]:
+    return sum(1 for f in flags if f) / len(flags) if flags else None
+
+
+VOLUME_PIECES = ("count", "depth", "status", "err")  # what a call's volume kernel leaves on the device (_Volume.launch)
 PARTS_PIECES = ("part_min", "part_count", "mask", "status")     # what a call's parts kernel leaves on the device (contact.grasp_parts)
-PARTS_FIELDS = ("fingers_in_contact", "part_contact", "part_dist")
-
-
-def _parts_json(host: Sequence[np.ndarray], parts: Dict[str, object]) -> Dict[str, list]:
-    """The three per-grasp JSON lists of a call's rows from the host copies of the parts kernel's tensors: float64 on the host, row by
-    row (contact.part_stats); null where a row has no figure."""
-    from . import contact
-    part_min, part_count, _, status = host
-    return contact.part_stats(part_min, part_count, status, parts["min_verts"], min(5, parts["table"].n_parts))
-
-
-def _parts_slice(lists: Dict[str, list], host: Sequence[np.ndarray], lo: int, hi: int, parts: Dict[str, object]) -> Dict[str, list]:
-    """An object's share of _parts_json's lists (its grasps are the rows lo .. hi of the copies) and its "hand_contact_map": at every
-    vertex, how many of those grasps touch there (contact.contact_map)."""
-    from . import contact
-    out = {k: lists[k][lo:hi] for k in PARTS_FIELDS}
-    out["hand_contact_map"] = contact.contact_map(host[2][lo:hi], parts["table"].n_verts).tolist()
-    return out
-
-
 SELF_PIECES = ("pen_count", "pen_depth", "gap_min", "pair_bits", "mask", "status")   # what a call's self-collision kernel leaves on the device
+MESH_PIECES = ("n_inside", "depth", "mask", "err")   # what a call's mesh kernel leaves on the device (_Mesh.launch)
 
 
-def _self_json(host: Sequence[np.ndarray]) -> Dict[str, list]:
-    """The five per-grasp JSON lists of a call's rows from the host copies of the self-collision kernel's tensors: float64 on the
-    host, row by row (contact.self_stats); null where a row has no figure."""
-    from . import contact
-    return contact.self_stats(dict(zip(SELF_PIECES, host)))
+class _Volume(_Figure):
+    """``--volume`` / ``--max_volume`` (settings ``res``, ``max_volume``): every object's convex hull once, on the host, from its own
+    unrotated cloud (contact.hull_planes: scipy), and ONE ``contact.grasp_volume`` over all rows of the call with the call's
+    ``obj_of_row``, ``R`` and ``t``.  Candidates whose voxel count exceeds ``contact.volume_limit`` join class 1 and those without a
+    figure class 2 (integer comparisons on the device).  The JSON fields are penetration_volume, penetration_depth and volume_voxels
+    (contact.volume_stats); null where the kernel gives no figure (count < 0)."""
+    key, scores_key, stem, pieces, shown = "volume", "volume_scores", "penetration", VOLUME_PIECES, 3
+
+    @staticmethod
+    def launch(s, call):
+        from . import contact
+        dev = call.vertices.device
+        topo = _hand_topology(call.net, call.vertices.shape[1], dev)
+        planes, plane_off = contact.pack_planes([contact.hull_planes(o[:3].T.cpu().numpy().astype(np.float64)) for o in call.objs])
+        bad = ops.new_err_flag(dev)
+        out = contact.grasp_volume(topo, call.vertices, torch.from_numpy(planes).to(dev), torch.from_numpy(plane_off).to(dev),
+                                   call.obj_of_row, *call.frame, s["res"], err=bad)
+        return {**out, "err": bad}
+
+    @staticmethod
+    def guard(s, dev):
+        from . import contact
+        if not s["max_volume"] < float("inf"):
+            return None
+        cnt = dev["count"]
+        over = (cnt > contact.volume_limit(s["max_volume"], s["res"])).to(torch.int32)
+        return torch.where(cnt < 0, torch.full_like(over, 2), over)
+
+    @staticmethod
+    def lists(s, host):
+        from . import contact
+        count, depth, _, bad = host
+        if int(bad[0]) != 0:
+            raise RuntimeError("generate_for_objects: volume: an index of the hand topology or of the hulls is out of range")
+        out = contact.volume_stats(count, depth, s["res"])
+        out["volume_voxels"] = [int(k) if k >= 0 else None for k in count]
+        return out
+
+    @staticmethod
+    def rows(j):                                                                   # (voxels, cm^3, cm) per grasp
+        return list(zip(*(j[k] for k in ("volume_voxels", "penetration_volume", "penetration_depth"))))
+
+    @staticmethod
+    def summary(args, net, rows):
+        # contact_ratio is the reference's rule, "volume > 0", on the voxel count
+        rows = [r for obj in rows for r in obj if r[0] is not None]
+        stat = {"res": args.volume_res, "grasps": len(rows), "mean_volume_cm3": _mean([r[1] for r in rows]),
+                "mean_depth_cm": _mean([r[2] for r in rows]), "contact_ratio": _share([r[0] >= 1 for r in rows])}
+        return stat, (f"penetration volume of {len(rows)} grasps at {args.volume_res} m: mean {stat['mean_volume_cm3']} cm^3, "
+                      f"mean depth {stat['mean_depth_cm']} cm, contact ratio {stat['contact_ratio']}")
 
 
-MESH_PIECES = ("n_inside", "depth", "mask", "err")   # what a call's mesh kernel leaves on the device (_mesh_launch)
-MESH_FIELDS = ("mesh_depth", "mesh_interior")
+class _Parts(_Figure):
+    """``--parts`` / ``--min_fingers`` / ``--need_thumb`` (settings ``table``, ``threshold``, ``min_verts``, ``min_fingers``,
+    ``need_thumb``): ONE ``contact.grasp_parts`` over all rows of the call, every hand vertex against its row's cloud.  Too few fingers
+    on the object joins class 1, a row without a figure class 2 (contact.parts_class).  The JSON fields are fingers_in_contact,
+    part_contact and part_dist (contact.part_stats; null where a row has no figure) and, per object, "hand_contact_map": at every
+    vertex, how many of its grasps touch there (contact.contact_map)."""
+    key, scores_key, stem, pieces = "parts", "part_scores", "hand_contact", PARTS_PIECES
+
+    @staticmethod
+    def launch(s, call):
+        from . import contact
+        return contact.grasp_parts(s["table"], call.vertices, call.cloud_xyz, s["threshold"])
+
+    @staticmethod
+    def guard(s, dev):
+        from . import contact
+        if not (s["min_fingers"] or s["need_thumb"]):
+            return None
+        return contact.parts_class(dev, s["min_fingers"], s["need_thumb"], s["min_verts"])
+
+    @staticmethod
+    def lists(s, host):
+        from . import contact
+        part_min, part_count, _, status = host
+        return contact.part_stats(part_min, part_count, status, s["min_verts"], min(5, s["table"].n_parts))
+
+    @staticmethod
+    def slice(s, lists, host, lo, hi, call, o):
+        from . import contact
+        return {**_Figure.slice(s, lists, host, lo, hi, call, o), "hand_contact_map": contact.contact_map(host[2][lo:hi], s["table"].n_verts).tolist()}
+
+    @staticmethod
+    def rows(j):                                                                   # (fingers per grasp, contact map)
+        return j["fingers_in_contact"], j["hand_contact_map"]
+
+    @staticmethod
+    def summary(args, net, rows):
+        fingers = [f for obj in rows for f in obj[0] if f is not None]
+        stat = {"parts": _hand_parts(net, args.hand_parts).names, "threshold": args.part_threshold, "min_verts": args.part_min_verts,
+                "grasps": len(fingers), "hand_contact_map": [int(sum(col)) for col in zip(*(obj[1] for obj in rows))],
+                "mean_fingers_in_contact": _mean(fingers), "fingers_histogram": [sum(1 for f in fingers if f == k) for k in range(6)]}
+        return stat, (f"hand-side contact of {len(fingers)} grasps at {args.part_threshold} m: mean fingers in contact "
+                      f"{stat['mean_fingers_in_contact']}, histogram 0..5 {stat['fingers_histogram']}")
 
 
-def _mesh_launch(meshes, vertices: torch.Tensor, obj_of_row: torch.Tensor, R: Optional[torch.Tensor],
-                 t: Optional[torch.Tensor]) -> Dict[str, torch.Tensor]:
-    """``--mesh_depth`` / ``--max_mesh_depth``: ONE ``contact.grasp_mesh`` over all rows of the call against the call's packed object
-    meshes (``contact.ObjectMeshes``, uploaded once), with the call's ``obj_of_row``, ``R`` and ``t``.  The device tensors n_inside,
-    depth, mask and the kernel's error flag, which _mesh_json reads on the host."""
-    from . import contact
-    bad = ops.new_err_flag(vertices.device)
-    out = contact.grasp_mesh(meshes, vertices, obj_of_row, R, t, err=bad)
-    return {**{k: out[k] for k in MESH_PIECES[:3]}, "err": bad}
+class _Self(_Figure):
+    """``--self_collision`` / ``--max_self_verts`` (settings ``table``, ``reach``, ``margin``, ``max_verts``): ONE ``contact.grasp_self``
+    over all rows of the call -- the hands against themselves.  More than ``max_verts`` self-penetrating vertices joins class 1, a row
+    without a figure class 2 (contact.self_class).  The JSON fields are the five of contact.self_stats; null where a row has no figure."""
+    key, scores_key, stem, pieces = "self", "self_scores", "self_collision", SELF_PIECES
+
+    @staticmethod
+    def launch(s, call):
+        from . import contact
+        return contact.grasp_self(_hand_topology(call.net, call.vertices.shape[1], call.vertices.device), s["table"], call.vertices, s["reach"],
+                                  s["margin"])
+
+    @staticmethod
+    def guard(s, dev):
+        from . import contact
+        return contact.self_class(dev, s["max_verts"]) if s["max_verts"] is not None else None
+
+    @staticmethod
+    def lists(s, host):
+        from . import contact
+        return contact.self_stats(dict(zip(SELF_PIECES, host)))
+
+    @staticmethod
+    def rows(j):                                                                   # (counts, pairs) per grasp
+        return j["self_penetrating"], j["self_pairs"]
+
+    @staticmethod
+    def summary(args, net, rows):
+        table = _self_table(net, args.hand_parts, args.self_seam, bool(args.self_palm))
+        counts = [c for obj in rows for c in obj[0] if c is not None]
+        pairs = [tuple(ab) for obj in rows for g in obj[1] if g is not None for ab in g]
+        names = table.parts.names
+        stat = {"parts": names, "reach": args.self_reach, "margin": args.self_margin, "seam": args.self_seam,
+                "palm": int(args.self_palm), "seam_vertices": table.n_seam, "grasps": len(counts),
+                "share_penetrating": _share([c > 0 for c in counts]), "mean_penetrating": _mean(counts),
+                "pair_histogram": [[pairs.count((a, b)) for b in range(len(names))] for a in range(len(names))]}
+        return stat, (f"self-collision of {len(counts)} grasps at reach {args.self_reach} m, margin {args.self_margin} m: share "
+                      f"with a penetrating vertex {stat['share_penetrating']}, mean count {stat['mean_penetrating']}")
 
 
-def _mesh_json(host: Sequence[np.ndarray]) -> Dict[str, list]:
-    """The two per-grasp JSON lists of a call's rows from the host copies of _mesh_launch's tensors: float64 on the host, row by row
-    (contact.mesh_stats); null where the kernel gives no figure (n_inside < 0)."""
-    from . import contact
-    n_inside, depth, _, bad = host
-    if int(bad[0]) != 0:
-        raise RuntimeError("generate_for_objects: mesh depth: an object index, an object's range or a face index is out of range")
-    return contact.mesh_stats({"n_inside": n_inside, "depth": depth})
+class _Mesh(_Figure):
+    """``--mesh_depth`` / ``--max_mesh_depth`` (settings ``max_depth`` in cm; the meshes are the call's ``contact.ObjectMeshes``, packed
+    and uploaded once per call): ONE ``contact.grasp_mesh`` over all rows of the call with the call's ``obj_of_row``, ``R`` and ``t``.
+    Deeper inside the object's mesh than ``max_depth`` joins class 1, a row without a figure class 2 (contact.mesh_class).  The JSON
+    fields are mesh_depth and mesh_interior (contact.mesh_stats; null where the kernel gives no figure, n_inside < 0) and, per object,
+    whether its mesh is closed and "mesh_penetration_map": at every hand vertex, how many of its grasps have it inside the mesh."""
+    key, scores_key, stem, pieces, shown = "mesh", "mesh_scores", "mesh_penetration", MESH_PIECES, 3
+
+    @staticmethod
+    def launch(s, call):
+        from . import contact
+        bad = ops.new_err_flag(call.vertices.device)
+        out = contact.grasp_mesh(call.meshes, call.vertices, call.obj_of_row, *call.frame, err=bad)
+        return {**{k: out[k] for k in MESH_PIECES[:3]}, "err": bad}
+
+    @staticmethod
+    def guard(s, dev):
+        from . import contact
+        return contact.mesh_class(dev, s["max_depth"]) if s["max_depth"] < float("inf") else None
+
+    @staticmethod
+    def lists(s, host):
+        from . import contact
+        n_inside, depth, _, bad = host
+        if int(bad[0]) != 0:
+            raise RuntimeError("generate_for_objects: mesh depth: an object index, an object's range or a face index is out of range")
+        return contact.mesh_stats({"n_inside": n_inside, "depth": depth})
+
+    @staticmethod
+    def slice(s, lists, host, lo, hi, call, o):
+        from . import contact
+        return {**_Figure.slice(s, lists, host, lo, hi, call, o), "mesh_closed": bool(call.meshes.closed[o]),
+                "mesh_penetration_map": contact.contact_map(host[2][lo:hi], call.vertices.shape[1]).tolist()}
+
+    @staticmethod
+    def rows(j):                                                                   # (depths, counts, map)
+        return j["mesh_depth"], j["mesh_interior"], j["mesh_penetration_map"]
+
+    @staticmethod
+    def summary(args, net, rows):
+        depths = [d for obj in rows for d in obj[0] if d is not None]
+        counts = [c for obj in rows for c in obj[1] if c is not None]
+        stat = {"grasps": len(counts), "mean_depth_cm": _mean(depths), "mean_interior": _mean(counts),
+                "share_penetrating": _share([c > 0 for c in counts]),
+                "mesh_penetration_map": [int(sum(col)) for col in zip(*(obj[2] for obj in rows))]}
+        return stat, (f"penetration depth against the meshes of {len(counts)} grasps: mean depth {stat['mean_depth_cm']} cm, "
+                      f"mean inside count {stat['mean_interior']}, share with a vertex inside {stat['share_penetrating']}")
 
 
-def _mesh_slice(lists: Dict[str, list], host: Sequence[np.ndarray], lo: int, hi: int, meshes, o: int, n_verts: int) -> Dict[str, object]:
-    """An object's share of _mesh_json's lists (its grasps are the rows lo .. hi of the copies), whether its mesh is closed, and its
-    "mesh_penetration_map": at every hand vertex, how many of those grasps have it inside the mesh (contact.contact_map)."""
-    from . import contact
-    out = {k: lists[k][lo:hi] for k in MESH_FIELDS}
-    out["mesh_closed"] = bool(meshes.closed[o])
-    out["mesh_penetration_map"] = contact.contact_map(host[2][lo:hi], n_verts).tolist()
-    return out
+FIGURES = (_Volume, _Parts, _Self, _Mesh)                                        # the order of launches, dict keys, JSON fields and summaries
 
 
 def _diversity_launch(kept: torch.Tensor, O: int, keep: int, clusters: int) -> List[torch.Tensor]:
@@ -952,62 +1051,34 @@ def _diversity_dicts(clusters: int, host: Sequence[np.ndarray]) -> List[Dict[str
             for d in dv.segment_statistics(clusters, counts, dist, used)]
 
 
-def _select_call(net: GenNet, batch: torch.Tensor, params: torch.Tensor, vertices: torch.Tensor, logp: Optional[torch.Tensor],
-                 err: torch.Tensor, O: int, M: int, keep: int, select_by: str, min_contact: int, want_logp: bool, proxies: bool,
-                 R: np.ndarray, angles: np.ndarray, t: np.ndarray, diverse_pool: int = 0,
-                 diverse_space: str = "params", refined: Optional[Dict[str, torch.Tensor]] = None,
-                 diversity: int = 0, stability: bool = False, max_penetration: float = float("inf"),
-                 torque_length: float = 0.1, vol: Optional[Dict[str, torch.Tensor]] = None,
-                 volume: Optional[Dict[str, float]] = None, prt: Optional[Dict[str, torch.Tensor]] = None,
-                 parts: Optional[Dict[str, object]] = None, sco: Optional[Dict[str, torch.Tensor]] = None,
-                 slf: Optional[Dict[str, object]] = None, msc: Optional[Dict[str, torch.Tensor]] = None,
-                 msh: Optional[Dict[str, object]] = None) -> List[Dict[str, object]]:
-    """Best-of-M for all the objects of a call together: the candidates' scores (one fused kernel), their keys, each object's
-    ``keep`` best (one kernel), one ``index_select`` of the kept rows and one device-to-host copy.  Row o * M + c is candidate c of
-    object o; nothing here depends on which objects share the call.  ``diverse_pool`` = P: each object's P best (the same kernel),
-    then the ``keep`` most spread-out of them in greedy farthest-point order (``ops.segment_diverse`` over the parameters or the
-    posed vertices, read in place); their pool positions and squared gaps ride along in the one copy.  ``refined``: the call's
-    rows were pushed out before (contact.refine_translation's dict; ``params`` and ``vertices`` are the refined ones): the kept rows'
-    offsets and iterates (and, where present, ``rotation``, ``curl`` and ``reverted``: REFINE_PIECES) ride along too.  ``diversity``: the
-    k-means statistic of the kept parameters (_diversity_launch) rides along as well.  ``stability``: the candidates' scores come from ``contact.grasp_stability`` (the one kernel in the place of
-    ``contact.grasp_scores``); the kept rows' sums and keys ride along and become the four JSON fields of _stability_json.
-    ``vol`` (_volume_launch over all candidates) with ``volume`` = its ``res`` and ``max_volume``: candidates whose voxel count exceeds
-    ``contact.volume_limit`` join class 1 and those without a figure class 2 (integer comparisons on the device), whatever ranks the
-    rest; the kept rows' counts, depths and states ride along and become the three JSON fields of _volume_json.
-    ``prt`` (contact.grasp_parts over all candidates) with ``parts`` = its settings: with ``min_fingers`` or ``need_thumb`` the class
-    becomes ``maximum(cls, contact.parts_class(...))`` -- too few fingers on the object joins class 1, a row without a figure class 2 --
-    whatever ranks the rest; the kept rows' four tensors ride along and become the fields of _parts_json.
-    ``sco`` (contact.grasp_self over all candidates) with ``slf`` = its settings: with ``max_verts`` = K the class becomes
-    ``maximum(cls, contact.self_class(sco, K))`` -- more than K self-penetrating vertices joins class 1, a row without a figure class
-    2 -- whatever ranks the rest; the kept rows' six tensors ride along and become the fields of _self_json.
-    ``msc`` (_mesh_launch over all candidates) with ``msh`` = its settings: with a finite ``max_depth`` (cm) the class becomes
-    ``maximum(cls, contact.mesh_class(msc, max_depth))`` -- deeper inside the object's mesh joins class 1, a row without a figure class
-    2 -- whatever ranks the rest; the kept rows' tensors ride along and become the fields of _mesh_json."""
+def _select_call(opt: _Options, call: _Call) -> List[Dict[str, object]]:
+    """Best-of-M for all the objects of a call together; row o * M + c is candidate c of object o, and nothing here depends on which
+    objects share the call.  The stages, in order:
+    1. the candidates' scores: ONE fused kernel (contact.grasp_stability with ``stability``, else contact.grasp_scores, or none where
+       the articulated push-out's guard has scored the rows), their classes and keys (contact.select_keys), and every active figure's
+       guard on the class (_Figure.guard);
+    2. each object's ``num_grasp`` best (ops.segment_topk: one kernel) -- or, with ``diverse_pool`` = P, its P best and the
+       ``num_grasp`` most spread-out of them in greedy farthest-point order (ops.segment_diverse over the parameters or the posed
+       vertices, read in place), whose pool positions and squared gaps ride along;
+    3. ONE ``index_select`` per tensor of the kept rows: parameters, vertices, scores, the push-out's REFINE_PIECES, the figures'
+       pieces; the k-means of ``diversity`` over the kept parameters (_diversity_launch);
+    4. the call's ONE device-to-host copy (_host_groups), the JSON lists of the kept rows and the per-object split."""
     from . import contact
-    dev = params.device
-    topo = _hand_topology(net, vertices.shape[1], dev)
-    if stability:
-        scores = contact.grasp_stability(topo, vertices, batch[:, :3].transpose(1, 2), torque_length)
-    else:
-        scores = (dict(refined["scores"]) if refined is not None and "scores" in refined     # the articulated push-out's guard has scored them
-                  else contact.grasp_scores(topo, vertices, batch[:, :3].transpose(1, 2)))
+    net, params, vertices, logp, refined = call.net, call.params, call.vertices, call.logp, call.refined
+    O, M, keep, dev = len(call.objs), call.G, opt.num_grasp, params.device
+    topo = _hand_topology(net, vertices.shape[1], dev) if opt.proxies else None
+    scores = _call_scores(opt, call)
     if logp is not None:
         scores["log_prob"] = logp
-    cls, key = contact.select_keys(scores, select_by, min_contact, log_prob=logp, max_penetration=max_penetration)
-    if vol is not None and volume["max_volume"] < float("inf"):
-        cnt = vol["count"]
-        over = (cnt > contact.volume_limit(volume["max_volume"], volume["res"])).to(torch.int32)
-        cls = torch.maximum(cls, torch.where(cnt < 0, torch.full_like(over, 2), over))
-    if prt is not None and (parts["min_fingers"] or parts["need_thumb"]):
-        cls = torch.maximum(cls, contact.parts_class(prt, parts["min_fingers"], parts["need_thumb"], parts["min_verts"]))
-    if sco is not None and slf["max_verts"] is not None:
-        cls = torch.maximum(cls, contact.self_class(sco, slf["max_verts"]))
-    if msc is not None and msh["max_depth"] < float("inf"):
-        cls = torch.maximum(cls, contact.mesh_class(msc, msh["max_depth"]))
+    cls, key = contact.select_keys(scores, opt.select_by, opt.min_contact, log_prob=logp, max_penetration=opt.max_penetration)
+    for fig, s, d in call.figs:
+        guard = fig.guard(s, d)
+        if guard is not None:
+            cls = torch.maximum(cls, guard)
     diverse = []
-    if diverse_pool:
-        pool = ops.segment_topk(cls.contiguous(), key.contiguous(), O, M, diverse_pool)   # [O,P] candidate indices, best first
-        feat = params if diverse_space == "params" else vertices.reshape(vertices.shape[0], -1)
+    if opt.diverse_pool:
+        pool = ops.segment_topk(cls.contiguous(), key.contiguous(), O, M, opt.diverse_pool)   # [O,P] candidate indices, best first
+        feat = params if opt.diverse_space == "params" else vertices.reshape(vertices.shape[0], -1)
         pool_err = ops.new_err_flag(dev)                                                  # read with everything else, below
         sel, rank, gap = ops.segment_diverse(feat, pool, O, M, keep, err=pool_err)        # [O,keep] in pick order
         diverse = [rank, gap, pool_err]
@@ -1019,88 +1090,52 @@ def _select_call(net: GenNet, batch: torch.Tensor, params: torch.Tensor, vertice
     names = sorted(kept_s)
     r_names = [k for k in REFINE_PIECES if k in refined] if refined is not None else []
     kept_r = [refined[k].index_select(0, rows) for k in r_names]
-    div = _diversity_launch(kept_p, O, keep, diversity) if diversity else []
-    kept_vol = [vol[k].index_select(0, rows) for k in VOLUME_PIECES[:3]] + [vol["err"]] if vol is not None else []
-    kept_prt = [prt[k].index_select(0, rows) for k in PARTS_PIECES] if prt is not None else []
-    kept_slf = [sco[k].index_select(0, rows) for k in SELF_PIECES] if sco is not None else []
-    kept_msh = [msc[k].index_select(0, rows) for k in MESH_PIECES[:3]] + [msc["err"]] if msc is not None else []
-    host = _host_copy([sel] + [kept_p] + [kept_s[k] for k in names] + kept_r + kept_vol + kept_prt + kept_slf + kept_msh + diverse + div + [err])  # ONE device-to-host copy per call
-    if int(host[-1][0]) != 0:
+    div = _diversity_launch(kept_p, O, keep, opt.diversity) if opt.diversity else []
+    kept_f = {fig.key: {k: d[k] if k == "err" else d[k].index_select(0, rows) for k in fig.pieces} for fig, _, d in call.figs}
+    host = _host_groups({"sel": [sel], "params": [kept_p], "scores": [kept_s[k] for k in names], "refine": kept_r,
+                         **{k: list(f.values()) for k, f in kept_f.items()}, "diverse": diverse, "diversity": div, "err": [call.err]})
+    if int(host["err"][0][0]) != 0:
         raise RuntimeError("generate_for_objects: object index out of range in transform_clouds")
-    sel_h, p_list = host[0], host[1].tolist()
-    s_list = {k: h.tolist() for k, h in zip(names, host[2:2 + len(names)]) if k not in ("centre", "sums", "key")}
-    stab_lists = {}
-    if stability:
-        s_host = dict(zip(names, host[2:2 + len(names)]))
-        stab_lists = _stability_json(s_host["sums"], s_host["n_contact"], s_host["key"])
-    if refined is not None:
-        r_lists = [h.tolist() for h in host[2 + len(names):2 + len(names) + len(kept_r)]]
-    vol_lists = {}
-    if vol is not None:
-        vat = 2 + len(names) + len(kept_r)
-        vol_lists = _volume_json(host[vat:vat + len(kept_vol)], volume["res"])
-    prt_lists = None
-    if prt is not None:
-        pat = 2 + len(names) + len(kept_r) + len(kept_vol)
-        prt_h = host[pat:pat + len(kept_prt)]
-        prt_lists = _parts_json(prt_h, parts)
-    slf_lists = None
-    if sco is not None:
-        sat = 2 + len(names) + len(kept_r) + len(kept_vol) + len(kept_prt)
-        slf_lists = _self_json(host[sat:sat + len(kept_slf)])
-    msh_lists = None
-    if msc is not None:
-        mat = 2 + len(names) + len(kept_r) + len(kept_vol) + len(kept_prt) + len(kept_slf)
-        msh_h = host[mat:mat + len(kept_msh)]
-        msh_lists = _mesh_json(msh_h)
-    if diverse_pool:
-        at = 2 + len(names) + len(kept_r) + len(kept_vol) + len(kept_prt) + len(kept_slf) + len(kept_msh)
-        rank_h, gap_h, pool_err_h = host[at:at + 3]
+    sel_h, p_list = host["sel"][0], host["params"][0].tolist()
+    s_host = dict(zip(names, host["scores"]))
+    s_list = {k: h.tolist() for k, h in s_host.items() if k not in ("centre", "sums", "key")}
+    stab_lists = _stability_json(s_host["sums"], s_host["n_contact"], s_host["key"]) if opt.stability else {}
+    r_lists = [h.tolist() for h in host["refine"]]
+    shown = [(fig, s, d, kept_f[fig.key], host[fig.key], fig.lists(s, host[fig.key])) for fig, s, d in call.figs]
+    if opt.diverse_pool:
+        rank_h, gap_h, pool_err_h = host["diverse"]
         if int(pool_err_h[0]) != 0:
             raise RuntimeError("generate_for_objects: pool entry out of range in segment_diverse")
         rank_list, gap_list = rank_h.tolist(), gap_h.tolist()
-    div_dicts = _diversity_dicts(diversity, host[-5:-1]) if diversity else None
+    div_dicts = _diversity_dicts(opt.diversity, host["diversity"]) if opt.diversity else None
     rows_h = (sel_h + np.arange(O)[:, None] * M).reshape(-1)
-    Rt_list = np.concatenate([R[rows_h], np.broadcast_to(t.reshape(1, 3, 1), (O * keep, 3, 1))], axis=2).tolist()
-    r_list = angles[rows_h].tolist()
+    t = call.t
+    Rt_list = np.concatenate([call.R[rows_h], np.broadcast_to(t.reshape(1, 3, 1), (O * keep, 3, 1))], axis=2).tolist()
+    r_list = call.angles[rows_h].tolist()
     c_list = sel_h.tolist()
     trans = t.reshape(3, 1).tolist()
-    json_scores = ["penetration", "n_interior", "n_contact"] + (["log_prob"] if want_logp or select_by == "log_prob" else [])
+    json_scores = ["penetration", "n_interior", "n_contact"] + (["log_prob"] if logp is not None else [])
     p_dev, v_dev = kept_p.split(keep), kept_v.split(keep)
     outs = []
     for o in range(O):
         lo, hi = o * keep, (o + 1) * keep
-        extra = {"log_prob": kept_s["log_prob"][lo:hi]} if "log_prob" in json_scores else {}
-        if proxies:                                                                # of the kept grasps, as the plain path returns them
-            extra["proxies"] = contact.grasp_proxies(topo, v_dev[o], batch.index_select(0, rows[lo:hi])[:, :3].transpose(1, 2))
+        extra = {"log_prob": kept_s["log_prob"][lo:hi]} if logp is not None else {}
+        if opt.proxies:                                                            # of the kept grasps, as the plain path returns them
+            extra["proxies"] = contact.grasp_proxies(topo, v_dev[o], call.batch.index_select(0, rows[lo:hi])[:, :3].transpose(1, 2))
         extra_json = {k: v[lo:hi] for k, v in stab_lists.items()}
-        if stability:
+        if opt.stability:
             extra["wrench_sums"], extra["stability_key"] = kept_s["sums"][lo:hi], kept_s["key"][lo:hi]
-        if diverse_pool:
+        if opt.diverse_pool:
             extra["rank"], extra["novelty"] = rank[o], gap[o]
-            extra_json = {**extra_json, "rank": rank_list[o], "novelty": gap_list[o]}
-        if refined is not None:
-            extra.update({"refine_" + k: x[lo:hi] for k, x in zip(r_names, kept_r)})
-            extra_json = {**extra_json, **{"refine_" + k: x[lo:hi] for k, x in zip(r_names, r_lists)}}
-        if diversity:
-            extra["diversity"] = div_dicts[o]
-            extra_json = {**extra_json, "diversity": div_dicts[o]}
-        if vol is not None:
-            extra["volume"] = {k: x[lo:hi] for k, x in zip(VOLUME_PIECES[:3], kept_vol)}
-            extra["volume_scores"] = {k: vol[k][o * M:(o + 1) * M] for k in VOLUME_PIECES[:3]}      # of ALL candidates
-            extra_json = {**extra_json, **{k: v[lo:hi] for k, v in vol_lists.items()}}
-        if prt is not None:
-            extra["parts"] = {k: x[lo:hi] for k, x in zip(PARTS_PIECES, kept_prt)}
-            extra["part_scores"] = {k: prt[k][o * M:(o + 1) * M] for k in PARTS_PIECES}                 # of ALL candidates
-            extra_json = {**extra_json, **_parts_slice(prt_lists, prt_h, lo, hi, parts)}
-        if sco is not None:
-            extra["self"] = {k: x[lo:hi] for k, x in zip(SELF_PIECES, kept_slf)}
-            extra["self_scores"] = {k: sco[k][o * M:(o + 1) * M] for k in SELF_PIECES}                  # of ALL candidates
-            extra_json = {**extra_json, **{k: v[lo:hi] for k, v in slf_lists.items()}}
-        if msc is not None:
-            extra["mesh"] = {k: x[lo:hi] for k, x in zip(MESH_PIECES[:3], kept_msh)}
-            extra["mesh_scores"] = {k: msc[k][o * M:(o + 1) * M] for k in MESH_PIECES[:3]}              # of ALL candidates
-            extra_json = {**extra_json, **_mesh_slice(msh_lists, msh_h, lo, hi, msh["meshes"], o, vertices.shape[1])}
+            extra_json.update(rank=rank_list[o], novelty=gap_list[o])
+        extra.update({"refine_" + k: x[lo:hi] for k, x in zip(r_names, kept_r)})
+        extra_json.update({"refine_" + k: x[lo:hi] for k, x in zip(r_names, r_lists)})
+        if opt.diversity:
+            extra["diversity"] = extra_json["diversity"] = div_dicts[o]
+        for fig, s, d, kept_d, fig_h, lists in shown:
+            extra[fig.key] = {k: kept_d[k][lo:hi] for k in fig.pieces[:fig.shown]}
+            extra[fig.scores_key] = {k: d[k][o * M:(o + 1) * M] for k in fig.pieces[:fig.shown]}    # of ALL candidates
+            extra_json.update(fig.slice(s, lists, fig_h, lo, hi, call, o))
         outs.append({**extra, "params": p_dev[o], "vertices": v_dev[o], "candidate": sel[o],
                      "scores": {k: v[o * M:(o + 1) * M] for k, v in scores.items()},
                      "json": {"recon_params": [[p] for p in p_list[lo:hi]], "R_list": Rt_list[lo:hi], "trans_list": [trans] * keep,
@@ -1364,17 +1399,20 @@ def generate_for_objects(net: GenNet, objs: Sequence[torch.Tensor], num_grasp: i
                         w_con=float(ttt_w_con), targets=_ttt_targets(ttt_prior), keep_best=bool(ttt_keep_best))
     elif ttt_prior is not None:
         raise RuntimeError("generate_for_objects: ttt_prior needs ttt_steps")
+    mesh_args = dict(max_depth=float(max_mesh_depth)) if want_mesh else None
+    opt = _Options(num_grasp=num_grasp, rotate=rotate, seed=seed, proxies=proxies, temperature=temperature, top_k=top_k, log_prob=log_prob,
+                   candidates=candidates, select_by=select_by, min_contact=min_contact, diverse_pool=diverse_pool, diverse_space=diverse_space,
+                   refine_steps=refine_steps, refine_push=refine_push, refine_pull=refine_pull, refine_spin=float(refine_spin),
+                   refine_curl=float(refine_curl), refine_max_curl=float(refine_max_curl), diversity=diversity, stability=stability,
+                   max_penetration=max_penetration, torque_length=torque_length, ttt=ttt_args,
+                   figures=tuple((fig, s) for fig, s in zip(FIGURES, (vol_args, parts_args, self_args, mesh_args)) if s is not None))
     out: List[Optional[Dict[str, object]]] = [None] * len(objs)
     for call in plan_calls([o.shape[1] for o in objs], candidates or num_grasp, rows_per_call):
-        mesh_args = None
+        meshes = None
         if want_mesh:                                                              # the call's objects, packed and uploaded once per call
             from . import contact
-            mesh_args = dict(meshes=contact.ObjectMeshes([object_meshes[p] for p in call]), max_depth=float(max_mesh_depth))
-        res = _generate_call(net, [objs[p] for p in call], num_grasp, rotate, seed, [object_indices[p] for p in call], proxies,
-                             temperature, top_k, log_prob, candidates, select_by, min_contact, diverse_pool, diverse_space, refine_steps,
-                             refine_push, refine_pull, diversity, stability, max_penetration, torque_length, vol_args, parts_args,
-                             float(refine_spin), float(refine_curl), float(refine_max_curl), self_args, ttt_args, beam,
-                             mesh_args)
+            meshes = contact.ObjectMeshes([object_meshes[p] for p in call])
+        res = _generate_call(net, opt, [objs[p] for p in call], [object_indices[p] for p in call], beam, meshes)
         for p, r in zip(call, res):
             out[p] = r
     return out
@@ -1393,6 +1431,12 @@ def _ttt_targets(prior):
 
 
 _TTT_TARGETS: Dict[str, object] = {}
+
+
+def _write_summary(out_dir: str, stem: str, rank: int, world: int, stat: Dict[str, object]) -> None:
+    """A run summary of ``main``: <stem>.json, or <stem>_rank{rank}.json when several ranks share the run."""
+    with open(os.path.join(out_dir, f"{stem}.json" if world == 1 else f"{stem}_rank{rank}.json"), "w") as f:
+        json.dump(stat, f)
 
 
 def main(dataset: str, argv: Optional[Sequence[str]] = None) -> List[str]:
@@ -1458,11 +1502,9 @@ def main(dataset: str, argv: Optional[Sequence[str]] = None) -> List[str]:
         if want_mesh:                                                              # this rank's objects' meshes, read once
             from . import contact
             meshes = [contact.load_mesh(p) for p in args.object_meshes[lo:hi]]
-        mesh_rows: Dict[int, tuple] = {}                                           # --mesh_depth: every object's (depths, counts, map)
-        self_rows: Dict[int, tuple] = {}                                           # --self_collision: every object's (counts, pairs) per grasp
+        active = [fig for fig, want in zip(FIGURES, (want_volume, want_parts, want_self, want_mesh)) if want]
+        fig_rows: Dict[str, Dict[int, object]] = {fig.key: {} for fig in active}   # every object's _Figure.rows, for the run summaries
         curl_rows: Dict[int, tuple] = {}                                           # --refine_curl: every object's (curled, reverted) counts
-        part_rows: Dict[int, tuple] = {}                                           # --parts: every object's (fingers per grasp, contact map)
-        vol_rows: Dict[int, list] = {}                                             # --volume: every object's (voxels, cm^3, cm) per grasp
         kept: Dict[int, np.ndarray] = {}                                           # --diversity: every object's kept parameters, on the host
         # grouped calls: one call's objects at a time, its files written before the next call starts, so the device and the host
         # hold one call's results, not the whole list's
@@ -1491,14 +1533,8 @@ def main(dataset: str, argv: Optional[Sequence[str]] = None) -> List[str]:
                 if args.refine_curl:
                     curl_rows[p] = (sum(1 for g in out["json"]["refine_curl"] if any(x != 0 for a in g for x in a)),
                                     sum(out["json"]["refine_reverted"]))
-                if want_volume:
-                    vol_rows[p] = list(zip(*(out["json"][k] for k in ("volume_voxels", "penetration_volume", "penetration_depth"))))
-                if want_parts:
-                    part_rows[p] = (out["json"]["fingers_in_contact"], out["json"]["hand_contact_map"])
-                if want_self:
-                    self_rows[p] = (out["json"]["self_penetrating"], out["json"]["self_pairs"])
-                if want_mesh:
-                    mesh_rows[p] = (out["json"]["mesh_depth"], out["json"]["mesh_interior"], out["json"]["mesh_penetration_map"])
+                for fig in active:
+                    fig_rows[fig.key][p] = fig.rows(out["json"])
             del outs, out
         written = [paths[p] for p in sorted(paths)]                                # object order, whatever the grouping
         if args.diversity and kept:
@@ -1506,10 +1542,8 @@ def main(dataset: str, argv: Optional[Sequence[str]] = None) -> List[str]:
             from . import diversity as dv
             pooled = torch.from_numpy(np.concatenate([kept[p] for p in sorted(kept)])).to(device)
             stat = dv.device_diversity(pooled, 1, pooled.shape[0], cls_num=args.diversity, iters=DIVERSITY_ITERS)[0]
-            name = "diversity.json" if world == 1 else f"diversity_rank{rank}.json"
-            with open(os.path.join(args.out_dir, name), "w") as f:
-                json.dump({**{k: stat[k] for k in ("clusters", "entropy", "mean_dist", "iters", "counts")},
-                           "grasps": int(pooled.shape[0])}, f)
+            _write_summary(args.out_dir, "diversity", rank, world,
+                           {**{k: stat[k] for k in ("clusters", "entropy", "mean_dist", "iters", "counts")}, "grasps": int(pooled.shape[0])})
             print(f"rank {rank}: diversity of {pooled.shape[0]} grasps in {stat['clusters']} clusters: entropy {stat['entropy']:.4f}, "
                   f"mean distance {stat['mean_dist']:.4f} ({stat['iters']} iterations)")
         if args.refine_curl:
@@ -1517,67 +1551,13 @@ def main(dataset: str, argv: Optional[Sequence[str]] = None) -> List[str]:
             stat = {"joints": _finger_rig(net).joints, "refine_curl": args.refine_curl, "refine_max_curl": args.refine_max_curl,
                     "grasps": args.num_grasp * len(curl_rows), "curled": sum(c for c, _ in curl_rows.values()),
                     "reverted": sum(r for _, r in curl_rows.values())}
-            name = "refine_curl.json" if world == 1 else f"refine_curl_rank{rank}.json"
-            with open(os.path.join(args.out_dir, name), "w") as f:
-                json.dump(stat, f)
+            _write_summary(args.out_dir, "refine_curl", rank, world, stat)
             print(f"rank {rank}: articulated push-out of {stat['grasps']} grasps: {stat['curled']} with a curled finger, "
                   f"{stat['reverted']} reverted")
-        if want_volume:
-            # the run's figures over this rank's grasps in object order (float64, exactly rounded sums: no grouping can change a bit);
-            # contact_ratio is the reference's rule, "volume > 0", on the voxel count
-            rows = [r for p in sorted(vol_rows) for r in vol_rows[p] if r[0] is not None]
-            stat = {"res": args.volume_res, "grasps": len(rows),
-                    "mean_volume_cm3": math.fsum(r[1] for r in rows) / len(rows) if rows else None,
-                    "mean_depth_cm": math.fsum(r[2] for r in rows) / len(rows) if rows else None,
-                    "contact_ratio": sum(1 for r in rows if r[0] >= 1) / len(rows) if rows else None}
-            name = "penetration.json" if world == 1 else f"penetration_rank{rank}.json"
-            with open(os.path.join(args.out_dir, name), "w") as f:
-                json.dump(stat, f)
-            print(f"rank {rank}: penetration volume of {len(rows)} grasps at {args.volume_res} m: mean {stat['mean_volume_cm3']} cm^3, "
-                  f"mean depth {stat['mean_depth_cm']} cm, contact ratio {stat['contact_ratio']}")
-        if want_parts:
-            # the run's figures over this rank's grasps in object order: integers, but for the mean (an exactly rounded sum)
-            fingers = [f for p in sorted(part_rows) for f in part_rows[p][0] if f is not None]
-            maps = [part_rows[p][1] for p in sorted(part_rows)]
-            stat = {"parts": _hand_parts(net, args.hand_parts).names, "threshold": args.part_threshold, "min_verts": args.part_min_verts,
-                    "grasps": len(fingers), "hand_contact_map": [int(sum(col)) for col in zip(*maps)],
-                    "mean_fingers_in_contact": math.fsum(fingers) / len(fingers) if fingers else None,
-                    "fingers_histogram": [sum(1 for f in fingers if f == k) for k in range(6)]}
-            name = "hand_contact.json" if world == 1 else f"hand_contact_rank{rank}.json"
-            with open(os.path.join(args.out_dir, name), "w") as f:
-                json.dump(stat, f)
-            print(f"rank {rank}: hand-side contact of {len(fingers)} grasps at {args.part_threshold} m: mean fingers in contact "
-                  f"{stat['mean_fingers_in_contact']}, histogram 0..5 {stat['fingers_histogram']}")
-        if want_self:
-            # the run's figures over this rank's grasps in object order: integers, but for the mean (an exactly rounded sum)
-            table = _self_table(net, args.hand_parts, args.self_seam, bool(args.self_palm))
-            counts = [c for p in sorted(self_rows) for c in self_rows[p][0] if c is not None]
-            pairs = [tuple(ab) for p in sorted(self_rows) for g in self_rows[p][1] if g is not None for ab in g]
-            names = table.parts.names
-            stat = {"parts": names, "reach": args.self_reach, "margin": args.self_margin, "seam": args.self_seam,
-                    "palm": int(args.self_palm), "seam_vertices": table.n_seam, "grasps": len(counts),
-                    "share_penetrating": sum(1 for c in counts if c > 0) / len(counts) if counts else None,
-                    "mean_penetrating": math.fsum(counts) / len(counts) if counts else None,
-                    "pair_histogram": [[pairs.count((a, b)) for b in range(len(names))] for a in range(len(names))]}
-            name = "self_collision.json" if world == 1 else f"self_collision_rank{rank}.json"
-            with open(os.path.join(args.out_dir, name), "w") as f:
-                json.dump(stat, f)
-            print(f"rank {rank}: self-collision of {len(counts)} grasps at reach {args.self_reach} m, margin {args.self_margin} m: share "
-                  f"with a penetrating vertex {stat['share_penetrating']}, mean count {stat['mean_penetrating']}")
-        if want_mesh:
-            # the run's figures over this rank's grasps in object order: integers, but for the means (exactly rounded sums)
-            depths = [d for p in sorted(mesh_rows) for d in mesh_rows[p][0] if d is not None]
-            counts = [c for p in sorted(mesh_rows) for c in mesh_rows[p][1] if c is not None]
-            maps = [mesh_rows[p][2] for p in sorted(mesh_rows)]
-            stat = {"grasps": len(counts), "mean_depth_cm": math.fsum(depths) / len(depths) if depths else None,
-                    "mean_interior": math.fsum(counts) / len(counts) if counts else None,
-                    "share_penetrating": sum(1 for c in counts if c > 0) / len(counts) if counts else None,
-                    "mesh_penetration_map": [int(sum(col)) for col in zip(*maps)]}
-            name = "mesh_penetration.json" if world == 1 else f"mesh_penetration_rank{rank}.json"
-            with open(os.path.join(args.out_dir, name), "w") as f:
-                json.dump(stat, f)
-            print(f"rank {rank}: penetration depth against the meshes of {len(counts)} grasps: mean depth {stat['mean_depth_cm']} cm, "
-                  f"mean inside count {stat['mean_interior']}, share with a vertex inside {stat['share_penetrating']}")
+        for fig in active:                                                         # the run's figures over this rank's grasps in object order
+            stat, line = fig.summary(args, net, [fig_rows[fig.key][p] for p in sorted(fig_rows[fig.key])])
+            _write_summary(args.out_dir, fig.stem, rank, world, stat)
+            print(f"rank {rank}: {line}")
     else:
         for gi, (name, obj) in enumerate(objs[lo:hi], start=lo):                   # --rows_per_call 0: one call per object
             torch.cuda.synchronize(device)

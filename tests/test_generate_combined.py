@@ -34,15 +34,19 @@ def seed_of(rotate):
 
 
 # ------------------------------------------------------------------------------------------------------ CPU: _host_copy
+def host_copy_pieces():
+    return [torch.zeros(0, dtype=torch.int64), torch.tensor([1.5], dtype=torch.float32), torch.tensor([2 ** 40 + 3], dtype=torch.int64),
+            torch.zeros((0, 3), dtype=torch.float32), torch.tensor([[-2 ** 62, 7], [5, -1]], dtype=torch.int64)[:, :1],
+            torch.tensor([[1, -2, 3]], dtype=torch.int32), torch.tensor([float("nan"), -0.0, 3e38], dtype=torch.float32),
+            torch.tensor([-9, 2 ** 63 - 1], dtype=torch.int64), torch.zeros(0, dtype=torch.int32),
+            torch.arange(12, dtype=torch.float32).reshape(3, 4).t(), torch.zeros((2, 0), dtype=torch.int64)]
+
+
 def test_host_copy_returns_every_piece_in_any_order():
     """int64 pieces at byte offsets 4, 12 and 36 (not multiples of 8), zero-length pieces of every type and at both ends: every piece
     comes back equal to its own .cpu().numpy(), so the function needs no rule about the order of its pieces."""
-    pieces = [torch.zeros(0, dtype=torch.int64), torch.tensor([1.5], dtype=torch.float32), torch.tensor([2 ** 40 + 3], dtype=torch.int64),
-              torch.zeros((0, 3), dtype=torch.float32), torch.tensor([[-2 ** 62, 7], [5, -1]], dtype=torch.int64)[:, :1],
-              torch.tensor([[1, -2, 3]], dtype=torch.int32), torch.tensor([float("nan"), -0.0, 3e38], dtype=torch.float32),
-              torch.tensor([-9, 2 ** 63 - 1], dtype=torch.int64), torch.zeros(0, dtype=torch.int32),
-              torch.arange(12, dtype=torch.float32).reshape(3, 4).t(), torch.zeros((2, 0), dtype=torch.int64)]
-    offsets = np.cumsum([0] + [p.numel() * p.element_size() for p in pieces])
+    pieces = host_copy_pieces()
+    offsets =np.cumsum([0] + [p.numel() * p.element_size() for p in pieces])
     assert [int(o) % 8 for o, p in zip(offsets, pieces) if p.dtype == torch.int64 and p.numel()] == [4, 4, 4]
     host = generate._host_copy(pieces)
     assert len(host) == len(pieces)
@@ -53,6 +57,29 @@ def test_host_copy_returns_every_piece_in_any_order():
     assert host[2].tolist() == [2 ** 40 + 3] and host[4].tolist() == [[-2 ** 62], [5]] and host[7].tolist() == [-9, 2 ** 63 - 1]
     assert [int(x) for x in host[4].reshape(-1)] == [-2 ** 62, 5] and int(host[7].sum()) == 2 ** 63 - 10
     assert generate._host_copy([torch.zeros(0)])[0].shape == (0,)
+
+
+def test_host_groups_returns_every_group_under_its_own_name(monkeypatch):
+    """The pieces above as named groups -- an empty group at the front, in the middle and at the end, and one of zero-length tensors
+    only: every group comes back under its name, its arrays byte-equal to .cpu().numpy() of its pieces, whatever the order of the
+    groups, through one ``.cpu()`` per call."""
+    p = host_copy_pieces()
+    wants = [x.cpu().numpy() for x in p]
+    copies, cpu = [], torch.Tensor.cpu
+    monkeypatch.setattr(torch.Tensor, "cpu", lambda self, *a, **k: (copies.append(1), cpu(self, *a, **k))[1])
+    groups = {"front": [], "hollow": [p[0], p[3]], "params": [p[1], p[2], p[4]], "middle": [], "scores": p[5:8], "mesh": p[8:], "end": []}
+    assert all(x.numel() == 0 for x in groups["hollow"]) and sum(len(g) for g in groups.values()) == len(p)
+    orders = [list(groups), list(groups)[::-1], ["scores", "end", "hollow", "front", "mesh", "middle", "params"]]
+    want_of = {id(x): w for x, w in zip(p, wants)}
+    for n, order in enumerate(orders):
+        host = generate._host_groups({name: groups[name] for name in order})
+        assert list(host) == order and len(copies) == n + 1
+        for name, pieces in groups.items():
+            assert isinstance(host[name], list) and len(host[name]) == len(pieces), name
+            for h, x in zip(host[name], pieces):
+                want = want_of[id(x)]
+                assert h.dtype == want.dtype and h.shape == want.shape and h.tobytes() == want.tobytes(), name
+    assert host["params"][1].tolist() == [2 ** 40 + 3] and host["front"] == host["middle"] == host["end"] == []
 
 
 # ------------------------------------------------------------------------------------------------------ CPU: the rotated objects
@@ -455,6 +482,85 @@ def test_every_combination_without_candidates(ctx, refine_steps, rotate):
         if refine_steps and stab and vol and div and lp:
             assert any((e["refine_iter"] > 0).any() for e in exp), "no row was pushed"
     print(f"refine {refine_steps} rotate {rotate}: JSON lengths seen {sorted(seen)}")
+
+
+# ------------------------------------------------------------------------------------------------------ GPU: every figure together
+def box(half, centre=gref.STILL_CENTRE):
+    """A closed box about ``centre``, 12 outward triangles (tests/test_grasp_mesh.py::cube, moved to the hand)."""
+    v = np.asarray([[x, y, z] for z in (-1, 1) for y in (-1, 1) for x in (-1, 1)], np.float64) * half + np.asarray(centre)
+    f = [[0, 2, 3], [0, 3, 1], [4, 5, 7], [4, 7, 6], [0, 1, 5], [0, 5, 4], [2, 6, 7], [2, 7, 3], [0, 4, 6], [0, 6, 2], [1, 3, 7], [1, 7, 5]]
+    return v, np.asarray(f, np.int64)
+
+
+PARTS_FIELDS = ["fingers_in_contact", "part_contact", "part_dist", "hand_contact_map"]
+MESH_FIELDS = ["mesh_depth", "mesh_interior", "mesh_closed", "mesh_penetration_map"]
+SCORES = ["penetration", "n_interior", "n_contact"]
+ALONE = {"stability": dict(stability=True), "volume": dict(volume=True, volume_res=RES), "parts": dict(parts=True),
+         "self": dict(self_collision=True), "mesh": dict(mesh_depth=True), "diversity": dict(diversity=CLUSTERS), "log_prob": dict(log_prob=True)}
+TOGETHER_KEYS = {0: ["log_prob", *SCORES, "wrench_sums", "stability_key", "volume", "diversity", "parts", "self", "mesh", "params", "vertices", "json"],
+                 M: ["log_prob", "wrench_sums", "stability_key", "diversity", "volume", "volume_scores", "parts", "part_scores", "self",
+                     "self_scores", "mesh", "mesh_scores", "params", "vertices", "candidate", "scores", "json"]}
+TOGETHER_FIELDS = {0: ["recon_params", "R_list", "trans_list", "r_list", "log_prob", *SCORES, *gref.STABILITY_FIELDS, *gref.VOLUME_FIELDS,
+                       "diversity", *PARTS_FIELDS, *contact.SELF_FIELDS, *MESH_FIELDS],
+                   M: ["recon_params", "R_list", "trans_list", "r_list", "candidate", *SCORES, "log_prob", *gref.STABILITY_FIELDS, "diversity",
+                       *gref.VOLUME_FIELDS, *PARTS_FIELDS, *contact.SELF_FIELDS, *MESH_FIELDS]}
+
+
+def same_entry(got, want, what):
+    """A dict entry of one run against the same entry of another: tensors byte for byte (so a NaN compares too), the tensors of a nested
+    dict that the other run has as well, anything else by ``==``."""
+    if torch.is_tensor(want):
+        assert got.dtype == want.dtype and got.shape == want.shape, what
+        assert got.cpu().numpy().tobytes() == want.cpu().numpy().tobytes(), what
+    elif isinstance(want, dict) and any(torch.is_tensor(v) for v in want.values()):
+        assert set(want) <= set(got), (what, set(got), set(want))
+        for k, v in want.items():
+            same_entry(got[k], v, f"{what}[{k}]")
+    else:
+        assert got == want, what
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("candidates", [0, M])
+def test_every_figure_together_is_every_figure_alone(ctx, candidates):
+    """Stability, volume, parts, self-collision, mesh depth, diversity and log_prob in ONE call, on both paths, with no guard limit: none
+    of them changes a parameter, so every dict entry and every JSON field equals the same entry of the run with that switch alone (each
+    pinned by its own stage test), and the keys and fields come in the documented order.  Parts, self-collision and mesh depth ride
+    together in the call's one copy nowhere else."""
+    base = dict(num_grasp=G, rotate=False, candidates=candidates, object_meshes=[box(0.05), box(0.06)])
+    alone = {name: ctx.run({**base, **switch}, n_obj=2) for name, switch in ALONE.items()}
+    everything = {**base, **{k: v for switch in ALONE.values() for k, v in switch.items()}}
+    text0 = None
+    for rows_per_call in (16384, 1):
+        got = ctx.run(everything, rows_per_call, n_obj=2)
+        for i, g in enumerate(got):
+            assert list(g) == TOGETHER_KEYS[candidates] and list(g["json"]) == TOGETHER_FIELDS[candidates], (list(g), list(g["json"]))
+            seen_keys, seen_fields = set(), set()
+            for name, runs in alone.items():
+                one = runs[i]
+                for k in one:
+                    if k != "json":
+                        same_entry(g[k], one[k], f"rows_per_call {rows_per_call} object {i} {name} alone: {k}")
+                for f in one["json"]:
+                    assert g["json"][f] == one["json"][f], (rows_per_call, i, name, f)
+                assert json.dumps({f: g["json"][f] for f in one["json"]}) == json.dumps(one["json"]), (rows_per_call, i, name)
+                seen_keys |= set(one)
+                seen_fields |= set(one["json"])
+            assert seen_keys == set(g) and seen_fields == set(g["json"]), "an entry of the combined run has no run of its own"
+        text = [json.dumps(g["json"]) for g in got]
+        assert "NaN" not in "".join(text)
+        text0 = text0 or text
+        assert text == text0, f"rows_per_call {rows_per_call}: the JSON differs from the first call's"
+    # the conditions on the inputs
+    voxels = [g["json"]["volume_voxels"] for g in got]
+    fingers = [g["json"]["fingers_in_contact"] for g in got]
+    inside = [g["json"]["mesh_interior"] for g in got]
+    print(f"candidates {candidates}: voxels {voxels} fingers in contact {fingers} vertices inside the boxes {inside} "
+          f"self-penetrating {[g['json']['self_penetrating'] for g in got]}")
+    assert all(any(v is not None and v > 0 for v in obj) for obj in voxels), "an object has no row with a positive voxel count"
+    assert any(f is not None and f > 0 for obj in fingers for f in obj), "no finger is in contact"
+    assert all(any(n is not None and n > 0 for n in obj) for obj in inside), "an object has no row with a vertex inside its box"
+    assert all(g["json"]["mesh_closed"] is True for g in got)
 
 
 # ------------------------------------------------------------------------------------------------------ GPU: the entry points
