@@ -14,6 +14,33 @@ import torch
 from . import ops
 
 
+def _host(x, dtype=None):
+    """A tensor (on any device) or an array-like as a numpy array."""
+    return np.asarray(x.detach().cpu() if torch.is_tensor(x) else x, dtype=dtype)
+
+
+class _DeviceTables:
+    """Host tables that the kernels read from device copies, uploaded once per device.  A subclass names its numpy arrays in
+    ``_tables`` and ends its ``__init__`` with ``_start_cache(device)``; ``on(device)`` returns the copies: a tuple in the order of
+    ``_tables``, or the tensor itself when there is one table."""
+    _tables = ()
+
+    def _start_cache(self, device):
+        self._dev = {}
+        if device is not None:
+            self.on(torch.device(device))
+
+    def _upload(self, device):
+        copies = tuple(torch.from_numpy(np.ascontiguousarray(getattr(self, name))).to(device) for name in self._tables)
+        return copies if len(copies) > 1 else copies[0]
+
+    def on(self, device):
+        key = str(device)
+        if key not in self._dev:
+            self._dev[key] = self._upload(device)
+        return self._dev[key]
+
+
 def face_csr(faces, n_verts):
     """faces [F,3] (array-like) -> (faces int32 [F,3], vf_off int32 [V+1], vf_face int32 [3F]) numpy arrays: for each
     vertex the faces that contain it, ascending."""
@@ -169,6 +196,26 @@ def _quat_mul(a, b):
             aw * by - ax * bz + ay * bw + az * bx, aw * bz + ax * by - ay * bx + az * bw)
 
 
+def _quat_rows(quat):
+    """(w, x, y, z) of quaternions [..., 4], float64, normalised."""
+    w, x, y, z = quat.to(torch.float64).unbind(-1)
+    n = torch.sqrt(w * w + x * x + y * y + z * z)
+    return w / n, x / n, y / n, z / n
+
+
+def _quat_matrix(w, x, y, z):
+    """The rotation matrix of a unit quaternion: three rows of three entries, elementwise."""
+    return [[1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y)],
+            [2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x)],
+            [2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)]]
+
+
+def _is_identity(quat):
+    """True where a quaternion [..., 4] is exactly (1, 0, 0, 0)."""
+    w, x, y, z = quat.to(torch.float64).unbind(-1)
+    return (w == 1) & (x == 0) & (y == 0) & (z == 0)
+
+
 def axis_angle_quat(axis_angle):
     """Axis-angle [B,3] -> the unit quaternion [B,4] (w, x, y, z) of the same rotation, float64, elementwise per row; safe at 0."""
     a = axis_angle.to(torch.float64)
@@ -216,20 +263,13 @@ def compose_orient(global_orient, quat):
     ``quat`` is exactly (1, 0, 0, 0) returns its ``global_orient`` untouched."""
     qw, qx, qy, qz = quat.to(torch.float64).unbind(-1)
     out = quat_axis_angle(torch.stack(_quat_mul((qw, qx, qy, qz), axis_angle_quat(global_orient).unbind(-1)), -1)).to(global_orient.dtype)
-    same = ((qw == 1) & (qx == 0) & (qy == 0) & (qz == 0)).unsqueeze(-1)
-    return torch.where(same, global_orient, out)
+    return torch.where(_is_identity(quat).unsqueeze(-1), global_orient, out)
 
 
 def apply_rigid(hand_xyz, pivot, offset, quat):
     """``R (v - c) + c + t`` for hand_xyz [B,V,3], pivot c [B,3], offset t [B,3] and quat [B,4] (w, x, y, z; normalised here): the hand
     ``refine_rigid`` reports, in float64 inside and in ``hand_xyz``'s dtype outside, elementwise per row."""
-    q = quat.to(torch.float64)
-    w, x, y, z = q.unbind(-1)
-    n = torch.sqrt(w * w + x * x + y * y + z * z)
-    w, x, y, z = w / n, x / n, y / n, z / n
-    R = [[1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y)],
-         [2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x)],
-         [2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)]]
+    R = _quat_matrix(*_quat_rows(quat))
     c, t = pivot.to(torch.float64).unsqueeze(1), offset.to(torch.float64).unsqueeze(1)
     d = hand_xyz.to(torch.float64) - c
     dx, dy, dz = d.unbind(-1)
@@ -237,14 +277,15 @@ def apply_rigid(hand_xyz, pivot, offset, quat):
     return (torch.stack(rows, -1) + c + t).to(hand_xyz.dtype)
 
 
-class FingerRig:
+class FingerRig(_DeviceTables):
     """What the articulated push-out knows of the hand's fingers: ``vert_part`` int32 [V] (the finger of every vertex, -1 = none),
     ``vert_w`` float32 [V] (how far the vertex follows its finger's turn, in [0, 1]) and ``joints`` (per finger the index of its
     knuckle among the layer's joints: the pivot of the finger's turn).  Device copies are made once per device (``on``)."""
+    _tables = ("vert_part", "vert_w")                         # on(device): (vert_part int32 [V], vert_w f32 [V])
 
     def __init__(self, vert_part, vert_w, joints, device=None):
-        part = np.asarray(vert_part.detach().cpu() if torch.is_tensor(vert_part) else vert_part)
-        w = np.asarray(vert_w.detach().cpu() if torch.is_tensor(vert_w) else vert_w, dtype=np.float64)
+        part = _host(vert_part)
+        w = _host(vert_w, np.float64)
         self.joints = [int(j) for j in joints]
         if not 1 <= len(self.joints) <= ops.GRASP_FINGERS_MAX_P:
             raise RuntimeError(f"FingerRig: between 1 and {ops.GRASP_FINGERS_MAX_P} fingers (got {len(self.joints)})")
@@ -257,16 +298,7 @@ class FingerRig:
             raise RuntimeError("FingerRig: vert_w must lie in [0, 1]")
         self.vert_part, self.vert_w = part.astype(np.int32), w.astype(np.float32)
         self.n_verts, self.n_fingers = int(part.size), len(self.joints)
-        self._dev = {}
-        if device is not None:
-            self.on(torch.device(device))
-
-    def on(self, device):
-        """(vert_part int32 [V], vert_w f32 [V]) on ``device`` (uploaded once per device)."""
-        key = str(device)
-        if key not in self._dev:
-            self._dev[key] = (torch.from_numpy(self.vert_part).to(device), torch.from_numpy(self.vert_w).to(device))
-        return self._dev[key]
+        self._start_cache(device)
 
     @classmethod
     def from_mano(cls, layer, device=None):
@@ -315,13 +347,6 @@ def refine_fingers(topology, rig, hand_xyz, obj_xyz, pivot, knuckles, steps, pus
     return dict(zip(names, out))
 
 
-def _quat_rows(quat):
-    """(w, x, y, z) of quaternions [..., 4], float64, normalised."""
-    w, x, y, z = quat.to(torch.float64).unbind(-1)
-    n = torch.sqrt(w * w + x * x + y * y + z * z)
-    return w / n, x / n, y / n, z / n
-
-
 def apply_fingers(hand_xyz, rig, knuckles, finger_quat):
     """The blend model of ``refine_fingers``: a vertex v of finger f with weight w becomes ``v + w (R_f (v - c_f) + c_f - v)`` for
     hand_xyz [B,V,3], knuckles c [B,P,3] and finger_quat [B,P,4] (w, x, y, z; normalised here); a vertex of no finger, or of a finger
@@ -331,12 +356,8 @@ def apply_fingers(hand_xyz, rig, knuckles, finger_quat):
     part, wv = rig.on(hand_xyz.device)
     part = part.to(torch.int64)
     v = hand_xyz.to(torch.float64)
-    qw, qx, qy, qz = finger_quat.to(torch.float64).unbind(-1)                       # [B,P]
-    same = (qw == 1) & (qx == 0) & (qy == 0) & (qz == 0)
-    w, x, y, z = _quat_rows(finger_quat)
-    R = [[1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y)],
-         [2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x)],
-         [2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)]]
+    same = _is_identity(finger_quat)                                                # [B,P]
+    R = _quat_matrix(*_quat_rows(finger_quat))
     idx = part.clamp(min=0)                                                         # [V]: finger per vertex (0 where none; masked below)
     c = knuckles.to(torch.float64).index_select(1, idx)                             # [B,V,3]
     d = v - c
@@ -385,8 +406,7 @@ def compose_finger_pose(layer, global_orient, hand_pose, finger_quat, rig):
     acc = z[:, 0:1] * inv[0]
     for k in range(1, 45):
         acc = acc + z[:, k:k + 1] * inv[k]
-    same = ((fq[..., 0] == 1) & (fq[..., 1] == 0) & (fq[..., 2] == 0) & (fq[..., 3] == 0)).all(dim=1, keepdim=True)
-    return torch.where(same, hand_pose, acc.to(hand_pose.dtype))
+    return torch.where(_is_identity(fq).all(dim=1, keepdim=True), hand_pose, acc.to(hand_pose.dtype))
 
 
 def grasp_stability(topology, hand_xyz, obj_xyz, length=0.1, contact_threshold=0.02 ** 2):
@@ -400,9 +420,7 @@ def grasp_stability(topology, hand_xyz, obj_xyz, length=0.1, contact_threshold=0
 
     ``length`` is in metres; 0.1 is a hand-sized default and is UNTUNED, as is the unit-force model.  This is a proxy: it replaces no
     physics run, and its effect on real grasps is NOT measured (no real checkpoint)."""
-    length = float(length)
-    if not 0.0 < length < float("inf"):
-        raise RuntimeError(f"grasp_stability: length must be finite and positive (got {length})")
+    length = ops._positive("grasp_stability", "length", length)
     pen, n_in, n_ct, centre, sums, key = ops.grasp_wrench(hand_xyz.contiguous(), topology.faces, topology.vf_off, topology.vf_face,
                                                           obj_xyz, 1.0 / length, contact_threshold)
     return {"penetration": pen, "n_interior": n_in, "n_contact": n_ct, "centre": centre, "sums": sums, "key": key}
@@ -415,8 +433,8 @@ def wrench_stats(sums, n_contact):
     singular value of the grasp matrix over sqrt(n): 0 = some wrench direction no contact resists).  Three lists of floats, ``None``
     where n == 0 or a sum is not finite (json writes null).  A sphere-like contact patch has near-zero torque rows, so ``min_sv`` is small there by
     construction."""
-    s = np.asarray(sums.detach().cpu() if torch.is_tensor(sums) else sums, dtype=np.float64).reshape(-1, 27)
-    n = np.asarray(n_contact.detach().cpu() if torch.is_tensor(n_contact) else n_contact, dtype=np.int64).reshape(-1)
+    s = _host(sums, np.float64).reshape(-1, 27)
+    n = _host(n_contact, np.int64).reshape(-1)
     if n.shape[0] != s.shape[0]:
         raise RuntimeError("wrench_stats: one n_contact per row of sums")
     iu = np.triu_indices(6)
@@ -485,13 +503,11 @@ def volume_stats(count, depth, res):
     """Host side, float64, row by row: ``penetration_volume`` = count * res^3 * 1e6 in cm^3 and ``penetration_depth`` = depth * 100 in
     cm from ``grasp_volume``'s ``count`` and ``depth`` (arrays or tensors); two lists of floats, ``None`` where count < 0 (json writes
     null)."""
-    c = np.asarray(count.detach().cpu() if torch.is_tensor(count) else count, dtype=np.int64).reshape(-1)
-    d = np.asarray(depth.detach().cpu() if torch.is_tensor(depth) else depth, dtype=np.float64).reshape(-1)
+    c = _host(count, np.int64).reshape(-1)
+    d = _host(depth, np.float64).reshape(-1)
     if c.shape[0] != d.shape[0]:
         raise RuntimeError("volume_stats: one depth per count")
-    res = float(res)
-    if not 0.0 < res < float("inf"):
-        raise RuntimeError(f"volume_stats: res must be finite and positive (got {res})")
+    res = ops._positive("volume_stats", "res", res)
     cell = res * res * res * 1e6
     return {"penetration_volume": [float(k) * cell if k >= 0 else None for k in c],
             "penetration_depth": [float(x) * 100.0 if k >= 0 else None for k, x in zip(c, d)]}
@@ -503,19 +519,20 @@ def volume_limit(max_volume, res):
     return int(min(np.floor(x), 2 ** 31 - 1))
 
 
-class ObjectMeshes:
+class ObjectMeshes(_DeviceTables):
     """The triangle meshes of a call's objects, packed for ``grasp_mesh``: a list of ``(verts [n,3], faces [m,3])`` -> ``verts`` fp32
     [sum n, 3], ``vert_off`` int32 [O+1], ``faces`` int32 [sum m, 3] (indices local to each object's vertices) and ``face_off`` int32
     [O+1] as numpy arrays, uploaded once per device by ``on``.  ``closed[o]``: every edge of object o is used by exactly two faces,
     once in each direction (computed here, on the host) -- only then is "inside" defined; an open mesh is NOT refused, as the
     reference does not refuse it either.  Refused: a face index outside the object's vertices, an object without a face, and more
     than ``ops.GRASP_MESH_MAX_FACES`` faces per object (decimate the mesh first)."""
+    _tables = ("verts", "vert_off", "faces", "face_off")      # on(device): the four of them, in this order
 
     def __init__(self, meshes, device=None):
         vs, fs, self.closed = [], [], []
         for o, (v, f) in enumerate(meshes):
-            v = np.asarray(v.detach().cpu() if torch.is_tensor(v) else v)
-            f = np.asarray(f.detach().cpu() if torch.is_tensor(f) else f)
+            v = _host(v)
+            f = _host(f)
             if v.ndim != 2 or v.shape[1] != 3 or f.ndim != 2 or f.shape[1] != 3 or f.dtype.kind not in "iu":
                 raise RuntimeError(f"ObjectMeshes: object {o}: verts must be [n,3] and faces an integer [m,3] (got {v.shape}, {f.dtype} {f.shape})")
             if f.shape[0] < 1:
@@ -537,9 +554,7 @@ class ObjectMeshes:
         self.vert_off, self.face_off = self.vert_off.astype(np.int32), self.face_off.astype(np.int32)
         self.verts = np.concatenate(vs).reshape(-1, 3) if vs else np.zeros((0, 3), np.float32)
         self.faces = np.concatenate(fs).reshape(-1, 3) if fs else np.zeros((0, 3), np.int32)
-        self._dev = {}
-        if device is not None:
-            self.on(torch.device(device))
+        self._start_cache(device)
 
     @staticmethod
     def _closed(f, n):
@@ -549,14 +564,6 @@ class ObjectMeshes:
             return False
         fwd, rev = np.sort(d[:, 0] * n + d[:, 1]), np.sort(d[:, 1] * n + d[:, 0])
         return bool((np.diff(fwd) != 0).all() and np.array_equal(fwd, rev))
-
-    def on(self, device):
-        """(verts, vert_off, faces, face_off) on ``device`` (uploaded once per device)."""
-        key = str(device)
-        if key not in self._dev:
-            self._dev[key] = tuple(torch.from_numpy(np.ascontiguousarray(x)).to(device)
-                                   for x in (self.verts, self.vert_off, self.faces, self.face_off))
-        return self._dev[key]
 
 
 def load_mesh(path):
@@ -600,6 +607,13 @@ def load_mesh(path):
     if faces.min() < 0 or faces.max() >= verts.shape[0]:
         raise RuntimeError(f"load_mesh: {path}: a face index is outside the file's {verts.shape[0]} vertices")
     return verts, faces
+
+
+def _guard_class(no_figure, poor):
+    """int32 [B] for ``torch.maximum`` with the class of ``select_keys``, from two boolean [B]: 2 where the row has no figure, else 1
+    where it is poor, else 0."""
+    zero = torch.zeros_like(no_figure, dtype=torch.int32)
+    return torch.where(no_figure, torch.full_like(zero, 2), torch.where(poor, torch.ones_like(zero), zero))
 
 
 MESH_OUTPUTS = ("n_inside", "depth", "deep_vertex", "deep_face", "mask", "status")
@@ -650,21 +664,21 @@ def mesh_class(out, max_depth_cm):
         raise RuntimeError(f"mesh_class: max_depth_cm must be >= 0 (got {max_depth_cm})")
     over = depth > torch.tensor(limit, dtype=torch.float64, device=depth.device).to(torch.float32) if limit < float("inf") \
         else torch.zeros_like(n, dtype=torch.bool)
-    one, two = torch.ones_like(n), torch.full_like(n, 2)
-    return torch.where(n < 0, two, torch.where(over, one, torch.zeros_like(n))).to(torch.int32)
+    return _guard_class(n < 0, over)
 
 
 HAND_PARTS_JSON = os.path.join(os.path.dirname(os.path.abspath(__file__)), "network", "hand_parts.json")
 PART_THRESHOLD = 0.005             # metres: the reference's hard-contact tolerance (penetration_tol, CMap_consistency_loss); untuned
 
 
-class HandParts:
+class HandParts(_DeviceTables):
     """A partition of the hand's vertices into parts for ``grasp_parts``: ``labels`` [V] (the part of every vertex, -1 = no part),
     ``names`` (one per part, at most 32; by convention the fingers come first, the thumb as part 0) and the device the int32 label
     vector lives on (None: it follows the first hand it is used with)."""
+    _tables = ("labels",)                                     # on(device): the int32 label vector
 
     def __init__(self, labels, names, device=None):
-        lab = np.asarray(labels.detach().cpu() if torch.is_tensor(labels) else labels)
+        lab = _host(labels)
         if lab.ndim != 1 or lab.size < 1 or lab.dtype.kind not in "iu":
             raise RuntimeError("HandParts: labels must be a non-empty 1-D integer array, one label per vertex")
         self.names = [str(n) for n in names]
@@ -674,16 +688,7 @@ class HandParts:
         self.labels = np.where((lab >= 0) & (lab < len(self.names)), lab, -1).astype(np.int32)
         self.n_verts, self.n_parts = int(lab.size), len(self.names)
         self.sizes = np.bincount(self.labels[self.labels >= 0], minlength=self.n_parts).astype(np.int64)
-        self._dev = {}
-        if device is not None:
-            self.on(torch.device(device))
-
-    def on(self, device):
-        """The int32 label vector on ``device`` (uploaded once per device)."""
-        key = str(device)
-        if key not in self._dev:
-            self._dev[key] = torch.from_numpy(self.labels).to(device)
-        return self._dev[key]
+        self._start_cache(device)
 
     @classmethod
     def from_json(cls, path=None, device=None):
@@ -718,9 +723,7 @@ def grasp_parts(parts, hand_xyz, obj_xyz, threshold=PART_THRESHOLD, want_verts=F
 
     A proximity figure from the hand's side: no contact-force model.  The default threshold is the reference's 5 mm hard-contact
     tolerance and is UNTUNED; its effect on real grasps is NOT measured (no real checkpoint)."""
-    threshold = float(threshold)
-    if not 0.0 < threshold < float("inf"):
-        raise RuntimeError(f"grasp_parts: threshold must be finite and positive (got {threshold})")
+    threshold = ops._positive("grasp_parts", "threshold", threshold)
     if not torch.is_tensor(hand_xyz) or hand_xyz.dim() != 3 or hand_xyz.shape[1] != parts.n_verts:
         raise RuntimeError(f"grasp_parts: the label table has {parts.n_verts} vertices, the hand "
                            f"{tuple(hand_xyz.shape) if torch.is_tensor(hand_xyz) else type(hand_xyz)}")
@@ -730,10 +733,6 @@ def grasp_parts(parts, hand_xyz, obj_xyz, threshold=PART_THRESHOLD, want_verts=F
     if want_verts:
         out.update(vert_dist=vert_dist, vert_idx=vert_idx)
     return out
-
-
-def _host(x, dtype):
-    return np.asarray(x.detach().cpu() if torch.is_tensor(x) else x, dtype=dtype)
 
 
 def part_stats(part_min, part_count, status, min_verts=1, n_fingers=5):
@@ -780,14 +779,13 @@ def parts_class(out, min_fingers, need_thumb, min_verts=1, n_fingers=5):
     poor = on.sum(dim=1) < int(min_fingers)
     if need_thumb:
         poor = poor | ~on[:, 0]
-    one, two = torch.ones_like(status), torch.full_like(status, 2)
-    return torch.where(status != 0, two, torch.where(poor, one, torch.zeros_like(status))).to(torch.int32)
+    return _guard_class(status != 0, poor)
 
 
 SELF_REACH, SELF_MARGIN, SELF_SEAM = 0.01, 0.001, 2    # metres, metres, edge rings: calibrated against false alarms only; untuned
 
 
-class SelfTable:
+class SelfTable(_DeviceTables):
     """What ``grasp_self`` tests a hand of ``parts`` (a ``HandParts``) against itself with: ``source`` int32 [V], 0 at the SEAM
     vertices -- parts of one hand are joined surfaces, and next to a join the vector to the nearest vertex of the other part is
     tangent to the surface, so the sign of the interior test is noise there: a vertex that an edge of ``faces`` joins to a vertex of
@@ -806,7 +804,7 @@ class SelfTable:
         n_fingers = min(n_fingers, P)                           # a table of fewer parts: all of them are fingers
         self.parts, self.seam, self.palm, self.n_fingers = parts, seam, bool(palm), n_fingers
         if source is None:
-            f = np.asarray(faces.detach().cpu() if torch.is_tensor(faces) else faces, dtype=np.int64).reshape(-1, 3)
+            f = _host(faces, np.int64).reshape(-1, 3)
             if f.size and (f.min() < 0 or f.max() >= V):
                 raise RuntimeError(f"SelfTable: a face index is outside [0, {V})")
             edges = np.concatenate([f[:, [0, 1]], f[:, [1, 2]], f[:, [2, 0]]])
@@ -821,7 +819,7 @@ class SelfTable:
                     near = grow
             src = (~near).astype(np.int32)
         else:
-            src = np.asarray(source.detach().cpu() if torch.is_tensor(source) else source)
+            src = _host(source)
             if src.shape != (V,) or src.dtype.kind not in "iub":
                 raise RuntimeError(f"SelfTable: source must be an integer array [{V}] (got {src.dtype} {src.shape})")
             src = (src != 0).astype(np.int32)
@@ -832,23 +830,15 @@ class SelfTable:
             rest = ((1 << P) - 1) & ~fingers if palm else 0
             words = [(fingers & ~(1 << a)) | rest if a < n_fingers else 0 for a in range(P)]
         else:
-            words = [int(w) for w in (pairs.tolist() if hasattr(pairs, "tolist") else pairs)]
-            if len(words) != P:
-                raise RuntimeError(f"SelfTable: pairs must hold {P} words, one per part (got {len(words)})")
-            for a, w in enumerate(words):
-                if not 0 <= w < 1 << P or (w >> a) & 1:
-                    raise RuntimeError(f"SelfTable: pairs[{a}] = {w:#x} names a part at or above {P}, or part {a} itself")
+            words, a = ops._pair_words("SelfTable", pairs, P)
+            if a is not None:
+                raise RuntimeError(f"SelfTable: pairs[{a}] = {words[a]:#x} names a part at or above {P}, or part {a} itself")
         self.pairs = np.asarray(words, dtype=np.uint32)
-        self._dev = {}
-        if device is not None:
-            self.on(torch.device(device))
+        self._start_cache(device)
 
-    def on(self, device):
-        """(labels, source) int32 [V] on ``device`` (uploaded once per device)."""
-        key = str(device)
-        if key not in self._dev:
-            self._dev[key] = (self.parts.on(device), torch.from_numpy(self.source).to(device))
-        return self._dev[key]
+    def _upload(self, device):
+        """(labels, source) int32 [V]; the labels are ``parts``' own copy."""
+        return self.parts.on(device), torch.from_numpy(self.source).to(device)
 
 
 def grasp_self(topology, table, hand_xyz, reach=SELF_REACH, margin=SELF_MARGIN):
@@ -864,11 +854,7 @@ def grasp_self(topology, table, hand_xyz, reach=SELF_REACH, margin=SELF_MARGIN):
     A proximity figure in the style of ``get_interior``, not a mesh-mesh intersection: vertices only, so a thin crossing between
     vertices is missed.  The defaults are calibrated only against false alarms on 48 posed hands of the real hand model and are
     UNTUNED otherwise; the effect on real grasps is NOT measured (no real checkpoint)."""
-    reach, margin = float(reach), float(margin)
-    if not 0.0 < reach < float("inf"):
-        raise RuntimeError(f"grasp_self: reach must be finite and positive (got {reach})")
-    if not 0.0 <= margin < float("inf"):
-        raise RuntimeError(f"grasp_self: margin must be finite and >= 0 (got {margin})")
+    reach, margin = ops._positive("grasp_self", "reach", reach), ops._non_negative("grasp_self", "margin", margin)
     if not isinstance(table, SelfTable):
         raise RuntimeError("grasp_self: table must be a SelfTable")
     V = table.parts.n_verts
@@ -916,8 +902,7 @@ def self_class(out, max_verts):
     ``grasp_self``'s output has no figure (status != 0), else 1 where more than ``max_verts`` vertices penetrate, else 0."""
     cnt, status = out["pen_count"], out["status"]
     over = cnt.sum(dim=1) > int(max_verts)
-    one, two = torch.ones_like(status), torch.full_like(status, 2)
-    return torch.where(status != 0, two, torch.where(over, one, torch.zeros_like(status))).to(torch.int32)
+    return _guard_class(status != 0, over)
 
 
 SELECT_BY = ("penetration", "log_prob", "stability")
@@ -956,14 +941,15 @@ TTT_MOMENTUM = 0.8
 TTT_MAX_STEPS = 1000
 
 
-class ContactTargets:
+class ContactTargets(_DeviceTables):
     """The hand vertices the contact term of ``ttt_terms`` measures distances to (the reference's ``prior_idx`` subset of
     ``Contact_loss``): built from a list of vertex indices or from a boolean mask of ``n_verts`` entries; ``from_json`` reads a JSON
     file that holds a list of indices.  ``on(device)`` is the int32 flag vector [n_verts] the kernel takes (uploaded once per device).
     An empty set is refused; "every vertex" is ``targets=None`` at the call, not an object of this class."""
+    _tables = ("flags",)
 
     def __init__(self, spec, n_verts=778, device=None):
-        a = np.asarray(spec.detach().cpu() if torch.is_tensor(spec) else spec)
+        a = _host(spec)
         n_verts = int(n_verts)
         if a.dtype == np.bool_:
             if a.ndim != 1 or a.size != n_verts:
@@ -981,16 +967,7 @@ class ContactTargets:
         self.indices = idx.astype(np.int64)
         self.flags = np.zeros(n_verts, np.int32)
         self.flags[idx] = 1
-        self._dev = {}
-        if device is not None:
-            self.on(torch.device(device))
-
-    def on(self, device):
-        """The int32 flag vector on ``device`` (uploaded once per device)."""
-        key = str(device)
-        if key not in self._dev:
-            self._dev[key] = torch.from_numpy(self.flags).to(device)
-        return self._dev[key]
+        self._start_cache(device)
 
     @classmethod
     def from_json(cls, path, n_verts=778, device=None):

@@ -6,7 +6,9 @@ torch caching allocator and enqueues the HIP work on torch's *current* stream.  
 """
 from __future__ import annotations
 
+import contextlib
 import math
+import threading
 import ctypes as C
 from typing import Dict, List, Optional, Sequence, Tuple
 
@@ -51,6 +53,51 @@ def _rows(t: Tensor, name: str) -> Tuple[int, int]:
     return t.data_ptr(), (t.stride(0) if t.shape[0] > 1 else max(t.stride(0), t.shape[1]))
 
 
+def _tensors(what: str, names: str, *xs) -> None:
+    """Every ``x`` must be a tensor; ``names`` holds their names, separated by blanks, for the refusal."""
+    for i, x in enumerate(xs):
+        if not isinstance(x, Tensor):
+            raise RuntimeError(f"{what}: {names.split()[i]} must be a tensor")
+
+
+def _int32_tables(what: str, names: str, *xs: Tensor) -> None:
+    for i, x in enumerate(xs):
+        if x.dtype != torch.int32 or not x.is_contiguous():
+            raise RuntimeError(f"{what}: {names.split()[i]} must be contiguous int32")
+
+
+def _positive(what: str, name: str, x) -> float:
+    x = float(x)
+    if not 0.0 < x < math.inf:
+        raise RuntimeError(f"{what}: {name} must be finite and positive (got {x})")
+    return x
+
+
+def _non_negative(what: str, name: str, x) -> float:
+    x = float(x)
+    if not 0.0 <= x < math.inf:
+        raise RuntimeError(f"{what}: {name} must be finite and >= 0 (got {x})")
+    return x
+
+
+def _obj_of_row(what: str, x: Tensor, B: int) -> None:
+    if _i64(x, "obj_of_row").shape != (B,) or not x.is_contiguous():
+        raise RuntimeError(f"{what}: `obj_of_row` must be a contiguous int64 [B] tensor")
+
+
+_F, _I, _L = torch.float32, torch.int32, torch.int64
+
+
+def _outputs(rows: int, dev: torch.device, *spec):
+    """One uninitialised [rows, *trailing] tensor per ``(dtype, *trailing)`` of ``spec``; ``None`` (an optional output that was not
+    asked for) stays ``None``, which ``_ptr`` hands to the library as a null pointer."""
+    return tuple(None if s is None else torch.empty(rows, *s[1:], dtype=s[0], device=dev) for s in spec)
+
+
+def _ptr(t: Optional[Tensor]):
+    return None if t is None else t.data_ptr()
+
+
 def _stream(dev: torch.device) -> int:
     return torch.cuda.current_stream(dev).cuda_stream
 
@@ -83,15 +130,25 @@ def new_err_flag(dev: torch.device) -> Tensor:
     return torch.zeros(1, dtype=torch.int32, device=dev)
 
 
+@contextlib.contextmanager
+def _err_flag(err: Optional[Tensor], dev: torch.device, message):
+    """``with _err_flag(err, dev, message) as flag:`` around a launch that reports through an int32 flag.  ``flag`` is the caller's
+    ``err`` -- then the caller reads it and nothing synchronises here -- or a fresh one, read once after the block: a non-zero value
+    raises ``RuntimeError(message)``; a wrapper whose bits mean different things passes a function of the value for ``message``."""
+    flag = new_err_flag(dev) if err is None else err
+    yield flag
+    if err is None:
+        bad = int(flag.item())
+        if bad:
+            raise RuntimeError(message(bad) if callable(message) else message)
+
+
 # ------------------------------------------------------------------------------------------ fp16 range
 # The default GEMM arithmetic carries activations as two fp16 pieces: a value beyond fp16's range (|x| >= 65 520) turns its output
 # ROW into NaN -- never a silently wrong number (csrc/gemm_f16x2.hip).  Every entry point that multiplies on those images looks at
 # its result once (one host synchronisation) and runs the call again on the six-product bf16 images, which have fp32's range, when
 # it holds a non-finite value; inputs that are themselves NaN / Inf come out non-finite there too, as in the reference.
 # GenNet.gen makes ONE such check for the whole path and switches the per-op checks off around its inner calls.
-import contextlib
-import threading
-
 _range_state = threading.local()                            # per host thread: one thread's gen() must not switch another's checks off
 
 
@@ -296,14 +353,9 @@ def vq_lookup(E: Tensor, idx: Tensor, out: Optional[Tensor] = None, err: Optiona
     if out is None:
         out = torch.empty(M, D, dtype=torch.float32, device=dev)
     po, ldo = _rows(_f32(out, "out"), "out")
-    own_err = err is None
-    if own_err:
-        err = new_err_flag(dev)
-    with torch.cuda.device(dev):
+    with _err_flag(err, dev, f"index out of bounds for codebook with {K} rows") as flag, torch.cuda.device(dev):
         check(lib.dvq_vq_lookup(E.data_ptr(), idx.data_ptr(), idx.stride(0) if M > 1 else 1, M, K, D, po, ldo,
-                                err.data_ptr(), _stream(dev)), "dvq_vq_lookup")
-    if own_err and int(err.item()) != 0:
-        raise RuntimeError(f"index out of bounds for codebook with {K} rows")
+                                flag.data_ptr(), _stream(dev)), "dvq_vq_lookup")
     return out
 
 
@@ -360,14 +412,9 @@ def exp1_noise_keyed(stream_ids: Tensor, row_ids: Tensor, cols: int, seed: int, 
         out = torch.empty(rows, cols, dtype=torch.float32, device=dev)
     if tuple(out.shape) != (rows, cols) or not out.is_contiguous() or out.dtype != torch.float32:
         raise RuntimeError("exp1_noise_keyed: `out` must be a contiguous float32 [rows, cols] tensor")
-    own_err = err is None
-    if own_err:
-        err = new_err_flag(dev)
-    with torch.cuda.device(dev):
+    with _err_flag(err, dev, "exp1_noise_keyed: stream id outside [0, 2^32) or negative row id") as flag, torch.cuda.device(dev):
         check(lib.dvq_exp1_noise_keyed(int(seed) & 0xFFFFFFFFFFFFFFFF, stream_ids.data_ptr(), row_ids.data_ptr(), rows, cols,
-                                       out.data_ptr(), err.data_ptr(), _stream(dev)), "dvq_exp1_noise_keyed")
-    if own_err and int(err.item()) != 0:
-        raise RuntimeError("exp1_noise_keyed: stream id outside [0, 2^32) or negative row id")
+                                       out.data_ptr(), flag.data_ptr(), _stream(dev)), "dvq_exp1_noise_keyed")
     return out
 
 
@@ -723,24 +770,18 @@ def transform_clouds(pc: Tensor, obj_of_row: Tensor, R: Tensor, t: Optional[Tens
     left unwritten)."""
     lib = _lib.load()
     dev = _require_gpu(pc, obj_of_row, R, t, err)
-    _f32(pc, "pc"), _f32(R, "R"), _i64(obj_of_row, "obj_of_row")
+    _f32(pc, "pc"), _f32(R, "R")
     if t is not None and (_f32(t, "t").numel() != 3 or not t.is_contiguous()):
         raise RuntimeError("transform_clouds: expected contiguous t [3]")
     B = R.shape[0]
     if pc.dim() != 3 or not pc.is_contiguous() or not R.is_contiguous() or tuple(R.shape[1:]) != (3, 3):
         raise RuntimeError("transform_clouds: expected contiguous pc [O,C,N] and R [B,3,3]")
-    if obj_of_row.dim() != 1 or obj_of_row.shape[0] != B or not obj_of_row.is_contiguous():
-        raise RuntimeError("transform_clouds: `obj_of_row` must be a contiguous int64 [B] tensor")
+    _obj_of_row("transform_clouds", obj_of_row, B)
     O, Cc, N = pc.shape
     out = torch.empty(B, Cc, N, dtype=torch.float32, device=dev)
-    own_err = err is None
-    if own_err:
-        err = new_err_flag(dev)
-    with torch.cuda.device(dev):
-        check(lib.dvq_transform_clouds(pc.data_ptr(), obj_of_row.data_ptr(), O, R.data_ptr(), t.data_ptr() if t is not None else None,
-                                       B, Cc, N, out.data_ptr(), err.data_ptr(), _stream(dev)), "dvq_transform_clouds")
-    if own_err and int(err.item()) != 0:
-        raise RuntimeError(f"transform_clouds: object index out of bounds for {O} clouds")
+    with _err_flag(err, dev, f"transform_clouds: object index out of bounds for {O} clouds") as flag, torch.cuda.device(dev):
+        check(lib.dvq_transform_clouds(pc.data_ptr(), obj_of_row.data_ptr(), O, R.data_ptr(), _ptr(t), B, Cc, N, out.data_ptr(),
+                                       flag.data_ptr(), _stream(dev)), "dvq_transform_clouds")
     return out
 
 
@@ -750,7 +791,7 @@ def _points(x: Tensor, name: str):
     if x.dim() != 3 or x.shape[2] != 3:
         raise RuntimeError(f"{name}: expected [B,N,3] (got {tuple(x.shape)})")
     _f32(x, name)
-    return x.data_ptr(), x.stride(0), x.stride(1), x.stride(2)
+    return (x.data_ptr(),) + x.stride()
 
 
 def nn_points(src: Tensor, trg: Tensor):
@@ -777,9 +818,7 @@ def vertex_normals(verts: Tensor, faces: Tensor, vf_off: Tensor, vf_face: Tensor
     lib = _lib.load()
     dev = _require_gpu(verts, faces, vf_off, vf_face)
     _f32(verts, "verts")
-    for t, n in ((faces, "faces"), (vf_off, "vf_off"), (vf_face, "vf_face")):
-        if t.dtype != torch.int32 or not t.is_contiguous():
-            raise RuntimeError(f"vertex_normals: {n} must be contiguous int32")
+    _int32_tables("vertex_normals", "faces vf_off vf_face", faces, vf_off, vf_face)
     if verts.dim() != 3 or verts.shape[2] != 3 or not verts.is_contiguous():
         raise RuntimeError("vertex_normals: verts must be contiguous [B,V,3]")
     B, V = verts.shape[0], verts.shape[1]
@@ -818,24 +857,61 @@ def _hand_cloud_args(what: str, hand: Tensor, faces: Tensor, vf_off: Tensor, vf_
     """The arguments ``grasp_scores``, ``grasp_wrench`` and ``grasp_refine`` share -- hand [B,V,3] contiguous, the topology of
     ``contact.face_csr``, obj [B,N,3] with any strides -- checked before any device use -> (obj's pointer and its three strides,
     B, V, N)."""
-    for t, n in ((hand, "hand"), (obj, "obj"), (faces, "faces"), (vf_off, "vf_off"), (vf_face, "vf_face")):
-        if not isinstance(t, Tensor):
-            raise RuntimeError(f"{what}: {n} must be a tensor")
-    _f32(hand, "hand")
-    for t, n in ((faces, "faces"), (vf_off, "vf_off"), (vf_face, "vf_face")):
-        if t.dtype != torch.int32 or not t.is_contiguous():
-            raise RuntimeError(f"{what}: {n} must be contiguous int32")
-    if hand.dim() != 3 or hand.shape[2] != 3 or not hand.is_contiguous():
-        raise RuntimeError(f"{what}: hand must be contiguous [B,V,3]")
-    po, ob, op, oc = _points(obj, "obj")
-    B, V, N = hand.shape[0], hand.shape[1], obj.shape[1]
-    if obj.shape[0] != B:
-        raise RuntimeError(f"{what}: batch mismatch")
-    if N < 1 or not 1 <= V <= GRASP_SCORES_MAX_V:
-        raise RuntimeError(f"{what}: need N >= 1 and 1 <= V <= {GRASP_SCORES_MAX_V} (got N={N} V={V})")
-    if faces.dim() != 2 or faces.shape[1] != 3 or vf_off.numel() != V + 1 or vf_face.numel() != faces.numel():
-        raise RuntimeError(f"{what}: CSR does not match the mesh")
+    _tensors(what, "hand obj faces vf_off vf_face", hand, obj, faces, vf_off, vf_face)
+    _int32_tables(what, "faces vf_off vf_face", faces, vf_off, vf_face)
+    po, ob, op, oc, B, V, N = _hand_cloud(what, hand, obj)
+    _csr(what, faces, vf_off, vf_face, V)
     return po, ob, op, oc, B, V, N
+
+
+def _hand(what: str, hand: Tensor, N: Optional[int] = None) -> Tuple[int, int]:
+    """hand fp32 [B,V,3], contiguous, 1 <= V <= GRASP_SCORES_MAX_V -> (B, V).  A wrapper that scans a cloud passes its point count
+    ``N``, which must be >= 1 and shares the bound's message."""
+    _f32(hand, "hand")
+    shape = hand.shape
+    if len(shape) != 3 or shape[2] != 3 or not hand.is_contiguous():
+        raise RuntimeError(f"{what}: hand must be contiguous [B,V,3]")
+    B, V = shape[0], shape[1]
+    if N is None:
+        if not 1 <= V <= GRASP_SCORES_MAX_V:
+            raise RuntimeError(f"{what}: need 1 <= V <= {GRASP_SCORES_MAX_V} (got V={V})")
+    elif N < 1 or not 1 <= V <= GRASP_SCORES_MAX_V:
+        raise RuntimeError(f"{what}: need N >= 1 and 1 <= V <= {GRASP_SCORES_MAX_V} (got N={N} V={V})")
+    return B, V
+
+
+def _hand_cloud(what: str, hand: Tensor, obj: Tensor):
+    """``_hand`` against a cloud obj [B,N,3] with any strides -> (obj's pointer and its three strides, B, V, N)."""
+    po, ob, op, oc = _points(obj, "obj")
+    rows, N, _ = obj.shape
+    B, V = _hand(what, hand, N)
+    if rows != B:
+        raise RuntimeError(f"{what}: batch mismatch")
+    return po, ob, op, oc, B, V, N
+
+
+def _csr(what: str, faces: Tensor, vf_off: Tensor, vf_face: Tensor, V: int) -> None:
+    shape = faces.shape
+    if len(shape) != 2 or shape[1] != 3 or vf_off.numel() != V + 1 or vf_face.numel() != 3 * shape[0]:
+        raise RuntimeError(f"{what}: CSR does not match the mesh")
+
+
+def _labels(what: str, V: int, names: str, *xs: Tensor) -> None:
+    """Per-vertex tables (``part_of_vertex``, ``source_of_vertex``): contiguous int32 [V]."""
+    for i, x in enumerate(xs):
+        if x.dtype != torch.int32 or not x.is_contiguous() or x.shape != (V,):
+            raise RuntimeError(f"{what}: {names.split()[i]} must be contiguous int32 [{V}] (got {x.dtype} {tuple(x.shape)})")
+
+
+def _frame(what: str, R: Optional[Tensor], t: Optional[Tensor], B: int) -> None:
+    """The object frame ``transform_clouds`` got: R [B,3,3] and t [3], fp32 and contiguous, or None for objects in place (the launch
+    passes ``_ptr(R)``, ``_ptr(t)``)."""
+    if R is None and t is not None:
+        raise RuntimeError(f"{what}: t without R")
+    if R is not None and (not isinstance(R, Tensor) or tuple(_f32(R, "R").shape) != (B, 3, 3) or not R.is_contiguous()):
+        raise RuntimeError(f"{what}: expected contiguous R [B,3,3]")
+    if t is not None and (not isinstance(t, Tensor) or _f32(t, "t").numel() != 3 or not t.is_contiguous()):
+        raise RuntimeError(f"{what}: expected contiguous t [3]")
 
 
 def grasp_scores(hand: Tensor, faces: Tensor, vf_off: Tensor, vf_face: Tensor, obj: Tensor, contact_threshold: float = 0.02 ** 2):
@@ -845,14 +921,11 @@ def grasp_scores(hand: Tensor, faces: Tensor, vf_off: Tensor, vf_face: Tensor, o
     po, ob, op, oc, B, V, N = _hand_cloud_args("grasp_scores", hand, faces, vf_off, vf_face, obj)
     dev = _require_gpu(hand, obj, faces, vf_off, vf_face)
     lib = _lib.load()
-    pen = torch.empty(B, dtype=torch.float32, device=dev)
-    n_in = torch.empty(B, dtype=torch.int32, device=dev)
-    n_ct = torch.empty(B, dtype=torch.int32, device=dev)
+    outs = _outputs(B, dev, (_F,), (_I,), (_I,))                                       # penetration, n_interior, n_contact
     with torch.cuda.device(dev):
         check(lib.dvq_grasp_scores(hand.data_ptr(), faces.data_ptr(), vf_off.data_ptr(), vf_face.data_ptr(), V, po, ob, op, oc, B, N,
-                                   float(contact_threshold), pen.data_ptr(), n_in.data_ptr(), n_ct.data_ptr(), _stream(dev)),
-              "dvq_grasp_scores")
-    return pen, n_in, n_ct
+                                   float(contact_threshold), *map(_ptr, outs), _stream(dev)), "dvq_grasp_scores")
+    return outs
 
 
 GRASP_WRENCH_SUMS = 27             # csrc/grasp_wrench.hip: GW_SUMS (the wrench's 6 sums, then the upper triangle of sum w w^T)
@@ -865,22 +938,14 @@ def grasp_wrench(hand: Tensor, faces: Tensor, vf_off: Tensor, vf_face: Tensor, o
     three are the bits of ``grasp_scores``; ``inv_length`` is the reciprocal of the length that scales torques to forces.
     Arguments as ``grasp_scores`` (obj [B,N,3] with any strides, read in place)."""
     po, ob, op, oc, B, V, N = _hand_cloud_args("grasp_wrench", hand, faces, vf_off, vf_face, obj)
-    inv_length = float(inv_length)
-    if not 0.0 < inv_length < float("inf"):
-        raise RuntimeError(f"grasp_wrench: inv_length must be finite and positive (got {inv_length})")
+    inv_length = _positive("grasp_wrench", "inv_length", inv_length)
     dev = _require_gpu(hand, obj, faces, vf_off, vf_face)
     lib = _lib.load()
-    pen = torch.empty(B, dtype=torch.float32, device=dev)
-    n_in = torch.empty(B, dtype=torch.int32, device=dev)
-    n_ct = torch.empty(B, dtype=torch.int32, device=dev)
-    centre = torch.empty(B, 3, dtype=torch.float32, device=dev)
-    sums = torch.empty(B, GRASP_WRENCH_SUMS, dtype=torch.float32, device=dev)
-    key = torch.empty(B, dtype=torch.float32, device=dev)
+    outs = _outputs(B, dev, (_F,), (_I,), (_I,), (_F, 3), (_F, GRASP_WRENCH_SUMS), (_F,))   # penetration .. n_contact, centre, sums, key
     with torch.cuda.device(dev):
         check(lib.dvq_grasp_wrench(hand.data_ptr(), faces.data_ptr(), vf_off.data_ptr(), vf_face.data_ptr(), V, po, ob, op, oc, B, N,
-                                   float(contact_threshold), inv_length, pen.data_ptr(), n_in.data_ptr(), n_ct.data_ptr(),
-                                   centre.data_ptr(), sums.data_ptr(), key.data_ptr(), _stream(dev)), "dvq_grasp_wrench")
-    return pen, n_in, n_ct, centre, sums, key
+                                   float(contact_threshold), inv_length, *map(_ptr, outs), _stream(dev)), "dvq_grasp_wrench")
+    return outs
 
 
 GRASP_PARTS_TILE = 2048            # csrc/grasp_parts.hip: GP_TILE (the cloud's points per LDS tile)
@@ -895,45 +960,39 @@ def grasp_parts(hand: Tensor, part_of_vertex: Tensor, n_parts: int, obj: Tensor,
     number of its vertices closer than the threshold, a bit per vertex (W = (V + 31) // 32), status 1 for a row with a non-finite
     coordinate (NaN / -1 / 0 there), and with ``want_verts`` the bits of ``nn_points(hand, obj)`` as f32 [B,V] and int32 [B,V]
     (None otherwise)."""
-    for t, n in ((hand, "hand"), (part_of_vertex, "part_of_vertex"), (obj, "obj")):
-        if not isinstance(t, Tensor):
-            raise RuntimeError(f"grasp_parts: {n} must be a tensor")
-    _f32(hand, "hand")
-    if hand.dim() != 3 or hand.shape[2] != 3 or not hand.is_contiguous():
-        raise RuntimeError("grasp_parts: hand must be contiguous [B,V,3]")
-    po, ob, op, oc = _points(obj, "obj")
-    B, V, N = hand.shape[0], hand.shape[1], obj.shape[1]
-    if obj.shape[0] != B:
-        raise RuntimeError("grasp_parts: batch mismatch")
-    if N < 1 or not 1 <= V <= GRASP_SCORES_MAX_V:
-        raise RuntimeError(f"grasp_parts: need N >= 1 and 1 <= V <= {GRASP_SCORES_MAX_V} (got N={N} V={V})")
+    _tensors("grasp_parts", "hand part_of_vertex obj", hand, part_of_vertex, obj)
+    po, ob, op, oc, B, V, N = _hand_cloud("grasp_parts", hand, obj)
     n_parts = int(n_parts)
     if not 1 <= n_parts <= GRASP_PARTS_MAX_P:
         raise RuntimeError(f"grasp_parts: need 1 <= n_parts <= {GRASP_PARTS_MAX_P} (got {n_parts})")
-    if part_of_vertex.dtype != torch.int32 or not part_of_vertex.is_contiguous() or tuple(part_of_vertex.shape) != (V,):
-        raise RuntimeError(f"grasp_parts: part_of_vertex must be contiguous int32 [{V}] (got {part_of_vertex.dtype} "
-                           f"{tuple(part_of_vertex.shape)})")
+    _labels("grasp_parts", V, "part_of_vertex", part_of_vertex)
     contact_threshold = float(contact_threshold)
     if math.isnan(contact_threshold):
         raise RuntimeError("grasp_parts: contact_threshold is NaN")
     dev = _require_gpu(hand, obj, part_of_vertex)
     lib = _lib.load()
-    W = (V + 31) // 32
-    part_min = torch.empty(B, n_parts, dtype=torch.float32, device=dev)
-    part_count = torch.empty(B, n_parts, dtype=torch.int32, device=dev)
-    mask = torch.empty(B, W, dtype=torch.int32, device=dev)
-    status = torch.empty(B, dtype=torch.int32, device=dev)
-    vert_dist = torch.empty(B, V, dtype=torch.float32, device=dev) if want_verts else None
-    vert_idx = torch.empty(B, V, dtype=torch.int32, device=dev) if want_verts else None
+    # part_min, part_count, mask, status, vert_dist, vert_idx
+    outs = _outputs(B, dev, (_F, n_parts), (_I, n_parts), (_I, (V + 31) // 32), (_I,), *(((_F, V), (_I, V)) if want_verts else (None, None)))
     with torch.cuda.device(dev):
         check(lib.dvq_grasp_parts(hand.data_ptr(), part_of_vertex.data_ptr(), V, n_parts, po, ob, op, oc, B, N, contact_threshold,
-                                  part_min.data_ptr(), part_count.data_ptr(), mask.data_ptr(), status.data_ptr(),
-                                  vert_dist.data_ptr() if want_verts else None, vert_idx.data_ptr() if want_verts else None,
-                                  _stream(dev)), "dvq_grasp_parts")
-    return part_min, part_count, mask, status, vert_dist, vert_idx
+                                  *map(_ptr, outs), _stream(dev)), "dvq_grasp_parts")
+    return outs
 
 
 GRASP_SELF_MAX_P = 32               # csrc/grasp_self.hip: GSELF_MAX_P (one bit per part)
+
+
+def _pair_words(what: str, pairs, n_parts: int):
+    """``pairs`` (a sequence of ints or an integer array) of ``grasp_self`` / ``contact.SelfTable`` -> (its ``n_parts`` words as ints,
+    the first index whose word names a part outside [0, n_parts) or its own part -- the caller words that refusal -- or None)."""
+    words = [int(w) for w in (pairs.tolist() if hasattr(pairs, "tolist") else pairs)]
+    if len(words) != n_parts:
+        raise RuntimeError(f"{what}: pairs must hold {n_parts} words, one per part (got {len(words)})")
+    top = 1 << n_parts
+    for a, w in enumerate(words):
+        if not 0 <= w < top or (w >> a) & 1:
+            return words, a
+    return words, None
 
 
 def grasp_self(hand: Tensor, faces: Tensor, vf_off: Tensor, vf_face: Tensor, part_of_vertex: Tensor, source_of_vertex: Tensor,
@@ -946,56 +1005,30 @@ def grasp_self(hand: Tensor, faces: Tensor, vf_off: Tensor, vf_face: Tensor, par
     pair_bits [B,P] i32, mask [B,W] i32, status [B] i32)``: per part the number of penetrating vertices, the largest depth (+0.0
     without one), the smallest squared distance of a source vertex to its targets (+inf without one) and the parts hit, a bit per
     vertex (W = (V + 31) // 32), status 1 for a row with a non-finite coordinate (-1 / NaN / NaN / 0 / 0 there)."""
-    for t, n in ((hand, "hand"), (faces, "faces"), (vf_off, "vf_off"), (vf_face, "vf_face"), (part_of_vertex, "part_of_vertex"),
-                 (source_of_vertex, "source_of_vertex")):
-        if not isinstance(t, Tensor):
-            raise RuntimeError(f"grasp_self: {n} must be a tensor")
-    _f32(hand, "hand")
-    for t, n in ((faces, "faces"), (vf_off, "vf_off"), (vf_face, "vf_face")):
-        if t.dtype != torch.int32 or not t.is_contiguous():
-            raise RuntimeError(f"grasp_self: {n} must be contiguous int32")
-    if hand.dim() != 3 or hand.shape[2] != 3 or not hand.is_contiguous():
-        raise RuntimeError("grasp_self: hand must be contiguous [B,V,3]")
-    B, V = hand.shape[0], hand.shape[1]
-    if not 1 <= V <= GRASP_SCORES_MAX_V:
-        raise RuntimeError(f"grasp_self: need 1 <= V <= {GRASP_SCORES_MAX_V} (got V={V})")
-    if faces.dim() != 2 or faces.shape[1] != 3 or vf_off.numel() != V + 1 or vf_face.numel() != faces.numel():
-        raise RuntimeError("grasp_self: CSR does not match the mesh")
+    what = "grasp_self"
+    _tensors(what, "hand faces vf_off vf_face part_of_vertex source_of_vertex", hand, faces, vf_off, vf_face, part_of_vertex, source_of_vertex)
+    _int32_tables(what, "faces vf_off vf_face", faces, vf_off, vf_face)
+    B, V = _hand(what, hand)
+    _csr(what, faces, vf_off, vf_face, V)
     n_parts = int(n_parts)
     if not 1 <= n_parts <= GRASP_SELF_MAX_P:
         raise RuntimeError(f"grasp_self: need 1 <= n_parts <= {GRASP_SELF_MAX_P} (got {n_parts})")
-    for t, n in ((part_of_vertex, "part_of_vertex"), (source_of_vertex, "source_of_vertex")):
-        if t.dtype != torch.int32 or not t.is_contiguous() or tuple(t.shape) != (V,):
-            raise RuntimeError(f"grasp_self: {n} must be contiguous int32 [{V}] (got {t.dtype} {tuple(t.shape)})")
-    words = [int(w) for w in (pairs.tolist() if hasattr(pairs, "tolist") else pairs)]
-    if len(words) != n_parts:
-        raise RuntimeError(f"grasp_self: pairs must hold {n_parts} words, one per part (got {len(words)})")
-    for a, w in enumerate(words):
-        if not 0 <= w < 1 << n_parts:
-            raise RuntimeError(f"grasp_self: pairs[{a}] = {w:#x} names a part at or above n_parts = {n_parts} (or is negative)")
-        if (w >> a) & 1:
-            raise RuntimeError(f"grasp_self: pairs[{a}] tests part {a} against itself")
-    reach2, margin = float(reach2), float(margin)
-    if not 0.0 < reach2 < float("inf"):
-        raise RuntimeError(f"grasp_self: reach2 must be finite and positive (got {reach2})")
-    if not 0.0 <= margin < float("inf"):
-        raise RuntimeError(f"grasp_self: margin must be finite and >= 0 (got {margin})")
+    _labels(what, V, "part_of_vertex source_of_vertex", part_of_vertex, source_of_vertex)
+    words, a = _pair_words(what, pairs, n_parts)
+    if a is not None:
+        raise RuntimeError(f"grasp_self: pairs[{a}] tests part {a} against itself" if 0 <= words[a] < 1 << n_parts else
+                           f"grasp_self: pairs[{a}] = {words[a]:#x} names a part at or above n_parts = {n_parts} (or is negative)")
+    reach2, margin = _positive(what, "reach2", reach2), _non_negative(what, "margin", margin)
     dev = _require_gpu(hand, faces, vf_off, vf_face, part_of_vertex, source_of_vertex)
     lib = _lib.load()
-    W = (V + 31) // 32
-    pen_count = torch.empty(B, n_parts, dtype=torch.int32, device=dev)
-    pen_depth = torch.empty(B, n_parts, dtype=torch.float32, device=dev)
-    gap_min = torch.empty(B, n_parts, dtype=torch.float32, device=dev)
-    pair_bits = torch.empty(B, n_parts, dtype=torch.int32, device=dev)
-    mask = torch.empty(B, W, dtype=torch.int32, device=dev)
-    status = torch.empty(B, dtype=torch.int32, device=dev)
+    # pen_count, pen_depth, gap_min, pair_bits, mask, status
+    outs = _outputs(B, dev, (_I, n_parts), (_F, n_parts), (_F, n_parts), (_I, n_parts), (_I, (V + 31) // 32), (_I,))
     host_pairs = (C.c_uint32 * n_parts)(*words)                # read by the library before the call returns
     with torch.cuda.device(dev):
         check(lib.dvq_grasp_self(hand.data_ptr(), faces.data_ptr(), vf_off.data_ptr(), vf_face.data_ptr(), V, part_of_vertex.data_ptr(),
                                  source_of_vertex.data_ptr(), n_parts, C.addressof(host_pairs), B, reach2, margin,
-                                 pen_count.data_ptr(), pen_depth.data_ptr(), gap_min.data_ptr(), pair_bits.data_ptr(), mask.data_ptr(),
-                                 status.data_ptr(), _stream(dev)), "dvq_grasp_self")
-    return pen_count, pen_depth, gap_min, pair_bits, mask, status
+                                 *map(_ptr, outs), _stream(dev)), "dvq_grasp_self")
+    return outs
 
 
 GRASP_TTT_MAX_N = 16384             # include/dvq.h: DVQ_GRASP_TTT_MAX_N (one word per object point sits in LDS)
@@ -1021,18 +1054,13 @@ def grasp_ttt(hand: Tensor, faces: Tensor, vf_off: Tensor, vf_face: Tensor, obj:
             raise RuntimeError(f"grasp_ttt: {n} must be a contiguous float32 tensor [{B}] or None")
     dev = _require_gpu(hand, obj, faces, vf_off, vf_face, targets, w_pen, w_con)
     lib = _lib.load()
-    pen = torch.empty(B, dtype=torch.float32, device=dev)
-    con = torch.empty(B, dtype=torch.float32, device=dev)
-    n_in = torch.empty(B, dtype=torch.int32, device=dev)
-    n_ct = torch.empty(B, dtype=torch.int32, device=dev)
-    grad = torch.empty(B, V, 3, dtype=torch.float32, device=dev) if want_grad else None
-    ptr = lambda t: None if t is None else t.data_ptr()
+    # penetration, contact_sum, n_interior, n_contact, grad_hand
+    outs = _outputs(B, dev, (_F,), (_F,), (_I,), (_I,), (_F, V, 3) if want_grad else None)
     with torch.cuda.device(dev):
         check(lib.dvq_grasp_ttt(hand.data_ptr(), faces.data_ptr(), vf_off.data_ptr(), vf_face.data_ptr(), V, po, ob, op, oc, B, N,
-                                float(contact_threshold), ptr(targets), ptr(w_pen), ptr(w_con), 1 if mean_contact else 0,
-                                pen.data_ptr(), con.data_ptr(), n_in.data_ptr(), n_ct.data_ptr(), ptr(grad), _stream(dev)),
-              "dvq_grasp_ttt")
-    return pen, con, n_in, n_ct, grad
+                                float(contact_threshold), _ptr(targets), _ptr(w_pen), _ptr(w_con), 1 if mean_contact else 0,
+                                *map(_ptr, outs), _stream(dev)), "dvq_grasp_ttt")
+    return outs
 
 
 GRASP_VOLUME_MAX_F = 8192         # csrc/grasp_volume.hip: GV_MAX_F
@@ -1051,20 +1079,11 @@ def grasp_volume(hand: Tensor, faces: Tensor, loop_off: Tensor, loop_vert: Tenso
     and t [3] as ``transform_clouds`` got them, or None for objects in place; ``res``: the lattice spacing.  An object index outside
     [0, O) raises RuntimeError unless an ``err`` flag tensor is supplied (then the caller checks it: bit 0; bit 1 = an index of the
     topology or a plane range out of bounds)."""
-    named = (("hand", hand), ("faces", faces), ("loop_off", loop_off), ("loop_vert", loop_vert), ("planes", planes),
-             ("plane_off", plane_off), ("obj_of_row", obj_of_row))
-    for n, x in named:
-        if not isinstance(x, Tensor):
-            raise RuntimeError(f"grasp_volume: {n} must be a tensor")
-    _f32(hand, "hand"), _f32(planes, "planes"), _i64(obj_of_row, "obj_of_row")
-    for n, x in named[1:4] + named[5:6]:
-        if x.dtype != torch.int32 or not x.is_contiguous():
-            raise RuntimeError(f"grasp_volume: {n} must be contiguous int32")
-    if hand.dim() != 3 or hand.shape[2] != 3 or not hand.is_contiguous():
-        raise RuntimeError("grasp_volume: hand must be contiguous [B,V,3]")
-    B, V = hand.shape[0], hand.shape[1]
-    if not 1 <= V <= GRASP_SCORES_MAX_V:
-        raise RuntimeError(f"grasp_volume: need 1 <= V <= {GRASP_SCORES_MAX_V} (got V={V})")
+    what = "grasp_volume"
+    _tensors(what, "hand faces loop_off loop_vert planes plane_off obj_of_row", hand, faces, loop_off, loop_vert, planes, plane_off, obj_of_row)
+    _f32(planes, "planes")
+    _int32_tables(what, "faces loop_off loop_vert plane_off", faces, loop_off, loop_vert, plane_off)
+    B, V = _hand(what, hand)
     if faces.dim() != 2 or faces.shape[1] != 3 or faces.shape[0] > GRASP_VOLUME_MAX_F:
         raise RuntimeError(f"grasp_volume: faces must be [F,3] with F <= {GRASP_VOLUME_MAX_F} (got {tuple(faces.shape)})")
     if loop_off.dim() != 1 or not 1 <= loop_off.numel() <= GRASP_VOLUME_MAX_LOOPS + 1 or loop_vert.dim() != 1:
@@ -1073,38 +1092,20 @@ def grasp_volume(hand: Tensor, faces: Tensor, loop_off: Tensor, loop_vert: Tenso
         raise RuntimeError("grasp_volume: planes must be contiguous [P,4]")
     if plane_off.dim() != 1 or plane_off.numel() < 1:
         raise RuntimeError("grasp_volume: plane_off must be [O+1]")
-    if obj_of_row.dim() != 1 or obj_of_row.shape[0] != B or not obj_of_row.is_contiguous():
-        raise RuntimeError("grasp_volume: `obj_of_row` must be a contiguous int64 [B] tensor")
-    if R is None and t is not None:
-        raise RuntimeError("grasp_volume: t without R")
-    if R is not None and (not isinstance(R, Tensor) or _f32(R, "R").dim() != 3 or tuple(R.shape) != (B, 3, 3) or not R.is_contiguous()):
-        raise RuntimeError("grasp_volume: expected contiguous R [B,3,3]")
-    if t is not None and (not isinstance(t, Tensor) or _f32(t, "t").numel() != 3 or not t.is_contiguous()):
-        raise RuntimeError("grasp_volume: expected contiguous t [3]")
-    res = float(res)
-    if not 0.0 < res < float("inf"):
-        raise RuntimeError(f"grasp_volume: res must be finite and positive (got {res})")
+    _obj_of_row(what, obj_of_row, B)
+    _frame(what, R, t, B)
+    res = _positive(what, "res", res)
     dev = _require_gpu(hand, faces, loop_off, loop_vert, planes, plane_off, obj_of_row, R, t, err)
     lib = _lib.load()
-    count = torch.empty(B, dtype=torch.int32, device=dev)
-    depth = torch.empty(B, dtype=torch.float32, device=dev)
-    status = torch.empty(B, dtype=torch.int32, device=dev)
-    own_err = err is None
-    if own_err:
-        err = new_err_flag(dev)
-    with torch.cuda.device(dev):
+    outs = _outputs(B, dev, (_I,), (_F,), (_I,))                                       # count, depth, status
+    message = lambda bad: (f"grasp_volume: object index out of bounds for {plane_off.numel() - 1} objects" if bad & 1 else
+                           "grasp_volume: an index of the topology or a plane range is out of bounds")
+    with _err_flag(err, dev, message) as flag, torch.cuda.device(dev):
         check(lib.dvq_grasp_volume(hand.data_ptr(), V, faces.data_ptr(), faces.shape[0], loop_off.data_ptr(), loop_vert.data_ptr(),
                                    loop_off.numel() - 1, loop_vert.numel(), planes.data_ptr(), planes.shape[0], plane_off.data_ptr(),
-                                   plane_off.numel() - 1, obj_of_row.data_ptr(), R.data_ptr() if R is not None else None,
-                                   t.data_ptr() if t is not None else None, B, res, count.data_ptr(), depth.data_ptr(),
-                                   status.data_ptr(), err.data_ptr(), _stream(dev)), "dvq_grasp_volume")
-    if own_err:
-        bad = int(err.item())
-        if bad & 1:
-            raise RuntimeError(f"grasp_volume: object index out of bounds for {plane_off.numel() - 1} objects")
-        if bad:
-            raise RuntimeError("grasp_volume: an index of the topology or a plane range is out of bounds")
-    return count, depth, status
+                                   plane_off.numel() - 1, obj_of_row.data_ptr(), _ptr(R), _ptr(t), B, res, *map(_ptr, outs), flag.data_ptr(),
+                                   _stream(dev)), "dvq_grasp_volume")
+    return outs
 
 
 GRASP_MESH_MAX_FACES = 262144      # include/dvq.h: DVQ_GRASP_MESH_MAX_FACES, per object
@@ -1121,63 +1122,31 @@ def grasp_mesh(hand: Tensor, mesh_verts: Tensor, vert_off: Tensor, mesh_faces: T
     got them, or None for objects in place.  With ``want_verts`` every inside vertex's squared distance and nearest face as f32 /
     int32 [B,V] (+inf / -1 outside; None otherwise).  An object index outside [0, O) raises RuntimeError unless an ``err`` flag tensor
     is supplied (then the caller checks it: bit 0; bit 1 = a face index or an object's range out of bounds)."""
-    named = (("hand", hand), ("mesh_verts", mesh_verts), ("vert_off", vert_off), ("mesh_faces", mesh_faces), ("face_off", face_off),
-             ("obj_of_row", obj_of_row))
-    for n, x in named:
-        if not isinstance(x, Tensor):
-            raise RuntimeError(f"grasp_mesh: {n} must be a tensor")
-    _f32(hand, "hand"), _f32(mesh_verts, "mesh_verts"), _i64(obj_of_row, "obj_of_row")
-    for n, x in (named[2], named[3], named[4]):
-        if x.dtype != torch.int32 or not x.is_contiguous():
-            raise RuntimeError(f"grasp_mesh: {n} must be contiguous int32")
-    if hand.dim() != 3 or hand.shape[2] != 3 or not hand.is_contiguous():
-        raise RuntimeError("grasp_mesh: hand must be contiguous [B,V,3]")
-    B, V = hand.shape[0], hand.shape[1]
-    if not 1 <= V <= GRASP_SCORES_MAX_V:
-        raise RuntimeError(f"grasp_mesh: need 1 <= V <= {GRASP_SCORES_MAX_V} (got V={V})")
+    what = "grasp_mesh"
+    _tensors(what, "hand mesh_verts vert_off mesh_faces face_off obj_of_row", hand, mesh_verts, vert_off, mesh_faces, face_off, obj_of_row)
+    _f32(mesh_verts, "mesh_verts")
+    _int32_tables(what, "vert_off mesh_faces face_off", vert_off, mesh_faces, face_off)
+    B, V = _hand(what, hand)
     if mesh_verts.dim() != 2 or mesh_verts.shape[1] != 3 or not mesh_verts.is_contiguous() or mesh_verts.shape[0] >= 2 ** 31:
         raise RuntimeError("grasp_mesh: mesh_verts must be contiguous [n,3]")
     if mesh_faces.dim() != 2 or mesh_faces.shape[1] != 3 or mesh_faces.shape[0] >= 2 ** 31:
         raise RuntimeError("grasp_mesh: mesh_faces must be contiguous [m,3]")
     if vert_off.dim() != 1 or vert_off.numel() < 1 or face_off.dim() != 1 or face_off.numel() != vert_off.numel():
         raise RuntimeError("grasp_mesh: vert_off and face_off must both be [O+1]")
-    if obj_of_row.dim() != 1 or obj_of_row.shape[0] != B or not obj_of_row.is_contiguous():
-        raise RuntimeError("grasp_mesh: `obj_of_row` must be a contiguous int64 [B] tensor")
-    if R is None and t is not None:
-        raise RuntimeError("grasp_mesh: t without R")
-    if R is not None and (not isinstance(R, Tensor) or _f32(R, "R").dim() != 3 or tuple(R.shape) != (B, 3, 3) or not R.is_contiguous()):
-        raise RuntimeError("grasp_mesh: expected contiguous R [B,3,3]")
-    if t is not None and (not isinstance(t, Tensor) or _f32(t, "t").numel() != 3 or not t.is_contiguous()):
-        raise RuntimeError("grasp_mesh: expected contiguous t [3]")
+    _obj_of_row(what, obj_of_row, B)
+    _frame(what, R, t, B)
     dev = _require_gpu(hand, mesh_verts, vert_off, mesh_faces, face_off, obj_of_row, R, t, err)
     lib = _lib.load()
-    W = (V + 31) // 32
-    n_inside = torch.empty(B, dtype=torch.int32, device=dev)
-    depth = torch.empty(B, dtype=torch.float32, device=dev)
-    deep_vertex = torch.empty(B, dtype=torch.int32, device=dev)
-    deep_face = torch.empty(B, dtype=torch.int32, device=dev)
-    mask = torch.empty(B, W, dtype=torch.int32, device=dev)
-    status = torch.empty(B, dtype=torch.int32, device=dev)
-    vert_d2 = torch.empty(B, V, dtype=torch.float32, device=dev) if want_verts else None
-    vert_face = torch.empty(B, V, dtype=torch.int32, device=dev) if want_verts else None
-    own_err = err is None
-    if own_err:
-        err = new_err_flag(dev)
-    with torch.cuda.device(dev):
+    # n_inside, depth, deep_vertex, deep_face, mask, status, vert_d2, vert_face
+    outs = _outputs(B, dev, (_I,), (_F,), (_I,), (_I,), (_I, (V + 31) // 32), (_I,), *(((_F, V), (_I, V)) if want_verts else (None, None)))
+    message = lambda bad: (f"grasp_mesh: object index out of bounds for {vert_off.numel() - 1} objects" if bad & 1 else
+                           "grasp_mesh: a face index or an object's vertex / face range is out of bounds")
+    with _err_flag(err, dev, message) as flag, torch.cuda.device(dev):
         check(lib.dvq_grasp_mesh(hand.data_ptr(), V, mesh_verts.data_ptr(), mesh_verts.shape[0], vert_off.data_ptr(),
                                  mesh_faces.data_ptr(), mesh_faces.shape[0], face_off.data_ptr(), vert_off.numel() - 1,
-                                 obj_of_row.data_ptr(), R.data_ptr() if R is not None else None,
-                                 t.data_ptr() if t is not None else None, B, n_inside.data_ptr(), depth.data_ptr(),
-                                 deep_vertex.data_ptr(), deep_face.data_ptr(), mask.data_ptr(), status.data_ptr(),
-                                 vert_d2.data_ptr() if want_verts else None, vert_face.data_ptr() if want_verts else None,
-                                 err.data_ptr(), _stream(dev)), "dvq_grasp_mesh")
-    if own_err:
-        bad = int(err.item())
-        if bad & 1:
-            raise RuntimeError(f"grasp_mesh: object index out of bounds for {vert_off.numel() - 1} objects")
-        if bad:
-            raise RuntimeError("grasp_mesh: a face index or an object's vertex / face range is out of bounds")
-    return n_inside, depth, deep_vertex, deep_face, mask, status, vert_d2, vert_face
+                                 obj_of_row.data_ptr(), _ptr(R), _ptr(t), B, *map(_ptr, outs), flag.data_ptr(), _stream(dev)),
+              "dvq_grasp_mesh")
+    return outs
 
 
 GRASP_REFINE_MAX_STEPS = 64        # csrc/grasp_refine.hip: GR_MAX_STEPS
@@ -1208,12 +1177,8 @@ def _refine_rows(what: str, name: str, x, shape, shown=None) -> None:
         raise RuntimeError(f"{what}: {name} must be contiguous {shown or list(shape)} (got {tuple(x.shape)})")
 
 
-def _refine_outputs(B: int, dev: torch.device, *state, iterate0: bool = False):
-    """A level's outputs: one fp32 [B,*s] per ``s`` of ``state`` (offset, quat, ...), then iter i32, penetration f32, n_interior i32,
-    n_contact i32, all [B]; with ``iterate0`` the three scores once more, for iterate 0."""
-    f32 = lambda *shape: torch.empty(B, *shape, dtype=torch.float32, device=dev)
-    i32 = lambda: torch.empty(B, dtype=torch.int32, device=dev)
-    return tuple(f32(*s) for s in state) + (i32(), f32(), i32(), i32()) + ((f32(), i32(), i32()) if iterate0 else ())
+_REFINE_SCORES = ((_F,), (_I,), (_I,))                   # penetration, n_interior, n_contact of an iterate
+_REFINE_BEST = ((_I,),) + _REFINE_SCORES                  # iter, then the scores of the iterate kept: the tail of every level's outputs
 
 
 def grasp_refine(hand: Tensor, faces: Tensor, vf_off: Tensor, vf_face: Tensor, obj: Tensor, steps: int, push: float = 1.0,
@@ -1228,7 +1193,7 @@ def grasp_refine(hand: Tensor, faces: Tensor, vf_off: Tensor, vf_face: Tensor, o
     push, pull = _refine_factors(what, push=push, pull=pull)
     dev = _require_gpu(hand, obj, faces, vf_off, vf_face)
     lib = _lib.load()
-    outs = _refine_outputs(B, dev, (3,))                                               # offset, iter, penetration, n_interior, n_contact
+    outs = _outputs(B, dev, (_F, 3), *_REFINE_BEST)                                    # offset, iter, penetration, n_interior, n_contact
     with torch.cuda.device(dev):
         check(lib.dvq_grasp_refine(hand.data_ptr(), faces.data_ptr(), vf_off.data_ptr(), vf_face.data_ptr(), V, po, ob, op, oc, B, N,
                                    float(contact_threshold), steps, push, pull, min_contact, *(t.data_ptr() for t in outs),
@@ -1251,7 +1216,7 @@ def grasp_refine_rigid(hand: Tensor, faces: Tensor, vf_off: Tensor, vf_face: Ten
     push, pull, spin = _refine_factors(what, push=push, pull=pull, spin=spin)
     dev = _require_gpu(hand, obj, faces, vf_off, vf_face, pivot)
     lib = _lib.load()
-    outs = _refine_outputs(B, dev, (3,), (4,))                                         # offset, quat, iter, penetration, n_interior, n_contact
+    outs = _outputs(B, dev, (_F, 3), (_F, 4), *_REFINE_BEST)                           # offset, quat, iter, penetration, n_interior, n_contact
     with torch.cuda.device(dev):
         check(lib.dvq_grasp_refine_rigid(hand.data_ptr(), faces.data_ptr(), vf_off.data_ptr(), vf_face.data_ptr(), V, po, ob, op, oc, B,
                                          N, pivot.data_ptr(), float(contact_threshold), steps, push, pull, spin, min_contact,
@@ -1294,7 +1259,7 @@ def grasp_refine_fingers(hand: Tensor, faces: Tensor, vf_off: Tensor, vf_face: T
     dev = _require_gpu(hand, obj, faces, vf_off, vf_face, vert_part, vert_w, pivot, knuckle)
     lib = _lib.load()
     # offset, quat, finger_quat, iter, penetration, n_interior, n_contact, then iterate 0's penetration0, n_interior0, n_contact0
-    outs = _refine_outputs(B, dev, (3,), (4,), (P, 4), iterate0=True)
+    outs = _outputs(B, dev, (_F, 3), (_F, 4), (_F, P, 4), *_REFINE_BEST, *_REFINE_SCORES)
     with torch.cuda.device(dev):
         check(lib.dvq_grasp_refine_fingers(hand.data_ptr(), faces.data_ptr(), vf_off.data_ptr(), vf_face.data_ptr(), V, vert_part.data_ptr(),
                                            vert_w.data_ptr(), P, po, ob, op, oc, B, N, pivot.data_ptr(), knuckle.data_ptr(),
@@ -1336,6 +1301,28 @@ def segment_diverse_lds_resident(pool: int, n_features: int) -> bool:
     return 32 + ((P + 3) & ~3) + P * (D | 1) <= SEGMENT_DIVERSE_LDS_FLOATS
 
 
+def _segment_feat(what: str, feat: Tensor, rows: int, max_d: int, d_note: str = "") -> Tuple[int, int]:
+    """The feature matrix of the segment kernels: [rows, D] with 1 <= D <= ``max_d``, ``stride(1) == 1`` and rows that do not
+    overlap -> (row stride, D)."""
+    shape, stride = feat.shape, feat.stride()
+    if len(shape) != 2 or shape[0] != rows:
+        raise RuntimeError(f"{what}: feat must be [O*M, D] = [{rows}, D] (got {tuple(shape)})")
+    D = int(shape[1])
+    if not 1 <= D <= max_d:
+        raise RuntimeError(f"{what}: need 1 <= D <= {max_d} (got D={D}{d_note})")
+    if D > 1 and stride[1] != 1:
+        raise RuntimeError(f"{what}: feat rows must be contiguous (stride(1) == 1, got strides {stride})")
+    ld = int(stride[0]) if rows > 1 else max(int(stride[0]), D)
+    if ld < D:
+        raise RuntimeError(f"{what}: feat rows overlap (stride(0) = {ld} < D = {D})")
+    return ld, D
+
+
+def _caller_err(what: str, err) -> None:
+    if err is not None and (not isinstance(err, Tensor) or err.dtype != torch.int32 or err.numel() != 1):
+        raise RuntimeError(f"{what}: err must be an int32 tensor of one element (ops.new_err_flag)")
+
+
 def segment_diverse(feat: Tensor, pool: Tensor, n_objects: int, n_candidates: int, keep: int, err: Optional[Tensor] = None):
     """Greedy farthest-point order inside each object's quality pool (dvq_segment_diverse; the definition is in include/dvq.h).
     feat fp32 [O*M, D] with ``stride(1) == 1`` and any ``stride(0) >= D`` (a column slice or ``vertices.view(B, -1)`` is read in
@@ -1352,32 +1339,15 @@ def segment_diverse(feat: Tensor, pool: Tensor, n_objects: int, n_candidates: in
     P = int(pool.shape[1])
     if O < 0 or not 1 <= keep <= P <= M <= SEGMENT_DIVERSE_MAX_D:
         raise RuntimeError(f"segment_diverse: need O >= 0 and 1 <= keep <= P <= M <= {SEGMENT_DIVERSE_MAX_D} (got O={O} M={M} P={P} keep={keep})")
-    if feat.dim() != 2 or feat.shape[0] != O * M:
-        raise RuntimeError(f"segment_diverse: feat must be [O*M, D] = [{O * M}, D] (got {tuple(feat.shape)})")
-    D = int(feat.shape[1])
-    if not 1 <= D <= SEGMENT_DIVERSE_MAX_D:
-        raise RuntimeError(f"segment_diverse: need 1 <= D <= {SEGMENT_DIVERSE_MAX_D} (got D={D})")
-    if D > 1 and feat.stride(1) != 1:
-        raise RuntimeError(f"segment_diverse: feat rows must be contiguous (stride(1) == 1, got strides {feat.stride()})")
-    ld = int(feat.stride(0)) if feat.shape[0] > 1 else max(int(feat.stride(0)), D)
-    if ld < D:
-        raise RuntimeError(f"segment_diverse: feat rows overlap (stride(0) = {ld} < D = {D})")
-    if err is not None and (not isinstance(err, Tensor) or err.dtype != torch.int32 or err.numel() != 1):
-        raise RuntimeError("segment_diverse: err must be an int32 tensor of one element (ops.new_err_flag)")
+    ld, D = _segment_feat("segment_diverse", feat, O * M, SEGMENT_DIVERSE_MAX_D)
+    _caller_err("segment_diverse", err)
     dev = _require_gpu(feat, pool, err)
     lib = _lib.load()
-    sel = torch.empty(O, keep, dtype=torch.int64, device=dev)
-    rank = torch.empty(O, keep, dtype=torch.int32, device=dev)
-    gap = torch.empty(O, keep, dtype=torch.float32, device=dev)
-    own_err = err is None
-    if own_err:
-        err = new_err_flag(dev)
-    with torch.cuda.device(dev):
-        check(lib.dvq_segment_diverse(feat.data_ptr(), ld, D, pool.data_ptr(), O, M, P, keep, sel.data_ptr(), rank.data_ptr(),
-                                      gap.data_ptr(), err.data_ptr(), _stream(dev)), "dvq_segment_diverse")
-    if own_err and int(err.item()) != 0:
-        raise RuntimeError(f"segment_diverse: pool entry out of bounds for {M} candidates")
-    return sel, rank, gap
+    outs = _outputs(O, dev, (_L, keep), (_I, keep), (_F, keep))                        # sel, rank, gap
+    with _err_flag(err, dev, f"segment_diverse: pool entry out of bounds for {M} candidates") as flag, torch.cuda.device(dev):
+        check(lib.dvq_segment_diverse(feat.data_ptr(), ld, D, pool.data_ptr(), O, M, P, keep, *map(_ptr, outs), flag.data_ptr(),
+                                      _stream(dev)), "dvq_segment_diverse")
+    return outs
 
 
 SEGMENT_KMEANS_MAX_M = 262144      # csrc/kmeans.hip: KM_MAX_M
@@ -1403,32 +1373,16 @@ def segment_kmeans(feat: Tensor, init: Tensor, n_objects: int, n_rows: int, iter
     if O < 0 or iters < 0 or not 1 <= k <= SEGMENT_KMEANS_MAX_K or not k <= M <= SEGMENT_KMEANS_MAX_M:
         raise RuntimeError(f"segment_kmeans: need O >= 0, iters >= 0, 1 <= k <= {SEGMENT_KMEANS_MAX_K} and k <= M <= {SEGMENT_KMEANS_MAX_M} "
                            f"(got O={O} M={M} k={k} iters={iters})")
-    if feat.dim() != 2 or feat.shape[0] != O * M:
-        raise RuntimeError(f"segment_kmeans: feat must be [O*M, D] = [{O * M}, D] (got {tuple(feat.shape)})")
-    D = int(feat.shape[1])
-    if not 1 <= D <= SEGMENT_KMEANS_MAX_D:
-        raise RuntimeError(f"segment_kmeans: need 1 <= D <= {SEGMENT_KMEANS_MAX_D} (got D={D}; vertex space is out of scope)")
-    if D > 1 and feat.stride(1) != 1:
-        raise RuntimeError(f"segment_kmeans: feat rows must be contiguous (stride(1) == 1, got strides {feat.stride()})")
-    ld = int(feat.stride(0)) if feat.shape[0] > 1 else max(int(feat.stride(0)), D)
-    if ld < D:
-        raise RuntimeError(f"segment_kmeans: feat rows overlap (stride(0) = {ld} < D = {D})")
-    if err is not None and (not isinstance(err, Tensor) or err.dtype != torch.int32 or err.numel() != 1):
-        raise RuntimeError("segment_kmeans: err must be an int32 tensor of one element (ops.new_err_flag)")
+    ld, D = _segment_feat("segment_kmeans", feat, O * M, SEGMENT_KMEANS_MAX_D, "; vertex space is out of scope")
+    _caller_err("segment_kmeans", err)
     dev = _require_gpu(feat, init, err)
     lib = _lib.load()
-    centres = torch.empty(O, k, D, dtype=torch.float32, device=dev)
-    counts = torch.empty(O, k, dtype=torch.int32, device=dev)
-    assign = torch.empty(O * M, dtype=torch.int32, device=dev)
-    dist = torch.empty(O * M, dtype=torch.float32, device=dev)
-    used = torch.empty(O, dtype=torch.int32, device=dev)
-    own_err = err is None
-    if own_err:
-        err = new_err_flag(dev)
-    with torch.cuda.device(dev):
+    centres, counts = _outputs(O, dev, (_F, k, D), (_I, k))
+    assign, dist = _outputs(O * M, dev, (_I,), (_F,))
+    used, = _outputs(O, dev, (_I,))
+    message = f"segment_kmeans: init entry out of bounds for {M} rows, repeated, or the position of a row that is not finite"
+    with _err_flag(err, dev, message) as flag, torch.cuda.device(dev):
         check(lib.dvq_segment_kmeans(feat.data_ptr(), ld, D, init.data_ptr(), O, M, k, iters, centres.data_ptr(), counts.data_ptr(),
-                                     assign.data_ptr(), dist.data_ptr(), used.data_ptr(), err.data_ptr(), _stream(dev)),
+                                     assign.data_ptr(), dist.data_ptr(), used.data_ptr(), flag.data_ptr(), _stream(dev)),
               "dvq_segment_kmeans")
-    if own_err and int(err.item()) != 0:
-        raise RuntimeError(f"segment_kmeans: init entry out of bounds for {M} rows, repeated, or the position of a row that is not finite")
     return centres, counts, assign, dist, used
