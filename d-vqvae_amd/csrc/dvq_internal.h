@@ -139,7 +139,8 @@ struct GemmSrc {
     long lda, ldw;
     int K;
     int wp_kind;          // DVQ_PLANES_BF16X3: Wp = three bf16 planes; DVQ_PLANES_F16X2: two fp16 planes of w * 2^t[row] (+ GemmParams::wscale)
-    const uint16_t* Wp;   // optional: W pre-split into planes [planes][N][ldw] (plane stride wp_plane elements)
+    const uint16_t* Wp;   // optional: W pre-split into planes [planes][N][ldw] (plane stride wp_plane elements); DVQ_PLANES_F16X2: a whole
+                          // [N][K] block in K-tile order (include/dvq.h, dvq_split_f16x2), ldw == K
     long wp_plane;
     // optional (fp16-plane kernels only): output row m reads activation row arow[m] instead of row m -- rows that are a function of
     // a class label only are computed once per class and read through the label (pixelcnn.hip)

@@ -22,8 +22,10 @@
 // of row r stored at c ^ ((4 - (r >> 2)) & 3)
 // (conflict-free ds_read_b128 in the 16-row fragment shape: the four lane groups of a read hit sixteen different 16-byte bank
 // groups).  Activations go global -> registers -> split -> LDS (once per element), weight planes by LDS-DMA with the swizzle on
-// the source address.  Weights are MFMA operand A: a lane owns ONE output row m and four consecutive columns per block, so
-// every store is 16 bytes and a wave-instruction covers 64-byte row segments.
+// the source address; the weight image is in K-tile order (the packer at the end of the file: element (n, k) of an [N][K] block at
+// (k / 32) N 32 + n 32 + k % 32), so the sixteen 64-byte rows of a DMA piece are eight whole 128-byte lines, where the natural order
+// touched sixteen lines and used half of each (profiles/r10_v3_ab_gemm_wimage.txt).  Weights are MFMA operand A: a lane owns ONE
+// output row m and four consecutive columns per block, so every store is 16 bytes and a wave-instruction covers 64-byte row segments.
 // The accumulation order of an output element -- k-tiles of 32 in source order; per tile hi: (a1 w1), lo: (a1 w2) then
 // (a2 w1) -- is the same in the skinny kernel below: results do not depend on the batch tiling (batched == loop, bitwise).
 #include "dvq_internal.h"
@@ -392,30 +394,33 @@ template <int NJ>
 struct PpCursorW {
     int s, tiles;
     lds_char* dma_dst[NJ];
-    const uint16_t* w_ptr[NJ];
+    // The weight image is in K-tile order (f16x2_split_kernel): a K-tile of a plane is N rows of 64 B back to back, so a DMA piece
+    // -- sixteen rows -- reads 1 KiB of whole cache lines, and the next K-tile of every row lies N * 64 B further.  The address of
+    // a piece is one wave-uniform pointer (the wave's plane of the source at the current K-tile: scalar registers, stepped by
+    // scalar adds) plus a byte offset per lane and piece that the launch never changes.
+    const uint16_t* w_tile;
+    unsigned w_off[NJ];
     const uint16_t* n_wp;                                   // source s + 1
-    long n_plane, n_ldw;
+    long n_plane;
     int n_k;
     __device__ __forceinline__ void fetch(const GemmParams& p) {
         const int i1 = min(s + 1, p.nsrc - 1);
         n_wp = p.src[i1].Wp;
         n_plane = p.src[i1].wp_plane;
-        n_ldw = p.src[i1].ldw;
         n_k = p.src[i1].K;
     }
     // The wave's NJ pieces of 16 rows x 64 B (8 NJ pieces: two planes x 64 NJ rows) are piece ids wave NJ .. wave NJ + NJ - 1: plane
-    // wave >> 2, row blocks (wave & 3) NJ + i.  The swizzle of a row depends on (row >> 2) & 3 = (lane >> 4) & 3 alone.
-    __device__ __forceinline__ void place(const GemmParams& p, const uint16_t* wp, long plane, long ldw, int n0, int wave, int lane) {
-        const uint16_t* base = wp + (wave >> 2) * plane + 8 * ((lane & 3) ^ swz16(lane >> 2));
-        const int nr = n0 + (wave & 3) * (16 * NJ) + (lane >> 2);
-#pragma unroll
-        for (int i = 0; i < NJ; ++i) w_ptr[i] = base + (long)min(nr + 16 * i, p.N - 1) * ldw;
-    }
+    // wave >> 2, row blocks (wave & 3) NJ + i.  The swizzle of a row depends on (row >> 2) & 3 = (lane >> 4) & 3 alone.  Rows past
+    // a ragged N are clamped to the last one (they feed outputs the epilogue masks).
     __device__ __forceinline__ void open(const GemmParams& p, int n0, int wave, int lane) {
         s = 0;
         const GemmSrc& src = p.src[0];
         tiles = (int)((unsigned)src.K / BK);
-        place(p, src.Wp, src.wp_plane, src.ldw, n0, wave, lane);
+        w_tile = src.Wp + (wave >> 2) * src.wp_plane;
+        const int nr = n0 + (wave & 3) * (16 * NJ) + (lane >> 2);
+        const int chunk = 8 * ((lane & 3) ^ swz16(lane >> 2));
+#pragma unroll
+        for (int i = 0; i < NJ; ++i) w_off[i] = 2u * (unsigned)(min(nr + 16 * i, p.N - 1) * BK + chunk);
         fetch(p);
     }
     // LDS address of the wave's piece i in stage 0: wave-uniform, formed once (the asm keeps it ONE scalar register that the
@@ -429,18 +434,20 @@ struct PpCursorW {
             asm volatile("" : "+s"(dma_dst[i]));
         }
     }
-    __device__ __forceinline__ void issue(int stage_off) const {
+    // (the asm keeps the offset a 32-bit value where it is used: widened once in front of the loop, the address would be formed per
+    // lane and piece in every K-tile, where the instruction takes a scalar base and a 32-bit lane offset as they are)
+    __device__ __forceinline__ void issue(int stage_off) {
+#pragma unroll
+        for (int i = 0; i < NJ; ++i) asm volatile("" : "+v"(w_off[i]));
 #pragma unroll
         for (int i = 0; i < NJ; ++i)
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)w_ptr[i],
+            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(reinterpret_cast<const char*>(w_tile) + w_off[i]),
                                              (__attribute__((address_space(3))) void*)(dma_dst[i] + stage_off), 16, 0, 0);
     }
-    __device__ __forceinline__ bool advance(const GemmParams& p, int n0, int wave, int lane) {
-#pragma unroll
-        for (int i = 0; i < NJ; ++i) w_ptr[i] += BK;
+    __device__ __forceinline__ bool advance(const GemmParams& p, int wave) {
+        w_tile += (long)p.N * BK;
         if (__builtin_expect(--tiles != 0, 1)) return false;
-        asm volatile("" : "+v"(lane));                      // the rows and the swizzle are formed HERE, not kept in registers all loop long
-        place(p, n_wp, n_plane, n_ldw, n0, wave, lane);
+        w_tile = n_wp + (wave >> 2) * n_plane;
         tiles = (int)((unsigned)n_k / BK);
         ++s;
         return true;
@@ -485,7 +492,7 @@ __global__ __launch_bounds__(512, 1) void gemm_f16x2_pp_kernel(const GemmParams 
         if (ca.advance(p, m0, tid)) refetch |= 2;
     };
     auto step_w = [&]() {
-        if (cw.advance(p, n0, wave, lane)) refetch |= 1;
+        if (cw.advance(p, wave)) refetch |= 1;
     };
     auto store_a = [&](lds_char* dst, const f32x4& qlo, const f32x4& qhi) {   // dst: the stage + a_dst
         h8 p1, p2;
@@ -681,7 +688,8 @@ int launch_tiled(const GemmParams& p, hipStream_t stream) {
 // of M; for the gate the block's rows are R = 8 tanh columns followed by their 8 sigmoid partners, exchanged by a lane shuffle in
 // the epilogue.  No LDS, no barrier: the wave
 // streams its weight rows HBM -> registers in the MFMA fragment shape (lane = row l & 15, 16-byte chunk l >> 4 of a
-// 64-byte k-step), its activation rows in whole 128-byte lines, PF k-steps ahead through a ring of register sets (no branch
+// 64-byte k-step: consecutive rows of the K-tile-ordered image, whole lines), its activation rows in whole 128-byte lines, PF
+// k-steps ahead through a ring of register sets (no branch
 // around a load: steps past the end re-load the last tile), splits the activations in registers and runs the tiled kernel's
 // MFMA sequence per output -- hi: (a1 w1), lo: (a1 w2) then (a2 w1), k-steps in source order -- so the result is bit-identical
 // to the batched path (an output's value does not depend on its position in the 16 x 16 block:
@@ -706,7 +714,7 @@ struct SkinnyCursor16 {
 #pragma unroll
         for (int b = 0; b < NB; ++b)
 #pragma unroll
-            for (int pl = 0; pl < 2; ++pl) w_ptr[b][pl] = src.Wp + pl * src.wp_plane + (long)n[b] * src.ldw + 8 * lc;
+            for (int pl = 0; pl < 2; ++pl) w_ptr[b][pl] = src.Wp + pl * src.wp_plane + (long)n[b] * BK + 8 * lc;   // K-tile order
     }
     __device__ __forceinline__ void load(SkinnySlot<NB>& t) const {
 #pragma unroll
@@ -724,7 +732,7 @@ struct SkinnyCursor16 {
         if (k_left > 0) {
             a_ptr += BK;
 #pragma unroll
-            for (int b = 0; b < NB; ++b) { w_ptr[b][0] += BK; w_ptr[b][1] += BK; }
+            for (int b = 0; b < NB; ++b) { w_ptr[b][0] += (long)p.N * BK; w_ptr[b][1] += (long)p.N * BK; }   // the rows' next K-tile
         } else open(p, s + 1, m, n, lc);
     }
 };
@@ -950,8 +958,12 @@ __global__ void f16x2_split_kernel(const float* __restrict__ w, long total, int 
     const _Float16 h1 = (_Float16)ws;
     const float r = ws - (float)h1;
     const _Float16 h2v = (_Float16)(r * 2048.0f);
-    planes[i] = __builtin_bit_cast(uint16_t, h1);
-    planes[total + i] = __builtin_bit_cast(uint16_t, h2v);
+    // K-tile order inside every [N][K] block (the GEMM kernels read a K-tile's rows back to back): (n, k) -> (k / 32) N 32 + n 32 + k % 32.
+    // A K that is no multiple of 32 keeps the natural order: no f16x2 kernel takes such an image (check_gemm rejects the K).
+    const int k = (int)(i % K);
+    const long j = K % BK ? i : i - ((long)n * K + k) + ((long)(k / BK) * N + n) * BK + k % BK;
+    planes[j] = __builtin_bit_cast(uint16_t, h1);
+    planes[total + j] = __builtin_bit_cast(uint16_t, h2v);
     if (i < N) row_scale[i] = ldexpf(1.0f, -f16x2_exponent(absmax[i]));
 }
 
@@ -963,6 +975,8 @@ static int check_f16x2(const GemmParams& p, GemmEpilogue epi) {
     for (int s = 0; s < p.nsrc; ++s) {
         const GemmSrc& g = p.src[s];
         DVQ_REQUIRE(g.Wp && dvq_aligned16(g.Wp) && g.wp_plane % 8 == 0 && g.ldw % 8 == 0, "gemm_f16x2: weight planes of source %d are not 16-byte aligned", s);
+        // the image is opaque (dvq_split_f16x2: K-tile order inside the [N][K] block): it has no row stride of its own
+        DVQ_REQUIRE(g.ldw == g.K, "gemm_f16x2: the fp16 image of source %d is the whole [N=%d][K=%d] block of dvq_split_f16x2 (ldw=%ld)", s, p.N, g.K, g.ldw);
     }
     bool a_ok = true;                                       // 16-byte activation loads
     for (int s = 0; s < p.nsrc; ++s) a_ok = a_ok && dvq_aligned16(p.src[s].A) && p.src[s].lda % 4 == 0;

@@ -82,7 +82,8 @@ def gemm_kind() -> int:
 
 
 class Planes:
-    """Pre-split image of one weight tensor [..., N, K]: ``planes`` int16 [P, *w.shape] (P = 3: bf16x3, 2: f16x2), ``scale`` =
+    """Pre-split image of one weight tensor [..., N, K]: ``planes`` int16 [P, *w.shape] (P = 3: bf16x3, 2: f16x2 -- that one opaque,
+    in the kernels' K-tile order: split_f16x2), ``scale`` =
     the f16x2 row scales [N] (shared by every tensor split in the same group), ``kind`` = DVQ_PLANES_*."""
     __slots__ = ("kind", "planes", "scale")
 
@@ -93,7 +94,9 @@ class Planes:
 def split_f16x2(ws) -> list:
     """fp16 images of tensors whose products are summed into the SAME output rows (the taps of a conv; horiz_stack and
     vert_to_horiz of a gated layer): each ``w`` is [N, K] or [outer, N, K]; one power-of-two scale per row for the whole group
-    (dvq_f16x2_row_absmax + dvq_split_f16x2).  Returns one ``Planes`` per tensor, all holding the same ``scale`` tensor."""
+    (dvq_f16x2_row_absmax + dvq_split_f16x2).  Returns one ``Planes`` per tensor, all holding the same ``scale`` tensor.
+    ``planes`` has the shape ``(2,) + w.shape`` but is an opaque image: inside every [N, K] block the elements stand in K-tile
+    order, element (n, k) at flat index (k // 32) * N * 32 + n * 32 + k % 32 (include/dvq.h); only the GEMM kernels read it."""
     lib = _lib.load()
     ws = [w.contiguous() for w in ws]
     N = ws[0].shape[-2]

@@ -74,7 +74,8 @@ typedef struct {
     int64_t ldx, ldw;
     int32_t K;
     int32_t wp_kind;    /* DVQ_PLANES_* of `wp` */
-    const uint16_t* wp; /* optional: w pre-split into planes [3 or 2][N][ldw] */
+    const uint16_t* wp; /* optional: w pre-split into planes [3 or 2][N][ldw]; DVQ_PLANES_F16X2: the OPAQUE image of dvq_split_f16x2,
+                           whole [N][K] blocks only (ldw == K) */
     int64_t wp_plane;   /* elements between planes */
     const float* w_scale; /* DVQ_PLANES_F16X2: [N] row scales 2^-t[n] (dvq_split_f16x2); ONE array for all sources of a call */
 } dvq_gemm_src;
@@ -107,7 +108,13 @@ int dvq_split_bf16x3(const float* w, int64_t n, uint16_t* planes, dvq_stream_t s
  *       calls this once per tensor whose products are summed into the same outputs (all taps of a conv; horiz_stack and
  *       vert_to_horiz of a gated layer, models.py:76-81);
  *   dvq_split_f16x2: t[n] = largest power of two with row_absmax[n] * 2^t < 2^15; planes[0] = fp16(w * 2^t[n]),
- *       planes[1] = fp16((w * 2^t[n] - planes[0]) * 2^11), both [outer][N][K]; row_scale[n] = 2^-t[n]. */
+ *       planes[1] = fp16((w * 2^t[n] - planes[0]) * 2^11), both [outer][N][K]; row_scale[n] = 2^-t[n].
+ *       The image is OPAQUE and made by this call only: a plane keeps the size and the [outer] blocks of w (block o starts at
+ *       o * N * K, the planes lie outer * N * K apart), but inside a block the elements stand in K-TILE ORDER, the order the GEMM
+ *       kernels read them in -- element (n, k) at (k / 32) * N * 32 + n * 32 + k % 32: the 32 k of a row that one K-tile
+ *       multiplies are 64 contiguous bytes, and the rows of a K-tile follow each other, so sixteen rows are eight whole 128-byte
+ *       lines.  (A K that is no multiple of 32 keeps the natural [N][K] order; no kernel takes such an image: K_s % 32 == 0.)
+ *       A GEMM source hands over a whole block: wp = planes + o * N * K, wp_plane = outer * N * K, ldw = K. */
 int dvq_f16x2_row_absmax(const float* w, int64_t outer, int N, int K, float* row_absmax, dvq_stream_t stream);
 int dvq_split_f16x2(const float* w, int64_t outer, int N, int K, const float* row_absmax, uint16_t* planes /* [2][outer][N][K] */,
                     float* row_scale /* [N] */, dvq_stream_t stream);
