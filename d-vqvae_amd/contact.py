@@ -782,6 +782,59 @@ def parts_class(out, min_fingers, need_thumb, min_verts=1, n_fingers=5):
     return _guard_class(status != 0, poor)
 
 
+OBJECT_CONTACT_OUTPUTS = ("touch", "inside", "dmin", "near_sum", "n_valid", "row_status")
+
+
+def object_contact(topology, hand_xyz, obj_xyz, O, K, rows=None, contact_threshold=0.02 ** 2, err=None):
+    """Where on the object its grasps land, from ONE fused kernel (ops.segment_contact; the definition is in include/dvq.h under
+    dvq_segment_contact): object o's grasps are the ``K`` rows ``rows[o*K:(o+1)*K]`` of hand_xyz [B,V,3] / obj_xyz [B,N,3] (any strides,
+    read in place; ``rows=None``: rows o*K .. o*K+K-1 of a batch of O*K), each row's cloud the object as that grasp sees it -- point p
+    is point p of the object whatever the row's rotation.  Returns ``touch`` [O,N] i32 (the grasps whose hand comes closer to point p
+    than the threshold, a SQUARED distance as in ``grasp_scores``), ``inside`` [O,N] i32 (the grasps with p inside the hand),
+    ``dmin`` [O,N] f32 (the smallest squared distance), ``near_sum`` [O,N] f32 (the summed distances of the touching grasps),
+    ``n_valid`` [O] i32 and ``row_status`` [O*K] i32 (1: a coordinate of the row is not finite; such a row takes part in nothing).
+    ``object_contact_stats`` turns them into the figures written.
+
+    A proximity figure at the scores' 2 cm threshold, which is UNTUNED; its effect on real grasps is NOT measured."""
+    out = ops.segment_contact(hand_xyz.contiguous(), topology.faces, topology.vf_off, topology.vf_face, obj_xyz, O, K, rows,
+                              contact_threshold, err)
+    return dict(zip(OBJECT_CONTACT_OUTPUTS, out))
+
+
+def object_contact_stats(touch, inside, dmin, near_sum, n_valid):
+    """Host side, float64, object by object, from ``object_contact``'s ``touch``, ``inside``, ``dmin``, ``near_sum`` [O,N] and
+    ``n_valid`` [O] (arrays or tensors) -> one dict per object: ``grasps`` = n_valid, ``coverage`` = the share of points at least one
+    grasp touches, ``entropy`` = -sum q ln q over q = touch / sum(touch) (natural logarithm as diversity.py; None when nothing is
+    touched), ``min_dist`` = 100 sqrt(dmin) per point in cm (None where the object has no valid grasp) and ``contact_dist`` =
+    100 near_sum / touch per point in cm (None where touch == 0).  ``inside`` only has to match in shape."""
+    tc, dm, ns = _host(touch, np.int64), _host(dmin, np.float64), _host(near_sum, np.float64)
+    nv = _host(n_valid, np.int64).reshape(-1)
+    if tc.ndim != 2 or not (tc.shape == _host(inside).shape == dm.shape == ns.shape) or nv.shape[0] != tc.shape[0]:
+        raise RuntimeError("object_contact_stats: touch, inside, dmin and near_sum [O,N], one n_valid per object")
+    out = []
+    for t, d, s, n in zip(tc, dm, ns, nv):
+        if n < 0:
+            raise RuntimeError("object_contact_stats: an object without a figure (a rows entry was out of bounds)")
+        total = int(t.sum())
+        entropy = None
+        if total > 0:
+            q = t[t > 0].astype(np.float64) / float(total)
+            entropy = float(-(q * np.log(q)).sum())
+        out.append({"grasps": int(n), "coverage": float(np.count_nonzero(t >= 1)) / t.shape[0], "entropy": entropy,
+                    "min_dist": [float(np.sqrt(x)) * 100.0 for x in d] if n > 0 else [None] * t.shape[0],
+                    "contact_dist": [100.0 * float(x) / int(k) if k > 0 else None for x, k in zip(s, t)]})
+    return out
+
+
+def pseudo_cmap(d2):
+    """The reference's 0-1 contact map (utils/utils.py get_pseudo_cmap: 1 - 2 (sigmoid(2 * 100 * distance) - 0.5)) of SQUARED
+    distances in metres, e.g. ``object_contact``'s ``dmin``: float64 on the host, 1 at the hand and falling towards 0 away from it
+    (+inf gives 0).  Not evaluated in the kernel: its bits would hang on an exp."""
+    d = np.sqrt(_host(d2, np.float64)) * 100.0
+    with np.errstate(over="ignore"):
+        return 1.0 - 2.0 * (1.0 / (1.0 + np.exp(-2.0 * d)) - 0.5)
+
+
 SELF_REACH, SELF_MARGIN, SELF_SEAM = 0.01, 0.001, 2    # metres, metres, edge rings: calibrated against false alarms only (DESIGN.md 3); untuned
 
 

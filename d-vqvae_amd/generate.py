@@ -11,6 +11,8 @@ from __future__ import annotations
 
 import argparse
 import dataclasses
+import functools
+import inspect
 import json
 import math
 import os
@@ -99,6 +101,14 @@ def build_parser(dataset: str) -> argparse.ArgumentParser:
                         "paper uses 20; <= num_grasp and <= 64) over each object's [num_grasp,61] parameters, one deterministic run "
                         "from evenly spaced starting rows; 0 = off; every JSON gains \"diversity\" (clusters, entropy, mean_dist, "
                         "iters, counts) and the run writes the pooled statistic of all its grasps to diversity.json")
+    p.add_argument("--object_contact", type=int, default=0,
+                   help="1: where on the object its grasps land, of the grasps written (one kernel per call): every object's JSON gains "
+                        "\"object_contact_map\" and \"object_interior_map\" (per point of the cloud file, how many of its grasps come "
+                        "closer than --object_contact_threshold / have the point inside the hand), \"object_min_dist\" (cm, the nearest "
+                        "any hand comes) and \"object_contact\" (grasps, coverage, entropy, threshold), and the run writes "
+                        "object_contact.json; a proximity figure with an untuned threshold, effect on real grasps not measured")
+    p.add_argument("--object_contact_threshold", type=float, default=0.02,
+                   help="--object_contact: a hand closer than this many metres to an object point touches it (the scores' 2 cm; untuned)")
     p.add_argument("--stability", type=int, default=0,
                    help="1: every grasp's JSON gains \"force_residual\", \"torque_residual\", \"min_sv\" and \"stability_key\" (beside the "
                         "three scores): a frictionless unit-force force-closure proxy over the contact wrenches, without selecting by it "
@@ -221,6 +231,10 @@ def parse_args(dataset: str, argv: Optional[Sequence[str]] = None) -> argparse.N
     if not 0 <= args.diversity <= min(args.num_grasp, ops.SEGMENT_KMEANS_MAX_K):
         p.error(f"--diversity must lie between 0 and min(--num_grasp, {ops.SEGMENT_KMEANS_MAX_K}) (got {args.diversity} for "
                 f"{args.num_grasp} grasps)")
+    if args.object_contact not in (0, 1):
+        p.error(f"--object_contact is 0 or 1 (got {args.object_contact})")
+    if not 0.0 < args.object_contact_threshold < float("inf"):
+        p.error(f"--object_contact_threshold must be finite and positive (got {args.object_contact_threshold})")
     if not 0 <= args.refine_steps <= ops.GRASP_REFINE_MAX_STEPS:
         p.error(f"--refine_steps must lie between 0 and {ops.GRASP_REFINE_MAX_STEPS} (got {args.refine_steps})")
     if not (0.0 <= args.refine_push < float("inf") and 0.0 <= args.refine_pull < float("inf")):
@@ -526,7 +540,8 @@ def plan_calls(point_counts: Sequence[int], num_grasp: int, rows_per_call: int) 
 class _Options:
     """What generate_for_objects has validated, the same for every call of it: its keywords under their own names, but ``stability``
     is also on with ``select_by="stability"``, ``figures`` holds the active per-row figures with their settings -- (_Figure, dict)
-    pairs in the order of FIGURES -- and ``ttt`` the settings of contact.refine_ttt, or None."""
+    pairs in the order of FIGURES -- ``ttt`` the settings of contact.refine_ttt, or None, and ``object_contact`` the threshold in
+    metres of the object-side contact map, or None without it."""
     num_grasp: int
     rotate: bool
     seed: int
@@ -551,6 +566,7 @@ class _Options:
     torque_length: float
     figures: tuple
     ttt: Optional[Dict[str, object]]
+    object_contact: Optional[float] = None
 
 
 @dataclasses.dataclass
@@ -594,8 +610,8 @@ def _generate_call(net: GenNet, opt: _Options, objs: Sequence[torch.Tensor], obj
     5. every active figure's ONE launch over all rows (_Figure.launch, in the order of FIGURES);
     6. with ``candidates``: _select_call.  Otherwise the scores where a push-out or ``stability`` asks for them (contact.grasp_stability
        in the place of contact.grasp_scores; neither where the articulated push-out's guard has scored the rows), the k-means of
-       ``diversity`` (_diversity_launch), the call's ONE device-to-host copy (_host_groups), the JSON lists of the whole call and the
-       per-object split;
+       ``diversity`` (_diversity_launch), the object-side contact map of ``object_contact`` over all rows (_object_contact_launch),
+       the call's ONE device-to-host copy (_host_groups), the JSON lists of the whole call and the per-object split;
     7. _ttt_attach and _beam_attach."""
     dev = next(net.parameters()).device
     rotate, seed = opt.rotate, opt.seed
@@ -659,13 +675,15 @@ def _generate_call(net: GenNet, opt: _Options, objs: Sequence[torch.Tensor], obj
     if opt.candidates:
         return _beam_attach(_ttt_attach(_select_call(opt, call), tuned, G), baux, beam)
     div = _diversity_launch(params, O, G, opt.diversity) if opt.diversity else []
+    omap = _object_contact_launch(call, O, G, None, opt.object_contact) if opt.object_contact else {}
     scores, s_names = {}, []
     if refined is not None or opt.stability:                                       # the scores of the hands written
         scores = _call_scores(opt, call)
         s_names = ["penetration", "n_interior", "n_contact"] + (["sums", "key"] if opt.stability else [])
     r_names = [k for k in REFINE_PIECES if k in refined] if refined is not None else []
     host = _host_groups({"params": [params], "refine": [refined[k] for k in r_names], "scores": [scores[k] for k in s_names],
-                         **{fig.key: [d[k] for k in fig.pieces] for fig, _, d in call.figs}, "diversity": div, "err": [err]})
+                         **{fig.key: [d[k] for k in fig.pieces] for fig, _, d in call.figs}, "diversity": div,
+                         "object_contact": [omap[k] for k in OBJECT_CONTACT_PIECES] if omap else [], "err": [err]})
     if int(host["err"][0][0]) != 0:
         raise RuntimeError("generate_for_objects: object index out of range in transform_clouds")
     # what every row shows beside its parameters, on the device and as JSON lists, in the order of the fields: the push-out's pieces,
@@ -680,6 +698,7 @@ def _generate_call(net: GenNet, opt: _Options, objs: Sequence[torch.Tensor], obj
     n_vol = sum(fig is _Volume for fig, _ in opt.figures)
     shown = shown[:n_vol] + ([None] if opt.diversity else []) + shown[n_vol:]    # here the diversity stands after the volume, before the rest
     div_dicts = _diversity_dicts(opt.diversity, host["diversity"]) if opt.diversity else None
+    omap_json = _object_contact_json(opt.object_contact, host["object_contact"]) if opt.object_contact else None
     topo = _hand_topology(net, final.vertices.shape[1], dev) if opt.proxies else None
     # the JSON fields of the whole call as Python lists in ONE pass each (a .tolist() per object costs more than the device work at
     # one grasp per object), then the per-object split
@@ -710,6 +729,9 @@ def _generate_call(net: GenNet, opt: _Options, objs: Sequence[torch.Tensor], obj
             fig, s, d, fig_h, lists = entry
             extra[fig.key] = {k: d[k][lo:hi] for k in fig.pieces[:fig.shown]}
             extra_json.update(fig.slice(s, lists, fig_h, lo, hi, call, o))
+        if opt.object_contact:
+            extra["object_contact"] = _object_contact_slice(omap, o, G)
+            extra_json.update(omap_json[o])
         outs.append({**extra, "params": p_dev[o], "vertices": v_dev[o],
                      "json": {"recon_params": [[p] for p in p_list[lo:hi]],           # [[61 floats]] per grasp, as the reference
                               "R_list": Rt_list[lo:hi], "trans_list": [trans] * G, "r_list": r_list[lo:hi], **extra_json}})
@@ -1051,6 +1073,41 @@ def _diversity_dicts(clusters: int, host: Sequence[np.ndarray]) -> List[Dict[str
             for d in dv.segment_statistics(clusters, counts, dist, used)]
 
 
+OBJECT_CONTACT_PIECES = ("touch", "inside", "dmin", "n_valid", "err")   # of _object_contact_launch's dict: what rides to the host, in this order
+
+
+def _object_contact_launch(call: _Call, O: int, K: int, rows: Optional[torch.Tensor], threshold: float) -> Dict[str, torch.Tensor]:
+    """``--object_contact``: one ``contact.object_contact`` over the grasps written -- all rows of the call (``rows`` = None: object o's
+    are rows o * K .. o * K + K - 1), or the kept rows by their index list against the call's hands and clouds, read in place (no
+    gather) -- at ``threshold`` metres; the kernel's tensors and its error flag."""
+    from . import contact
+    dev = call.vertices.device
+    bad = ops.new_err_flag(dev)
+    out = contact.object_contact(_hand_topology(call.net, call.vertices.shape[1], dev), call.vertices, call.cloud_xyz, O, K, rows,
+                                 float(threshold) ** 2, err=bad)
+    return {**out, "err": bad}
+
+
+def _object_contact_slice(omap: Dict[str, torch.Tensor], o: int, K: int) -> Dict[str, torch.Tensor]:
+    """Object o's part of _object_contact_launch's tensors, on the device."""
+    return {**{k: omap[k][o] for k in ("touch", "inside", "dmin", "near_sum", "n_valid")}, "row_status": omap["row_status"][o * K:(o + 1) * K]}
+
+
+def _object_contact_json(threshold: float, host: Sequence[np.ndarray]) -> List[Dict[str, object]]:
+    """The four object-side contact fields of every object of a call from the host copies of OBJECT_CONTACT_PIECES: float64 on the host,
+    per object (contact.object_contact_stats), so that an object's entry does not depend on which objects share the call.  Index p is
+    point p of the object's cloud.  A distance that is not finite becomes null."""
+    from . import contact
+    touch, inside, dmin, n_valid, bad = host
+    if int(bad[0]) != 0:
+        raise RuntimeError("generate_for_objects: object_contact: a row index is out of range")
+    stats = contact.object_contact_stats(touch, inside, dmin, np.zeros_like(dmin), n_valid)
+    return [{"object_contact_map": t.tolist(), "object_interior_map": i.tolist(),
+             "object_min_dist": [x if x is not None and math.isfinite(x) else None for x in st["min_dist"]],
+             "object_contact": {"grasps": st["grasps"], "coverage": st["coverage"], "entropy": st["entropy"], "threshold": float(threshold)}}
+            for t, i, st in zip(touch, inside, stats)]
+
+
 def _select_call(opt: _Options, call: _Call) -> List[Dict[str, object]]:
     """Best-of-M for all the objects of a call together; row o * M + c is candidate c of object o, and nothing here depends on which
     objects share the call.  The stages, in order:
@@ -1061,7 +1118,8 @@ def _select_call(opt: _Options, call: _Call) -> List[Dict[str, object]]:
        ``num_grasp`` most spread-out of them in greedy farthest-point order (ops.segment_diverse over the parameters or the posed
        vertices, read in place), whose pool positions and squared gaps ride along;
     3. ONE ``index_select`` per tensor of the kept rows: parameters, vertices, scores, the push-out's REFINE_PIECES, the figures'
-       pieces; the k-means of ``diversity`` over the kept parameters (_diversity_launch);
+       pieces; the k-means of ``diversity`` over the kept parameters (_diversity_launch); the object-side contact map of
+       ``object_contact`` over the kept rows, by their index list against the call's hands and clouds (_object_contact_launch);
     4. the call's ONE device-to-host copy (_host_groups), the JSON lists of the kept rows and the per-object split."""
     from . import contact
     net, params, vertices, logp, refined = call.net, call.params, call.vertices, call.logp, call.refined
@@ -1091,9 +1149,11 @@ def _select_call(opt: _Options, call: _Call) -> List[Dict[str, object]]:
     r_names = [k for k in REFINE_PIECES if k in refined] if refined is not None else []
     kept_r = [refined[k].index_select(0, rows) for k in r_names]
     div = _diversity_launch(kept_p, O, keep, opt.diversity) if opt.diversity else []
+    omap = _object_contact_launch(call, O, keep, rows, opt.object_contact) if opt.object_contact else {}
     kept_f = {fig.key: {k: d[k] if k == "err" else d[k].index_select(0, rows) for k in fig.pieces} for fig, _, d in call.figs}
     host = _host_groups({"sel": [sel], "params": [kept_p], "scores": [kept_s[k] for k in names], "refine": kept_r,
-                         **{k: list(f.values()) for k, f in kept_f.items()}, "diverse": diverse, "diversity": div, "err": [call.err]})
+                         **{k: list(f.values()) for k, f in kept_f.items()}, "diverse": diverse, "diversity": div,
+                         "object_contact": [omap[k] for k in OBJECT_CONTACT_PIECES] if omap else [], "err": [call.err]})
     if int(host["err"][0][0]) != 0:
         raise RuntimeError("generate_for_objects: object index out of range in transform_clouds")
     sel_h, p_list = host["sel"][0], host["params"][0].tolist()
@@ -1108,6 +1168,7 @@ def _select_call(opt: _Options, call: _Call) -> List[Dict[str, object]]:
             raise RuntimeError("generate_for_objects: pool entry out of range in segment_diverse")
         rank_list, gap_list = rank_h.tolist(), gap_h.tolist()
     div_dicts = _diversity_dicts(opt.diversity, host["diversity"]) if opt.diversity else None
+    omap_json = _object_contact_json(opt.object_contact, host["object_contact"]) if opt.object_contact else None
     rows_h = (sel_h + np.arange(O)[:, None] * M).reshape(-1)
     t = call.t
     Rt_list = np.concatenate([call.R[rows_h], np.broadcast_to(t.reshape(1, 3, 1), (O * keep, 3, 1))], axis=2).tolist()
@@ -1136,6 +1197,9 @@ def _select_call(opt: _Options, call: _Call) -> List[Dict[str, object]]:
             extra[fig.key] = {k: kept_d[k][lo:hi] for k in fig.pieces[:fig.shown]}
             extra[fig.scores_key] = {k: d[k][o * M:(o + 1) * M] for k in fig.pieces[:fig.shown]}    # of ALL candidates
             extra_json.update(fig.slice(s, lists, fig_h, lo, hi, call, o))
+        if opt.object_contact:
+            extra["object_contact"] = _object_contact_slice(omap, o, keep)
+            extra_json.update(omap_json[o])
         outs.append({**extra, "params": p_dev[o], "vertices": v_dev[o], "candidate": sel[o],
                      "scores": {k: v[o * M:(o + 1) * M] for k, v in scores.items()},
                      "json": {"recon_params": [[p] for p in p_list[lo:hi]], "R_list": Rt_list[lo:hi], "trans_list": [trans] * keep,
@@ -1286,6 +1350,39 @@ def generate_for_objects(net: GenNet, objs: Sequence[torch.Tensor], num_grasp: i
     better beam with the same six hand codes, or -1).  Excludes ``temperature`` / ``top_k``; the searches of a call do not depend on
     one another, so the results do not depend on ``rows_per_call``.  fp16 weight images only, no bf16 fallback inside the search;
     whether likelier grids are better grasps is not measured.  ``beam_width = 0`` is the call without the keyword."""
+    return _generate_objects(None, **locals())                                     # (first statement: the locals are the keywords)
+
+
+def generate_with_object_contact(net: GenNet, objs: Sequence[torch.Tensor], num_grasp: int, rotate: bool, seed: int,
+                                 object_indices: Sequence[int], object_contact_threshold: float = 0.02, **options) -> List[Dict[str, object]]:
+    """``generate_for_objects(net, objs, num_grasp, rotate, seed, object_indices, **options)`` with the object-side contact map:
+    where on the object its grasps land, at ``object_contact_threshold`` = T metres.  After selection, push-out and refinement every
+    call launches ONE ``contact.object_contact`` over the grasps WRITTEN -- all rows of the call, or with ``candidates`` the kept rows
+    by their index list against the call's hands and clouds (no gather) -- one segment per object.  Each dict gains
+    ``object_contact`` (touch, inside, dmin, near_sum [N], n_valid, row_status [num_grasp] on the device) and ``json`` gains
+    "object_contact_map" and "object_interior_map" (N ints: how many of the object's grasps come closer than T to point p / have it
+    inside the hand), "object_min_dist" (N floats in cm, null without a valid grasp) and "object_contact" (grasps, coverage, entropy,
+    threshold: ``contact.object_contact_stats``, float64 on the host), after every other field.  Index p is point p of the object's
+    cloud: a rotation does not permute points.  The maps ride in the call's one device-to-host copy and do not depend on
+    ``rows_per_call``; everything else is what ``generate_for_objects`` returns, bit for bit.  A proximity figure at an untuned
+    threshold; the effect on real grasps is not measured.  (A function of its own: the keywords of ``generate_for_objects`` are pinned.)"""
+    if not 0.0 < float(object_contact_threshold) < float("inf"):
+        raise RuntimeError(f"generate_with_object_contact: object_contact_threshold must be finite and positive (got {object_contact_threshold})")
+    _hand_faces(net)                                                               # no face list: raise before any work
+    call = inspect.signature(generate_for_objects).bind(net, objs, num_grasp, rotate, seed, object_indices, **options)
+    call.apply_defaults()
+    return _generate_objects(float(object_contact_threshold), **call.arguments)
+
+
+def _generate_objects(object_contact, net, objs, num_grasp, rotate, seed, object_indices, proxies, rows_per_call,
+                      temperature, top_k, log_prob, candidates, select_by, min_contact, diverse_pool, diverse_space,
+                      refine_steps, refine_push, refine_pull, diversity, stability, max_penetration, torque_length,
+                      volume, volume_res, max_volume, parts, part_threshold, part_min_verts, min_fingers, need_thumb,
+                      hand_parts, refine_spin, refine_curl, refine_max_curl, self_collision, self_reach, self_margin,
+                      self_seam, self_palm, max_self_verts, object_meshes, mesh_depth, max_mesh_depth, ttt_steps,
+                      ttt_lr, ttt_momentum, ttt_w_pen, ttt_w_con, ttt_prior, ttt_keep_best, beam_width, beam_poses) -> List[Dict[str, object]]:
+    """The body of ``generate_for_objects`` (its keywords, validated here) and of ``generate_with_object_contact``: ``object_contact``
+    is the threshold in metres of the object-side contact map, or None without it."""
     beam = None
     if beam_width:
         rows = candidates or num_grasp
@@ -1405,6 +1502,7 @@ def generate_for_objects(net: GenNet, objs: Sequence[torch.Tensor], num_grasp: i
                    refine_steps=refine_steps, refine_push=refine_push, refine_pull=refine_pull, refine_spin=float(refine_spin),
                    refine_curl=float(refine_curl), refine_max_curl=float(refine_max_curl), diversity=diversity, stability=stability,
                    max_penetration=max_penetration, torque_length=torque_length, ttt=ttt_args,
+                   object_contact=object_contact,
                    figures=tuple((fig, s) for fig, s in zip(FIGURES, (vol_args, parts_args, self_args, mesh_args)) if s is not None))
     out: List[Optional[Dict[str, object]]] = [None] * len(objs)
     for call in plan_calls([o.shape[1] for o in objs], candidates or num_grasp, rows_per_call):
@@ -1467,7 +1565,7 @@ def main(dataset: str, argv: Optional[Sequence[str]] = None) -> List[str]:
     want_self = bool(args.self_collision) or args.max_self_verts is not None
     want_mesh = bool(args.mesh_depth) or args.max_mesh_depth < float("inf")
     if (args.rows_per_call > 0 or args.candidates or args.refine_steps or args.diversity or args.stability or want_volume or want_parts
-            or want_self or want_mesh or args.ttt_steps or args.beam_width):
+            or want_self or want_mesh or args.ttt_steps or args.beam_width or args.object_contact):
         # grouped calls (best-of-M, push-out, the diversity statistic and the stability proxy always: --rows_per_call 0 is then one
         # object per call)
         rows_per_call, per_object = max(1, args.rows_per_call), (args.candidates or args.num_grasp)
@@ -1506,18 +1604,22 @@ def main(dataset: str, argv: Optional[Sequence[str]] = None) -> List[str]:
         fig_rows: Dict[str, Dict[int, object]] = {fig.key: {} for fig in active}   # every object's _Figure.rows, for the run summaries
         curl_rows: Dict[int, tuple] = {}                                           # --refine_curl: every object's (curled, reverted) counts
         kept: Dict[int, np.ndarray] = {}                                           # --diversity: every object's kept parameters, on the host
+        omap_rows: Dict[int, Dict[str, object]] = {}                               # --object_contact: every object's "object_contact" entry
         # grouped calls: one call's objects at a time, its files written before the next call starts, so the device and the host
         # hold one call's results, not the whole list's
         mine = objs[lo:hi]
         paths: Dict[int, str] = {}
+        generate_call = generate_for_objects
+        if args.object_contact:
+            generate_call = functools.partial(generate_with_object_contact, object_contact_threshold=args.object_contact_threshold)
         for call in plan_calls([o.shape[1] for _, o in mine], per_object, rows_per_call):
             torch.cuda.synchronize(device)
             t0 = time.time()
-            outs = generate_for_objects(net, [mine[p][1] for p in call], args.num_grasp, rotate, args.seed, [lo + p for p in call],
-                                        rows_per_call=rows_per_call, temperature=args.temperature, top_k=args.top_k,
-                                        log_prob=bool(args.log_prob), **selection,
-                                        **(dict(object_meshes=[meshes[p] for p in call], mesh_depth=True,
-                                                max_mesh_depth=args.max_mesh_depth) if want_mesh else {}))
+            outs = generate_call(net, [mine[p][1] for p in call], args.num_grasp, rotate, args.seed, [lo + p for p in call],
+                                 rows_per_call=rows_per_call, temperature=args.temperature, top_k=args.top_k,
+                                 log_prob=bool(args.log_prob), **selection,
+                                 **(dict(object_meshes=[meshes[p] for p in call], mesh_depth=True,
+                                         max_mesh_depth=args.max_mesh_depth) if want_mesh else {}))
             torch.cuda.synchronize(device)
             dt = time.time() - t0
             total_t += dt
@@ -1530,6 +1632,8 @@ def main(dataset: str, argv: Optional[Sequence[str]] = None) -> List[str]:
                     json.dump(out["json"], f)
                 if args.diversity:
                     kept[p] = np.asarray(out["json"]["recon_params"], dtype=np.float32).reshape(args.num_grasp, -1)
+                if args.object_contact:
+                    omap_rows[p] = out["json"]["object_contact"]
                 if args.refine_curl:
                     curl_rows[p] = (sum(1 for g in out["json"]["refine_curl"] if any(x != 0 for a in g for x in a)),
                                     sum(out["json"]["refine_reverted"]))
@@ -1546,6 +1650,18 @@ def main(dataset: str, argv: Optional[Sequence[str]] = None) -> List[str]:
                            {**{k: stat[k] for k in ("clusters", "entropy", "mean_dist", "iters", "counts")}, "grasps": int(pooled.shape[0])})
             print(f"rank {rank}: diversity of {pooled.shape[0]} grasps in {stat['clusters']} clusters: entropy {stat['entropy']:.4f}, "
                   f"mean distance {stat['mean_dist']:.4f} ({stat['iters']} iterations)")
+        if args.object_contact:
+            # the run's figures of the object-side contact maps over this rank's objects in object order: exactly rounded sums of
+            # per-object figures, so that no grouping can change a bit
+            per_obj = [omap_rows[p] for p in sorted(omap_rows)]
+            entropies = [d["entropy"] for d in per_obj if d["entropy"] is not None]
+            stat = {"threshold": args.object_contact_threshold, "objects": len(per_obj), "grasps": sum(d["grasps"] for d in per_obj),
+                    "mean_coverage": _mean([d["coverage"] for d in per_obj]), "mean_entropy": _mean(entropies),
+                    "share_untouched": _share([d["entropy"] is None for d in per_obj])}
+            _write_summary(args.out_dir, "object_contact", rank, world, stat)
+            print(f"rank {rank}: object-side contact of {stat['grasps']} grasps on {stat['objects']} objects at "
+                  f"{args.object_contact_threshold} m: mean coverage {stat['mean_coverage']}, mean entropy {stat['mean_entropy']}, "
+                  f"share of objects no grasp touches {stat['share_untouched']}")
         if args.refine_curl:
             # the run's metadata of the articulated push-out: the rig's joints (the order of "refine_curl") and two integer counts
             stat = {"joints": _finger_rig(net).joints, "refine_curl": args.refine_curl, "refine_max_curl": args.refine_max_curl,

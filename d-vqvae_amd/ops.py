@@ -1386,3 +1386,40 @@ def segment_kmeans(feat: Tensor, init: Tensor, n_objects: int, n_rows: int, iter
                                      assign.data_ptr(), dist.data_ptr(), used.data_ptr(), flag.data_ptr(), _stream(dev)),
               "dvq_segment_kmeans")
     return centres, counts, assign, dist, used
+
+
+SEGMENT_CONTACT_TILE = 1024        # csrc/segment_contact.hip: SC_TILE (the object points one workgroup holds still)
+SEGMENT_CONTACT_MAX_K = 262144     # csrc/segment_contact.hip: SC_MAX_K (rows per segment)
+
+
+def segment_contact(hand: Tensor, faces: Tensor, vf_off: Tensor, vf_face: Tensor, obj: Tensor, n_objects: int, n_rows: int,
+                    rows: Optional[Tensor] = None, contact_threshold: float = 0.02 ** 2, err: Optional[Tensor] = None):
+    """Contact from the object's side in one fused kernel (dvq_segment_contact; the definition is in include/dvq.h): per object point,
+    over the ``n_rows`` = K grasps of each of the ``n_objects`` = O segments, ``(touch [O,N] i32, inside [O,N] i32, dmin [O,N] f32,
+    near_sum [O,N] f32, n_valid [O] i32, row_status [O*K] i32)``: how many valid rows come closer than ``contact_threshold`` (a squared
+    distance), how many have the point inside the hand, the smallest squared distance (+inf without a valid row), the summed distances
+    of the touching rows in the fixed four-chain order, the valid rows, and 1 for a row with a non-finite coordinate.  hand, the
+    topology and obj [B,N,3] (any strides, read in place) as ``grasp_scores`` takes them; segment o is the rows ``rows[o*K:(o+1)*K]``
+    of them (int64 [O*K] contiguous on the device: a gather by index, nothing is copied), or with ``rows=None`` rows o*K .. o*K+K-1,
+    and then B must be O*K.  Per row and point the bits of ``grasp_scores``.  An entry of ``rows`` outside [0, B) raises RuntimeError
+    unless an ``err`` flag tensor is supplied (then the caller checks it; that segment's outputs are -1 / NaN)."""
+    po, ob, op, oc, B, V, N = _hand_cloud_args("segment_contact", hand, faces, vf_off, vf_face, obj)
+    O, K = int(n_objects), int(n_rows)
+    if O < 0 or not 1 <= K <= SEGMENT_CONTACT_MAX_K:
+        raise RuntimeError(f"segment_contact: need O >= 0 and 1 <= K <= {SEGMENT_CONTACT_MAX_K} (got O={O} K={K})")
+    if rows is None:
+        if B != O * K:
+            raise RuntimeError(f"segment_contact: without rows the batch must hold O * K = {O * K} rows (got B={B})")
+    elif not isinstance(rows, Tensor) or _i64(rows, "segment_contact: rows").shape != (O * K,) or not rows.is_contiguous():
+        raise RuntimeError(f"segment_contact: rows must be a contiguous int64 [O*K] = [{O * K}] tensor")
+    contact_threshold = _positive("segment_contact", "contact_threshold", contact_threshold)
+    _caller_err("segment_contact", err)
+    dev = _require_gpu(hand, obj, faces, vf_off, vf_face, rows, err)
+    lib = _lib.load()
+    maps = _outputs(O, dev, (_I, N), (_I, N), (_F, N), (_F, N), (_I,))                # touch, inside, dmin, near_sum, n_valid
+    status, = _outputs(O * K, dev, (_I,))
+    with _err_flag(err, dev, f"segment_contact: rows entry out of bounds for {B} rows") as flag, torch.cuda.device(dev):
+        check(lib.dvq_segment_contact(hand.data_ptr(), faces.data_ptr(), vf_off.data_ptr(), vf_face.data_ptr(), V, po, ob, op, oc, B, N,
+                                      _ptr(rows), O, K, contact_threshold, *map(_ptr, maps), status.data_ptr(), flag.data_ptr(),
+                                      _stream(dev)), "dvq_segment_contact")
+    return maps + (status,)

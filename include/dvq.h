@@ -44,7 +44,7 @@ typedef enum {
  * working, the version stays): dvq_pixelcnn_sample_ctl, dvq_grasp_scores, dvq_segment_topk, dvq_segment_diverse,
  * dvq_grasp_refine, dvq_segment_kmeans, dvq_grasp_wrench, dvq_grasp_volume, dvq_grasp_parts, dvq_grasp_refine_rigid,
  * dvq_grasp_refine_fingers, dvq_grasp_self, dvq_mano_backward_workspace_bytes, dvq_mano_backward, dvq_grasp_ttt,
- * dvq_pixelcnn_beam_workspace_bytes, dvq_pixelcnn_beam, dvq_grasp_mesh. */
+ * dvq_pixelcnn_beam_workspace_bytes, dvq_pixelcnn_beam, dvq_grasp_mesh, dvq_segment_contact. */
 int dvq_abi_version(void);
 const char* dvq_last_error(void);
 /* number of visible HIP devices, or -1; does not create a context */
@@ -904,6 +904,37 @@ int dvq_segment_diverse(const float* feat, int64_t ld, int D, const int64_t* poo
 int dvq_segment_kmeans(const float* feat, int64_t ld, int D, const int64_t* init /* [O,k] */, int64_t O, int M, int k, int iters,
                        float* centres /* [O,k,D] */, int32_t* counts /* [O,k] */, int32_t* assign /* [O*M] */, float* dist /* [O*M] */,
                        int32_t* iters_used /* [O] */, int32_t* err, dvq_stream_t stream);
+/* Object-side contact map: for every point of an object's cloud, over the grasps of that object, how many hands touch it, how many
+ * have it inside, the nearest any hand comes and the summed touching distances -- the figure the reference's contact-map code is
+ * built around (utils/utils.py get_pseudo_cmap: the object points' nearest-hand distances as a map over the object), reduced over a
+ * segment of grasps on the device: no [B,N] intermediate.  ONE kernel that turns the scan of dvq_grasp_scores round: a workgroup
+ * holds 1024 object points still and walks the segment's rows.  No workspace; nothing depends on O, on which segments share a call,
+ * on B or on scheduling.
+ * Inputs: hand [B,V,3] contiguous fp32, the topology and obj with strides in floats exactly as dvq_grasp_scores takes them (a
+ * channel-first cloud is read in place); segment o is the K rows r(o,i) = rows[o * K + i], i = 0 .. K-1 (device int64 [O*K]); with
+ * rows == NULL r(o,i) = o * K + i and B == O * K is required.  The hand and the cloud of row r are read in place: a row may appear in
+ * several segments or several times in one.
+ *   1. Row validity: a row is valid iff all 3 V hand coordinates and all 3 N cloud coordinates of that row are finite.
+ *      row_status[o * K + i] = 0 for a valid row, 1 otherwise; n_valid[o] = the number of valid rows.  An invalid row takes part in
+ *      nothing below.
+ *   2. Per valid row and point p: normals, d_p, j_p and inside_p exactly as dvq_grasp_scores defines them (nearest vertex with the
+ *      lowest index on ties, the tangent-plane test against it): the same bits.
+ *   3. touch[o,p] = the number of valid rows with d_p < contact_threshold; inside[o,p] = the number with inside_p; dmin[o,p] = the
+ *      minimum of d_p over the valid rows, +inf with none.
+ *   4. near_sum[o,p] = the sum of sqrtf(d_p) (IEEE square root) over the valid rows with d_p < contact_threshold, as four chains:
+ *      chain g starts at +0.0f and adds over ascending segment positions i = g (mod 4); S = (c0 + c1) + (c2 + c3); every operation
+ *      rounded to fp32 on its own, nothing fused (the chain rule of dvq_segment_kmeans).  The only float sum; its order is fixed by
+ *      the segment positions.
+ *   5. Bad index: an entry of rows outside [0, B) sets bit 0 of *err (device int32, zeroed by the caller); that segment's touch,
+ *      inside, n_valid and row_status are -1, its dmin and near_sum NaN, and nothing is read through the bad index.
+ * Outputs: touch, inside int32 [O,N]; dmin, near_sum fp32 [O,N]; n_valid int32 [O]; row_status int32 [O*K].
+ * O >= 0, 1 <= K <= 262144, N >= 1, 1 <= V <= 2048, contact_threshold finite and > 0, no null pointer except rows; anything else is
+ * DVQ_EINVAL, nothing launched.  O == 0 returns DVQ_OK before any pointer is looked at. */
+int dvq_segment_contact(const float* hand /* [B,V,3] */, const int32_t* faces, const int32_t* vf_off, const int32_t* vf_face, int V,
+                        const float* obj, int64_t obj_batch_stride, int64_t obj_point_stride, int64_t obj_coord_stride,
+                        int64_t B, int N, const int64_t* rows /* device [O*K] or NULL */, int64_t O, int K, float contact_threshold,
+                        int32_t* touch /* [O,N] */, int32_t* inside /* [O,N] */, float* dmin /* [O,N] */, float* near_sum /* [O,N] */,
+                        int32_t* n_valid /* [O] */, int32_t* row_status /* [O*K] */, int32_t* err, dvq_stream_t stream);
 
 /* ------------------------------------------------------------------ all-gather of the generated MANO parameters (multi-GPU)
  * The batch of objects shards contiguously over R ranks (one process per GPU); the only exchange of the path is
