@@ -11,19 +11,19 @@ from __future__ import annotations
 
 import argparse
 import dataclasses
-import functools
 import inspect
 import json
 import math
 import os
+import re
 import time
 import types
-from typing import Dict, List, Optional, Sequence
+from typing import Callable, Dict, List, Optional, Sequence
 
 import numpy as np
 import torch
 
-from . import dist, mano as dmano, ops, synth
+from . import contact, dist, mano as dmano, ops, synth
 from .network.gen_net import GenNet
 
 CANONICAL_OFFSET = (-0.0793, 0.0208, -0.6924)       # gen_diverse_grasp_ho3d.py:221
@@ -218,104 +218,13 @@ def build_parser(dataset: str) -> argparse.ArgumentParser:
 
 
 def parse_args(dataset: str, argv: Optional[Sequence[str]] = None) -> argparse.Namespace:
-    """build_parser(dataset).parse_args(argv) plus the checks that span two flags."""
+    """build_parser(dataset).parse_args(argv) plus the checks of RULES; the dataset says whether its objects are rotated."""
     p = build_parser(dataset)
     args = p.parse_args(argv)
-    if args.candidates < 0 or 0 < args.candidates < args.num_grasp:
-        p.error(f"--candidates must be 0 or at least --num_grasp (got {args.candidates} for {args.num_grasp} grasps)")
-    if args.diverse_pool < 0 or (args.diverse_pool and not args.candidates):
-        p.error(f"--diverse_pool must be 0, or positive together with --candidates (got {args.diverse_pool} with --candidates {args.candidates})")
-    if args.diverse_pool and not args.num_grasp <= args.diverse_pool <= args.candidates:
-        p.error(f"--diverse_pool must lie between --num_grasp and --candidates (got {args.diverse_pool} for {args.num_grasp} grasps of "
-                f"{args.candidates} candidates)")
-    if not 0 <= args.diversity <= min(args.num_grasp, ops.SEGMENT_KMEANS_MAX_K):
-        p.error(f"--diversity must lie between 0 and min(--num_grasp, {ops.SEGMENT_KMEANS_MAX_K}) (got {args.diversity} for "
-                f"{args.num_grasp} grasps)")
-    if args.object_contact not in (0, 1):
-        p.error(f"--object_contact is 0 or 1 (got {args.object_contact})")
-    if not 0.0 < args.object_contact_threshold < float("inf"):
-        p.error(f"--object_contact_threshold must be finite and positive (got {args.object_contact_threshold})")
-    if not 0 <= args.refine_steps <= ops.GRASP_REFINE_MAX_STEPS:
-        p.error(f"--refine_steps must lie between 0 and {ops.GRASP_REFINE_MAX_STEPS} (got {args.refine_steps})")
-    if not (0.0 <= args.refine_push < float("inf") and 0.0 <= args.refine_pull < float("inf")):
-        p.error(f"--refine_push and --refine_pull must be finite and >= 0 (got {args.refine_push}, {args.refine_pull})")
-    if not 0.0 <= args.refine_spin < float("inf"):
-        p.error(f"--refine_spin must be finite and >= 0 (got {args.refine_spin})")
-    if args.refine_spin and not args.refine_steps:
-        p.error("--refine_spin needs --refine_steps (it turns the hand during the push-out)")
-    if not 0.0 <= args.refine_curl < float("inf"):
-        p.error(f"--refine_curl must be finite and >= 0 (got {args.refine_curl})")
-    if args.refine_curl and not args.refine_steps:
-        p.error("--refine_curl needs --refine_steps (it curls the fingers during the push-out)")
-    if not 0.0 < args.refine_max_curl <= math.pi:
-        p.error(f"--refine_max_curl must lie in (0, pi] (got {args.refine_max_curl})")
-    if not 0 <= args.ttt_steps <= TTT_MAX_STEPS:
-        p.error(f"--ttt_steps must lie between 0 and {TTT_MAX_STEPS} (got {args.ttt_steps})")
-    if not (0.0 <= args.ttt_lr < float("inf") and 0.0 <= args.ttt_momentum < 1.0):
-        p.error(f"--ttt_lr must be finite and >= 0 and --ttt_momentum in [0, 1) (got {args.ttt_lr}, {args.ttt_momentum})")
-    if not (0.0 <= args.ttt_w_pen < float("inf") and 0.0 <= args.ttt_w_con < float("inf")):
-        p.error(f"--ttt_w_pen and --ttt_w_con must be finite and >= 0 (got {args.ttt_w_pen}, {args.ttt_w_con})")
-    if args.ttt_keep_best not in (0, 1):
-        p.error(f"--ttt_keep_best is 0 or 1 (got {args.ttt_keep_best})")
-    if args.ttt_prior is not None and not args.ttt_steps:
-        p.error("--ttt_prior needs --ttt_steps (it names the contact vertices of the gradient refinement)")
-    if not 0.0 < args.torque_length < float("inf"):
-        p.error(f"--torque_length must be finite and positive (got {args.torque_length})")
-    if not args.max_penetration >= 0.0:
-        p.error(f"--max_penetration must be >= 0 (got {args.max_penetration})")
-    if not 0.0 < args.volume_res < float("inf"):
-        p.error(f"--volume_res must be finite and positive (got {args.volume_res})")
-    if not args.max_volume >= 0.0:
-        p.error(f"--max_volume must be >= 0 (got {args.max_volume})")
-    if args.max_volume < float("inf") and not args.candidates:
-        p.error("--max_volume needs --candidates (it ranks candidates; --volume 1 alone writes the figure)")
-    if not 0.0 < args.part_threshold < float("inf"):
-        p.error(f"--part_threshold must be finite and positive (got {args.part_threshold})")
-    if args.part_min_verts < 1:
-        p.error(f"--part_min_verts must be at least 1 (got {args.part_min_verts})")
-    if not 0 <= args.min_fingers <= 5:
-        p.error(f"--min_fingers must lie between 0 and 5 (got {args.min_fingers})")
-    if args.need_thumb not in (0, 1) or args.parts not in (0, 1):
-        p.error(f"--need_thumb and --parts are 0 or 1 (got {args.need_thumb}, {args.parts})")
-    if (args.min_fingers or args.need_thumb) and not args.candidates:
-        p.error("--min_fingers and --need_thumb need --candidates (they rank candidates; --parts 1 alone writes the figures)")
-    if args.self_collision not in (0, 1) or args.self_palm not in (0, 1):
-        p.error(f"--self_collision and --self_palm are 0 or 1 (got {args.self_collision}, {args.self_palm})")
-    if not 0.0 < args.self_reach < float("inf"):
-        p.error(f"--self_reach must be finite and positive (got {args.self_reach})")
-    if not 0.0 <= args.self_margin < float("inf"):
-        p.error(f"--self_margin must be finite and >= 0 (got {args.self_margin})")
-    if args.self_seam < 0:
-        p.error(f"--self_seam must be >= 0 (got {args.self_seam})")
-    if args.max_self_verts is not None and args.max_self_verts < 0:
-        p.error(f"--max_self_verts must be >= 0 (got {args.max_self_verts})")
-    if not 0 <= args.beam_width <= ops.PIXELCNN_BEAM_MAX_W or args.beam_poses < 1:
-        p.error(f"--beam_width must lie between 0 and {ops.PIXELCNN_BEAM_MAX_W} and --beam_poses be at least 1 "
-                f"(got {args.beam_width}, {args.beam_poses})")
-    if not args.beam_width and args.beam_poses != 1:
-        p.error("--beam_poses needs --beam_width (it counts the poses a beam search runs for)")
-    if args.beam_width:
-        if args.beam_poses != 1 and not DATASETS[dataset]["rotate"]:
-            p.error(f"--beam_poses must be 1 for {dataset}: its objects are not rotated, every pose would be the same search")
-        rows = args.beam_poses * args.beam_width
-        if (args.candidates or args.num_grasp) != rows:
-            p.error(f"--beam_width: {'--candidates' if args.candidates else '--num_grasp'} must equal --beam_poses * --beam_width = {rows} "
-                    f"(got {args.candidates or args.num_grasp})")
-        if args.temperature != 1.0 or args.top_k != 0:
-            p.error("--beam_width excludes --temperature and --top_k: a beam search draws nothing")
-    if args.max_self_verts is not None and not args.candidates:
-        p.error("--max_self_verts needs --candidates (it ranks candidates; --self_collision 1 alone writes the figures)")
-    if args.mesh_depth not in (0, 1):
-        p.error(f"--mesh_depth is 0 or 1 (got {args.mesh_depth})")
-    if args.object_meshes and len(args.object_meshes) != len(args.objects):
-        p.error(f"--object_meshes needs one mesh per --objects file, in the same order (got {len(args.object_meshes)} for "
-                f"{len(args.objects)} objects)")
-    if not args.max_mesh_depth >= 0.0:
-        p.error(f"--max_mesh_depth must be >= 0 (got {args.max_mesh_depth})")
-    if (args.mesh_depth or args.max_mesh_depth < float("inf")) and not args.object_meshes:
-        p.error("--mesh_depth and --max_mesh_depth need --object_meshes (the surfaces they test against)")
-    if args.max_mesh_depth < float("inf") and not args.candidates:
-        p.error("--max_mesh_depth needs --candidates (it ranks candidates; --mesh_depth 1 alone writes the figures)")
+    o = types.SimpleNamespace(**vars(args), rotate=DATASETS[dataset]["rotate"])
+    rule = _broken_rule(o, cli=True)
+    if rule is not None:
+        p.error(_rule_message(rule, o, cli=True))
     return args
 
 
@@ -413,7 +322,6 @@ def generate_for_object(net: GenNet, obj4n: torch.Tensor, num_grasp: int, rotate
         extra["log_prob"] = grasp_log_prob(rest[0]["logp_model"])
         extra_json["log_prob"] = extra["log_prob"].cpu().numpy().tolist()
     if proxies:
-        from . import contact
         extra["proxies"] = contact.grasp_proxies(_hand_topology(net, final.vertices.shape[1], dev), final.vertices, batch[:, :3].transpose(1, 2))
     return {**extra, "params": params, "vertices": final.vertices,
             "json": {"recon_params": [[p] for p in params.cpu().numpy().tolist()],   # [[61 floats]] per grasp, as the reference
@@ -433,7 +341,6 @@ def _hand_faces(net: GenNet) -> np.ndarray:
 
 
 def _hand_topology(net: GenNet, n_verts: int, dev):
-    from . import contact
     faces = _hand_faces(net)
     topo = getattr(net, "_hand_topology", None)
     if topo is None or topo.faces.device != dev:
@@ -444,7 +351,6 @@ def _hand_topology(net: GenNet, n_verts: int, dev):
 
 def _finger_rig(net: GenNet):
     """The ``contact.FingerRig`` of the net's MANO layer, built once and kept on the model."""
-    from . import contact
     rig = getattr(net, "_finger_rig", None)
     if rig is None:
         rig = contact.FingerRig.from_mano(net.rh_mano)
@@ -464,7 +370,6 @@ def _refine_fingers_call(net: GenNet, topo, params: torch.Tensor, first, cloud_x
     worse than that of the hand as generated takes back its generated parameters, its first-pass vertices and joints, a zero offset,
     identity turns and iterate 0.  ``torch.where`` only: no host sync, no third MANO pass.  Returns (params, the hands written,
     refined); ``refined["scores"]`` holds ``contact.grasp_scores`` of the hands written, merged from the two score sets at hand."""
-    from . import contact
     rig = _finger_rig(net)
     knuckles = first.joints[:, rig.joints].contiguous()                            # [B,P,3]
     out = contact.refine_fingers(topo, rig, first.vertices, cloud_xyz, first.joints[:, 0].contiguous(), knuckles, steps, push, pull,
@@ -500,7 +405,6 @@ def _refine_fingers_call(net: GenNet, topo, params: torch.Tensor, first, cloud_x
 def _hand_parts(net: GenNet, table):
     """The label table of ``generate_for_objects``' ``hand_parts``: a ``contact.HandParts`` as given, else the one read from the JSON
     path (None: the packaged table), kept on the model so that a run reads and uploads it once."""
-    from . import contact
     if isinstance(table, contact.HandParts):
         return table
     cached = getattr(net, "_hand_parts", None)
@@ -513,7 +417,6 @@ def _hand_parts(net: GenNet, table):
 def _self_table(net: GenNet, hand_parts, seam: int, palm: bool):
     """The ``contact.SelfTable`` of ``generate_for_objects``' self-collision switches: the label table of _hand_parts with the hand
     model's faces, kept on the model so that a run derives the seam and uploads it once."""
-    from . import contact
     parts = _hand_parts(net, hand_parts)
     cached = getattr(net, "_self_table", None)
     if cached is None or cached[0] is not parts or cached[1:3] != (int(seam), bool(palm)):
@@ -538,10 +441,11 @@ def plan_calls(point_counts: Sequence[int], num_grasp: int, rows_per_call: int) 
 
 @dataclasses.dataclass(frozen=True)
 class _Options:
-    """What generate_for_objects has validated, the same for every call of it: its keywords under their own names, but ``stability``
-    is also on with ``select_by="stability"``, ``figures`` holds the active per-row figures with their settings -- (_Figure, dict)
-    pairs in the order of FIGURES -- ``ttt`` the settings of contact.refine_ttt, or None, and ``object_contact`` the threshold in
-    metres of the object-side contact map, or None without it."""
+    """What generate_for_objects has validated, the same for every call of it: its keywords under their own names, filled by name, and
+    five derived fields (_generate_objects): ``stability`` is also on with ``select_by="stability"``, ``figures`` holds the active
+    per-row figures with their settings -- (_Figure, dict) pairs in the order of FIGURES -- ``ttt`` the settings of
+    contact.refine_ttt, or None, ``beam`` (poses, width) of a beam search, or None, and ``object_contact`` the threshold in metres of
+    the object-side contact map, or None without it."""
     num_grasp: int
     rotate: bool
     seed: int
@@ -566,6 +470,7 @@ class _Options:
     torque_length: float
     figures: tuple
     ttt: Optional[Dict[str, object]]
+    beam: Optional[tuple] = None
     object_contact: Optional[float] = None
 
 
@@ -596,8 +501,7 @@ class _Call:
 
 
 @torch.no_grad()
-def _generate_call(net: GenNet, opt: _Options, objs: Sequence[torch.Tensor], object_indices: Sequence[int],
-                   beam: Optional[Sequence[int]] = None, meshes=None) -> List[Dict[str, object]]:
+def _generate_call(net: GenNet, opt: _Options, objs: Sequence[torch.Tensor], object_indices: Sequence[int], meshes=None) -> List[Dict[str, object]]:
     """One batched call: the ``num_grasp`` grasps (with ``candidates`` = M: the M candidates) of each of ``objs`` (all of one point
     count), row o * G + g = grasp g of object o.  Every step is row-independent and keyed per row, so each object's slice holds the bits
     of its own ``generate_for_object`` call.  The stages, in order:
@@ -614,7 +518,7 @@ def _generate_call(net: GenNet, opt: _Options, objs: Sequence[torch.Tensor], obj
        the call's ONE device-to-host copy (_host_groups), the JSON lists of the whole call and the per-object split;
     7. _ttt_attach and _beam_attach."""
     dev = next(net.parameters()).device
-    rotate, seed = opt.rotate, opt.seed
+    rotate, seed, beam = opt.rotate, opt.seed, opt.beam
     G, O = (opt.candidates or opt.num_grasp), len(objs)
     log_prob = bool(opt.log_prob) or bool(beam) or (bool(opt.candidates) and opt.select_by == "log_prob")   # the beams' scores: always written
     if rotate:                                  # each object's own generator, as the loop draws them; beam: its first P draws, W rows each
@@ -642,7 +546,6 @@ def _generate_call(net: GenNet, opt: _Options, objs: Sequence[torch.Tensor], obj
     final = _pose(net, params)
     refined = None
     if opt.refine_steps:
-        from . import contact
         topo = _hand_topology(net, final.vertices.shape[1], dev)
         if opt.refine_curl:                                                        # fingers too: parameters, hands and the guard in one place
             params, final, refined = _refine_fingers_call(net, topo, params, final, cloud_xyz, opt.refine_steps, opt.refine_push,
@@ -660,7 +563,6 @@ def _generate_call(net: GenNet, opt: _Options, objs: Sequence[torch.Tensor], obj
             final = _pose(net, params)
     tuned = None
     if opt.ttt:                                                                    # gradient refinement: after any push-out, before any score
-        from . import contact
         ttt = opt.ttt
         tuned = contact.refine_ttt(net.rh_mano, _hand_topology(net, final.vertices.shape[1], dev), params, cloud_xyz, ttt["steps"], ttt["lr"],
                                    ttt["momentum"], ttt["targets"], ttt["w_pen"], ttt["w_con"], ttt["keep_best"])
@@ -717,7 +619,6 @@ def _generate_call(net: GenNet, opt: _Options, objs: Sequence[torch.Tensor], obj
             extra["log_prob"] = logp[lo:hi]
             extra_json["log_prob"] = lp_list[lo:hi]
         if opt.proxies:                                                            # per object: the reductions see the loop's shapes
-            from . import contact
             extra["proxies"] = contact.grasp_proxies(topo, final.vertices[lo:hi], batch[lo:hi, :3].transpose(1, 2))
         if row_dev:                                                                # (one test: this loop is the cost of a call at one grasp per object)
             extra.update({k: x[lo:hi] for k, x in row_dev.items()})
@@ -741,7 +642,6 @@ def _generate_call(net: GenNet, opt: _Options, objs: Sequence[torch.Tensor], obj
 def _call_scores(opt: _Options, call: _Call) -> Dict[str, torch.Tensor]:
     """The scores of a call's hands against their clouds: ONE fused kernel -- contact.grasp_stability with ``stability``, else
     contact.grasp_scores -- or none where the articulated push-out's guard has scored these very hands (_refine_fingers_call)."""
-    from . import contact
     if not opt.stability and call.refined is not None and "scores" in call.refined:
         return dict(call.refined["scores"])
     topo = _hand_topology(call.net, call.vertices.shape[1], call.vertices.device)
@@ -811,7 +711,6 @@ def _stability_json(sums: np.ndarray, n_contact: np.ndarray, key: np.ndarray) ->
     """``--stability`` / ``--select_by stability``: the four JSON lists of a call's rows from the host copies of the kernel's sums,
     contact counts and keys -- float64 on the host, row by row (contact.wrench_stats), so that a grasp's figures do not depend on which
     rows share the call.  A hand that touches nothing has no figure: null, and so has a key that is not finite."""
-    from . import contact
     out = contact.wrench_stats(sums, n_contact)
     out["stability_key"] = [float(k) if np.isfinite(k) else None for k in key]
     return out
@@ -837,8 +736,17 @@ class _Figure:
     figures do not depend on which rows share the call; raises on the figure's own error flag.  ``slice(s, lists, host, lo, hi, call,
     o)``: the JSON fields of object o, whose grasps are the rows lo .. hi of the copies.  ``stem``, ``rows(json)`` and ``summary(args,
     net, rows)``: the run summary ``main`` writes to <stem>.json -- what it keeps of every object's JSON, and from those (in object
-    order) the summary and the line printed; integers and exactly rounded sums, so that no grouping can change a bit."""
+    order) the summary and the line printed; integers and exactly rounded sums, so that no grouping can change a bit.
+    A figure is also the option group that asks for it (GROUPS, under ``key``): ``switch`` is the keyword that turns it on, ``limits``
+    the keywords of its guard, ``limited(o)`` whether ``o`` -- anything with the options as attributes -- sets one of them, ``wanted(o)``
+    whether the figure runs, ``keywords`` what ``main`` passes with it beside ``switch=True``, ``faces`` whether it needs the hand
+    model's face list, and ``settings(o, net)`` the dict ``s``, built once every value check of the call has passed."""
     shown = None                                                                   # every piece
+    faces = False
+
+    @classmethod
+    def wanted(cls, o) -> bool:
+        return bool(getattr(o, cls.switch)) or cls.limited(o)
 
     @staticmethod
     def guard(s, dev):
@@ -870,10 +778,18 @@ class _Volume(_Figure):
     figure class 2 (integer comparisons on the device).  The JSON fields are penetration_volume, penetration_depth and volume_voxels
     (contact.volume_stats); null where the kernel gives no figure (count < 0)."""
     key, scores_key, stem, pieces, shown = "volume", "volume_scores", "penetration", VOLUME_PIECES, 3
+    switch, limits, keywords, faces = "volume", ("max_volume",), ("volume_res", "max_volume"), True
+
+    @staticmethod
+    def limited(o):
+        return o.max_volume < math.inf
+
+    @staticmethod
+    def settings(o, net):
+        return dict(res=float(o.volume_res), max_volume=float(o.max_volume))
 
     @staticmethod
     def launch(s, call):
-        from . import contact
         dev = call.vertices.device
         topo = _hand_topology(call.net, call.vertices.shape[1], dev)
         planes, plane_off = contact.pack_planes([contact.hull_planes(o[:3].T.cpu().numpy().astype(np.float64)) for o in call.objs])
@@ -884,7 +800,6 @@ class _Volume(_Figure):
 
     @staticmethod
     def guard(s, dev):
-        from . import contact
         if not s["max_volume"] < float("inf"):
             return None
         cnt = dev["count"]
@@ -893,7 +808,6 @@ class _Volume(_Figure):
 
     @staticmethod
     def lists(s, host):
-        from . import contact
         count, depth, _, bad = host
         if int(bad[0]) != 0:
             raise RuntimeError("generate_for_objects: volume: an index of the hand topology or of the hulls is out of range")
@@ -922,28 +836,35 @@ class _Parts(_Figure):
     part_contact and part_dist (contact.part_stats; null where a row has no figure) and, per object, "hand_contact_map": at every
     vertex, how many of its grasps touch there (contact.contact_map)."""
     key, scores_key, stem, pieces = "parts", "part_scores", "hand_contact", PARTS_PIECES
+    switch, limits = "parts", ("min_fingers", "need_thumb")
+    keywords = ("part_threshold", "part_min_verts", "min_fingers", "need_thumb", "hand_parts")
+
+    @staticmethod
+    def limited(o):
+        return o.min_fingers > 0 or bool(o.need_thumb)
+
+    @staticmethod
+    def settings(o, net):
+        return dict(table=_hand_parts(net, o.hand_parts), threshold=float(o.part_threshold), min_verts=int(o.part_min_verts),
+                    min_fingers=int(o.min_fingers), need_thumb=bool(o.need_thumb))
 
     @staticmethod
     def launch(s, call):
-        from . import contact
         return contact.grasp_parts(s["table"], call.vertices, call.cloud_xyz, s["threshold"])
 
     @staticmethod
     def guard(s, dev):
-        from . import contact
         if not (s["min_fingers"] or s["need_thumb"]):
             return None
         return contact.parts_class(dev, s["min_fingers"], s["need_thumb"], s["min_verts"])
 
     @staticmethod
     def lists(s, host):
-        from . import contact
         part_min, part_count, _, status = host
         return contact.part_stats(part_min, part_count, status, s["min_verts"], min(5, s["table"].n_parts))
 
     @staticmethod
     def slice(s, lists, host, lo, hi, call, o):
-        from . import contact
         return {**_Figure.slice(s, lists, host, lo, hi, call, o), "hand_contact_map": contact.contact_map(host[2][lo:hi], s["table"].n_verts).tolist()}
 
     @staticmethod
@@ -965,21 +886,29 @@ class _Self(_Figure):
     over all rows of the call -- the hands against themselves.  More than ``max_verts`` self-penetrating vertices joins class 1, a row
     without a figure class 2 (contact.self_class).  The JSON fields are the five of contact.self_stats; null where a row has no figure."""
     key, scores_key, stem, pieces = "self", "self_scores", "self_collision", SELF_PIECES
+    switch, limits = "self_collision", ("max_self_verts",)
+    keywords = ("self_reach", "self_margin", "self_seam", "self_palm", "max_self_verts", "hand_parts")
+
+    @staticmethod
+    def limited(o):
+        return o.max_self_verts is not None
+
+    @staticmethod
+    def settings(o, net):
+        return dict(table=_self_table(net, o.hand_parts, int(o.self_seam), bool(o.self_palm)), reach=float(o.self_reach),
+                    margin=float(o.self_margin), max_verts=None if o.max_self_verts is None else int(o.max_self_verts))
 
     @staticmethod
     def launch(s, call):
-        from . import contact
         return contact.grasp_self(_hand_topology(call.net, call.vertices.shape[1], call.vertices.device), s["table"], call.vertices, s["reach"],
                                   s["margin"])
 
     @staticmethod
     def guard(s, dev):
-        from . import contact
         return contact.self_class(dev, s["max_verts"]) if s["max_verts"] is not None else None
 
     @staticmethod
     def lists(s, host):
-        from . import contact
         return contact.self_stats(dict(zip(SELF_PIECES, host)))
 
     @staticmethod
@@ -1007,22 +936,28 @@ class _Mesh(_Figure):
     fields are mesh_depth and mesh_interior (contact.mesh_stats; null where the kernel gives no figure, n_inside < 0) and, per object,
     whether its mesh is closed and "mesh_penetration_map": at every hand vertex, how many of its grasps have it inside the mesh."""
     key, scores_key, stem, pieces, shown = "mesh", "mesh_scores", "mesh_penetration", MESH_PIECES, 3
+    switch, limits, keywords = "mesh_depth", ("max_mesh_depth",), ("max_mesh_depth",)   # (``object_meshes`` goes per call)
+
+    @staticmethod
+    def limited(o):
+        return o.max_mesh_depth < math.inf
+
+    @staticmethod
+    def settings(o, net):
+        return dict(max_depth=float(o.max_mesh_depth))
 
     @staticmethod
     def launch(s, call):
-        from . import contact
         bad = ops.new_err_flag(call.vertices.device)
         out = contact.grasp_mesh(call.meshes, call.vertices, call.obj_of_row, *call.frame, err=bad)
         return {**{k: out[k] for k in MESH_PIECES[:3]}, "err": bad}
 
     @staticmethod
     def guard(s, dev):
-        from . import contact
         return contact.mesh_class(dev, s["max_depth"]) if s["max_depth"] < float("inf") else None
 
     @staticmethod
     def lists(s, host):
-        from . import contact
         n_inside, depth, _, bad = host
         if int(bad[0]) != 0:
             raise RuntimeError("generate_for_objects: mesh depth: an object index, an object's range or a face index is out of range")
@@ -1030,7 +965,6 @@ class _Mesh(_Figure):
 
     @staticmethod
     def slice(s, lists, host, lo, hi, call, o):
-        from . import contact
         return {**_Figure.slice(s, lists, host, lo, hi, call, o), "mesh_closed": bool(call.meshes.closed[o]),
                 "mesh_penetration_map": contact.contact_map(host[2][lo:hi], call.vertices.shape[1]).tolist()}
 
@@ -1080,7 +1014,6 @@ def _object_contact_launch(call: _Call, O: int, K: int, rows: Optional[torch.Ten
     """``--object_contact``: one ``contact.object_contact`` over the grasps written -- all rows of the call (``rows`` = None: object o's
     are rows o * K .. o * K + K - 1), or the kept rows by their index list against the call's hands and clouds, read in place (no
     gather) -- at ``threshold`` metres; the kernel's tensors and its error flag."""
-    from . import contact
     dev = call.vertices.device
     bad = ops.new_err_flag(dev)
     out = contact.object_contact(_hand_topology(call.net, call.vertices.shape[1], dev), call.vertices, call.cloud_xyz, O, K, rows,
@@ -1097,7 +1030,6 @@ def _object_contact_json(threshold: float, host: Sequence[np.ndarray]) -> List[D
     """The four object-side contact fields of every object of a call from the host copies of OBJECT_CONTACT_PIECES: float64 on the host,
     per object (contact.object_contact_stats), so that an object's entry does not depend on which objects share the call.  Index p is
     point p of the object's cloud.  A distance that is not finite becomes null."""
-    from . import contact
     touch, inside, dmin, n_valid, bad = host
     if int(bad[0]) != 0:
         raise RuntimeError("generate_for_objects: object_contact: a row index is out of range")
@@ -1121,7 +1053,6 @@ def _select_call(opt: _Options, call: _Call) -> List[Dict[str, object]]:
        pieces; the k-means of ``diversity`` over the kept parameters (_diversity_launch); the object-side contact map of
        ``object_contact`` over the kept rows, by their index list against the call's hands and clouds (_object_contact_launch);
     4. the call's ONE device-to-host copy (_host_groups), the JSON lists of the kept rows and the per-object split."""
-    from . import contact
     net, params, vertices, logp, refined = call.net, call.params, call.vertices, call.logp, call.refined
     O, M, keep, dev = len(call.objs), call.G, opt.num_grasp, params.device
     topo = _hand_topology(net, vertices.shape[1], dev) if opt.proxies else None
@@ -1206,6 +1137,150 @@ def _select_call(opt: _Options, call: _Call) -> List[Dict[str, object]]:
                               "r_list": r_list[lo:hi], "candidate": c_list[o], **{k: s_list[k][lo:hi] for k in json_scores},
                               **extra_json}})
     return outs
+
+
+@dataclasses.dataclass(frozen=True)
+class _Group:
+    """An option group without a per-row figure, in the vocabulary of _Figure: ``wanted(o)`` whether it is on, ``keywords`` what ``main``
+    passes when it is (under the flags' own names), ``switch`` the bool keyword forced on with it, ``faces`` whether it needs the hand
+    model's face list, ``settings(o, net)`` what _Options holds for it, built once every value check of the call has passed."""
+    wanted: Callable[[object], bool]
+    keywords: tuple
+    switch: Optional[str] = None
+    faces: bool = False
+    settings: Optional[Callable] = None
+
+
+def _ttt_settings(o, net) -> Dict[str, object]:
+    return dict(steps=int(o.ttt_steps), lr=float(o.ttt_lr), momentum=float(o.ttt_momentum), w_pen=float(o.ttt_w_pen),
+                w_con=float(o.ttt_w_con), targets=_ttt_targets(o.ttt_prior), keep_best=bool(o.ttt_keep_best))
+
+
+# every option group by name: what is on for an ``o`` -- the parsed flags, or the bound keywords of a call -- is asked here and nowhere else
+GROUPS = {
+    "selection": _Group(lambda o: bool(o.candidates), ("candidates", "select_by", "min_contact"), faces=True),
+    "diverse": _Group(lambda o: bool(o.diverse_pool), ("diverse_pool", "diverse_space")),
+    "pushout": _Group(lambda o: bool(o.refine_steps), ("refine_steps", "refine_push", "refine_pull", "min_contact"), faces=True),
+    "spin": _Group(lambda o: bool(o.refine_spin), ("refine_spin",)),
+    "curl": _Group(lambda o: bool(o.refine_curl), ("refine_curl", "refine_max_curl")),
+    "ttt": _Group(lambda o: bool(o.ttt_steps), ("ttt_steps", "ttt_lr", "ttt_momentum", "ttt_w_pen", "ttt_w_con", "ttt_prior", "ttt_keep_best"),
+                  faces=True, settings=_ttt_settings),
+    "diversity": _Group(lambda o: bool(o.diversity), ("diversity",)),
+    "beam": _Group(lambda o: bool(o.beam_width), ("beam_width", "beam_poses"), settings=lambda o, net: (int(o.beam_poses), int(o.beam_width))),
+    "stability": _Group(lambda o: bool(o.stability) or (bool(o.candidates) and o.select_by == "stability"),
+                        ("max_penetration", "torque_length"), switch="stability", faces=True),
+    **{fig.key: fig for fig in FIGURES},
+    # (a flag, but no keyword of generate_for_objects: on the keyword path it is on inside generate_with_object_contact)
+    "object_contact": _Group(lambda o: bool(o.object_contact), ("object_contact_threshold",), faces=True,
+                             settings=lambda o, net: float(o.object_contact_threshold)),
+}
+
+
+@dataclasses.dataclass(frozen=True)
+class _Rule:
+    """One check of the options, stated once for both entry paths.  ``names``: the options refused; ``ok(o)``: the predicate over
+    anything with the options as attributes (``rotate`` among them); ``text``: what follows the names in the message, ``$`` marking
+    further option names; ``gate``: the group that must be on for the KEYWORD path to apply the rule (parse_args applies every rule it
+    has: ``--torque_length -1`` is refused without ``--stability``); ``only``: "cli" or "keywords" where one path alone has the rule."""
+    names: tuple
+    ok: Callable[[object], bool]
+    text: str
+    gate: Optional[str] = None
+    only: Optional[str] = None
+
+
+def _rule(names: str, ok, text: str, gate: Optional[str] = None, only: Optional[str] = None) -> _Rule:
+    return _Rule(tuple(names.split()), ok, text, gate, only)
+
+
+def _positive(x) -> bool:
+    return 0.0 < x < math.inf
+
+
+def _not_negative(x) -> bool:
+    return 0.0 <= x < math.inf
+
+
+RULES = (
+    _rule("candidates", lambda o: not o.candidates or o.candidates >= max(1, o.num_grasp), "must be 0 or at least $num_grasp"),
+    # keywords only, as it has been: ``--candidates 5000`` gets past parse_args and dies in the call; drop the marker to refuse it there
+    _rule("candidates", lambda o: o.candidates <= ops.SEGMENT_TOPK_MAX_M, f"may be at most {ops.SEGMENT_TOPK_MAX_M} per object", only="keywords"),
+    _rule("select_by", lambda o: o.select_by in contact.SELECT_BY, f"must be one of {contact.SELECT_BY}", "selection", "keywords"),
+    _rule("diverse_pool", lambda o: not o.diverse_pool or (bool(o.candidates) and o.num_grasp <= o.diverse_pool <= o.candidates),
+          "must be 0, or lie between $num_grasp and $candidates"),
+    _rule("diverse_space", lambda o: o.diverse_space in DIVERSE_SPACES, f"must be one of {DIVERSE_SPACES}", "diverse", "keywords"),
+    _rule("diversity", lambda o: 0 <= o.diversity <= min(o.num_grasp, ops.SEGMENT_KMEANS_MAX_K),
+          f"must lie between 0 and min($num_grasp, {ops.SEGMENT_KMEANS_MAX_K})"),
+    *(_rule(name, lambda o, name=name: getattr(o, name) in (0, 1), "is 0 or 1", only="cli")
+      for name in ("object_contact", "ttt_keep_best", "need_thumb", "parts", "self_collision", "self_palm", "mesh_depth")),
+    _rule("object_contact_threshold", lambda o: _positive(o.object_contact_threshold), "must be finite and positive", "object_contact"),
+    _rule("refine_steps", lambda o: 0 <= o.refine_steps <= ops.GRASP_REFINE_MAX_STEPS, f"must lie between 0 and {ops.GRASP_REFINE_MAX_STEPS}"),
+    _rule("refine_push refine_pull", lambda o: _not_negative(o.refine_push) and _not_negative(o.refine_pull), "must be finite and >= 0", "pushout"),
+    _rule("refine_spin", lambda o: _not_negative(o.refine_spin), "must be finite and >= 0"),
+    _rule("refine_spin", lambda o: not o.refine_spin or bool(o.refine_steps), "needs $refine_steps (it turns the hand during the push-out)"),
+    _rule("refine_curl", lambda o: _not_negative(o.refine_curl), "must be finite and >= 0"),
+    _rule("refine_curl", lambda o: not o.refine_curl or bool(o.refine_steps), "needs $refine_steps (it curls the fingers during the push-out)"),
+    _rule("refine_max_curl", lambda o: 0.0 < o.refine_max_curl <= math.pi, "must lie in (0, pi]"),
+    _rule("ttt_steps", lambda o: 0 <= o.ttt_steps <= TTT_MAX_STEPS, f"must lie between 0 and {TTT_MAX_STEPS}"),
+    _rule("ttt_lr", lambda o: _not_negative(o.ttt_lr), "must be finite and >= 0", "ttt"),
+    _rule("ttt_momentum", lambda o: 0.0 <= o.ttt_momentum < 1.0, "must lie in [0, 1)", "ttt"),
+    _rule("ttt_w_pen ttt_w_con", lambda o: _not_negative(o.ttt_w_pen) and _not_negative(o.ttt_w_con), "must be finite and >= 0", "ttt"),
+    _rule("ttt_prior", lambda o: o.ttt_prior is None or bool(o.ttt_steps),
+          "needs $ttt_steps (it names the contact vertices of the gradient refinement)"),
+    _rule("torque_length", lambda o: _positive(o.torque_length), "must be finite and positive", "stability"),
+    _rule("max_penetration", lambda o: o.max_penetration >= 0.0, "must be >= 0", "stability"),
+    _rule("volume_res", lambda o: _positive(o.volume_res), "must be finite and positive", "volume"),
+    _rule("max_volume", lambda o: o.max_volume >= 0.0, "must be >= 0", "volume"),
+    _rule("part_threshold", lambda o: _positive(o.part_threshold), "must be finite and positive", "parts"),
+    _rule("part_min_verts", lambda o: o.part_min_verts >= 1, "must be at least 1", "parts"),
+    _rule("min_fingers", lambda o: 0 <= o.min_fingers <= 5, "must lie between 0 and 5"),
+    _rule("self_reach", lambda o: _positive(o.self_reach), "must be finite and positive", "self"),
+    _rule("self_margin", lambda o: _not_negative(o.self_margin), "must be finite and >= 0", "self"),
+    _rule("self_seam", lambda o: o.self_seam >= 0, "must be >= 0", "self"),
+    _rule("max_self_verts", lambda o: o.max_self_verts is None or o.max_self_verts >= 0, "must be >= 0"),
+    _rule("max_mesh_depth", lambda o: o.max_mesh_depth >= 0.0, "must be >= 0", "mesh"),
+    *(_rule(" ".join(fig.limits), lambda o, fig=fig: not fig.limited(o) or bool(o.candidates),
+            f"needs $candidates (a guard on the ranking of candidates; ${fig.switch} alone writes the figures)") for fig in FIGURES),
+    _rule("object_meshes", lambda o: not o.object_meshes or len(o.object_meshes) == len(o.objects),
+          "needs one mesh per $objects file, in the same order", only="cli"),
+    _rule("mesh_depth max_mesh_depth", lambda o: not _Mesh.wanted(o) or bool(o.object_meshes),
+          "need $object_meshes (the surfaces they test against)", only="cli"),
+    _rule("object_meshes", lambda o: o.object_meshes is not None and len(o.object_meshes) == len(o.objs),
+          "must hold one (verts, faces) per object of $objs: what mesh_depth and max_mesh_depth test against", "mesh", "keywords"),
+    _rule("object_indices", lambda o: len(o.object_indices) == len(o.objs), "must hold one index per object of $objs", only="keywords"),
+    _rule("beam_width", lambda o: 0 <= o.beam_width <= ops.PIXELCNN_BEAM_MAX_W, f"must lie between 0 and {ops.PIXELCNN_BEAM_MAX_W}"),
+    _rule("beam_poses", lambda o: o.beam_poses >= 1, "must be at least 1"),
+    _rule("beam_poses", lambda o: bool(o.beam_width) or o.beam_poses == 1, "needs $beam_width (it counts the poses a beam search runs for)"),
+    _rule("beam_poses", lambda o: not o.beam_width or o.beam_poses == 1 or bool(o.rotate),
+          "must be 1 where the objects are not rotated: every pose would be the same $beam_width search"),
+    _rule("beam_width", lambda o: not o.beam_width or (o.candidates or o.num_grasp) == o.beam_poses * o.beam_width,
+          "times $beam_poses must equal $candidates or, without it, $num_grasp"),
+    _rule("beam_width", lambda o: not o.beam_width or (o.temperature == 1.0 and o.top_k == 0),
+          "excludes $temperature and $top_k: a beam search draws nothing"),
+)
+
+
+def _rule_options(rule: _Rule) -> List[str]:
+    """The options a rule reads: its names, then those its text marks."""
+    return list(dict.fromkeys(list(rule.names) + re.findall(r"\$(\w+)", rule.text)))
+
+
+def _broken_rule(o, cli: bool) -> Optional[_Rule]:
+    """The first of RULES that ``o`` breaks on the flag path (``cli``) or the keyword path, or None."""
+    for rule in RULES:
+        if rule.only == ("keywords" if cli else "cli") or (rule.gate and not cli and not GROUPS[rule.gate].wanted(o)):
+            continue
+        if not rule.ok(o):
+            return rule
+    return None
+
+
+def _rule_message(rule: _Rule, o, cli: bool) -> str:
+    """``--names text (got ...)`` for parse_args, the same without the dashes for the keyword path; a sequence shows its length."""
+    dash = "--" if cli else ""
+    got = ((n, getattr(o, n)) for n in _rule_options(rule))
+    got = ", ".join(f"{dash}{n} {'of %d entries' % len(v) if isinstance(v, (list, tuple)) else repr(v)}" for n, v in got)
+    return f"{' and '.join(dash + n for n in rule.names)} {rule.text.replace('$', dash)} (got {got})"
 
 
 def generate_for_objects(net: GenNet, objs: Sequence[torch.Tensor], num_grasp: int, rotate: bool, seed: int,
@@ -1350,7 +1425,11 @@ def generate_for_objects(net: GenNet, objs: Sequence[torch.Tensor], num_grasp: i
     better beam with the same six hand codes, or -1).  Excludes ``temperature`` / ``top_k``; the searches of a call do not depend on
     one another, so the results do not depend on ``rows_per_call``.  fp16 weight images only, no bf16 fallback inside the search;
     whether likelier grids are better grasps is not measured.  ``beam_width = 0`` is the call without the keyword."""
-    return _generate_objects(None, **locals())                                     # (first statement: the locals are the keywords)
+    return _generate_objects(locals())                                             # (first statement: the locals are the keywords)
+
+
+# the keywords that are 0/1 integers as flags: ``main`` converts them
+BOOL_KEYWORDS = frozenset(k for k, p in inspect.signature(generate_for_objects).parameters.items() if isinstance(p.default, bool))
 
 
 def generate_with_object_contact(net: GenNet, objs: Sequence[torch.Tensor], num_grasp: int, rotate: bool, seed: int,
@@ -1366,151 +1445,32 @@ def generate_with_object_contact(net: GenNet, objs: Sequence[torch.Tensor], num_
     cloud: a rotation does not permute points.  The maps ride in the call's one device-to-host copy and do not depend on
     ``rows_per_call``; everything else is what ``generate_for_objects`` returns, bit for bit.  A proximity figure at an untuned
     threshold; the effect on real grasps is not measured.  (A function of its own: the keywords of ``generate_for_objects`` are pinned.)"""
-    if not 0.0 < float(object_contact_threshold) < float("inf"):
-        raise RuntimeError(f"generate_with_object_contact: object_contact_threshold must be finite and positive (got {object_contact_threshold})")
-    _hand_faces(net)                                                               # no face list: raise before any work
     call = inspect.signature(generate_for_objects).bind(net, objs, num_grasp, rotate, seed, object_indices, **options)
     call.apply_defaults()
-    return _generate_objects(float(object_contact_threshold), **call.arguments)
+    return _generate_objects(call.arguments, object_contact_threshold)
 
 
-def _generate_objects(object_contact, net, objs, num_grasp, rotate, seed, object_indices, proxies, rows_per_call,
-                      temperature, top_k, log_prob, candidates, select_by, min_contact, diverse_pool, diverse_space,
-                      refine_steps, refine_push, refine_pull, diversity, stability, max_penetration, torque_length,
-                      volume, volume_res, max_volume, parts, part_threshold, part_min_verts, min_fingers, need_thumb,
-                      hand_parts, refine_spin, refine_curl, refine_max_curl, self_collision, self_reach, self_margin,
-                      self_seam, self_palm, max_self_verts, object_meshes, mesh_depth, max_mesh_depth, ttt_steps,
-                      ttt_lr, ttt_momentum, ttt_w_pen, ttt_w_con, ttt_prior, ttt_keep_best, beam_width, beam_poses) -> List[Dict[str, object]]:
-    """The body of ``generate_for_objects`` (its keywords, validated here) and of ``generate_with_object_contact``: ``object_contact``
-    is the threshold in metres of the object-side contact map, or None without it."""
-    beam = None
-    if beam_width:
-        rows = candidates or num_grasp
-        if not 1 <= int(beam_width) <= ops.PIXELCNN_BEAM_MAX_W or int(beam_poses) < 1 or int(beam_width) * int(beam_poses) != rows:
-            raise RuntimeError(f"generate_for_objects: beam_width in 1 .. {ops.PIXELCNN_BEAM_MAX_W} and beam_poses * beam_width = "
-                               f"{'candidates' if candidates else 'num_grasp'} (got {beam_width}, {beam_poses} for {rows} rows)")
-        if int(beam_poses) != 1 and not rotate:
-            raise RuntimeError("generate_for_objects: beam_poses must be 1 without rotation")
-        if float(temperature) != 1.0 or int(top_k) != 0:
-            raise RuntimeError("generate_for_objects: beam_width excludes temperature and top_k")
-        beam = (int(beam_poses), int(beam_width))
-    elif int(beam_poses) != 1:
-        raise RuntimeError("generate_for_objects: beam_poses needs beam_width")
-    self_args = None
-    if self_collision or max_self_verts is not None:
-        if not 0.0 < float(self_reach) < float("inf") or not 0.0 <= float(self_margin) < float("inf"):
-            raise RuntimeError(f"generate_for_objects: self_reach must be finite and positive, self_margin finite and >= 0 "
-                               f"(got {self_reach}, {self_margin})")
-        if int(self_seam) < 0:
-            raise RuntimeError(f"generate_for_objects: self_seam must be >= 0 (got {self_seam})")
-        if max_self_verts is not None and (int(max_self_verts) < 0 or not candidates):
-            raise RuntimeError(f"generate_for_objects: max_self_verts must be >= 0 and needs candidates (got {max_self_verts})")
-        self_args = dict(table=_self_table(net, hand_parts, int(self_seam), bool(self_palm)), reach=float(self_reach),
-                         margin=float(self_margin), max_verts=None if max_self_verts is None else int(max_self_verts))
-    want_mesh = bool(mesh_depth) or float(max_mesh_depth) < float("inf")
-    if want_mesh:
-        if object_meshes is None or len(object_meshes) != len(objs):
-            raise RuntimeError("generate_for_objects: mesh_depth and max_mesh_depth need object_meshes, one (verts, faces) per object")
-        if not float(max_mesh_depth) >= 0.0:
-            raise RuntimeError(f"generate_for_objects: max_mesh_depth must be >= 0 (got {max_mesh_depth})")
-        if float(max_mesh_depth) < float("inf") and not candidates:
-            raise RuntimeError("generate_for_objects: max_mesh_depth needs candidates")
-    parts_args = None
-    if parts or min_fingers or need_thumb:
-        from . import contact
-        if not 0.0 < float(part_threshold) < float("inf"):
-            raise RuntimeError(f"generate_for_objects: part_threshold must be finite and positive (got {part_threshold})")
-        if int(part_min_verts) < 1 or not 0 <= int(min_fingers) <= 5:
-            raise RuntimeError(f"generate_for_objects: part_min_verts >= 1 and 0 <= min_fingers <= 5 (got {part_min_verts}, {min_fingers})")
-        if (min_fingers or need_thumb) and not candidates:
-            raise RuntimeError("generate_for_objects: min_fingers and need_thumb need candidates")
-        parts_args = dict(table=_hand_parts(net, hand_parts), threshold=float(part_threshold), min_verts=int(part_min_verts),
-                          min_fingers=int(min_fingers), need_thumb=bool(need_thumb))
-    vol_args = None
-    if volume or float(max_volume) < float("inf"):
-        if not 0.0 < float(volume_res) < float("inf"):
-            raise RuntimeError(f"generate_for_objects: volume_res must be finite and positive (got {volume_res})")
-        if not float(max_volume) >= 0.0:
-            raise RuntimeError(f"generate_for_objects: max_volume must be >= 0 (got {max_volume})")
-        if float(max_volume) < float("inf") and not candidates:
-            raise RuntimeError("generate_for_objects: max_volume needs candidates")
-        _hand_faces(net)                                                           # no face list: raise before any work
-        vol_args = dict(res=float(volume_res), max_volume=float(max_volume))
-    stability = bool(stability) or (bool(candidates) and select_by == "stability")
-    if stability:
-        if not 0.0 < float(torque_length) < float("inf"):
-            raise RuntimeError(f"generate_for_objects: torque_length must be finite and positive (got {torque_length})")
-        if not float(max_penetration) >= 0.0:
-            raise RuntimeError(f"generate_for_objects: max_penetration must be >= 0 (got {max_penetration})")
-        _hand_faces(net)                                                           # no face list: raise before any work
-    if len(object_indices) != len(objs):
-        raise RuntimeError("generate_for_objects: one object index per object")
-    if diverse_pool:
-        if diverse_space not in DIVERSE_SPACES:
-            raise RuntimeError(f"generate_for_objects: diverse_space must be one of {DIVERSE_SPACES} (got {diverse_space!r})")
-        if diverse_pool < 0 or not candidates:
-            raise RuntimeError(f"generate_for_objects: diverse_pool must be 0, or positive together with candidates (got {diverse_pool} "
-                               f"with candidates={candidates})")
-        if not num_grasp <= diverse_pool <= candidates:
-            raise RuntimeError(f"generate_for_objects: diverse_pool must lie between num_grasp and candidates (got {diverse_pool} for "
-                               f"{num_grasp} grasps of {candidates} candidates)")
-    if candidates:
-        from . import contact
-        if candidates < num_grasp:
-            raise RuntimeError(f"generate_for_objects: candidates must be 0 or >= num_grasp (got {candidates} for {num_grasp})")
-        if candidates > ops.SEGMENT_TOPK_MAX_M:
-            raise RuntimeError(f"generate_for_objects: at most {ops.SEGMENT_TOPK_MAX_M} candidates per object (got {candidates})")
-        if select_by not in contact.SELECT_BY:
-            raise RuntimeError(f"generate_for_objects: select_by must be one of {contact.SELECT_BY} (got {select_by!r})")
-        _hand_faces(net)                                                           # no face list: raise before any work
-    if diversity and not 0 < diversity <= min(num_grasp, ops.SEGMENT_KMEANS_MAX_K):
-        raise RuntimeError(f"generate_for_objects: diversity must lie between 0 and min(num_grasp, {ops.SEGMENT_KMEANS_MAX_K}) "
-                           f"(got {diversity} for {num_grasp} grasps)")
-    if not 0.0 <= float(refine_spin) < float("inf"):
-        raise RuntimeError(f"generate_for_objects: refine_spin must be finite and >= 0 (got {refine_spin})")
-    if refine_spin and not refine_steps:
-        raise RuntimeError("generate_for_objects: refine_spin needs refine_steps")
-    if not 0.0 <= float(refine_curl) < float("inf"):
-        raise RuntimeError(f"generate_for_objects: refine_curl must be finite and >= 0 (got {refine_curl})")
-    if refine_curl and not refine_steps:
-        raise RuntimeError("generate_for_objects: refine_curl needs refine_steps")
-    if not 0.0 < float(refine_max_curl) <= math.pi:
-        raise RuntimeError(f"generate_for_objects: refine_max_curl must lie in (0, pi] (got {refine_max_curl})")
-    if refine_steps:
-        if not 0 < refine_steps <= ops.GRASP_REFINE_MAX_STEPS:
-            raise RuntimeError(f"generate_for_objects: refine_steps must lie between 0 and {ops.GRASP_REFINE_MAX_STEPS} (got {refine_steps})")
-        if not (0.0 <= refine_push < float("inf") and 0.0 <= refine_pull < float("inf")):
-            raise RuntimeError(f"generate_for_objects: refine_push and refine_pull must be finite and >= 0 (got {refine_push}, {refine_pull})")
-        _hand_faces(net)                                                           # no face list: raise before any work
-    ttt_args = None
-    if ttt_steps:
-        from . import contact
-        if not 0 < int(ttt_steps) <= TTT_MAX_STEPS:
-            raise RuntimeError(f"generate_for_objects: ttt_steps must lie between 0 and {TTT_MAX_STEPS} (got {ttt_steps})")
-        if not (0.0 <= float(ttt_lr) < float("inf") and 0.0 <= float(ttt_momentum) < 1.0):
-            raise RuntimeError(f"generate_for_objects: ttt_lr must be finite and >= 0, ttt_momentum in [0, 1) (got {ttt_lr}, {ttt_momentum})")
-        if not (0.0 <= float(ttt_w_pen) < float("inf") and 0.0 <= float(ttt_w_con) < float("inf")):
-            raise RuntimeError(f"generate_for_objects: ttt_w_pen and ttt_w_con must be finite and >= 0 (got {ttt_w_pen}, {ttt_w_con})")
-        _hand_faces(net)                                                           # no face list: raise before any work
-        ttt_args = dict(steps=int(ttt_steps), lr=float(ttt_lr), momentum=float(ttt_momentum), w_pen=float(ttt_w_pen),
-                        w_con=float(ttt_w_con), targets=_ttt_targets(ttt_prior), keep_best=bool(ttt_keep_best))
-    elif ttt_prior is not None:
-        raise RuntimeError("generate_for_objects: ttt_prior needs ttt_steps")
-    mesh_args = dict(max_depth=float(max_mesh_depth)) if want_mesh else None
-    opt = _Options(num_grasp=num_grasp, rotate=rotate, seed=seed, proxies=proxies, temperature=temperature, top_k=top_k, log_prob=log_prob,
-                   candidates=candidates, select_by=select_by, min_contact=min_contact, diverse_pool=diverse_pool, diverse_space=diverse_space,
-                   refine_steps=refine_steps, refine_push=refine_push, refine_pull=refine_pull, refine_spin=float(refine_spin),
-                   refine_curl=float(refine_curl), refine_max_curl=float(refine_max_curl), diversity=diversity, stability=stability,
-                   max_penetration=max_penetration, torque_length=torque_length, ttt=ttt_args,
-                   object_contact=object_contact,
-                   figures=tuple((fig, s) for fig, s in zip(FIGURES, (vol_args, parts_args, self_args, mesh_args)) if s is not None))
-    out: List[Optional[Dict[str, object]]] = [None] * len(objs)
-    for call in plan_calls([o.shape[1] for o in objs], candidates or num_grasp, rows_per_call):
-        meshes = None
-        if want_mesh:                                                              # the call's objects, packed and uploaded once per call
-            from . import contact
-            meshes = contact.ObjectMeshes([object_meshes[p] for p in call])
-        res = _generate_call(net, opt, [objs[p] for p in call], [object_indices[p] for p in call], beam, meshes)
+def _generate_objects(keywords, object_contact_threshold: Optional[float] = None) -> List[Dict[str, object]]:
+    """The body of ``generate_for_objects`` -- ``keywords`` are its bound arguments by name -- and of ``generate_with_object_contact``,
+    which adds the threshold.  Every value check (RULES) comes first and sees no more than the values; then the face list, the tables
+    and the files the groups' settings need; then one _Options for all the calls."""
+    o = types.SimpleNamespace(**keywords, object_contact=object_contact_threshold is not None, object_contact_threshold=object_contact_threshold)
+    rule = _broken_rule(o, cli=False)
+    if rule is not None:
+        raise RuntimeError("generate_for_objects: " + _rule_message(rule, o, cli=False))
+    on = {name: group for name, group in GROUPS.items() if group.wanted(o)}
+    if any(group.faces for group in on.values()):
+        _hand_faces(o.net)                                                         # no face list: raise before any work
+    settings = {name: group.settings(o, o.net) for name, group in on.items() if group.settings is not None}
+    named = {f.name: keywords[f.name] for f in dataclasses.fields(_Options) if f.name in keywords}
+    opt = _Options(**{**named, "stability": "stability" in on, "ttt": settings.get("ttt"), "beam": settings.get("beam"),
+                      "object_contact": settings.get("object_contact"),
+                      "figures": tuple((fig, settings[fig.key]) for fig in FIGURES if fig.key in on)})
+    out: List[Optional[Dict[str, object]]] = [None] * len(o.objs)
+    for call in plan_calls([x.shape[1] for x in o.objs], o.candidates or o.num_grasp, o.rows_per_call):
+        # the call's objects' meshes, packed and uploaded once per call
+        meshes = contact.ObjectMeshes([o.object_meshes[p] for p in call]) if _Mesh.key in on else None
+        res = _generate_call(o.net, opt, [o.objs[p] for p in call], [o.object_indices[p] for p in call], meshes)
         for p, r in zip(call, res):
             out[p] = r
     return out
@@ -1519,7 +1479,6 @@ def _generate_objects(object_contact, net, objs, num_grasp, rotate, seed, object
 def _ttt_targets(prior):
     """``ttt_prior`` -> what contact.refine_ttt takes: None (every vertex), a ``contact.ContactTargets`` as given, or the path of a
     JSON list of vertex indices (read once per path)."""
-    from . import contact
     if prior is None or isinstance(prior, contact.ContactTargets):
         return prior
     key = os.path.abspath(str(prior))
@@ -1560,47 +1519,19 @@ def main(dataset: str, argv: Optional[Sequence[str]] = None) -> List[str]:
     if args.diversity and (hi - lo) * args.num_grasp > ops.SEGMENT_KMEANS_MAX_M:
         raise RuntimeError(f"--diversity: the pooled statistic takes at most {ops.SEGMENT_KMEANS_MAX_M} grasps per rank "
                            f"(got {(hi - lo) * args.num_grasp})")
-    want_volume = bool(args.volume) or args.max_volume < float("inf")
-    want_parts = bool(args.parts) or args.min_fingers > 0 or bool(args.need_thumb)
-    want_self = bool(args.self_collision) or args.max_self_verts is not None
-    want_mesh = bool(args.mesh_depth) or args.max_mesh_depth < float("inf")
-    if (args.rows_per_call > 0 or args.candidates or args.refine_steps or args.diversity or args.stability or want_volume or want_parts
-            or want_self or want_mesh or args.ttt_steps or args.beam_width or args.object_contact):
-        # grouped calls (best-of-M, push-out, the diversity statistic and the stability proxy always: --rows_per_call 0 is then one
-        # object per call)
+    on = {name: group for name, group in GROUPS.items() if group.wanted(args)}
+    if args.rows_per_call > 0 or on:
+        # grouped calls (with any option group always: --rows_per_call 0 is then one object per call).  A group that is on passes its
+        # keywords under the flags' names and forces its switch: --max_volume alone is volume=True
         rows_per_call, per_object = max(1, args.rows_per_call), (args.candidates or args.num_grasp)
-        selection = dict(candidates=args.candidates, select_by=args.select_by, min_contact=args.min_contact) if args.candidates else {}
-        if args.diverse_pool:
-            selection.update(diverse_pool=args.diverse_pool, diverse_space=args.diverse_space)
-        if args.refine_steps:
-            selection.update(refine_steps=args.refine_steps, refine_push=args.refine_push, refine_pull=args.refine_pull,
-                             min_contact=args.min_contact)
-            if args.refine_spin:
-                selection.update(refine_spin=args.refine_spin)
-            if args.refine_curl:
-                selection.update(refine_curl=args.refine_curl, refine_max_curl=args.refine_max_curl)
-        if args.ttt_steps:
-            selection.update(ttt_steps=args.ttt_steps, ttt_lr=args.ttt_lr, ttt_momentum=args.ttt_momentum, ttt_w_pen=args.ttt_w_pen,
-                             ttt_w_con=args.ttt_w_con, ttt_prior=args.ttt_prior, ttt_keep_best=bool(args.ttt_keep_best))
-        if args.diversity:
-            selection.update(diversity=args.diversity)
-        if args.beam_width:
-            selection.update(beam_width=args.beam_width, beam_poses=args.beam_poses)
-        if args.stability or (args.candidates and args.select_by == "stability"):
-            selection.update(stability=True, max_penetration=args.max_penetration, torque_length=args.torque_length)
-        if want_volume:
-            selection.update(volume=True, volume_res=args.volume_res, max_volume=args.max_volume)
-        if want_parts:
-            selection.update(parts=True, part_threshold=args.part_threshold, part_min_verts=args.part_min_verts,
-                             min_fingers=args.min_fingers, need_thumb=bool(args.need_thumb), hand_parts=args.hand_parts)
-        if want_self:
-            selection.update(self_collision=True, self_reach=args.self_reach, self_margin=args.self_margin, self_seam=args.self_seam,
-                             self_palm=bool(args.self_palm), max_self_verts=args.max_self_verts, hand_parts=args.hand_parts)
-        meshes = []
-        if want_mesh:                                                              # this rank's objects' meshes, read once
-            from . import contact
-            meshes = [contact.load_mesh(p) for p in args.object_meshes[lo:hi]]
-        active = [fig for fig, want in zip(FIGURES, (want_volume, want_parts, want_self, want_mesh)) if want]
+        flags = {"rows_per_call": rows_per_call, **{k: getattr(args, k) for k in ("temperature", "top_k", "log_prob")}}
+        for group in on.values():
+            flags.update({k: getattr(args, k) for k in group.keywords}, **({group.switch: True} if group.switch else {}))
+        flags = {k: bool(v) if k in BOOL_KEYWORDS else v for k, v in flags.items()}    # the 0/1 flags
+        generate_call = generate_with_object_contact if "object_contact" in on else generate_for_objects
+        # this rank's objects' meshes, read once
+        meshes = [contact.load_mesh(p) for p in args.object_meshes[lo:hi]] if _Mesh.key in on else []
+        active = [fig for fig in FIGURES if fig.key in on]
         fig_rows: Dict[str, Dict[int, object]] = {fig.key: {} for fig in active}   # every object's _Figure.rows, for the run summaries
         curl_rows: Dict[int, tuple] = {}                                           # --refine_curl: every object's (curled, reverted) counts
         kept: Dict[int, np.ndarray] = {}                                           # --diversity: every object's kept parameters, on the host
@@ -1609,17 +1540,11 @@ def main(dataset: str, argv: Optional[Sequence[str]] = None) -> List[str]:
         # hold one call's results, not the whole list's
         mine = objs[lo:hi]
         paths: Dict[int, str] = {}
-        generate_call = generate_for_objects
-        if args.object_contact:
-            generate_call = functools.partial(generate_with_object_contact, object_contact_threshold=args.object_contact_threshold)
         for call in plan_calls([o.shape[1] for _, o in mine], per_object, rows_per_call):
             torch.cuda.synchronize(device)
             t0 = time.time()
             outs = generate_call(net, [mine[p][1] for p in call], args.num_grasp, rotate, args.seed, [lo + p for p in call],
-                                 rows_per_call=rows_per_call, temperature=args.temperature, top_k=args.top_k,
-                                 log_prob=bool(args.log_prob), **selection,
-                                 **(dict(object_meshes=[meshes[p] for p in call], mesh_depth=True,
-                                         max_mesh_depth=args.max_mesh_depth) if want_mesh else {}))
+                                 **flags, **({"object_meshes": [meshes[p] for p in call]} if _Mesh.key in on else {}))
             torch.cuda.synchronize(device)
             dt = time.time() - t0
             total_t += dt
