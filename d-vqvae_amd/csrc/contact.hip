@@ -125,16 +125,7 @@ __global__ __launch_bounds__(GRASP_THREADS) void grasp_scores_kernel(const float
     for (long p0 = t; p0 < N; p0 += GRASP_THREADS * GRASP_P) {   // points p0 + k * 256: thread t's points, ascending
         float sx[GRASP_P], sy[GRASP_P], sz[GRASP_P], best[GRASP_P];
         int bi[GRASP_P];
-        bool slow = hand_odd;
-#pragma unroll
-        for (int k = 0; k < GRASP_P; ++k) {
-            const long p = p0 + k * GRASP_THREADS;
-            const bool in = p < N;
-            sx[k] = in ? ob[p * osp] : 0.f;
-            sy[k] = in ? ob[p * osp + osc] : 0.f;
-            sz[k] = in ? ob[p * osp + 2 * osc] : 0.f;
-            slow |= !grasp_finite(sx[k], sy[k], sz[k]);
-        }
+        const bool slow = grasp_points4(ob, osp, osc, N, p0, sx, sy, sz) || hand_odd;
         grasp_scan4(hx, hy, hz, V, slow, sx, sy, sz, best, bi);
 #pragma unroll
         for (int k = 0; k < GRASP_P; ++k) {
@@ -212,24 +203,14 @@ extern "C" int dvq_nn_points(const float* src, int64_t src_batch_stride, int64_t
     DVQ_REQUIRE(B <= 65535LL * 65535LL, "nn_points: B too large");
     hipStream_t st = (hipStream_t)stream;
     static DvqOncePerDevice attr_once;
-    {
-        const hipError_t e = attr_once.run([] {
-            return hipFuncSetAttribute(reinterpret_cast<const void*>(&nn_points_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       NN_MAX_TRG * 12);
-        });
-        if (e != hipSuccess) {
-            dvq_set_error("nn_points: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
-            return DVQ_ELAUNCH;
-        }
-    }
-    for (int64_t b0 = 0; b0 < B; b0 += 65535) {                  // gridDim.y limit
-        const int64_t nb = B - b0 < 65535 ? B - b0 : 65535;
+    DVQ_PROPAGATE(dvq_lds_limit(attr_once, reinterpret_cast<const void*>(&nn_points_kernel), (size_t)NN_MAX_TRG * 12, "nn_points"));
+    dvq_for_row_chunks(B, [&](int64_t b0, int64_t nb) {
         DVQ_PROF("nn_points", 8.0 * nb * N1 * N2, (double)nb * (N1 + N2) * 12 + (double)nb * N1 * 12, st);
         DVQ_LAUNCH(nn_points_kernel, dim3((N1 + 255) / 256, (unsigned)nb), dim3(256), (size_t)N2 * 12, st,
                            src + b0 * src_batch_stride, (long)src_batch_stride, (long)src_point_stride, (long)src_coord_stride,
                            trg + b0 * trg_batch_stride, (long)trg_batch_stride, (long)trg_point_stride, (long)trg_coord_stride,
                            N1, N2, dist + b0 * N1, idx + b0 * N1);
-    }
+    });
     DVQ_CHECK_LAUNCH("nn_points");
     return DVQ_OK;
 }
@@ -240,11 +221,10 @@ extern "C" int dvq_vertex_normals(const float* verts, int64_t B, int V, const in
     if (B == 0) return DVQ_OK;
     DVQ_REQUIRE(verts && faces && vf_off && vf_face && normals, "vertex_normals: null pointer");
     hipStream_t st = (hipStream_t)stream;
-    for (int64_t b0 = 0; b0 < B; b0 += 65535) {
-        const int64_t nb = B - b0 < 65535 ? B - b0 : 65535;
+    dvq_for_row_chunks(B, [&](int64_t b0, int64_t nb) {
         DVQ_LAUNCH(vertex_normals_kernel, dim3((V + 127) / 128, (unsigned)nb), dim3(128), 0, st,
                            verts + b0 * V * 3, faces, vf_off, vf_face, V, normals + b0 * V * 3);
-    }
+    });
     DVQ_CHECK_LAUNCH("vertex_normals");
     return DVQ_OK;
 }
@@ -256,12 +236,11 @@ extern "C" int dvq_interior(const float* normals, const float* hand, int V, cons
     if (B == 0 || N == 0) return DVQ_OK;
     DVQ_REQUIRE(normals && hand && obj && nn_idx && interior, "interior: null pointer");
     hipStream_t st = (hipStream_t)stream;
-    for (int64_t b0 = 0; b0 < B; b0 += 65535) {
-        const int64_t nb = B - b0 < 65535 ? B - b0 : 65535;
+    dvq_for_row_chunks(B, [&](int64_t b0, int64_t nb) {
         DVQ_LAUNCH(interior_kernel, dim3((N + 255) / 256, (unsigned)nb), dim3(256), 0, st, normals + b0 * V * 3,
                            hand + b0 * V * 3, V, obj + b0 * obj_batch_stride, (long)obj_batch_stride, (long)obj_point_stride,
                            (long)obj_coord_stride, nn_idx + b0 * N, N, interior + b0 * N);
-    }
+    });
     DVQ_CHECK_LAUNCH("interior");
     return DVQ_OK;
 }
@@ -280,15 +259,14 @@ extern "C" int dvq_grasp_scores(const float* hand, const int32_t* faces, const i
     static DvqOncePerDevice attr_once;
     DVQ_PROPAGATE(dvq_lds_limit(attr_once, reinterpret_cast<const void*>(&grasp_scores_kernel), grasp_lds_bytes(GRASP_MAX_V, more),
                                 "grasp_scores"));
-    for (int64_t b0 = 0; b0 < B; b0 += 65535) {                  // the grid-dimension limit the neighbouring entry points chunk by
-        const int64_t nb = B - b0 < 65535 ? B - b0 : 65535;
+    dvq_for_row_chunks(B, [&](int64_t b0, int64_t nb) {
         // per (point, vertex) pair 3 subtractions, 1 product, 2 fmas = 8 FLOPs; in: the hand, the cloud and the topology once per
         // grasp; out: 12 B per grasp
         DVQ_PROF("grasp_scores", 8.0 * nb * N * V, (double)nb * ((double)(V + N) * 12 + 12), st);
         DVQ_LAUNCH(grasp_scores_kernel, dim3((unsigned)nb), dim3(GRASP_THREADS), lds, st, hand + b0 * V * 3, faces, vf_off, vf_face, V,
                    obj + b0 * obj_batch_stride, (long)obj_batch_stride, (long)obj_point_stride, (long)obj_coord_stride, N,
                    contact_threshold, penetration + b0, n_interior + b0, n_contact + b0);
-    }
+    });
     DVQ_CHECK_LAUNCH("grasp_scores");
     return DVQ_OK;
 }

@@ -108,6 +108,14 @@ static inline int dvq_lds_limit(DvqOncePerDevice& once, const void* kernel, size
     return DVQ_OK;
 }
 
+// Rows of a batch take a grid dimension; a launch has at most this many.  dvq_for_row_chunks runs launch(b0, nb) over the chunks
+// [b0, b0 + nb) of B rows, ascending: the callable holds the launcher's DVQ_PROF and DVQ_LAUNCH, DVQ_CHECK_LAUNCH follows the call.
+constexpr int64_t DVQ_GRID_ROWS = 65535;
+template <class F>
+static inline void dvq_for_row_chunks(int64_t B, F&& launch) {
+    for (int64_t b0 = 0; b0 < B; b0 += DVQ_GRID_ROWS) launch(b0, B - b0 < DVQ_GRID_ROWS ? B - b0 : DVQ_GRID_ROWS);
+}
+
 static inline bool dvq_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 static inline size_t dvq_round_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 

@@ -386,8 +386,7 @@ extern "C" int dvq_grasp_mesh(const float* hand, int V, const float* mesh_verts,
                 "grasp_mesh: null pointer");
     hipStream_t st = (hipStream_t)stream;
     const int64_t W = (V + 31) / 32;
-    for (int64_t b0 = 0; b0 < B; b0 += 65535) {                  // the grid-dimension limit the neighbouring entry points chunk by
-        const int64_t nb = B - b0 < 65535 ? B - b0 : 65535;
+    dvq_for_row_chunks(B, [&](int64_t b0, int64_t nb) {
         // the work depends on the data (each row's face count lives on the device, pass 2 runs for inside vertices only): reported
         // as 0 FLOPs.  in: the hand twice (the check, the registers); out: the five scalars, the mask and, when asked for, 8 B per vertex
         DVQ_PROF("grasp_mesh", 0.0, (double)nb * (24.0 * V + 20 + 4.0 * W + (vert_d2 ? 4.0 * V : 0) + (vert_face ? 4.0 * V : 0)), st);
@@ -395,7 +394,7 @@ extern "C" int dvq_grasp_mesh(const float* hand, int V, const float* mesh_verts,
                    mesh_faces, n_mf, face_off, (long)O, obj_of_row + b0, R ? R + b0 * 9 : nullptr, t, n_inside + b0, depth + b0,
                    deep_vertex + b0, deep_face + b0, inside_mask + b0 * W, status + b0, vert_d2 ? vert_d2 + b0 * V : nullptr,
                    vert_face ? vert_face + b0 * V : nullptr, err_flag);
-    }
+    });
     DVQ_CHECK_LAUNCH("grasp_mesh");
     return DVQ_OK;
 }

@@ -168,8 +168,7 @@ extern "C" int dvq_grasp_parts(const float* hand, const int32_t* part_of_vertex,
     hipStream_t st = (hipStream_t)stream;
     const int64_t W = (V + 31) / 32;
     const double slots = (double)((V + GP_SLOTS - 1) / GP_SLOTS) * GP_SLOTS;
-    for (int64_t b0 = 0; b0 < B; b0 += 65535) {                  // the grid-dimension limit the neighbouring entry points chunk by
-        const int64_t nb = B - b0 < 65535 ? B - b0 : 65535;
+    dvq_for_row_chunks(B, [&](int64_t b0, int64_t nb) {
         // per (vertex slot, point) pair 8 FLOPs as in grasp_scores; in: the hand twice (the check, the registers), the cloud once per
         // pass of 1024 vertices; out: the parts, the mask and, when asked for, 8 B per vertex
         DVQ_PROF("grasp_parts", 8.0 * nb * N * slots,
@@ -179,7 +178,7 @@ extern "C" int dvq_grasp_parts(const float* hand, const int32_t* part_of_vertex,
                    obj + b0 * obj_batch_stride, (long)obj_batch_stride, (long)obj_point_stride, (long)obj_coord_stride, N,
                    contact_threshold, part_min + b0 * P, part_count + b0 * P, mask + b0 * W, status + b0,
                    vert_dist ? vert_dist + b0 * V : nullptr, vert_idx ? vert_idx + b0 * V : nullptr);
-    }
+    });
     DVQ_CHECK_LAUNCH("grasp_parts");
     return DVQ_OK;
 }

@@ -430,8 +430,7 @@ int gr_launch(const char* what, double bytes, const float* hand, const int32_t* 
     static DvqOncePerDevice attr_once;                           // one per level
     DVQ_PROPAGATE(dvq_lds_limit(attr_once, reinterpret_cast<const void*>(&grasp_refine_kernel<LEVEL>),
                                 grasp_lds_bytes(GRASP_MAX_V, gr_lds_floats(LEVEL)), what));
-    for (int64_t b0 = 0; b0 < B; b0 += 65535) {                  // the grid-dimension limit the neighbouring entry points chunk by
-        const int64_t nb = B - b0 < 65535 ? B - b0 : 65535;
+    dvq_for_row_chunks(B, [&](int64_t b0, int64_t nb) {
         // at most steps + 1 scans of 8 FLOPs per (point, vertex) pair (a grasp may end early)
         DVQ_PROF(what, 8.0 * nb * N * V * (steps + 1), (double)nb * bytes, st);
         DVQ_LAUNCH(grasp_refine_kernel<LEVEL>, dim3((unsigned)nb), dim3(GRASP_THREADS), lds, st, hand + b0 * V * 3, faces, vf_off, vf_face,
@@ -440,7 +439,7 @@ int gr_launch(const char* what, double bytes, const float* hand, const int32_t* 
                    curl, min_w, min_contact, offset + 3 * b0, gr_at(quat, 4 * b0), gr_at(finger_quat, 4 * P * b0), iter + b0,
                    penetration + b0, n_interior + b0, n_contact + b0, gr_at(penetration0, b0), gr_at(n_interior0, b0),
                    gr_at(n_contact0, b0));
-    }
+    });
     DVQ_CHECK_LAUNCH(what);
     return DVQ_OK;
 }

@@ -6,7 +6,7 @@
 // The six planes of grasp_scan.h hold the hand and its normals (its loaders, unchanged); a seventh plane holds every vertex's part bit
 // as a TARGET (1u << label, 0 = no part; the padding up to VP is 0).  Every thread keeps four SOURCE vertices (v0 + t + 256 k) in
 // registers with the word of parts each is tested against (pairs[label]; 0 for a slot beyond V, an unlabelled vertex or one that is
-// no source: such a slot meets no target) and scans the planes sixteen bytes at a time: the loop of grasp_scan4 with one AND and one
+// no source: such a slot meets no target) and scans the planes sixteen bytes at a time: the walk of grasp_scan.h with one AND and one
 // select more per pair -- a target that is not allowed contributes +inf, which is never below the running best.  A hand of more than
 // 1024 vertices takes a second pass.
 //
@@ -15,7 +15,7 @@
 //
 // A row with a non-finite coordinate has no figure: the flag the hand's load sets is final after the barrier that publishes the
 // planes, and the whole workgroup takes the status = 1 exit before the normals and before any scan.  With every coordinate finite no
-// distance is a NaN (a difference may overflow to +-inf, its square is +inf), so the fast loop of grasp_scan4 is the whole scan; a
+// distance is a NaN (a difference may overflow to +-inf, its square is +inf), so the walk of grasp_scan.h is the whole scan; a
 // source all of whose targets lie at +inf takes the lowest target after the scan (the minimum is +inf, attained by every target).
 #include "dvq_internal.h"
 #include "grasp_scan.h"
@@ -43,6 +43,14 @@ __device__ __forceinline__ int src_label(const int* __restrict__ part_of_vertex,
     const int l = part_of_vertex[v];
     return (l >= 0 && l < P && source_of_vertex[v] != 0) ? l : -1;
 }
+
+// The walk's aux: vertex j's part bit as a target.
+struct SelfTargets {
+    const unsigned* tb;
+    __device__ __forceinline__ u32x4 load4(int j) const { return *reinterpret_cast<const u32x4*>(tb + j); }
+    __device__ __forceinline__ unsigned at(u32x4 T, int u) const { return T[u]; }
+    __device__ __forceinline__ unsigned load1(int j) const { return tb[j]; }
+};
 
 // amdgpu_waves_per_eu(6): left to itself the scheduler spends 101 VGPRs on the scan (four waves per SIMD); asked for the siblings' six
 // waves it needs 53 and spills nothing.
@@ -97,8 +105,9 @@ __global__ __launch_bounds__(GRASP_THREADS) __attribute__((amdgpu_waves_per_eu(6
     grasp_normals(faces, vf_off, vf_face, V, t, hx, hy, hz, nx, ny, nz);
     dvq_lds_barrier();
     for (int v0 = 0; v0 < V; v0 += GSELF_SLOTS) {                // sources v0 + t + 256 k: one pass over the planes
-        float sx[GRASP_P], sy[GRASP_P], sz[GRASP_P], best[GRASP_P];
-        int bi[GRASP_P];
+        float sx[GRASP_P], sy[GRASP_P], sz[GRASP_P];
+        f32x4 best;                                              // (vectors, updated by element: grasp_walk4's comment)
+        i32x4 bi;
         unsigned am[GRASP_P];
 #pragma unroll
         for (int k = 0; k < GRASP_P; ++k) {
@@ -113,37 +122,12 @@ __global__ __launch_bounds__(GRASP_THREADS) __attribute__((amdgpu_waves_per_eu(6
             best[k] = INFINITY;
             bi[k] = -1;
         }
-        const int V4 = V & ~3;
-        for (int j = 0; j < V4; j += 4) {
-            const f32x4 X = *reinterpret_cast<const f32x4*>(hx + j);
-            const f32x4 Y = *reinterpret_cast<const f32x4*>(hy + j);
-            const f32x4 Z = *reinterpret_cast<const f32x4*>(hz + j);
-            const u32x4 T = *reinterpret_cast<const u32x4*>(tb + j);
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-#pragma unroll
-                for (int k = 0; k < GRASP_P; ++k) {
-                    const float dx = sx[k] - X[u], dy = sy[k] - Y[u], dz = sz[k] - Z[u];
-                    const float d = fmaf(dz, dz, fmaf(dy, dy, dx * dx));
-                    const float da = (T[u] & am[k]) ? d : INFINITY;
-                    const bool better = da < best[k];
-                    best[k] = better ? da : best[k];
-                    bi[k] = better ? j + u : bi[k];
-                }
-            }
-        }
-        for (int j = V4; j < V; ++j) {
-            const unsigned T = tb[j];
-#pragma unroll
-            for (int k = 0; k < GRASP_P; ++k) {
-                const float dx = sx[k] - hx[j], dy = sy[k] - hy[j], dz = sz[k] - hz[j];
-                const float d = fmaf(dz, dz, fmaf(dy, dy, dx * dx));
-                const float da = (T & am[k]) ? d : INFINITY;
-                const bool better = da < best[k];
-                best[k] = better ? da : best[k];
-                bi[k] = better ? j : bi[k];
-            }
-        }
+        grasp_walk4(hx, hy, hz, V, sx, sy, sz, SelfTargets{tb}, [&](int k, int j, float d, unsigned T) {
+            const float da = (T & am[k]) ? d : INFINITY;
+            const bool better = da < best[k];
+            best[k] = better ? da : best[k];
+            bi[k] = better ? j : bi[k];
+        });
 #pragma unroll
         for (int k = 0; k < GRASP_P; ++k) {
             if (bi[k] < 0 && am[k] != 0u) {                      // every target at +inf (or none in the hand): the lowest target, if any
@@ -216,15 +200,14 @@ extern "C" int dvq_grasp_self(const float* hand, const int32_t* faces, const int
     DVQ_PROPAGATE(dvq_lds_limit(attr_once, reinterpret_cast<const void*>(&grasp_self_kernel),
                                 grasp_lds_bytes(GRASP_MAX_V, gself_more_floats(GRASP_MAX_V)), "grasp_self"));
     const double slots = (double)((V + GSELF_SLOTS - 1) / GSELF_SLOTS) * GSELF_SLOTS;
-    for (int64_t b0 = 0; b0 < B; b0 += 65535) {                  // the grid-dimension limit the neighbouring entry points chunk by
-        const int64_t nb = B - b0 < 65535 ? B - b0 : 65535;
+    dvq_for_row_chunks(B, [&](int64_t b0, int64_t nb) {
         // per (source slot, target) pair 8 FLOPs as in grasp_scores; in: the hand, the labels and the topology once per grasp; out: the
         // parts' four rows, the mask, the status
         DVQ_PROF("grasp_self", 8.0 * nb * V * slots, (double)nb * (12.0 * V + 8.0 * V + 16.0 * P + 4.0 * W + 4), st);
         DVQ_LAUNCH(grasp_self_kernel, dim3((unsigned)nb), dim3(GRASP_THREADS), lds, st, hand + b0 * V * 3, faces, vf_off, vf_face, V,
                    part_of_vertex, source_of_vertex, P, pw, reach2, margin, pen_count + b0 * P, pen_depth + b0 * P, gap_min + b0 * P,
                    pair_bits + b0 * P, mask + b0 * W, status + b0);
-    }
+    });
     DVQ_CHECK_LAUNCH("grasp_self");
     return DVQ_OK;
 }

@@ -6,11 +6,14 @@
 // flag, and a seventh plane of one BYTE per vertex: 1 where the vertex is a contact target (the padding up to VP is 0).  At V = 778,
 // N = 1024 that is 18 720 + 4096 + 3072 + 16 + 780 = 26 684 B: six workgroups share the 160 KB of a CU.
 //
-// Scan phase.  The loop of grasp_scan4 with a second running minimum: a vertex that is no target contributes +inf to it, which is
-// never below the running best (one bit test per vertex, one select more per pair).  Both minima come out of the one pass over the
-// planes.  Every point leaves one word: bits 0..11 the vertex its penetration term pulls on (j_p if inside_p, else 0xfff), bits
-// 12..23 the vertex its contact term pulls on (jc_p if contact_p, else 0xfff).  The three scores and the contact sum are reduced as
-// dvq_grasp_scores reduces (the two counts share one integer: both are at most 16 384).
+// Scan phase.  A COPY of the walk of grasp_scan.h (grasp_walk4: keep the two in step) and of its tile load, with a second running
+// minimum.  Called through the helpers the kernel gives the same bits and the same scan and gather loops, but its launch with the
+// gradient measured 0.6 - 0.7 % slower at N = 3000 in two sessions and the listing does not say why ("The walk against the
+// parent, measured"); with this text the kernel's listing is the one it had.  A vertex that is no target contributes +inf to the
+// second minimum, which is never below the running best (one bit test per vertex, one select more per pair).  Both minima come out
+// of the one pass over the planes.  Every point leaves one word: bits 0..11 the vertex its penetration term pulls on (j_p if
+// inside_p, else 0xfff), bits 12..23 the vertex its contact term pulls on (jc_p if contact_p, else 0xfff).  The three scores and
+// the contact sum are reduced as dvq_grasp_scores reduces (the two counts share one integer: both are at most 16 384).
 //
 // Gather phase (only with grad_hand).  Thread t owns the vertices t, t + 256, ...; it walks the words in ascending p -- every lane
 // reads the same address, a broadcast -- and adds hand[v] - obj[p] for the points that name one of its vertices: two compares per
@@ -83,7 +86,7 @@ __global__ __launch_bounds__(GRASP_THREADS) __attribute__((amdgpu_waves_per_eu(6
             bic[k] = -1;
         }
         if (!slow) {
-            // grasp_scan4's fast loop (every coordinate finite: no distance is NaN) with the target-restricted minimum beside it
+            // grasp_walk4's two loops (every coordinate finite: no distance is NaN) with the target-restricted minimum beside them
 #pragma unroll
             for (int k = 0; k < GRASP_P; ++k) {
                 best[k] = INFINITY;
@@ -259,8 +262,7 @@ extern "C" int dvq_grasp_ttt(const float* hand, const int32_t* faces, const int3
     DVQ_PROPAGATE(dvq_lds_limit(attr_once, reinterpret_cast<const void*>(&grasp_ttt_kernel), gttt_lds_bytes(GRASP_MAX_V, GTTT_MAX_N),
                                 "grasp_ttt"));
     const double walks = grad_hand != nullptr ? (double)((V + GTTT_SLOTS - 1) / GTTT_SLOTS) : 0.0;
-    for (int64_t b0 = 0; b0 < B; b0 += 65535) {                  // the grid-dimension limit the neighbouring entry points chunk by
-        const int64_t nb = B - b0 < 65535 ? B - b0 : 65535;
+    dvq_for_row_chunks(B, [&](int64_t b0, int64_t nb) {
         // per (point, vertex) pair the 8 FLOPs of grasp_scores (the second minimum is compares and selects); in: the hand, the cloud
         // and the topology once per grasp (the cloud's hit points a second time, from cache); out: 16 B and the gradient per grasp
         DVQ_PROF("grasp_ttt", 8.0 * nb * N * V, (double)nb * ((double)(V + N) * 12 + 16 + walks * 12.0 * V), st);
@@ -268,7 +270,7 @@ extern "C" int dvq_grasp_ttt(const float* hand, const int32_t* faces, const int3
                    obj + b0 * obj_batch_stride, (long)obj_batch_stride, (long)obj_point_stride, (long)obj_coord_stride, N,
                    contact_threshold, target_of_vertex, w_pen ? w_pen + b0 : nullptr, w_con ? w_con + b0 : nullptr, mean_contact,
                    penetration + b0, contact_sum + b0, n_interior + b0, n_contact + b0, grad_hand ? grad_hand + b0 * V * 3 : nullptr);
-    }
+    });
     DVQ_CHECK_LAUNCH("grasp_ttt");
     return DVQ_OK;
 }

@@ -375,8 +375,7 @@ extern "C" int dvq_grasp_volume(const float* hand, int V, const int32_t* faces, 
     DVQ_REQUIRE((reinterpret_cast<uintptr_t>(planes) & 15) == 0, "grasp_volume: planes must be 16-byte aligned");
     hipStream_t st = (hipStream_t)stream;
     const size_t lds = gv_lds_bytes(V, L);                                 // <= 49 KB: below the default limit, no attribute to set
-    for (int64_t b0 = 0; b0 < B; b0 += 65535) {                            // the grid-dimension limit the neighbouring entry points chunk by
-        const int64_t nb = B - b0 < 65535 ? B - b0 : 65535;
+    dvq_for_row_chunks(B, [&](int64_t b0, int64_t nb) {
         // the work depends on the data (the box, the hull's planes, how much of the box the hull meets): only the depth's part is
         // known here, 8 FLOPs per (vertex, plane) pair with the plane count unknown to the host -- reported as 0 FLOPs.  in: the hand;
         // out: 12 B per grasp
@@ -384,7 +383,7 @@ extern "C" int dvq_grasp_volume(const float* hand, int V, const int32_t* faces, 
         DVQ_LAUNCH(grasp_volume_kernel, dim3((unsigned)nb), dim3(GV_THREADS), lds, st, hand + b0 * V * 3, V, faces, F, loop_off, loop_vert,
                    L, n_loop, planes, n_planes, plane_off, (long)O, obj_of_row + b0, R ? R + b0 * 9 : nullptr, t, h, count + b0, depth + b0, status + b0,
                    err_flag);
-    }
+    });
     DVQ_CHECK_LAUNCH("grasp_volume");
     return DVQ_OK;
 }

@@ -77,16 +77,7 @@ __global__ __launch_bounds__(GRASP_THREADS) void grasp_wrench_kernel(const float
     for (long p0 = t; p0 < N; p0 += GRASP_THREADS * GRASP_P) {   // points p0 + k * 256: thread t's points, ascending
         float sx[GRASP_P], sy[GRASP_P], sz[GRASP_P], best[GRASP_P];
         int bi[GRASP_P];
-        bool slow = hand_odd;
-#pragma unroll
-        for (int k = 0; k < GRASP_P; ++k) {
-            const long p = p0 + k * GRASP_THREADS;
-            const bool in = p < N;
-            sx[k] = in ? ob[p * osp] : 0.f;
-            sy[k] = in ? ob[p * osp + osc] : 0.f;
-            sz[k] = in ? ob[p * osp + 2 * osc] : 0.f;
-            slow |= !grasp_finite(sx[k], sy[k], sz[k]);
-        }
+        const bool slow = grasp_points4(ob, osp, osc, N, p0, sx, sy, sz) || hand_odd;
         grasp_scan4(hx, hy, hz, V, slow, sx, sy, sz, best, bi);
 #pragma unroll
         for (int k = 0; k < GRASP_P; ++k) {
@@ -169,8 +160,7 @@ extern "C" int dvq_grasp_wrench(const float* hand, const int32_t* faces, const i
     static DvqOncePerDevice attr_once;
     DVQ_PROPAGATE(dvq_lds_limit(attr_once, reinterpret_cast<const void*>(&grasp_wrench_kernel), (size_t)(gw_region(GRASP_MAX_V) + GW_TAIL) * 4,
                                 "grasp_wrench"));
-    for (int64_t b0 = 0; b0 < B; b0 += 65535) {                  // the grid-dimension limit the neighbouring entry points chunk by
-        const int64_t nb = B - b0 < 65535 ? B - b0 : 65535;
+    dvq_for_row_chunks(B, [&](int64_t b0, int64_t nb) {
         // per (point, vertex) pair 8 FLOPs as in grasp_scores, plus 3 additions per point for the centre; the work on the contact
         // points (at most 63 FLOPs each) depends on the data and is not counted.  in: the hand and the topology once, the cloud twice
         // (the centre's pass and the scan); out: 12 + 12 + 108 + 4 B per grasp
@@ -179,7 +169,7 @@ extern "C" int dvq_grasp_wrench(const float* hand, const int32_t* faces, const i
                    obj + b0 * obj_batch_stride, (long)obj_batch_stride, (long)obj_point_stride, (long)obj_coord_stride, N,
                    contact_threshold, inv_length, penetration + b0, n_interior + b0, n_contact + b0, centre + 3 * b0,
                    sums + GW_SUMS * b0, key + b0);
-    }
+    });
     DVQ_CHECK_LAUNCH("grasp_wrench");
     return DVQ_OK;
 }

@@ -166,8 +166,7 @@ extern "C" int dvq_segment_contact(const float* hand, const int32_t* faces, cons
     DVQ_PROPAGATE(dvq_lds_limit(attr_once, reinterpret_cast<const void*>(&segment_contact_kernel), grasp_lds_bytes(GRASP_MAX_V, SC_MORE),
                                 "segment_contact"));
     const unsigned tiles = (unsigned)(((long)N + SC_TILE - 1) / SC_TILE);
-    for (int64_t o0 = 0; o0 < O; o0 += 65535) {                  // the grid-dimension limit the neighbouring entry points chunk by
-        const int64_t no = O - o0 < 65535 ? O - o0 : 65535;
+    dvq_for_row_chunks(O, [&](int64_t o0, int64_t no) {
         // per (row, point, vertex) 8 FLOPs as in grasp_scores, over the tile's 1024 point slots; in: per tile and row the hand, the
         // topology and the whole cloud (the validity test); out: 16 B per point, 4 B per row
         DVQ_PROF("segment_contact", 8.0 * no * K * (double)tiles * SC_TILE * V,
@@ -175,7 +174,7 @@ extern "C" int dvq_segment_contact(const float* hand, const int32_t* faces, cons
         DVQ_LAUNCH(segment_contact_kernel, dim3(tiles, (unsigned)no), dim3(GRASP_THREADS), lds, st, hand, faces, vf_off, vf_face, V, obj,
                    (long)obj_batch_stride, (long)obj_point_stride, (long)obj_coord_stride, (long)B, N, rows, (long)o0, K,
                    contact_threshold, touch, inside, dmin, near_sum, n_valid, row_status, err);
-    }
+    });
     DVQ_CHECK_LAUNCH("segment_contact");
     return DVQ_OK;
 }

@@ -7,7 +7,11 @@ The references are tests/grasp_score_ref.py, grasp_refine_ref.py and grasp_wrenc
 
 The three levels of the push-out (csrc/grasp_refine.hip: translation, rigid, fingers) are one kernel text, so the two upper levels go
 to the same sizes (``ladder``): the pivot at vertex 0, two fingers that share the rim vertices alternately with weights 1 and 0.5, their
-knuckles at vertices 1 and 2, against tests/grasp_refine_rigid_ref.py and grasp_refine_fingers_ref.py."""
+knuckles at vertices 1 and 2, against tests/grasp_refine_rigid_ref.py and grasp_refine_fingers_ref.py.
+
+dvq_grasp_ttt runs the header's vertex walk with a target flag per vertex (a packed byte plane: a word per four-vertex block, a byte
+per tail vertex), so it goes to the same sizes with every odd vertex a target: at V = 5 the tail vertex is no target, at V = 7 the
+tail holds both kinds.  Against tests/grasp_ttt_ref.py bit for bit, and its three scores against dvq_grasp_scores on the device."""
 import functools
 import hashlib
 
@@ -22,6 +26,7 @@ import grasp_refine_fingers_ref as fingers_ref
 import grasp_refine_ref as refine_ref
 import grasp_refine_rigid_ref as rigid_ref
 import grasp_score_ref as score_ref
+import grasp_ttt_ref as ttt_ref
 import grasp_wrench_ref as wrench_ref
 
 DEV = "cuda:0"
@@ -32,6 +37,7 @@ REFINE = ("offset", "iter") + SCORES
 WRENCH = SCORES + ("centre", "sums", "key")
 RIGID = ("offset", "quat", "iter") + SCORES
 FINGERS = fingers_ref.NAMES
+TTT = ("penetration", "contact_sum", "n_interior", "n_contact", "grad")
 N_FINGERS, MAX_CURL = 2, 0.35
 IDENTITY = np.asarray([1, 0, 0, 0], np.float32)
 
@@ -81,6 +87,19 @@ def ladder(V, N):
     return pivot, vert_part, vert_w, knuckle, want
 
 
+@functools.lru_cache(maxsize=None)
+def ttt_case(V, N):
+    """(targets, the ttt reference's outputs on ``case(V, N)`` with every odd vertex a target): computed once per size, never written to."""
+    hand, faces, obj, _ = case(V, N)
+    targets = np.arange(1, V, 2)
+    with np.errstate(all="ignore"):
+        full = ttt_ref.grasp_ttt(hand, faces, obj, targets, contact_threshold=THR)
+    want = {k: full[k] for k in TTT}
+    for a in [targets] + list(want.values()):
+        a.setflags(write=False)
+    return targets, want
+
+
 def assert_same_bits(got, want, names, what):
     """Every number bit for bit; a NaN is a NaN (its payload is nobody's contract)."""
     for k in names:
@@ -119,6 +138,12 @@ PINNED_LADDER = {
     (5, 257): dict(rigid=[2, 0, 1], fingers=[2, 0, 1]),
     (7, 1025): dict(rigid=[2, 0, 2], fingers=[2, 0, 2]),
 }
+# the ttt reference's counts on the same two sizes with the odd vertices as targets, as they stood when the header's walk was
+# written
+PINNED_TTT = {
+    (5, 257): dict(n_contact=[40, 0, 47], n_interior=[88, 0, 150]),
+    (7, 1025): dict(n_contact=[97, 0, 181], n_interior=[559, 0, 346]),
+}
 
 
 @pytest.mark.parametrize("V,N", sorted(PINNED))
@@ -156,6 +181,27 @@ def test_the_upper_levels_references_reduce_to_the_level_below(V, N):
         assert curled.any(), up["fingers"]["finger_quat"][0]
     if (V, N) in PINNED_LADDER:
         assert dict(rigid=up["rigid"]["iter"].tolist(), fingers=up["fingers"]["iter"].tolist()) == PINNED_LADDER[(V, N)]
+
+
+def assert_the_ttt_case_is_what_it_is_for(V, N):
+    """The ttt reference's scores are the score reference's, rows 1 and 2 have no contact sum and no gradient, and from N = 257 up
+    the finite row has contact and interior points and a gradient to gather."""
+    _, _, _, want = case(V, N)
+    _, ttt = ttt_case(V, N)
+    assert_same_bits(ttt, want["scores"], SCORES, "reference: the ttt's scores")
+    assert np.isnan(ttt["contact_sum"][1:]).all() and np.isnan(ttt["grad"][1:]).all()
+    assert np.isfinite(ttt["contact_sum"][0]) and np.isfinite(ttt["grad"][0]).all()
+    if N >= 257:
+        assert ttt["n_contact"][0] > 0 and ttt["n_interior"][0] > 0 and ttt["grad"][0].any()
+
+
+@pytest.mark.parametrize("V,N", SIZES)
+def test_the_ttt_reference_on_the_seam_sizes(V, N):
+    targets, ttt = ttt_case(V, N)
+    assert targets.tolist() == {3: [1], 5: [1, 3], 7: [1, 3, 5]}[V]       # V = 5: the tail vertex 4 is none; V = 7: of the tail 4, 5, 6 one is
+    assert_the_ttt_case_is_what_it_is_for(V, N)
+    if (V, N) in PINNED_TTT:
+        assert dict(n_contact=ttt["n_contact"].tolist(), n_interior=ttt["n_interior"].tolist()) == PINNED_TTT[(V, N)]
 
 
 def gpu(a):
@@ -201,3 +247,20 @@ def test_the_upper_levels_agree_with_their_references_and_the_level_below(V, N):
     assert_same_bits(fingers(0.0), turned, RIGID, "grasp_refine_fingers(curl=0) against grasp_refine_rigid")
     scores = host(SCORES, ops.grasp_scores(*mesh, cloud, contact_threshold=THR))
     assert_same_bits({k: curled[k + "0"] for k in SCORES}, scores, SCORES, "grasp_refine_fingers' iterate 0 against grasp_scores")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("V,N", SIZES)
+def test_the_ttt_kernel_agrees_with_its_reference_and_with_grasp_scores(V, N):
+    hand, faces, obj, _ = case(V, N)
+    targets, want = ttt_case(V, N)
+    assert_the_ttt_case_is_what_it_is_for(V, N)
+    topo = contact.HandTopology(faces, V, DEV)
+    args = (gpu(hand), topo.faces, topo.vf_off, topo.vf_face, gpu(obj))
+    host = lambda names, out: dict(zip(names, (x.cpu().numpy() for x in out)))
+    flags = contact.ContactTargets(targets, n_verts=V).on(DEV)
+    got = host(TTT, ops.grasp_ttt(*args, flags, want_grad=True, contact_threshold=THR))
+    scores = host(SCORES, ops.grasp_scores(*args, contact_threshold=THR))
+    assert_same_bits(got, want, TTT, "grasp_ttt")
+    assert_same_bits(got, scores, SCORES, "grasp_ttt's scores against grasp_scores")
+    assert np.isnan(got["contact_sum"][1:]).all() and np.isnan(got["grad"][1:]).all()

@@ -304,10 +304,10 @@ def both(hand, faces, labels, source, P, pairs, reach2=REACH * REACH, margin=MAR
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("V", [5, 6, 7, 33, 64, 65])
+@pytest.mark.parametrize("V", [4, 5, 6, 7, 33, 64, 65])
 def test_grasp_self_equals_the_reference_bit_for_bit(V):
-    """V = 5, 6, 7: the tail loop behind the sixteen-byte reads and the padding of the one mask word; 33, 64, 65: a second mask word,
-    a whole wave's ballot and one vertex past it."""
+    """V = 4: one whole sixteen-byte block and no tail; 5, 6, 7: the tail behind the sixteen-byte reads and the padding of the one mask
+    word; 33, 64, 65: a second mask word, a whole wave's ballot and one vertex past it."""
     P = 3
     hand, faces, labels = scene(f"small{V}", 3, V, P)
     got, want = both(hand, faces, labels, np.ones(V), P, ring_pairs(P), what=f"V={V}")
