@@ -175,6 +175,9 @@ SIGNATURES = {
     "dvq_segment_contact": (C.c_int, [c_f32p, c_i32p, c_i32p, c_i32p, C.c_int, c_f32p, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
                                       C.c_int, c_i64p, C.c_int64, C.c_int, C.c_float, c_i32p, c_i32p, c_f32p, c_f32p, c_i32p, c_i32p,
                                       c_i32p, c_stream]),
+    "dvq_mesh_sample": (C.c_int, [c_f32p, C.c_int, c_i32p, c_i32p, C.c_int, c_i32p, C.c_int64, C.c_int, C.c_uint64, c_i64p, C.c_void_p,
+                                  c_f32p, c_i32p, c_i32p, c_i32p, c_stream]),
+    "dvq_cloud_fps": (C.c_int, [c_f32p, C.c_int64, C.c_int, C.c_int, c_i32p, c_f32p, c_i32p, c_stream]),
     "dvq_comm_available": (C.c_int, []),
     "dvq_comm_unique_id": (C.c_int, [C.c_void_p, C.c_size_t]),
     "dvq_comm_init": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),

@@ -609,6 +609,37 @@ def load_mesh(path):
     return verts, faces
 
 
+def sample_clouds(meshes, n_points, seed, object_indices, even=1, device=None):
+    """Point clouds of a call's meshes, made on the device: ``meshes`` an ``ObjectMeshes``, ``object_indices`` every object's GLOBAL
+    index (with ``seed`` and the sample index it fixes a draw, whatever else shares the call) -> ``points`` [O,n_points,3] f32 and
+    ``face`` [O,n_points] i32 (the local face each point lies on).  ``even`` = 1: the first ``n_points`` area-weighted samples of
+    ``ops.mesh_sample`` (the definition is in include/dvq.h under dvq_mesh_sample: the library's own Philox stream, NOT trimesh's).
+    ``even`` = F > 1: F * n_points samples (at most ``ops.CLOUD_FPS_MAX_P``), of which ``ops.cloud_fps`` keeps the n_points most
+    spread-out, in pick order from sample 0.  Raises on an object without a face with area (or with a range out of bounds), naming it."""
+    if not isinstance(meshes, ObjectMeshes):
+        raise RuntimeError("sample_clouds: meshes must be an ObjectMeshes")
+    n, F, ids = int(n_points), int(even), [int(i) for i in object_indices]
+    if len(ids) != meshes.n_objects:
+        raise RuntimeError(f"sample_clouds: object_indices must hold one index per mesh (got {len(ids)} for {meshes.n_objects})")
+    if n < 1 or F < 1 or n * F > (ops.CLOUD_FPS_MAX_P if F > 1 else ops.MESH_SAMPLE_MAX_S):
+        raise RuntimeError(f"sample_clouds: need n_points >= 1, even >= 1 and n_points * even <= {ops.CLOUD_FPS_MAX_P} where even > 1 "
+                           f"(<= {ops.MESH_SAMPLE_MAX_S} samples otherwise; got n_points={n} even={F})")
+    device = torch.device("cuda" if device is None else device)
+    verts, vert_off, faces, face_off = meshes.on(device)
+    stream_ids = torch.tensor(ids, dtype=torch.int64, device=device)
+    points, face, status, _ = ops.mesh_sample(verts, vert_off, faces, face_off, n * F, int(seed), stream_ids)
+    if F > 1:
+        sel, _, fps_status = ops.cloud_fps(points, n)
+        status = torch.maximum(status, fps_status)
+        sel = sel.clamp_(min=0).long()                                           # (a refused pool's -1: the status raises below)
+        points, face = torch.gather(points, 1, sel[:, :, None].expand(-1, -1, 3)), torch.gather(face, 1, sel)
+    bad = torch.nonzero(status).flatten().tolist()
+    if bad:
+        raise RuntimeError(f"sample_clouds: object {bad[0]} (global index {ids[bad[0]]}) has no face with area, or a coordinate that "
+                           f"is not finite (status {int(status[bad[0]])})")
+    return points.contiguous(), face.contiguous()
+
+
 def _guard_class(no_figure, poor):
     """int32 [B] for ``torch.maximum`` with the class of ``select_keys``, from two boolean [B]: 2 where the row has no figure, else 1
     where it is poor, else 0."""

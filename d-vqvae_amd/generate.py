@@ -170,7 +170,8 @@ def build_parser(dataset: str) -> argparse.ArgumentParser:
     p.add_argument("--object_meshes", nargs="*", default=[],
                    help="the objects' triangle meshes, one per --objects file in the same order and in the cloud's own frame: .npz "
                         "(verts [n,3], faces [m,3]) or a Wavefront .obj of v / f lines; at most "
-                        f"{ops.GRASP_MESH_MAX_FACES} faces each (decimate larger ones); what --mesh_depth and --max_mesh_depth test against")
+                        f"{ops.GRASP_MESH_MAX_FACES} faces each (decimate larger ones); what --mesh_depth and --max_mesh_depth test against "
+                        "and what --mesh_points samples the clouds from (then there are no --objects files)")
     p.add_argument("--mesh_depth", type=int, default=0,
                    help="1: every grasp's JSON gains \"mesh_depth\" (cm) and \"mesh_interior\": the hand vertices inside the object's MESH "
                         "(a +z ray, watertight at edges and vertices) and the largest distance of one of them to its surface -- the "
@@ -182,6 +183,17 @@ def build_parser(dataset: str) -> argparse.ArgumentParser:
                    help="best-of-M: candidates whose mesh depth exceeds this many cm rank after all others that touch the object (the "
                         "class --max_penetration uses), whatever --select_by ranks by; needs --candidates and --object_meshes "
                         "(default: no guard)")
+    p.add_argument("--mesh_points", type=int, default=0,
+                   help="make every object's cloud from its mesh, on the device, instead of reading --objects: this many area-weighted "
+                        "random points on the surface of each --object_meshes file (0 = off; the reference samples 3000 with trimesh). "
+                        "The draws are the library's own keyed stream (seed, the object's global index, the sample index), NOT "
+                        "trimesh's; objects are named by the mesh files' stems and every cloud is written to <out_dir>/obj_cloud_<name>.npy "
+                        "([N,3] float32: the file --object_contact's point indices refer to); excludes --objects")
+    p.add_argument("--mesh_points_even", type=int, default=1,
+                   help="--mesh_points: above 1, draw mesh_points_even times as many samples and keep the mesh_points most spread-out "
+                        "(farthest-point order from sample 0, on the device), so that the point-counting figures do not carry the "
+                        f"sampling's clumps and holes; mesh_points * mesh_points_even <= {ops.CLOUD_FPS_MAX_P}; 1 = the samples as drawn; "
+                        "effect on grasp quality not measured")
     p.add_argument("--refine_push", type=float, default=1.0, help="--refine_steps: step factor on the mean pull vector of the interior points")
     p.add_argument("--refine_pull", type=float, default=0.25,
                    help="--refine_steps: step factor on the mean pull vector of the points within 2 cm outside the hand")
@@ -1241,7 +1253,7 @@ RULES = (
     _rule("max_mesh_depth", lambda o: o.max_mesh_depth >= 0.0, "must be >= 0", "mesh"),
     *(_rule(" ".join(fig.limits), lambda o, fig=fig: not fig.limited(o) or bool(o.candidates),
             f"needs $candidates (a guard on the ranking of candidates; ${fig.switch} alone writes the figures)") for fig in FIGURES),
-    _rule("object_meshes", lambda o: not o.object_meshes or len(o.object_meshes) == len(o.objects),
+    _rule("object_meshes", lambda o: not o.object_meshes or bool(o.mesh_points) or len(o.object_meshes) == len(o.objects),
           "needs one mesh per $objects file, in the same order", only="cli"),
     _rule("mesh_depth max_mesh_depth", lambda o: not _Mesh.wanted(o) or bool(o.object_meshes),
           "need $object_meshes (the surfaces they test against)", only="cli"),
@@ -1257,6 +1269,18 @@ RULES = (
           "times $beam_poses must equal $candidates or, without it, $num_grasp"),
     _rule("beam_width", lambda o: not o.beam_width or (o.temperature == 1.0 and o.top_k == 0),
           "excludes $temperature and $top_k: a beam search draws nothing"),
+    # (new rules go to the END of the table: the tests name a rule by its position)
+    _rule("mesh_points", lambda o: 0 <= o.mesh_points <= ops.MESH_SAMPLE_MAX_S, f"must lie between 0 and {ops.MESH_SAMPLE_MAX_S}", only="cli"),
+    _rule("mesh_points_even", lambda o: o.mesh_points_even >= 1, "must be at least 1", only="cli"),
+    _rule("mesh_points", lambda o: o.mesh_points_even <= 1 or o.mesh_points * o.mesh_points_even <= ops.CLOUD_FPS_MAX_P,
+          f"times $mesh_points_even may be at most {ops.CLOUD_FPS_MAX_P} where $mesh_points_even is above 1 (the pool the even "
+          "subsampling holds in registers)", only="cli"),
+    _rule("mesh_points mesh_points_even", lambda o: not o.mesh_points or bool(o.object_meshes),
+          "need $object_meshes (the surfaces the clouds are sampled from)", only="cli"),
+    _rule("mesh_points", lambda o: not o.mesh_points or not o.objects,
+          "excludes $objects: the clouds come from $object_meshes", only="cli"),
+    _rule("mesh_points_even", lambda o: o.mesh_points_even == 1 or bool(o.mesh_points),
+          "needs $mesh_points (it thins the cloud sampled from the mesh)", only="cli"),
 )
 
 
@@ -1496,6 +1520,20 @@ def _write_summary(out_dir: str, stem: str, rank: int, world: int, stat: Dict[st
         json.dump(stat, f)
 
 
+def _mesh_clouds(meshes, names: Sequence[str], object_indices: Sequence[int], args, device) -> List[tuple]:
+    """--mesh_points: the (name, [4,N] tensor) of every mesh of this rank, the clouds sampled on the device in one call -- a cloud's
+    bits depend on (seed, its global object index, its mesh) only -- and each written to <out_dir>/obj_cloud_<name>.npy as [N,3]
+    float32: the file that ``--objects`` reads back to the same bits."""
+    points, _ = contact.sample_clouds(contact.ObjectMeshes(meshes), args.mesh_points, args.seed, object_indices, even=args.mesh_points_even,
+                                      device=device)
+    clouds = points.cpu().numpy()
+    out = []
+    for name, cloud in zip(names, clouds):
+        np.save(os.path.join(args.out_dir, f"obj_cloud_{name}.npy"), cloud)
+        out.append((name, object_tensor(cloud.astype(np.float64))))
+    return out
+
+
 def main(dataset: str, argv: Optional[Sequence[str]] = None) -> List[str]:
     args = parse_args(dataset, argv)
     rank, local_rank, world = dist.init()
@@ -1505,12 +1543,20 @@ def main(dataset: str, argv: Optional[Sequence[str]] = None) -> List[str]:
     torch.cuda.set_device(device)
     torch.manual_seed(args.seed)
     net = load_model(args, device)
-    if args.objects:
+    os.makedirs(args.out_dir, exist_ok=True)
+    rank_meshes = None                                                             # --mesh_points: this rank's meshes, read once
+    if args.mesh_points:
+        names = [os.path.splitext(os.path.basename(p))[0] for p in args.object_meshes]
+        lo, hi = dist.shard_range(len(names), rank, world)
+        rank_meshes = [contact.load_mesh(p) for p in args.object_meshes[lo:hi]]
+        objs = [(name, None) for name in names]                                    # (another rank's objects are never looked at)
+        if hi > lo:
+            objs[lo:hi] = _mesh_clouds(rank_meshes, names[lo:hi], list(range(lo, hi)), args, device)
+    elif args.objects:
         objs = [(os.path.splitext(os.path.basename(p))[0], object_tensor(np.load(p).astype(np.float64))) for p in args.objects]
     else:
         clouds = synth.synthetic_clouds(args.num_objects, args.points, seed=args.seed)
         objs = [(f"synthetic_{i}", clouds[i]) for i in range(args.num_objects)]
-    os.makedirs(args.out_dir, exist_ok=True)
     written = []
     lo, hi = dist.shard_range(len(objs), rank, world)                              # objects are independent: shard them
     total_t, total_g = 0.0, 0
@@ -1530,7 +1576,7 @@ def main(dataset: str, argv: Optional[Sequence[str]] = None) -> List[str]:
         flags = {k: bool(v) if k in BOOL_KEYWORDS else v for k, v in flags.items()}    # the 0/1 flags
         generate_call = generate_with_object_contact if "object_contact" in on else generate_for_objects
         # this rank's objects' meshes, read once
-        meshes = [contact.load_mesh(p) for p in args.object_meshes[lo:hi]] if _Mesh.key in on else []
+        meshes = [] if _Mesh.key not in on else rank_meshes if rank_meshes is not None else [contact.load_mesh(p) for p in args.object_meshes[lo:hi]]
         active = [fig for fig in FIGURES if fig.key in on]
         fig_rows: Dict[str, Dict[int, object]] = {fig.key: {} for fig in active}   # every object's _Figure.rows, for the run summaries
         curl_rows: Dict[int, tuple] = {}                                           # --refine_curl: every object's (curled, reverted) counts

@@ -1112,6 +1112,17 @@ GRASP_MESH_MAX_FACES = 262144      # include/dvq.h: DVQ_GRASP_MESH_MAX_FACES, pe
 GRASP_MESH_TILE = 256              # csrc/grasp_mesh.hip: GM_TILE (the faces per LDS tile)
 
 
+def _mesh_tables(what: str, mesh_verts: Tensor, vert_off: Tensor, mesh_faces: Tensor, face_off: Tensor) -> int:
+    """The shapes of the four CSR tables of ``contact.ObjectMeshes`` (their dtypes are checked before) -> O."""
+    if mesh_verts.dim() != 2 or mesh_verts.shape[1] != 3 or not mesh_verts.is_contiguous() or mesh_verts.shape[0] >= 2 ** 31:
+        raise RuntimeError(f"{what}: mesh_verts must be contiguous [n,3]")
+    if mesh_faces.dim() != 2 or mesh_faces.shape[1] != 3 or mesh_faces.shape[0] >= 2 ** 31:
+        raise RuntimeError(f"{what}: mesh_faces must be contiguous [m,3]")
+    if vert_off.dim() != 1 or vert_off.numel() < 1 or face_off.dim() != 1 or face_off.numel() != vert_off.numel():
+        raise RuntimeError(f"{what}: vert_off and face_off must both be [O+1]")
+    return vert_off.numel() - 1
+
+
 def grasp_mesh(hand: Tensor, mesh_verts: Tensor, vert_off: Tensor, mesh_faces: Tensor, face_off: Tensor, obj_of_row: Tensor,
                R: Optional[Tensor] = None, t: Optional[Tensor] = None, want_verts: bool = False, err: Optional[Tensor] = None):
     """The hand vertices inside each row's object MESH (parity along +z, watertight at edges and vertices) and the largest distance
@@ -1127,12 +1138,7 @@ def grasp_mesh(hand: Tensor, mesh_verts: Tensor, vert_off: Tensor, mesh_faces: T
     _f32(mesh_verts, "mesh_verts")
     _int32_tables(what, "vert_off mesh_faces face_off", vert_off, mesh_faces, face_off)
     B, V = _hand(what, hand)
-    if mesh_verts.dim() != 2 or mesh_verts.shape[1] != 3 or not mesh_verts.is_contiguous() or mesh_verts.shape[0] >= 2 ** 31:
-        raise RuntimeError("grasp_mesh: mesh_verts must be contiguous [n,3]")
-    if mesh_faces.dim() != 2 or mesh_faces.shape[1] != 3 or mesh_faces.shape[0] >= 2 ** 31:
-        raise RuntimeError("grasp_mesh: mesh_faces must be contiguous [m,3]")
-    if vert_off.dim() != 1 or vert_off.numel() < 1 or face_off.dim() != 1 or face_off.numel() != vert_off.numel():
-        raise RuntimeError("grasp_mesh: vert_off and face_off must both be [O+1]")
+    _mesh_tables(what, mesh_verts, vert_off, mesh_faces, face_off)
     _obj_of_row(what, obj_of_row, B)
     _frame(what, R, t, B)
     dev = _require_gpu(hand, mesh_verts, vert_off, mesh_faces, face_off, obj_of_row, R, t, err)
@@ -1423,3 +1429,61 @@ def segment_contact(hand: Tensor, faces: Tensor, vf_off: Tensor, vf_face: Tensor
                                       _ptr(rows), O, K, contact_threshold, *map(_ptr, maps), status.data_ptr(), flag.data_ptr(),
                                       _stream(dev)), "dvq_segment_contact")
     return maps + (status,)
+
+
+MESH_SAMPLE_MAX_S = 1 << 20        # include/dvq.h: DVQ_MESH_SAMPLE_MAX_S, samples per object and call
+MESH_SAMPLE_CHUNK = 1024           # csrc/mesh_sample.hip: MS_T (the faces per chunk of the prefix sum)
+CLOUD_FPS_MAX_P = 16384            # include/dvq.h: DVQ_CLOUD_FPS_MAX_P (the pool sits in the registers of one workgroup)
+
+
+def mesh_sample(verts: Tensor, vert_off: Tensor, faces: Tensor, face_off: Tensor, n_samples: int, seed: int, stream_ids: Tensor,
+                err: Optional[Tensor] = None):
+    """Area-weighted random points on each object's triangle mesh (dvq_mesh_sample; the definition is in include/dvq.h): ``(points
+    [O,S,3] f32, face [O,S] i32, status [O] i32, cdf [n_mf] int64)``.  verts [n,3] f32, vert_off int32 [O+1], faces [m,3] int32 (indices
+    local to the object's vertices) and face_off int32 [O+1] (``contact.ObjectMeshes``); ``n_samples`` = S per object; stream_ids int64
+    [O]: every object's GLOBAL index, which with ``seed`` and the sample index fixes a draw whatever shares the call.  ``face`` is the
+    LOCAL face a point lies on; status 0 fine, 1 no face with area (points NaN, face -1), 4 a range out of bounds; ``cdf`` holds the
+    inclusive sums of the integer face weights (the bits of the ABI's uint64).  A face index or an object's range out of bounds (bit 1)
+    or a stream id outside [0, 2^32) (bit 0) raises RuntimeError unless an ``err`` flag tensor is supplied (then the caller checks it)."""
+    what = "mesh_sample"
+    _tensors(what, "verts vert_off faces face_off stream_ids", verts, vert_off, faces, face_off, stream_ids)
+    _f32(verts, "mesh_sample: verts")
+    _int32_tables(what, "vert_off faces face_off", vert_off, faces, face_off)
+    O = _mesh_tables(what, verts, vert_off, faces, face_off)
+    S = int(n_samples)
+    if not 1 <= S <= MESH_SAMPLE_MAX_S:
+        raise RuntimeError(f"mesh_sample: need 1 <= n_samples <= {MESH_SAMPLE_MAX_S} (got {S})")
+    if _i64(stream_ids, "mesh_sample: stream_ids").shape != (O,) or not stream_ids.is_contiguous():
+        raise RuntimeError(f"mesh_sample: stream_ids must be a contiguous int64 [O] = [{O}] tensor")
+    _caller_err(what, err)
+    dev = _require_gpu(verts, vert_off, faces, face_off, stream_ids, err)
+    lib = _lib.load()
+    points, face, status = _outputs(O, dev, (_F, S, 3), (_I, S), (_I,))
+    cdf = torch.zeros(faces.shape[0], dtype=torch.int64, device=dev)       # (an object of status 4 leaves its words unwritten)
+    message = lambda bad: ("mesh_sample: a stream id is outside [0, 2^32)" if bad & 1 else
+                           "mesh_sample: a face index or an object's vertex / face range is out of bounds")
+    with _err_flag(err, dev, message) as flag, torch.cuda.device(dev):
+        check(lib.dvq_mesh_sample(verts.data_ptr(), verts.shape[0], vert_off.data_ptr(), faces.data_ptr(), faces.shape[0],
+                                  face_off.data_ptr(), O, S, int(seed) & 0xFFFFFFFFFFFFFFFF, stream_ids.data_ptr(), cdf.data_ptr(), points.data_ptr(),
+                                  face.data_ptr(), status.data_ptr(), flag.data_ptr(), _stream(dev)), "dvq_mesh_sample")
+    return points, face, status, cdf
+
+
+def cloud_fps(points: Tensor, keep: int):
+    """Farthest-point subsampling of 3-D pools (dvq_cloud_fps; the definition is in include/dvq.h): points [O,P,3] f32 contiguous ->
+    ``(sel [O,keep] i32, gap [O,keep] f32, status [O] i32)``: the pool positions in greedy k-centre order from position 0, each pick's
+    squared distance to the nearest earlier pick (-1 for pick 0), and 1 for a pool with a non-finite coordinate (sel -1, gap -1)."""
+    if not isinstance(points, Tensor):
+        raise RuntimeError("cloud_fps: points must be a tensor")
+    _f32(points, "cloud_fps: points")
+    if points.dim() != 3 or points.shape[2] != 3 or not points.is_contiguous():
+        raise RuntimeError(f"cloud_fps: points must be contiguous [O,P,3] (got {tuple(points.shape)})")
+    O, P, keep = int(points.shape[0]), int(points.shape[1]), int(keep)
+    if not 1 <= keep <= P <= CLOUD_FPS_MAX_P:
+        raise RuntimeError(f"cloud_fps: need 1 <= keep <= P <= {CLOUD_FPS_MAX_P} (got P={P} keep={keep})")
+    dev = _require_gpu(points)
+    lib = _lib.load()
+    outs = _outputs(O, dev, (_I, keep), (_F, keep), (_I,))                             # sel, gap, status
+    with torch.cuda.device(dev):
+        check(lib.dvq_cloud_fps(points.data_ptr(), O, P, keep, *map(_ptr, outs), _stream(dev)), "dvq_cloud_fps")
+    return outs

@@ -44,7 +44,7 @@ typedef enum {
  * working, the version stays): dvq_pixelcnn_sample_ctl, dvq_grasp_scores, dvq_segment_topk, dvq_segment_diverse,
  * dvq_grasp_refine, dvq_segment_kmeans, dvq_grasp_wrench, dvq_grasp_volume, dvq_grasp_parts, dvq_grasp_refine_rigid,
  * dvq_grasp_refine_fingers, dvq_grasp_self, dvq_mano_backward_workspace_bytes, dvq_mano_backward, dvq_grasp_ttt,
- * dvq_pixelcnn_beam_workspace_bytes, dvq_pixelcnn_beam, dvq_grasp_mesh, dvq_segment_contact. */
+ * dvq_pixelcnn_beam_workspace_bytes, dvq_pixelcnn_beam, dvq_grasp_mesh, dvq_segment_contact, dvq_mesh_sample, dvq_cloud_fps. */
 int dvq_abi_version(void);
 const char* dvq_last_error(void);
 /* number of visible HIP devices, or -1; does not create a context */
@@ -935,6 +935,61 @@ int dvq_segment_contact(const float* hand /* [B,V,3] */, const int32_t* faces, c
                         int64_t B, int N, const int64_t* rows /* device [O*K] or NULL */, int64_t O, int K, float contact_threshold,
                         int32_t* touch /* [O,N] */, int32_t* inside /* [O,N] */, float* dmin /* [O,N] */, float* near_sum /* [O,N] */,
                         int32_t* n_valid /* [O] */, int32_t* row_status /* [O*K] */, int32_t* err, dvq_stream_t stream);
+
+/* ------------------------------------------------------------------ object clouds from meshes
+ * Area-weighted random points on the surface of each object's triangle mesh: what the reference's datasets get from trimesh
+ * (dataset/utils_HO3D_FPHA.py:61-73, trimesh.sample.sample_surface(obj_mesh, 3000)), defined here to the bit.  It is NOT trimesh's
+ * stream: that one comes from numpy's global generator and a float64 cumulative sum, which no other library can restate; this is the
+ * same distribution (up to the weight quantisation below) from the library's own keyed Philox generator.  Two launches: one workgroup
+ * per object for the weights and their prefix sum, then one thread per (object, sample).
+ * Inputs: the four CSR tables exactly as dvq_grasp_mesh takes them (mesh_verts [n_mv,3] fp32, vert_off int32 [O+1], mesh_faces
+ * [n_mf,3] int32 LOCAL indices, face_off int32 [O+1]); S samples per object; seed; stream_ids int64 [O]: the object's GLOBAL index,
+ * as the prior's noise keys use it (dvq_exp1_noise_keyed); cdf uint64 [n_mf]: the caller's, the only workspace and also an output.
+ * Everything is fp32; every operation is rounded on its own, nothing is fused; "/" is the IEEE division and sqrtf the IEEE square
+ * root.  Per object o, over its faces f = 0 .. nf-1 (a, b, c = the face's three vertices):
+ *   1. Face weight: e1 = b - a, e2 = c - a per component; n = e1 x e2: n.x = e1.y * e2.z - e1.z * e2.y, n.y = e1.z * e2.x - e1.x *
+ *      e2.z, n.z = e1.x * e2.y - e1.y * e2.x, each product and each difference rounded alone; w = sqrtf((n.x * n.x + n.y * n.y) +
+ *      n.z * n.z) (twice the area); a w that is not finite counts as 0, and so does the w of a face with an index outside the
+ *      object's vertices (bit 1 of *err_flag, as in dvq_grasp_mesh; nothing is read through the index).  amax = the object's largest w.
+ *      q_f = 0 if w == 0, else 1 + (uint32)truncf((w / amax) * 1048575.0f): an integer in [1, 2^20].
+ *      cdf[face_off[o] + f] = q_0 + .. + q_f as uint64 (the inclusive sum in ascending order); T = the last one.
+ *      The weights are INTEGERS on purpose: an integer prefix sum is exact and associative, so any parallel scan gives the same bits.
+ *      The price is a bias: a face is drawn with probability q_f / T in place of w_f / sum w, and q_f is off from its exact share by
+ *      less than one unit, i.e. by less than 2^-20 of the LARGEST face's share, per face.
+ *   2. Draw for sample s = 0 .. S-1: X = Philox4x32-10 of counter (0xFFFFFFF0, s, 0, stream_ids[o]) under the key (seed low, seed
+ *      high): the generator of dvq_exp1_noise.  The tag word keeps these draws apart from the prior's noise, whose first counter word
+ *      is a column quad below 2^31.  t = the high 64 bits of the 128-bit product ((X0 << 32) | X1) * T, so 0 <= t < T; the face is the
+ *      smallest f with cdf[f] > t.  A face with q_f = 0 is never drawn.
+ *   3. Point: r1 = ((float)(X2 >> 8) + 0.5f) * 2^-24, r2 likewise from X3; if r1 + r2 > 1.0f then r1 = 1.0f - r1 and r2 = 1.0f - r2
+ *      (trimesh's fold of the unit square onto the triangle); p = (a + r1 * e1) + r2 * e2 per component.
+ *   4. status[o], the first that applies: 4 = the object's vertex or face range leaves [0, n_mv] / [0, n_mf] or holds more than
+ *      DVQ_GRASP_MESH_MAX_FACES faces (bit 1 of *err_flag), or stream_ids[o] is outside [0, 2^32) (bit 0): no cdf word of the object is
+ *      written; 1 = T == 0 (no face with area); both give points NaN and face -1.  0 otherwise.
+ * A sample's bits depend on (seed, stream id, s, the object's mesh) only: not on O, not on which objects share the call, not on S.
+ * Outputs: points fp32 [O,S,3]; face int32 [O,S]: the LOCAL face index; status int32 [O]; cdf as above.
+ * O >= 0, 1 <= S <= DVQ_MESH_SAMPLE_MAX_S, O * ceil(S / 256) < 2^31, n_mv >= 0, n_mf >= 0, no null pointer but the arrays of an
+ * empty pool; anything else is DVQ_EINVAL, nothing launched.  (O = 0 returns DVQ_OK before any pointer is looked at.) */
+#define DVQ_MESH_SAMPLE_MAX_S 1048576
+int dvq_mesh_sample(const float* mesh_verts /* [n_mv,3] */, int n_mv, const int32_t* vert_off /* [O+1] */,
+                    const int32_t* mesh_faces /* [n_mf,3] local indices */, int n_mf, const int32_t* face_off /* [O+1] */, int64_t O,
+                    int S, uint64_t seed, const int64_t* stream_ids /* device [O] */, uint64_t* cdf /* [n_mf] */,
+                    float* points /* [O,S,3] */, int32_t* face /* [O,S] */, int32_t* status /* [O] */, int32_t* err_flag,
+                    dvq_stream_t stream);
+/* Farthest-point subsampling of a 3-D pool: the greedy k-centre order of dvq_segment_diverse for point clouds, where that one stops
+ * at 4096 rows and walks a generic D.  One workgroup of 1024 threads per object, the pool in registers, no workspace; nothing depends
+ * on O, on which objects share a call or on scheduling.  New here: the reference uses its random samples as they come.
+ * Inputs: points fp32 [O,P,3] contiguous.  Distance: dx = x_i - x_j (likewise dy, dz), d = ((dx * dx) + (dy * dy)) + (dz * dz), every
+ * operation rounded to fp32 on its own, nothing fused.
+ * Selection: pick 0 is pool position 0; then mind[i] = d(i, pick 0) for every position i.  For r = 1 .. keep-1: pick r = the unpicked
+ *   position of the largest mind, the lowest position among equals; gap[r] = that mind; then mind[i] = d < mind[i] ? d : mind[i] with
+ *   d = d(i, pick r).  gap[0] = -1.0f.  So exact duplicates of a pick (mind 0) come last, in position order; gap[1:] is non-increasing
+ *   and its minimum is the kept set's smallest pairwise distance, bit for bit.
+ * A pool with a coordinate that is not finite: status[o] = 1, sel all -1, gap all -1.0f.  status[o] = 0 otherwise.
+ * Outputs: sel int32 [O,keep]: pool positions in pick order; gap fp32 [O,keep]; status int32 [O].
+ * O >= 0, 1 <= keep <= P <= DVQ_CLOUD_FPS_MAX_P, no null pointer; anything else is DVQ_EINVAL, nothing launched. */
+#define DVQ_CLOUD_FPS_MAX_P 16384
+int dvq_cloud_fps(const float* points /* [O,P,3] */, int64_t O, int P, int keep, int32_t* sel /* [O,keep] */,
+                  float* gap /* [O,keep] */, int32_t* status /* [O] */, dvq_stream_t stream);
 
 /* ------------------------------------------------------------------ all-gather of the generated MANO parameters (multi-GPU)
  * The batch of objects shards contiguously over R ranks (one process per GPU); the only exchange of the path is
