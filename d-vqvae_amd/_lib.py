@@ -167,6 +167,9 @@ SIGNATURES = {
                                    c_f32p, C.c_int64, C.c_float, c_i32p, c_f32p, c_i32p, c_i32p, c_stream]),
     "dvq_grasp_mesh": (C.c_int, [c_f32p, C.c_int, c_f32p, C.c_int, c_i32p, c_i32p, C.c_int, c_i32p, C.c_int64, c_i64p, c_f32p, c_f32p,
                                  C.c_int64, c_i32p, c_f32p, c_i32p, c_i32p, c_i32p, c_i32p, c_f32p, c_i32p, c_i32p, c_stream]),
+    "dvq_grasp_mesh_volume": (C.c_int, [c_f32p, C.c_int, c_i32p, C.c_int, c_i32p, c_i32p, C.c_int, C.c_int, c_f32p, C.c_int, c_i32p, c_i32p,
+                                        C.c_int, c_i32p, C.c_int64, c_i64p, c_f32p, c_f32p, C.c_int64, C.c_float, c_i32p, c_i32p, c_i32p,
+                                        c_stream]),
     "dvq_segment_topk": (C.c_int, [c_i32p, c_f32p, C.c_int64, C.c_int, C.c_int, c_i64p, c_stream]),
     "dvq_segment_diverse": (C.c_int, [c_f32p, C.c_int64, C.c_int, c_i64p, C.c_int64, C.c_int, C.c_int, C.c_int, c_i64p, c_i32p, c_f32p,
                                       c_i32p, c_stream]),

@@ -674,6 +674,29 @@ def grasp_mesh(meshes, hand_xyz, obj_of_row, R=None, t=None, want_verts=False, e
     return res
 
 
+def grasp_mesh_volume(topology, meshes, hand_xyz, obj_of_row, R=None, t=None, res=0.001, err=None):
+    """Penetration volume against the object's MESH from ONE fused kernel (ops.grasp_mesh_volume; the definition is in include/dvq.h
+    under dvq_grasp_mesh_volume): the hand mesh of ``topology`` sealed at its open boundary (``seal_faces``) against the closed
+    triangle mesh of each row's object (``meshes`` an ``ObjectMeshes`` in the clouds' own frame), on a lattice of spacing ``res``
+    metres in the object's own frame (``R`` [B,3,3], ``t`` [3]: what ``ops.transform_clouds`` got, None for objects in place).  Returns
+    ``count`` [B] i32 (voxels in both; -1 = no figure) and ``status`` [B] i32 (0 fine, 1 no voxel of the hand's box is in the object or
+    the object has no face, 2 the box has more than 1024 cells on an axis, 3 a vertex is not finite, 4 the object index or its ranges
+    are out of bounds).  No depth: the depth against the mesh is ``grasp_mesh``'s.  ``volume_stats`` turns the count into cm^3.
+
+    The solid intersection on the object's own lattice -- a finger in the hollow of a cup shares nothing with the cup, where
+    ``grasp_volume``'s hull counts it.  It is NOT the reference's metric/intersect.py figure (trimesh's surface voxels of the object
+    inside the hand), no igl / trimesh run pins parity, and on an open mesh (``meshes.closed[o]`` False) it is undefined."""
+    if not isinstance(meshes, ObjectMeshes):
+        raise RuntimeError("grasp_mesh_volume: meshes must be an ObjectMeshes")
+    if not torch.is_tensor(hand_xyz) or hand_xyz.dim() != 3:
+        raise RuntimeError("grasp_mesh_volume: hand_xyz must be a [B,V,3] tensor")
+    faces, loop_off, loop_vert = topology.sealed()
+    verts, vert_off, mfaces, face_off = meshes.on(hand_xyz.device)
+    count, status = ops.grasp_mesh_volume(hand_xyz.contiguous(), faces, loop_off, loop_vert, verts, vert_off, mfaces, face_off, obj_of_row,
+                                          R, t, res, err=err)
+    return {"count": count, "status": status}
+
+
 def mesh_stats(out):
     """Host side, float64, row by row, from ``grasp_mesh``'s dict (tensors or arrays): ``mesh_depth`` = depth * 100 in cm and
     ``mesh_interior`` = n_inside; two lists, ``None`` where n_inside < 0 (json writes null)."""

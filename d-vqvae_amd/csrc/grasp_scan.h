@@ -13,7 +13,8 @@
 //     with the gradient measured slower: DESIGN.md);
 //   grasp_self_kernel: the planes, the hand load, the normals; the walk with a part word per vertex for its masked minimum;
 //   grasp_parts_kernel: grasp_scan4 with a tile of object points as the planes and the hand's vertices as the points;
-//   grasp_volume_kernel: the hand load; grasp_mesh_kernel: GRASP_THREADS, GRASP_P and GRASP_MAX_V.
+//   grasp_volume_kernel, grasp_mesh_volume_kernel: the hand load (the rest of what they share is grasp_raster.h);
+//   grasp_mesh_kernel: GRASP_THREADS, GRASP_P and GRASP_MAX_V.
 //
 // No helper contains a barrier: where the planes are published is visible in each kernel.
 #pragma once

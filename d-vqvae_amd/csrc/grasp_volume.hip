@@ -2,6 +2,8 @@
 // in ONE kernel, one workgroup of 256 threads per grasp.  The definition is the ABI (include/dvq.h); this file only says how the
 // kernel is laid out.  The count is an integer, so nothing below has to keep an order.
 //
+// The hand's side -- steps 1 - 8: the planes, the box, the tile split, phase R -- is grasp_raster.h's, shared with grasp_mesh_volume.hip.
+//
 // The hand's V + L vertices sit in LDS in the object's frame as x|y|z planes.  The box of cells is walked in tiles of columns.
 // Per tile:
 //   H  every thread takes columns and intersects them with the object's half-spaces (planes from global memory, the same address
@@ -15,45 +17,16 @@
 // LDS: 12 (V + L) + 16 KB of bit words (the box's and the depth's reduction columns borrow them first) + 8 KB of ranges: 33 KB at
 // MANO's 779 vertices (four workgroups per CU), 49 KB at the largest hand.
 #include "dvq_internal.h"
-#include "grasp_scan.h"
+#include "grasp_raster.h"
 
 namespace {
 
-constexpr int GV_THREADS = GRASP_THREADS;   // (the hand load is grasp_scan.h's)
-constexpr int GV_MAX_V = GRASP_MAX_V;
-constexpr int GV_MAX_L = 64;
-constexpr int GV_MAX_F = 8192;
 constexpr int GV_MAX_P = 8192;
-constexpr int GV_MAX_CELLS = 1024;          // per axis of the box
-constexpr int GV_IDX_LIMIT = 4194302;       // |cell index| up to here: (float)i + 0.5f is exact
-constexpr int GV_MASK_WORDS = 4096;         // bit words of a tile
-constexpr int GV_MAX_COLS = 2048;           // columns of a tile
-constexpr int GV_TILE_X = 64;
-constexpr int GV_SMALL = 16;                // ints: flags and the count
 static_assert(7 * GV_THREADS <= GV_MASK_WORDS, "the box's and the depth's reduction columns borrow the bit words");
 
-__host__ __device__ constexpr int gv_vp(int V, int L) { return (V + L + 3) & ~3; }
 __host__ __device__ constexpr size_t gv_lds_bytes(int V, int L) {
     return (size_t)(3 * gv_vp(V, L) + GV_MASK_WORDS + GV_MAX_COLS + GV_SMALL) * 4;
 }
-
-__device__ __forceinline__ float gv_c(int i, float h) { return ((float)i + 0.5f) * h; }
-
-// the number of cells kk in [0, nk) with c(lo + kk) < z (STRICT) or <= z: c is non-decreasing in kk, so a guess and two walks
-template <bool STRICT>
-__device__ __forceinline__ int gv_cells(float z, float h, int lo, int nk) {
-    if (z != z) return 0;
-    const float gf = floorf(z / h - 0.5f) - (float)lo + 1.0f;
-    int g = gf < 0.0f ? 0 : (gf > (float)nk ? nk : (int)gf);
-    // (a step or two each; kept scalar: the loop vectoriser would turn them into eight-wide searches with packed-fp32 arithmetic)
-#pragma clang loop vectorize(disable) interleave(disable)
-    while (g < nk && (STRICT ? gv_c(lo + g, h) < z : gv_c(lo + g, h) <= z)) ++g;
-#pragma clang loop vectorize(disable) interleave(disable)
-    while (g > 0 && !(STRICT ? gv_c(lo + g - 1, h) < z : gv_c(lo + g - 1, h) <= z)) --g;
-    return g;
-}
-
-__device__ __forceinline__ bool gv_index_ok(float f) { return fabsf(f) <= (float)GV_IDX_LIMIT; }   // false for a NaN
 
 __global__ __launch_bounds__(GV_THREADS) void grasp_volume_kernel(const float* __restrict__ hand, int V, const int32_t* __restrict__ faces,
                                                                   int F, const int32_t* __restrict__ loop_off,
@@ -105,55 +78,10 @@ __global__ __launch_bounds__(GV_THREADS) void grasp_volume_kernel(const float* _
         }
         return;
     }
-    if (t < L) {                                                           // fan centres, in the row's frame
-        int q0 = loop_off[t], q1 = loop_off[t + 1];
-        float sx = 0.0f, sy = 0.0f, sz = 0.0f;
-        if (q0 < 0 || q1 > n_loop) q0 = q1 = 0;                           // offsets outside loop_vert: an empty loop
-        bool bad = q1 <= q0;
-        for (int q = q0; q < q1; ++q) {
-            const int v = loop_vert[q];
-            if ((unsigned)v >= (unsigned)V) {
-                bad = true;
-                continue;
-            }
-            sx += vx[v];
-            sy += vy[v];
-            sz += vz[v];
-        }
-        const float len = (float)(q1 - q0);
-        vx[V + t] = q1 > q0 ? sx / len : 0.0f;
-        vy[V + t] = q1 > q0 ? sy / len : 0.0f;
-        vz[V + t] = q1 > q0 ? sz / len : 0.0f;
-        if (bad) atomicOr(err_flag, 2);
-    }
+    if (t < L) gv_fan_centre(t, loop_off, loop_vert, n_loop, V, vx, vy, vz, err_flag);   // in the row's frame
     dvq_lds_barrier();
     float mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
-    {                                                                      // into the object's frame, each vertex by its owner
-        float r[9], tt[3];
-#pragma unroll
-        for (int i = 0; i < 9; ++i) r[i] = R ? R[b * 9 + i] : 0.0f;
-#pragma unroll
-        for (int i = 0; i < 3; ++i) tt[i] = tr ? tr[i] : 0.0f;
-        for (int i = t; i < VT; i += GV_THREADS) {
-            float x = vx[i], y = vy[i], z = vz[i];
-            if (R) {
-                const float u0 = tr ? x - tt[0] : x, u1 = tr ? y - tt[1] : y, u2 = tr ? z - tt[2] : z;
-                x = fmaf(r[6], u2, fmaf(r[3], u1, r[0] * u0));
-                y = fmaf(r[7], u2, fmaf(r[4], u1, r[1] * u0));
-                z = fmaf(r[8], u2, fmaf(r[5], u1, r[2] * u0));
-                vx[i] = x;
-                vy[i] = y;
-                vz[i] = z;
-            }
-            mn[0] = x < mn[0] ? x : mn[0];
-            mn[1] = y < mn[1] ? y : mn[1];
-            mn[2] = z < mn[2] ? z : mn[2];
-            mx[0] = x > mx[0] ? x : mx[0];
-            mx[1] = y > mx[1] ? y : mx[1];
-            mx[2] = z > mx[2] ? z : mx[2];
-            if (x != x || y != y || z != z) mn[0] = nanf_;               // a NaN from R: the box is refused below
-        }
-    }
+    gv_object_frame(t, b, VT, R, tr, vx, vy, vz, mn, mx);                 // each vertex by its owner
     dvq_lds_barrier();                                                     // every vertex is in place
     float deep = 0.0f;                                                     // depth: thread t's vertices against every plane
     for (int i = t; i < V; i += GV_THREADS) {
@@ -175,13 +103,7 @@ __global__ __launch_bounds__(GV_THREADS) void grasp_volume_kernel(const float* _
     dvq_lds_barrier();
     for (int s = GV_THREADS / 2; s >= 1; s >>= 1) {
         if (t < s) {
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                const float a = red[c * GV_THREADS + t], a2 = red[c * GV_THREADS + t + s];
-                red[c * GV_THREADS + t] = (a2 < a || a2 != a2) ? a2 : a;  // a NaN sticks
-                const float m = red[(3 + c) * GV_THREADS + t], m2 = red[(3 + c) * GV_THREADS + t + s];
-                red[(3 + c) * GV_THREADS + t] = m2 > m ? m2 : m;
-            }
+            gv_reduce_extent(red, t, s);
             const float d = red[6 * GV_THREADS + t], d2 = red[6 * GV_THREADS + t + s];
             red[6 * GV_THREADS + t] = d2 > d ? d2 : d;
         }
@@ -197,15 +119,7 @@ __global__ __launch_bounds__(GV_THREADS) void grasp_volume_kernel(const float* _
         return;
     }
     int lo[3], n[3];
-    bool fits = true;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        const float fl = floorf(red[c * GV_THREADS] / h), fh = floorf(red[(3 + c) * GV_THREADS] / h);
-        const bool ok = gv_index_ok(fl) && gv_index_ok(fh);
-        lo[c] = ok ? (int)fl - 1 : 0;
-        n[c] = ok ? ((int)fh + 1) - lo[c] + 1 : GV_MAX_CELLS + 1;
-        fits &= n[c] <= GV_MAX_CELLS;
-    }
+    const bool fits = gv_box(red, h, lo, n);
     if (!fits) {
         if (t == 0) {
             count[b] = -1;
@@ -215,16 +129,11 @@ __global__ __launch_bounds__(GV_THREADS) void grasp_volume_kernel(const float* _
         return;
     }
     const int nx = n[0], ny = n[1], nk = n[2], ilo = lo[0], jlo = lo[1], klo = lo[2];
-    const int W = (nk + 31) >> 5;                                          // <= 32 bit words per column
-    const int per_tile = GV_MASK_WORDS / W < GV_MAX_COLS ? GV_MASK_WORDS / W : GV_MAX_COLS;   // >= 128
-    const int TX = nx < GV_TILE_X ? nx : GV_TILE_X;
-    const int TY = per_tile / TX < ny ? per_tile / TX : ny;                // >= 1: per_tile >= 128 >= TX
+    const GvTiles tiles = gv_tiles(nx, ny, nk);
+    const int W = tiles.W, TX = tiles.TX, TY = tiles.TY;
     const float zbot = gv_c(klo, h), ztop = gv_c(klo + nk - 1, h);
     int mine = 0, hull_seen = 0, tile = 0;
-    for (int f = t; f < F; f += GV_THREADS) {
-        if ((unsigned)faces[3 * f] >= (unsigned)VT || (unsigned)faces[3 * f + 1] >= (unsigned)VT || (unsigned)faces[3 * f + 2] >= (unsigned)VT)
-            atomicOr(err_flag, 2);
-    }
+    gv_check_faces(t, faces, F, VT, err_flag);
     for (int ty0 = 0; ty0 < ny; ty0 += TY) {
         for (int tx0 = 0; tx0 < nx; tx0 += TX, ++tile) {
             const int tw = nx - tx0 < TX ? nx - tx0 : TX, th = ny - ty0 < TY ? ny - ty0 : TY;
@@ -269,57 +178,8 @@ __global__ __launch_bounds__(GV_THREADS) void grasp_volume_kernel(const float* _
             for (int i = t; i < ncol * W; i += GV_THREADS) mask[i] = 0u;
             dvq_lds_barrier();
             // R: every triangle toggles one bit in each column it covers
-            const int ia = ilo + tx0, ib = ia + tw - 1, ja = jlo + ty0, jb = ja + th - 1;
-            for (int f = t; f < F; f += GV_THREADS) {
-                const int a = faces[3 * f], bb = faces[3 * f + 1], c = faces[3 * f + 2];
-                if ((unsigned)a >= (unsigned)VT || (unsigned)bb >= (unsigned)VT || (unsigned)c >= (unsigned)VT) {
-                    continue;                                              // (reported once, before the tiles)
-                }
-                const float ax = vx[a], ay = vy[a], az = vz[a], bx = vx[bb], by = vy[bb], bz = vz[bb], cx = vx[c], cy = vy[c], cz = vz[c];
-                const float A = (bx - ax) * (cy - ay) - (by - ay) * (cx - ax);
-                if (!(A > 0.0f) && !(A < 0.0f)) continue;
-                const float xmn = fminf(ax, fminf(bx, cx)), xmx = fmaxf(ax, fmaxf(bx, cx));
-                const float ymn = fminf(ay, fminf(by, cy)), ymx = fmaxf(ay, fmaxf(by, cy));
-                int i0 = (int)floorf(xmn / h) - 1, i1 = (int)floorf(xmx / h) + 1;   // inside the box: the box is made of these values
-                int j0 = (int)floorf(ymn / h) - 1, j1 = (int)floorf(ymx / h) + 1;
-                i0 = i0 < ia ? ia : i0;
-                i1 = i1 > ib ? ib : i1;
-                j0 = j0 < ja ? ja : j0;
-                j1 = j1 > jb ? jb : j1;
-                if (i0 > i1 || j0 > j1) continue;
-                // the three edges in canonical direction: e1 of (a,b), e2 of (b,c), e3 of (c,a); rev: the triangle runs Q -> P
-                const bool r1 = a > bb, r2 = bb > c, r3 = c > a;
-                const float p1x = r1 ? bx : ax, p1y = r1 ? by : ay, d1x = r1 ? ax - bx : bx - ax, d1y = r1 ? ay - by : by - ay;
-                const float p2x = r2 ? cx : bx, p2y = r2 ? cy : by, d2x = r2 ? bx - cx : cx - bx, d2y = r2 ? by - cy : cy - by;
-                const float p3x = r3 ? ax : cx, p3y = r3 ? ay : cy, d3x = r3 ? cx - ax : ax - cx, d3y = r3 ? cy - ay : ay - cy;
-                const bool up = A > 0.0f;
-                // what an edge value of exactly 0 counts as: its sign at the column moved by (eps, eps^2)
-                const bool z1 = d1y < 0.0f || (d1y == 0.0f && d1x > 0.0f), z2 = d2y < 0.0f || (d2y == 0.0f && d2x > 0.0f),
-                           z3 = d3y < 0.0f || (d3y == 0.0f && d3x > 0.0f);
-                for (int j = j0; j <= j1; ++j) {
-                    const float y = gv_c(j, h);
-                    if (!(ymn <= y && y <= ymx)) continue;
-                    for (int i = i0; i <= i1; ++i) {
-                        const float x = gv_c(i, h);
-                        if (!(xmn <= x && x <= xmx)) continue;
-                        const int col = (j - ja) * tw + (i - ia);
-                        const int rg = range[col];
-                        if (rg == 0) continue;                             // no cell of the column is in the hull
-                        const float e1 = d1x * (y - p1y) - d1y * (x - p1x);
-                        const float e2 = d2x * (y - p2y) - d2y * (x - p2x);
-                        const float e3 = d3x * (y - p3y) - d3y * (x - p3x);
-                        // the positive side of an edge belongs to the triangle iff (A > 0) != (it runs Q -> P)
-                        const bool s1 = e1 > 0.0f || (e1 == 0.0f && z1), s2 = e2 > 0.0f || (e2 == 0.0f && z2),
-                                   s3 = e3 > 0.0f || (e3 == 0.0f && z3);
-                        if (s1 != (up != r1) || s2 != (up != r2) || s3 != (up != r3)) continue;
-                        if (e1 != e1 || e2 != e2 || e3 != e3) continue;
-                        const float wc = r1 ? -e1 : e1, wa = r2 ? -e2 : e2, wb = r3 ? -e3 : e3;
-                        const float zc = ((wa * az + wb * bz) + wc * cz) / ((wa + wb) + wc);
-                        const int m = gv_cells<true>(zc, h, klo, nk);     // cells 0 .. m-1 lie below the crossing
-                        if (m > 0) atomicXor(&mask[((m - 1) >> 5) * ncol + col], 1u << ((m - 1) & 31));
-                    }
-                }
-            }
+            gv_raster_hand(t, faces, F, VT, vx, vy, vz, h, ilo + tx0, ilo + tx0 + tw - 1, jlo + ty0, jlo + ty0 + th - 1, klo, nk, mask,
+                           [&](int col) { return range[col] != 0; });     // (a column without a cell in the hull takes no bit)
             dvq_lds_barrier();
             // C: suffix parity from the top word down, cut to the hull's cells
             for (int c = t; c < ncol; c += GV_THREADS) {
@@ -329,12 +189,7 @@ __global__ __launch_bounds__(GV_THREADS) void grasp_volume_kernel(const float* _
                 unsigned carry = 0u;
                 for (int w = W - 1; w >= (ka >> 5); --w) {
                     const unsigned v = mask[w * ncol + c];
-                    unsigned s = v;
-                    s ^= s >> 1;
-                    s ^= s >> 2;
-                    s ^= s >> 4;
-                    s ^= s >> 8;
-                    s ^= s >> 16;                                          // bit i = parity of the bits i .. 31
+                    unsigned s = gv_suffix_parity(v);                      // bit i = parity of the bits i .. 31
                     s ^= carry;
                     carry ^= (__popc(v) & 1) ? 0xffffffffu : 0u;
                     const int base = w << 5;

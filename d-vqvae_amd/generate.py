@@ -129,6 +129,14 @@ def build_parser(dataset: str) -> argparse.ArgumentParser:
     p.add_argument("--max_volume", type=float, default=float("inf"),
                    help="best-of-M: candidates whose penetration volume exceeds this many cm^3 rank after all others that touch the object "
                         "(the class --max_penetration uses), whatever --select_by ranks by; needs --candidates (default: no limit)")
+    p.add_argument("--volume_mesh", type=int, default=0,
+                   help="--volume / --max_volume: what the hand's voxels are counted against.  0 = the convex hull of the object's "
+                        "cloud (a lower bound of the reference's figure); 1 = the convex hull of the object's MESH vertices, the "
+                        "reference's geometry (built on the host, the same kernel); 2 = the mesh itself, so that a finger in the hollow "
+                        "of a cup or through a handle shares nothing with the object (one kernel per call): the solid intersection on "
+                        "the object's own lattice, not metric/intersect.py's surface-voxel figure, undefined on an open mesh; "
+                        "\"penetration_depth\" is then null (the depth against the mesh is --mesh_depth's).  1 and 2 need "
+                        "--object_meshes; penetration.json gains \"against\"")
     p.add_argument("--parts", type=int, default=0,
                    help="1: every grasp's JSON gains \"fingers_in_contact\", \"part_contact\" and \"part_dist\" (cm) and every object's "
                         "\"hand_contact_map\": which parts of the hand -- thumb, four fingers, palm -- have vertices within "
@@ -505,6 +513,7 @@ class _Call:
     logp: Optional[torch.Tensor]                # [O*G] where the log-likelihood is written or ranked by
     refined: Optional[Dict[str, torch.Tensor]]  # the push-out's dict
     meshes: object                              # the contact.ObjectMeshes of the call's objects, or None
+    indices: Sequence[int] = ()                 # the objects' global indices, for messages
     figs: Sequence = ()                         # (figure, settings, its launch's device tensors) of the active figures
 
     @property
@@ -584,7 +593,7 @@ def _generate_call(net: GenNet, opt: _Options, objs: Sequence[torch.Tensor], obj
             refined = {k: v for k, v in refined.items() if k != "scores"}
     call = _Call(net=net, objs=objs, G=G, batch=batch, err=err, obj_of_row=obj_of_row, frame=(R_dev, t_dev) if rotate else (None, None),
                  R=R, angles=angles, t=t, params=params, vertices=final.vertices, logp=logp, refined=refined,
-                 meshes=meshes)
+                 meshes=meshes, indices=list(object_indices))
     call.figs = [(fig, s, fig.launch(s, call)) for fig, s in opt.figures]          # after the push-out: the hands of the parameters written
     if opt.candidates:
         return _beam_attach(_ttt_attach(_select_call(opt, call), tuned, G), baux, beam)
@@ -778,6 +787,7 @@ def _share(flags: Sequence[bool]) -> Optional[float]:
 
 
 VOLUME_PIECES = ("count", "depth", "status", "err")  # what a call's volume kernel leaves on the device (_Volume.launch)
+VOLUME_AGAINST = {1: "mesh_hull", 2: "mesh"}         # --volume_mesh: what penetration.json's "against" says (absent at 0: the cloud's hull)
 PARTS_PIECES = ("part_min", "part_count", "mask", "status")     # what a call's parts kernel leaves on the device (contact.grasp_parts)
 SELF_PIECES = ("pen_count", "pen_depth", "gap_min", "pair_bits", "mask", "status")   # what a call's self-collision kernel leaves on the device
 MESH_PIECES = ("n_inside", "depth", "mask", "err")   # what a call's mesh kernel leaves on the device (_Mesh.launch)
@@ -786,7 +796,9 @@ MESH_PIECES = ("n_inside", "depth", "mask", "err")   # what a call's mesh kernel
 class _Volume(_Figure):
     """``--volume`` / ``--max_volume`` (settings ``res``, ``max_volume``): every object's convex hull once, on the host, from its own
     unrotated cloud (contact.hull_planes: scipy), and ONE ``contact.grasp_volume`` over all rows of the call with the call's
-    ``obj_of_row``, ``R`` and ``t``.  Candidates whose voxel count exceeds ``contact.volume_limit`` join class 1 and those without a
+    ``obj_of_row``, ``R`` and ``t``.  ``--volume_mesh`` (setting ``mesh``, present only when it is not 0; the meshes are the call's
+    ``contact.ObjectMeshes``): 1 = the hulls are those of the meshes' vertices, 2 = ONE ``contact.grasp_mesh_volume`` against the meshes
+    themselves, which has no depth (the piece is NaN on the device and null in the JSON).  Candidates whose voxel count exceeds ``contact.volume_limit`` join class 1 and those without a
     figure class 2 (integer comparisons on the device).  The JSON fields are penetration_volume, penetration_depth and volume_voxels
     (contact.volume_stats); null where the kernel gives no figure (count < 0)."""
     key, scores_key, stem, pieces, shown = "volume", "volume_scores", "penetration", VOLUME_PIECES, 3
@@ -798,14 +810,29 @@ class _Volume(_Figure):
 
     @staticmethod
     def settings(o, net):
-        return dict(res=float(o.volume_res), max_volume=float(o.max_volume))
+        mesh = int(getattr(o, "volume_mesh", 0))
+        return dict(res=float(o.volume_res), max_volume=float(o.max_volume), **({"mesh": mesh} if mesh else {}))
 
     @staticmethod
     def launch(s, call):
         dev = call.vertices.device
         topo = _hand_topology(call.net, call.vertices.shape[1], dev)
-        planes, plane_off = contact.pack_planes([contact.hull_planes(o[:3].T.cpu().numpy().astype(np.float64)) for o in call.objs])
         bad = ops.new_err_flag(dev)
+        mesh = s.get("mesh", 0)
+        if mesh == 2:                                                              # against the meshes themselves: no depth
+            out = contact.grasp_mesh_volume(topo, call.meshes, call.vertices, call.obj_of_row, *call.frame, s["res"], err=bad)
+            return {"count": out["count"], "depth": torch.full_like(out["count"], math.nan, dtype=torch.float32), "status": out["status"],
+                    "err": bad}
+        if mesh == 1:                                                              # the hulls of the meshes' vertices: the reference's geometry
+            vo = call.meshes.vert_off
+            hulls = [contact.hull_planes(call.meshes.verts[vo[o]:vo[o + 1]].astype(np.float64)) for o in range(len(call.objs))]
+            for o, hull in enumerate(hulls):
+                if hull.shape[0] > ops.GRASP_VOLUME_MAX_PLANES:
+                    raise RuntimeError(f"generate_for_objects: volume_mesh=1: the hull of the mesh of object {call.indices[o]} has "
+                                       f"{hull.shape[0]} planes, at most {ops.GRASP_VOLUME_MAX_PLANES} fit (decimate the mesh)")
+        else:
+            hulls = [contact.hull_planes(o[:3].T.cpu().numpy().astype(np.float64)) for o in call.objs]
+        planes, plane_off = contact.pack_planes(hulls)
         out = contact.grasp_volume(topo, call.vertices, torch.from_numpy(planes).to(dev), torch.from_numpy(plane_off).to(dev),
                                    call.obj_of_row, *call.frame, s["res"], err=bad)
         return {**out, "err": bad}
@@ -822,8 +849,10 @@ class _Volume(_Figure):
     def lists(s, host):
         count, depth, _, bad = host
         if int(bad[0]) != 0:
-            raise RuntimeError("generate_for_objects: volume: an index of the hand topology or of the hulls is out of range")
+            raise RuntimeError("generate_for_objects: volume: an index of the hand topology, of the hulls or of the meshes is out of range")
         out = contact.volume_stats(count, depth, s["res"])
+        if s.get("mesh", 0) == 2:                                                  # no depth against the mesh: null, never a NaN
+            out["penetration_depth"] = [None] * len(out["penetration_depth"])
         out["volume_voxels"] = [int(k) if k >= 0 else None for k in count]
         return out
 
@@ -836,7 +865,9 @@ class _Volume(_Figure):
         # contact_ratio is the reference's rule, "volume > 0", on the voxel count
         rows = [r for obj in rows for r in obj if r[0] is not None]
         stat = {"res": args.volume_res, "grasps": len(rows), "mean_volume_cm3": _mean([r[1] for r in rows]),
-                "mean_depth_cm": _mean([r[2] for r in rows]), "contact_ratio": _share([r[0] >= 1 for r in rows])}
+                "mean_depth_cm": _mean([r[2] for r in rows if r[2] is not None]), "contact_ratio": _share([r[0] >= 1 for r in rows])}
+        if args.volume_mesh:
+            stat["against"] = VOLUME_AGAINST[args.volume_mesh]
         return stat, (f"penetration volume of {len(rows)} grasps at {args.volume_res} m: mean {stat['mean_volume_cm3']} cm^3, "
                       f"mean depth {stat['mean_depth_cm']} cm, contact ratio {stat['contact_ratio']}")
 
@@ -1201,6 +1232,9 @@ class _Rule:
     only: Optional[str] = None
 
 
+VOLUME_MESH_OPTIONS = (0, 1, 2)   # --volume_mesh: the cloud's hull, the hull of the mesh's vertices, the mesh itself
+
+
 def _rule(names: str, ok, text: str, gate: Optional[str] = None, only: Optional[str] = None) -> _Rule:
     return _Rule(tuple(names.split()), ok, text, gate, only)
 
@@ -1212,6 +1246,16 @@ def _positive(x) -> bool:
 def _not_negative(x) -> bool:
     return 0.0 <= x < math.inf
 
+
+# --volume_mesh.  Marked "cli": the keyword is generate_with_volume_mesh's, not generate_for_objects' (whose keywords are pinned), so
+# the keyword path's table has no such option to look at; _generate_objects applies these same three to it.
+VOLUME_MESH_RULES = (
+    _rule("volume_mesh", lambda o: o.volume_mesh in VOLUME_MESH_OPTIONS, "must be 0, 1 or 2", only="cli"),
+    _rule("volume_mesh", lambda o: not o.volume_mesh or (bool(o.object_meshes) and len(o.object_meshes) == len(getattr(o, "objs", o.object_meshes))),
+          "needs $object_meshes, one per object (the surfaces it counts against)", only="cli"),
+    _rule("volume_mesh", lambda o: not o.volume_mesh or _Volume.wanted(o),
+          "needs $volume or $max_volume (it says what the volume figure is counted against)", only="cli"),
+)
 
 RULES = (
     _rule("candidates", lambda o: not o.candidates or o.candidates >= max(1, o.num_grasp), "must be 0 or at least $num_grasp"),
@@ -1281,6 +1325,7 @@ RULES = (
           "excludes $objects: the clouds come from $object_meshes", only="cli"),
     _rule("mesh_points_even", lambda o: o.mesh_points_even == 1 or bool(o.mesh_points),
           "needs $mesh_points (it thins the cloud sampled from the mesh)", only="cli"),
+    *VOLUME_MESH_RULES,
 )
 
 
@@ -1474,12 +1519,34 @@ def generate_with_object_contact(net: GenNet, objs: Sequence[torch.Tensor], num_
     return _generate_objects(call.arguments, object_contact_threshold)
 
 
-def _generate_objects(keywords, object_contact_threshold: Optional[float] = None) -> List[Dict[str, object]]:
-    """The body of ``generate_for_objects`` -- ``keywords`` are its bound arguments by name -- and of ``generate_with_object_contact``,
-    which adds the threshold.  Every value check (RULES) comes first and sees no more than the values; then the face list, the tables
-    and the files the groups' settings need; then one _Options for all the calls."""
-    o = types.SimpleNamespace(**keywords, object_contact=object_contact_threshold is not None, object_contact_threshold=object_contact_threshold)
-    rule = _broken_rule(o, cli=False)
+def generate_with_volume_mesh(net: GenNet, objs: Sequence[torch.Tensor], num_grasp: int, rotate: bool, seed: int,
+                              object_indices: Sequence[int], volume_mesh: int = 0, object_contact_threshold: Optional[float] = None,
+                              **options) -> List[Dict[str, object]]:
+    """``generate_for_objects(net, objs, num_grasp, rotate, seed, object_indices, **options)`` with the volume figure (``volume=True``
+    or a finite ``max_volume``) counted against the objects' MESHES, ``options["object_meshes"]``: the flag ``--volume_mesh`` under its
+    own name and default.  0: the call without the keyword -- the hull of each object's cloud, the same bytes, no other launch.
+    1: the half-spaces are ``contact.hull_planes`` of each mesh's VERTICES -- the reference's geometry, trimesh.convex.convex_hull of the
+    object mesh -- through the same ``contact.grasp_volume``; a hull with more planes than ``contact.pack_planes`` admits raises, naming
+    the object.  2: ONE ``contact.grasp_mesh_volume`` per call against the meshes themselves, so that a finger in the hollow of a cup or
+    through a handle shares nothing with the object: the solid intersection on the object's own lattice -- not metric/intersect.py's
+    figure (trimesh's surface voxels of the object inside the hand), undefined on an open mesh ("mesh_closed" of ``mesh_depth`` reports
+    it), and with no igl / trimesh run behind it.  The kernel has no depth: ``volume["depth"]`` is NaN and "penetration_depth" null per
+    grasp; ``max_volume`` compares the count as before.  Every call packs its objects' meshes once (``contact.ObjectMeshes``), whether
+    or not ``mesh_depth`` asks for them too.  ``object_contact_threshold``: as ``generate_with_object_contact`` takes it, None for no
+    map.  The results do not depend on ``rows_per_call``.  (A function of its own: the keywords of ``generate_for_objects`` are pinned.)"""
+    call = inspect.signature(generate_for_objects).bind(net, objs, num_grasp, rotate, seed, object_indices, **options)
+    call.apply_defaults()
+    return _generate_objects(call.arguments, object_contact_threshold, volume_mesh)
+
+
+def _generate_objects(keywords, object_contact_threshold: Optional[float] = None, volume_mesh: int = 0) -> List[Dict[str, object]]:
+    """The body of ``generate_for_objects`` -- ``keywords`` are its bound arguments by name -- of ``generate_with_object_contact``,
+    which adds the threshold, and of ``generate_with_volume_mesh``, which adds its option.  Every value check (RULES) comes first and
+    sees no more than the values; then the face list, the tables and the files the groups' settings need; then one _Options for all
+    the calls."""
+    o = types.SimpleNamespace(**keywords, object_contact=object_contact_threshold is not None, object_contact_threshold=object_contact_threshold,
+                              volume_mesh=volume_mesh)
+    rule = _broken_rule(o, cli=False) or next((r for r in VOLUME_MESH_RULES if not r.ok(o)), None)
     if rule is not None:
         raise RuntimeError("generate_for_objects: " + _rule_message(rule, o, cli=False))
     on = {name: group for name, group in GROUPS.items() if group.wanted(o)}
@@ -1493,7 +1560,7 @@ def _generate_objects(keywords, object_contact_threshold: Optional[float] = None
     out: List[Optional[Dict[str, object]]] = [None] * len(o.objs)
     for call in plan_calls([x.shape[1] for x in o.objs], o.candidates or o.num_grasp, o.rows_per_call):
         # the call's objects' meshes, packed and uploaded once per call
-        meshes = contact.ObjectMeshes([o.object_meshes[p] for p in call]) if _Mesh.key in on else None
+        meshes = contact.ObjectMeshes([o.object_meshes[p] for p in call]) if _Mesh.key in on or o.volume_mesh else None
         res = _generate_call(o.net, opt, [o.objs[p] for p in call], [o.object_indices[p] for p in call], meshes)
         for p, r in zip(call, res):
             out[p] = r
@@ -1575,8 +1642,11 @@ def main(dataset: str, argv: Optional[Sequence[str]] = None) -> List[str]:
             flags.update({k: getattr(args, k) for k in group.keywords}, **({group.switch: True} if group.switch else {}))
         flags = {k: bool(v) if k in BOOL_KEYWORDS else v for k, v in flags.items()}    # the 0/1 flags
         generate_call = generate_with_object_contact if "object_contact" in on else generate_for_objects
+        if args.volume_mesh:                                                       # (the threshold, when on, is among the flags)
+            generate_call, flags["volume_mesh"] = generate_with_volume_mesh, args.volume_mesh
+        need_meshes = _Mesh.key in on or bool(args.volume_mesh)
         # this rank's objects' meshes, read once
-        meshes = [] if _Mesh.key not in on else rank_meshes if rank_meshes is not None else [contact.load_mesh(p) for p in args.object_meshes[lo:hi]]
+        meshes = [] if not need_meshes else rank_meshes if rank_meshes is not None else [contact.load_mesh(p) for p in args.object_meshes[lo:hi]]
         active = [fig for fig in FIGURES if fig.key in on]
         fig_rows: Dict[str, Dict[int, object]] = {fig.key: {} for fig in active}   # every object's _Figure.rows, for the run summaries
         curl_rows: Dict[int, tuple] = {}                                           # --refine_curl: every object's (curled, reverted) counts
@@ -1590,7 +1660,7 @@ def main(dataset: str, argv: Optional[Sequence[str]] = None) -> List[str]:
             torch.cuda.synchronize(device)
             t0 = time.time()
             outs = generate_call(net, [mine[p][1] for p in call], args.num_grasp, rotate, args.seed, [lo + p for p in call],
-                                 **flags, **({"object_meshes": [meshes[p] for p in call]} if _Mesh.key in on else {}))
+                                 **flags, **({"object_meshes": [meshes[p] for p in call]} if need_meshes else {}))
             torch.cuda.synchronize(device)
             dt = time.time() - t0
             total_t += dt

@@ -1155,6 +1155,46 @@ def grasp_mesh(hand: Tensor, mesh_verts: Tensor, vert_off: Tensor, mesh_faces: T
     return outs
 
 
+GRASP_MESH_VOLUME_LIST = 2048      # csrc/grasp_mesh_volume.hip: GMV_LIST (the culled faces a grasp keeps in LDS; more: every tile walks all)
+
+
+def grasp_mesh_volume(hand: Tensor, faces: Tensor, loop_off: Tensor, loop_vert: Tensor, mesh_verts: Tensor, vert_off: Tensor,
+                      mesh_faces: Tensor, face_off: Tensor, obj_of_row: Tensor, R: Optional[Tensor] = None, t: Optional[Tensor] = None,
+                      res: float = 0.001, err: Optional[Tensor] = None):
+    """The voxels shared by the sealed hand mesh and each row's object MESH (not its hull: hollows and holes are seen) in one fused
+    kernel (dvq_grasp_mesh_volume; the definition is in include/dvq.h): ``(count [B] i32, status [B] i32)``; no depth -- the depth
+    against the mesh is ``grasp_mesh``'s.  hand, faces, loop_off, loop_vert, R, t and ``res`` as ``grasp_volume`` takes them; mesh_verts,
+    vert_off, mesh_faces, face_off as ``grasp_mesh`` takes them (``contact.ObjectMeshes``); obj_of_row int64 [B].  An object index
+    outside [0, O) raises RuntimeError unless an ``err`` flag tensor is supplied (then the caller checks it: bit 0; bit 1 = an index of
+    the topology, a face index or an object's vertex / face range out of bounds)."""
+    what = "grasp_mesh_volume"
+    _tensors(what, "hand faces loop_off loop_vert mesh_verts vert_off mesh_faces face_off obj_of_row", hand, faces, loop_off, loop_vert,
+             mesh_verts, vert_off, mesh_faces, face_off, obj_of_row)
+    _f32(mesh_verts, "mesh_verts")
+    _int32_tables(what, "faces loop_off loop_vert vert_off mesh_faces face_off", faces, loop_off, loop_vert, vert_off, mesh_faces, face_off)
+    B, V = _hand(what, hand)
+    if faces.dim() != 2 or faces.shape[1] != 3 or faces.shape[0] > GRASP_VOLUME_MAX_F:
+        raise RuntimeError(f"grasp_mesh_volume: faces must be [F,3] with F <= {GRASP_VOLUME_MAX_F} (got {tuple(faces.shape)})")
+    if loop_off.dim() != 1 or not 1 <= loop_off.numel() <= GRASP_VOLUME_MAX_LOOPS + 1 or loop_vert.dim() != 1:
+        raise RuntimeError(f"grasp_mesh_volume: loop_off must be [L+1] with L <= {GRASP_VOLUME_MAX_LOOPS} and loop_vert 1-D")
+    _mesh_tables(what, mesh_verts, vert_off, mesh_faces, face_off)
+    _obj_of_row(what, obj_of_row, B)
+    _frame(what, R, t, B)
+    res = _positive(what, "res", res)
+    dev = _require_gpu(hand, faces, loop_off, loop_vert, mesh_verts, vert_off, mesh_faces, face_off, obj_of_row, R, t, err)
+    lib = _lib.load()
+    outs = _outputs(B, dev, (_I,), (_I,))                                              # count, status
+    message = lambda bad: (f"grasp_mesh_volume: object index out of bounds for {vert_off.numel() - 1} objects" if bad & 1 else
+                           "grasp_mesh_volume: an index of the topology, a face index or an object's vertex / face range is out of bounds")
+    with _err_flag(err, dev, message) as flag, torch.cuda.device(dev):
+        check(lib.dvq_grasp_mesh_volume(hand.data_ptr(), V, faces.data_ptr(), faces.shape[0], loop_off.data_ptr(), loop_vert.data_ptr(),
+                                        loop_off.numel() - 1, loop_vert.numel(), mesh_verts.data_ptr(), mesh_verts.shape[0],
+                                        vert_off.data_ptr(), mesh_faces.data_ptr(), mesh_faces.shape[0], face_off.data_ptr(),
+                                        vert_off.numel() - 1, obj_of_row.data_ptr(), _ptr(R), _ptr(t), B, res, *map(_ptr, outs),
+                                        flag.data_ptr(), _stream(dev)), "dvq_grasp_mesh_volume")
+    return outs
+
+
 GRASP_REFINE_MAX_STEPS = 64        # csrc/grasp_refine.hip: GR_MAX_STEPS
 GRASP_FINGERS_MAX_P = 5            # csrc/grasp_refine.hip: GR_MAX_P
 

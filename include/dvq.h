@@ -44,7 +44,8 @@ typedef enum {
  * working, the version stays): dvq_pixelcnn_sample_ctl, dvq_grasp_scores, dvq_segment_topk, dvq_segment_diverse,
  * dvq_grasp_refine, dvq_segment_kmeans, dvq_grasp_wrench, dvq_grasp_volume, dvq_grasp_parts, dvq_grasp_refine_rigid,
  * dvq_grasp_refine_fingers, dvq_grasp_self, dvq_mano_backward_workspace_bytes, dvq_mano_backward, dvq_grasp_ttt,
- * dvq_pixelcnn_beam_workspace_bytes, dvq_pixelcnn_beam, dvq_grasp_mesh, dvq_segment_contact, dvq_mesh_sample, dvq_cloud_fps. */
+ * dvq_pixelcnn_beam_workspace_bytes, dvq_pixelcnn_beam, dvq_grasp_mesh, dvq_segment_contact, dvq_mesh_sample, dvq_cloud_fps,
+ * dvq_grasp_mesh_volume. */
 int dvq_abi_version(void);
 const char* dvq_last_error(void);
 /* number of visible HIP devices, or -1; does not create a context */
@@ -849,6 +850,47 @@ int dvq_grasp_mesh(const float* hand /* [B,V,3] */, int V, const float* mesh_ver
                    float* depth /* [B] */, int32_t* deep_vertex /* [B] */, int32_t* deep_face /* [B] */,
                    int32_t* inside_mask /* [B,W] */, int32_t* status /* [B] */, float* vert_d2 /* [B,V] or NULL */,
                    int32_t* vert_face /* [B,V] or NULL */, int32_t* err_flag, dvq_stream_t stream);
+/* Penetration volume of grasps against the object's MESH: the voxels, on the lattice of dvq_grasp_volume, whose centres lie both
+ * inside the (sealed) hand mesh and inside the closed triangle mesh of the row's object -- an INTEGER per grasp, defined to the bit --
+ * in ONE kernel, one workgroup of 256 threads per grasp.  dvq_grasp_volume counts against the object's convex HULL, which swallows the
+ * hollow of a cup and the hole of a handle; this one sees them.  It is the solid intersection on the object's own lattice: NOT the
+ * reference's metric/intersect.py figure (trimesh's SURFACE voxels of the object inside the hand), and no igl / trimesh output pins
+ * parity.  An open mesh is not refused: its parity, and with it the count, is then undefined.
+ * Inputs: hand, faces, loop_off, loop_vert, R, t, h exactly as dvq_grasp_volume takes them; mesh_verts, vert_off, mesh_faces (indices
+ * LOCAL to the object's vertex range), face_off exactly as dvq_grasp_mesh takes them; obj_of_row int64 [B].
+ * Arithmetic as in dvq_grasp_volume.  Per grasp b, with o = obj_of_row[b] and the faces of o:
+ *   1 - 8. Steps 1 - 8 of dvq_grasp_volume, verbatim: the fan centres, the object frame, the lattice c(i) and the box from the HAND's
+ *      V+L vertices (cells lo .. hi of the three axes), and which voxels of the box are in the hand.
+ *   9'. Voxel (i,j,k) of the box is in the object iff the number of object faces that count for it is odd.  A face (a,b,c) counts iff
+ *      it covers the column (c(i), c(j)) by rules 4 - 6 -- its edges in canonical direction by the lower LOCAL vertex index, a value
+ *      of exactly 0 decided by the edge's side, as dvq_grasp_mesh takes them -- and its crossing height zc of rule 7 exceeds c(k),
+ *      unless az <= c(lo_z), bz <= c(lo_z) and cz <= c(lo_z) all hold: a face wholly at or below the lowest cell centre never counts
+ *      (no crossing of it exceeds a cell centre but for rounding; the rule takes the rounding out, so that such faces can be dropped
+ *      before any column is looked at).  A face wholly above the box still counts: it flips its whole column.
+ *  10'. count = the number of voxels of the box that are in both: an integer, free of any summation order.  No depth is produced: the
+ *      depth against the mesh is dvq_grasp_mesh's figure.
+ *  11'. status, the first that applies: 4 = obj_of_row[b] is outside [0, O) (bit 0 of *err_flag, a device int32 zeroed by the caller),
+ *      or the object's vertex or face range leaves [0, n_mv] / [0, n_mf] or holds more than DVQ_GRASP_MESH_MAX_FACES faces (bit 1):
+ *      count = -1; 3 = a component of hand[b] is not finite: count = -1; 1 = the object has no face: count = 0; 2 = the box is refused
+ *      exactly as dvq_grasp_volume refuses it: count = -1; 1 = no voxel of the box is in the object: count = 0; else 0.
+ * In a row that reaches step 9', a face with an index outside the object's vertex range sets bit 1 of *err_flag and is skipped.  A face
+ * with a NaN coordinate covers nothing, or has a NaN crossing that exceeds no cell centre: that follows from the comparisons.  Bit 1
+ * is also what dvq_grasp_volume sets for the hand's topology (a face index outside [0, V+L), a loop entry outside [0, V), an empty loop).
+ * Object coordinates are arbitrary (1e30, infinities): a face's column range is cut to the box before anything is converted to an
+ * integer, which changes no result -- the bounds test of rule 6 decides.
+ * Only integers and bits are produced, so nothing depends on a reduction order or a schedule, and a grasp's outputs depend on neither B,
+ * nor its row, nor which objects share the call.
+ * Outputs: count, status int32 [B].
+ * B >= 0, 1 <= V <= 2048, 0 <= F <= 8192, 0 <= L <= 64, O >= 0, n_loop >= 0, n_mv >= 0, n_mf >= 0, h finite and > 0, t only with R, no
+ * null pointer but R, t and the arrays of an empty pool; anything else is DVQ_EINVAL, nothing launched.  (B = 0 returns DVQ_OK before
+ * any pointer is looked at.) */
+int dvq_grasp_mesh_volume(const float* hand /* [B,V,3] */, int V, const int32_t* faces /* [F,3] */, int F,
+                          const int32_t* loop_off /* [L+1] */, const int32_t* loop_vert, int L, int n_loop,
+                          const float* mesh_verts /* [n_mv,3] */, int n_mv, const int32_t* vert_off /* [O+1] */,
+                          const int32_t* mesh_faces /* [n_mf,3] local indices */, int n_mf, const int32_t* face_off /* [O+1] */,
+                          int64_t O, const int64_t* obj_of_row /* [B] */, const float* R /* [B,3,3] or NULL */,
+                          const float* t /* [3] or NULL */, int64_t B, float h, int32_t* count /* [B] */, int32_t* status /* [B] */,
+                          int32_t* err_flag, dvq_stream_t stream);
 /* Per-object selection: cls, key [O*M] (candidate c of object o at o * M + c) -> sel [O,keep]: the candidate indices (0 .. M-1) of
  * each object's keep best candidates, best first.  Candidate a ranks before b iff (cls, key, index) is smaller: cls as signed
  * integers; within a class a NaN key sorts after every number and -0.0 == +0.0; the index breaks every tie.  One workgroup per
