@@ -157,6 +157,9 @@ SIGNATURES = {
                                            c_f32p, c_i32p, c_i32p, c_f32p, c_i32p, c_i32p, c_stream]),
     "dvq_grasp_wrench": (C.c_int, [c_f32p, c_i32p, c_i32p, c_i32p, C.c_int, c_f32p, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
                                    C.c_int, C.c_float, C.c_float, c_f32p, c_i32p, c_i32p, c_f32p, c_f32p, c_f32p, c_stream]),
+    "dvq_grasp_closure": (C.c_int, [c_f32p, c_i32p, c_i32p, c_i32p, C.c_int, c_f32p, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
+                                    C.c_int, C.c_float, C.c_float, C.c_float, c_f32p, C.c_int, c_f32p, c_i32p, c_i32p, c_i32p, c_f32p,
+                                    c_f32p, c_stream]),
     "dvq_grasp_parts": (C.c_int, [c_f32p, c_i32p, C.c_int, C.c_int, c_f32p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int,
                                   C.c_float, c_f32p, c_i32p, c_i32p, c_i32p, c_f32p, c_i32p, c_stream]),
     "dvq_grasp_self": (C.c_int, [c_f32p, c_i32p, c_i32p, c_i32p, C.c_int, c_i32p, c_i32p, C.c_int, C.c_void_p, C.c_int64, C.c_float,

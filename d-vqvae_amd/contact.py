@@ -452,6 +452,120 @@ def wrench_stats(sums, n_contact):
     return {"force_residual": force, "torque_residual": torque, "min_sv": min_sv}
 
 
+CLOSURE_BASES = (2, 3, 5, 7, 11, 13)   # the Halton bases of closure_directions, one per wrench component
+CLOSURE_OUTPUTS = ("quality", "worst_dir", "status", "n_contact", "centre")
+
+
+def _radical_inverse(i, b):
+    f, r = 1.0, 0.0
+    while i > 0:
+        f /= b
+        r += f * (i % b)
+        i //= b
+    return r
+
+
+class _ClosureTable(_DeviceTables):
+    """The direction table of ``closure_directions`` for one D, made once; its device copies are cached as every table's are."""
+    _tables = ("dirs",)
+
+    def __init__(self, D):
+        rows = [[(1.0 if s == 0 else -1.0) if c == a else 0.0 for c in range(6)] for a in range(6) for s in range(2)]
+        i = 0
+        while len(rows) < D:
+            i += 1
+            x = [2.0 * _radical_inverse(i, b) - 1.0 for b in CLOSURE_BASES]
+            q = 0.0
+            for v in x:
+                q += v * v
+            if 0.01 <= q <= 1.0:
+                n = math.sqrt(q)
+                u = [v / n for v in x]
+                rows += [u, [-v for v in u]]
+        self.dirs = np.asarray(rows[:D], dtype=np.float64).astype(np.float32)
+        self.shown = self.dirs.view()                                  # what callers get: read-only
+        self.shown.setflags(write=False)
+        self._start_cache(None)
+
+
+_CLOSURE_TABLES = {}
+
+
+def _closure_table(D):
+    D = int(D)
+    if not 1 <= D <= ops.GRASP_CLOSURE_MAX_DIRS:
+        raise RuntimeError(f"closure_directions: need 1 <= D <= {ops.GRASP_CLOSURE_MAX_DIRS} (got {D})")
+    if D not in _CLOSURE_TABLES:
+        _CLOSURE_TABLES[D] = _ClosureTable(D)
+    return _CLOSURE_TABLES[D]
+
+
+def closure_directions(D):
+    """The [D,6] float32 table of unit directions in wrench space that ``grasp_closure`` samples, deterministic and without a random
+    generator: rows 0 .. 11 are +e_0, -e_0, +e_1, ..., -e_5; the rest come from the Halton points i = 1, 2, ... in the bases (2, 3, 5,
+    7, 11, 13): x = 2 h - 1 in float64, accepted iff 0.01 <= |x|^2 <= 1 (|x|^2 summed left to right), u = x / sqrt(|x|^2), and u, then
+    -u, are appended; the table is cut at D (an odd D cuts a pair).  The radical inverse is the plain float64 loop ``f /= b; r += f *
+    (i % b); i //= b``.  A read-only numpy array, made once per D; the device copies are cached per (D, device)."""
+    return _closure_table(D).shown
+
+
+def grasp_closure(topology, hand_xyz, obj_xyz, length=0.1, friction=0.5, dirs=256, threshold=0.02 ** 2, want_support=False):
+    """Force-closure quality with Coulomb friction from ONE fused kernel (ops.grasp_closure; the definition is in include/dvq.h under
+    dvq_grasp_closure): every object point within the contact threshold of the hand is a point contact with the normal of its nearest
+    hand vertex and the friction coefficient ``friction``; torques are taken about the cloud's centre with the arm divided by
+    ``length``.  Per grasp ``quality`` [B] is the smallest value, over the ``dirs`` directions of ``closure_directions`` (an int D, or
+    a [D,6] fp32 tensor of the caller's own on the device), of the support function of the contacts' friction cones: an UPPER BOUND of
+    the L1 Ferrari-Canny quality, so ``quality <= 0`` certifies that the grasp is NOT in force closure, and a positive value certifies
+    nothing.  Also ``worst_dir`` [B] (the lowest direction that attains it, -1 without a figure), ``status`` [B] (0; 1 = no contact:
+    quality -inf; 2 = a coordinate is not finite: quality NaN), ``n_contact`` [B] (the bits of ``grasp_scores``), ``centre`` [B,3] (the
+    bits of ``grasp_stability``) and with ``want_support`` ``support`` [B,D].
+
+    No physics run and no soft contact; ``friction`` and ``length`` are UNTUNED; contacts are cloud points within ``threshold`` (a
+    squared distance, the scores' 2 cm), penetrating ones included; the effect on real grasps is NOT measured."""
+    length = ops._positive("grasp_closure", "length", length)
+    friction = ops._non_negative("grasp_closure", "friction", friction)
+    if not torch.is_tensor(dirs):
+        table = _closure_table(dirs)
+        if not torch.is_tensor(hand_xyz):
+            raise RuntimeError("grasp_closure: hand_xyz must be a tensor")
+        dirs = table.on(hand_xyz.device) if hand_xyz.is_cuda else torch.from_numpy(table.dirs)
+    out = ops.grasp_closure(hand_xyz.contiguous(), topology.faces, topology.vf_off, topology.vf_face, obj_xyz, 1.0 / length, friction,
+                            dirs, threshold, want_support)
+    res = dict(zip(CLOSURE_OUTPUTS, out[:5]))
+    if want_support:
+        res["support"] = out[5]
+    return res
+
+
+def closure_stats(quality, worst_dir, status):
+    """Host side, float64, row by row, from ``grasp_closure``'s outputs (tensors or arrays): ``closure_quality`` (the quality; ``None``
+    where status != 0 or the value is not finite: json writes null), ``force_closure`` (quality > 0 -- False certifies that the grasp
+    is not in force closure, True only says that no sampled direction refutes it -- or ``None``) and ``closure_direction`` (the row of
+    ``closure_directions`` that attains the quality, or ``None``).  Three lists."""
+    q = _host(quality, np.float64).reshape(-1)
+    k = _host(worst_dir, np.int64).reshape(-1)
+    st = _host(status, np.int64).reshape(-1)
+    if not q.shape[0] == k.shape[0] == st.shape[0]:
+        raise RuntimeError("closure_stats: one worst_dir and one status per quality")
+    has = [int(s) == 0 and math.isfinite(x) for x, s in zip(q, st)]
+    return {"closure_quality": [float(x) if ok else None for x, ok in zip(q, has)],
+            "force_closure": [bool(x > 0.0) if ok else None for x, ok in zip(q, has)],
+            "closure_direction": [int(d) if ok else None for d, ok in zip(k, has)]}
+
+
+def closure_class(out, min_closure):
+    """int32 [B] on the device for ``torch.maximum`` with the class of ``select_keys``: 2 where the row of ``grasp_closure``'s output
+    has no figure because a coordinate is not finite (status 2), else 1 where the hand touches nothing (status 1) or the quality is
+    below ``min_closure``, else 0.  One fp32 comparison per row, ``quality < fp32(min_closure)``: no sum, so nothing depends on which
+    rows share the call."""
+    quality, status = out["quality"], out["status"]
+    limit = float(min_closure)
+    if math.isnan(limit):
+        raise RuntimeError("closure_class: min_closure is NaN")
+    below = quality < torch.tensor(limit, dtype=torch.float64, device=quality.device).to(torch.float32)
+    return _guard_class(status == 2, below | (status == 1))
+
+
 def hull_planes(points_xyz):
     """[N,3] cloud -> fp32 [P,4] rows (n, d), |n| = 1, with n.x <= d for every x inside the cloud's convex hull: the unique rows of
     ``scipy.spatial.ConvexHull(points).equations`` (float64; qhull lists a plane once per triangle of a facet), normalised, in

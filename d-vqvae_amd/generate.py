@@ -119,6 +119,20 @@ def build_parser(dataset: str) -> argparse.ArgumentParser:
                         "the guard against hands that wrap the object by sinking into it (default: no limit)")
     p.add_argument("--torque_length", type=float, default=0.1,
                    help="--stability / --select_by stability: the length in metres that scales torques to forces (hand-sized default, untuned)")
+    p.add_argument("--closure", type=int, default=0,
+                   help="1: every grasp's JSON gains \"closure_quality\", \"force_closure\" and \"closure_direction\": the force-closure "
+                        "quality with Coulomb friction of the hands written (one kernel per call) -- the smallest value, over "
+                        "--closure_dirs sampled directions in wrench space, of the support function of the contacts' friction cones: an "
+                        "upper bound of the L1 Ferrari-Canny quality, so a value <= 0 certifies NO force closure and a positive one "
+                        "certifies nothing -- and the run writes closure.json; torques are scaled by --torque_length; null where the hand "
+                        "touches nothing; no physics run, no soft contact, untuned constants, effect on real grasps not measured")
+    p.add_argument("--friction", type=float, default=0.5, help="--closure / --min_closure: the Coulomb friction coefficient (untuned)")
+    p.add_argument("--closure_dirs", type=int, default=256,
+                   help=f"--closure / --min_closure: the number of sampled directions, 12..{ops.GRASP_CLOSURE_MAX_DIRS} (the signed axes, then "
+                        "Halton points on the sphere in pairs u, -u)")
+    p.add_argument("--min_closure", type=float, default=float("-inf"),
+                   help="best-of-M: candidates whose closure quality is below this rank after all others that touch the object (the class "
+                        "--max_penetration uses), whatever --select_by ranks by; needs --candidates (default: no guard)")
     p.add_argument("--volume", type=int, default=0,
                    help="1: every grasp's JSON gains \"penetration_volume\" (cm^3), \"penetration_depth\" (cm) and \"volume_voxels\": the "
                         "voxels shared by the sealed hand mesh and the convex hull of the object's cloud, counted on the device (one "
@@ -463,7 +477,7 @@ def plan_calls(point_counts: Sequence[int], num_grasp: int, rows_per_call: int) 
 class _Options:
     """What generate_for_objects has validated, the same for every call of it: its keywords under their own names, filled by name, and
     five derived fields (_generate_objects): ``stability`` is also on with ``select_by="stability"``, ``figures`` holds the active
-    per-row figures with their settings -- (_Figure, dict) pairs in the order of FIGURES -- ``ttt`` the settings of
+    per-row figures with their settings -- (_Figure, dict) pairs in the order of FIGURES, then those of EXTRA_FIGURES -- ``ttt`` the settings of
     contact.refine_ttt, or None, ``beam`` (poses, width) of a beam search, or None, and ``object_contact`` the threshold in metres of
     the object-side contact map, or None without it."""
     num_grasp: int
@@ -532,7 +546,7 @@ def _generate_call(net: GenNet, opt: _Options, objs: Sequence[torch.Tensor], obj
     3. ``refine_steps``: the push-out of every row (contact.refine_translation; with ``refine_spin`` contact.refine_rigid about the root
        joint of the first pass; with ``refine_curl`` _refine_fingers_call) into the parameters, and MANO posed again;
     4. ``ttt``: contact.refine_ttt on every row, and MANO posed again -- everything below sees the hands of the parameters written;
-    5. every active figure's ONE launch over all rows (_Figure.launch, in the order of FIGURES);
+    5. every active figure's ONE launch over all rows (_Figure.launch, in the order of FIGURES, then EXTRA_FIGURES);
     6. with ``candidates``: _select_call.  Otherwise the scores where a push-out or ``stability`` asks for them (contact.grasp_stability
        in the place of contact.grasp_scores; neither where the articulated push-out's guard has scored the rows), the k-means of
        ``diversity`` (_diversity_launch), the object-side contact map of ``object_contact`` over all rows (_object_contact_launch),
@@ -1028,6 +1042,56 @@ class _Mesh(_Figure):
 
 FIGURES = (_Volume, _Parts, _Self, _Mesh)                                        # the order of launches, dict keys, JSON fields and summaries
 
+CLOSURE_PIECES = ("quality", "worst_dir", "status")  # what a call's closure kernel leaves on the device (contact.grasp_closure)
+
+
+class _Closure(_Figure):
+    """``--closure`` / ``--min_closure`` (settings ``friction``, ``dirs``, ``min_closure``, ``length``): ONE ``contact.grasp_closure``
+    over all rows of the call, the hands against their clouds at the scores' contact threshold and the stability proxy's torque length.
+    A quality below ``min_closure`` joins class 1, and so does a hand that touches nothing; a row with a coordinate that is not finite
+    joins class 2 (contact.closure_class).  The JSON fields are closure_quality, force_closure and closure_direction
+    (contact.closure_stats; null where a row has no figure).  A figure like the four of FIGURES, but not one of them and not in GROUPS:
+    its options are no keywords of generate_for_objects (they are generate_with_closure's), so _generate_objects appends it to the
+    active figures, after the four, and ``main`` asks it by name."""
+    key, scores_key, stem, pieces = "closure", "closure_scores", "closure", CLOSURE_PIECES
+    switch, limits, keywords, faces = "closure", ("min_closure",), ("friction", "closure_dirs", "min_closure"), True
+
+    @staticmethod
+    def limited(o):
+        return o.min_closure > -math.inf
+
+    @staticmethod
+    def settings(o, net):
+        return dict(friction=float(o.friction), dirs=int(o.closure_dirs), min_closure=float(o.min_closure), length=float(o.torque_length))
+
+    @staticmethod
+    def launch(s, call):
+        topo = _hand_topology(call.net, call.vertices.shape[1], call.vertices.device)
+        return contact.grasp_closure(topo, call.vertices, call.cloud_xyz, s["length"], s["friction"], s["dirs"])
+
+    @staticmethod
+    def guard(s, dev):
+        return contact.closure_class(dev, s["min_closure"]) if s["min_closure"] > -math.inf else None
+
+    @staticmethod
+    def lists(s, host):
+        return contact.closure_stats(*host)
+
+    @staticmethod
+    def rows(j):                                                                   # (quality, force closure) per grasp
+        return list(zip(j["closure_quality"], j["force_closure"]))
+
+    @staticmethod
+    def summary(args, net, rows):
+        rows = [r for obj in rows for r in obj if r[0] is not None]
+        stat = {"friction": args.friction, "dirs": args.closure_dirs, "torque_length": args.torque_length, "grasps": len(rows),
+                "closure_ratio": _share([r[1] for r in rows]), "mean_quality": _mean([r[0] for r in rows])}
+        return stat, (f"force-closure quality of {len(rows)} grasps at friction {args.friction} over {args.closure_dirs} directions: "
+                      f"share not refuted {stat['closure_ratio']}, mean quality {stat['mean_quality']}")
+
+
+EXTRA_FIGURES = (_Closure,)                                                      # figures outside FIGURES and GROUPS, in the order they follow the four
+
 
 def _diversity_launch(kept: torch.Tensor, O: int, keep: int, clusters: int) -> List[torch.Tensor]:
     """``--diversity``: one ``ops.segment_kmeans`` over the call's kept parameters [O*keep,61], one segment per object, from evenly
@@ -1257,6 +1321,23 @@ VOLUME_MESH_RULES = (
           "needs $volume or $max_volume (it says what the volume figure is counted against)", only="cli"),
 )
 
+# --closure and its three options.  Marked "cli" for the same reason: the keywords are generate_with_closure's, and _generate_objects
+# applies these same six to them.  (The fifth names its second way in without the marker: the options a rule marks are the ones its
+# message shows.)
+CLOSURE_RULES = (
+    _rule("closure", lambda o: o.closure in (0, 1), "is 0 or 1", only="cli"),
+    _rule("friction", lambda o: _not_negative(o.friction), "must be finite and >= 0", only="cli"),
+    _rule("closure_dirs", lambda o: 12 <= o.closure_dirs <= ops.GRASP_CLOSURE_MAX_DIRS,
+          f"must lie between 12 and {ops.GRASP_CLOSURE_MAX_DIRS} (the directions $closure samples: the twelve signed axes first)", only="cli"),
+    _rule("min_closure", lambda o: not math.isnan(o.min_closure), "must not be NaN", only="cli"),
+    _rule("min_closure", lambda o: not _Closure.limited(o) or bool(o.candidates),
+          "needs $candidates (a guard on the ranking of candidates; $closure alone writes the figures)", only="cli"),
+    _rule("closure_dirs friction", lambda o: (o.closure_dirs == 256 and o.friction == 0.5) or _Closure.wanted(o),
+          "away from their defaults need $closure, or a min_closure limit (they are the closure figure's settings)", only="cli"),
+)
+
+_TORQUE_LENGTH_RULE = _rule("torque_length", lambda o: _positive(o.torque_length), "must be finite and positive", "stability")
+
 RULES = (
     _rule("candidates", lambda o: not o.candidates or o.candidates >= max(1, o.num_grasp), "must be 0 or at least $num_grasp"),
     # keywords only, as it has been: ``--candidates 5000`` gets past parse_args and dies in the call; drop the marker to refuse it there
@@ -1283,7 +1364,7 @@ RULES = (
     _rule("ttt_w_pen ttt_w_con", lambda o: _not_negative(o.ttt_w_pen) and _not_negative(o.ttt_w_con), "must be finite and >= 0", "ttt"),
     _rule("ttt_prior", lambda o: o.ttt_prior is None or bool(o.ttt_steps),
           "needs $ttt_steps (it names the contact vertices of the gradient refinement)"),
-    _rule("torque_length", lambda o: _positive(o.torque_length), "must be finite and positive", "stability"),
+    _TORQUE_LENGTH_RULE,
     _rule("max_penetration", lambda o: o.max_penetration >= 0.0, "must be >= 0", "stability"),
     _rule("volume_res", lambda o: _positive(o.volume_res), "must be finite and positive", "volume"),
     _rule("max_volume", lambda o: o.max_volume >= 0.0, "must be >= 0", "volume"),
@@ -1325,6 +1406,7 @@ RULES = (
           "excludes $objects: the clouds come from $object_meshes", only="cli"),
     _rule("mesh_points_even", lambda o: o.mesh_points_even == 1 or bool(o.mesh_points),
           "needs $mesh_points (it thins the cloud sampled from the mesh)", only="cli"),
+    *CLOSURE_RULES,
     *VOLUME_MESH_RULES,
 )
 
@@ -1539,24 +1621,55 @@ def generate_with_volume_mesh(net: GenNet, objs: Sequence[torch.Tensor], num_gra
     return _generate_objects(call.arguments, object_contact_threshold, volume_mesh)
 
 
-def _generate_objects(keywords, object_contact_threshold: Optional[float] = None, volume_mesh: int = 0) -> List[Dict[str, object]]:
+def generate_with_closure(net: GenNet, objs: Sequence[torch.Tensor], num_grasp: int, rotate: bool, seed: int,
+                          object_indices: Sequence[int], friction: float = 0.5, closure_dirs: int = 256, min_closure: float = float("-inf"),
+                          object_contact_threshold: Optional[float] = None, volume_mesh: int = 0, **options) -> List[Dict[str, object]]:
+    """``generate_for_objects(net, objs, num_grasp, rotate, seed, object_indices, **options)`` with the force-closure quality of the
+    grasps WRITTEN: after push-out and gradient refinement every call launches ONE ``contact.grasp_closure`` over all its rows --
+    Coulomb friction ``friction``, ``closure_dirs`` sampled directions (12 .. 1024: ``contact.closure_directions``), the torque length
+    of ``options["torque_length"]`` and the scores' 2 cm contact threshold.  ``min_closure`` above -inf (needs ``candidates``):
+    candidates whose quality is below it, or that touch nothing, join class 1 and rows with a coordinate that is not finite class 2
+    (``contact.closure_class``), whatever ``select_by`` ranks by: a guard only, nothing is ranked by it.  Each dict gains ``closure``
+    (quality, worst_dir, status of its grasps; with ``candidates`` also ``closure_scores``, those of ALL candidates) and ``json`` gains
+    "closure_quality", "force_closure" and "closure_direction" per grasp (``contact.closure_stats``, float64 on the host; null without
+    a figure), after the fields of the other figures.  They ride in the call's one device-to-host copy and do not depend on
+    ``rows_per_call``; everything else is what ``generate_for_objects`` returns, bit for bit.  ``object_contact_threshold`` and
+    ``volume_mesh``: as ``generate_with_object_contact`` and ``generate_with_volume_mesh`` take them (None / 0: off).  The quality is
+    an upper bound of the L1 Ferrari-Canny figure over the sampled directions: <= 0 certifies no force closure, > 0 certifies nothing;
+    no physics run, untuned constants, effect on real grasps not measured.  (A function of its own: the keywords of
+    ``generate_for_objects`` are pinned.)"""
+    call = inspect.signature(generate_for_objects).bind(net, objs, num_grasp, rotate, seed, object_indices, **options)
+    call.apply_defaults()
+    return _generate_objects(call.arguments, object_contact_threshold, volume_mesh,
+                             dict(closure=1, friction=friction, closure_dirs=closure_dirs, min_closure=min_closure))
+
+
+CLOSURE_OFF = dict(closure=0, friction=0.5, closure_dirs=256, min_closure=-math.inf)   # the flags' defaults
+
+
+def _generate_objects(keywords, object_contact_threshold: Optional[float] = None, volume_mesh: int = 0,
+                      closure: Optional[Dict[str, object]] = None) -> List[Dict[str, object]]:
     """The body of ``generate_for_objects`` -- ``keywords`` are its bound arguments by name -- of ``generate_with_object_contact``,
-    which adds the threshold, and of ``generate_with_volume_mesh``, which adds its option.  Every value check (RULES) comes first and
-    sees no more than the values; then the face list, the tables and the files the groups' settings need; then one _Options for all
-    the calls."""
+    which adds the threshold, of ``generate_with_volume_mesh``, which adds its option, and of ``generate_with_closure``, which adds
+    its four (``closure``).  Every value check (RULES) comes first and sees no more than the values; then the face list, the tables and
+    the files the groups' settings need; then one _Options for all the calls."""
     o = types.SimpleNamespace(**keywords, object_contact=object_contact_threshold is not None, object_contact_threshold=object_contact_threshold,
-                              volume_mesh=volume_mesh)
-    rule = _broken_rule(o, cli=False) or next((r for r in VOLUME_MESH_RULES if not r.ok(o)), None)
+                              volume_mesh=volume_mesh, **(closure or CLOSURE_OFF))
+    extra = [fig for fig in EXTRA_FIGURES if fig.wanted(o)]
+    rule = _broken_rule(o, cli=False) or next((r for r in (*CLOSURE_RULES, *VOLUME_MESH_RULES) if not r.ok(o)), None)
+    if rule is None and extra and not _TORQUE_LENGTH_RULE.ok(o):                   # (its gate is the stability proxy's: the closure figure reads it too)
+        rule = _TORQUE_LENGTH_RULE
     if rule is not None:
         raise RuntimeError("generate_for_objects: " + _rule_message(rule, o, cli=False))
     on = {name: group for name, group in GROUPS.items() if group.wanted(o)}
-    if any(group.faces for group in on.values()):
+    if any(group.faces for group in (*on.values(), *extra)):
         _hand_faces(o.net)                                                         # no face list: raise before any work
     settings = {name: group.settings(o, o.net) for name, group in on.items() if group.settings is not None}
     named = {f.name: keywords[f.name] for f in dataclasses.fields(_Options) if f.name in keywords}
     opt = _Options(**{**named, "stability": "stability" in on, "ttt": settings.get("ttt"), "beam": settings.get("beam"),
                       "object_contact": settings.get("object_contact"),
-                      "figures": tuple((fig, settings[fig.key]) for fig in FIGURES if fig.key in on)})
+                      "figures": tuple((fig, settings[fig.key]) for fig in FIGURES if fig.key in on)
+                                 + tuple((fig, fig.settings(o, o.net)) for fig in extra)})
     out: List[Optional[Dict[str, object]]] = [None] * len(o.objs)
     for call in plan_calls([x.shape[1] for x in o.objs], o.candidates or o.num_grasp, o.rows_per_call):
         # the call's objects' meshes, packed and uploaded once per call
@@ -1633,7 +1746,8 @@ def main(dataset: str, argv: Optional[Sequence[str]] = None) -> List[str]:
         raise RuntimeError(f"--diversity: the pooled statistic takes at most {ops.SEGMENT_KMEANS_MAX_M} grasps per rank "
                            f"(got {(hi - lo) * args.num_grasp})")
     on = {name: group for name, group in GROUPS.items() if group.wanted(args)}
-    if args.rows_per_call > 0 or on:
+    extra = [fig for fig in EXTRA_FIGURES if fig.wanted(args)]                     # (no group of GROUPS: their keywords are generate_with_closure's)
+    if args.rows_per_call > 0 or on or extra:
         # grouped calls (with any option group always: --rows_per_call 0 is then one object per call).  A group that is on passes its
         # keywords under the flags' names and forces its switch: --max_volume alone is volume=True
         rows_per_call, per_object = max(1, args.rows_per_call), (args.candidates or args.num_grasp)
@@ -1644,10 +1758,13 @@ def main(dataset: str, argv: Optional[Sequence[str]] = None) -> List[str]:
         generate_call = generate_with_object_contact if "object_contact" in on else generate_for_objects
         if args.volume_mesh:                                                       # (the threshold, when on, is among the flags)
             generate_call, flags["volume_mesh"] = generate_with_volume_mesh, args.volume_mesh
+        if _Closure in extra:                                                      # (it takes the threshold and volume_mesh too)
+            generate_call = generate_with_closure
+            flags.update({k: getattr(args, k) for k in _Closure.keywords}, torque_length=args.torque_length)
         need_meshes = _Mesh.key in on or bool(args.volume_mesh)
         # this rank's objects' meshes, read once
         meshes = [] if not need_meshes else rank_meshes if rank_meshes is not None else [contact.load_mesh(p) for p in args.object_meshes[lo:hi]]
-        active = [fig for fig in FIGURES if fig.key in on]
+        active = [fig for fig in FIGURES if fig.key in on] + extra
         fig_rows: Dict[str, Dict[int, object]] = {fig.key: {} for fig in active}   # every object's _Figure.rows, for the run summaries
         curl_rows: Dict[int, tuple] = {}                                           # --refine_curl: every object's (curled, reverted) counts
         kept: Dict[int, np.ndarray] = {}                                           # --diversity: every object's kept parameters, on the host

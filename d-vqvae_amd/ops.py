@@ -948,6 +948,35 @@ def grasp_wrench(hand: Tensor, faces: Tensor, vf_off: Tensor, vf_face: Tensor, o
     return outs
 
 
+GRASP_CLOSURE_MAX_DIRS = 1024      # include/dvq.h: DVQ_GRASP_CLOSURE_MAX_DIRS (a thread of the workgroup owns at most four directions)
+
+
+def grasp_closure(hand: Tensor, faces: Tensor, vf_off: Tensor, vf_face: Tensor, obj: Tensor, inv_length: float, mu: float, dirs: Tensor,
+                  contact_threshold: float = 0.02 ** 2, want_support: bool = False):
+    """Force-closure quality with friction in one fused kernel (dvq_grasp_closure; the definition is in include/dvq.h):
+    ``(quality [B] f32, worst_dir [B] i32, status [B] i32, n_contact [B] i32, centre [B,3] f32, support)`` -- per grasp the smallest
+    value over ``dirs`` [D,6] (fp32, contiguous, on the device, 1 <= D <= GRASP_CLOSURE_MAX_DIRS) of the support function of the
+    contacts' friction cones at coefficient ``mu`` (finite, >= 0), the lowest direction that attains it, 0 / 1 (no contact) / 2 (a
+    coordinate is not finite), the contact count of ``grasp_scores`` and the centre of ``grasp_wrench``; with ``want_support`` the
+    whole [B,D] support table as well (None otherwise).  Arguments as ``grasp_wrench`` (obj [B,N,3] with any strides, read in place)."""
+    po, ob, op, oc, B, V, N = _hand_cloud_args("grasp_closure", hand, faces, vf_off, vf_face, obj)
+    inv_length = _positive("grasp_closure", "inv_length", inv_length)
+    mu = _non_negative("grasp_closure", "mu", mu)
+    _tensors("grasp_closure", "dirs", dirs)
+    if _f32(dirs, "dirs").dim() != 2 or dirs.shape[1] != 6 or not dirs.is_contiguous() or not 1 <= dirs.shape[0] <= GRASP_CLOSURE_MAX_DIRS:
+        raise RuntimeError(f"grasp_closure: dirs must be contiguous [D,6] with 1 <= D <= {GRASP_CLOSURE_MAX_DIRS} (got {tuple(dirs.shape)})")
+    D = dirs.shape[0]
+    dev = _require_gpu(hand, obj, faces, vf_off, vf_face, dirs)
+    lib = _lib.load()
+    # quality, worst_dir, status, n_contact, centre, support
+    outs = _outputs(B, dev, (_F,), (_I,), (_I,), (_I,), (_F, 3), (_F, D) if want_support else None)
+    with torch.cuda.device(dev):
+        check(lib.dvq_grasp_closure(hand.data_ptr(), faces.data_ptr(), vf_off.data_ptr(), vf_face.data_ptr(), V, po, ob, op, oc, B, N,
+                                    float(contact_threshold), inv_length, mu, dirs.data_ptr(), D, *map(_ptr, outs), _stream(dev)),
+              "dvq_grasp_closure")
+    return outs
+
+
 GRASP_PARTS_TILE = 2048            # csrc/grasp_parts.hip: GP_TILE (the cloud's points per LDS tile)
 GRASP_PARTS_MAX_P = 32             # GP_MAX_P
 

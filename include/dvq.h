@@ -45,7 +45,7 @@ typedef enum {
  * dvq_grasp_refine, dvq_segment_kmeans, dvq_grasp_wrench, dvq_grasp_volume, dvq_grasp_parts, dvq_grasp_refine_rigid,
  * dvq_grasp_refine_fingers, dvq_grasp_self, dvq_mano_backward_workspace_bytes, dvq_mano_backward, dvq_grasp_ttt,
  * dvq_pixelcnn_beam_workspace_bytes, dvq_pixelcnn_beam, dvq_grasp_mesh, dvq_segment_contact, dvq_mesh_sample, dvq_cloud_fps,
- * dvq_grasp_mesh_volume. */
+ * dvq_grasp_mesh_volume, dvq_grasp_closure. */
 int dvq_abi_version(void);
 const char* dvq_last_error(void);
 /* number of visible HIP devices, or -1; does not create a context */
@@ -630,6 +630,47 @@ int dvq_grasp_wrench(const float* hand /* [B,V,3] */, const int32_t* faces, cons
                      int64_t B, int N, float contact_threshold, float inv_length, float* penetration /* [B] */,
                      int32_t* n_interior /* [B] */, int32_t* n_contact /* [B] */, float* centre /* [B,3] */, float* sums /* [B,27] */,
                      float* key /* [B] */, dvq_stream_t stream);
+/* Force-closure quality of grasps with friction: the support function of the contacts' Coulomb friction cones over a table of D
+ * directions in wrench space, its minimum and the direction that attains it, in ONE kernel, one workgroup of 256 threads per grasp.
+ * dvq_grasp_wrench above is frictionless and sums unit forces: it cannot tell a hand that could balance any disturbance from one whose
+ * contacts merely cancel.  The classical answer (Ferrari & Canny, L1 form): take the convex hull of the wrenches that unit normal
+ * forces within every contact's friction cone can exert; the grasp is in force closure iff the origin lies strictly inside, and the
+ * quality eps is the origin's distance to the hull's boundary.  The hull is never built: its support function is h(u) = the largest
+ * w . u over contacts and cone forces, and eps = the minimum of h over unit u in R^6.  For the exact circular cone the inner maximum
+ * has the closed form below, so `quality`, the minimum over the D directions given, is an UPPER BOUND of eps, and quality <= 0
+ * CERTIFIES that the grasp is not in force closure; quality > 0 certifies nothing.  No physics run, no soft contact; mu and the torque
+ * length are untuned; contacts are the cloud points within the threshold of the hand, penetrating ones included; the effect on real
+ * grasps is NOT MEASURED.
+ * Inputs exactly as dvq_grasp_wrench (hand [B,V,3] contiguous, the topology, obj with strides in floats, contact_threshold a squared
+ * distance, inv_length) plus mu, the friction coefficient, dirs [D,6] fp32 on the device (the callers' table holds unit vectors; the
+ * kernel does not look) and D.
+ * Everything is fp32, every operation rounded on its own, fma = the only fused ones; dot(a,b) = fma(a.z,b.z, fma(a.y,b.y, a.x*b.x));
+ * cross(a,b) = (a.y*b.z - a.z*b.y, a.z*b.x - a.x*b.z, a.x*b.y - a.y*b.x), every product rounded, no fma; sqrtf is IEEE.  Per grasp:
+ *   1. centre: step 1 of dvq_grasp_wrench.
+ *   2. per point p: normals, d, j exactly as dvq_grasp_scores defines them; contact = d < contact_threshold, the set n_contact counts.
+ *   3. per contact p: n = n[j]; r = ((obj.x - centre.x) * inv_length, (obj.y - centre.y) * inv_length, (obj.z - centre.z) * inv_length).
+ *   4. per direction k with u = dirs[k], uf = u[0:3], ut = u[3:6], and per contact:
+ *        a = uf + cross(ut, r) per component (so that w . u = f . a for the wrench w = (f, cross(r, f)) of a force f at the contact);
+ *        s = dot(n, a);  c = cross(n, a);  h = fma(mu, sqrtf(dot(c, c)), s)
+ *      -- the largest f . a over the cone f = n + mu t, |t| <= 1, t normal to n (the tangential part of a is taken from the cross
+ *      product, not from |a|^2 - s^2, which cancels).  support[k] = (the largest h over the contacts) + 0.0f: the maximum starts from -inf,
+ *      h > max replaces, so a NaN never does; the addition makes a zero +0.0f, so that the contacts' order reaches no bit.
+ *   5. quality = the smallest support[k]: it starts from +inf and a smaller value replaces; worst_dir = the lowest k with support[k]
+ *      == quality.
+ *   6. status, the first that applies: 2 = a coordinate of the hand or of the cloud is not finite: quality NaN, worst_dir -1, every
+ *      support NaN; 1 = n_contact == 0: quality -inf, worst_dir -1, every support -inf; 0 otherwise.
+ * Only maxima, one minimum and an integer count follow the per-point results -- no float sum over contacts -- so nothing depends on a
+ * reduction order, and a grasp's outputs depend on neither B nor its row.
+ * Outputs: quality fp32 [B]; worst_dir, status int32 [B]; n_contact int32 [B]: the bits of dvq_grasp_scores; centre fp32 [B,3]: the bits
+ * of dvq_grasp_wrench; support fp32 [B,D], which may be NULL (not written).
+ * B >= 0, N >= 1, 1 <= V <= 2048, 1 <= D <= DVQ_GRASP_CLOSURE_MAX_DIRS, mu finite and >= 0, no null pointer but support; anything else
+ * is DVQ_EINVAL, nothing launched. */
+#define DVQ_GRASP_CLOSURE_MAX_DIRS 1024
+int dvq_grasp_closure(const float* hand /* [B,V,3] */, const int32_t* faces, const int32_t* vf_off, const int32_t* vf_face, int V,
+                      const float* obj, int64_t obj_batch_stride, int64_t obj_point_stride, int64_t obj_coord_stride,
+                      int64_t B, int N, float contact_threshold, float inv_length, float mu, const float* dirs /* [D,6] */, int D,
+                      float* quality /* [B] */, int32_t* worst_dir /* [B] */, int32_t* status /* [B] */, int32_t* n_contact /* [B] */,
+                      float* centre /* [B,3] */, float* support /* [B,D] or NULL */, dvq_stream_t stream);
 /* Hand-side contact of grasps: for every hand vertex its nearest object point, and from those which PARTS of the hand touch the
  * object -- per part the smallest squared distance and the number of touching vertices, and a bit per vertex -- in ONE kernel, one
  * workgroup of 256 threads per grasp.  The scores above look from the object's side (how many cloud points lie near the hand); this
